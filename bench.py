@@ -17,6 +17,11 @@ Multi-GPU (weak scaling): every rank denoises its own seed with a full weight re
 path shards over independent forwards only; no data-path collective.  The
 CFG-pair split with an RCCL all-gather of velocities (config 4) is `--shard cfgpair`.
 
+A plain run sets up, warms up, times the K steps and prints the headline line.  `--full` adds everything else the
+benchmark measures: the per-kernel instrumented pass and roofline objects, the text-K/V-cached variant, the CFG-pair
+line (even N) and its one-GPU prediction, the VAE-decode leg and the CPU baseline.  `--dump-outputs DIR` writes the
+latents the last timed step returned to DIR/latents.npy (float32; rank 0's seed).
+
 Prints ONE JSON line on rank 0.
 """
 from __future__ import annotations
@@ -334,7 +339,12 @@ def main() -> None:
     ap.add_argument("--no-vae", action="store_true")
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of the captured step graph")
     ap.add_argument("--cache-context", action="store_true", help="reuse ctx K/V across steps (reported separately)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the secondary measurements (kernel rooflines, cached-context and CFG-pair lines, VAE decode, CPU baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the latents of the last timed step to DIR/latents.npy (float32)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         raise SystemExit(self_launch(args.gpus))
@@ -385,16 +395,28 @@ def main() -> None:
 
     graph_cache = {}
 
-    def run_steps(k: int, start: int = 0, graph: bool = True):
+    def run_steps(k: int, start: int = 0, graph: bool = True, lat=None):
         # k consecutive steps of the 40-step schedule (sigma values only select scalars; cost is step-invariant).
         # The step is replayed from one captured hipGraph (built during warm-up, like the reference's
         # mx.compile'd step_fn, generate.py:1109-1177); every kernel still runs every step.
         s = sig_all[start:start + k + 1].clone()
+        x = latents if lat is None else lat
         if pg_shard is not None:
-            return pg_shard.denoise_dev(latents, positions, ctx_pos, ctx_neg, model, s, cfg_scale=4.0)
-        return denoise_dev(latents, positions, ctx_pos, ctx_neg, model, s, cfg_scale=4.0, compile_step=True,
+            return pg_shard.denoise_dev(x, positions, ctx_pos, ctx_neg, model, s, cfg_scale=4.0)
+        return denoise_dev(x, positions, ctx_pos, ctx_neg, model, s, cfg_scale=4.0, compile_step=True,
                            cfg_batch=True, use_graph=graph and not args.no_graph, graph_cache=graph_cache,
                            cache_context=args.cache_context)
+
+    def run_k(k: int, start: int = 0, graph: bool = True):
+        # exactly k steps: up to 40 as one slice of the schedule; beyond that the schedule is run again from its start,
+        # each pass continuing from the latents the previous one returned
+        if k <= 40:
+            return run_steps(k, start=min(start, 40 - k), graph=graph)
+        x, left = latents, k
+        while left > 0:
+            x = run_steps(min(left, 40), graph=graph, lat=x)
+            left -= 40
+        return x
 
     def barrier():
         if dist is not None:
@@ -402,7 +424,7 @@ def main() -> None:
         torch.cuda.synchronize()
 
     try:
-        run_steps(max(args.warmup, 1) if not args.no_graph else args.warmup)      # W untimed steps (>= 1: builds the step graph)
+        run_k(max(args.warmup, 1) if not args.no_graph else args.warmup)      # W untimed steps (>= 1: builds the step graph)
     except RuntimeError as e:
         # Only a CAPTURE failure may fall back to eager launches (a failed capture must not cost the measurement); a kernel
         # fault also surfaces as RuntimeError and must end the run - a headline from a poisoned context is worthless.
@@ -415,11 +437,11 @@ def main() -> None:
         probe = torch.ones(1024, device=dev)
         if float((probe * 2).sum().item()) != 2048.0:            # the context must still compute (and synchronise) correctly
             raise SystemExit("[bench] GPU context unhealthy after the failed capture")
-        run_steps(args.warmup)
+        run_k(args.warmup)
     # ---- timed region: exactly K steps, barrier + synchronize on both sides, MAX over ranks ----
     barrier()
     t0 = time.perf_counter()
-    out = run_steps(args.steps, start=min(args.warmup, 40 - args.steps))
+    out = run_k(args.steps, start=args.warmup)
     barrier()
     dt = time.perf_counter() - t0
     if not torch.isfinite(out.float()).all():
@@ -428,20 +450,28 @@ def main() -> None:
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives: the latents after the last timed step (fixed seeds: identical
+        # inputs for identical arguments, so two builds compare output for output)
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "latents.npy"), out.float().cpu().numpy())
     # ---- the same K steps again with a HIP event pair around every kernel launch (on the launch stream):
     # per-kernel durations for the roofline object.  ~2000 extra event records per step perturb the
     # step time by a few %, so this pass is reported next to, not as, `value`.
-    ops.TIMER = ops.KernelTimer()
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    run_steps(args.steps, start=min(args.warmup, 40 - args.steps), graph=False)
-    torch.cuda.synchronize()
-    dt_instr = time.perf_counter() - t1
-    timer, ops.TIMER = ops.TIMER, None
+    fams, dt_instr = {}, None
+    if args.full:
+        ops.TIMER = ops.KernelTimer()
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        run_k(args.steps, start=args.warmup, graph=False)
+        torch.cuda.synchronize()
+        dt_instr = time.perf_counter() - t1
+        fams, ops.TIMER = ops.TIMER.summary(), None
     # ---- optional extra: the same steps with the step-invariant caption projection + text-context K/V
     # computed once and reused (an algorithmic change relative to the reference, reported separately) ----
     dt_cached = None
-    if not args.cache_context and pg_shard is None:
+    if args.full and not args.cache_context and pg_shard is None:
         gc2 = {}
         s_c = sig_all[:args.steps + 1].clone()
         kwc = dict(cfg_scale=4.0, compile_step=True, cfg_batch=True, use_graph=True, graph_cache=gc2, cache_context=True)
@@ -456,7 +486,7 @@ def main() -> None:
     # ---- second line of the same run (N even, >= 2): BASELINE config 4's CFG-pair sharding - ranks (2i, 2i+1) denoise
     # seed i, one forward each, RCCL all-gather of the two velocities per step, fused tail on both (sharding.py) ----
     cfgpair = None
-    if dist is not None and world >= 2 and world % 2 == 0 and pg_shard is None and os.environ.get("LTXK_BENCH_CFGPAIR", "1") != "0":
+    if args.full and dist is not None and world >= 2 and world % 2 == 0 and pg_shard is None and os.environ.get("LTXK_BENCH_CFGPAIR", "1") != "0":
         from mlx_video_amd.sharding import CfgPairSharding
         try:
             sh = CfgPairSharding(dist, rank, world)
@@ -486,7 +516,7 @@ def main() -> None:
     # Plus the 2-seed batch (B=4, M=5120: every N=4096 launch then fills whole rounds of 320x256 tiles) as an EXTRA line.
     cfgpair_pred = None
     batch2 = None
-    if world == 1 and args.layers == 48 and os.environ.get("LTXK_BENCH_EXTRAS", "1") != "0":
+    if args.full and world == 1 and args.layers == 48 and os.environ.get("LTXK_BENCH_EXTRAS", "1") != "0":
         try:
             cfgpair_pred = {}
             for n_tok in (1280, 3328):
@@ -501,7 +531,6 @@ def main() -> None:
 
     seeds = world if pg_shard is None else max(world // 2, 1)
     steps_per_s = seeds * args.steps / dt
-    fams = timer.summary()
 
     result = {
         "metric": "denoise steps/sec/GPU + VAE frames/sec, LTX-2 19B 512x512x33 bf16",
@@ -509,7 +538,6 @@ def main() -> None:
         "unit": "denoise steps/s (whole job; one step = 2 CFG forwards + CFG + x0 + Euler)",
         "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": 1000.0 * dt / args.steps,
-        "ms_per_step_instrumented": 1000.0 * dt_instr / args.steps,
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
         "dtype": "bf16", "data": "synthetic (random-init weights of the LTX-2 video DiT, N(0,1) latents/context)",
         "config": {"workload": f"LTX-2 19B dev {args.width}x{args.height}x{args.frames}, CFG 4.0, cfg_batch, "
@@ -563,8 +591,10 @@ def main() -> None:
             result[f"{k}_GBs"] = gbs
     if "gemm_bf16" in rooflines:
         result["roofline"] = rooflines["gemm_bf16"]          # the dominant kernel (85 % of the step)
-    result["roofline_by_family"] = rooflines
-    result["kernel_breakdown_ms_per_step"] = {k: v["ms"] / args.steps for k, v in fams.items()}
+    if args.full:
+        result["ms_per_step_instrumented"] = 1000.0 * dt_instr / args.steps
+        result["roofline_by_family"] = rooflines
+        result["kernel_breakdown_ms_per_step"] = {k: v["ms"] / args.steps for k, v in fams.items()}
     result["kernel_source_sha"] = source_sha()
     if cfgpair is not None:
         result["cfgpair"] = cfgpair
@@ -578,7 +608,7 @@ def main() -> None:
     if batch2 is not None:
         result["two_seed_batch"] = batch2
 
-    if not args.no_vae:
+    if args.full and not args.no_vae:
         try:
             from mlx_video_amd import video_vae
             vres = video_vae.bench_decode(dev, Fl, Hl, Wl)
@@ -600,7 +630,7 @@ def main() -> None:
         except ImportError:
             result["vae_decode_fps"] = None
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         del model
         torch.cuda.empty_cache()
         result["cpu_baseline"] = cpu_baseline_block(min(len(os.sched_getaffinity(0)), 16))

@@ -220,6 +220,7 @@ def timestep_embed(t: torch.Tensor, dim: int = 256, mult: float = 1.0) -> torch.
 
 def rope_table(positions: torch.Tensor, freq: torch.Tensor, H: int, dim: int, max_pos) -> tuple:
     """positions (3,T,2) fp32, freq (n_freq) fp32 -> cos, sin (H,T,dim/2/H) fp32."""
+    _req(positions, torch.float32, "rope_table.positions"); _req(freq, torch.float32, "rope_table.freq")
     T = positions.shape[1]
     per_head = dim // 2 // H
     cos = torch.empty((H, T, per_head), dtype=torch.float32, device=positions.device)
