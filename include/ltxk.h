@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define LTXK_VERSION 400
+#define LTXK_VERSION 401
 
 #define LTXK_OK 0
 #define LTXK_EINVAL (-1)   /* bad argument (shape / alignment / null pointer) */
@@ -37,7 +37,8 @@ extern "C" {
 
 int ltxk_version(void);
 const char* ltxk_last_error(void);
-/* sizeof the argument structs in THIS build: 0 = ltxk_gemm_args, 1 = ltxk_conv3d_args, 2 = ltxk_attn_args; anything else returns -1;
+/* sizeof the argument structs in THIS build: 0 = ltxk_gemm_args, 1 = ltxk_conv3d_args, 2 = ltxk_attn_args,
+ * 3 = struct ltxk_gemm_plan; anything else returns -1;
  * lets a foreign-language binding verify its struct layout before the first call.        */
 int ltxk_abi_sizeof(int which);
 
@@ -92,6 +93,23 @@ typedef struct ltxk_gemm_args {
 } ltxk_gemm_args;
 
 int ltxk_gemm_bf16(const ltxk_gemm_args* args, void* stream);
+
+/* The launch form ltxk_gemm_bf16 takes for `args`, decided without launching anything (host only: pointers are checked for
+ * NULL / alignment, never read).  ltxk_gemm_bf16 decides its form by the same host function, so a plan and a launch of the
+ * same arguments cannot disagree; the same argument checks run and return the same error codes.
+ * Only the split-K form sums a row's products in an order that depends on M (through its slice count): single-pass and
+ * big-tile launches give a row the same bits whatever M is.  A caller that needs bits independent of how many rows share
+ * the launch passes no workspace.                                                                                      */
+enum { LTXK_GEMM_FORM_SINGLE = 0, LTXK_GEMM_FORM_BIG = 1, LTXK_GEMM_FORM_SPLITK = 2 };
+struct ltxk_gemm_plan {   /* a struct tag only: the name is also the function's */
+  int32_t form;                 /* LTXK_GEMM_FORM_*                                                                */
+  int32_t tile_rows, tile_cols; /* workgroup tile                                                                  */
+  int32_t row_tiles, col_tiles; /* tiles over M and over N                                                         */
+  int32_t slices;               /* K slices (1 unless split-K)                                                     */
+  int32_t ksteps;               /* 64-wide K-steps per slice; the last slice may have fewer                        */
+};
+
+int ltxk_gemm_plan(const ltxk_gemm_args* args, struct ltxk_gemm_plan* plan);
 
 /* ---------------------------------------------------------------------------------------
  * Fused attention: replaces mx.fast.scaled_dot_product_attention (attention.py:47) incl. the

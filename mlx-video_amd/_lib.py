@@ -26,6 +26,13 @@ class GemmArgs(Structure):
     ]
 
 
+class GemmPlan(Structure):
+    _fields_ = [
+        ("form", c_int32), ("tile_rows", c_int32), ("tile_cols", c_int32),
+        ("row_tiles", c_int32), ("col_tiles", c_int32), ("slices", c_int32), ("ksteps", c_int32),
+    ]
+
+
 class AttnArgs(Structure):
     _fields_ = [
         ("q", c_void_p), ("k", c_void_p), ("vt", c_void_p), ("out", c_void_p),
@@ -54,6 +61,7 @@ SIGNATURES = {
     "ltxk_last_error": (c_char_p, []),
     "ltxk_abi_sizeof": (c_int32, [c_int32]),
     "ltxk_gemm_bf16": (c_int32, [POINTER(GemmArgs), c_void_p]),
+    "ltxk_gemm_plan": (c_int32, [POINTER(GemmArgs), POINTER(GemmPlan)]),
     "ltxk_flash_attn": (c_int32, [POINTER(AttnArgs), c_void_p]),
     "ltxk_flash_attn_bf16": (c_int32, [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32,
                                        c_int32, c_int32, c_int32, c_int32, c_float, c_void_p]),
@@ -104,6 +112,7 @@ SIGNATURES = {
 _lib = None
 AB_LIB_PATH = os.path.join(_HERE, "libltxk_ab.so")
 ATTN_NO_TAIL_SPLIT = 1        # ltxk.h: LTXK_ATTN_NO_TAIL_SPLIT
+GEMM_FORM_SINGLE, GEMM_FORM_BIG, GEMM_FORM_SPLITK = 0, 1, 2     # ltxk.h: LTXK_GEMM_FORM_*
 
 
 def _open(path: str) -> ctypes.CDLL:
@@ -117,7 +126,7 @@ def _open(path: str) -> ctypes.CDLL:
         fn = getattr(lib, name)  # AttributeError if the .so is stale
         fn.restype = res
         fn.argtypes = args
-    for which, st in enumerate((GemmArgs, Conv3dArgs, AttnArgs)):
+    for which, st in enumerate((GemmArgs, Conv3dArgs, AttnArgs, GemmPlan)):
         if lib.ltxk_abi_sizeof(which) != ctypes.sizeof(st):
             raise LtxkError(f"{path} is stale: sizeof({st.__name__}) is {lib.ltxk_abi_sizeof(which)} in the library, "
                             f"{ctypes.sizeof(st)} in this binding; rebuild it (make -C mlx-video_amd/csrc)")

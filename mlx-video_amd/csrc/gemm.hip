@@ -1087,10 +1087,16 @@ static int big_tile_choice(int M, int N) {
   return 0;
 }
 
-}  // namespace ltxk
+// The launch form of one ltxk_gemm_bf16 call: the argument checks, then big tile / 160-row family (pick_tile) / split-K slices.
+// ltxk_gemm_bf16 launches what this decides and ltxk_gemm_plan reports it, so the two cannot drift apart.
+struct GemmForm {
+  struct ltxk_gemm_plan plan;
+  int tt, nt;        // kernel of the single-pass / split-K forms: 32 x tt rows, 64 x nt columns
+  int rb;            // big tile: rows-per-wave blocks (5: 320 x 256, 4: 256 x 256); 0 otherwise
+  bool split, trans;
+};
 
-extern "C" int ltxk_gemm_bf16(const ltxk_gemm_args* a, void* stream) {
-  using namespace ltxk;
+static int gemm_form(const ltxk_gemm_args* a, GemmForm& f) {
   LTXK_CHECK_ARG(a != nullptr, "ltxk_gemm_bf16: null args");
   LTXK_CHECK_ARG(a->A && a->W && a->out, "ltxk_gemm_bf16: null A/W/out");
   LTXK_CHECK_ARG(a->M > 0 && a->N > 0 && a->K > 0, "ltxk_gemm_bf16: bad dims M=%d N=%d K=%d", a->M, a->N, a->K);
@@ -1099,6 +1105,8 @@ extern "C" int ltxk_gemm_bf16(const ltxk_gemm_args* a, void* stream) {
   LTXK_CHECK_ARG(a->lda >= a->K && a->lda % 8 == 0, "ltxk_gemm_bf16: lda=%d (K=%d) must be >=K, multiple of 8", a->lda, a->K);
   LTXK_CHECK_ARG(((uintptr_t)a->A & 15) == 0 && ((uintptr_t)a->W & 15) == 0 && ((uintptr_t)a->out & 7) == 0,
                  "ltxk_gemm_bf16: A/W must be 16-byte aligned, out 8-byte aligned");
+  // (checked here and not only by the single-pass dispatch: the split-K epilogue launch would run an unknown one as EPI_BIAS)
+  LTXK_CHECK_ARG(a->epilogue >= LTXK_EPI_BIAS && a->epilogue <= LTXK_EPI_SCALE_RES, "ltxk_gemm_bf16: unknown epilogue %d", a->epilogue);
   const bool split = a->n_split > 0;
   const bool trans = a->out_tokens_per_batch > 0 && !split;
   if (split) {
@@ -1125,6 +1133,94 @@ extern "C" int ltxk_gemm_bf16(const ltxk_gemm_args* a, void* stream) {
   if (a->epilogue == LTXK_EPI_BIAS_GATE_RES) {
     LTXK_CHECK_ARG(a->gate != nullptr && a->gate_stride % 4 == 0, "ltxk_gemm_bf16: gate epilogue needs gate");
   }
+  f.split = split;
+  f.trans = trans;
+  struct ltxk_gemm_plan& pl = f.plan;
+  const int nk = a->K / GEMM_BK;
+  const int tt_env = LTXK_AB_INT("LTXK_GEMM_TT", 0);
+  const int nt_env = LTXK_AB_INT("LTXK_GEMM_NT", 0);                  // A/B build: 2 / 4 forces the 128- / 256-column tile
+  const bool nt2_legal = !split || a->n_split % 128 == 0;
+  TileChoice tc = pick_tile(a->M, a->N, nt_env == 2 && nt2_legal ? 2 : (nt_env == 4 || !nt2_legal ? 4 : 0));
+  if (tt_env >= 1 && tt_env <= 5) tc.tt = tt_env;
+  f.tt = tc.tt;
+  f.nt = tc.nt;
+  pl.form = LTXK_GEMM_FORM_SINGLE;
+  pl.tile_rows = 32 * tc.tt;
+  pl.tile_cols = 64 * tc.nt;
+  pl.row_tiles = (a->M + pl.tile_rows - 1) / pl.tile_rows;
+  pl.col_tiles = (a->N + pl.tile_cols - 1) / pl.tile_cols;
+  pl.slices = 1;
+  pl.ksteps = nk;
+  const int big_env = LTXK_AB_INT("LTXK_GEMM_BIG", 1);
+  const bool big_legal = a->N % BIG_BN == 0 && a->K <= (1 << 20) &&
+                         (a->epilogue == LTXK_EPI_BIAS || ((a->epilogue == LTXK_EPI_BIAS_GELU || a->epilogue == LTXK_EPI_BIAS_SILU) && !a->sumsq));
+  // A/B build: LTXK_GEMM_BIG=0 never, 2 / 3 the 320-row / 256-row tile whenever legal (tests compare the tiles bit for bit)
+  f.rb = !big_legal || tt_env != 0 || nt_env != 0 || big_env == 0 ? 0 : (big_env == 2 ? 5 : (big_env == 3 ? 4 : big_tile_choice(a->M, a->N)));
+  if (f.rb) {
+    pl.form = LTXK_GEMM_FORM_BIG;
+    pl.tile_rows = 64 * f.rb;
+    pl.tile_cols = BIG_BN;
+    pl.row_tiles = (a->M + pl.tile_rows - 1) / pl.tile_rows;
+    pl.col_tiles = a->N / BIG_BN;
+    return LTXK_OK;
+  }
+  // Small M: the launch is a weight stream, and a 32..160-row tiling gives it far fewer workgroups than the chip has CUs (M=64,
+  // N=4096: 16 tiles of 256 columns - 16 CUs pulling 32 MB).  Split-K on the 128-column tile: every K slice is a workgroup of its
+  // own that parks its fp32 accumulators in the caller's workspace, and splitk_epilogue_kernel sums the slices in order and
+  // applies the epilogue (deterministic; fp32 sum of slice sums instead of one running sum: another summation order, one rounding).
+  // S depends on M, so the same row sums in another order when it shares the launch with more or fewer rows (ltxk.h).
+  const int ks_env = LTXK_AB_INT("LTXK_GEMM_KSPLIT", 0);             // A/B build: -1 never, n >= 2 forces n slices where legal
+  int S = 0;
+  if (ks_env >= 0 && a->workspace != nullptr && nt2_legal && a->N % 4 == 0 && ((uintptr_t)a->workspace & 15) == 0 &&
+      (a->M <= LTXK_AB_INT("LTXK_GEMM_KSPLIT_MAXM", 640) || ks_env >= 2)) {
+    // the tallest row tile that covers M (every row tile re-streams its W slab), then as many K slices as fill the 256 CUs
+    // (one workgroup each: the deep ring takes most of a CU's LDS) - but never more fp32 slice traffic (S x M x N x 8 bytes,
+    // written and read back) than the weight panel itself (N x K x 2 bytes), and at least 8 K-steps per slice
+    const int tt2 = a->M >= 160 ? 5 : (a->M + 31) / 32;
+    const long tiles = ((long)(a->M + 32 * tt2 - 1) / (32 * tt2)) * ((a->N + 127) / 128);
+    const long have = (long)pl.row_tiles * pl.col_tiles;
+    if (ks_env >= 2) S = ks_env;
+    else if (tiles <= 160 && have <= 240 && (long)a->N * a->K >= (1L << 21)) {     // a real weight stream (>= 4 MB) the tiling cannot spread well (have: its workgroups unsplit - up to 240 small LDS-bound tiles, M=640 FF2)
+      S = (int)((256 + tiles / 2) / tiles);
+      const int cap = a->K / (4 * a->M);
+      if (S > cap) S = cap;
+    }
+    if (S > nk / 8 && ks_env < 2) S = nk / 8;
+    if (S > nk) S = nk;
+    const long per = (long)a->M * a->N * 4;
+    if (S > 1 && (long)S * per > a->workspace_bytes) S = (int)(a->workspace_bytes / per);
+    if (S >= 2) {
+      f.tt = tt2;
+      f.nt = 2;
+      pl.form = LTXK_GEMM_FORM_SPLITK;
+      pl.tile_rows = 32 * tt2;
+      pl.tile_cols = 128;
+      pl.row_tiles = (a->M + pl.tile_rows - 1) / pl.tile_rows;
+      pl.col_tiles = (a->N + 127) / 128;
+      pl.ksteps = (nk + S - 1) / S;
+      pl.slices = (nk + pl.ksteps - 1) / pl.ksteps;                    // no empty slice
+    }
+  }
+  return LTXK_OK;
+}
+
+}  // namespace ltxk
+
+extern "C" int ltxk_gemm_plan(const ltxk_gemm_args* a, struct ltxk_gemm_plan* plan) {
+  using namespace ltxk;
+  LTXK_CHECK_ARG(plan != nullptr, "ltxk_gemm_plan: null plan");
+  GemmForm f;
+  const int rc = gemm_form(a, f);
+  if (rc == LTXK_OK) *plan = f.plan;
+  return rc;
+}
+
+extern "C" int ltxk_gemm_bf16(const ltxk_gemm_args* a, void* stream) {
+  using namespace ltxk;
+  GemmForm f;
+  const int rc = gemm_form(a, f);
+  if (rc != LTXK_OK) return rc;
+  const bool split = f.split, trans = f.trans;
   GemmParams p;
   p.A = (const bf16*)a->A; p.W = (const bf16*)a->W; p.bias = (const bf16*)a->bias;
   p.out = (bf16*)a->out; p.resid = (const bf16*)a->resid; p.gate = (const bf16*)a->gate;
@@ -1137,26 +1233,13 @@ extern "C" int ltxk_gemm_bf16(const ltxk_gemm_args* a, void* stream) {
   // not for the GELU epilogue: its direct stores already issue under the activation arithmetic, and staging
   // them behind it measured 2 % slower on FF1
   p.wide = (!trans && wide_env && a->epilogue != LTXK_EPI_BIAS_GELU && a->ldo % 8 == 0 && ((uintptr_t)a->out & 15) == 0) ? 1 : 0;
-  const int tt_env = LTXK_AB_INT("LTXK_GEMM_TT", 0);
-  const int nt_env = LTXK_AB_INT("LTXK_GEMM_NT", 0);                  // A/B build: 2 / 4 forces the 128- / 256-column tile
-  const bool nt2_legal = !split || a->n_split % 128 == 0;
-  TileChoice tc = pick_tile(a->M, a->N, nt_env == 2 && nt2_legal ? 2 : (nt_env == 4 || !nt2_legal ? 4 : 0));
-  if (tt_env >= 1 && tt_env <= 5) tc.tt = tt_env;
-  const int tt = tc.tt;
-  const int bm = 32 * tt;
-  p.RT = (a->M + bm - 1) / bm;
-  p.CT = (a->N + 64 * tc.nt - 1) / (64 * tc.nt);
-  p.part = nullptr; p.ksteps = a->K / GEMM_BK;
+  p.RT = f.plan.row_tiles;
+  p.CT = f.plan.col_tiles;
+  p.part = nullptr;
+  p.ksteps = f.plan.ksteps;
   hipStream_t st = (hipStream_t)stream;
-  const int big_env = LTXK_AB_INT("LTXK_GEMM_BIG", 1);
-  const bool big_legal = a->N % BIG_BN == 0 && a->K <= (1 << 20) &&
-                         (a->epilogue == LTXK_EPI_BIAS || ((a->epilogue == LTXK_EPI_BIAS_GELU || a->epilogue == LTXK_EPI_BIAS_SILU) && !a->sumsq));
-  // A/B build: LTXK_GEMM_BIG=0 never, 2 / 3 the 320-row / 256-row tile whenever legal (tests compare the tiles bit for bit)
-  const int rb = !big_legal || tt_env != 0 || nt_env != 0 || big_env == 0 ? 0 : (big_env == 2 ? 5 : (big_env == 3 ? 4 : big_tile_choice(a->M, a->N)));
-  if (rb) {
-    const int bm = 64 * rb;
-    p.RT = (a->M + bm - 1) / bm;
-    p.CT = a->N / BIG_BN;
+  if (f.plan.form == LTXK_GEMM_FORM_BIG) {
+    const int rb = f.rb;
     if (split) return launch_big<LTXK_EPI_BIAS, 2>(p, st, rb);
     if (trans) return launch_big<LTXK_EPI_BIAS, 1>(p, st, rb);
     switch (a->epilogue) {
@@ -1165,46 +1248,14 @@ extern "C" int ltxk_gemm_bf16(const ltxk_gemm_args* a, void* stream) {
       default: return launch_big<LTXK_EPI_BIAS_SILU, 0>(p, st, rb);
     }
   }
-  // Small M: the launch is a weight stream, and a 32..160-row tiling gives it far fewer workgroups than the chip has CUs (M=64,
-  // N=4096: 16 tiles of 256 columns - 16 CUs pulling 32 MB).  Split-K on the 128-column tile: every K slice is a workgroup of its
-  // own that parks its fp32 accumulators in the caller's workspace, and splitk_epilogue_kernel sums the slices in order and
-  // applies the epilogue (deterministic; fp32 sum of slice sums instead of one running sum: another summation order, one rounding).
-  {
-    const int ks_env = LTXK_AB_INT("LTXK_GEMM_KSPLIT", 0);           // A/B build: -1 never, n >= 2 forces n slices where legal
-    const int nk = a->K / GEMM_BK;
-    int S = 0;
-    if (ks_env >= 0 && rb == 0 && a->workspace != nullptr && nt2_legal && a->N % 4 == 0 && ((uintptr_t)a->workspace & 15) == 0 &&
-        (a->M <= LTXK_AB_INT("LTXK_GEMM_KSPLIT_MAXM", 640) || ks_env >= 2)) {
-      // the tallest row tile that covers M (every row tile re-streams its W slab), then as many K slices as fill the 256 CUs
-      // (one workgroup each: the deep ring takes most of a CU's LDS) - but never more fp32 slice traffic (S x M x N x 8 bytes,
-      // written and read back) than the weight panel itself (N x K x 2 bytes), and at least 8 K-steps per slice
-      const int tt2 = a->M >= 160 ? 5 : (a->M + 31) / 32;
-      const long tiles = ((long)(a->M + 32 * tt2 - 1) / (32 * tt2)) * ((a->N + 127) / 128);
-      const long have = ((long)p.RT * p.CT);
-      if (ks_env >= 2) S = ks_env;
-      else if (tiles <= 160 && have <= 240 && (long)a->N * a->K >= (1L << 21)) {     // a real weight stream (>= 4 MB) the tiling cannot spread well (have: its workgroups unsplit - up to 240 small LDS-bound tiles, M=640 FF2)
-        S = (int)((256 + tiles / 2) / tiles);
-        const int cap = a->K / (4 * a->M);
-        if (S > cap) S = cap;
-      }
-      if (S > nk / 8 && ks_env < 2) S = nk / 8;
-      if (S > nk) S = nk;
-      const long per = (long)a->M * a->N * 4;
-      if (S > 1 && (long)S * per > a->workspace_bytes) S = (int)(a->workspace_bytes / per);
-      if (S >= 2) {
-        p.RT = (a->M + 32 * tt2 - 1) / (32 * tt2);
-        p.CT = (a->N + 127) / 128;
-        p.ksteps = (nk + S - 1) / S;
-        S = (nk + p.ksteps - 1) / p.ksteps;                            // no empty slice
-        p.part = (float*)a->workspace;
-        const int rc = launch_partial(p, tt2, S, st);
-        if (rc != LTXK_OK) return rc;
-        const long threads = (long)a->M * (a->N / 4);
-        hipLaunchKernelGGL(splitk_epilogue_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, p, S, a->epilogue, trans ? 1 : 0);
-        LTXK_CHECK_LAUNCH("ltxk_gemm_bf16 (split-K epilogue)");
-        return LTXK_OK;
-      }
-    }
+  if (f.plan.form == LTXK_GEMM_FORM_SPLITK) {
+    p.part = (float*)a->workspace;
+    const int rc2 = launch_partial(p, f.tt, f.plan.slices, st);
+    if (rc2 != LTXK_OK) return rc2;
+    const long threads = (long)a->M * (a->N / 4);
+    hipLaunchKernelGGL(splitk_epilogue_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, p, f.plan.slices, a->epilogue, trans ? 1 : 0);
+    LTXK_CHECK_LAUNCH("ltxk_gemm_bf16 (split-K epilogue)");
+    return LTXK_OK;
   }
-  return tc.nt == 2 ? dispatch_tt<2>(p, tt, a->epilogue, trans, st) : dispatch_tt<4>(p, tt, a->epilogue, trans, st);
+  return f.nt == 2 ? dispatch_tt<2>(p, f.tt, a->epilogue, trans, st) : dispatch_tt<4>(p, f.tt, a->epilogue, trans, st);
 }

@@ -140,8 +140,14 @@ class LTXModel:
         self.fuse = int(fuse)
         # every token through the token->row map even when all tokens share one timestep row (A/B runs only)
         self.tok2row_always = False
-        # ops.flash_attn(tail_split=): False makes a forward's bits independent of the batch it runs in (B=1 per CFG-pair
-        # rank == row b of the B=2 cfg_batch forward), at ~5 % of attention time at N=1280 (attention.hip)
+        # True makes a forward's bits independent of the batch it runs in (B=1 per CFG-pair rank == row b of the B=2
+        # cfg_batch forward): every ops.gemm single-pass (split_k=False - the split-K slice count depends on M, so at
+        # M <= ops.SPLITK_MAX_M a row sums its products in another order when the launch holds more rows) and every
+        # attention without the tail split.  Costs the split-K weight stream of small-M launches.
+        self.batch_invariant = False
+        # ops.flash_attn(tail_split=) alone (attention only; batch_invariant turns it off too): False makes attention's bits
+        # independent of the batch, at ~5 % of attention time at N=1280 (attention.hip).  The GEMMs of a forward with
+        # M <= ops.SPLITK_MAX_M still depend on it.
         self.attn_tail_split = True
         self._pack(weights)
         # the split-K scratch of ops.gemm (small-M launches) must exist before anyone captures a forward into a hipGraph: allocated
@@ -289,8 +295,9 @@ class LTXModel:
     def _prepare_context(self, context: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """ltx.py:77-89: caption_projection, (B,S,3840) -> (B*S,D)."""
         b, s, c = context.shape
-        h = ops.gemm(context.reshape(b * s, c), self.c1_w, self.c1_b, epilogue=ops.EPI_BIAS_GELU)
-        return ops.gemm(h, self.c2_w, self.c2_b, out=out)
+        sk = not self.batch_invariant
+        h = ops.gemm(context.reshape(b * s, c), self.c1_w, self.c1_b, epilogue=ops.EPI_BIAS_GELU, split_k=sk)
+        return ops.gemm(h, self.c2_w, self.c2_b, out=out, split_k=sk)
 
     def _context_kv(self, blk: _Block, ctx: torch.Tensor, b: int, s: int, sp: int, out: Optional[tuple] = None):
         D, H, eps = self.inner_dim, self.num_attention_heads, self.config.norm_eps
@@ -303,11 +310,12 @@ class LTXModel:
             k2, vt2, ss = out
         # k (row-major, with its per-row sums of squares) and V^T from one launch over the packed k|v panel
         st = ss if self.fuse & 2 else None
+        sk = not self.batch_invariant
         if self.fuse & 1:
-            ops.gemm(ctx, blk.wkv2, blk.bkv2, out=k2, out2=vt2, n_split=D, out_tokens_per_batch=s, sumsq=st)
+            ops.gemm(ctx, blk.wkv2, blk.bkv2, out=k2, out2=vt2, n_split=D, out_tokens_per_batch=s, sumsq=st, split_k=sk)
         else:
-            ops.gemm(ctx, blk.wkv2[:D], blk.bkv2[:D], out=k2, sumsq=st)
-            ops.gemm(ctx, blk.wkv2[D:], blk.bkv2[D:], out=vt2, out_tokens_per_batch=s)
+            ops.gemm(ctx, blk.wkv2[:D], blk.bkv2[:D], out=k2, sumsq=st, split_k=sk)
+            ops.gemm(ctx, blk.wkv2[D:], blk.bkv2[D:], out=vt2, out_tokens_per_batch=s, split_k=sk)
         ops.qknorm_rope(k2, 1, D, blk.wkn2, None, None, s, H, eps, sumsq=st)
         return k2, vt2, ss
 
@@ -355,12 +363,13 @@ class LTXModel:
         # Row statistics travel with the residual stream: every GEMM that writes x also emits the per-row sums of
         # squares of what it stored (64-column partials), so the rms_norm that follows does not re-reduce the row.
         P = D // 64
+        sk = not self.batch_invariant
         xss = torch.empty((M, P), dtype=torch.float32, device=dev)
-        x = ops.gemm(latent.reshape(M, C), self.patchify_w, self.patchify_b, sumsq=xss)
+        x = ops.gemm(latent.reshape(M, C), self.patchify_w, self.patchify_b, sumsq=xss, split_k=sk)
         tproj = ops.timestep_embed(plan.values, 256, float(cfg.timestep_scale_multiplier))
-        h = ops.gemm(tproj, self.t1_w, self.t1_b, epilogue=ops.EPI_BIAS_SILU)
-        emb = ops.gemm(h, self.t2_w, self.t2_b)                           # embedded_timestep (U,D)
-        ada = ops.gemm(ops.silu(emb), self.ada_w, self.ada_b)             # (U,6D)
+        h = ops.gemm(tproj, self.t1_w, self.t1_b, epilogue=ops.EPI_BIAS_SILU, split_k=sk)
+        emb = ops.gemm(h, self.t2_w, self.t2_b, split_k=sk)               # embedded_timestep (U,D)
+        ada = ops.gemm(ops.silu(emb), self.ada_w, self.ada_b, split_k=sk)   # (U,6D)
         # (L,U,6,D): shift, 1+scale, gate, shift, 1+scale, gate - the (1 + scale) factor is the same for every token of a row
         # (without the carried row statistics the self-reducing norm kernel takes the raw scale and adds 1 itself)
         mods = ops.ada_combine(self.tables, ada, cfg.num_layers, U, 6, D, one_plus_mask=0b010010 if self.fuse & 2 else 0)
@@ -399,7 +408,7 @@ class LTXModel:
                       torch.empty((B * S, D // 64), dtype=torch.float32, device=dev))
 
         fq, fs, fp = self.fuse & 1, self.fuse & 2, (self.fuse & 6) == 6
-        ts_ = self.attn_tail_split
+        ts_ = self.attn_tail_split and not self.batch_invariant
         s_x, s_qk, s_q2 = (xss, qkss, q2ss) if fs else (None, None, None)
         for li, blk in enumerate(self.blocks):
             mod = mods[li]                                           # (U,6,D): shift, 1+scale, gate x2
@@ -412,10 +421,10 @@ class LTXModel:
             # with q|k|v as ONE launch (M=1296: 39.4 against 41.2 ms, 3328: 87.6 / 89.2, 5184: 141.5 / 143.8, 6656: 161.5 / 164.7;
             # scripts/exp_qkv_one_launch.py), and at small M every launch is a weight stream with ~5 us of fixed cost)
             if fq and (not (self.fuse & 8) or M <= ops.SPLITK_MAX_M or M % 320 != 0):
-                ops.gemm(nx, blk.wqkv, blk.bqkv, out=qk, out2=vt, n_split=2 * D, out_tokens_per_batch=N, sumsq=s_qk)
+                ops.gemm(nx, blk.wqkv, blk.bqkv, out=qk, out2=vt, n_split=2 * D, out_tokens_per_batch=N, sumsq=s_qk, split_k=sk)
             else:
-                ops.gemm(nx, blk.wqkv[:2 * D], blk.bqkv[:2 * D], out=qk, sumsq=s_qk)
-                ops.gemm(nx, blk.wqkv[2 * D:], blk.bqkv[2 * D:], out=vt, out_tokens_per_batch=N)
+                ops.gemm(nx, blk.wqkv[:2 * D], blk.bqkv[:2 * D], out=qk, sumsq=s_qk, split_k=sk)
+                ops.gemm(nx, blk.wqkv[2 * D:], blk.bqkv[2 * D:], out=vt, out_tokens_per_batch=N, split_k=sk)
             if fp:
                 ops.qknorm_rope(qk[:, D:], 1, D, blk.wkn, cos, sin, N, H, eps, sumsq=qkss[:, P:])
                 ops.flash_attn(qk[:, :D], qk[:, D:], vt, att, B, H, N, N, scale, q_sumsq=qkss, q_norm_weight=blk.wqn,
@@ -424,28 +433,28 @@ class LTXModel:
                 ops.qknorm_rope(qk, 2, D, blk.wqkn, cos, sin, N, H, eps, sumsq=s_qk)
                 ops.flash_attn(qk[:, :D], qk[:, D:], vt, att, B, H, N, N, scale, tail_split=ts_)
             ops.gemm(att, blk.wo, blk.bo, epilogue=ops.EPI_BIAS_GATE_RES, out=x, resid=x,
-                     gate=mod[:, 2], gate_row=tok2row, gate_stride=ms, sumsq=s_x)
+                     gate=mod[:, 2], gate_row=tok2row, gate_stride=ms, sumsq=s_x, split_k=sk)
             # text cross-attention (transformer.py:257-261)
             ops.rmsnorm_modulate(x, eps, out=nx, sumsq=s_x)
-            ops.gemm(nx, blk.wq2, blk.bq2, out=q2, sumsq=s_q2)
+            ops.gemm(nx, blk.wq2, blk.bq2, out=q2, sumsq=s_q2, split_k=sk)
             kv = ctx_kv.kv[li] if ctx_kv is not None else self._context_kv(blk, ctx, B, S, sp64, kv_buf)
             if fp:
                 ops.flash_attn(q2, kv[0], kv[1], att, B, H, N, S, scale, q_sumsq=q2ss, q_norm_weight=blk.wqn2, eps=eps, tail_split=ts_)
             else:
                 ops.qknorm_rope(q2, 1, D, blk.wqn2, None, None, N, H, eps, sumsq=s_q2)
                 ops.flash_attn(q2, kv[0], kv[1], att, B, H, N, S, scale, tail_split=ts_)
-            ops.gemm(att, blk.wo2, blk.bo2, epilogue=ops.EPI_BIAS_RES, out=x, resid=x, sumsq=s_x)
+            ops.gemm(att, blk.wo2, blk.bo2, epilogue=ops.EPI_BIAS_RES, out=x, resid=x, sumsq=s_x, split_k=sk)
             # feed-forward (transformer.py:343-347)
             ops.rmsnorm_modulate(x, eps, mod[:, 4], mod[:, 3], ms, tok2row, out=nx, sumsq=s_x, scale_is_one_plus=bool(fs))
-            ops.gemm(nx, blk.w1, blk.b1, epilogue=ops.EPI_BIAS_GELU, out=hff)
+            ops.gemm(nx, blk.w1, blk.b1, epilogue=ops.EPI_BIAS_GELU, out=hff, split_k=sk)
             ops.gemm(hff, blk.w2, blk.b2, epilogue=ops.EPI_BIAS_GATE_RES, out=x, resid=x,
-                     gate=mod[:, 5], gate_row=tok2row, gate_stride=ms, sumsq=s_x)
+                     gate=mod[:, 5], gate_row=tok2row, gate_stride=ms, sumsq=s_x, split_k=sk)
             if hidden is not None:
                 hidden.append(x.reshape(B, N, D).clone())
 
         # --- output head (ltx.py:432-457) ---
         ops.layernorm_modulate(x, eps, head[:, 1], head[:, 0], 2 * D, tok2row, out=nx)
-        v = ops.gemm(nx, self.out_w, self.out_b)
+        v = ops.gemm(nx, self.out_w, self.out_b, split_k=sk)
         return v.reshape(B, N, cfg.out_channels)
 
     def __call__(self, video: Optional[Modality] = None, audio: Optional[Modality] = None):

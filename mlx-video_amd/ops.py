@@ -4,7 +4,8 @@ on torch's current HIP stream (so a torch.cuda.graph capture records the whole s
 from __future__ import annotations
 
 import ctypes
-from typing import Optional
+from dataclasses import dataclass
+from typing import Optional, Tuple
 
 import torch
 
@@ -84,15 +85,21 @@ def _gemm_workspace(dev: torch.device) -> torch.Tensor:
     return _GEMM_WS[key]
 
 
+def _offers_workspace(M: int, split_k: bool) -> bool:
+    return split_k and M <= SPLITK_MAX_M
+
+
 def gemm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], *, epilogue: int = EPI_BIAS,
          out: Optional[torch.Tensor] = None, resid: Optional[torch.Tensor] = None,
          gate: Optional[torch.Tensor] = None, gate_row: Optional[torch.Tensor] = None,
          gate_stride: int = 0, out_tokens_per_batch: int = 0, alpha: float = 1.0,
-         out2: Optional[torch.Tensor] = None, n_split: int = 0, sumsq: Optional[torch.Tensor] = None) -> torch.Tensor:
+         out2: Optional[torch.Tensor] = None, n_split: int = 0, sumsq: Optional[torch.Tensor] = None,
+         split_k: bool = True) -> torch.Tensor:
     """out = epi(a @ w.T + bias).  a (M,K) (row stride may exceed K), w (N,K) contiguous.
     ``n_split``/``out2``: columns >= n_split go transposed per batch (out_tokens_per_batch tokens) to out2
     (B, N-n_split, ld).  ``sumsq``: (M, >= cols/64) fp32, receives the per-64-column sums of squares of the stored
-    row-major outputs."""
+    row-major outputs.  ``split_k=False``: no split-K scratch is offered, so the launch is single-pass (or big-tile) and
+    a row's bits do not depend on M; with it the library may split K at M <= SPLITK_MAX_M (``gemm_plan`` tells)."""
     _req(a, BF16, "gemm.a"); _req(w, BF16, "gemm.w")
     M, K = a.shape
     N = w.shape[0]
@@ -120,12 +127,63 @@ def gemm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], *, epil
     args.alpha = alpha
     args.out2, args.n_split, args.ldo2 = _p(out2), n_split, (out2.stride(-2) if out2 is not None else 0)
     args.sumsq, args.sumsq_ld = _p(sumsq), (sumsq.stride(0) if sumsq is not None else 0)
-    if M <= SPLITK_MAX_M:
+    if _offers_workspace(M, split_k):
         ws = _gemm_workspace(a.device)
         args.workspace, args.workspace_bytes = ws.data_ptr(), ws.numel() * 4
     with _timed("gemm_bf16", 2.0 * M * N * K, 2.0 * (M * K + N * K + M * N)):
         check(_lib.load().ltxk_gemm_bf16(ctypes.byref(args), _stream()), "ltxk_gemm_bf16")
     return out
+
+
+@dataclass(frozen=True)
+class GemmPlan:
+    """ltxk_gemm_plan: the launch form of one ltxk_gemm_bf16 call (_lib.GEMM_FORM_*), its tile, and its K slices."""
+    form: int
+    tile_rows: int
+    tile_cols: int
+    row_tiles: int
+    col_tiles: int
+    slices: int
+    ksteps: int
+
+    @property
+    def split_k(self) -> bool:
+        return self.form == _lib.GEMM_FORM_SPLITK
+
+
+_PLAN_ADDR = 1 << 12          # stands in for every device pointer of a planned call: non-NULL, aligned, never read
+
+
+def gemm_plan(M: int, N: int, K: int, *, epilogue: int = EPI_BIAS, lda: Optional[int] = None, ldo: Optional[int] = None,
+              out_tokens_per_batch: int = 0, n_split: int = 0, ldo2: Optional[int] = None, sumsq: bool = False,
+              split_k: bool = True, workspace: Optional[Tuple[int, int]] = None) -> GemmPlan:
+    """The form ``gemm`` takes for an (M,K) x (N,K)^T launch with these options, decided on the host by the function the
+    launch itself uses (no device needed).  The split-K scratch is offered exactly as ``gemm`` offers it (``split_k``,
+    SPLITK_MAX_M); ``workspace=(address, bytes)`` offers that one instead (address 0: none).  Strides default to those of
+    contiguous tensors (V^T: tokens padded to 64).  Raises LtxkError where ``gemm`` would refuse the arguments."""
+    args = GemmArgs()
+    args.A = args.W = args.out = _PLAN_ADDR
+    args.M, args.N, args.K = M, N, K
+    args.lda = K if lda is None else lda
+    ld_t = (out_tokens_per_batch + 63) // 64 * 64
+    args.ldo = ldo if ldo is not None else (ld_t if out_tokens_per_batch and not n_split else (n_split or N))
+    if epilogue in (EPI_BIAS_GATE_RES, EPI_BIAS_RES, EPI_SCALE_RES):
+        args.resid, args.ldr = _PLAN_ADDR, N
+    if epilogue == EPI_BIAS_GATE_RES:
+        args.gate = _PLAN_ADDR
+    args.epilogue = epilogue
+    args.out_tokens_per_batch = out_tokens_per_batch
+    if n_split:
+        args.out2, args.n_split, args.ldo2 = _PLAN_ADDR, n_split, (ld_t if ldo2 is None else ldo2)
+    if sumsq:
+        args.sumsq, args.sumsq_ld = _PLAN_ADDR, (n_split or N) // 64
+    if workspace is not None:
+        args.workspace, args.workspace_bytes = workspace
+    elif _offers_workspace(M, split_k):
+        args.workspace, args.workspace_bytes = _PLAN_ADDR, GEMM_WORKSPACE_BYTES
+    pl = _lib.GemmPlan()
+    check(_lib.load().ltxk_gemm_plan(ctypes.byref(args), ctypes.byref(pl)), "ltxk_gemm_plan")
+    return GemmPlan(pl.form, pl.tile_rows, pl.tile_cols, pl.row_tiles, pl.col_tiles, pl.slices, pl.ksteps)
 
 
 def flash_attn(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, out: torch.Tensor, B: int, H: int,

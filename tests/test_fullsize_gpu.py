@@ -122,10 +122,12 @@ def test_vae_fullsize_properties(dev):
     assert torch.equal(dec.decode_tiled(lat, TilingConfig.spatial_only(512, 64)), nc)
     tiled = dec.decode_tiled(lat, TilingConfig.spatial_only(256, 64))
     assert tiled.shape == nc.shape and bool(torch.isfinite(tiled.float()).all())
-    # (iii) batch consistency: decoding two latents together == separately (bit exact)
+    # (iii) batch consistency: decoding two latents together == separately, equal up to split-K grouping (the small-volume
+    # stages' slice count depends on B x voxels), each row checked on its own
     lat2 = torch.cat([lat, lat.flip(2)], 0)
     both = dec(lat2)
-    parity.auto(rel_l2(both[0].float(), nc[0].float()) < 1.5e-2 and rel_l2(both[1].float(), dec(lat.flip(2))[0].float()), 1.5e-2)
+    parity.auto(rel_l2(both[1].float(), dec(lat.flip(2))[0].float()), 1.5e-2)
+    parity.auto(rel_l2(both[0].float(), nc[0].float()), 1.5e-2, tag="batch_row0")
     assert torch.equal(dec(lat2), both)                      # same geometry twice: deterministic (slab split-K, no atomics)
     # (iv) uint8 conversion: monotone, range, layout
     u8 = to_uint8_frames(nc)

@@ -32,7 +32,7 @@ def test_library_exports_every_declared_symbol():
     hdr = open(os.path.join(ROOT, "include", "ltxk.h")).read()
     assert lib.ltxk_version() == int(re.search(r"#define LTXK_VERSION (\d+)", hdr).group(1))
     import ctypes
-    for which, st in enumerate((_lib.GemmArgs, _lib.Conv3dArgs, _lib.AttnArgs)):       # binding layout == compiled layout
+    for which, st in enumerate((_lib.GemmArgs, _lib.Conv3dArgs, _lib.AttnArgs, _lib.GemmPlan)):   # binding layout == compiled layout
         assert lib.ltxk_abi_sizeof(which) == ctypes.sizeof(st)
 
 
