@@ -65,6 +65,14 @@ __device__ __forceinline__ float gelu_tanh_f(float x) {
   return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(t));
 }
 
+// x / (1 + exp(-x)) in fp32 with correctly rounded division, for the standalone SiLU kernels.  Below x = -88.72 exp(-x)
+// overflows and the quotient would flush to -0 results that are still normal floats (silu(-89) = -2.0e-37); there
+// 1 + exp(-x) == exp(-x) in fp32, so x * exp(x) is the same quotient without the overflow.  Bits elsewhere unchanged.
+__device__ __forceinline__ float silu_div(float x) {
+  const float e = expf(-x);
+  return __builtin_isinf(e) ? x * expf(x) : x / (1.0f + e);
+}
+
 __device__ __forceinline__ float silu_f(float x) { return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * x)); }
 
 // LDS-DMA of one 1-KiB piece: lane i's 16 bytes at gsrc land at lds_dst + 16*i (lds_dst wave-uniform).

@@ -335,7 +335,7 @@ __global__ void silu_kernel(const bf16* __restrict__ x, bf16* __restrict__ y, in
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
     const float f = (float)v[j];
-    o[j] = (bf16)(f / (1.0f + expf(-f)));
+    o[j] = (bf16)silu_div(f);
   }
   *(bf16x8*)(y + idx * 8) = o;
 }

@@ -289,7 +289,7 @@ __global__ __launch_bounds__(256) void groupnorm_act_kernel(const bf16* __restri
     const int64_t off = (i / cg) * C + c;
     float y = rbf(__fdiv_rn((float)xb[off] - mean, sd) * (float)gamma[g * cg + c] + (float)beta[g * cg + c]);
     if (rb) y = rbf(y + (float)rb[off]);
-    if (apply_silu) y = y / (1.0f + expf(-y));
+    if (apply_silu) y = silu_div(y);
     ob[off] = (bf16)y;
   }
 }

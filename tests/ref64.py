@@ -1,0 +1,294 @@
+"""Float64 restatements of the row, elementwise and VAE glue kernels of include/ltxk.h, for the edge-shape tests
+(tests/test_rowops_gpu.py, tests/test_vae_glue_gpu.py; checked against the oracle in tests/test_ref64_cpu.py).
+
+Every function computes in float64 and rounds to bf16 only where the kernel and the reference model materialise a bf16
+array (the kernel comments and the oracle/ function of the same op name those points).  The rounding is done here in
+float64 (``rbf``), never through float32, so a reference value is the correctly rounded bf16 of the exact expression.
+Scalars the kernels receive as fp32 are passed in already rounded to fp32 (``f32``).
+
+``assert_bf16_close`` is the comparator: bf16 ulps measured at max(|ref|, mag) with an absolute floor of 2^-126 (a
+kernel that flushes a subnormal result to zero is not wrong); no element more than ``max_ulps`` away and at most
+``max_frac`` of the elements off at all.  NaN where the reference is finite (an untouched sentinel) counts as infinitely
+far."""
+from __future__ import annotations
+
+import math
+from typing import Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+Tensor = torch.Tensor
+F64 = torch.float64
+BF = torch.bfloat16
+ULP_FLOOR = 2.0 ** -126
+
+
+def f64(x) -> Tensor:
+    if not isinstance(x, torch.Tensor):
+        return torch.as_tensor(x, dtype=F64)
+    return x.detach().cpu().to(F64)
+
+
+def f32(v: float) -> float:
+    """A host scalar as the kernel receives it (fp32)."""
+    return float(np.float32(v))
+
+
+def ulp_bf16(m: Tensor) -> Tensor:
+    """bf16 ulp at magnitude m (the spacing of the binade m lies in), never below ULP_FLOOR."""
+    m = f64(m).abs().clamp_min(ULP_FLOOR)
+    m = torch.where(torch.isfinite(m), m, torch.full_like(m, 2.0 ** 127))
+    e = torch.floor(torch.log2(m))
+    e = torch.where(torch.exp2(e) > m, e - 1, e)          # log2 of a value just below a power of two may round up
+    return torch.exp2(e - 7).clamp_min(ULP_FLOOR)
+
+
+def rbf(x) -> Tensor:
+    """float64 -> nearest bf16 (ties to even), returned as float64.  Overflow -> +-inf; NaN/inf pass through."""
+    x = f64(x)
+    a = x.abs()
+    e = torch.floor(torch.log2(a.clamp_min(2.0 ** -133)))
+    e = torch.where(torch.exp2(e) > a.clamp_min(2.0 ** -133), e - 1, e)
+    q = torch.exp2(e.clamp_min(-126) - 7)                  # spacing; subnormal bf16 below 2^-126
+    r = torch.round(x / q) * q                             # torch.round: half to even; x/q is exact (power-of-two scale)
+    r = torch.where(r.abs() > 3.3895313892515355e38, torch.sign(x) * math.inf, r)
+    return torch.where(torch.isfinite(x), r, x)
+
+
+def silu(x: Tensor) -> Tensor:
+    """float64 silu of bf16 inputs, one rounding (adaln.py:45, upsampler.py:160-174)."""
+    x = f64(x)
+    return rbf(x / (1.0 + torch.exp(-x)))
+
+
+def bf16_stats(got, ref, mag=None) -> Tuple[float, float]:
+    """(max ulp error, fraction of elements off at all) of got against ref, ulp at max(|ref|, mag)."""
+    g, r = f64(got).flatten(), f64(ref).flatten()
+    m = r.abs() if mag is None else torch.maximum(r.abs(), f64(mag).flatten().abs())
+    d = (g - r).abs()
+    same = (g == r) | (torch.isnan(g) & torch.isnan(r))
+    d = torch.where(same, torch.zeros_like(d), d)
+    d = torch.where(torch.isnan(d), torch.full_like(d, math.inf), d)
+    u = d / ulp_bf16(m)
+    return float(u.max()) if u.numel() else 0.0, float((d > 0).double().mean()) if d.numel() else 0.0
+
+
+def assert_bf16_close(got, ref, *, max_ulps: float = 1, max_frac: float = 0.0, mag=None, what: str = "") -> Tuple[float, float]:
+    ulps, frac = bf16_stats(got, ref, mag)
+    assert ulps <= max_ulps, f"{what}: an element is {ulps:.3g} bf16 ulps off (allowed {max_ulps})"
+    assert frac <= max_frac, f"{what}: {frac:.3e} of the elements differ (allowed {max_frac:.3e})"
+    return ulps, frac
+
+
+# --------------------------------------------------------------------------------------------------- DiT step rows
+def norm_modulate(x, eps: float, scale=None, shift=None, *, layernorm: bool = False, one_plus: bool = False):
+    """rms_norm (weight 1) or LayerNorm(affine=False) + modulation: n = bf16(norm), one_p = bf16(1+scale) (or scale as
+    given when it already holds bf16(1+scale)), out = bf16(bf16(n*one_p) + shift).  Returns (out, mag) with mag the
+    magnitude of the terms of the final add (it can cancel)."""
+    x = f64(x)
+    if layernorm:
+        mu = x.mean(-1, keepdim=True)
+        var = ((x - mu) ** 2).mean(-1, keepdim=True)
+        pre = (x - mu) / torch.sqrt(var + eps)
+    else:
+        pre = x / torch.sqrt((x * x).mean(-1, keepdim=True) + eps)
+    if scale is None:
+        return rbf(pre), None
+    n = rbf(pre)
+    one_p = f64(scale) if one_plus else rbf(1.0 + f64(scale))
+    prod = rbf(n * one_p)
+    return rbf(prod + f64(shift)), (n * one_p).abs() + f64(shift).abs()
+
+
+def qknorm_rope(x, weight, cos, sin, T: int, H: int, eps: float):
+    """q/k RMSNorm over each D-wide segment (learned weight, one rounding) + SPLIT rope (fp32 math, one rounding).
+    x (M, nseg*D); weight (nseg, D); cos/sin (H, T, 64) or None; row m is token m % T.  Returns (out, mag): mag the
+    terms of the rotation (it can cancel a rounding of the normalised pair), None without rope."""
+    x = f64(x)
+    M = x.shape[0]
+    nseg, D = weight.shape
+    seg = x.reshape(M, nseg, D)
+    rstd = 1.0 / torch.sqrt((seg * seg).mean(-1, keepdim=True) + eps)
+    y = rbf(seg * rstd * f64(weight)[None])
+    if cos is None:
+        return y.reshape(M, nseg * D), None
+    yh = y.reshape(M, nseg, H, 2, 64)
+    t = torch.arange(M) % T
+    c = f64(cos)[:, t].permute(1, 0, 2)[:, None]          # (M,1,H,64)
+    s = f64(sin)[:, t].permute(1, 0, 2)[:, None]
+    x1, x2 = yh[..., 0, :], yh[..., 1, :]
+    o = torch.stack([x1 * c - s * x2, x2 * c + s * x1], dim=-2)
+    mag = torch.stack([(x1 * c).abs() + (s * x2).abs(), (x2 * c).abs() + (s * x1).abs()], dim=-2)
+    return rbf(o).reshape(M, nseg * D), mag.reshape(M, nseg * D)
+
+
+def rope_table(positions, freq, H: int, dim: int, max_pos: Sequence[float]):
+    """SPLIT rope table, middle-of-interval positions: positions (3,T,2), freq (n_freq), max_pos 3 scalars (fp32).
+    Returns cos, sin, ang, frac_freq (all (H,T,dim/2/H) float64): ang the exact angle of the fp32 inputs and
+    frac_freq = |2*frac*freq|, the size of the term whose fp32 rounding the angle error scales with."""
+    pos, fr = f64(positions), f64(freq)
+    T, nf = pos.shape[1], fr.numel()
+    half = dim // 2
+    pad = half - 3 * nf
+    mid = (pos[..., 0] + pos[..., 1]) / 2.0                                     # (3,T)
+    frac = mid / f64([f32(m) for m in max_pos])[:, None]
+    ang = ((frac * 2.0 - 1.0).T[:, None, :] * fr[None, :, None]).reshape(T, 3 * nf)   # idx-major, axis-minor
+    big = ((frac * 2.0).abs().T[:, None, :] * fr.abs()[None, :, None]).reshape(T, 3 * nf)
+    z = torch.zeros(T, pad, dtype=F64)
+    ang = torch.cat([z, ang], 1)
+    big = torch.cat([z, big], 1)
+    c = torch.cat([torch.ones(T, pad, dtype=F64), torch.cos(ang[:, pad:])], 1)
+    s = torch.cat([z, torch.sin(ang[:, pad:])], 1)
+    per = half // H
+    r = lambda a: a.reshape(T, H, per).permute(1, 0, 2).contiguous()
+    return r(c), r(s), r(ang), r(big)
+
+
+def timestep_embed(t, dim: int, mult: float):
+    """[cos | sin](bf16(t*mult) * exp(-ln(1e4) i/half)), one rounding each.  Returns (out (U,dim), ang (U,dim)) with
+    ang the exact argument of each output."""
+    tt = rbf(f64(t).flatten() * f32(mult))
+    half = dim // 2
+    fr = torch.exp(-math.log(10000.0) * torch.arange(half, dtype=F64) / half)
+    ang = tt[:, None] * fr[None]
+    return torch.cat([rbf(torch.cos(ang)), rbf(torch.sin(ang))], 1), torch.cat([ang, ang], 1)
+
+
+def ada_combine(table, ada, one_plus_mask: int = 0):
+    """table (L,K,D), ada (U,K*D) -> (L,U,K,D): bf16(table + ada), then bf16(1 + that) for the k in one_plus_mask."""
+    tb = f64(table)
+    L, K, D = tb.shape
+    a = f64(ada).reshape(-1, K, D)
+    v = rbf(tb[:, None] + a[None])
+    bits = torch.tensor([(one_plus_mask >> k) & 1 for k in range(K)], dtype=torch.bool)[None, None, :, None]
+    return torch.where(bits, rbf(1.0 + v), v)
+
+
+def cfg_euler_step(v_pos, v_neg, latent, sigma: float, sigma_next: float, cfg: float = 1.0, clean=None, mask=None,
+                   bf16_euler: bool = False):
+    """The step tail: CFG combine (per-op bf16) + token -> latent transpose + x0 = bf16(x - sigma*v) + mask blend +
+    Euler (fp32 formula with one rounding, or op by op in bf16).  v_* (B,S,C) tokens, latent (B,C,S), clean (B,C,S),
+    mask (B,S).  Returns (out (B,C,S), mag): mag bounds every intermediate the output inherits a rounding from."""
+    vp = f64(v_pos).transpose(1, 2)
+    x = f64(latent)
+    v = vp
+    mag = vp.abs()
+    if v_neg is not None:
+        vn = f64(v_neg).transpose(1, 2)
+        d = rbf(vp - vn)
+        v = rbf(vp + rbf((cfg - 1.0) * d))
+        mag = torch.maximum(vp.abs(), ((cfg - 1.0) * d).abs())
+    x0 = rbf(x - sigma * v)
+    mag = torch.maximum(torch.maximum(mag, x.abs()), (sigma * v).abs())
+    if mask is not None:
+        m = f64(mask)[:, None, :]
+        x0 = rbf(rbf(x0 * m) + rbf(f64(clean) * rbf(1.0 - m)))
+        mag = torch.maximum(mag, f64(clean).abs())
+    if bf16_euler:
+        out = rbf(x0 + rbf(rbf(sigma_next * rbf(x - x0)) / sigma))
+    elif sigma_next > 0:
+        out = rbf(x0 + sigma_next * (x - x0) / sigma)
+    else:
+        out = x0
+    return out, mag
+
+
+def euler_step(latent, denoised, sigma: float, sigma_next: float):
+    """bf16(x0 + sigma_next*(x - x0)/sigma), one rounding.  Returns (out, mag of the final add's terms)."""
+    x, d = f64(latent), f64(denoised)
+    step = sigma_next * (x - d) / sigma
+    return rbf(d + step), d.abs() + step.abs()
+
+
+# ------------------------------------------------------------------------------------------------------- VAE glue
+def groupnorm_act(x, gamma, beta, G: int, eps: float, resid=None, apply_silu: bool = False):
+    """GroupNorm over (voxels, C/G) per (batch, group), float64 mean and centred variance, then
+    bf16((x-mean)/sqrt(var+eps)*gamma+beta) [+ resid -> bf16] [silu -> bf16].  x (B,V,C) channels-last.
+    Returns (out, mag): mag = |norm*gamma| + |beta| (the affine add can cancel) plus |gamma*mean/sd|*2^-12 (the fp32
+    statistics of a kernel are good to far less than that: an allowance of ~2^-19 |mean| per ulp near zero), plus
+    |resid| with a residual."""
+    x = f64(x)
+    B, V, C = x.shape
+    xg = x.reshape(B, V, G, C // G)
+    mean = xg.mean(dim=(1, 3), keepdim=True)
+    var = ((xg - mean) ** 2).mean(dim=(1, 3), keepdim=True)
+    sd = torch.sqrt(var + eps)
+    y = ((xg - mean) / sd).reshape(B, V, C)
+    gm = f64(gamma)
+    mag = (y * gm).abs() + f64(beta).abs() + ((mean / sd).expand_as(xg).reshape(B, V, C) * gm).abs() * 2.0 ** -12
+    y = rbf(y * gm + f64(beta))
+    if resid is not None:
+        mag = torch.maximum(mag, y.abs() + f64(resid).abs())
+        y = rbf(y + f64(resid))
+    if apply_silu:                                 # silu(y) ~ y/2 near 0: a flip of y is up to two ulps of the output
+        y = silu(y)
+    return y, mag
+
+
+def latent_denorm_cl(latent, mean, std, noise=None, noise_scale: float = 0.0):
+    """(B,C,S) -> (B,S,C): bf16(x*std + mean) in one rounding; with noise the blend bf16(bf16(noise*s) + bf16((1-s)*x))
+    first, 1-s formed in fp32 as the kernel (and the reference's scalar arithmetic) forms it.  Returns (out, mag) with
+    mag = |x*std| + |mean| (the add can cancel a rounding of the blend)."""
+    x = f64(latent)
+    if noise is not None:
+        s = f32(noise_scale)
+        oms = f32(1.0 - s)
+        x = rbf(rbf(f64(noise) * s) + rbf(oms * x))
+    xs, mu = x * f64(std)[None, :, None], f64(mean)[None, :, None]
+    return rbf(xs + mu).transpose(1, 2).contiguous(), (xs.abs() + mu.abs()).transpose(1, 2).contiguous()
+
+
+def latent_norm_cf(x, mean, std):
+    """(B,S,C) -> (B,C,S): bf16((x - mean)/std), one rounding."""
+    y = (f64(x) - f64(mean)) / f64(std)
+    return rbf(y).transpose(1, 2).contiguous()
+
+
+def tile_blend(tiles, F: int, H: int, W: int):
+    """Tiled-decode blend in float64: tiles = [(tile (B,C,Tt,Th,Tw), (at,ah,aw), mt, mh, mw, (t0,h0,w0))];
+    out = bf16(sum tile*m / max(sum m, 1e-8)) with m = mt[t]*mh[y]*mw[x] over the used box of each tile."""
+    B, C = tiles[0][0].shape[:2]
+    acc = torch.zeros(B, C, F, H, W, dtype=F64)
+    ws = torch.zeros(B, 1, F, H, W, dtype=F64)
+    for tile, (at, ah, aw), mt, mh, mw, (t0, h0, w0) in tiles:
+        m = f64(mt)[:at, None, None] * f64(mh)[None, :ah, None] * f64(mw)[None, None, :aw]
+        acc[:, :, t0:t0 + at, h0:h0 + ah, w0:w0 + aw] += f64(tile)[:, :, :at, :ah, :aw] * m
+        ws[:, :, t0:t0 + at, h0:h0 + ah, w0:w0 + aw] += m
+    return rbf(acc / ws.clamp_min(1e-8))
+
+
+def to_uint8(video) -> Tensor:
+    """(B,C,F,H,W) bf16 video in [-1,1] -> (B,F,H,W,C) uint8: u = bf16(bf16(x+1)/2) clamped to [0,1],
+    trunc(bf16(u*255))."""
+    v = f64(video).permute(0, 2, 3, 4, 1)
+    u = rbf(rbf(v + 1.0) / 2.0).clamp(0.0, 1.0)
+    return torch.trunc(rbf(u * 255.0)).to(torch.uint8)
+
+
+def patchify(video, P: int, Cpad: Optional[int] = None) -> Tensor:
+    """(B,C,D,H,W) -> (B,D,H/P,W/P,Cpad) channels-last, channel c*P*P + p_w*P + p_h holding video[b,c,d,h*P+p_h,
+    w*P+p_w] (ops.py:9-44, width before height); channels past C*P*P zero.  A gather over explicit indices."""
+    v = torch.as_tensor(video)
+    B, C, D, H, W = v.shape
+    Cpad = C * P * P if Cpad is None else Cpad
+    ch = torch.arange(C * P * P)
+    c, pw, ph = ch // (P * P), (ch // P) % P, ch % P
+    hh = (torch.arange(H // P)[:, None] * P + ph[None, :])                     # (Hp, CPP)
+    ww = (torch.arange(W // P)[:, None] * P + pw[None, :])                     # (Wp, CPP)
+    g = v[:, c[None, None, :], :, hh[:, None, :], ww[None, :, :]]             # (Hp,Wp,CPP,B,D)... advanced-index order
+    g = g.permute(3, 4, 0, 1, 2)                                               # (B,D,Hp,Wp,CPP)
+    out = torch.zeros(B, D, H // P, W // P, Cpad, dtype=v.dtype)
+    out[..., :C * P * P] = g
+    return out
+
+
+def unpatchify(x, C: int, P: int) -> Tensor:
+    """(B,D,H,W,C*P*P) channels-last -> (B,C,D,H*P,W*P): out[b,c,d,y,x] = x[b,d,y//P,x//P, c*P*P + (x%P)*P + y%P]."""
+    x = torch.as_tensor(x)
+    B, D, H, W, _ = x.shape
+    yo, xo = torch.arange(H * P), torch.arange(W * P)
+    c = torch.arange(C)
+    ch = c[:, None, None] * P * P + (xo % P)[None, None, :] * P + (yo % P)[None, :, None]   # (C,Ho,Wo)
+    g = x[:, :, (yo // P)[None, :, None], (xo // P)[None, None, :], ch]                  # (B,D,C,Ho,Wo)
+    return g.permute(0, 2, 1, 3, 4).contiguous()
