@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define LTXK_VERSION 401
+#define LTXK_VERSION 402
 
 #define LTXK_OK 0
 #define LTXK_EINVAL (-1)   /* bad argument (shape / alignment / null pointer) */
@@ -38,7 +38,7 @@ extern "C" {
 int ltxk_version(void);
 const char* ltxk_last_error(void);
 /* sizeof the argument structs in THIS build: 0 = ltxk_gemm_args, 1 = ltxk_conv3d_args, 2 = ltxk_attn_args,
- * 3 = struct ltxk_gemm_plan; anything else returns -1;
+ * 3 = struct ltxk_gemm_plan, 4 = ltxk_step_args; anything else returns -1;
  * lets a foreign-language binding verify its struct layout before the first call.        */
 int ltxk_abi_sizeof(int which);
 
@@ -243,6 +243,39 @@ int ltxk_cfg_euler_step(const void* v_pos, const void* v_neg, const void* latent
 int ltxk_cfg_euler_step_dev(const void* v_pos, const void* v_neg, const void* latent, void* out,
                             const void* clean, const float* mask, int32_t B, int32_t C, int32_t S,
                             float cfg_scale, const float* sigmas_dev, int32_t flags, void* stream);
+
+/* The step tail with spatio-temporal guidance (STG): a third velocity v_pert (B,S,C) - the forward of the positive
+ * prompt with the video self-attention of chosen blocks skipped (ltxk_attn_value_passthrough) - pushes the guided
+ * velocity away from it, in velocity space, before x0:
+ *   g = v_neg ? bf16(v_pos + bf16((cfg_scale-1) * bf16(v_pos - v_neg))) : v_pos       (exactly the CFG combine above)
+ *   v = bf16(g + bf16(stg_scale * bf16(v_pos - v_pert)))
+ * then x0, mask blend and Euler exactly as ltxk_cfg_euler_step.  x0 = x - sigma*v is affine in v with coefficients that
+ * sum to one, so this is cond + CFGGuider.delta + STGGuider.delta of the x0-space guiders (guiders.py) in exact
+ * arithmetic.  sigmas_dev != NULL: {sigma, sigma_next} are read from device memory (as ltxk_cfg_euler_step_dev).
+ * v_pert == NULL: the very launch ltxk_cfg_euler_step(_dev) makes (stg_scale ignored).                           */
+typedef struct ltxk_step_args {
+  const void* v_pos;          /* (B,S,C) bf16                                                      */
+  const void* v_neg;          /* (B,S,C) bf16 or NULL (no CFG)                                     */
+  const void* v_pert;         /* (B,S,C) bf16 or NULL (no STG)                                     */
+  const void* latent;         /* (B,C,S) bf16                                                      */
+  void* out;                  /* (B,C,S) bf16; may be `latent`                                     */
+  const void* clean;          /* (B,C,S) bf16 or NULL                                              */
+  const float* mask;          /* (B,S) fp32 or NULL (with clean)                                   */
+  const float* sigmas_dev;    /* 2 fp32 in device memory, or NULL: use sigma / sigma_next          */
+  int32_t B, C, S;
+  float cfg_scale, stg_scale, sigma, sigma_next;
+  int32_t flags;              /* LTXK_STEP_*                                                       */
+} ltxk_step_args;
+
+int ltxk_guided_euler_step(const ltxk_step_args* args, void* stream);
+
+/* The value passthrough of a skipped video self-attention (STG, perturbations.py SKIP_VIDEO_SELF_ATTN): for every batch
+ * row b whose bit is set in row_mask, out[(b*T+t)*ldo + c] = vt[(b*D+c)*ldvt + t] for t < T, c < D - the V^T buffer of
+ * the q|k|v GEMM (ltxk_gemm_bf16 split output) transposed back to the token-major rows the out-projection reads, a
+ * bit-exact copy.  Rows whose bit is clear are not touched.  B <= 64; D a multiple of 128; ldvt >= T and ldo >= D,
+ * both multiples of 8; vt and out 16-byte aligned.                                       */
+int ltxk_attn_value_passthrough(const void* vt, int32_t ldvt, void* out, int32_t ldo, int32_t B, int32_t D, int32_t T,
+                                uint64_t row_mask, void* stream);
 
 /* Per-step scalars of a replayed step graph: with s = min(*step, n_steps-1), copies ts_all[s,:] (U bf16
  * timestep values = bf16(sigma_s)*mask, generate.py:1084,1237) to ts and sig_all[s,:] ({sigma, sigma_next}

@@ -4,7 +4,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_char_p, c_float, c_int32, c_int64, c_uint32, c_void_p
+from ctypes import POINTER, Structure, c_char_p, c_float, c_int32, c_int64, c_uint32, c_uint64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LTXK_LIB", os.path.join(_HERE, "libltxk.so"))
@@ -52,6 +52,15 @@ class Conv3dArgs(Structure):
         ("causal", c_int32), ("pad_mode", c_int32),
         ("workspace", c_void_p), ("workspace_bytes", c_int64), ("taps_d", c_int32),
         ("act_out", c_void_p), ("act_scale", c_void_p), ("act_shift", c_void_p), ("act_eps", c_float), ("act_silu", c_int32),
+    ]
+
+
+class StepArgs(Structure):
+    _fields_ = [
+        ("v_pos", c_void_p), ("v_neg", c_void_p), ("v_pert", c_void_p), ("latent", c_void_p), ("out", c_void_p),
+        ("clean", c_void_p), ("mask", c_void_p), ("sigmas_dev", c_void_p),
+        ("B", c_int32), ("C", c_int32), ("S", c_int32),
+        ("cfg_scale", c_float), ("stg_scale", c_float), ("sigma", c_float), ("sigma_next", c_float), ("flags", c_int32),
     ]
 
 
@@ -105,9 +114,15 @@ SIGNATURES = {
     "ltxk_euler_step": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_void_p]),
     "ltxk_cfg_euler_step_dev": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32,
                                           c_int32, c_float, c_void_p, c_int32, c_void_p]),
+    "ltxk_guided_euler_step": (c_int32, [POINTER(StepArgs), c_void_p]),
+    "ltxk_attn_value_passthrough": (c_int32, [c_void_p, c_int32, c_void_p, c_int32, c_int32, c_int32, c_int32, c_uint64,
+                                              c_void_p]),
     "ltxk_cfg_euler_step": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32,
                                       c_int32, c_float, c_float, c_float, c_int32, c_void_p]),
 }
+
+# ltxk_abi_sizeof(i) is the size of ABI_STRUCTS[i]
+ABI_STRUCTS = (GemmArgs, Conv3dArgs, AttnArgs, GemmPlan, StepArgs)
 
 _lib = None
 AB_LIB_PATH = os.path.join(_HERE, "libltxk_ab.so")
@@ -126,7 +141,7 @@ def _open(path: str) -> ctypes.CDLL:
         fn = getattr(lib, name)  # AttributeError if the .so is stale
         fn.restype = res
         fn.argtypes = args
-    for which, st in enumerate((GemmArgs, Conv3dArgs, AttnArgs, GemmPlan)):
+    for which, st in enumerate(ABI_STRUCTS):
         if lib.ltxk_abi_sizeof(which) != ctypes.sizeof(st):
             raise LtxkError(f"{path} is stale: sizeof({st.__name__}) is {lib.ltxk_abi_sizeof(which)} in the library, "
                             f"{ctypes.sizeof(st)} in this binding; rebuild it (make -C mlx-video_amd/csrc)")

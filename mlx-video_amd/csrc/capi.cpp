@@ -22,6 +22,7 @@ extern "C" int ltxk_abi_sizeof(int which) {
     case 1: return (int)sizeof(ltxk_conv3d_args);
     case 2: return (int)sizeof(ltxk_attn_args);
     case 3: return (int)sizeof(struct ltxk_gemm_plan);
+    case 4: return (int)sizeof(ltxk_step_args);
   }
   return -1;
 }

@@ -353,11 +353,15 @@ __global__ void latent_to_tokens_kernel(const bf16* __restrict__ lat, bf16* __re
     *(bf16x8*)(tok + (((size_t)(r * B + b)) * S + s) * C + cg * 8) = v;
 }
 
+// STG: a third velocity (the perturbed forward, vq) pushes the CFG-guided velocity g away from it in velocity space,
+// v = bf16(g + bf16(stg * bf16(v+ - vq))), before x0; without it the kernel is the plain CFG step tail.
+template <bool STG>
 __global__ void cfg_euler_kernel(const bf16* __restrict__ vp, const bf16* __restrict__ vn,
                                  const bf16* __restrict__ lat, bf16* __restrict__ out,
                                  const bf16* __restrict__ clean, const float* __restrict__ mask,
                                  int B, int C, int S, float cfg, float sigma, float sigma_next,
-                                 const float* __restrict__ sig_dev, int flags) {
+                                 const float* __restrict__ sig_dev, int flags,
+                                 const bf16* __restrict__ vq = nullptr, float stg = 0.f) {
   if (sig_dev) {            // graph replay: the two scalars live in device memory
     sigma = sig_dev[0];
     sigma_next = sig_dev[1];
@@ -369,6 +373,8 @@ __global__ void cfg_euler_kernel(const bf16* __restrict__ vp, const bf16* __rest
   const bf16x8 p = *(const bf16x8*)(vp + tokoff);
   bf16x8 n = p;
   if (vn) n = *(const bf16x8*)(vn + tokoff);
+  bf16x8 q;
+  if constexpr (STG) q = *(const bf16x8*)(vq + tokoff);
   float m = 1.f;
   if (mask) m = mask[(size_t)b * S + s];
 #pragma unroll
@@ -376,6 +382,7 @@ __global__ void cfg_euler_kernel(const bf16* __restrict__ vp, const bf16* __rest
     const size_t li = ((size_t)b * C + cg * 8 + j) * S + s;
     float v = (float)p[j];
     if (vn) v = rbf(v + rbf((cfg - 1.0f) * rbf(v - (float)n[j])));
+    if constexpr (STG) v = rbf(v + rbf(stg * rbf((float)p[j] - (float)q[j])));
     const float x = (float)lat[li];
     float x0 = rbf(x - sigma * v);
     if (mask) x0 = rbf(rbf(x0 * m) + rbf((float)clean[li] * rbf(1.0f - m)));
@@ -417,6 +424,49 @@ __global__ void step_scalars_kernel(const bf16* __restrict__ ts_all, const float
   for (int i = threadIdx.x; i < U; i += blockDim.x) ts[i] = ts_all[(size_t)s * U + i];
   if (threadIdx.x < 2) sig[threadIdx.x] = sig_all[2 * s + threadIdx.x];
   if (threadIdx.x == 0) *step = s + 1;
+}
+
+// Value passthrough of a skipped self-attention (STG): out[(b*T+t)*ldo + c] = vt[(b*D+c)*ldvt + t] for every batch row b
+// whose bit is set in row_mask - the V^T buffer the q|k|v GEMM wrote, transposed back to the token-major rows the
+// out-projection reads.  A 64(t) x 64(c) tile per workgroup through LDS: 16-byte global loads along t (8 tokens of one
+// channel), 16-byte global stores along c (8 channels of one token).  The LDS row holds 66 bf16 (33 dwords) so that a
+// wave's transposed reads - 8 channel groups x 8 tokens, one bf16 each - fall into distinct banks.
+constexpr int VP_TILE = 64, VP_LD = VP_TILE + 2;
+
+__global__ __launch_bounds__(256) void value_passthrough_kernel(const bf16* __restrict__ vt, int ldvt, bf16* __restrict__ out,
+                                                                int ldo, int D, int T, uint64_t row_mask) {
+  const int b = blockIdx.z;
+  if (!((row_mask >> b) & 1ull)) return;
+  __shared__ uint32_t tile[VP_TILE * VP_LD / 2];
+  const int t0 = blockIdx.x * VP_TILE, c0 = blockIdx.y * VP_TILE;
+  const int tid = threadIdx.x;
+  const bf16* src = vt + ((size_t)b * D + c0) * ldvt + t0;
+#pragma unroll
+  for (int it = 0; it < 2; ++it) {
+    const int chunk = tid + it * 256;          // 64 channels x 8 chunks of 8 tokens
+    const int c = chunk >> 3, tc = (chunk & 7) * 8;
+    // t0 + tc < T <= ldvt and both multiples of 8: the 16 bytes lie inside the padded row
+    if (t0 + tc < T) {
+      const uint4 v = *(const uint4*)(src + (size_t)c * ldvt + tc);
+      uint32_t* d = tile + (c * VP_LD + tc) / 2;
+      d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
+    }
+  }
+  __syncthreads();
+  const unsigned short* t16 = (const unsigned short*)tile;
+#pragma unroll
+  for (int it = 0; it < 2; ++it) {
+    const int item = tid + it * 256;           // 64 tokens x 8 channel groups; a wave covers 8 tokens x all 8 groups
+    const int cg = item & 7, t = item >> 3;
+    if (t0 + t >= T) continue;
+    unsigned short h[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) h[j] = t16[(cg * 8 + j) * VP_LD + t];
+    uint4 o;
+    o.x = h[0] | ((uint32_t)h[1] << 16); o.y = h[2] | ((uint32_t)h[3] << 16);
+    o.z = h[4] | ((uint32_t)h[5] << 16); o.w = h[6] | ((uint32_t)h[7] << 16);
+    *(uint4*)(out + ((size_t)b * T + t0 + t) * ldo + c0 + cg * 8) = o;
+  }
 }
 
 }  // namespace ltxk
@@ -596,9 +646,9 @@ static int cfg_euler_launch(const void* v_pos, const void* v_neg, const void* la
   LTXK_CHECK_ARG(v_pos && latent && out && B > 0 && S > 0 && C > 0 && C % 8 == 0, "%s: bad arguments", name);
   LTXK_CHECK_ARG((clean == nullptr) == (mask == nullptr), "%s: clean and mask must both be set or both NULL", name);
   LTXK_CHECK_ARG(sig_dev != nullptr || sigma > 0.f, "%s: sigma must be > 0", name);
-  hipLaunchKernelGGL(cfg_euler_kernel, dim3((S + 63) / 64, C / 8, B), dim3(64), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(cfg_euler_kernel<false>, dim3((S + 63) / 64, C / 8, B), dim3(64), 0, (hipStream_t)stream,
                      (const bf16*)v_pos, (const bf16*)v_neg, (const bf16*)latent, (bf16*)out, (const bf16*)clean, mask,
-                     B, C, S, cfg_scale, sigma, sigma_next, sig_dev, (int)flags);
+                     B, C, S, cfg_scale, sigma, sigma_next, sig_dev, (int)flags, nullptr, 0.f);
   LTXK_CHECK_LAUNCH(name);
   return LTXK_OK;
 }
@@ -616,4 +666,36 @@ extern "C" int ltxk_cfg_euler_step_dev(const void* v_pos, const void* v_neg, con
   LTXK_CHECK_ARG(sigmas_dev != nullptr, "ltxk_cfg_euler_step_dev: null sigmas_dev");
   return cfg_euler_launch(v_pos, v_neg, latent, out, clean, mask, B, C, S, cfg_scale, 1.f, 0.f, sigmas_dev, flags, stream,
                           "ltxk_cfg_euler_step_dev");
+}
+
+extern "C" int ltxk_guided_euler_step(const ltxk_step_args* a, void* stream) {
+  LTXK_CHECK_ARG(a != nullptr, "ltxk_guided_euler_step: null args");
+  if (a->v_pert == nullptr)      // no STG term: exactly the launch ltxk_cfg_euler_step(_dev) makes
+    return cfg_euler_launch(a->v_pos, a->v_neg, a->latent, a->out, a->clean, a->mask, a->B, a->C, a->S, a->cfg_scale,
+                            a->sigma, a->sigma_next, a->sigmas_dev, a->flags, stream, "ltxk_guided_euler_step");
+  LTXK_CHECK_ARG(a->v_pos && a->latent && a->out && a->B > 0 && a->S > 0 && a->C > 0 && a->C % 8 == 0,
+                 "ltxk_guided_euler_step: bad arguments");
+  LTXK_CHECK_ARG((a->clean == nullptr) == (a->mask == nullptr), "ltxk_guided_euler_step: clean and mask must both be set or both NULL");
+  LTXK_CHECK_ARG(a->sigmas_dev != nullptr || a->sigma > 0.f, "ltxk_guided_euler_step: sigma must be > 0");
+  hipLaunchKernelGGL(cfg_euler_kernel<true>, dim3((a->S + 63) / 64, a->C / 8, a->B), dim3(64), 0, (hipStream_t)stream,
+                     (const bf16*)a->v_pos, (const bf16*)a->v_neg, (const bf16*)a->latent, (bf16*)a->out, (const bf16*)a->clean,
+                     a->mask, a->B, a->C, a->S, a->cfg_scale, a->sigma, a->sigma_next, a->sigmas_dev, (int)a->flags,
+                     (const bf16*)a->v_pert, a->stg_scale);
+  LTXK_CHECK_LAUNCH("ltxk_guided_euler_step");
+  return LTXK_OK;
+}
+
+extern "C" int ltxk_attn_value_passthrough(const void* vt, int32_t ldvt, void* out, int32_t ldo, int32_t B, int32_t D, int32_t T,
+                                           uint64_t row_mask, void* stream) {
+  LTXK_CHECK_ARG(vt && out && B > 0 && B <= 64 && T > 0 && D > 0 && D % 128 == 0,
+                 "ltxk_attn_value_passthrough: bad arguments (B in [1,64], T > 0, D a multiple of 128)");
+  LTXK_CHECK_ARG(ldvt >= T && ldvt % 8 == 0 && ldo >= D && ldo % 8 == 0,
+                 "ltxk_attn_value_passthrough: ldvt must be >= T, ldo >= D, both multiples of 8");
+  LTXK_CHECK_ARG(((uintptr_t)vt & 15) == 0 && ((uintptr_t)out & 15) == 0, "ltxk_attn_value_passthrough: vt/out must be 16-byte aligned");
+  if (B < 64) row_mask &= (1ull << B) - 1;
+  if (row_mask == 0) return LTXK_OK;
+  hipLaunchKernelGGL(value_passthrough_kernel, dim3((T + VP_TILE - 1) / VP_TILE, D / VP_TILE, B), dim3(256), 0,
+                     (hipStream_t)stream, (const bf16*)vt, (int)ldvt, (bf16*)out, (int)ldo, (int)D, (int)T, row_mask);
+  LTXK_CHECK_LAUNCH("ltxk_attn_value_passthrough");
+  return LTXK_OK;
 }

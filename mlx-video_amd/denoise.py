@@ -15,6 +15,7 @@ import torch
 
 from . import ops
 from .conditioning import LatentState
+from .guidance import BatchedPerturbationConfig, PerturbationConfig, stg_perturbation
 from .ltx_model import ContextKV, LTXModel, TimestepPlan, precompute_freqs_cis
 
 BF16 = torch.bfloat16
@@ -59,36 +60,84 @@ class _StepPlan:
         return TimestepPlan(self._ts_dev[i], self.tok2row)
 
 
+class _Guidance:
+    """What one step evaluates: the positive forward, the negative one (CFG, cfg_scale != 1) and the perturbed one (STG,
+    stg_scale != 0), either as separate forwards or - ``batched`` (cfg_batch) - as one forward over the rows
+    [pos | neg | pos+], each block of ``b`` rows."""
+
+    def __init__(self, b: int, cfg_scale: float, cfg_batch: bool, stg_scale: float, pert: Optional[PerturbationConfig]):
+        self.b = b
+        self.use_cfg = cfg_scale != 1.0
+        self.use_stg = pert is not None
+        self.cfg_scale, self.stg_scale = float(cfg_scale), float(stg_scale)
+        self.batched = bool(cfg_batch) and (self.use_cfg or self.use_stg)
+        self.reps = (1 + self.use_cfg + self.use_stg) if self.batched else 1
+        # the batched forward perturbs its last b rows; the separate perturbed forward all of its b rows
+        self.pert_batched = BatchedPerturbationConfig([PerturbationConfig.empty()] * ((self.reps - 1) * b) + [pert] * b) \
+            if self.use_stg and self.batched else None
+        self.pert_alone = BatchedPerturbationConfig([pert] * b) if self.use_stg and not self.batched else None
+
+    def context_rows(self, ctx_pos, ctx_neg):
+        """The contexts of the batched forward's rows, in row order."""
+        return [ctx_pos] + ([ctx_neg] if self.use_cfg else []) + ([ctx_pos] if self.use_stg else [])
+
+    def velocities(self, tr: LTXModel, lat, tp, pe, ctx_rows, kv_rows, ctx_pos, kv_pos, ctx_neg, kv_neg):
+        """(v_pos, v_neg | None, v_pert | None) of one step.  ``ctx_rows``/``kv_rows``: the batched forward's context (and its
+        ContextKV or None); ``ctx_pos``/``kv_pos``, ``ctx_neg``/``kv_neg``: those of the separate forwards."""
+        b = self.b
+        if self.batched:
+            v = tr.forward_tokens(ops.latent_to_tokens(lat, rep=self.reps), tp, ctx_rows, pe, kv_rows,
+                                  perturbations=self.pert_batched)
+            v_neg = v[b:2 * b] if self.use_cfg else None
+            v_pert = v[(self.reps - 1) * b:] if self.use_stg else None
+            return v[:b], v_neg, v_pert
+        tok = ops.latent_to_tokens(lat, rep=1)
+        v_pos = tr.forward_tokens(tok, tp, ctx_pos, pe, kv_pos)
+        v_neg = tr.forward_tokens(tok, tp, ctx_neg, pe, kv_neg) if self.use_cfg else None
+        v_pert = tr.forward_tokens(tok, tp, ctx_pos, pe, kv_pos, perturbations=self.pert_alone) if self.use_stg else None
+        return v_pos, v_neg, v_pert
+
+    def tail(self, v_pos, v_neg, v_pert, latents, s, s_next, clean, mask_tok, out=None, sigmas_dev=None, bf16_euler=False):
+        if v_pert is None:            # no STG: today's CFG step tail, launch for launch
+            return ops.cfg_euler_step(v_pos, v_neg, latents, self.cfg_scale, s, s_next, clean, mask_tok, out=out,
+                                      sigmas_dev=sigmas_dev, bf16_euler=bf16_euler)
+        return ops.guided_euler_step(v_pos, v_neg, v_pert, latents, self.cfg_scale, self.stg_scale, s, s_next, clean, mask_tok,
+                                     out=out, sigmas_dev=sigmas_dev, bf16_euler=bf16_euler)
+
+
 def _denoise(latents: torch.Tensor, positions: torch.Tensor, ctx_pos_in: torch.Tensor, ctx_neg_in: Optional[torch.Tensor],
              transformer: LTXModel, sig: List[float], cfg_scale: float, state: Optional[LatentState], compile_step: bool,
-             cfg_batch: bool, use_graph: bool, graph_cache: Optional[dict], cache_context: bool, bf16_euler: bool) -> torch.Tensor:
+             cfg_batch: bool, use_graph: bool, graph_cache: Optional[dict], cache_context: bool, bf16_euler: bool,
+             stg_scale: float = 0.0, stg_pert: Optional[PerturbationConfig] = None, stg_key: tuple = ()) -> torch.Tensor:
     if state is not None:
         latents = state.latent
     latents = latents.to(BF16).contiguous()
     use_cfg = cfg_scale != 1.0
-    cfg_batch = cfg_batch and use_cfg
     bf16_euler = bf16_euler and compile_step          # the eager body always updates in fp32 (generate.py:835-849)
     if len(sig) < 2:
         return latents
+    b = latents.shape[0]
+    gd = _Guidance(b, cfg_scale, cfg_batch, stg_scale, stg_pert)
     pe = precompute_freqs_cis(positions[:1].contiguous(), transformer.inner_dim, transformer.positional_embedding_theta,
                               transformer.positional_embedding_max_pos, transformer.num_attention_heads)
-    plan = _StepPlan(latents, state, 2 if cfg_batch else 1, sig)
+    plan = _StepPlan(latents, state, gd.reps, sig)
     ctx_pos = ctx_pos_in.to(BF16).contiguous()
     ctx_neg = ctx_neg_in.to(BF16).contiguous() if use_cfg else None
-    b = latents.shape[0]
     if use_graph and compile_step and len(sig) - 1 <= GRAPH_MAX_STEPS:
-        key = (tuple(latents.shape), bool(cfg_batch), bool(use_cfg), float(cfg_scale), tuple(ctx_pos.shape), id(transformer),
+        key = (tuple(latents.shape), bool(gd.batched), bool(use_cfg), float(cfg_scale), tuple(ctx_pos.shape), id(transformer),
                state is not None, plan.U, bool(bf16_euler), bool(cache_context))
+        if gd.use_stg:                # STG off: today's key
+            key = key + stg_key
         cache = graph_cache if graph_cache is not None else {}
         ent = cache.get(key)
         if ent is None:
-            ent = _StepGraph(latents, plan, transformer, ctx_pos, cfg_scale, cfg_batch, use_cfg, bf16_euler, cache_context)
+            ent = _StepGraph(latents, plan, transformer, ctx_pos, gd, bf16_euler, cache_context)
             cache[key] = ent
         return ent.run(latents, plan, ctx_pos, ctx_neg, pe)
-    ctx_cat = torch.cat([ctx_pos, ctx_neg], 0).contiguous() if cfg_batch else None
+    ctx_cat = torch.cat(gd.context_rows(ctx_pos, ctx_neg), 0).contiguous() if gd.batched else None
     kv_pos = kv_neg = kv_cat = None
     if cache_context:
-        if cfg_batch:
+        if gd.batched:
             kv_cat = transformer.prepare_context(ctx_cat)
         else:
             kv_pos = transformer.prepare_context(ctx_pos)
@@ -96,22 +145,14 @@ def _denoise(latents: torch.Tensor, positions: torch.Tensor, ctx_pos_in: torch.T
     for i in range(len(sig) - 1):
         s_bf, sn_bf = plan.sig_bf[i], plan.sig_bf[i + 1]
         tp = plan.timestep_plan(i)
-        if cfg_batch:
-            tok = ops.latent_to_tokens(latents, rep=2)
-            v = transformer.forward_tokens(tok, tp, ctx_cat, pe, kv_cat)
-            v_pos, v_neg = v[:b], v[b:]
-        else:
-            tok = ops.latent_to_tokens(latents, rep=1)
-            v_pos = transformer.forward_tokens(tok, tp, ctx_pos, pe, kv_pos)
-            v_neg = transformer.forward_tokens(tok, tp, ctx_neg, pe, kv_neg) if use_cfg else None
+        v_pos, v_neg, v_pert = gd.velocities(transformer, latents, tp, pe, ctx_cat, kv_cat, ctx_pos, kv_pos, ctx_neg, kv_neg)
         # x0 uses the bf16 sigma in both paths; Euler: bf16 sigmas if compiled else Python floats.
         # The fused kernel takes one sigma for x0 and the ratio terms; when they differ (eager path)
         # x0 and Euler run as two launches.
         if compile_step or (s_bf == sig[i] and sn_bf == sig[i + 1]):
-            latents = ops.cfg_euler_step(v_pos, v_neg, latents, cfg_scale, s_bf, sn_bf, plan.clean, plan.mask_tok_f32,
-                                         bf16_euler=bf16_euler)
+            latents = gd.tail(v_pos, v_neg, v_pert, latents, s_bf, sn_bf, plan.clean, plan.mask_tok_f32, bf16_euler=bf16_euler)
         else:
-            latents = _eager_tail(v_pos, v_neg, latents, cfg_scale, s_bf, sig[i], sig[i + 1], plan)
+            latents = _eager_tail(gd, v_pos, v_neg, v_pert, latents, s_bf, sig[i], sig[i + 1], plan)
     return latents
 
 
@@ -120,7 +161,8 @@ def denoise_dev(latents: torch.Tensor, positions: torch.Tensor, text_embeddings_
                 cfg_scale: float = 4.0, verbose: bool = False, state: Optional[LatentState] = None,
                 eval_interval: int = 1, compile_step: bool = False, compile_shapeless: bool = False,
                 cfg_batch: bool = False, ui_phase: str = "denoise", use_graph: bool = False,
-                graph_cache: Optional[dict] = None, cache_context: bool = False) -> torch.Tensor:
+                graph_cache: Optional[dict] = None, cache_context: bool = False, stg_scale: float = 0.0,
+                stg_blocks: Optional[Sequence[int]] = None, stg_mode: str = "stg_v") -> torch.Tensor:
     """generate.py:1060-1327.  latents (B,128,F,H,W) bf16 on the GPU; returns the same shape.
     ``use_graph``: capture the whole step (forward(s) + fused tail, ~1000 launches) once as a hipGraph and
     replay it per step — the analogue of the reference's mx.compile'd step_fn (generate.py:1109-1177);
@@ -130,10 +172,20 @@ def denoise_dev(latents: torch.Tensor, positions: torch.Tensor, text_embeddings_
     (latents, contexts, clean latent, mask, token->row map, RoPE table) and each call REFRESHES them, so a new
     prompt / mask / conditioning never sees stale data whatever addresses the new tensors happen to get.
     ``cache_context``: compute the text-only part of the forward (caption projection, cross-attention K/V)
-    once per call instead of every step — an algorithmic change relative to the reference."""
+    once per call instead of every step — an algorithmic change relative to the reference.
+    ``stg_scale`` != 0 turns on spatio-temporal guidance (STG, upstream LTX-2's STGGuider): every step also evaluates the
+    positive prompt with the video self-attention of ``stg_blocks`` skipped (each returns its value projection; None = every
+    block) and pushes the guided velocity away from that prediction by ``stg_scale`` (ltxk_guided_euler_step; DESIGN.md
+    "Spatio-temporal guidance").  With ``cfg_batch`` the three predictions are one B=3 forward [pos, neg, pos+] ([pos, pos+]
+    when cfg_scale == 1); without it a third forward.  ``stg_mode``: "stg_v" or "stg_av"; the latter also perturbs the
+    audio self-attention upstream, and as this model has no audio branch it acts as "stg_v".  ``stg_blocks`` that is
+    empty or names a block outside [0, num_layers) is a ValueError.  stg_scale == 0: no STG, today's loop bit for bit."""
+    stg_scale = float(stg_scale or 0.0)
+    pert = stg_perturbation(stg_blocks, stg_mode, transformer.config.num_layers) if stg_scale != 0.0 else None
+    stg_key = (stg_scale, None if stg_blocks is None else tuple(int(x) for x in stg_blocks), stg_mode)
     sig = [float(s) for s in (sigmas.tolist() if torch.is_tensor(sigmas) else sigmas)]
     return _denoise(latents, positions, text_embeddings_pos, text_embeddings_neg, transformer, sig, cfg_scale, state,
-                    compile_step, cfg_batch, use_graph, graph_cache, cache_context, False)
+                    compile_step, cfg_batch, use_graph, graph_cache, cache_context, False, stg_scale, pert, stg_key)
 
 
 class _StepGraph:
@@ -143,16 +195,14 @@ class _StepGraph:
     first step of the first run executes eagerly (it doubles as the warm-up torch requires before capture:
     allocator, lazy hipFuncSetAttribute calls), then the step is captured and every later step is a replay."""
 
-    def __init__(self, latents, plan: _StepPlan, transformer: LTXModel, ctx_pos, cfg_scale, cfg_batch, use_cfg, bf16_euler,
-                 cache_context):
+    def __init__(self, latents, plan: _StepPlan, transformer: LTXModel, ctx_pos, gd: _Guidance, bf16_euler, cache_context):
         dev = latents.device
         self.tr = transformer                       # strong reference: id(transformer) in the cache key stays unique
-        self.cfg_scale, self.cfg_batch, self.use_cfg, self.bf16_euler = cfg_scale, cfg_batch, use_cfg, bf16_euler
-        self.b = latents.shape[0]
+        self.gd, self.bf16_euler = gd, bf16_euler
         self.lat_buf = torch.empty_like(latents)
-        reps = 2 if cfg_batch else 1
-        self.ctx_a = torch.empty((reps * ctx_pos.shape[0],) + tuple(ctx_pos.shape[1:]), dtype=BF16, device=dev)   # pos (| neg)
-        self.ctx_b = torch.empty_like(ctx_pos) if (use_cfg and not cfg_batch) else None                            # neg
+        # the batched forward's rows pos (| neg) (| pos+); unbatched: pos, and neg for CFG
+        self.ctx_a = torch.empty((gd.reps * ctx_pos.shape[0],) + tuple(ctx_pos.shape[1:]), dtype=BF16, device=dev)
+        self.ctx_b = torch.empty_like(ctx_pos) if (gd.use_cfg and not gd.batched) else None
         self.clean = torch.empty_like(plan.clean) if plan.clean is not None else None
         self.mask_tok = torch.empty_like(plan.mask_tok_f32) if plan.mask_tok_f32 is not None else None
         self.tok2row = torch.empty_like(plan.tok2row)
@@ -170,10 +220,10 @@ class _StepGraph:
     def _load(self, latents, plan: _StepPlan, ctx_pos, ctx_neg, pe) -> None:
         """Refresh every per-call input in the buffers the captured kernels read."""
         self.lat_buf.copy_(latents)
-        if self.cfg_batch:
+        if self.gd.batched:
             n = ctx_pos.shape[0]
-            self.ctx_a[:n].copy_(ctx_pos)
-            self.ctx_a[n:].copy_(ctx_neg)
+            for r, c in enumerate(self.gd.context_rows(ctx_pos, ctx_neg)):
+                self.ctx_a[r * n:(r + 1) * n].copy_(c)
         else:
             self.ctx_a.copy_(ctx_pos)
             if self.ctx_b is not None:
@@ -200,15 +250,14 @@ class _StepGraph:
     def _step(self):
         ops.step_scalars(self.ts_all, self.sig_all, self.step, self.ts_buf, self.sig_buf)
         tp = TimestepPlan(self.ts_buf, self.tok2row)
-        if self.cfg_batch:
-            v = self.tr.forward_tokens(ops.latent_to_tokens(self.lat_buf, rep=2), tp, self.ctx_a, self.pe, self.kv_a)
-            v_pos, v_neg = v[:self.b], v[self.b:]
+        gd = self.gd
+        if gd.batched:
+            v_pos, v_neg, v_pert = gd.velocities(self.tr, self.lat_buf, tp, self.pe, self.ctx_a, self.kv_a, None, None, None, None)
         else:
-            tok = ops.latent_to_tokens(self.lat_buf, rep=1)
-            v_pos = self.tr.forward_tokens(tok, tp, self.ctx_a, self.pe, self.kv_a)
-            v_neg = self.tr.forward_tokens(tok, tp, self.ctx_b, self.pe, self.kv_b) if self.use_cfg else None
-        ops.cfg_euler_step(v_pos, v_neg, self.lat_buf, self.cfg_scale, 1.0, 0.0, self.clean, self.mask_tok, out=self.lat_buf,
-                           sigmas_dev=self.sig_buf, bf16_euler=self.bf16_euler)
+            v_pos, v_neg, v_pert = gd.velocities(self.tr, self.lat_buf, tp, self.pe, None, None, self.ctx_a, self.kv_a,
+                                                 self.ctx_b, self.kv_b)
+        gd.tail(v_pos, v_neg, v_pert, self.lat_buf, 1.0, 0.0, self.clean, self.mask_tok, out=self.lat_buf, sigmas_dev=self.sig_buf,
+                bf16_euler=self.bf16_euler)
 
     def run(self, latents, plan: _StepPlan, ctx_pos, ctx_neg, pe) -> torch.Tensor:
         self._load(latents, plan, ctx_pos, ctx_neg, pe)
@@ -230,10 +279,10 @@ class _StepGraph:
         return self.lat_buf.clone()
 
 
-def _eager_tail(v_pos, v_neg, latents, cfg_scale, s_bf, s, s_next, plan):
+def _eager_tail(gd: _Guidance, v_pos, v_neg, v_pert, latents, s_bf, s, s_next, plan):
     """generate.py:1283-1301: x0 = x - bf16(sigma)*v (rounded to bf16), then fp32 Euler with the
     un-rounded Python-float sigmas."""
-    x0 = ops.cfg_euler_step(v_pos, v_neg, latents, cfg_scale, s_bf, 0.0, plan.clean, plan.mask_tok_f32)
+    x0 = gd.tail(v_pos, v_neg, v_pert, latents, s_bf, 0.0, plan.clean, plan.mask_tok_f32)
     if s_next <= 0:
         return x0
     return ops.euler_only(latents, x0, s, s_next)

@@ -177,12 +177,16 @@ def generate_video(model_repo: Optional[str] = None, text_encoder_repo: Optional
                    negative_prompt_embeds: Optional[torch.Tensor] = None, text_encoder: Optional[Callable] = None,
                    noise_fn: Optional[Callable] = None, device=None, on_frames_ready: Optional[Callable] = None,
                    return_latents: bool = False, lora_in_place: Optional[bool] = None,
-                   hoist_context: bool = False) -> np.ndarray:
+                   hoist_context: bool = False, stg_scale: Optional[float] = None, stg_blocks: Optional[list] = None,
+                   stg_mode: Optional[str] = None) -> np.ndarray:
     """See the module docstring.  Returns uint8 frames (F,H,W,3) (generate.py:4195-4197).
     ``hoist_context`` (not in the reference, off by default): the part of the forward that depends on the text context only -
     caption projection and the 48 cross-attention K / V^T projections, 3.37 TFLOP that the reference recomputes in every forward
     (ltx.py:77-89, attention.py:123-126) - is computed once per denoise call and reused by every step: the same kernels on the
-    same inputs, hence the same latents bit for bit, 8-10 % less work per dev step at 512x512x33."""
+    same inputs, hence the same latents bit for bit, 8-10 % less work per dev step at 512x512x33.
+    ``stg_scale`` / ``stg_blocks`` / ``stg_mode`` (--stg-scale / --stg-blocks / --stg-mode; the reference parses and ignores
+    them): spatio-temporal guidance in every guided (denoise_dev) stage - the dev pipeline, and stage 2 with ``stage2_dev``.
+    A non-zero ``stg_scale`` on a run without a guided stage is a ValueError.  None / 0: off."""
     t_start = time.perf_counter()
     if isinstance(pipeline, str):
         pipeline = PipelineType(pipeline)
@@ -205,6 +209,12 @@ def generate_video(model_repo: Optional[str] = None, text_encoder_repo: Optional
         raise ValueError("Video conditioning is only supported in ic_lora/distilled pipelines.")
     if sigma_subsample not in ("uniform", "farthest"):
         raise ValueError(f"Unknown sigma subsample method: {sigma_subsample}")
+    stg = {"stg_scale": float(stg_scale or 0.0), "stg_blocks": stg_blocks, "stg_mode": stg_mode or "stg_v"}
+    if stg["stg_scale"] != 0.0 and is_distilled and not stage2_dev:
+        raise ValueError(f"STG (stg_scale={stg_scale}) needs a guided denoise stage: the {pipeline.value} pipeline has none "
+                         "without stage2_dev (--stage2-dev)")
+    if stg["stg_mode"] not in ("stg_v", "stg_av"):
+        raise ValueError(f"Unknown stg_mode: {stg_mode!r}")
 
     out_h, out_w = height, width
     height, width, crop = _pad_dims(height, width, 64 if is_distilled else 32)
@@ -331,7 +341,8 @@ def generate_video(model_repo: Optional[str] = None, text_encoder_repo: Optional
         with timer.phase("stage2_denoise"):
             if stage2_dev:
                 latents = denoise_dev(latents, pos2, ctx_pos, ctx_neg, tr2, torch.tensor(sig2), cfg_scale=cfg_scale,
-                                      state=state2, compile_step=compile_step, cfg_batch=cfg_batch, use_graph=compile_step, cache_context=hoist_context)
+                                      state=state2, compile_step=compile_step, cfg_batch=cfg_batch, use_graph=compile_step, cache_context=hoist_context,
+                                      **stg)
             else:
                 latents, _ = denoise_distilled(latents, pos2, ctx_pos, tr2, sig2, state=state2, compile_step=compile_step,
                                                fp32_euler=fp32_euler, use_graph=compile_step, cache_context=hoist_context)
@@ -349,7 +360,8 @@ def generate_video(model_repo: Optional[str] = None, text_encoder_repo: Optional
         latents = state.latent if state is not None else noise_fn(shape)
         with timer.phase("dev_denoise"):
             latents = denoise_dev(latents, pos, ctx_pos, ctx_neg, transformer, sigmas, cfg_scale=cfg_scale, state=state,
-                                  compile_step=compile_step, cfg_batch=cfg_batch, use_graph=compile_step, cache_context=hoist_context)
+                                  compile_step=compile_step, cfg_batch=cfg_batch, use_graph=compile_step, cache_context=hoist_context,
+                                  **stg)
 
     if return_latents:
         return latents
@@ -481,6 +493,11 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--negative-prompt-embeds", type=str, default=None)
     ap.add_argument("--synthetic", action="store_true", help="random-init weights + random text embeddings (no checkpoints offline)")
     ap.add_argument("--layers", type=int, default=48)
+    # spatio-temporal guidance (the reference's spellings and defaults; it ignores them, this port runs them)
+    ap.add_argument("--stg-scale", type=float, default=None, help="STG scale (0 / unset: off); dev pipeline or --stage2-dev")
+    ap.add_argument("--stg-blocks", type=int, nargs="*", default=None, help="Blocks whose video self-attention the STG pass skips (default: all)")
+    ap.add_argument("--stg-mode", type=str, choices=["stg_av", "stg_v"], default=None,
+                    help="stg_av acts as stg_v: the model has no audio branch")
     return ap
 
 
@@ -563,7 +580,7 @@ def main(argv: Optional[Sequence[str]] = None) -> None:
                    stage2_steps=args.stage2_steps, sigma_subsample=args.sigma_subsample, verbose=True, device=dev,
                    images=images, video_conditionings=videos, loras=args.lora, distilled_loras=args.distilled_lora,
                    conditioning_mode=args.conditioning_mode, stream=args.stream, stage2_dev=args.stage2_dev,
-                   fp32_euler=args.fp32_euler, **kw)
+                   fp32_euler=args.fp32_euler, stg_scale=args.stg_scale, stg_blocks=args.stg_blocks, stg_mode=args.stg_mode, **kw)
 
 
 if __name__ == "__main__":

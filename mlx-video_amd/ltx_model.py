@@ -24,6 +24,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import torch
 
 from . import ops
+from .guidance import BatchedPerturbationConfig, PerturbationType
 
 BF16 = torch.bfloat16
 
@@ -336,13 +337,17 @@ class LTXModel:
 
     def forward_tokens(self, latent: torch.Tensor, plan: TimestepPlan, context: torch.Tensor,
                        pe: Tuple[torch.Tensor, torch.Tensor], ctx_kv: Optional[ContextKV] = None,
-                       hidden: Optional[List[torch.Tensor]] = None) -> torch.Tensor:
+                       hidden: Optional[List[torch.Tensor]] = None,
+                       perturbations: Optional[BatchedPerturbationConfig] = None) -> torch.Tensor:
         """latent (B,N,128) bf16; context (B,S,3840) bf16; pe = (cos,sin) each (1|B,H,N,64) fp32
         (one table shared by every batch row, as in cfg_batch where it is a broadcast,
         generate.py:1196-1202).  ``ctx_kv``: a ContextKV of THIS context (prepare_context); without it the
         caption projection and the text K/V are recomputed here, as the reference does every forward.
         ``hidden``: a list that receives a copy of the residual stream (B,N,D) after every block (the reference's
-        debug taps, transformer.py; used by the per-layer parity tests)."""
+        debug taps, transformer.py; used by the per-layer parity tests).
+        ``perturbations``: one PerturbationConfig per batch row (guidance.py); in a row perturbed with SKIP_VIDEO_SELF_ATTN at
+        a block, that block's self-attention returns its value projection v instead of softmax(q k^T) v (then to_out, gate and
+        residual as usual) - STG, DESIGN.md "Spatio-temporal guidance".  None: no row is perturbed."""
         cfg = self.config
         D, H, eps = self.inner_dim, self.num_attention_heads, cfg.norm_eps
         B, N, C = latent.shape
@@ -407,6 +412,12 @@ class LTXModel:
                       torch.zeros((B, D, sp64), dtype=BF16, device=dev) if sp64 != S else torch.empty((B, D, sp64), dtype=BF16, device=dev),
                       torch.empty((B * S, D // 64), dtype=torch.float32, device=dev))
 
+        skip_rows = [[] for _ in self.blocks]          # per block: the batch rows whose self-attention is skipped (STG)
+        if perturbations is not None:
+            if len(perturbations.perturbations) != B:
+                raise ValueError(f"perturbations has {len(perturbations.perturbations)} rows, the batch {B}")
+            skip_rows = [perturbations.rows(PerturbationType.SKIP_VIDEO_SELF_ATTN, li) for li in range(len(self.blocks))]
+
         fq, fs, fp = self.fuse & 1, self.fuse & 2, (self.fuse & 6) == 6
         ts_ = self.attn_tail_split and not self.batch_invariant
         s_x, s_qk, s_q2 = (xss, qkss, q2ss) if fs else (None, None, None)
@@ -425,13 +436,21 @@ class LTXModel:
             else:
                 ops.gemm(nx, blk.wqkv[:2 * D], blk.bqkv[:2 * D], out=qk, sumsq=s_qk, split_k=sk)
                 ops.gemm(nx, blk.wqkv[2 * D:], blk.bqkv[2 * D:], out=vt, out_tokens_per_batch=N, split_k=sk)
+            skip = skip_rows[li]
             if fp:
                 ops.qknorm_rope(qk[:, D:], 1, D, blk.wkn, cos, sin, N, H, eps, sumsq=qkss[:, P:])
-                ops.flash_attn(qk[:, :D], qk[:, D:], vt, att, B, H, N, N, scale, q_sumsq=qkss, q_norm_weight=blk.wqn,
-                               cos=cos, sin=sin, eps=eps, tail_split=ts_)
             else:
                 ops.qknorm_rope(qk, 2, D, blk.wqkn, cos, sin, N, H, eps, sumsq=s_qk)
-                ops.flash_attn(qk[:, :D], qk[:, D:], vt, att, B, H, N, N, scale, tail_split=ts_)
+            # attention over each maximal run of rows that keep it (all B rows in one launch when nothing is skipped)
+            for r0, r1 in _runs(B, skip):
+                t0, t1 = r0 * N, r1 * N
+                if fp:
+                    ops.flash_attn(qk[t0:t1, :D], qk[t0:t1, D:], vt[r0:r1], att[t0:t1], r1 - r0, H, N, N, scale,
+                                   q_sumsq=qkss[t0:t1], q_norm_weight=blk.wqn, cos=cos, sin=sin, eps=eps, tail_split=ts_)
+                else:
+                    ops.flash_attn(qk[t0:t1, :D], qk[t0:t1, D:], vt[r0:r1], att[t0:t1], r1 - r0, H, N, N, scale, tail_split=ts_)
+            if skip:          # STG: the skipped rows' attention output is their value projection, v = (V^T)^T
+                ops.attn_value_passthrough(vt, att, B, N, sum(1 << r for r in skip))
             ops.gemm(att, blk.wo, blk.bo, epilogue=ops.EPI_BIAS_GATE_RES, out=x, resid=x,
                      gate=mod[:, 2], gate_row=tok2row, gate_stride=ms, sumsq=s_x, split_k=sk)
             # text cross-attention (transformer.py:257-261)
@@ -457,7 +476,8 @@ class LTXModel:
         v = ops.gemm(nx, self.out_w, self.out_b, split_k=sk)
         return v.reshape(B, N, cfg.out_channels)
 
-    def __call__(self, video: Optional[Modality] = None, audio: Optional[Modality] = None):
+    def __call__(self, video: Optional[Modality] = None, audio: Optional[Modality] = None,
+                 perturbations: Optional[BatchedPerturbationConfig] = None):
         if audio is not None:
             raise ValueError("Audio is not enabled for this model")      # ltx.py:468-469
         if video is None:
@@ -472,8 +492,24 @@ class LTXModel:
             pe = precompute_freqs_cis(video.positions, self.inner_dim, self.positional_embedding_theta,
                                       self.positional_embedding_max_pos, self.num_attention_heads)
         plan = TimestepPlan.from_timesteps(video.timesteps.to(BF16))
-        v = self.forward_tokens(lat.to(BF16).contiguous(), plan, video.context.to(BF16).contiguous(), pe)
+        v = self.forward_tokens(lat.to(BF16).contiguous(), plan, video.context.to(BF16).contiguous(), pe,
+                                perturbations=perturbations)
         return v, None
+
+
+def _runs(B: int, skip: Sequence[int]) -> List[Tuple[int, int]]:
+    """Maximal [r0, r1) runs of the rows in range(B) that are not in ``skip``."""
+    runs, r0 = [], None
+    for r in range(B):
+        if r in skip:
+            if r0 is not None:
+                runs.append((r0, r))
+            r0 = None
+        elif r0 is None:
+            r0 = r
+    if r0 is not None:
+        runs.append((r0, B))
+    return runs
 
 
 class X0Model:
@@ -484,8 +520,9 @@ class X0Model:
     def __init__(self, velocity_model: LTXModel):
         self.velocity_model = velocity_model
 
-    def __call__(self, video: Optional[Modality] = None, audio: Optional[Modality] = None):
-        v, _ = self.velocity_model(video, audio)
+    def __call__(self, video: Optional[Modality] = None, audio: Optional[Modality] = None,
+                 perturbations: Optional[BatchedPerturbationConfig] = None):
+        v, _ = self.velocity_model(video, audio, perturbations=perturbations)
         if v is None:
             return None, None
         lat = video.latent.to(BF16)

@@ -10,7 +10,7 @@ from typing import Optional, Tuple
 import torch
 
 from . import _lib
-from ._lib import AttnArgs, GemmArgs, check
+from ._lib import AttnArgs, GemmArgs, StepArgs, check
 
 EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_SILU, EPI_BIAS_GATE_RES, EPI_BIAS_RES, EPI_SCALE_RES = 0, 1, 2, 3, 4, 5
 BF16 = torch.bfloat16
@@ -336,6 +336,61 @@ def cfg_euler_step(v_pos: torch.Tensor, v_neg: Optional[torch.Tensor], latent: t
     check(_lib.load().ltxk_cfg_euler_step(_p(v_pos), _p(v_neg), _p(latent), _p(out), _p(clean), _p(mask_tok),
                                           B, C, S, cfg_scale, sigma, sigma_next, int(bf16_euler), _stream()),
           "ltxk_cfg_euler_step")
+    return out
+
+
+def guided_euler_step(v_pos: torch.Tensor, v_neg: Optional[torch.Tensor], v_pert: Optional[torch.Tensor], latent: torch.Tensor,
+                      cfg_scale: float, stg_scale: float, sigma: float, sigma_next: float, clean: Optional[torch.Tensor] = None,
+                      mask_tok: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                      sigmas_dev: Optional[torch.Tensor] = None, bf16_euler: bool = False) -> torch.Tensor:
+    """``cfg_euler_step`` with the STG term (ltxk_guided_euler_step): v_pert (B,S,C) is the velocity of the perturbed
+    forward; v = bf16(g + bf16(stg_scale * bf16(v_pos - v_pert))) with g the CFG-guided velocity.  ``v_pert=None``: the
+    launch cfg_euler_step makes."""
+    _req(latent, BF16, "guided_euler_step.latent")
+    _req(v_pos, BF16, "guided_euler_step.v_pos")
+    B, C = latent.shape[:2]
+    S = latent.numel() // (B * C)
+    for name, t in (("v_pos", v_pos), ("v_neg", v_neg), ("v_pert", v_pert)):
+        if t is None:
+            continue
+        _req(t, BF16, f"guided_euler_step.{name}")
+        if t.numel() != B * S * C or not t.is_contiguous():
+            raise ValueError(f"guided_euler_step: {name} must be a contiguous (B,S,C) = ({B},{S},{C}) tensor, got {tuple(t.shape)}")
+    if not latent.is_contiguous():
+        raise ValueError("guided_euler_step: latent must be contiguous")
+    if (clean is None) != (mask_tok is None):
+        raise ValueError("guided_euler_step: clean and mask_tok must both be given or both be None")
+    if clean is not None:
+        _req(clean, BF16, "guided_euler_step.clean")
+        _req(mask_tok, torch.float32, "guided_euler_step.mask_tok")
+    if sigmas_dev is not None:
+        _req(sigmas_dev, torch.float32, "guided_euler_step.sigmas_dev")
+    if out is None:
+        out = torch.empty_like(latent)
+    a = StepArgs()
+    a.v_pos, a.v_neg, a.v_pert, a.latent, a.out = _p(v_pos), _p(v_neg), _p(v_pert), _p(latent), _p(out)
+    a.clean, a.mask, a.sigmas_dev = _p(clean), _p(mask_tok), _p(sigmas_dev)
+    a.B, a.C, a.S = B, C, S
+    a.cfg_scale, a.stg_scale, a.sigma, a.sigma_next = cfg_scale, stg_scale, sigma, sigma_next
+    a.flags = int(bf16_euler)
+    check(_lib.load().ltxk_guided_euler_step(ctypes.byref(a), _stream()), "ltxk_guided_euler_step")
+    return out
+
+
+def attn_value_passthrough(vt: torch.Tensor, out: torch.Tensor, B: int, T: int, row_mask: int) -> torch.Tensor:
+    """STG's skipped self-attention: rows b with bit b of ``row_mask`` set get out[b*T+t, :D] = vt[b, :, t] (bit-exact
+    transpose of the (B, D, ldvt) V^T buffer into the (B*T, >=D) token-major attention output).  Other rows untouched."""
+    _req(vt, BF16, "attn_value_passthrough.vt")
+    _req(out, BF16, "attn_value_passthrough.out")
+    if vt.dim() != 3 or vt.shape[0] < B or vt.stride(-1) != 1 or vt.stride(0) != vt.shape[1] * vt.stride(1):
+        raise ValueError(f"attn_value_passthrough: vt must be a (B, D, ldvt) buffer with unit inner stride, got {tuple(vt.shape)}")
+    D = vt.shape[1]
+    if vt.shape[2] < T or out.dim() != 2 or out.stride(-1) != 1 or out.shape[0] < B * T or out.shape[1] < D:
+        raise ValueError(f"attn_value_passthrough: shapes do not fit B={B} T={T} D={D}: vt {tuple(vt.shape)}, out {tuple(out.shape)}")
+    if not 0 <= int(row_mask) < (1 << 64):
+        raise ValueError("attn_value_passthrough: row_mask must fit 64 bits")
+    check(_lib.load().ltxk_attn_value_passthrough(_p(vt), vt.stride(1), _p(out), out.stride(0), B, D, T, int(row_mask), _stream()),
+          "ltxk_attn_value_passthrough")
     return out
 
 
