@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define LTXK_VERSION 402
+#define LTXK_VERSION 403
 
 #define LTXK_OK 0
 #define LTXK_EINVAL (-1)   /* bad argument (shape / alignment / null pointer) */
@@ -110,6 +110,44 @@ struct ltxk_gemm_plan {   /* a struct tag only: the name is also the function's 
 };
 
 int ltxk_gemm_plan(const ltxk_gemm_args* args, struct ltxk_gemm_plan* plan);
+
+/* Grouped GEMM: G problems that share A, M, N, K and the split output layout, as ONE persistent launch of 256-column big
+ * tiles - the text k | V^T projections of every transformer block (attention.py:123-125 on the text side), none of which
+ * depends on the token stream.  Group g computes exactly what
+ *   ltxk_gemm_bf16{A, W[g], bias[g], out + g*out_gstride, out2 + g*out2_gstride, sumsq + g*sumsq_gstride, n_split, EPI_BIAS}
+ * computes without a workspace, bit for bit (same K order, same MFMA, same rounding points, same sumsq order).
+ * Per-group operands: W and bias are DEVICE arrays of G device pointers (weights stay wherever they live; the table is read
+ * by the kernel, never by the host, so every W[g] must be 16-byte aligned and every bias[g] 8-byte aligned on the caller's
+ * word); the outputs are one buffer each with a group stride in ELEMENTS.
+ * Launch form: min(tiles, CUs) workgroups, each walking the static list t = workgroup, workgroup + grid, ... of the G x row
+ * tiles x column tiles (groups in order, the single launch's XCD-aware tile order inside a group).  Tiles are independent:
+ * no counter, no hand-over between workgroups.  Rows beyond the last whole row tile run on a shorter tile body.
+ * Needs n_split > 0 (a multiple of 256), N a multiple of 256, K a multiple of 64, EPI_BIAS.                              */
+typedef struct ltxk_gemm_grouped_args {
+  const void* A;             /* (M,K) bf16, row stride lda; shared by every group                  */
+  const void* const* W;      /* device array of G pointers to (N,K) bf16 row-major panels          */
+  const void* const* bias;   /* device array of G pointers to (N) bf16, or NULL: no bias           */
+  void* out;                 /* group g: (M,n_split) bf16 row stride ldo at out + g*out_gstride    */
+  void* out2;                /* group g: (B,N-n_split,ldo2) bf16 at out2 + g*out2_gstride          */
+  float* sumsq;              /* group g: (M,sumsq_ld) fp32 at sumsq + g*sumsq_gstride, or NULL     */
+  int64_t out_gstride, out2_gstride, sumsq_gstride;   /* in elements                               */
+  int32_t G, M, N, K;
+  int32_t lda, ldo, ldo2, sumsq_ld;
+  int32_t n_split, out_tokens_per_batch;
+} ltxk_gemm_grouped_args;
+
+int ltxk_gemm_bf16_grouped(const ltxk_gemm_grouped_args* args, void* stream);
+/* sizeof(ltxk_gemm_grouped_args) in this build (the struct has an entry of its own; the index list above is closed).     */
+int ltxk_gemm_grouped_args_sizeof(void);
+
+/* The tiling ltxk_gemm_bf16_grouped takes (host only, nothing is launched or read).  tile_rows: 320 or 256; rem_rows: the
+ * height of the body that runs the rows left after the whole row tiles (0: none; 128, 256 or tile_rows).                 */
+struct ltxk_gemm_grouped_plan {
+  int32_t tile_rows, rem_rows;
+  int32_t row_tiles, col_tiles;  /* per group, the remainder row tile included                      */
+  int32_t tiles;                 /* G * row_tiles * col_tiles                                        */
+};
+int ltxk_gemm_grouped_plan(const ltxk_gemm_grouped_args* args, struct ltxk_gemm_grouped_plan* plan);
 
 /* ---------------------------------------------------------------------------------------
  * Fused attention: replaces mx.fast.scaled_dot_product_attention (attention.py:47) incl. the
@@ -196,6 +234,13 @@ int ltxk_qknorm_rope(void* buf, int32_t ld, int32_t M, int32_t nseg, int32_t D,
 int ltxk_qknorm_rope_ss(void* buf, int32_t ld, int32_t M, int32_t nseg, int32_t D,
                         const void* weight, const float* cos, const float* sin,
                         int32_t T, int32_t H, float eps, const float* sumsq, int32_t sumsq_ld, void* stream);
+
+/* The q/k RMSNorm above without rotation over G stacked buffers in one launch (the text-side k of every block): group g is
+ * the (M,D) rows at buf + g*buf_gstride (row stride ld) with weight row g of the (G,D) table and the statistics at
+ * sumsq + g*sumsq_gstride; strides in elements.  Same bits as G calls of the single-buffer form with nseg = 1, no cos/sin. */
+int ltxk_qknorm_grouped_ss(void* buf, int64_t buf_gstride, int32_t ld, int32_t G, int32_t M, int32_t D,
+                           const void* weight, int32_t H, float eps, const float* sumsq, int64_t sumsq_gstride,
+                           int32_t sumsq_ld, void* stream);
 
 /* Sinusoidal timestep projection: utils.py:486-526 (flip_sin_to_cos, shift 0), applied to
  * bf16(t*mult) (ltx.py:68: timestep*timestep_scale_multiplier stays in the model dtype).

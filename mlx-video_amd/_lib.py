@@ -33,6 +33,22 @@ class GemmPlan(Structure):
     ]
 
 
+class GemmGroupedArgs(Structure):
+    _fields_ = [
+        ("A", c_void_p), ("W", c_void_p), ("bias", c_void_p), ("out", c_void_p), ("out2", c_void_p), ("sumsq", c_void_p),
+        ("out_gstride", c_int64), ("out2_gstride", c_int64), ("sumsq_gstride", c_int64),
+        ("G", c_int32), ("M", c_int32), ("N", c_int32), ("K", c_int32),
+        ("lda", c_int32), ("ldo", c_int32), ("ldo2", c_int32), ("sumsq_ld", c_int32),
+        ("n_split", c_int32), ("out_tokens_per_batch", c_int32),
+    ]
+
+
+class GemmGroupedPlan(Structure):
+    _fields_ = [
+        ("tile_rows", c_int32), ("rem_rows", c_int32), ("row_tiles", c_int32), ("col_tiles", c_int32), ("tiles", c_int32),
+    ]
+
+
 class AttnArgs(Structure):
     _fields_ = [
         ("q", c_void_p), ("k", c_void_p), ("vt", c_void_p), ("out", c_void_p),
@@ -71,6 +87,11 @@ SIGNATURES = {
     "ltxk_abi_sizeof": (c_int32, [c_int32]),
     "ltxk_gemm_bf16": (c_int32, [POINTER(GemmArgs), c_void_p]),
     "ltxk_gemm_plan": (c_int32, [POINTER(GemmArgs), POINTER(GemmPlan)]),
+    "ltxk_gemm_bf16_grouped": (c_int32, [POINTER(GemmGroupedArgs), c_void_p]),
+    "ltxk_gemm_grouped_args_sizeof": (c_int32, []),
+    "ltxk_gemm_grouped_plan": (c_int32, [POINTER(GemmGroupedArgs), POINTER(GemmGroupedPlan)]),
+    "ltxk_qknorm_grouped_ss": (c_int32, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_float,
+                                         c_void_p, c_int64, c_int32, c_void_p]),
     "ltxk_flash_attn": (c_int32, [POINTER(AttnArgs), c_void_p]),
     "ltxk_flash_attn_bf16": (c_int32, [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32,
                                        c_int32, c_int32, c_int32, c_int32, c_float, c_void_p]),
@@ -145,6 +166,10 @@ def _open(path: str) -> ctypes.CDLL:
         if lib.ltxk_abi_sizeof(which) != ctypes.sizeof(st):
             raise LtxkError(f"{path} is stale: sizeof({st.__name__}) is {lib.ltxk_abi_sizeof(which)} in the library, "
                             f"{ctypes.sizeof(st)} in this binding; rebuild it (make -C mlx-video_amd/csrc)")
+    # (structs added after the ltxk_abi_sizeof index list was closed report their size through an entry of their own)
+    if lib.ltxk_gemm_grouped_args_sizeof() != ctypes.sizeof(GemmGroupedArgs):
+        raise LtxkError(f"{path} is stale: sizeof(GemmGroupedArgs) is {lib.ltxk_gemm_grouped_args_sizeof()} in the library, "
+                        f"{ctypes.sizeof(GemmGroupedArgs)} in this binding; rebuild it (make -C mlx-video_amd/csrc)")
     return lib
 
 

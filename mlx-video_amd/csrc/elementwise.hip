@@ -211,7 +211,11 @@ __global__ __launch_bounds__(256) void qknorm_rope_kernel(
 __global__ __launch_bounds__(256) void qknorm_rope_ss_kernel(
     bf16* __restrict__ buf, int ld, int M, int nseg, int D, const bf16* __restrict__ weight,
     const float* __restrict__ cosb, const float* __restrict__ sinb, int T, int H, float eps,
-    const float* __restrict__ sumsq, int ss_ld, int NP) {
+    const float* __restrict__ sumsq, int ss_ld, int NP, size_t buf_gs, size_t w_gs, size_t ss_gs) {
+  // blockIdx.y = group (ltxk_qknorm_grouped_ss: the text k of every block in one launch); a single call has one group
+  buf += blockIdx.y * buf_gs;
+  weight += blockIdx.y * w_gs;
+  sumsq += blockIdx.y * ss_gs;
   const int lane = threadIdx.x & 63;
   const int npass = (H + 7) >> 3;
   const int item = blockIdx.x * ROWS_PER_BLOCK + (threadIdx.x >> 6);
@@ -568,8 +572,26 @@ extern "C" int ltxk_qknorm_rope_ss(void* buf, int32_t ld, int32_t M, int32_t nse
   const int npass = (H + 7) / 8;
   const long long items = (long long)M * nseg * npass;
   hipLaunchKernelGGL(qknorm_rope_ss_kernel, dim3((unsigned)((items + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK)), dim3(256), 0, (hipStream_t)stream,
-                     (bf16*)buf, ld, M, nseg, D, (const bf16*)weight, cos, sin, T, H, eps, sumsq, sumsq_ld, D / 64);
+                     (bf16*)buf, ld, M, nseg, D, (const bf16*)weight, cos, sin, T, H, eps, sumsq, sumsq_ld, D / 64, (size_t)0, (size_t)0, (size_t)0);
   LTXK_CHECK_LAUNCH("ltxk_qknorm_rope_ss");
+  return LTXK_OK;
+}
+
+extern "C" int ltxk_qknorm_grouped_ss(void* buf, int64_t buf_gstride, int32_t ld, int32_t G, int32_t M, int32_t D,
+                                      const void* weight, int32_t H, float eps, const float* sumsq, int64_t sumsq_gstride,
+                                      int32_t sumsq_ld, void* stream) {
+  LTXK_CHECK_ARG(buf && weight && sumsq && M > 0 && G > 0 && G <= 65535, "ltxk_qknorm_grouped_ss: null/empty input (G=%d M=%d)", G, M);
+  LTXK_CHECK_ARG(D == H * 128 && H % 4 == 0, "ltxk_qknorm_grouped_ss: need D == H*128, H %% 4 == 0 (D=%d H=%d)", D, H);
+  LTXK_CHECK_ARG(ld >= D && ld % 8 == 0 && ((uintptr_t)buf & 15) == 0 && buf_gstride % 8 == 0, "ltxk_qknorm_grouped_ss: ld=%d must be >= D and a multiple of 8, buf 16-byte aligned, group stride a multiple of 8", ld);
+  LTXK_CHECK_ARG(sumsq_ld >= D / 64, "ltxk_qknorm_grouped_ss: sumsq_ld >= D/64");
+  LTXK_CHECK_ARG(G == 1 || (buf_gstride >= (int64_t)(M - 1) * ld + D && sumsq_gstride >= (int64_t)(M - 1) * sumsq_ld + D / 64),
+                 "ltxk_qknorm_grouped_ss: a group stride is smaller than one group");
+  const int npass = (H + 7) / 8;
+  const long long items = (long long)M * npass;
+  hipLaunchKernelGGL(qknorm_rope_ss_kernel, dim3((unsigned)((items + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK), (unsigned)G), dim3(256), 0,
+                     (hipStream_t)stream, (bf16*)buf, ld, M, 1, D, (const bf16*)weight, (const float*)nullptr, (const float*)nullptr, 1, H, eps,
+                     sumsq, sumsq_ld, D / 64, (size_t)buf_gstride, (size_t)D, (size_t)sumsq_gstride);
+  LTXK_CHECK_LAUNCH("ltxk_qknorm_grouped_ss");
   return LTXK_OK;
 }
 

@@ -4,6 +4,7 @@
 // transformer.py:254,257,347 as epilogues.
 #include "gemm_core.h"
 #include <stdlib.h>
+#include <atomic>
 #include <utility>
 
 #ifndef LTXK_DEFER_GROUPS
@@ -1087,6 +1088,151 @@ static int big_tile_choice(int M, int N) {
   return 0;
 }
 
+// ---- grouped persistent launch: G split-output GEMMs over one A (the text k | V^T projections of all blocks) -------------
+// One launch of M=2048, N=8192 is quantised either way: 8 x 32 tiles of 256 rows fill the 256 CUs exactly once on the
+// dearer tile, 7 x 32 tiles of 320 rows leave 32 CUs idle; and each launch pays its own fill, cold prologue and store tail.
+// Over G launches' worth of tiles neither matters: min(tiles, CUs) workgroups each walk the static list
+// t = blockIdx.x, blockIdx.x + gridDim.x, ... of the G x RT x CT tiles, group-major (one group's weight panel is streamed
+// once), map_tile order inside a group.  Tiles are independent - no tile counter, no hand-over between workgroups, no wait
+// on another workgroup of any kind.  With RT*CT and gridDim.x multiples of 8 a workgroup keeps its XCD's column band in
+// every group, so an XCD's 32 workgroups still share A rows and W columns as in the single launch.
+// The rows left after the whole row tiles run on a body of their own height (RR row blocks per wave: 128 or 256 rows)
+// instead of a full tile of which most MFMAs multiply clamped rows.  At M=2048 on 320-row tiles (6 whole + 128 rows, CT=32:
+// 224 tiles per group, 256 workgroups) workgroup w's k-th tile is tile (w + 32k) % 224 of its group: it meets every row
+// tile equally often (6 times each over 48 groups), so the static lists are balanced by cost without a cost table.
+struct GroupedParams {
+  GemmParams p;                       // A, dims, strides; W / bias / out / out2 / sumsq are those of group 0
+  const bf16* const* w_tab;           // device: G weight panels
+  const bf16* const* b_tab;           // device: G bias rows, or nullptr
+  long out_gs, out2_gs, ss_gs;        // group strides in elements
+  int tiles_per_group, total;         // RT * CT, G * RT * CT
+  int full_rt;                        // row tiles below this index are whole (RB blocks); the one at it, if any, runs RR
+};
+
+// a wave-uniform pointer the compiler holds in vector registers, moved to scalar ones
+__device__ __forceinline__ const bf16* uniform_gptr(const bf16* ptr) {
+  const uint64_t u = (uint64_t)ptr;
+  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)u), hi = __builtin_amdgcn_readfirstlane((uint32_t)(u >> 32));
+  return (const bf16*)(((uint64_t)hi << 32) | lo);
+}
+
+template <int RB, int RR>
+__global__ __launch_bounds__(512) void gemm_grouped_big_kernel(GroupedParams gp) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  for (int t = blockIdx.x; t < gp.total; t += gridDim.x) {
+    // (integer division runs on the vector ALU: its wave-uniform results go back to scalar registers by hand)
+    const int g = __builtin_amdgcn_readfirstlane(t / gp.tiles_per_group), i = t - g * gp.tiles_per_group;
+    int rt, ct;
+    map_tile(i, gp.p.RT, gp.p.CT, rt, ct);
+    rt = __builtin_amdgcn_readfirstlane(rt);
+    ct = __builtin_amdgcn_readfirstlane(ct);
+    GemmParams p = gp.p;
+    // (a table entry comes back from a vector load; the LDS-DMA takes its base from scalar registers)
+    p.W = uniform_gptr(gp.w_tab[g]);
+    p.bias = gp.b_tab ? uniform_gptr(gp.b_tab[g]) : nullptr;
+    p.out += (size_t)g * gp.out_gs;
+    p.out2 += (size_t)g * gp.out2_gs;
+    if (p.sumsq) p.sumsq += (size_t)g * gp.ss_gs;
+    const int m0 = rt * BigGeom<RB>::BM, n0 = ct * BIG_BN;
+    // the previous tile's last K-step may still be read by a slower wave where this tile's first stage lands
+    if (t != (int)blockIdx.x) __syncthreads();
+    if (RR != RB && rt == gp.full_rt) {
+      if (n0 < p.n_split) gemm_big_tile<LTXK_EPI_BIAS, false, RR>(p, smem, m0, n0, wave, lane);
+      else gemm_big_tile<LTXK_EPI_BIAS, true, RR>(p, smem, m0, n0, wave, lane);
+    } else {
+      if (n0 < p.n_split) gemm_big_tile<LTXK_EPI_BIAS, false, RB>(p, smem, m0, n0, wave, lane);
+      else gemm_big_tile<LTXK_EPI_BIAS, true, RB>(p, smem, m0, n0, wave, lane);
+    }
+  }
+}
+
+// hipFuncSetAttribute once per (kernel, device): a bit per device, set after the first success.  (The older launchers keep a
+// thread_local "last device", which sets the attribute again for every thread and every device switch.)
+static int ensure_dyn_lds(const void* kern, int bytes, std::atomic<uint64_t>& done, const char* who) {
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  const uint64_t bit = 1ull << (dev & 63);
+  if (done.load(std::memory_order_acquire) & bit) return LTXK_OK;
+  hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  if (e != hipSuccess) {
+    ltxk_set_error("%s: hipFuncSetAttribute: %s", who, hipGetErrorString(e));
+    return LTXK_ELAUNCH;
+  }
+  if (dev < 64) done.fetch_or(bit, std::memory_order_release);
+  return LTXK_OK;
+}
+
+template <int RB, int RR>
+static int launch_grouped(const GroupedParams& gp, int workgroups, hipStream_t stream) {
+  constexpr int LDS = BigGeom<RB>::LDS;        // RR <= RB: the remainder body's two stages fit inside
+  static_assert(RR <= RB && RR >= 2, "remainder body: 2..RB row blocks (the loader issues 3 pieces per MFMA row)");
+  auto kern = gemm_grouped_big_kernel<RB, RR>;
+  static std::atomic<uint64_t> attr_set{0};
+  const int rc = ensure_dyn_lds((const void*)kern, LDS, attr_set, "ltxk_gemm_bf16_grouped");
+  if (rc != LTXK_OK) return rc;
+  hipLaunchKernelGGL(kern, dim3(workgroups), dim3(512), LDS, stream, gp);
+  LTXK_CHECK_LAUNCH("ltxk_gemm_bf16_grouped");
+  return LTXK_OK;
+}
+
+// Tile of the grouped launch, priced over ALL groups' tiles: (rounds of 256 workgroups over G x tiles) x (mean tile cost),
+// tile cost = 0.78 x rows + 38 - the line through the two measured big tiles (320 rows: 0.90 x 320, 256 rows: 0.93 x 256,
+// big_tile_choice above), which prices a 128-row remainder body at 138 (its W fragment reads do not shrink with its rows).
+// The 256-row tile only where it needs no remainder.  M=2048: 6 x 320 + 128 -> 320; M=1024: 4 x 256 (3 x 320 + 64 rows on a
+// 128-row body costs more) -> 256.
+struct GroupedForm { int rb, rr, full_rt, RT, CT; };
+static GroupedForm grouped_tile_choice(int G, int M, int N) {
+  const long CT = N / BIG_BN;
+  auto cost = [](int rows) { return 78L * rows + 3800; };
+  auto rem_blocks = [](int rem, int rb) { return rem == 0 ? 0 : (rem <= 128 ? 2 : (rem <= 256 && rb > 4 ? 4 : rb)); };
+  auto form = [&](int rb) {
+    const int bm = 64 * rb, full = M / bm, rr = rem_blocks(M - full * bm, rb);
+    return GroupedForm{rb, rr ? rr : rb, rr ? full : -1, full + (rr ? 1 : 0), (int)CT};
+  };
+  auto total = [&](const GroupedForm& f) {
+    const long per_col = (long)(f.full_rt < 0 ? f.RT : f.full_rt) * cost(64 * f.rb) + (f.full_rt < 0 ? 0 : cost(64 * f.rr));
+    const long tiles = (long)G * f.RT * CT, rounds = (tiles + 255) / 256;
+    return rounds * (per_col * CT * G / tiles);
+  };
+  const GroupedForm f5 = form(5), f4 = form(4);
+  const int env = LTXK_AB_INT("LTXK_GEMM_GROUPED_RB", 0);       // A/B build: 5, or 4 where M is a whole number of 256-row tiles, forces the tile
+  GroupedForm f = ((env == 4 && M % 256 == 0) || (env == 0 && M % 256 == 0 && total(f4) < total(f5))) ? f4 : f5;
+  if (LTXK_AB_INT("LTXK_GEMM_GROUPED_FULLREM", 0) && f.full_rt >= 0) f.rr = f.rb;     // A/B build: the remainder at full tile cost
+  return f;
+}
+
+static int grouped_form(const ltxk_gemm_grouped_args* a, GroupedForm& f) {
+  LTXK_CHECK_ARG(a != nullptr, "ltxk_gemm_bf16_grouped: null args");
+  LTXK_CHECK_ARG(a->A && a->W && a->out && a->out2, "ltxk_gemm_bf16_grouped: null A/W/out/out2");
+  LTXK_CHECK_ARG(a->G > 0 && a->G <= 4096 && a->M > 0 && a->N > 0 && a->K > 0, "ltxk_gemm_bf16_grouped: bad dims G=%d M=%d N=%d K=%d", a->G, a->M, a->N, a->K);
+  LTXK_CHECK_ARG(a->K % GEMM_BK == 0 && a->K <= (1 << 20), "ltxk_gemm_bf16_grouped: K=%d must be a multiple of %d", a->K, GEMM_BK);
+  LTXK_CHECK_ARG(a->N % BIG_BN == 0, "ltxk_gemm_bf16_grouped: N=%d must be a multiple of %d", a->N, BIG_BN);
+  LTXK_CHECK_ARG(a->lda >= a->K && a->lda % 8 == 0, "ltxk_gemm_bf16_grouped: lda=%d (K=%d) must be >=K, multiple of 8", a->lda, a->K);
+  LTXK_CHECK_ARG(((uintptr_t)a->A & 15) == 0 && ((uintptr_t)a->out & 7) == 0 && ((uintptr_t)a->out2 & 7) == 0 &&
+                 ((uintptr_t)a->W & 7) == 0 && ((uintptr_t)a->bias & 7) == 0,
+                 "ltxk_gemm_bf16_grouped: A must be 16-byte aligned, out/out2 and the pointer tables 8-byte aligned");
+  LTXK_CHECK_ARG(a->n_split > 0 && a->n_split % 256 == 0 && a->n_split < a->N, "ltxk_gemm_bf16_grouped: n_split=%d must be a multiple of 256 below N=%d", a->n_split, a->N);
+  LTXK_CHECK_ARG(a->out_tokens_per_batch > 0 && a->M % a->out_tokens_per_batch == 0, "ltxk_gemm_bf16_grouped: out_tokens_per_batch must divide M=%d", a->M);
+  LTXK_CHECK_ARG(a->ldo2 >= a->out_tokens_per_batch && a->ldo2 % 4 == 0, "ltxk_gemm_bf16_grouped: transposed ldo2=%d", a->ldo2);
+  LTXK_CHECK_ARG(a->ldo >= a->n_split && a->ldo % 4 == 0, "ltxk_gemm_bf16_grouped: ldo=%d (n_split=%d)", a->ldo, a->n_split);
+  // a group's outputs must not reach into the next group's, and must stay 8-byte (sumsq: 4-byte) aligned
+  LTXK_CHECK_ARG(a->out_gstride % 4 == 0 && a->out2_gstride % 4 == 0, "ltxk_gemm_bf16_grouped: group strides must be multiples of 4 elements");
+  if (a->G > 1) {
+    LTXK_CHECK_ARG(a->out_gstride >= (int64_t)(a->M - 1) * a->ldo + a->n_split, "ltxk_gemm_bf16_grouped: out_gstride smaller than one group's output");
+    LTXK_CHECK_ARG(a->out2_gstride >= ((int64_t)(a->M / a->out_tokens_per_batch) * (a->N - a->n_split) - 1) * a->ldo2 + a->out_tokens_per_batch,
+                   "ltxk_gemm_bf16_grouped: out2_gstride smaller than one group's transposed output");
+  }
+  if (a->sumsq) {
+    LTXK_CHECK_ARG(a->sumsq_ld >= a->n_split / 64 && ((uintptr_t)a->sumsq & 3) == 0, "ltxk_gemm_bf16_grouped: sumsq_ld >= n_split/64, 4-byte aligned");
+    LTXK_CHECK_ARG(a->G == 1 || a->sumsq_gstride >= (int64_t)(a->M - 1) * a->sumsq_ld + a->n_split / 64, "ltxk_gemm_bf16_grouped: sumsq_gstride smaller than one group's statistics");
+  }
+  f = grouped_tile_choice(a->G, a->M, a->N);
+  LTXK_CHECK_ARG((long)a->G * f.RT * f.CT < (1L << 30), "ltxk_gemm_bf16_grouped: too many tiles");
+  return LTXK_OK;
+}
+
 // The launch form of one ltxk_gemm_bf16 call: the argument checks, then big tile / 160-row family (pick_tile) / split-K slices.
 // ltxk_gemm_bf16 launches what this decides and ltxk_gemm_plan reports it, so the two cannot drift apart.
 struct GemmForm {
@@ -1258,4 +1404,54 @@ extern "C" int ltxk_gemm_bf16(const ltxk_gemm_args* a, void* stream) {
     return LTXK_OK;
   }
   return f.nt == 2 ? dispatch_tt<2>(p, f.tt, a->epilogue, trans, st) : dispatch_tt<4>(p, f.tt, a->epilogue, trans, st);
+}
+
+extern "C" int ltxk_gemm_grouped_args_sizeof(void) { return (int)sizeof(ltxk_gemm_grouped_args); }
+
+extern "C" int ltxk_gemm_grouped_plan(const ltxk_gemm_grouped_args* a, struct ltxk_gemm_grouped_plan* plan) {
+  using namespace ltxk;
+  LTXK_CHECK_ARG(plan != nullptr, "ltxk_gemm_grouped_plan: null plan");
+  GroupedForm f;
+  const int rc = grouped_form(a, f);
+  if (rc != LTXK_OK) return rc;
+  plan->tile_rows = 64 * f.rb;
+  plan->rem_rows = f.full_rt < 0 ? 0 : 64 * f.rr;
+  plan->row_tiles = f.RT;
+  plan->col_tiles = f.CT;
+  plan->tiles = a->G * f.RT * f.CT;
+  return LTXK_OK;
+}
+
+extern "C" int ltxk_gemm_bf16_grouped(const ltxk_gemm_grouped_args* a, void* stream) {
+  using namespace ltxk;
+  GroupedForm f;
+  const int rc = grouped_form(a, f);
+  if (rc != LTXK_OK) return rc;
+  GroupedParams gp;
+  GemmParams& p = gp.p;
+  p.A = (const bf16*)a->A; p.W = nullptr; p.bias = nullptr;
+  p.out = (bf16*)a->out; p.resid = nullptr; p.gate = nullptr; p.gate_row = nullptr;
+  p.M = a->M; p.N = a->N; p.K = a->K; p.lda = a->lda; p.ldo = a->ldo; p.ldr = 0;
+  p.gate_stride = 0; p.T = a->out_tokens_per_batch; p.alpha = 1.f; p.wide = 0;
+  p.out2 = (bf16*)a->out2; p.n_split = a->n_split; p.ldo2 = a->ldo2;
+  p.sumsq = a->sumsq; p.sumsq_ld = a->sumsq_ld;
+  p.RT = f.RT; p.CT = f.CT;
+  p.part = nullptr; p.ksteps = a->K / GEMM_BK;
+  gp.w_tab = (const bf16* const*)a->W;
+  gp.b_tab = (const bf16* const*)a->bias;
+  gp.out_gs = a->out_gstride; gp.out2_gs = a->out2_gstride; gp.ss_gs = a->sumsq_gstride;
+  gp.tiles_per_group = f.RT * f.CT;
+  gp.total = a->G * gp.tiles_per_group;
+  gp.full_rt = f.full_rt;
+  int dev = 0, cus = 0;
+  (void)hipGetDevice(&dev);
+  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+  const int wgs = gp.total < cus ? gp.total : cus;      // one workgroup per CU (its LDS holds one)
+  hipStream_t st = (hipStream_t)stream;
+  if (f.rb == 4) return launch_grouped<4, 4>(gp, wgs, st);
+  switch (f.rr) {
+    case 2: return launch_grouped<5, 2>(gp, wgs, st);
+    case 4: return launch_grouped<5, 4>(gp, wgs, st);
+    default: return launch_grouped<5, 5>(gp, wgs, st);
+  }
 }

@@ -117,7 +117,8 @@ class ContextKV:
     def __init__(self, shape: Tuple[int, int, int]):
         self.shape = tuple(shape)           # (B,S,caption_channels) it was built for
         self.ctx: Optional[torch.Tensor] = None
-        self.kv: List[tuple] = []
+        self.kv: List[tuple] = []           # per block: (k, V^T, sumsq)
+        self.stacked: Optional[tuple] = None   # the (L, ...) buffers the entries of kv are slices of, when one grouped launch wrote them
 
 
 class LTXModel:
@@ -150,6 +151,9 @@ class LTXModel:
         # independent of the batch, at ~5 % of attention time at N=1280 (attention.hip).  The GEMMs of a forward with
         # M <= ops.SPLITK_MAX_M still depend on it.
         self.attn_tail_split = True
+        # the text K / V^T of all blocks by one grouped launch per forward (_context_kv_all); False: one launch pair per block
+        # (_context_kv - the same bits; kept as the reference of the equality tests and for A/B timing)
+        self.grouped_context_kv = True
         self._pack(weights)
         # the split-K scratch of ops.gemm (small-M launches) must exist before anyone captures a forward into a hipGraph: allocated
         # inside a capture it would come from that graph's private pool
@@ -200,6 +204,13 @@ class LTXModel:
             tables.append(g(f"{pre}.scale_shift_table"))
             self.blocks.append(b)
         self.tables = torch.stack(tables, 0).contiguous()      # (L,6,D)
+        # the text k | V^T projections of all blocks as one grouped launch (_context_kv_all): the k-norm weights stacked into one
+        # (L,D) table - the blocks keep rows of it - and device tables of the panels' addresses; the panels stay where they are
+        self.wkn2_all = torch.stack([b.wkn2 for b in self.blocks], 0).contiguous()
+        for i, b in enumerate(self.blocks):
+            b.wkn2 = self.wkn2_all[i]
+        self.wkv2_table = ops.pointer_table([b.wkv2 for b in self.blocks])
+        self.bkv2_table = ops.pointer_table([b.bkv2 for b in self.blocks])
 
     def weight_views(self) -> Dict[str, torch.Tensor]:
         """Checkpoint key -> the (out,in) matrix as it lives inside THIS model: the packed q|k|v and text k|v panels are
@@ -320,6 +331,30 @@ class LTXModel:
         ops.qknorm_rope(k2, 1, D, blk.wkn2, None, None, s, H, eps, sumsq=st)
         return k2, vt2, ss
 
+    def _grouped_context_ok(self, b: int, s: int) -> bool:
+        """Whether the grouped launch gives the bits of the per-block ``_context_kv`` calls: it is single-pass, as they are unless
+        the library would split K at this row count (small M with the split-K scratch on offer)."""
+        D = self.inner_dim
+        if not self.grouped_context_kv or (self.fuse & 3) != 3 or D % 256 != 0:
+            return False
+        return not ops.gemm_plan(b * s, 2 * D, D, n_split=D, out_tokens_per_batch=s, sumsq=True,
+                                 split_k=not self.batch_invariant).split_k
+
+    def _context_kv_all(self, ctx: torch.Tensor, b: int, s: int, sp: int, out: Optional[tuple] = None):
+        """``_context_kv`` of every block at once: one grouped GEMM launch over the L packed k|v panels into (L, ...) buffers and
+        one k-norm launch over them.  Returns (k (L,b*s,D), V^T (L,b,D,sp), sumsq (L,b*s,D/64)); block li reads index li."""
+        D, H, eps, L = self.inner_dim, self.num_attention_heads, self.config.norm_eps, len(self.blocks)
+        if out is None:
+            k2 = torch.empty((L, b * s, D), dtype=BF16, device=ctx.device)
+            vt2 = torch.zeros((L, b, D, sp), dtype=BF16, device=ctx.device) if sp != s else \
+                torch.empty((L, b, D, sp), dtype=BF16, device=ctx.device)
+            ss = torch.empty((L, b * s, D // 64), dtype=torch.float32, device=ctx.device)
+        else:
+            k2, vt2, ss = out
+        ops.gemm_grouped(ctx, self.wkv2_table, self.bkv2_table, 2 * D, out=k2, out2=vt2, n_split=D, out_tokens_per_batch=s, sumsq=ss)
+        ops.qknorm_grouped(k2, self.wkn2_all, H, eps, ss)
+        return k2, vt2, ss
+
     def prepare_context(self, context: torch.Tensor, out: Optional[ContextKV] = None) -> ContextKV:
         """Everything of the forward that depends on the text context only (3.37 TFLOP at S=1024, SURVEY.md
         §8d).  The reference recomputes it in every forward; a denoise loop may hoist it (an algorithmic
@@ -331,8 +366,14 @@ class LTXModel:
         if kv.shape != tuple(context.shape):
             raise ValueError(f"ContextKV was built for context {kv.shape}, got {tuple(context.shape)}")
         kv.ctx = self._prepare_context(context, kv.ctx)
+        if self._grouped_context_ok(b, s):
+            k2, vt2, ss = self._context_kv_all(kv.ctx, b, s, sp, kv.stacked)
+            kv.stacked = (k2, vt2, ss)
+            kv.kv = [(k2[i], vt2[i], ss[i]) for i in range(len(self.blocks))]
+            return kv
         new = [self._context_kv(blk, kv.ctx, b, s, sp, kv.kv[i] if kv.kv else None) for i, blk in enumerate(self.blocks)]
         kv.kv = new
+        kv.stacked = None
         return kv
 
     def forward_tokens(self, latent: torch.Tensor, plan: TimestepPlan, context: torch.Tensor,
@@ -399,18 +440,24 @@ class LTXModel:
         q2ss = torch.empty((M, P), dtype=torch.float32, device=dev)
         hff = torch.empty((M, 4 * D), dtype=BF16, device=dev)
         ms = 6 * D
-        kv_buf = None
-        if ctx_kv is None:                  # text K / V^T of the current block, recomputed every forward (one buffer set)
-            # (computing block li+1's text K / V^T on a side stream beside block li - they do not depend on the token
-            # stream - measured 1.7 % SLOWER eagerly and unchanged in a captured graph: the main kernels leave no CU idle
-            # long enough for a 156-KiB-LDS GEMM workgroup; profiles/r02_launch_structure_ab.log.  k's q_norm + RoPE on a side
-            # stream beside the V^T GEMM - a memory-bound kernel that needs no LDS - measured the same way: 1.269 against
-            # 1.264 ms per block.  Forked graph branches cost more than they overlap.  Nor does one GRID for two independent GEMMs
-            # (q|k on 320x256 tiles with v's 160x256 tiles back-filling behind them; text k|v with q2): 1269.6 us per block
-            # either way, big tiles first or last - the tail of one launch is not where the time goes.)
-            kv_buf = (torch.empty((B * S, D), dtype=BF16, device=dev),
-                      torch.zeros((B, D, sp64), dtype=BF16, device=dev) if sp64 != S else torch.empty((B, D, sp64), dtype=BF16, device=dev),
-                      torch.empty((B * S, D // 64), dtype=torch.float32, device=dev))
+        kv_buf = kv_all = None
+        if ctx_kv is None:
+            # Text K / V^T are recomputed every forward, as the reference does.  They depend on ctx and the block's weights only,
+            # so all L of them are computed HERE, before block 0, by one grouped persistent GEMM launch and one k-norm launch
+            # into (L, ...) buffers (0.8 GB each for k and V^T at B=2, S=1024, L=48; allocated per forward like every other
+            # activation): over 48 launches' worth of tiles the 320-row tile fills its rounds, which one M=2048 launch cannot,
+            # and the launch ramp is paid once.  Same work on the main stream, same bits.
+            # Rejected before, and still: block li+1's text K / V^T on a side stream beside block li measured 1.7 % SLOWER eagerly
+            # and unchanged in a captured graph - the main kernels leave no CU idle long enough for a 156-KiB-LDS GEMM
+            # workgroup (profiles/r02_launch_structure_ab.log); k's q_norm on a side stream beside the V^T GEMM: 1.269 against
+            # 1.264 ms per block - forked graph branches cost more than they overlap; one GRID for two independent GEMMs (q|k
+            # on 320x256 tiles with v's 160x256 tiles back-filling behind them; text k|v with q2): 1269.6 us per block either way.
+            if self._grouped_context_ok(B, S):
+                kv_all = self._context_kv_all(ctx, B, S, sp64)
+            else:             # per block, one buffer set (the library would split K here, or the fused forms are off)
+                kv_buf = (torch.empty((B * S, D), dtype=BF16, device=dev),
+                          torch.zeros((B, D, sp64), dtype=BF16, device=dev) if sp64 != S else torch.empty((B, D, sp64), dtype=BF16, device=dev),
+                          torch.empty((B * S, D // 64), dtype=torch.float32, device=dev))
 
         skip_rows = [[] for _ in self.blocks]          # per block: the batch rows whose self-attention is skipped (STG)
         if perturbations is not None:
@@ -456,7 +503,12 @@ class LTXModel:
             # text cross-attention (transformer.py:257-261)
             ops.rmsnorm_modulate(x, eps, out=nx, sumsq=s_x)
             ops.gemm(nx, blk.wq2, blk.bq2, out=q2, sumsq=s_q2, split_k=sk)
-            kv = ctx_kv.kv[li] if ctx_kv is not None else self._context_kv(blk, ctx, B, S, sp64, kv_buf)
+            if ctx_kv is not None:
+                kv = ctx_kv.kv[li]
+            elif kv_all is not None:
+                kv = (kv_all[0][li], kv_all[1][li], kv_all[2][li])
+            else:
+                kv = self._context_kv(blk, ctx, B, S, sp64, kv_buf)
             if fp:
                 ops.flash_attn(q2, kv[0], kv[1], att, B, H, N, S, scale, q_sumsq=q2ss, q_norm_weight=blk.wqn2, eps=eps, tail_split=ts_)
             else:

@@ -10,7 +10,7 @@ from typing import Optional, Tuple
 import torch
 
 from . import _lib
-from ._lib import AttnArgs, GemmArgs, StepArgs, check
+from ._lib import AttnArgs, GemmArgs, GemmGroupedArgs, StepArgs, check
 
 EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_SILU, EPI_BIAS_GATE_RES, EPI_BIAS_RES, EPI_SCALE_RES = 0, 1, 2, 3, 4, 5
 BF16 = torch.bfloat16
@@ -186,6 +186,73 @@ def gemm_plan(M: int, N: int, K: int, *, epilogue: int = EPI_BIAS, lda: Optional
     return GemmPlan(pl.form, pl.tile_rows, pl.tile_cols, pl.row_tiles, pl.col_tiles, pl.slices, pl.ksteps)
 
 
+def pointer_table(tensors) -> torch.Tensor:
+    """Device array of the tensors' addresses (int64): the per-group operand table of ``gemm_grouped``.  It holds
+    addresses only - the caller keeps the tensors alive and in place for as long as the table is used."""
+    return torch.tensor([t.data_ptr() for t in tensors], dtype=torch.int64, device=tensors[0].device)
+
+
+def _grouped_args(G: int, M: int, N: int, K: int, n_split: int, out_tokens_per_batch: int) -> GemmGroupedArgs:
+    args = GemmGroupedArgs()
+    args.G, args.M, args.N, args.K = G, M, N, K
+    args.n_split, args.out_tokens_per_batch = n_split, out_tokens_per_batch
+    return args
+
+
+def gemm_grouped(a: torch.Tensor, w_table: torch.Tensor, bias_table: Optional[torch.Tensor], N: int, *,
+                 out: torch.Tensor, out2: torch.Tensor, n_split: int, out_tokens_per_batch: int,
+                 sumsq: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ltxk_gemm_bf16_grouped: for every group g, ``gemm(a, W[g], bias[g], out=out[g], out2=out2[g], n_split=...,
+    sumsq=sumsq[g], split_k=False)`` - the same bits - as ONE persistent launch.  a (M,K); w_table / bias_table:
+    ``pointer_table`` of G contiguous (N,K) panels / (N) rows; out (G,M,n_split), out2 (G,B,N-n_split,ld), sumsq
+    (G,M,>=n_split/64) fp32, each with contiguous inner dimensions."""
+    _req(a, BF16, "gemm_grouped.a"); _req(out, BF16, "gemm_grouped.out"); _req(out2, BF16, "gemm_grouped.out2")
+    _req(w_table, torch.int64, "gemm_grouped.w_table")
+    M, K = a.shape
+    G = w_table.numel()
+    if a.stride(1) != 1 or out.dim() != 3 or out2.dim() != 4 or out.shape[0] != G or out2.shape[0] != G or \
+            out.stride(-1) != 1 or out2.stride(-1) != 1 or (bias_table is not None and bias_table.numel() != G):
+        raise ValueError(f"gemm_grouped: bad operand layout a{tuple(a.shape)} out{tuple(out.shape)} out2{tuple(out2.shape)} G={G}")
+    if out2.stride(1) != out2.shape[2] * out2.stride(2) or out.shape[1] != M:
+        raise ValueError("gemm_grouped: out2 must be (G,B,N-n_split,ld) with contiguous batches, out (G,M,n_split)")
+    if sumsq is not None and (sumsq.dtype != torch.float32 or sumsq.stride(-1) != 1 or sumsq.dim() != 3 or sumsq.shape[0] != G):
+        raise TypeError("gemm_grouped: sumsq must be (G,M,>=n_split/64) float32 with unit inner stride")
+    args = _grouped_args(G, M, N, K, n_split, out_tokens_per_batch)
+    args.A, args.W, args.bias = _p(a), _p(w_table), _p(bias_table)
+    args.out, args.out2, args.sumsq = _p(out), _p(out2), _p(sumsq)
+    args.out_gstride, args.out2_gstride = out.stride(0), out2.stride(0)
+    args.sumsq_gstride = sumsq.stride(0) if sumsq is not None else 0
+    args.lda, args.ldo, args.ldo2 = a.stride(0), out.stride(1), out2.stride(2)
+    args.sumsq_ld = sumsq.stride(1) if sumsq is not None else 0
+    with _timed("gemm_bf16", 2.0 * G * M * N * K, 2.0 * (M * K + G * (N * K + M * N))):
+        check(_lib.load().ltxk_gemm_bf16_grouped(ctypes.byref(args), _stream()), "ltxk_gemm_bf16_grouped")
+    return out
+
+
+@dataclass(frozen=True)
+class GemmGroupedPlan:
+    """ltxk_gemm_grouped_plan: the tiling of one ltxk_gemm_bf16_grouped launch."""
+    tile_rows: int
+    rem_rows: int
+    row_tiles: int
+    col_tiles: int
+    tiles: int
+
+
+def gemm_grouped_plan(G: int, M: int, N: int, K: int, *, n_split: int, out_tokens_per_batch: int) -> GemmGroupedPlan:
+    """The tile ``gemm_grouped`` takes for G (M,K) x (N,K)^T problems, decided on the host (no device needed) by the function
+    the launch itself uses.  Strides are those of contiguous buffers."""
+    args = _grouped_args(G, M, N, K, n_split, out_tokens_per_batch)
+    args.A = args.W = args.out = args.out2 = _PLAN_ADDR
+    ld_t = (out_tokens_per_batch + 63) // 64 * 64
+    args.lda, args.ldo, args.ldo2 = K, n_split, ld_t
+    args.out_gstride = M * n_split
+    args.out2_gstride = (M // max(out_tokens_per_batch, 1)) * (N - n_split) * ld_t
+    pl = _lib.GemmGroupedPlan()
+    check(_lib.load().ltxk_gemm_grouped_plan(ctypes.byref(args), ctypes.byref(pl)), "ltxk_gemm_grouped_plan")
+    return GemmGroupedPlan(pl.tile_rows, pl.rem_rows, pl.row_tiles, pl.col_tiles, pl.tiles)
+
+
 def flash_attn(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, out: torch.Tensor, B: int, H: int,
                Tq: int, Tk: int, scale: float, q_sumsq: Optional[torch.Tensor] = None,
                q_norm_weight: Optional[torch.Tensor] = None, cos: Optional[torch.Tensor] = None,
@@ -266,6 +333,21 @@ def qknorm_rope(buf: torch.Tensor, nseg: int, D: int, weight: torch.Tensor, cos:
     with _timed("qknorm_rope", 0.0, 4.0 * buf.shape[0] * nseg * D + (8.0 * buf.shape[0] * D // 2 if cos is not None else 0.0)):
         check(_lib.load().ltxk_qknorm_rope(_p(buf), buf.stride(0), buf.shape[0], nseg, D, _p(weight), _p(cos), _p(sin),
                                            T, H, eps, _stream()), "ltxk_qknorm_rope")
+    return buf
+
+
+def qknorm_grouped(buf: torch.Tensor, weight: torch.Tensor, H: int, eps: float, sumsq: torch.Tensor) -> torch.Tensor:
+    """ltxk_qknorm_grouped_ss: q/k RMSNorm without rotation, in place on buf (G,M,D) with weight row g of the (G,D) table
+    and the row statistics sumsq (G,M,>=D/64) of ``gemm_grouped`` - the bits of G ``qknorm_rope(buf[g], 1, D, weight[g],
+    None, None, ..., sumsq=sumsq[g])`` calls, in one launch."""
+    _req(buf, BF16, "qknorm_grouped.buf"); _req(weight, BF16, "qknorm_grouped.weight"); _req(sumsq, torch.float32, "qknorm_grouped.sumsq")
+    G, M, D = buf.shape
+    if buf.stride(2) != 1 or sumsq.dim() != 3 or sumsq.stride(2) != 1 or sumsq.shape[:2] != buf.shape[:2] or \
+            tuple(weight.shape) != (G, D) or not weight.is_contiguous():
+        raise ValueError(f"qknorm_grouped: bad operand layout buf{tuple(buf.shape)} weight{tuple(weight.shape)} sumsq{tuple(sumsq.shape)}")
+    with _timed("qknorm_rope", 0.0, 4.0 * G * M * D):
+        check(_lib.load().ltxk_qknorm_grouped_ss(_p(buf), buf.stride(0), buf.stride(1), G, M, D, _p(weight), H, eps, _p(sumsq),
+                                                 sumsq.stride(0), sumsq.stride(1), _stream()), "ltxk_qknorm_grouped_ss")
     return buf
 
 
