@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define LTXK_VERSION 403
+#define LTXK_VERSION 404
 
 #define LTXK_OK 0
 #define LTXK_EINVAL (-1)   /* bad argument (shape / alignment / null pointer) */
@@ -110,6 +110,20 @@ struct ltxk_gemm_plan {   /* a struct tag only: the name is also the function's 
 };
 
 int ltxk_gemm_plan(const ltxk_gemm_args* args, struct ltxk_gemm_plan* plan);
+
+/* The same GEMM over an FP8 weight panel (W8A16): args->W is (N,K) OCP e4m3fn BYTES, row-major, 16-byte aligned; everything
+ * else in `args` means what it means to ltxk_gemm_bf16, and the same argument checks return the same error codes.  The
+ * panel is staged as fp8 (half the weight bytes from memory and through LDS) and widened to bf16 in registers in front of
+ * the same v_mfma_f32_16x16x32_bf16 with the same K order; every e4m3 value is a bf16 value, so with w_scale == NULL the
+ * outputs (out, out2, sumsq) equal those of ltxk_gemm_bf16 on the panel converted to bf16, bit for bit.  No bf16 copy of
+ * the panel is made anywhere.
+ * w_scale: (N) fp32 per-output-channel factors, 4-byte aligned, or NULL.  Applied as acc[n] * w_scale[n] on the fp32
+ * accumulator before the bias (in the split-K form: on the summed slices); NULL: no multiply at all.
+ * Launch forms: the single-pass 160-row family and split-K.  ltxk_gemm_w8_plan reports the form by the host rules of
+ * ltxk_gemm_plan, except that a call the bf16 entry would run on the big tile is planned SINGLE: the split-K decision,
+ * slice count and ksteps are those of the bf16 call with the same M, N, K and workspace.                                 */
+int ltxk_gemm_w8(const ltxk_gemm_args* args, const float* w_scale, void* stream);
+int ltxk_gemm_w8_plan(const ltxk_gemm_args* args, struct ltxk_gemm_plan* plan);
 
 /* Grouped GEMM: G problems that share A, M, N, K and the split output layout, as ONE persistent launch of 256-column big
  * tiles - the text k | V^T projections of every transformer block (attention.py:123-125 on the text side), none of which

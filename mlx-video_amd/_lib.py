@@ -87,6 +87,8 @@ SIGNATURES = {
     "ltxk_abi_sizeof": (c_int32, [c_int32]),
     "ltxk_gemm_bf16": (c_int32, [POINTER(GemmArgs), c_void_p]),
     "ltxk_gemm_plan": (c_int32, [POINTER(GemmArgs), POINTER(GemmPlan)]),
+    "ltxk_gemm_w8": (c_int32, [POINTER(GemmArgs), c_void_p, c_void_p]),
+    "ltxk_gemm_w8_plan": (c_int32, [POINTER(GemmArgs), POINTER(GemmPlan)]),
     "ltxk_gemm_bf16_grouped": (c_int32, [POINTER(GemmGroupedArgs), c_void_p]),
     "ltxk_gemm_grouped_args_sizeof": (c_int32, []),
     "ltxk_gemm_grouped_plan": (c_int32, [POINTER(GemmGroupedArgs), POINTER(GemmGroupedPlan)]),

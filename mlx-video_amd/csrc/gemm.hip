@@ -5,6 +5,7 @@
 #include "gemm_core.h"
 #include <stdlib.h>
 #include <atomic>
+#include <type_traits>
 #include <utility>
 
 #ifndef LTXK_DEFER_GROUPS
@@ -61,12 +62,15 @@ struct GemmParams {
   // fp32 accumulators to part[(s*M + m)*N + n]; splitk_epilogue_kernel sums the slices in order and applies the epilogue
   float* part;
   int ksteps;
+  // weight-fp8 forms (W8 kernels; W then points at e4m3fn bytes): per-output-channel fp32 factor on the accumulator, or nullptr
+  const float* w_scale;
 };
 
 // NT = 16-column MFMA tiles per wave: 4 -> 256-column workgroup tiles (64 per wave), 2 -> 128-column ones (32 per wave).
-template <int TT, int NT, int EPI, bool TRANS>
+// W8: W is (N,K) e4m3fn bytes, staged as fp8 (gemm_core.h) and widened after the fragment read; everything else is shared.
+template <int TT, int NT, int EPI, bool TRANS, bool W8 = false>
 __device__ __forceinline__ void gemm_tile(const GemmParams& p, char* smem, int m0, int n0, int kbase, int nk, int wave, int lane) {
-  using G = GemmGeom<TT, 4, NT>;
+  using G = GemmGeom<TT, 4, NT, W8>;
   constexpr int GEMM_W_STAGE_BYTES = G::W_STAGE_BYTES;
   constexpr int WPW = G::W_PER_WAVE;          // W pieces per wave per stage (4 / 2)
   constexpr int WC = 16 * NT;                 // columns per wave
@@ -75,12 +79,15 @@ __device__ __forceinline__ void gemm_tile(const GemmParams& p, char* smem, int m
   // ---- loader: per-lane source pointers (row clamped, 16-byte chunk pre-swizzled) ----
   const int lrow = lane >> 3;
   const int chunk = (lane & 7) ^ lrow;
-  const bf16* wptr[WPW];
+  // (W8: a piece is 16 rows of 64 bytes - lane -> row lane >> 2, 16-byte chunk (lane & 3) ^ ((row >> 2) & 3); wptr and the
+  // K offsets below then count bytes, one per element)
+  using wel = std::conditional_t<W8, uint8_t, bf16>;
+  const wel* wptr[WPW];
 #pragma unroll
   for (int i = 0; i < WPW; ++i) {
-    int r = n0 + (wave * WPW + i) * 8 + lrow;
+    int r = n0 + (wave * WPW + i) * (W8 ? 16 : 8) + (W8 ? lane >> 2 : lrow);
     r = r < p.N ? r : p.N - 1;
-    wptr[i] = p.W + (size_t)r * p.K + chunk * 8;
+    wptr[i] = (const wel*)p.W + (size_t)r * p.K + (W8 ? ((lane & 3) ^ (lane >> 4)) * 16 : chunk * 8);
   }
   // Every wave issues exactly WPW W pieces + MAXA A pieces per stage, so one constant vmcnt retires a
   // stage.  A_PIECES is not a multiple of 8 (20 at BM=160): waves past A_REM own one piece fewer and
@@ -235,7 +242,7 @@ __device__ __forceinline__ void gemm_tile(const GemmParams& p, char* smem, int m
     if constexpr (TT >= 2) {
       pipe.step(smem + s * G::STAGE_BYTES, wm, wn, lane, acc, issue);
     } else {
-      mma_stage_pipelined<TT, 4, TRANS, NT>(smem + s * G::STAGE_BYTES, wm, wn, lane, acc, issue);
+      mma_stage_pipelined<TT, 4, TRANS, NT, W8>(smem + s * G::STAGE_BYTES, wm, wn, lane, acc, issue);
     }
     s = s + 1 == 3 ? 0 : s + 1;
   };
@@ -256,12 +263,12 @@ __device__ __forceinline__ void gemm_tile(const GemmParams& p, char* smem, int m
   if constexpr (TT >= 2) {
 #if LTXK_STAGGER
     if (wave >= 4) {                  // SIMD partners of waves 0-3 run half a K-step out of phase
-      MmaPipe<TT, 4, TRANS, TT, NT> pipe;
+      MmaPipe<TT, 4, TRANS, TT, NT, W8> pipe;
       kloop(pipe);
     } else
 #endif
     {
-      MmaPipe<TT, 4, TRANS, (LTXK_DEFER_GROUPS <= TT ? LTXK_DEFER_GROUPS : TT), NT> pipe;
+      MmaPipe<TT, 4, TRANS, (LTXK_DEFER_GROUPS <= TT ? LTXK_DEFER_GROUPS : TT), NT, W8> pipe;
       kloop(pipe);
     }
   } else {
@@ -295,6 +302,29 @@ __device__ __forceinline__ void gemm_tile(const GemmParams& p, char* smem, int m
     }
   }
   LTXK_STAMP(3);
+  if constexpr (W8) {
+    // per-output-channel scale on the fp32 accumulators, in front of the shared epilogue (no scale: no multiply)
+    if (p.w_scale) {
+#pragma unroll
+      for (int nt = 0; nt < NT; ++nt) {
+        float sc[4];
+        if constexpr (TRANS) {
+          int n = n0 + wn * WC + nt * 16 + (lane & 15);
+          n = n < p.N ? n : p.N - 1;
+          sc[0] = sc[1] = sc[2] = sc[3] = p.w_scale[n];
+        } else {
+          int n = n0 + wn * WC + nt * 16 + (lane >> 4) * 4;
+          n = n < p.N ? n : p.N - 4;
+#pragma unroll
+          for (int j = 0; j < 4; ++j) sc[j] = p.w_scale[n + j];
+        }
+#pragma unroll
+        for (int tt = 0; tt < TT; ++tt)
+#pragma unroll
+          for (int j = 0; j < 4; ++j) acc[tt][nt][j] *= sc[j];
+      }
+    }
+  }
 
   // ---- epilogue ----
   if constexpr (!TRANS) {
@@ -302,6 +332,7 @@ __device__ __forceinline__ void gemm_tile(const GemmParams& p, char* smem, int m
     // instruction; with p.wide each wave instead transposes its (16*TT x WC) block through a private LDS image
     // (rows of WC*2 bytes, 16-byte chunks XOR-swizzled by row) and stores whole rows of it per instruction.
     constexpr int RB = WC * 2, CPR = RB / 16;       // staged row bytes (128 / 64), 16-byte chunks per row (8 / 4)
+    static_assert(8 * TT * 16 * RB + (NT == 2 ? 4 * TT * 64 * 4 : 0) <= G::LDS_BYTES, "the epilogue's LDS images must fit the ring");
     const int nq = (lane >> 4) * 4;
     char* stg = smem + wave * (TT * 16 * RB);
     const bool want_ss = p.sumsq != nullptr;
@@ -460,9 +491,9 @@ __device__ __forceinline__ void gemm_tile(const GemmParams& p, char* smem, int m
 
 // MODE 0: every tile row-major with epilogue EPI; 1: every tile transposed (V^T); 2: split output - tiles with
 // n0 < n_split row-major (EPI), the rest transposed (one launch for q|k|v, or for the text k|v pair)
-template <int TT, int NT, int EPI, int MODE>
+template <int TT, int NT, int EPI, int MODE, bool W8 = false>
 __global__ __launch_bounds__(GEMM_THREADS) void gemm_bf16_kernel(GemmParams p) {
-  using G = GemmGeom<TT, 4, NT>;
+  using G = GemmGeom<TT, 4, NT, W8>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   LTXK_STAMP(4);
   const int tid = threadIdx.x;
@@ -473,12 +504,12 @@ __global__ __launch_bounds__(GEMM_THREADS) void gemm_bf16_kernel(GemmParams p) {
   const int m0 = rt * G::BM, n0 = ct * G::BN;
   const int kbase = 0, nk = p.K / GEMM_BK;
   if constexpr (MODE == 0) {
-    gemm_tile<TT, NT, EPI, false>(p, smem, m0, n0, kbase, nk, wave, lane);
+    gemm_tile<TT, NT, EPI, false, W8>(p, smem, m0, n0, kbase, nk, wave, lane);
   } else if constexpr (MODE == 1) {
-    gemm_tile<TT, NT, LTXK_EPI_BIAS, true>(p, smem, m0, n0, kbase, nk, wave, lane);
+    gemm_tile<TT, NT, LTXK_EPI_BIAS, true, W8>(p, smem, m0, n0, kbase, nk, wave, lane);
   } else {
-    if (n0 < p.n_split) gemm_tile<TT, NT, EPI, false>(p, smem, m0, n0, kbase, nk, wave, lane);
-    else gemm_tile<TT, NT, LTXK_EPI_BIAS, true>(p, smem, m0, n0, kbase, nk, wave, lane);
+    if (n0 < p.n_split) gemm_tile<TT, NT, EPI, false, W8>(p, smem, m0, n0, kbase, nk, wave, lane);
+    else gemm_tile<TT, NT, LTXK_EPI_BIAS, true, W8>(p, smem, m0, n0, kbase, nk, wave, lane);
   }
 #ifdef LTXK_DIAG
   __syncthreads();
@@ -500,17 +531,17 @@ __global__ __launch_bounds__(GEMM_THREADS) void gemm_bf16_kernel(GemmParams p) {
 // stages a 64 x 128 tile pulled ~50 GB/s - 160 of them 1 TB/s of a 32-MB panel (profiles/r04_small_m_ab.log).  Every wave
 // issues the same number of LDS-DMA pieces per K-step (a clamped re-load of the last stage into a free slot once the real
 // ones run out), so one constant counted vmcnt retires a stage.
-template <int TT> struct StreamGeom {
-  using G = GemmGeom<TT, 4, 2>;
+template <int TT, bool W8 = false> struct StreamGeom {
+  using G = GemmGeom<TT, 4, 2, W8>;
   static constexpr int D = (160 * 1024) / G::STAGE_BYTES < 6 ? (160 * 1024) / G::STAGE_BYTES : 6;
   static constexpr int LDS = D * G::STAGE_BYTES;
   static_assert(D >= 3, "ring too shallow");
 };
 
-template <int TT>
+template <int TT, bool W8 = false>
 __global__ __launch_bounds__(GEMM_THREADS) void gemm_stream_kernel(GemmParams p) {
-  using G = GemmGeom<TT, 4, 2>;
-  constexpr int D = StreamGeom<TT>::D, NT = 2, WPW = G::W_PER_WAVE, PER_STAGE = WPW + G::MAXA;
+  using G = GemmGeom<TT, 4, 2, W8>;
+  constexpr int D = StreamGeom<TT, W8>::D, NT = 2, WPW = G::W_PER_WAVE, PER_STAGE = WPW + G::MAXA;
   static_assert(PER_STAGE * (D - 2) <= 63, "vmcnt is a 6-bit counter");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = threadIdx.x & 63;
@@ -522,12 +553,13 @@ __global__ __launch_bounds__(GEMM_THREADS) void gemm_stream_kernel(GemmParams p)
   const int kbase = (int)blockIdx.y * p.ksteps;
   const int nk = nk_all - kbase < p.ksteps ? nk_all - kbase : p.ksteps;
   const int lrow = lane >> 3, chunk = (lane & 7) ^ lrow;
-  const bf16* wptr[WPW];
+  using wel = std::conditional_t<W8, uint8_t, bf16>;           // (W8: 16-row pieces of 64-byte rows, as in gemm_tile)
+  const wel* wptr[WPW];
 #pragma unroll
   for (int i = 0; i < WPW; ++i) {
-    int r = n0 + (wave * WPW + i) * 8 + lrow;
+    int r = n0 + (wave * WPW + i) * (W8 ? 16 : 8) + (W8 ? lane >> 2 : lrow);
     r = r < p.N ? r : p.N - 1;
-    wptr[i] = p.W + (size_t)r * p.K + chunk * 8;
+    wptr[i] = (const wel*)p.W + (size_t)r * p.K + (W8 ? ((lane & 3) ^ (lane >> 4)) * 16 : chunk * 8);
   }
   const int nA = G::A_BASE + (wave < G::A_REM ? 1 : 0);
   const int a0 = wave * G::A_BASE + (wave < G::A_REM ? wave : G::A_REM);
@@ -563,12 +595,12 @@ __global__ __launch_bounds__(GEMM_THREADS) void gemm_stream_kernel(GemmParams p)
       const int pre = slot == 0 ? D - 1 : slot - 1;            // slot of stage kt + D - 1 = the one consumed in step kt - 1
       auto issue = [&](int i) __attribute__((always_inline)) { issue_piece(i, kt + D - 1, pre); };
       if constexpr (TT >= 2) pipe.step(smem + slot * G::STAGE_BYTES, wm, wn, lane, acc, issue);
-      else mma_stage_pipelined<TT, 4, false, NT>(smem + slot * G::STAGE_BYTES, wm, wn, lane, acc, issue);
+      else mma_stage_pipelined<TT, 4, false, NT, W8>(smem + slot * G::STAGE_BYTES, wm, wn, lane, acc, issue);
       slot = slot + 1 == D ? 0 : slot + 1;
     }
   };
   if constexpr (TT >= 2) {
-    MmaPipe<TT, 4, false, 2, NT> pipe;
+    MmaPipe<TT, 4, false, 2, NT, W8> pipe;
     pipe.init();
     loop(pipe);
     pipe.finish(acc);
@@ -591,21 +623,21 @@ __global__ __launch_bounds__(GEMM_THREADS) void gemm_stream_kernel(GemmParams p)
   }
 }
 
-template <int TT>
+template <int TT, bool W8>
 static int launch_stream(const GemmParams& p, int ksplit, hipStream_t stream) {
-  auto kern = gemm_stream_kernel<TT>;
+  auto kern = gemm_stream_kernel<TT, W8>;
   static thread_local int attr_dev = -1;
   int dev = 0;
   (void)hipGetDevice(&dev);
   if (dev != attr_dev) {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, StreamGeom<TT>::LDS);
+    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, StreamGeom<TT, W8>::LDS);
     if (e != hipSuccess) {
       ltxk_set_error("ltxk_gemm_bf16: hipFuncSetAttribute: %s", hipGetErrorString(e));
       return LTXK_ELAUNCH;
     }
     attr_dev = dev;
   }
-  hipLaunchKernelGGL(kern, dim3(p.RT * p.CT, ksplit), dim3(GEMM_THREADS), StreamGeom<TT>::LDS, stream, p);
+  hipLaunchKernelGGL(kern, dim3(p.RT * p.CT, ksplit), dim3(GEMM_THREADS), (StreamGeom<TT, W8>::LDS), stream, p);
   LTXK_CHECK_LAUNCH("ltxk_gemm_bf16 (split-K slices)");
   return LTXK_OK;
 }
@@ -632,6 +664,10 @@ __global__ __launch_bounds__(256) void splitk_epilogue_kernel(GemmParams p, int 
     const f32x4 b = *(const f32x4*)(src + (size_t)sl * slab);
 #pragma unroll
     for (int j = 0; j < 4; ++j) a[j] += b[j];
+  }
+  if (p.w_scale) {                                 // weight-fp8 launches: per-output-channel factor on the summed slices
+#pragma unroll
+    for (int j = 0; j < 4; ++j) a[j] *= p.w_scale[n + j];
   }
   bf16x4 bias = {(bf16)0.f, (bf16)0.f, (bf16)0.f, (bf16)0.f};
   if (p.bias) bias = *(const bf16x4*)(p.bias + n);
@@ -683,10 +719,10 @@ __global__ __launch_bounds__(256) void splitk_epilogue_kernel(GemmParams p, int 
   }
 }
 
-template <int TT, int NT, int EPI, int MODE>
+template <int TT, int NT, int EPI, int MODE, bool W8>
 static int launch(const GemmParams& p, hipStream_t stream) {
-  using G = GemmGeom<TT, 4, NT>;
-  auto kern = gemm_bf16_kernel<TT, NT, EPI, MODE>;
+  using G = GemmGeom<TT, 4, NT, W8>;
+  auto kern = gemm_bf16_kernel<TT, NT, EPI, MODE, W8>;
   static thread_local int attr_dev = -1;
   int dev = 0;
   (void)hipGetDevice(&dev);
@@ -704,41 +740,42 @@ static int launch(const GemmParams& p, hipStream_t stream) {
   return LTXK_OK;
 }
 
-template <int TT, int NT>
+template <int TT, int NT, bool W8>
 static int dispatch_epi(const GemmParams& p, int epi, bool trans, hipStream_t stream) {
-  if (p.n_split) return launch<TT, NT, LTXK_EPI_BIAS, 2>(p, stream);
-  if (trans) return launch<TT, NT, LTXK_EPI_BIAS, 1>(p, stream);
+  if (p.n_split) return launch<TT, NT, LTXK_EPI_BIAS, 2, W8>(p, stream);
+  if (trans) return launch<TT, NT, LTXK_EPI_BIAS, 1, W8>(p, stream);
   switch (epi) {
-    case LTXK_EPI_BIAS: return launch<TT, NT, LTXK_EPI_BIAS, 0>(p, stream);
-    case LTXK_EPI_BIAS_GELU: return launch<TT, NT, LTXK_EPI_BIAS_GELU, 0>(p, stream);
-    case LTXK_EPI_BIAS_SILU: return launch<TT, NT, LTXK_EPI_BIAS_SILU, 0>(p, stream);
-    case LTXK_EPI_BIAS_GATE_RES: return launch<TT, NT, LTXK_EPI_BIAS_GATE_RES, 0>(p, stream);
-    case LTXK_EPI_BIAS_RES: return launch<TT, NT, LTXK_EPI_BIAS_RES, 0>(p, stream);
-    case LTXK_EPI_SCALE_RES: return launch<TT, NT, LTXK_EPI_SCALE_RES, 0>(p, stream);
+    case LTXK_EPI_BIAS: return launch<TT, NT, LTXK_EPI_BIAS, 0, W8>(p, stream);
+    case LTXK_EPI_BIAS_GELU: return launch<TT, NT, LTXK_EPI_BIAS_GELU, 0, W8>(p, stream);
+    case LTXK_EPI_BIAS_SILU: return launch<TT, NT, LTXK_EPI_BIAS_SILU, 0, W8>(p, stream);
+    case LTXK_EPI_BIAS_GATE_RES: return launch<TT, NT, LTXK_EPI_BIAS_GATE_RES, 0, W8>(p, stream);
+    case LTXK_EPI_BIAS_RES: return launch<TT, NT, LTXK_EPI_BIAS_RES, 0, W8>(p, stream);
+    case LTXK_EPI_SCALE_RES: return launch<TT, NT, LTXK_EPI_SCALE_RES, 0, W8>(p, stream);
   }
   ltxk_set_error("ltxk_gemm_bf16: unknown epilogue %d", epi);
   return LTXK_EINVAL;
 }
 
-template <int NT>
+template <int NT, bool W8>
 static int dispatch_tt(const GemmParams& p, int tt, int epi, bool trans, hipStream_t st) {
   switch (tt) {
-    case 5: return dispatch_epi<5, NT>(p, epi, trans, st);
-    case 4: return dispatch_epi<4, NT>(p, epi, trans, st);
-    case 3: return dispatch_epi<3, NT>(p, epi, trans, st);
-    case 2: return dispatch_epi<2, NT>(p, epi, trans, st);
-    default: return dispatch_epi<1, NT>(p, epi, trans, st);
+    case 5: return dispatch_epi<5, NT, W8>(p, epi, trans, st);
+    case 4: return dispatch_epi<4, NT, W8>(p, epi, trans, st);
+    case 3: return dispatch_epi<3, NT, W8>(p, epi, trans, st);
+    case 2: return dispatch_epi<2, NT, W8>(p, epi, trans, st);
+    default: return dispatch_epi<1, NT, W8>(p, epi, trans, st);
   }
 }
 
 // split-K slices on the 128-column tile (the weight-streaming form for small M): fp32 partial tiles, then the epilogue launch
+template <bool W8>
 static int launch_partial(const GemmParams& p, int tt, int ksplit, hipStream_t st) {
   switch (tt) {
-    case 5: return launch_stream<5>(p, ksplit, st);
-    case 4: return launch_stream<4>(p, ksplit, st);
-    case 3: return launch_stream<3>(p, ksplit, st);
-    case 2: return launch_stream<2>(p, ksplit, st);
-    default: return launch_stream<1>(p, ksplit, st);
+    case 5: return launch_stream<5, W8>(p, ksplit, st);
+    case 4: return launch_stream<4, W8>(p, ksplit, st);
+    case 3: return launch_stream<3, W8>(p, ksplit, st);
+    case 2: return launch_stream<2, W8>(p, ksplit, st);
+    default: return launch_stream<1, W8>(p, ksplit, st);
   }
 }
 
@@ -1242,7 +1279,10 @@ struct GemmForm {
   bool split, trans;
 };
 
-static int gemm_form(const ltxk_gemm_args* a, GemmForm& f) {
+// w8: the form of ltxk_gemm_w8 - the same rules, with the 160-row single-pass tile wherever the bf16 call takes the big tile
+// (which has no weight-fp8 form).  The split-K decision, slice count and K-steps per slice are therefore those of the bf16 call
+// with the same M, N, K and workspace, so the two calls sum every row's products in the same order.
+static int gemm_form(const ltxk_gemm_args* a, GemmForm& f, bool w8 = false) {
   LTXK_CHECK_ARG(a != nullptr, "ltxk_gemm_bf16: null args");
   LTXK_CHECK_ARG(a->A && a->W && a->out, "ltxk_gemm_bf16: null A/W/out");
   LTXK_CHECK_ARG(a->M > 0 && a->N > 0 && a->K > 0, "ltxk_gemm_bf16: bad dims M=%d N=%d K=%d", a->M, a->N, a->K);
@@ -1302,6 +1342,10 @@ static int gemm_form(const ltxk_gemm_args* a, GemmForm& f) {
                          (a->epilogue == LTXK_EPI_BIAS || ((a->epilogue == LTXK_EPI_BIAS_GELU || a->epilogue == LTXK_EPI_BIAS_SILU) && !a->sumsq));
   // A/B build: LTXK_GEMM_BIG=0 never, 2 / 3 the 320-row / 256-row tile whenever legal (tests compare the tiles bit for bit)
   f.rb = !big_legal || tt_env != 0 || nt_env != 0 || big_env == 0 ? 0 : (big_env == 2 ? 5 : (big_env == 3 ? 4 : big_tile_choice(a->M, a->N)));
+  if (f.rb && w8) {
+    f.rb = 0;
+    return LTXK_OK;
+  }
   if (f.rb) {
     pl.form = LTXK_GEMM_FORM_BIG;
     pl.tile_rows = 64 * f.rb;
@@ -1361,11 +1405,14 @@ extern "C" int ltxk_gemm_plan(const ltxk_gemm_args* a, struct ltxk_gemm_plan* pl
   return rc;
 }
 
-extern "C" int ltxk_gemm_bf16(const ltxk_gemm_args* a, void* stream) {
-  using namespace ltxk;
+namespace ltxk {
+// ltxk_gemm_bf16 (W8 = false) and ltxk_gemm_w8: one body, so the two launch the same forms with the same parameters
+template <bool W8>
+static int gemm_run(const ltxk_gemm_args* a, const float* w_scale, void* stream) {
   GemmForm f;
-  const int rc = gemm_form(a, f);
+  const int rc = gemm_form(a, f, W8);
   if (rc != LTXK_OK) return rc;
+  LTXK_CHECK_ARG(((uintptr_t)w_scale & 3) == 0, "ltxk_gemm_w8: w_scale must be 4-byte aligned");
   const bool split = f.split, trans = f.trans;
   GemmParams p;
   p.A = (const bf16*)a->A; p.W = (const bf16*)a->W; p.bias = (const bf16*)a->bias;
@@ -1383,8 +1430,9 @@ extern "C" int ltxk_gemm_bf16(const ltxk_gemm_args* a, void* stream) {
   p.CT = f.plan.col_tiles;
   p.part = nullptr;
   p.ksteps = f.plan.ksteps;
+  p.w_scale = w_scale;
   hipStream_t st = (hipStream_t)stream;
-  if (f.plan.form == LTXK_GEMM_FORM_BIG) {
+  if constexpr (!W8) if (f.plan.form == LTXK_GEMM_FORM_BIG) {
     const int rb = f.rb;
     if (split) return launch_big<LTXK_EPI_BIAS, 2>(p, st, rb);
     if (trans) return launch_big<LTXK_EPI_BIAS, 1>(p, st, rb);
@@ -1396,14 +1444,28 @@ extern "C" int ltxk_gemm_bf16(const ltxk_gemm_args* a, void* stream) {
   }
   if (f.plan.form == LTXK_GEMM_FORM_SPLITK) {
     p.part = (float*)a->workspace;
-    const int rc2 = launch_partial(p, f.tt, f.plan.slices, st);
+    const int rc2 = launch_partial<W8>(p, f.tt, f.plan.slices, st);
     if (rc2 != LTXK_OK) return rc2;
     const long threads = (long)a->M * (a->N / 4);
     hipLaunchKernelGGL(splitk_epilogue_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, p, f.plan.slices, a->epilogue, trans ? 1 : 0);
     LTXK_CHECK_LAUNCH("ltxk_gemm_bf16 (split-K epilogue)");
     return LTXK_OK;
   }
-  return f.nt == 2 ? dispatch_tt<2>(p, f.tt, a->epilogue, trans, st) : dispatch_tt<4>(p, f.tt, a->epilogue, trans, st);
+  return f.nt == 2 ? dispatch_tt<2, W8>(p, f.tt, a->epilogue, trans, st) : dispatch_tt<4, W8>(p, f.tt, a->epilogue, trans, st);
+}
+}  // namespace ltxk
+
+extern "C" int ltxk_gemm_bf16(const ltxk_gemm_args* a, void* stream) { return ltxk::gemm_run<false>(a, nullptr, stream); }
+
+extern "C" int ltxk_gemm_w8(const ltxk_gemm_args* a, const float* w_scale, void* stream) { return ltxk::gemm_run<true>(a, w_scale, stream); }
+
+extern "C" int ltxk_gemm_w8_plan(const ltxk_gemm_args* a, struct ltxk_gemm_plan* plan) {
+  using namespace ltxk;
+  LTXK_CHECK_ARG(plan != nullptr, "ltxk_gemm_w8_plan: null plan");
+  GemmForm f;
+  const int rc = gemm_form(a, f, true);
+  if (rc == LTXK_OK) *plan = f.plan;
+  return rc;
 }
 
 extern "C" int ltxk_gemm_grouped_args_sizeof(void) { return (int)sizeof(ltxk_gemm_grouped_args); }
@@ -1436,7 +1498,7 @@ extern "C" int ltxk_gemm_bf16_grouped(const ltxk_gemm_grouped_args* a, void* str
   p.out2 = (bf16*)a->out2; p.n_split = a->n_split; p.ldo2 = a->ldo2;
   p.sumsq = a->sumsq; p.sumsq_ld = a->sumsq_ld;
   p.RT = f.RT; p.CT = f.CT;
-  p.part = nullptr; p.ksteps = a->K / GEMM_BK;
+  p.part = nullptr; p.ksteps = a->K / GEMM_BK; p.w_scale = nullptr;
   gp.w_tab = (const bf16* const*)a->W;
   gp.b_tab = (const bf16* const*)a->bias;
   gp.out_gs = a->out_gstride; gp.out2_gs = a->out2_gstride; gp.ss_gs = a->sumsq_gstride;

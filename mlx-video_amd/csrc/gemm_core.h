@@ -13,6 +13,15 @@
 // (row & 7): the DMA destination is lane-linear, so the permutation is applied to the per-lane
 // SOURCE address and again on the ds_read_b128 fragment reads (conflict-free for the 16x16x32
 // operand map).
+// W8 (weight-fp8) forms: the W half of a stage holds e4m3 bytes, 64-byte rows ([row][64 fp8]); the A half is unchanged.  A
+// 1-KiB LDS-DMA piece is then 16 rows x 64 B (half as many W pieces per wave), and a lane's fragment is the 8 consecutive
+// bytes of the 8 k-positions its bf16x8 holds in the bf16 form, read with ds_read_b64 and widened in registers by four
+// v_cvt_scalef32_pk_bf16_fp8 (scale 1.0: every e4m3 value is a bf16 value) in front of the first MFMA group that uses it:
+// the MFMAs, their operands and their order are those of the bf16 form.  ds_read_b64 banks over 256 B = four 64-byte rows
+// and conflicts inside a 32-lane half, which reads 16 rows x two 8-byte chunks: rows r, r+4, r+8, r+12 share 16 banks, so
+// the 16-byte chunk index (0..3) is XOR-swizzled by ((row >> 2) & 3) - each of the four rows then owns its own 16 bytes of
+// the shared banks for every k-quarter.  The swizzle unit is the DMA's 16 bytes, so it is again applied to the per-lane
+// source address.
 #pragma once
 #include "common.h"
 
@@ -35,15 +44,17 @@ __device__ __forceinline__ const __attribute__((address_space(1))) T* opaque_gpt
 constexpr int GEMM_BK = 64;
 constexpr int GEMM_THREADS = 512;
 
-template <int TT, int WN, int NT = 4>
+template <int TT, int WN, int NT = 4, bool W8 = false>
 struct GemmGeom {
   static constexpr int WM = 8 / WN;
   static constexpr int BM = 16 * TT * WM;
   static constexpr int BN = 16 * NT * WN;
   static_assert(BN % 64 == 0, "whole 1-KiB W pieces per wave");
-  static constexpr int W_PIECES = BN / 8;          // 1 KiB pieces (8 rows x 128 B)
+  static constexpr int W_ROW_BYTES = W8 ? GEMM_BK : GEMM_BK * 2;
+  static constexpr int W_PIECES = BN * W_ROW_BYTES / 1024;   // 1 KiB pieces (8 rows x 128 B; fp8: 16 rows x 64 B)
+  static_assert(W_PIECES % 8 == 0, "the same number of W pieces for every wave");
   static constexpr int W_PER_WAVE = W_PIECES / 8;
-  static constexpr int W_STAGE_BYTES = BN * GEMM_BK * 2;
+  static constexpr int W_STAGE_BYTES = BN * W_ROW_BYTES;
   static constexpr int A_PIECES = BM / 8;
   static constexpr int A_BASE = A_PIECES / 8;      // pieces per wave (floor)
   static constexpr int A_REM = A_PIECES % 8;       // first A_REM waves take one more
@@ -112,6 +123,22 @@ __device__ __forceinline__ void wait_stage_and_barrier(int keep) {
   }
 }
 
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+
+// 8 e4m3fn bytes -> the bf16x8 with the same values in the same order (exact: e4m3 is a subset of bf16)
+__device__ __forceinline__ bf16x8 fp8x8_to_bf16x8(u32x2 v) {
+  const bf16x2 a = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(v[0], 1.0f, false);
+  const bf16x2 b = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(v[0], 1.0f, true);
+  const bf16x2 c = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(v[1], 1.0f, false);
+  const bf16x2 d = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(v[1], 1.0f, true);
+  return bf16x8{a[0], a[1], b[0], b[1], c[0], c[1], d[0], d[1]};
+}
+
+// Byte offset, inside a lane's 64-byte fp8 W row, of its fragment of K-sub-step ks (the swizzle of the header comment)
+__device__ __forceinline__ int w8_koff(int lane, int ks) {
+  return ((ks * 4 + (lane >> 4)) ^ (((lane >> 2) & 3) << 1)) << 3;
+}
+
 // Operand roles.  SWAP=false: acc tile = D[n (4 regs)][row (lane&15)]  (W is the MFMA A operand), so a lane
 // holds 4 consecutive output columns of one row: 8-byte row-major stores.  SWAP=true: acc tile =
 // D[row (4 regs)][n (lane&15)]: 4 consecutive rows of one column, used for the transposed (V^T) output.
@@ -121,25 +148,29 @@ __device__ __forceinline__ void wait_stage_and_barrier(int keep) {
 // sprinkled one (or PPG) per group instead of being issued as a burst in front of the MFMAs — the
 // DMA issue cost (~60-180 cycles per 1-KiB piece) then hides under the matrix pipe.
 // issue(i): launch this wave's i-th LDS-DMA piece of the prefetched stage (no-op for i >= count).
-template <int TT, int WN, bool SWAP, int NT = 4, class IssueFn>
+template <int TT, int WN, bool SWAP, int NT = 4, bool W8 = false, class IssueFn>
 __device__ __forceinline__ void mma_stage_pipelined(const char* st, int wm, int wn, int lane,
                                                     f32x4 (&acc)[TT][NT], IssueFn&& issue) {
-  using G = GemmGeom<TT, WN, NT>;
+  using G = GemmGeom<TT, WN, NT, W8>;
   constexpr int NG = 2 * TT;                                   // MFMA groups per K-step
   constexpr int MAXP = G::W_PER_WAVE + G::MAXA;                // LDS-DMA pieces per wave per stage
   constexpr int PPG = (MAXP + NG - 1) / NG;
-  const char* wb = st + (wn * 16 * NT) * 128 + (lane & 15) * 128;
+  const char* wb = st + (wn * 16 * NT + (lane & 15)) * G::W_ROW_BYTES;
   const char* ab = st + G::W_STAGE_BYTES + (wm * TT * 16) * 128 + (lane & 15) * 128;
   const int koff0 = (((lane >> 4)) ^ (lane & 7)) << 4;
   const int koff1 = (((4 + (lane >> 4))) ^ (lane & 7)) << 4;
+  const int kw0 = w8_koff(lane, 0), kw1 = w8_koff(lane, 1);
   bf16x8 wf[2][NT], af[2][TT];
+  u32x2 wraw[2][NT];                  // W8: the fragments as read, widened into wf in front of their first MFMA group
   // flat read order: W0[0..NT-1], A0[0..TT-1], W1[0..NT-1], A1[0..TT-1]
   auto rd = [&](int idx) {
     // idx is a compile-time constant after unrolling
     const int ks = idx / (NT + TT), r = idx % (NT + TT);
     const int ko = ks ? koff1 : koff0;
-    if (r < NT) wf[ks][r] = *(const bf16x8*)(wb + r * 2048 + ko);
-    else af[ks][r - NT] = *(const bf16x8*)(ab + (r - NT) * 2048 + ko);
+    if (r < NT) {
+      if constexpr (W8) wraw[ks][r] = *(const u32x2*)(wb + r * 1024 + (ks ? kw1 : kw0));
+      else wf[ks][r] = *(const bf16x8*)(wb + r * 2048 + ko);
+    } else af[ks][r - NT] = *(const bf16x8*)(ab + (r - NT) * 2048 + ko);
   };
   constexpr int TOTAL = 2 * (NT + TT);
   auto need = [](int g) { return (g / TT) * (NT + TT) + NT + (g % TT) + 1; };
@@ -157,6 +188,12 @@ __device__ __forceinline__ void mma_stage_pipelined(const char* st, int wm, int 
 #pragma unroll
     for (int q = 0; q < PPG; ++q) issue(g * PPG + q);
     const int ks = g / TT, tt = g % TT;
+    if constexpr (W8) {
+      if (tt == 0) {
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) wf[ks][nt] = fp8x8_to_bf16x8(wraw[ks][nt]);
+      }
+    }
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt)
       acc[tt][nt] = SWAP ? __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[ks][tt], wf[ks][nt], acc[tt][nt], 0, 0, 0)
@@ -182,9 +219,9 @@ __device__ __forceinline__ void mma_stage_pipelined(const char* st, int wm, int 
 // all deferred groups use the ks=1 W fragments).  DG=2 hides the LDS cold start; DG=TT additionally puts a
 // wave half a K-step out of phase with a DG=2 wave — used for waves 4-7, the SIMD partners of waves 0-3, so
 // that the two waves of a SIMD do not hit their LDS-read bursts, DMA issues and MFMA-dense stretches together.
-template <int TT, int WN, bool SWAP, int DG = 2, int NT = 4>
+template <int TT, int WN, bool SWAP, int DG = 2, int NT = 4, bool W8 = false>
 struct MmaPipe {
-  using G = GemmGeom<TT, WN, NT>;
+  using G = GemmGeom<TT, WN, NT, W8>;
   static constexpr int PD = LTXK_PREFETCH_GROUPS;   // fragment reads run PD MFMA groups ahead of their use
   static constexpr int NG = 2 * TT;
   static constexpr int MAXP = G::W_PER_WAVE + G::MAXA;
@@ -198,6 +235,14 @@ struct MmaPipe {
   // fragment registers persist across K-steps: after step() wf[1][*] and af[1][TT-DG..TT-1] hold the operands
   // of the deferred groups; the next step() consumes them before overwriting them.
   bf16x8 wf[2][NT], af[2][TT];
+  // W8: the W fragments as read (8 fp8 bytes), widened into wf[ks] in front of the first MFMA group of K-sub-step ks; the
+  // groups deferred past the barrier then find bf16 operands in wf[1] exactly as in the bf16 form
+  u32x2 wraw[2][W8 ? NT : 1];
+
+  __device__ __forceinline__ void widen(int ks) {
+#pragma unroll
+    for (int nt = 0; nt < (W8 ? NT : 0); ++nt) wf[ks][nt] = fp8x8_to_bf16x8(wraw[ks][nt]);
+  }
 
   __device__ __forceinline__ void init() {
 #pragma unroll
@@ -219,18 +264,21 @@ struct MmaPipe {
 
   template <class IssueFn>
   __device__ __forceinline__ void step(const char* st, int wm, int wn, int lane, f32x4 (&acc)[TT][NT], IssueFn&& issue) {
-    const char* wb = st + (wn * 16 * NT) * 128 + (lane & 15) * 128;
+    const char* wb = st + (wn * 16 * NT + (lane & 15)) * G::W_ROW_BYTES;
     const char* ab = st + G::W_STAGE_BYTES + (wm * TT * 16) * 128 + (lane & 15) * 128;
     const int koff0 = (((lane >> 4)) ^ (lane & 7)) << 4;
     const int koff1 = (((4 + (lane >> 4))) ^ (lane & 7)) << 4;
+    const int kw0 = w8_koff(lane, 0), kw1 = w8_koff(lane, 1);
     auto rd = [&](int idx) {
       const int ks = idx / (NT + TT), r = idx % (NT + TT);
       const int ko = ks ? koff1 : koff0;
 #ifdef LTXK_PROBE_FEWER_LDS_READS      // energy probe only (WRONG results): the ks=1 fragments are copies of the ks=0 ones
       if (ks == 1) { if (r < NT) wf[1][r] = wf[0][r]; else af[1][r - NT] = af[0][r - NT]; return; }
 #endif
-      if (r < NT) wf[ks][r] = *(const bf16x8*)(wb + r * 2048 + ko);
-      else af[ks][r - NT] = *(const bf16x8*)(ab + (r - NT) * 2048 + ko);
+      if (r < NT) {
+        if constexpr (W8) wraw[ks][r < NT ? r : 0] = *(const u32x2*)(wb + r * 1024 + (ks ? kw1 : kw0));
+        else wf[ks][r] = *(const bf16x8*)(wb + r * 2048 + ko);
+      } else af[ks][r - NT] = *(const bf16x8*)(ab + (r - NT) * 2048 + ko);
     };
     // reads needed by real group g of THIS stage (flat order W0, A0[*], W1, A1[*]); g >= NG: everything
     auto need = [](int g) { return g < 0 ? 0 : (g >= NG ? TOTAL : (g / TT) * (NT + TT) + NT + (g % TT) + 1); };
@@ -258,6 +306,9 @@ struct MmaPipe {
       issued = target > issued ? target : issued;
 #pragma unroll
       for (int q = 0; q < PPG; ++q) issue((g + DG) * PPG + q);
+      if constexpr (W8) {
+        if (g % TT == 0) widen(g / TT);
+      }
       group(af[g / TT][g % TT], wf[g / TT], acc[g % TT]);
       __builtin_amdgcn_sched_barrier(0);
     }
@@ -265,6 +316,7 @@ struct MmaPipe {
 #pragma unroll
     for (int i = 0; i < TOTAL; ++i)
       if (i >= issued) rd(i);
+    if constexpr (W8 && DG == TT) widen(1);            // no real group of this step used the ks=1 fragments
   }
 
   __device__ __forceinline__ void finish(f32x4 (&acc)[TT][NT]) {

@@ -178,7 +178,7 @@ def generate_video(model_repo: Optional[str] = None, text_encoder_repo: Optional
                    noise_fn: Optional[Callable] = None, device=None, on_frames_ready: Optional[Callable] = None,
                    return_latents: bool = False, lora_in_place: Optional[bool] = None,
                    hoist_context: bool = False, stg_scale: Optional[float] = None, stg_blocks: Optional[list] = None,
-                   stg_mode: Optional[str] = None) -> np.ndarray:
+                   stg_mode: Optional[str] = None, enable_fp8: bool = False, fp8_scaling: str = "channel") -> np.ndarray:
     """See the module docstring.  Returns uint8 frames (F,H,W,3) (generate.py:4195-4197).
     ``hoist_context`` (not in the reference, off by default): the part of the forward that depends on the text context only -
     caption projection and the 48 cross-attention K / V^T projections, 3.37 TFLOP that the reference recomputes in every forward
@@ -186,7 +186,12 @@ def generate_video(model_repo: Optional[str] = None, text_encoder_repo: Optional
     same inputs, hence the same latents bit for bit, 8-10 % less work per dev step at 512x512x33.
     ``stg_scale`` / ``stg_blocks`` / ``stg_mode`` (--stg-scale / --stg-blocks / --stg-mode; the reference parses and ignores
     them): spatio-temporal guidance in every guided (denoise_dev) stage - the dev pipeline, and stage 2 with ``stage2_dev``.
-    A non-zero ``stg_scale`` on a run without a guided stage is a ValueError.  None / 0: off."""
+    A non-zero ``stg_scale`` on a run without a guided stage is a ValueError.  None / 0: off.
+    ``enable_fp8`` (--enable-fp8; the reference parses and ignores it): every transformer this call builds keeps its Linear
+    matrices as FP8 e4m3 panels, calculations still in bf16 (ltxk_gemm_w8) - half the weight bytes in memory and per forward.
+    ``fp8_scaling``: "channel" (per-output-channel scale, amax -> 448) or "none" (the upstream plain cast).  LoRAs are merged in
+    bf16 and the merged weights quantised (never merged into fp8 panels), so a LoRA-merged stage-2 transformer is a fresh fp8
+    model.  A ``transformer=`` / ``stage2_transformer=`` passed in is used as it is."""
     t_start = time.perf_counter()
     if isinstance(pipeline, str):
         pipeline = PipelineType(pipeline)
@@ -215,6 +220,16 @@ def generate_video(model_repo: Optional[str] = None, text_encoder_repo: Optional
                          "without stage2_dev (--stage2-dev)")
     if stg["stg_mode"] not in ("stg_v", "stg_av"):
         raise ValueError(f"Unknown stg_mode: {stg_mode!r}")
+    from .weights import FP8_SCALINGS
+    if fp8_scaling not in FP8_SCALINGS:
+        raise ValueError(f"Unknown fp8_scaling: {fp8_scaling!r} (expected one of {FP8_SCALINGS})")
+
+    def _build(cfg_, weights_) -> LTXModel:
+        """A transformer from a module-key weight dict; under enable_fp8 from its quantised twin (an fp8 dict is kept as it is)."""
+        if enable_fp8:
+            from .weights import quantize_transformer_weights
+            weights_ = quantize_transformer_weights(weights_, fp8_scaling)
+        return LTXModel(cfg_, weights_)
 
     out_h, out_w = height, width
     height, width, crop = _pad_dims(height, width, 64 if is_distilled else 32)
@@ -236,19 +251,25 @@ def generate_video(model_repo: Optional[str] = None, text_encoder_repo: Optional
                              "transformer_weights= (the dict the transformer was built from) or a model_repo")
         from .lora import LoraSpec, apply_lora_to_weights
         merged = apply_lora_to_weights(transformer_weights, [LoraSpec(Path(pth), float(st)) for pth, st in lora_list], verbose=verbose)
-        return LTXModel(transformer_config or (transformer.config if transformer is not None else LTXModelConfig()), merged)
+        return _build(transformer_config or (transformer.config if transformer is not None else LTXModelConfig()), merged)
 
     # LoRAs may be merged INTO the model when nobody needs its un-merged weights again (`loras` alone: one merged model serves every
     # stage; `distilled_loras` alone: the stage-1 model is dead when stage 2 starts): by default only when the weights are loaded
     # here (this call owns them); a caller that passes its own model opts in explicitly
     if lora_in_place is None:
         lora_in_place = transformer is None and transformer_weights is None
+    if enable_fp8 and (transformer is None or transformer.weight_dtype != BF16):
+        # fp8 panels take no in-place merge: merge-then-quantise builds the merged model afresh, and an fp8 replica is no
+        # larger than what the in-place merge was saving
+        lora_in_place = False
     if transformer is None and transformer_weights is None:
         if model_repo is None:
             raise FileNotFoundError("no transformer: pass transformer= or a local model_repo directory with LTX-2 safetensors")
         from .weights import load_pipeline_modules
         mods = load_pipeline_modules(model_repo, device or torch.device("cuda:0"), need_encoder=bool(images_list or video_conditionings),
-                                     need_upsampler=is_distilled, build_transformer=False)
+                                     need_upsampler=is_distilled, build_transformer=False,
+                                     # with LoRAs to merge the base dict stays bf16 (they are merged in bf16, then quantised)
+                                     fp8=enable_fp8 and not (loras or distilled_loras), fp8_scaling=fp8_scaling)
         transformer_weights, transformer_config = mods["transformer_weights"], mods["transformer_config"]
         vae_decoder = vae_decoder or mods["vae_decoder"]
         vae_encoder, upsampler = vae_encoder or mods.get("vae_encoder"), upsampler or mods.get("upsampler")
@@ -261,12 +282,12 @@ def generate_video(model_repo: Optional[str] = None, text_encoder_repo: Optional
                                  "(the dict the transformer was built from) or a model_repo")
             from .lora import LoraSpec, apply_lora_to_weights
             if transformer is None:
-                transformer = LTXModel(transformer_config or LTXModelConfig(), transformer_weights)
+                transformer = _build(transformer_config or LTXModelConfig(), transformer_weights)
             apply_lora_to_weights(transformer.weight_views(), [LoraSpec(Path(pth), float(st)) for pth, st in loras], verbose=verbose, in_place=True)
         else:
             transformer = _with_loras(loras, "loras")              # stage 1 / dev: base + loras
     elif transformer is None:
-        transformer = LTXModel(transformer_config or LTXModelConfig(), transformer_weights)
+        transformer = _build(transformer_config or LTXModelConfig(), transformer_weights)
     if vae_decoder is None:
         raise FileNotFoundError("no VAE decoder: pass vae_decoder= or a model_repo containing VAE weights")
     dev = device or transformer.tables.device
@@ -498,6 +519,11 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--stg-blocks", type=int, nargs="*", default=None, help="Blocks whose video self-attention the STG pass skips (default: all)")
     ap.add_argument("--stg-mode", type=str, choices=["stg_av", "stg_v"], default=None,
                     help="stg_av acts as stg_v: the model has no audio branch")
+    # the reference's flag (it parses and ignores it): keep the model in lower precision, calculations still in bfloat16
+    ap.add_argument("--enable-fp8", action="store_true", default=False,
+                    help="Keep the transformer's Linear weights as FP8 (e4m3) panels; calculations still in bfloat16")
+    ap.add_argument("--fp8-scaling", type=str, choices=["channel", "none"], default="channel",
+                    help="(not in the reference CLI) channel: per-output-channel scale; none: the plain cast")
     return ap
 
 
@@ -552,7 +578,11 @@ def main(argv: Optional[Sequence[str]] = None) -> None:
         videos.append((args.reference_video, 0, 1.0))
     if args.synthetic:
         from .video_vae import random_decoder_weights
-        kw["transformer"] = LTXModel.random_init(LTXModelConfig(num_layers=args.layers), dev)
+        if args.enable_fp8:       # the weight dict instead of the model: generate_video quantises what it builds
+            kw["transformer_config"] = LTXModelConfig(num_layers=args.layers)
+            kw["transformer_weights"] = LTXModel.random_weights(kw["transformer_config"], dev)
+        else:
+            kw["transformer"] = LTXModel.random_init(LTXModelConfig(num_layers=args.layers), dev)
         kw["vae_decoder"] = LTX2VideoDecoder(random_decoder_weights(dev))
         g = torch.Generator(device=dev).manual_seed(43)
         kw["prompt_embeds"] = torch.randn((1, 1024, 3840), generator=g, device=dev).to(BF16)
@@ -580,7 +610,8 @@ def main(argv: Optional[Sequence[str]] = None) -> None:
                    stage2_steps=args.stage2_steps, sigma_subsample=args.sigma_subsample, verbose=True, device=dev,
                    images=images, video_conditionings=videos, loras=args.lora, distilled_loras=args.distilled_lora,
                    conditioning_mode=args.conditioning_mode, stream=args.stream, stage2_dev=args.stage2_dev,
-                   fp32_euler=args.fp32_euler, stg_scale=args.stg_scale, stg_blocks=args.stg_blocks, stg_mode=args.stg_mode, **kw)
+                   fp32_euler=args.fp32_euler, stg_scale=args.stg_scale, stg_blocks=args.stg_blocks, stg_mode=args.stg_mode,
+                   enable_fp8=args.enable_fp8, fp8_scaling=args.fp8_scaling, **kw)
 
 
 if __name__ == "__main__":

@@ -151,6 +151,10 @@ def apply_lora_to_weights(weights: Dict[str, torch.Tensor], lora_specs: Iterable
                 Bp, At = _pack_group([a for _, a, _ in chunk], [b for _, _, b in chunk], dev)
                 for i, (key, _, _) in enumerate(chunk):
                     w = updated[key]
+                    if w.dtype != BF16:
+                        # (an e4m3 panel cannot take a bf16 delta: it would be re-rounded to 3 mantissa bits per merge)
+                        raise TypeError(f"LoRA merge into {key} ({w.dtype}): weights are merged in bf16 and quantised afterwards - "
+                                        "merge into the bf16 weight dict (in_place=False) and build the fp8 model from the result")
                     if in_place:
                         if w.dim() != 2 or not w.is_contiguous():
                             raise ValueError(f"in-place LoRA merge needs a contiguous 2-D weight, got {key} {tuple(w.shape)}")

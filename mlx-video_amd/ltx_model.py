@@ -27,6 +27,7 @@ from . import ops
 from .guidance import BatchedPerturbationConfig, PerturbationType
 
 BF16 = torch.bfloat16
+FP8 = torch.float8_e4m3fn
 
 
 @dataclass(frozen=True)
@@ -105,7 +106,14 @@ def precompute_freqs_cis(positions: torch.Tensor, dim: int, theta: float = 10000
 
 class _Block:
     __slots__ = ("wqkv", "bqkv", "wqn", "wkn", "wqkn", "wo", "bo", "wq2", "bq2", "wkv2", "bkv2",
-                 "wqn2", "wkn2", "wo2", "bo2", "w1", "b1", "w2", "b2")
+                 "wqn2", "wkn2", "wo2", "bo2", "w1", "b1", "w2", "b2",
+                 # per-output-channel fp32 scales of the e4m3 panels (None: bf16 model, or an unscaled fp8 panel)
+                 "sqkv", "so", "sq2", "skv2", "so2", "s1", "s2")
+
+
+def _rows(t: Optional[torch.Tensor], a: Optional[int], b: Optional[int]) -> Optional[torch.Tensor]:
+    """t[a:b] of a panel's scale vector, which may be absent."""
+    return None if t is None else t[a:b]
 
 
 class ContextKV:
@@ -174,33 +182,60 @@ class LTXModel:
                 raise TypeError(f"weight {k}: expected a bf16 device tensor")
             return t.contiguous()
 
-        self.patchify_w, self.patchify_b = g("patchify_proj.weight"), g("patchify_proj.bias")
+        # The (out,in) matrices of the Linear layers are all bf16, or all float8_e4m3fn (weights.transformer_weights(fp8=True)):
+        # an fp8 matrix may come with a per-output-channel scale under "<key>_scale" and stays fp8 inside the model - every
+        # GEMM over it is ltxk_gemm_w8, no bf16 copy of a panel is ever made.
+        mats = [k for k in self.expected_keys(cfg) if k.endswith(".weight") and W[k].ndim == 2]
+        self.weight_dtype = FP8 if any(W[k].dtype == FP8 for k in mats) else BF16
+        fp8 = self.weight_dtype == FP8
+
+        def gw(k):
+            """-> [matrix, scale or None]"""
+            if not fp8:
+                return [g(k), None]
+            t, sc = W[k], W.get(k + "_scale")
+            if t.dtype != FP8 or not t.is_cuda:
+                raise TypeError(f"weight {k}: an fp8 model takes every Linear matrix as a float8_e4m3fn device tensor, got {t.dtype}")
+            if sc is not None and (sc.dtype != torch.float32 or sc.shape != (t.shape[0],) or sc.device != t.device):
+                raise TypeError(f"weight {k}_scale: expected a ({t.shape[0]},) float32 device tensor")
+            return [t.contiguous(), None if sc is None else sc.contiguous()]
+
+        def cat(parts):
+            """Row-wise concatenation of [matrix, scale] pairs into one packed panel (fp8 through its bytes) and one scale vector."""
+            ws, ss = [w for w, _ in parts], [sc for _, sc in parts]
+            w = torch.cat([t.view(torch.uint8) for t in ws], 0).view(FP8) if fp8 else torch.cat(ws, 0)
+            if all(sc is None for sc in ss):
+                return w, None
+            ones = [torch.ones(t.shape[0], dtype=torch.float32, device=t.device) if sc is None else sc for t, sc in parts]
+            return w, torch.cat(ones, 0).contiguous()
+
+        (self.patchify_w, self.patchify_s), self.patchify_b = gw("patchify_proj.weight"), g("patchify_proj.bias")
         p = "adaln_single.emb.timestep_embedder"
-        self.t1_w, self.t1_b = g(f"{p}.linear1.weight"), g(f"{p}.linear1.bias")
-        self.t2_w, self.t2_b = g(f"{p}.linear2.weight"), g(f"{p}.linear2.bias")
-        self.ada_w, self.ada_b = g("adaln_single.linear.weight"), g("adaln_single.linear.bias")
-        self.c1_w, self.c1_b = g("caption_projection.linear1.weight"), g("caption_projection.linear1.bias")
-        self.c2_w, self.c2_b = g("caption_projection.linear2.weight"), g("caption_projection.linear2.bias")
+        (self.t1_w, self.t1_s), self.t1_b = gw(f"{p}.linear1.weight"), g(f"{p}.linear1.bias")
+        (self.t2_w, self.t2_s), self.t2_b = gw(f"{p}.linear2.weight"), g(f"{p}.linear2.bias")
+        (self.ada_w, self.ada_s), self.ada_b = gw("adaln_single.linear.weight"), g("adaln_single.linear.bias")
+        (self.c1_w, self.c1_s), self.c1_b = gw("caption_projection.linear1.weight"), g("caption_projection.linear1.bias")
+        (self.c2_w, self.c2_s), self.c2_b = gw("caption_projection.linear2.weight"), g("caption_projection.linear2.bias")
         self.head_table = g("scale_shift_table").reshape(1, 2, -1)
-        self.out_w, self.out_b = g("proj_out.weight"), g("proj_out.bias")
+        (self.out_w, self.out_s), self.out_b = gw("proj_out.weight"), g("proj_out.bias")
         self.blocks: List[_Block] = []
         tables = []
         for i in range(cfg.num_layers):
             pre = f"transformer_blocks.{i}"
             b = _Block()
             # one (3D,D) panel for to_q|to_k|to_v: a single GEMM launch writes q|k row-major and V^T (split output)
-            b.wqkv = torch.cat([g(f"{pre}.attn1.to_{n}.weight") for n in "qkv"], 0)
+            b.wqkv, b.sqkv = cat([gw(f"{pre}.attn1.to_{n}.weight") for n in "qkv"])
             b.bqkv = torch.cat([g(f"{pre}.attn1.to_{n}.bias") for n in "qkv"], 0)
             b.wqn, b.wkn = g(f"{pre}.attn1.q_norm.weight"), g(f"{pre}.attn1.k_norm.weight")
             b.wqkn = torch.cat([b.wqn, b.wkn], 0)
-            b.wo, b.bo = g(f"{pre}.attn1.to_out.weight"), g(f"{pre}.attn1.to_out.bias")
-            b.wq2, b.bq2 = g(f"{pre}.attn2.to_q.weight"), g(f"{pre}.attn2.to_q.bias")
-            b.wkv2 = torch.cat([g(f"{pre}.attn2.to_k.weight"), g(f"{pre}.attn2.to_v.weight")], 0)     # text k | V^T, one launch
+            (b.wo, b.so), b.bo = gw(f"{pre}.attn1.to_out.weight"), g(f"{pre}.attn1.to_out.bias")
+            (b.wq2, b.sq2), b.bq2 = gw(f"{pre}.attn2.to_q.weight"), g(f"{pre}.attn2.to_q.bias")
+            b.wkv2, b.skv2 = cat([gw(f"{pre}.attn2.to_k.weight"), gw(f"{pre}.attn2.to_v.weight")])     # text k | V^T, one launch
             b.bkv2 = torch.cat([g(f"{pre}.attn2.to_k.bias"), g(f"{pre}.attn2.to_v.bias")], 0)
             b.wqn2, b.wkn2 = g(f"{pre}.attn2.q_norm.weight"), g(f"{pre}.attn2.k_norm.weight")
-            b.wo2, b.bo2 = g(f"{pre}.attn2.to_out.weight"), g(f"{pre}.attn2.to_out.bias")
-            b.w1, b.b1 = g(f"{pre}.ff.proj_in.weight"), g(f"{pre}.ff.proj_in.bias")
-            b.w2, b.b2 = g(f"{pre}.ff.proj_out.weight"), g(f"{pre}.ff.proj_out.bias")
+            (b.wo2, b.so2), b.bo2 = gw(f"{pre}.attn2.to_out.weight"), g(f"{pre}.attn2.to_out.bias")
+            (b.w1, b.s1), b.b1 = gw(f"{pre}.ff.proj_in.weight"), g(f"{pre}.ff.proj_in.bias")
+            (b.w2, b.s2), b.b2 = gw(f"{pre}.ff.proj_out.weight"), g(f"{pre}.ff.proj_out.bias")
             tables.append(g(f"{pre}.scale_shift_table"))
             self.blocks.append(b)
         self.tables = torch.stack(tables, 0).contiguous()      # (L,6,D)
@@ -216,6 +251,10 @@ class LTXModel:
         """Checkpoint key -> the (out,in) matrix as it lives inside THIS model: the packed q|k|v and text k|v panels are
         returned as their row ranges.  Writing through these views changes the model (lora.apply_lora_to_weights(...,
         in_place=True): the stage-2 transformer of the distilled pipeline without a second 21-GB replica, generate.py:3229-3283)."""
+        if self.weight_dtype != BF16:
+            raise TypeError("weight_views: this model keeps its matrices in float8_e4m3fn, which cannot take an in-place LoRA merge; "
+                            "merge into the bf16 weight dict (lora.apply_lora_to_weights(weights, specs), the fresh-copy path), "
+                            "quantise the result (weights.quantize_transformer_weights) and build a model from it")
         D = self.inner_dim
         v = {"patchify_proj.weight": self.patchify_w, "adaln_single.emb.timestep_embedder.linear1.weight": self.t1_w,
              "adaln_single.emb.timestep_embedder.linear2.weight": self.t2_w, "adaln_single.linear.weight": self.ada_w,
@@ -228,6 +267,27 @@ class LTXModel:
             v[f"{pre}.attn2.to_k.weight"], v[f"{pre}.attn2.to_v.weight"] = b.wkv2[:D], b.wkv2[D:]
             v[f"{pre}.attn2.to_out.weight"], v[f"{pre}.ff.proj_in.weight"], v[f"{pre}.ff.proj_out.weight"] = b.wo2, b.w1, b.w2
         return v
+
+    def weight_bytes(self) -> int:
+        """Device bytes of everything this model holds of its checkpoint: the matrices (bf16, or e4m3 panels plus their scale
+        vectors), biases, norm weights and scale-shift tables."""
+        seen, total = set(), 0
+
+        def add(t):
+            nonlocal total
+            if torch.is_tensor(t) and t.data_ptr() not in seen:
+                seen.add(t.data_ptr())
+                total += t.numel() * t.element_size()
+
+        for n in ("patchify", "t1", "t2", "ada", "c1", "c2", "out"):
+            for suf in ("_w", "_s", "_b"):
+                add(getattr(self, n + suf))
+        add(self.head_table); add(self.tables); add(self.wkn2_all)
+        for b in self.blocks:
+            for n in _Block.__slots__:
+                if n not in ("wkn2", "wqkn"):          # a row of wkn2_all; a copy of wqn | wkn made for one launch form
+                    add(getattr(b, n))
+        return total
 
     @staticmethod
     def expected_keys(cfg: LTXModelConfig) -> List[str]:
@@ -308,8 +368,8 @@ class LTXModel:
         """ltx.py:77-89: caption_projection, (B,S,3840) -> (B*S,D)."""
         b, s, c = context.shape
         sk = not self.batch_invariant
-        h = ops.gemm(context.reshape(b * s, c), self.c1_w, self.c1_b, epilogue=ops.EPI_BIAS_GELU, split_k=sk)
-        return ops.gemm(h, self.c2_w, self.c2_b, out=out, split_k=sk)
+        h = ops.gemm(context.reshape(b * s, c), self.c1_w, self.c1_b, epilogue=ops.EPI_BIAS_GELU, split_k=sk, w_scale=self.c1_s)
+        return ops.gemm(h, self.c2_w, self.c2_b, out=out, split_k=sk, w_scale=self.c2_s)
 
     def _context_kv(self, blk: _Block, ctx: torch.Tensor, b: int, s: int, sp: int, out: Optional[tuple] = None):
         D, H, eps = self.inner_dim, self.num_attention_heads, self.config.norm_eps
@@ -324,10 +384,10 @@ class LTXModel:
         st = ss if self.fuse & 2 else None
         sk = not self.batch_invariant
         if self.fuse & 1:
-            ops.gemm(ctx, blk.wkv2, blk.bkv2, out=k2, out2=vt2, n_split=D, out_tokens_per_batch=s, sumsq=st, split_k=sk)
+            ops.gemm(ctx, blk.wkv2, blk.bkv2, out=k2, out2=vt2, n_split=D, out_tokens_per_batch=s, sumsq=st, split_k=sk, w_scale=blk.skv2)
         else:
-            ops.gemm(ctx, blk.wkv2[:D], blk.bkv2[:D], out=k2, sumsq=st, split_k=sk)
-            ops.gemm(ctx, blk.wkv2[D:], blk.bkv2[D:], out=vt2, out_tokens_per_batch=s, split_k=sk)
+            ops.gemm(ctx, blk.wkv2[:D], blk.bkv2[:D], out=k2, sumsq=st, split_k=sk, w_scale=_rows(blk.skv2, None, D))
+            ops.gemm(ctx, blk.wkv2[D:], blk.bkv2[D:], out=vt2, out_tokens_per_batch=s, split_k=sk, w_scale=_rows(blk.skv2, D, None))
         ops.qknorm_rope(k2, 1, D, blk.wkn2, None, None, s, H, eps, sumsq=st)
         return k2, vt2, ss
 
@@ -336,6 +396,8 @@ class LTXModel:
         the library would split K at this row count (small M with the split-K scratch on offer)."""
         D = self.inner_dim
         if not self.grouped_context_kv or (self.fuse & 3) != 3 or D % 256 != 0:
+            return False
+        if self.weight_dtype != BF16:         # the grouped launch has no weight-fp8 form: per block (the same bits)
             return False
         return not ops.gemm_plan(b * s, 2 * D, D, n_split=D, out_tokens_per_batch=s, sumsq=True,
                                  split_k=not self.batch_invariant).split_k
@@ -411,11 +473,11 @@ class LTXModel:
         P = D // 64
         sk = not self.batch_invariant
         xss = torch.empty((M, P), dtype=torch.float32, device=dev)
-        x = ops.gemm(latent.reshape(M, C), self.patchify_w, self.patchify_b, sumsq=xss, split_k=sk)
+        x = ops.gemm(latent.reshape(M, C), self.patchify_w, self.patchify_b, sumsq=xss, split_k=sk, w_scale=self.patchify_s)
         tproj = ops.timestep_embed(plan.values, 256, float(cfg.timestep_scale_multiplier))
-        h = ops.gemm(tproj, self.t1_w, self.t1_b, epilogue=ops.EPI_BIAS_SILU, split_k=sk)
-        emb = ops.gemm(h, self.t2_w, self.t2_b, split_k=sk)               # embedded_timestep (U,D)
-        ada = ops.gemm(ops.silu(emb), self.ada_w, self.ada_b, split_k=sk)   # (U,6D)
+        h = ops.gemm(tproj, self.t1_w, self.t1_b, epilogue=ops.EPI_BIAS_SILU, split_k=sk, w_scale=self.t1_s)
+        emb = ops.gemm(h, self.t2_w, self.t2_b, split_k=sk, w_scale=self.t2_s)               # embedded_timestep (U,D)
+        ada = ops.gemm(ops.silu(emb), self.ada_w, self.ada_b, split_k=sk, w_scale=self.ada_s)   # (U,6D)
         # (L,U,6,D): shift, 1+scale, gate, shift, 1+scale, gate - the (1 + scale) factor is the same for every token of a row
         # (without the carried row statistics the self-reducing norm kernel takes the raw scale and adds 1 itself)
         mods = ops.ada_combine(self.tables, ada, cfg.num_layers, U, 6, D, one_plus_mask=0b010010 if self.fuse & 2 else 0)
@@ -479,10 +541,11 @@ class LTXModel:
             # with q|k|v as ONE launch (M=1296: 39.4 against 41.2 ms, 3328: 87.6 / 89.2, 5184: 141.5 / 143.8, 6656: 161.5 / 164.7;
             # scripts/exp_qkv_one_launch.py), and at small M every launch is a weight stream with ~5 us of fixed cost)
             if fq and (not (self.fuse & 8) or M <= ops.SPLITK_MAX_M or M % 320 != 0):
-                ops.gemm(nx, blk.wqkv, blk.bqkv, out=qk, out2=vt, n_split=2 * D, out_tokens_per_batch=N, sumsq=s_qk, split_k=sk)
+                ops.gemm(nx, blk.wqkv, blk.bqkv, out=qk, out2=vt, n_split=2 * D, out_tokens_per_batch=N, sumsq=s_qk, split_k=sk,
+                         w_scale=blk.sqkv)
             else:
-                ops.gemm(nx, blk.wqkv[:2 * D], blk.bqkv[:2 * D], out=qk, sumsq=s_qk, split_k=sk)
-                ops.gemm(nx, blk.wqkv[2 * D:], blk.bqkv[2 * D:], out=vt, out_tokens_per_batch=N, split_k=sk)
+                ops.gemm(nx, blk.wqkv[:2 * D], blk.bqkv[:2 * D], out=qk, sumsq=s_qk, split_k=sk, w_scale=_rows(blk.sqkv, None, 2 * D))
+                ops.gemm(nx, blk.wqkv[2 * D:], blk.bqkv[2 * D:], out=vt, out_tokens_per_batch=N, split_k=sk, w_scale=_rows(blk.sqkv, 2 * D, None))
             skip = skip_rows[li]
             if fp:
                 ops.qknorm_rope(qk[:, D:], 1, D, blk.wkn, cos, sin, N, H, eps, sumsq=qkss[:, P:])
@@ -499,10 +562,10 @@ class LTXModel:
             if skip:          # STG: the skipped rows' attention output is their value projection, v = (V^T)^T
                 ops.attn_value_passthrough(vt, att, B, N, sum(1 << r for r in skip))
             ops.gemm(att, blk.wo, blk.bo, epilogue=ops.EPI_BIAS_GATE_RES, out=x, resid=x,
-                     gate=mod[:, 2], gate_row=tok2row, gate_stride=ms, sumsq=s_x, split_k=sk)
+                     gate=mod[:, 2], gate_row=tok2row, gate_stride=ms, sumsq=s_x, split_k=sk, w_scale=blk.so)
             # text cross-attention (transformer.py:257-261)
             ops.rmsnorm_modulate(x, eps, out=nx, sumsq=s_x)
-            ops.gemm(nx, blk.wq2, blk.bq2, out=q2, sumsq=s_q2, split_k=sk)
+            ops.gemm(nx, blk.wq2, blk.bq2, out=q2, sumsq=s_q2, split_k=sk, w_scale=blk.sq2)
             if ctx_kv is not None:
                 kv = ctx_kv.kv[li]
             elif kv_all is not None:
@@ -514,18 +577,18 @@ class LTXModel:
             else:
                 ops.qknorm_rope(q2, 1, D, blk.wqn2, None, None, N, H, eps, sumsq=s_q2)
                 ops.flash_attn(q2, kv[0], kv[1], att, B, H, N, S, scale, tail_split=ts_)
-            ops.gemm(att, blk.wo2, blk.bo2, epilogue=ops.EPI_BIAS_RES, out=x, resid=x, sumsq=s_x, split_k=sk)
+            ops.gemm(att, blk.wo2, blk.bo2, epilogue=ops.EPI_BIAS_RES, out=x, resid=x, sumsq=s_x, split_k=sk, w_scale=blk.so2)
             # feed-forward (transformer.py:343-347)
             ops.rmsnorm_modulate(x, eps, mod[:, 4], mod[:, 3], ms, tok2row, out=nx, sumsq=s_x, scale_is_one_plus=bool(fs))
-            ops.gemm(nx, blk.w1, blk.b1, epilogue=ops.EPI_BIAS_GELU, out=hff, split_k=sk)
+            ops.gemm(nx, blk.w1, blk.b1, epilogue=ops.EPI_BIAS_GELU, out=hff, split_k=sk, w_scale=blk.s1)
             ops.gemm(hff, blk.w2, blk.b2, epilogue=ops.EPI_BIAS_GATE_RES, out=x, resid=x,
-                     gate=mod[:, 5], gate_row=tok2row, gate_stride=ms, sumsq=s_x, split_k=sk)
+                     gate=mod[:, 5], gate_row=tok2row, gate_stride=ms, sumsq=s_x, split_k=sk, w_scale=blk.s2)
             if hidden is not None:
                 hidden.append(x.reshape(B, N, D).clone())
 
         # --- output head (ltx.py:432-457) ---
         ops.layernorm_modulate(x, eps, head[:, 1], head[:, 0], 2 * D, tok2row, out=nx)
-        v = ops.gemm(nx, self.out_w, self.out_b, split_k=sk)
+        v = ops.gemm(nx, self.out_w, self.out_b, split_k=sk, w_scale=self.out_s)
         return v.reshape(B, N, cfg.out_channels)
 
     def __call__(self, video: Optional[Modality] = None, audio: Optional[Modality] = None,

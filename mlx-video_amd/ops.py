@@ -14,6 +14,7 @@ from ._lib import AttnArgs, GemmArgs, GemmGroupedArgs, StepArgs, check
 
 EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_SILU, EPI_BIAS_GATE_RES, EPI_BIAS_RES, EPI_SCALE_RES = 0, 1, 2, 3, 4, 5
 BF16 = torch.bfloat16
+FP8 = torch.float8_e4m3fn
 
 
 class KernelTimer:
@@ -94,13 +95,23 @@ def gemm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], *, epil
          gate: Optional[torch.Tensor] = None, gate_row: Optional[torch.Tensor] = None,
          gate_stride: int = 0, out_tokens_per_batch: int = 0, alpha: float = 1.0,
          out2: Optional[torch.Tensor] = None, n_split: int = 0, sumsq: Optional[torch.Tensor] = None,
-         split_k: bool = True) -> torch.Tensor:
+         split_k: bool = True, w_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
     """out = epi(a @ w.T + bias).  a (M,K) (row stride may exceed K), w (N,K) contiguous.
+    ``w`` may be ``torch.float8_e4m3fn`` (ltxk_gemm_w8: the panel is read as fp8 and widened in registers; with no ``w_scale``
+    the result equals the bf16 call on ``w.to(bfloat16)`` bit for bit); ``w_scale`` (N) fp32 then multiplies the accumulator
+    per output channel before the bias.  A bf16 ``w`` takes ltxk_gemm_bf16 and no ``w_scale``.
     ``n_split``/``out2``: columns >= n_split go transposed per batch (out_tokens_per_batch tokens) to out2
     (B, N-n_split, ld).  ``sumsq``: (M, >= cols/64) fp32, receives the per-64-column sums of squares of the stored
     row-major outputs.  ``split_k=False``: no split-K scratch is offered, so the launch is single-pass (or big-tile) and
     a row's bits do not depend on M; with it the library may split K at M <= SPLITK_MAX_M (``gemm_plan`` tells)."""
-    _req(a, BF16, "gemm.a"); _req(w, BF16, "gemm.w")
+    w8 = w.dtype == FP8
+    _req(a, BF16, "gemm.a"); _req(w, FP8 if w8 else BF16, "gemm.w")
+    if w_scale is not None:
+        if not w8:
+            raise TypeError("gemm: w_scale goes with a float8_e4m3fn weight")
+        _req(w_scale, torch.float32, "gemm.w_scale")
+        if w_scale.shape != (w.shape[0],) or not w_scale.is_contiguous():
+            raise ValueError(f"gemm: w_scale must be a contiguous ({w.shape[0]},) vector, got {tuple(w_scale.shape)}")
     M, K = a.shape
     N = w.shape[0]
     if w.shape[1] != K or not w.is_contiguous() or a.stride(1) != 1:
@@ -130,6 +141,10 @@ def gemm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], *, epil
     if _offers_workspace(M, split_k):
         ws = _gemm_workspace(a.device)
         args.workspace, args.workspace_bytes = ws.data_ptr(), ws.numel() * 4
+    if w8:
+        with _timed("gemm_w8", 2.0 * M * N * K, 2.0 * (M * K + M * N) + 1.0 * N * K):
+            check(_lib.load().ltxk_gemm_w8(ctypes.byref(args), _p(w_scale), _stream()), "ltxk_gemm_w8")
+        return out
     with _timed("gemm_bf16", 2.0 * M * N * K, 2.0 * (M * K + N * K + M * N)):
         check(_lib.load().ltxk_gemm_bf16(ctypes.byref(args), _stream()), "ltxk_gemm_bf16")
     return out
@@ -156,11 +171,12 @@ _PLAN_ADDR = 1 << 12          # stands in for every device pointer of a planned 
 
 def gemm_plan(M: int, N: int, K: int, *, epilogue: int = EPI_BIAS, lda: Optional[int] = None, ldo: Optional[int] = None,
               out_tokens_per_batch: int = 0, n_split: int = 0, ldo2: Optional[int] = None, sumsq: bool = False,
-              split_k: bool = True, workspace: Optional[Tuple[int, int]] = None) -> GemmPlan:
+              split_k: bool = True, workspace: Optional[Tuple[int, int]] = None, w8: bool = False) -> GemmPlan:
     """The form ``gemm`` takes for an (M,K) x (N,K)^T launch with these options, decided on the host by the function the
     launch itself uses (no device needed).  The split-K scratch is offered exactly as ``gemm`` offers it (``split_k``,
     SPLITK_MAX_M); ``workspace=(address, bytes)`` offers that one instead (address 0: none).  Strides default to those of
-    contiguous tensors (V^T: tokens padded to 64).  Raises LtxkError where ``gemm`` would refuse the arguments."""
+    contiguous tensors (V^T: tokens padded to 64).  Raises LtxkError where ``gemm`` would refuse the arguments.
+    ``w8``: the plan of the same call with a float8_e4m3fn weight (ltxk_gemm_w8_plan)."""
     args = GemmArgs()
     args.A = args.W = args.out = _PLAN_ADDR
     args.M, args.N, args.K = M, N, K
@@ -182,7 +198,10 @@ def gemm_plan(M: int, N: int, K: int, *, epilogue: int = EPI_BIAS, lda: Optional
     elif _offers_workspace(M, split_k):
         args.workspace, args.workspace_bytes = _PLAN_ADDR, GEMM_WORKSPACE_BYTES
     pl = _lib.GemmPlan()
-    check(_lib.load().ltxk_gemm_plan(ctypes.byref(args), ctypes.byref(pl)), "ltxk_gemm_plan")
+    if w8:
+        check(_lib.load().ltxk_gemm_w8_plan(ctypes.byref(args), ctypes.byref(pl)), "ltxk_gemm_w8_plan")
+    else:
+        check(_lib.load().ltxk_gemm_plan(ctypes.byref(args), ctypes.byref(pl)), "ltxk_gemm_plan")
     return GemmPlan(pl.form, pl.tile_rows, pl.tile_cols, pl.row_tiles, pl.col_tiles, pl.slices, pl.ksteps)
 
 

@@ -29,6 +29,8 @@ class MLXPipelineConfig:
     stream: bool = False
     tiling: str = "auto"
     conditioning_mode: str = "replace"
+    fp8transformer: bool = False        # ltx_pipelines/utils/model_ledger.py:36; --enable-fp8
+    fp8_scaling: str = "channel"
 
 
 def _ensure_list(v):
@@ -86,7 +88,8 @@ def run_generate(prompt: str, pipeline: PipelineType, cfg: MLXPipelineConfig, ou
                             image=None, images=_normalize_images(images),
                             video_conditionings=_normalize_video_conditions(video_conditionings),
                             conditioning_mode=cfg.conditioning_mode, tiling=cfg.tiling, stream=cfg.stream, audio=cfg.audio,
-                            loras=_normalize_loras(loras), distilled_loras=_normalize_loras(distilled_loras), **inject)
+                            loras=_normalize_loras(loras), distilled_loras=_normalize_loras(distilled_loras),
+                            enable_fp8=cfg.fp8transformer, fp8_scaling=cfg.fp8_scaling, **inject)
     return output_path if output_path is not None else frames
 
 
@@ -113,6 +116,8 @@ class _Base:
     verbose: bool = False
     stream: bool = False
     tiling: str = "auto"
+    fp8transformer: bool = False
+    fp8_scaling: str = "channel"
 
     def _cfg(self, **over) -> MLXPipelineConfig:
         names = {f.name for f in fields(MLXPipelineConfig)}

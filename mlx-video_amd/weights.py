@@ -13,6 +13,10 @@ from typing import Dict, Iterable, List, Optional
 import torch
 
 BF16 = torch.bfloat16
+FP8 = torch.float8_e4m3fn
+FP8_MAX = 448.0                     # largest finite e4m3fn value
+FP8_SCALINGS = ("channel", "none")
+SCALE_SUFFIX = "_scale"             # "<name>.weight" (e4m3fn) is accompanied by "<name>.weight_scale" ((N) fp32) when it has one
 
 
 def _to_dev(t: torch.Tensor, device) -> torch.Tensor:
@@ -55,6 +59,56 @@ def read_metadata(path: Path) -> dict:
     return dict(scan_header(path).get("__metadata__") or {})
 
 
+def quantize_fp8(w: torch.Tensor, scaling: str = "channel"):
+    """(N,K) matrix -> (e4m3fn matrix, per-output-channel fp32 scale or None), so that w ~ w8 * scale[:, None].
+    "none": the plain cast of the upstream --enable-fp8 path (w.to(float8_e4m3fn)), no scale.
+    "channel": scale_n = amax_n / 448 - the row's largest magnitude lands on +-448 exactly and the row uses the whole e4m3
+    range; |w - dequantize| <= amax_n * 2^-4 (half an ulp of the 3-bit mantissa in the top binade).  A zero row gets scale 1."""
+    if scaling not in FP8_SCALINGS:
+        raise ValueError(f"fp8 scaling {scaling!r}: expected one of {FP8_SCALINGS}")
+    if w.ndim != 2:
+        raise ValueError(f"quantize_fp8: expected a matrix, got shape {tuple(w.shape)}")
+    wf = w.float()
+    if scaling == "none":
+        return w.to(FP8), None
+    amax = wf.abs().amax(dim=1)
+    scale = torch.where(amax > 0, amax / FP8_MAX, torch.ones_like(amax))
+    q = (wf / scale[:, None]).clamp(-FP8_MAX, FP8_MAX)
+    # the row's extreme element is +-448 by construction (x / (x / 448) may round one ulp off it)
+    q = torch.where(wf.abs() == amax[:, None], torch.copysign(torch.full_like(q, FP8_MAX), wf), q)
+    q = torch.where(wf == 0, torch.zeros_like(q), q)
+    return q.to(FP8), scale.contiguous()
+
+
+def dequantize_fp8(w8: torch.Tensor, scale: Optional[torch.Tensor] = None, dtype=torch.float32) -> torch.Tensor:
+    """The matrix an e4m3fn panel (and its per-output-channel scale) stands for, in ``dtype``."""
+    w = w8.float()
+    if scale is not None:
+        w = w * scale.float()[:, None]
+    return w.to(dtype)
+
+
+def is_fp8_matrix_key(key: str, t: torch.Tensor) -> bool:
+    """The tensors --enable-fp8 keeps in e4m3: the (out,in) matrices of the Linear layers (every one of them is a GEMM panel
+    of LTXModel._pack); biases, norm weights and the scale-shift tables stay bf16."""
+    return key.endswith(".weight") and t.ndim == 2
+
+
+def _put_transformer_tensor(out: Dict[str, torch.Tensor], key: str, v: torch.Tensor, device, fp8: bool, fp8_scaling: str) -> None:
+    """One checkpoint tensor under its module key.  fp8: Linear matrices go to e4m3fn - an F8_E4M3 tensor of the checkpoint as
+    it is (no upcast, no scale), anything else quantised here, one tensor at a time, on the device it will live on."""
+    if fp8 and is_fp8_matrix_key(key, v):
+        if v.dtype == FP8:
+            out[key] = v.to(device=device).contiguous()
+            return
+        w8, scale = quantize_fp8(v.to(device=device), fp8_scaling)
+        out[key] = w8.contiguous()
+        if scale is not None:
+            out[key + SCALE_SUFFIX] = scale
+        return
+    out[key] = _to_dev(v, device)
+
+
 _TR_PREFIXES = ("transformer_blocks.", "patchify_proj.", "adaln_single.", "caption_projection.", "proj_out.", "scale_shift_table")
 
 
@@ -77,12 +131,27 @@ def _transformer_key(raw_key: str) -> Optional[str]:
     return k
 
 
-def transformer_weights(raw: Dict[str, torch.Tensor], device) -> Dict[str, torch.Tensor]:
+def transformer_weights(raw: Dict[str, torch.Tensor], device, fp8: bool = False, fp8_scaling: str = "channel") -> Dict[str, torch.Tensor]:
+    """Module-key dict of the video transformer.  ``fp8``: the Linear matrices as e4m3fn panels (plus "<key>_scale" vectors
+    under ``fp8_scaling="channel"``) for LTXModel's weight-fp8 GEMMs; off, every tensor is bf16 (an fp8 checkpoint is upcast)."""
+    if fp8 and fp8_scaling not in FP8_SCALINGS:
+        raise ValueError(f"fp8 scaling {fp8_scaling!r}: expected one of {FP8_SCALINGS}")
     out = {}
     for k, v in raw.items():
         kk = _transformer_key(k)
         if kk is not None:
-            out[kk] = _to_dev(v, device)
+            _put_transformer_tensor(out, kk, v, device, fp8, fp8_scaling)
+    return out
+
+
+def quantize_transformer_weights(W: Dict[str, torch.Tensor], fp8_scaling: str = "channel") -> Dict[str, torch.Tensor]:
+    """A bf16 module-key dict (e.g. after a LoRA merge) -> the dict ``transformer_weights(fp8=True)`` gives; the input is kept."""
+    out: Dict[str, torch.Tensor] = {}
+    for k, v in W.items():
+        if k.endswith(SCALE_SUFFIX) or v.dtype == FP8:            # already quantised (an fp8 dict passes through unchanged)
+            out[k] = v
+        else:
+            _put_transformer_tensor(out, k, v, v.device, True, fp8_scaling)
     return out
 
 
@@ -240,7 +309,8 @@ def infer_encoder_blocks(keys: Iterable[str]):
 
 
 def load_pipeline_modules(model_repo: str, device, need_encoder: bool = False, need_upsampler: bool = False,
-                          loras: Optional[list] = None, build_transformer: bool = True) -> dict:
+                          loras: Optional[list] = None, build_transformer: bool = True, fp8: bool = False,
+                          fp8_scaling: str = "channel") -> dict:
     """Local-directory loader (no network: repo *names* are not resolved, utils.py:78-374 is out of scope).
     Headers are scanned first (keys, shapes, `timestep_conditioning` metadata), the architecture is inferred from the
     shapes, then tensors stream one by one straight into device memory under their module keys (ltx.py:548-826,
@@ -285,7 +355,8 @@ def load_pipeline_modules(model_repo: str, device, need_encoder: bool = False, n
     for k, v in iter_safetensors(main):
         tk = _transformer_key(k)
         if tk is not None:
-            tw[tk] = _to_dev(v, device)
+            # (a LoRA is merged into bf16 matrices and the merged dict quantised: merge-then-quantise)
+            _put_transformer_tensor(tw, tk, v, device, fp8 and not loras, fp8_scaling)
             continue
         dk = _vae_decoder_key(k)
         if dk is not None:
@@ -302,6 +373,8 @@ def load_pipeline_modules(model_repo: str, device, need_encoder: bool = False, n
         if loras:
             from .lora import LoraSpec, apply_lora_to_weights
             w = apply_lora_to_weights(tw, [LoraSpec(Path(p), float(s)) for p, s in loras])
+            if fp8:
+                w = quantize_transformer_weights(w, fp8_scaling)
         mods["transformer"] = LTXModel(tcfg, w)
     nres = 1 + max((int(k.split(".")[3]) for k in dw if k.startswith("up_blocks.0.res_blocks.")), default=4)
     mods["vae_decoder"] = LTX2VideoDecoder(dw, timestep_conditioning=any(sniff_timestep_conditioning(f) for f in main),
