@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define LTXK_VERSION 404
+#define LTXK_VERSION 405
 
 #define LTXK_OK 0
 #define LTXK_EINVAL (-1)   /* bad argument (shape / alignment / null pointer) */
@@ -124,6 +124,25 @@ int ltxk_gemm_plan(const ltxk_gemm_args* args, struct ltxk_gemm_plan* plan);
  * slice count and ksteps are those of the bf16 call with the same M, N, K and workspace.                                 */
 int ltxk_gemm_w8(const ltxk_gemm_args* args, const float* w_scale, void* stream);
 int ltxk_gemm_w8_plan(const ltxk_gemm_args* args, struct ltxk_gemm_plan* plan);
+
+/* The same GEMM with FP8 activations too (W8A8, opt-in): args->A is (M,K) OCP e4m3fn BYTES with row stride lda in BYTES (pointer
+ * and lda 16-byte aligned), args->W an e4m3fn panel as for ltxk_gemm_w8; K must be a multiple of 128 (LTXK_EINVAL otherwise).
+ * Both operands are staged as fp8 and multiplied by v_mfma_scale_f32_16x16x128_f8f6f4 (both formats e4m3, both block scales
+ * 1.0) into the fp32 accumulators of the bf16 kernel; then acc * a_scale[m], then * w_scale[n] if given, then the bias and
+ * the epilogue of ltxk_gemm_bf16 (every epilogue, the transposed and split outputs and sumsq are the shared code).
+ * a_scale: (M) fp32 per-row factors, required (ltxk_quant_rows_fp8 writes them); w_scale: (N) fp32 or NULL.
+ * Launch forms: the single-pass 160-row family only (every tile height, both tile widths); args->workspace is ignored, so a
+ * row's bits never depend on M.  ltxk_gemm_w8a8_plan reports SINGLE with that tile and ksteps = K / 128.  There is no
+ * split-K, big-tile or grouped W8A8 form: small-M launches are weight streams that gain nothing from fp8 arithmetic (callers
+ * keep ltxk_gemm_w8 there), the other two are follow-ups.                                                                 */
+int ltxk_gemm_w8a8(const ltxk_gemm_args* args, const float* a_scale, const float* w_scale, void* stream);
+int ltxk_gemm_w8a8_plan(const ltxk_gemm_args* args, struct ltxk_gemm_plan* plan);
+
+/* Row quantiser in front of ltxk_gemm_w8a8: x (M,K) bf16 with row stride lda -> q (M,K) e4m3fn bytes with row stride ldq
+ * (bytes) and a_scale (M) fp32.  Per row, no special cases: amax = max|x|; scale = max(amax, 2^-64) / 448 in fp32 (correctly
+ * rounded); q = e4m3 round-to-nearest-even, saturating, of fp32(x) / scale (IEEE fp32 division).  A zero row gives code 0.
+ * Inputs must be finite.  K, lda, ldq multiples of 8; x 16-byte, q 8-byte aligned (the GEMM wants q and ldq 16-byte aligned). */
+int ltxk_quant_rows_fp8(const void* x, int32_t lda, void* q, int32_t ldq, float* a_scale, int32_t M, int32_t K, void* stream);
 
 /* Grouped GEMM: G problems that share A, M, N, K and the split output layout, as ONE persistent launch of 256-column big
  * tiles - the text k | V^T projections of every transformer block (attention.py:123-125 on the text side), none of which

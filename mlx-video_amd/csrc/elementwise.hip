@@ -7,6 +7,8 @@
 
 namespace ltxk {
 
+typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
+
 constexpr int ROWS_PER_BLOCK = 4;  // one wave per row, 4 waves per workgroup
 constexpr int MAX_CHUNKS = 16;     // D <= 16*512 = 8192
 
@@ -473,9 +475,102 @@ __global__ __launch_bounds__(256) void value_passthrough_kernel(const bf16* __re
   }
 }
 
+// ---------------------------------------------------------------------------------------
+// Row quantiser of the fp8 x fp8 GEMMs (ltxk_quant_rows_fp8): bf16 rows -> OCP e4m3fn bytes + one fp32 scale per row.
+//   amax = max |x| ; scale = max(amax, 2^-64) / 448 ; q = e4m3_rne_sat(fp32(x) / scale)     (IEEE fp32 divisions)
+// One workgroup per row: every thread loads its 16-byte chunks (chunk c of the row to thread c % 256: whole 4-KiB lines per
+// instruction), the row maximum goes through a wave butterfly (v_permlane32/16_swap, then DPP row rotates) and four LDS words,
+// and the second sweep runs over the registers (CH chunks per thread, K <= 2048 * CH); CH = 0 re-reads the row instead.
+// ---------------------------------------------------------------------------------------
+template <int OFF>
+__device__ __forceinline__ float lane_butterfly_max(float v) {
+  if constexpr (OFF == 32) return lane_xor32_max(v);
+  else if constexpr (OFF == 16) return lane_xor16_max(v);
+  else {
+    const int r = __builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x120 + OFF, 0xf, 0xf, false);      // row_ror:OFF
+    return vmax(v, __int_as_float(r));
+  }
+}
+
+__device__ __forceinline__ float absmax8(const bf16x8& v, float m) {
+#pragma unroll
+  for (int j = 0; j < 8; ++j) m = vmax(m, __builtin_fabsf((float)v[j]));
+  return m;
+}
+
+__device__ __forceinline__ u32x2_t quant8(const bf16x8& v, float scale) {
+  float f[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) f[j] = __builtin_amdgcn_fmed3f((float)v[j] / scale, -448.f, 448.f);
+  int lo = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], 0, false);
+  lo = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], lo, true);
+  int hi = __builtin_amdgcn_cvt_pk_fp8_f32(f[4], f[5], 0, false);
+  hi = __builtin_amdgcn_cvt_pk_fp8_f32(f[6], f[7], hi, true);
+  return u32x2_t{(unsigned)lo, (unsigned)hi};
+}
+
+template <int CH>
+__global__ __launch_bounds__(256) void quant_rows_fp8_kernel(const bf16* __restrict__ x, int lda, uint8_t* __restrict__ q, int ldq,
+                                                             float* __restrict__ a_scale, int K) {
+  __shared__ float wmax[4];
+  const int tid = threadIdx.x, row = blockIdx.x;
+  const bf16* xr = x + (size_t)row * lda;
+  uint8_t* qr = q + (size_t)row * ldq;
+  const int nch = K >> 3;
+  bf16x8 v[CH > 0 ? CH : 1];
+  float amax = 0.f;
+  if constexpr (CH > 0) {
+#pragma unroll
+    for (int i = 0; i < CH; ++i)
+      if (i * 256 + tid < nch) v[i] = *(const bf16x8*)(xr + (size_t)(i * 256 + tid) * 8);
+#pragma unroll
+    for (int i = 0; i < CH; ++i)
+      if (i * 256 + tid < nch) amax = absmax8(v[i], amax);
+  } else {
+    for (int c = tid; c < nch; c += 256) amax = absmax8(*(const bf16x8*)(xr + (size_t)c * 8), amax);
+  }
+  amax = lane_butterfly_max<32>(amax);
+  amax = lane_butterfly_max<16>(amax);
+  amax = lane_butterfly_max<8>(amax);
+  amax = lane_butterfly_max<4>(amax);
+  amax = lane_butterfly_max<2>(amax);
+  amax = lane_butterfly_max<1>(amax);
+  if ((tid & 63) == 0) wmax[tid >> 6] = amax;
+  __syncthreads();
+  amax = vmax(vmax(wmax[0], wmax[1]), vmax(wmax[2], wmax[3]));
+  const float scale = vmax(amax, 0x1p-64f) / 448.0f;
+  if (tid == 0) a_scale[row] = scale;
+  if constexpr (CH > 0) {
+#pragma unroll
+    for (int i = 0; i < CH; ++i)
+      if (i * 256 + tid < nch) *(u32x2_t*)(qr + (size_t)(i * 256 + tid) * 8) = quant8(v[i], scale);
+  } else {
+    for (int c = tid; c < nch; c += 256) *(u32x2_t*)(qr + (size_t)c * 8) = quant8(*(const bf16x8*)(xr + (size_t)c * 8), scale);
+  }
+}
+
 }  // namespace ltxk
 
 using namespace ltxk;
+
+extern "C" int ltxk_quant_rows_fp8(const void* x, int32_t lda, void* q, int32_t ldq, float* a_scale, int32_t M, int32_t K,
+                                   void* stream) {
+  const char* name = "ltxk_quant_rows_fp8";
+  LTXK_CHECK_ARG(x && q && a_scale && M > 0 && K > 0, "%s: null/empty input", name);
+  LTXK_CHECK_ARG(K % 8 == 0 && lda >= K && lda % 8 == 0 && ldq >= K && ldq % 8 == 0, "%s: K=%d, lda=%d, ldq=%d must be multiples of 8, strides >= K", name, K, lda, ldq);
+  LTXK_CHECK_ARG(((uintptr_t)x & 15) == 0 && ((uintptr_t)q & 7) == 0 && ((uintptr_t)a_scale & 3) == 0,
+                 "%s: x must be 16-byte, q 8-byte, a_scale 4-byte aligned", name);
+  hipStream_t st = (hipStream_t)stream;
+  const bf16* xb = (const bf16*)x;
+  uint8_t* qb = (uint8_t*)q;
+  if (K <= 2048) hipLaunchKernelGGL(quant_rows_fp8_kernel<1>, dim3(M), dim3(256), 0, st, xb, (int)lda, qb, (int)ldq, a_scale, (int)K);
+  else if (K <= 4096) hipLaunchKernelGGL(quant_rows_fp8_kernel<2>, dim3(M), dim3(256), 0, st, xb, (int)lda, qb, (int)ldq, a_scale, (int)K);
+  else if (K <= 8192) hipLaunchKernelGGL(quant_rows_fp8_kernel<4>, dim3(M), dim3(256), 0, st, xb, (int)lda, qb, (int)ldq, a_scale, (int)K);
+  else if (K <= 16384) hipLaunchKernelGGL(quant_rows_fp8_kernel<8>, dim3(M), dim3(256), 0, st, xb, (int)lda, qb, (int)ldq, a_scale, (int)K);
+  else hipLaunchKernelGGL(quant_rows_fp8_kernel<0>, dim3(M), dim3(256), 0, st, xb, (int)lda, qb, (int)ldq, a_scale, (int)K);
+  LTXK_CHECK_LAUNCH(name);
+  return LTXK_OK;
+}
 
 extern "C" int ltxk_step_scalars(const void* ts_all, const float* sig_all, int32_t* step, void* ts, float* sig,
                                  int32_t U, int32_t n_steps, void* stream) {

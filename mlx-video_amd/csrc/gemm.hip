@@ -2,6 +2,8 @@
 // Replaces nn.Linear at attention.py:123-126,142; feed_forward.py:35-40; adaln.py:46,134-138;
 // text_projection.py:22-25; ltx.py:130,455 — and the residual/gate algebra of
 // transformer.py:254,257,347 as epilogues.
+// Also ltxk_gemm_w8 (e4m3 weight panel, bf16 activations) and ltxk_gemm_w8a8 (e4m3 on both sides, fp8 x fp8 MFMA): the same tile
+// body with template flags.  W8A8 exists as the single-pass 160-row family only - no split-K, big-tile or grouped form.
 #include "gemm_core.h"
 #include <stdlib.h>
 #include <atomic>
@@ -60,7 +62,12 @@ struct GemmParams {
   int sumsq_ld;
   // split-K (gemm_stream_kernel): blockIdx.y = K slice; slice s covers K-steps [s*ksteps, min(K/64, (s+1)*ksteps)) and stores its
   // fp32 accumulators to part[(s*M + m)*N + n]; splitk_epilogue_kernel sums the slices in order and applies the epilogue
-  float* part;
+  // (fp8 x fp8 forms - A8 kernels, which never split K: the same slot holds a_scale, the per-row fp32 factor on the accumulator
+  // of the quantised activations A then points at; sharing it keeps the parameter block, and with it every other kernel, as it was)
+  union {
+    float* part;
+    const float* a_scale;
+  };
   int ksteps;
   // weight-fp8 forms (W8 kernels; W then points at e4m3fn bytes): per-output-channel fp32 factor on the accumulator, or nullptr
   const float* w_scale;
@@ -68,9 +75,14 @@ struct GemmParams {
 
 // NT = 16-column MFMA tiles per wave: 4 -> 256-column workgroup tiles (64 per wave), 2 -> 128-column ones (32 per wave).
 // W8: W is (N,K) e4m3fn bytes, staged as fp8 (gemm_core.h) and widened after the fragment read; everything else is shared.
-template <int TT, int NT, int EPI, bool TRANS, bool W8 = false>
+// A8 (with W8): A is e4m3fn bytes too - 128-k K-steps of 128-byte rows on both sides, multiplied as fp8 by MmaPipe8 (gemm_core.h);
+// loader, ring, counted waits and epilogues are the shared code, plus the per-row factor a_scale on the accumulators.
+template <int TT, int NT, int EPI, bool TRANS, bool W8 = false, bool A8 = false>
 __device__ __forceinline__ void gemm_tile(const GemmParams& p, char* smem, int m0, int n0, int kbase, int nk, int wave, int lane) {
-  using G = GemmGeom<TT, 4, NT, W8>;
+  static_assert(W8 || !A8, "fp8 activations go with fp8 weights");
+  constexpr bool W64 = W8 && !A8;             // the W half of a stage holds 64-byte fp8 rows (W8A16)
+  constexpr int KSTEP = A8 ? GEMM_BK8 : GEMM_BK;
+  using G = GemmGeom<TT, 4, NT, W64>;
   constexpr int GEMM_W_STAGE_BYTES = G::W_STAGE_BYTES;
   constexpr int WPW = G::W_PER_WAVE;          // W pieces per wave per stage (4 / 2)
   constexpr int WC = 16 * NT;                 // columns per wave
@@ -85,23 +97,24 @@ __device__ __forceinline__ void gemm_tile(const GemmParams& p, char* smem, int m
   const wel* wptr[WPW];
 #pragma unroll
   for (int i = 0; i < WPW; ++i) {
-    int r = n0 + (wave * WPW + i) * (W8 ? 16 : 8) + (W8 ? lane >> 2 : lrow);
+    int r = n0 + (wave * WPW + i) * (W64 ? 16 : 8) + (W64 ? lane >> 2 : lrow);
     r = r < p.N ? r : p.N - 1;
-    wptr[i] = (const wel*)p.W + (size_t)r * p.K + (W8 ? ((lane & 3) ^ (lane >> 4)) * 16 : chunk * 8);
+    wptr[i] = (const wel*)p.W + (size_t)r * p.K + (W64 ? ((lane & 3) ^ (lane >> 4)) * 16 : chunk * (A8 ? 16 : 8));
   }
   // Every wave issues exactly WPW W pieces + MAXA A pieces per stage, so one constant vmcnt retires a
   // stage.  A_PIECES is not a multiple of 8 (20 at BM=160): waves past A_REM own one piece fewer and
   // re-issue their last piece (same source, same LDS bytes: benign) to keep the count uniform.
   const int nA = G::A_BASE + (wave < G::A_REM ? 1 : 0);
   const int a0 = wave * G::A_BASE + (wave < G::A_REM ? wave : G::A_REM);
-  const bf16* aptr[G::MAXA];
+  using ael = std::conditional_t<A8, uint8_t, bf16>;      // (A8: lda and the K offsets count bytes)
+  const ael* aptr[G::MAXA];
   int adst[G::MAXA];
 #pragma unroll
   for (int i = 0; i < G::MAXA; ++i) {
     const int pi = nA > 0 ? a0 + (i < nA ? i : nA - 1) : G::A_PIECES - 1;   // no own piece: re-issue the tile's last one
     int r = m0 + pi * 8 + lrow;
     r = r < p.M ? r : p.M - 1;
-    aptr[i] = p.A + (size_t)r * p.lda + chunk * 8;
+    aptr[i] = (const ael*)p.A + (size_t)r * p.lda + chunk * (A8 ? 16 : 8);
     adst[i] = GEMM_W_STAGE_BYTES + (pi < G::A_PIECES ? pi : G::A_PIECES - 1) * 1024;
   }
   constexpr int PER_STAGE = WPW + G::MAXA;
@@ -110,7 +123,7 @@ __device__ __forceinline__ void gemm_tile(const GemmParams& p, char* smem, int m
   // i-th LDS-DMA piece of this wave for K-step kt (of this launch slice) into ring slot s (pieces 0..WPW-1 = W, then A)
   auto issue_piece = [&](int i, int kt, int s) __attribute__((always_inline)) {
     char* base = smem + s * G::STAGE_BYTES;
-    const int ko = (kbase + kt) * GEMM_BK;
+    const int ko = (kbase + kt) * KSTEP;
     if (i < WPW) {
       glds16(wptr[i < WPW ? i : 0] + ko, base + (wave * WPW + i) * 1024);
     } else if (i < PER_STAGE) {
@@ -239,7 +252,7 @@ __device__ __forceinline__ void gemm_tile(const GemmParams& p, char* smem, int m
     auto issue = [&](int i) __attribute__((always_inline)) {
       if constexpr (KC != -2 && KC != -3) issue_piece(i, kt2, s2);
     };
-    if constexpr (TT >= 2) {
+    if constexpr (A8 || TT >= 2) {
       pipe.step(smem + s * G::STAGE_BYTES, wm, wn, lane, acc, issue);
     } else {
       mma_stage_pipelined<TT, 4, TRANS, NT, W8>(smem + s * G::STAGE_BYTES, wm, wn, lane, acc, issue);
@@ -247,7 +260,7 @@ __device__ __forceinline__ void gemm_tile(const GemmParams& p, char* smem, int m
     s = s + 1 == 3 ? 0 : s + 1;
   };
   auto kloop = [&](auto& pipe) __attribute__((always_inline)) {
-    if constexpr (TT >= 2) pipe.init();
+    if constexpr (A8 || TT >= 2) pipe.init();
     [&]<int... I>(std::integer_sequence<int, I...>) __attribute__((always_inline)) {
       ((I < nk ? kstep(pipe, I, IntC<I>{}) : (void)0), ...);
     }(std::make_integer_sequence<int, PEEL>{});
@@ -258,9 +271,12 @@ __device__ __forceinline__ void gemm_tile(const GemmParams& p, char* smem, int m
       kstep(pipe, nk - 2, IntC<-2>{});
       kstep(pipe, nk - 1, IntC<-3>{});
     }
-    if constexpr (TT >= 2) pipe.finish(acc);
+    if constexpr (A8 || TT >= 2) pipe.finish(acc);
   };
-  if constexpr (TT >= 2) {
+  if constexpr (A8) {
+    MmaPipe8<TT, TRANS, NT> pipe;
+    kloop(pipe);
+  } else if constexpr (TT >= 2) {
 #if LTXK_STAGGER
     if (wave >= 4) {                  // SIMD partners of waves 0-3 run half a K-step out of phase
       MmaPipe<TT, 4, TRANS, TT, NT, W8> pipe;
@@ -302,6 +318,29 @@ __device__ __forceinline__ void gemm_tile(const GemmParams& p, char* smem, int m
     }
   }
   LTXK_STAMP(3);
+  if constexpr (A8) {
+    // per-row scale of the quantised activations on the fp32 accumulators, first (then w_scale, then the shared epilogue)
+#pragma unroll
+    for (int tt = 0; tt < TT; ++tt) {
+      float sa[4];
+      if constexpr (TRANS) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          int m = m0 + wm * TT * 16 + tt * 16 + (lane >> 4) * 4 + j;
+          m = m < p.M ? m : p.M - 1;
+          sa[j] = p.a_scale[m];
+        }
+      } else {
+        int m = m0 + wm * TT * 16 + tt * 16 + (lane & 15);
+        m = m < p.M ? m : p.M - 1;
+        sa[0] = sa[1] = sa[2] = sa[3] = p.a_scale[m];
+      }
+#pragma unroll
+      for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[tt][nt][j] *= sa[j];
+    }
+  }
   if constexpr (W8) {
     // per-output-channel scale on the fp32 accumulators, in front of the shared epilogue (no scale: no multiply)
     if (p.w_scale) {
@@ -491,9 +530,9 @@ __device__ __forceinline__ void gemm_tile(const GemmParams& p, char* smem, int m
 
 // MODE 0: every tile row-major with epilogue EPI; 1: every tile transposed (V^T); 2: split output - tiles with
 // n0 < n_split row-major (EPI), the rest transposed (one launch for q|k|v, or for the text k|v pair)
-template <int TT, int NT, int EPI, int MODE, bool W8 = false>
+template <int TT, int NT, int EPI, int MODE, bool W8 = false, bool A8 = false>
 __global__ __launch_bounds__(GEMM_THREADS) void gemm_bf16_kernel(GemmParams p) {
-  using G = GemmGeom<TT, 4, NT, W8>;
+  using G = GemmGeom<TT, 4, NT, W8 && !A8>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   LTXK_STAMP(4);
   const int tid = threadIdx.x;
@@ -502,14 +541,14 @@ __global__ __launch_bounds__(GEMM_THREADS) void gemm_bf16_kernel(GemmParams p) {
   int rt, ct;
   map_tile(blockIdx.x, p.RT, p.CT, rt, ct);
   const int m0 = rt * G::BM, n0 = ct * G::BN;
-  const int kbase = 0, nk = p.K / GEMM_BK;
+  const int kbase = 0, nk = p.K / (A8 ? GEMM_BK8 : GEMM_BK);
   if constexpr (MODE == 0) {
-    gemm_tile<TT, NT, EPI, false, W8>(p, smem, m0, n0, kbase, nk, wave, lane);
+    gemm_tile<TT, NT, EPI, false, W8, A8>(p, smem, m0, n0, kbase, nk, wave, lane);
   } else if constexpr (MODE == 1) {
-    gemm_tile<TT, NT, LTXK_EPI_BIAS, true, W8>(p, smem, m0, n0, kbase, nk, wave, lane);
+    gemm_tile<TT, NT, LTXK_EPI_BIAS, true, W8, A8>(p, smem, m0, n0, kbase, nk, wave, lane);
   } else {
-    if (n0 < p.n_split) gemm_tile<TT, NT, EPI, false, W8>(p, smem, m0, n0, kbase, nk, wave, lane);
-    else gemm_tile<TT, NT, LTXK_EPI_BIAS, true, W8>(p, smem, m0, n0, kbase, nk, wave, lane);
+    if (n0 < p.n_split) gemm_tile<TT, NT, EPI, false, W8, A8>(p, smem, m0, n0, kbase, nk, wave, lane);
+    else gemm_tile<TT, NT, LTXK_EPI_BIAS, true, W8, A8>(p, smem, m0, n0, kbase, nk, wave, lane);
   }
 #ifdef LTXK_DIAG
   __syncthreads();
@@ -719,10 +758,10 @@ __global__ __launch_bounds__(256) void splitk_epilogue_kernel(GemmParams p, int 
   }
 }
 
-template <int TT, int NT, int EPI, int MODE, bool W8>
+template <int TT, int NT, int EPI, int MODE, bool W8, bool A8>
 static int launch(const GemmParams& p, hipStream_t stream) {
-  using G = GemmGeom<TT, 4, NT, W8>;
-  auto kern = gemm_bf16_kernel<TT, NT, EPI, MODE, W8>;
+  using G = GemmGeom<TT, 4, NT, W8 && !A8>;
+  auto kern = gemm_bf16_kernel<TT, NT, EPI, MODE, W8, A8>;
   static thread_local int attr_dev = -1;
   int dev = 0;
   (void)hipGetDevice(&dev);
@@ -740,30 +779,30 @@ static int launch(const GemmParams& p, hipStream_t stream) {
   return LTXK_OK;
 }
 
-template <int TT, int NT, bool W8>
+template <int TT, int NT, bool W8, bool A8>
 static int dispatch_epi(const GemmParams& p, int epi, bool trans, hipStream_t stream) {
-  if (p.n_split) return launch<TT, NT, LTXK_EPI_BIAS, 2, W8>(p, stream);
-  if (trans) return launch<TT, NT, LTXK_EPI_BIAS, 1, W8>(p, stream);
+  if (p.n_split) return launch<TT, NT, LTXK_EPI_BIAS, 2, W8, A8>(p, stream);
+  if (trans) return launch<TT, NT, LTXK_EPI_BIAS, 1, W8, A8>(p, stream);
   switch (epi) {
-    case LTXK_EPI_BIAS: return launch<TT, NT, LTXK_EPI_BIAS, 0, W8>(p, stream);
-    case LTXK_EPI_BIAS_GELU: return launch<TT, NT, LTXK_EPI_BIAS_GELU, 0, W8>(p, stream);
-    case LTXK_EPI_BIAS_SILU: return launch<TT, NT, LTXK_EPI_BIAS_SILU, 0, W8>(p, stream);
-    case LTXK_EPI_BIAS_GATE_RES: return launch<TT, NT, LTXK_EPI_BIAS_GATE_RES, 0, W8>(p, stream);
-    case LTXK_EPI_BIAS_RES: return launch<TT, NT, LTXK_EPI_BIAS_RES, 0, W8>(p, stream);
-    case LTXK_EPI_SCALE_RES: return launch<TT, NT, LTXK_EPI_SCALE_RES, 0, W8>(p, stream);
+    case LTXK_EPI_BIAS: return launch<TT, NT, LTXK_EPI_BIAS, 0, W8, A8>(p, stream);
+    case LTXK_EPI_BIAS_GELU: return launch<TT, NT, LTXK_EPI_BIAS_GELU, 0, W8, A8>(p, stream);
+    case LTXK_EPI_BIAS_SILU: return launch<TT, NT, LTXK_EPI_BIAS_SILU, 0, W8, A8>(p, stream);
+    case LTXK_EPI_BIAS_GATE_RES: return launch<TT, NT, LTXK_EPI_BIAS_GATE_RES, 0, W8, A8>(p, stream);
+    case LTXK_EPI_BIAS_RES: return launch<TT, NT, LTXK_EPI_BIAS_RES, 0, W8, A8>(p, stream);
+    case LTXK_EPI_SCALE_RES: return launch<TT, NT, LTXK_EPI_SCALE_RES, 0, W8, A8>(p, stream);
   }
   ltxk_set_error("ltxk_gemm_bf16: unknown epilogue %d", epi);
   return LTXK_EINVAL;
 }
 
-template <int NT, bool W8>
+template <int NT, bool W8, bool A8 = false>
 static int dispatch_tt(const GemmParams& p, int tt, int epi, bool trans, hipStream_t st) {
   switch (tt) {
-    case 5: return dispatch_epi<5, NT, W8>(p, epi, trans, st);
-    case 4: return dispatch_epi<4, NT, W8>(p, epi, trans, st);
-    case 3: return dispatch_epi<3, NT, W8>(p, epi, trans, st);
-    case 2: return dispatch_epi<2, NT, W8>(p, epi, trans, st);
-    default: return dispatch_epi<1, NT, W8>(p, epi, trans, st);
+    case 5: return dispatch_epi<5, NT, W8, A8>(p, epi, trans, st);
+    case 4: return dispatch_epi<4, NT, W8, A8>(p, epi, trans, st);
+    case 3: return dispatch_epi<3, NT, W8, A8>(p, epi, trans, st);
+    case 2: return dispatch_epi<2, NT, W8, A8>(p, epi, trans, st);
+    default: return dispatch_epi<1, NT, W8, A8>(p, epi, trans, st);
   }
 }
 
@@ -1282,13 +1321,16 @@ struct GemmForm {
 // w8: the form of ltxk_gemm_w8 - the same rules, with the 160-row single-pass tile wherever the bf16 call takes the big tile
 // (which has no weight-fp8 form).  The split-K decision, slice count and K-steps per slice are therefore those of the bf16 call
 // with the same M, N, K and workspace, so the two calls sum every row's products in the same order.
-static int gemm_form(const ltxk_gemm_args* a, GemmForm& f, bool w8 = false) {
+// a8: the form of ltxk_gemm_w8a8 - A is e4m3 bytes (lda in bytes, a multiple of 16), K-steps are 128 wide, and the launch is
+// always the single-pass 160-row family with the tile pick_tile gives: no big tile, no split-K.
+static int gemm_form(const ltxk_gemm_args* a, GemmForm& f, bool w8 = false, bool a8 = false) {
   LTXK_CHECK_ARG(a != nullptr, "ltxk_gemm_bf16: null args");
   LTXK_CHECK_ARG(a->A && a->W && a->out, "ltxk_gemm_bf16: null A/W/out");
   LTXK_CHECK_ARG(a->M > 0 && a->N > 0 && a->K > 0, "ltxk_gemm_bf16: bad dims M=%d N=%d K=%d", a->M, a->N, a->K);
-  LTXK_CHECK_ARG(a->K % GEMM_BK == 0, "ltxk_gemm_bf16: K=%d must be a multiple of %d", a->K, GEMM_BK);
+  const int bk = a8 ? GEMM_BK8 : GEMM_BK;
+  LTXK_CHECK_ARG(a->K % bk == 0, "ltxk_gemm_bf16: K=%d must be a multiple of %d", a->K, bk);
   LTXK_CHECK_ARG(a->N % 8 == 0, "ltxk_gemm_bf16: N=%d must be a multiple of 8", a->N);
-  LTXK_CHECK_ARG(a->lda >= a->K && a->lda % 8 == 0, "ltxk_gemm_bf16: lda=%d (K=%d) must be >=K, multiple of 8", a->lda, a->K);
+  LTXK_CHECK_ARG(a->lda >= a->K && a->lda % (a8 ? 16 : 8) == 0, "ltxk_gemm_bf16: lda=%d (K=%d) must be >=K, multiple of %d", a->lda, a->K, a8 ? 16 : 8);
   LTXK_CHECK_ARG(((uintptr_t)a->A & 15) == 0 && ((uintptr_t)a->W & 15) == 0 && ((uintptr_t)a->out & 7) == 0,
                  "ltxk_gemm_bf16: A/W must be 16-byte aligned, out 8-byte aligned");
   // (checked here and not only by the single-pass dispatch: the split-K epilogue launch would run an unknown one as EPI_BIAS)
@@ -1322,7 +1364,7 @@ static int gemm_form(const ltxk_gemm_args* a, GemmForm& f, bool w8 = false) {
   f.split = split;
   f.trans = trans;
   struct ltxk_gemm_plan& pl = f.plan;
-  const int nk = a->K / GEMM_BK;
+  const int nk = a->K / bk;
   const int tt_env = LTXK_AB_INT("LTXK_GEMM_TT", 0);
   const int nt_env = LTXK_AB_INT("LTXK_GEMM_NT", 0);                  // A/B build: 2 / 4 forces the 128- / 256-column tile
   const bool nt2_legal = !split || a->n_split % 128 == 0;
@@ -1337,6 +1379,8 @@ static int gemm_form(const ltxk_gemm_args* a, GemmForm& f, bool w8 = false) {
   pl.col_tiles = (a->N + pl.tile_cols - 1) / pl.tile_cols;
   pl.slices = 1;
   pl.ksteps = nk;
+  f.rb = 0;
+  if (a8) return LTXK_OK;
   const int big_env = LTXK_AB_INT("LTXK_GEMM_BIG", 1);
   const bool big_legal = a->N % BIG_BN == 0 && a->K <= (1 << 20) &&
                          (a->epilogue == LTXK_EPI_BIAS || ((a->epilogue == LTXK_EPI_BIAS_GELU || a->epilogue == LTXK_EPI_BIAS_SILU) && !a->sumsq));
@@ -1406,13 +1450,15 @@ extern "C" int ltxk_gemm_plan(const ltxk_gemm_args* a, struct ltxk_gemm_plan* pl
 }
 
 namespace ltxk {
-// ltxk_gemm_bf16 (W8 = false) and ltxk_gemm_w8: one body, so the two launch the same forms with the same parameters
-template <bool W8>
-static int gemm_run(const ltxk_gemm_args* a, const float* w_scale, void* stream) {
+// ltxk_gemm_bf16 (W8 = false), ltxk_gemm_w8 and ltxk_gemm_w8a8 (W8 and A8): one body, so they launch the same forms with the
+// same parameters
+template <bool W8, bool A8 = false>
+static int gemm_run(const ltxk_gemm_args* a, const float* w_scale, void* stream, const float* a_scale = nullptr) {
   GemmForm f;
-  const int rc = gemm_form(a, f, W8);
+  const int rc = gemm_form(a, f, W8, A8);
   if (rc != LTXK_OK) return rc;
   LTXK_CHECK_ARG(((uintptr_t)w_scale & 3) == 0, "ltxk_gemm_w8: w_scale must be 4-byte aligned");
+  if constexpr (A8) LTXK_CHECK_ARG(a_scale != nullptr && ((uintptr_t)a_scale & 3) == 0, "ltxk_gemm_w8a8: a_scale is required, 4-byte aligned");
   const bool split = f.split, trans = f.trans;
   GemmParams p;
   p.A = (const bf16*)a->A; p.W = (const bf16*)a->W; p.bias = (const bf16*)a->bias;
@@ -1432,6 +1478,10 @@ static int gemm_run(const ltxk_gemm_args* a, const float* w_scale, void* stream)
   p.ksteps = f.plan.ksteps;
   p.w_scale = w_scale;
   hipStream_t st = (hipStream_t)stream;
+  if constexpr (A8) {           // single-pass only (gemm_form)
+    p.a_scale = a_scale;
+    return f.nt == 2 ? dispatch_tt<2, true, true>(p, f.tt, a->epilogue, trans, st) : dispatch_tt<4, true, true>(p, f.tt, a->epilogue, trans, st);
+  }
   if constexpr (!W8) if (f.plan.form == LTXK_GEMM_FORM_BIG) {
     const int rb = f.rb;
     if (split) return launch_big<LTXK_EPI_BIAS, 2>(p, st, rb);
@@ -1464,6 +1514,19 @@ extern "C" int ltxk_gemm_w8_plan(const ltxk_gemm_args* a, struct ltxk_gemm_plan*
   LTXK_CHECK_ARG(plan != nullptr, "ltxk_gemm_w8_plan: null plan");
   GemmForm f;
   const int rc = gemm_form(a, f, true);
+  if (rc == LTXK_OK) *plan = f.plan;
+  return rc;
+}
+
+extern "C" int ltxk_gemm_w8a8(const ltxk_gemm_args* a, const float* a_scale, const float* w_scale, void* stream) {
+  return ltxk::gemm_run<true, true>(a, w_scale, stream, a_scale);
+}
+
+extern "C" int ltxk_gemm_w8a8_plan(const ltxk_gemm_args* a, struct ltxk_gemm_plan* plan) {
+  using namespace ltxk;
+  LTXK_CHECK_ARG(plan != nullptr, "ltxk_gemm_w8a8_plan: null plan");
+  GemmForm f;
+  const int rc = gemm_form(a, f, true, true);
   if (rc == LTXK_OK) *plan = f.plan;
   return rc;
 }

@@ -22,6 +22,13 @@
 // the 16-byte chunk index (0..3) is XOR-swizzled by ((row >> 2) & 3) - each of the four rows then owns its own 16 bytes of
 // the shared banks for every k-quarter.  The swizzle unit is the DMA's 16 bytes, so it is again applied to the per-lane
 // source address.
+// W8A8 (fp8 x fp8) forms: a K-step is 128 k and BOTH halves of a stage hold e4m3 bytes in 128-byte rows ([row][128 fp8]) - the
+// byte geometry, LDS-DMA pieces, swizzle and counted waits of the bf16 stage.  One v_mfma_scale_f32_16x16x128_f8f6f4 (both
+// formats e4m3, both block scales the E8M0 code of 1.0) per 16x16 tile and K-step takes 32 bytes per lane and operand: lane l
+// reads the two 16-byte chunks (l >> 4) and 4 + (l >> 4) of row (l & 15) - exactly the two ds_read_b128 the bf16 form issues for
+// its K-sub-steps 0 and 1, at the same swizzled addresses, so they are conflict-free by the same bank rule.  The lane therefore
+// holds k = 16g..16g+15 and 64+16g..64+16g+15 (g = l >> 4) of the 128, not the instruction's nominal 32g..32g+31: the sum over
+// k is order-free and the A and W fragments use the same assignment (MmaPipe8).
 #pragma once
 #include "common.h"
 
@@ -322,6 +329,85 @@ struct MmaPipe {
   __device__ __forceinline__ void finish(f32x4 (&acc)[TT][NT]) {
 #pragma unroll
     for (int v = 0; v < DG; ++v) group(af[1][TT - DG + v], wf[1], acc[TT - DG + v]);
+  }
+};
+
+// ---- fp8 x fp8 (W8A8): the 160-row family on v_mfma_scale_f32_16x16x128_f8f6f4 ------------------------------------------
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+typedef int i32x8 __attribute__((ext_vector_type(8)));
+
+constexpr int GEMM_BK8 = 128;                       // k per K-step of the fp8 x fp8 forms (128-byte rows)
+constexpr int E8M0_ONE_X4 = 0x7f7f7f7f;             // block scale 1.0 in every byte, whichever one op_sel picks
+
+// The rotated pipeline of MmaPipe for one MFMA per tile and K-step: a K-step is TT groups of NT MFMAs (one A-row fragment x NT W
+// fragments), each MFMA twice as long as a 16x16x32 bf16 one, so the step spends the matrix-pipe cycles of the bf16 step's 2*TT
+// groups.  Every group uses ALL W fragments, so only ONE group (the last) is deferred past the next barrier: it runs on the
+// previous stage's W registers while the new stage's first A fragment is in flight, and the W fragments are re-read behind it.
+// A fragments are read one group ahead of their use.  The stage's LDS-DMA pieces are spread over the TT groups.  TT = 1 has
+// nothing to defer: read, issue, multiply.
+template <int TT, bool SWAP, int NT = 4>
+struct MmaPipe8 {
+  using G = GemmGeom<TT, 4, NT, false>;             // 128-byte rows in both halves: the bf16 stage's geometry
+  static constexpr int DG = TT >= 2 ? 1 : 0;
+  static constexpr int MAXP = G::W_PER_WAVE + G::MAXA;
+  static constexpr int PPG = (MAXP + TT - 1) / TT;
+  i32x8 wf[NT], af[TT];
+
+  __device__ __forceinline__ void init() {
+#pragma unroll
+    for (int i = 0; i < NT; ++i)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) wf[i][j] = 0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) af[TT - 1][j] = 0;
+  }
+
+  static __device__ __forceinline__ void group(const i32x8& a, const i32x8 (&w)[NT], f32x4 (&acc)[NT]) {
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt)
+      acc[nt] = SWAP ? __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a, w[nt], acc[nt], 0, 0, 0, E8M0_ONE_X4, 0, E8M0_ONE_X4)
+                     : __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(w[nt], a, acc[nt], 0, 0, 0, E8M0_ONE_X4, 0, E8M0_ONE_X4);
+  }
+
+  template <class IssueFn>
+  __device__ __forceinline__ void step(const char* st, int wm, int wn, int lane, f32x4 (&acc)[TT][NT], IssueFn&& issue) {
+    const char* wb = st + (wn * 16 * NT + (lane & 15)) * 128;
+    const char* ab = st + G::W_STAGE_BYTES + (wm * TT * 16 + (lane & 15)) * 128;
+    const int koff0 = (((lane >> 4)) ^ (lane & 7)) << 4;
+    const int koff1 = (((4 + (lane >> 4))) ^ (lane & 7)) << 4;
+    auto frag = [&](const char* row) {
+      const i32x4 lo = *(const i32x4*)(row + koff0), hi = *(const i32x4*)(row + koff1);
+      return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+    };
+    if constexpr (DG) {
+      af[0] = frag(ab);
+#pragma unroll
+      for (int q = 0; q < PPG; ++q) issue(q);
+      group(af[TT - 1], wf, acc[TT - 1]);              // deferred from the previous K-step (step 0: zeros)
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int nt = 0; nt < NT; ++nt) wf[nt] = frag(wb + nt * 2048);
+#pragma unroll
+      for (int g = 0; g < TT - 1; ++g) {
+        af[g + 1] = frag(ab + (g + 1) * 2048);         // (the last one feeds the group deferred to the next step)
+#pragma unroll
+        for (int q = 0; q < PPG; ++q) issue((g + 1) * PPG + q);
+        group(af[g], wf, acc[g]);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    } else {
+#pragma unroll
+      for (int nt = 0; nt < NT; ++nt) wf[nt] = frag(wb + nt * 2048);
+      af[0] = frag(ab);
+#pragma unroll
+      for (int q = 0; q < PPG; ++q) issue(q);
+      group(af[0], wf, acc[0]);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  }
+
+  __device__ __forceinline__ void finish(f32x4 (&acc)[TT][NT]) {
+    if constexpr (DG) group(af[TT - 1], wf, acc[TT - 1]);
   }
 };
 

@@ -178,7 +178,8 @@ def generate_video(model_repo: Optional[str] = None, text_encoder_repo: Optional
                    noise_fn: Optional[Callable] = None, device=None, on_frames_ready: Optional[Callable] = None,
                    return_latents: bool = False, lora_in_place: Optional[bool] = None,
                    hoist_context: bool = False, stg_scale: Optional[float] = None, stg_blocks: Optional[list] = None,
-                   stg_mode: Optional[str] = None, enable_fp8: bool = False, fp8_scaling: str = "channel") -> np.ndarray:
+                   stg_mode: Optional[str] = None, enable_fp8: bool = False, fp8_scaling: str = "channel",
+                   fp8_activations: bool = False) -> np.ndarray:
     """See the module docstring.  Returns uint8 frames (F,H,W,3) (generate.py:4195-4197).
     ``hoist_context`` (not in the reference, off by default): the part of the forward that depends on the text context only -
     caption projection and the 48 cross-attention K / V^T projections, 3.37 TFLOP that the reference recomputes in every forward
@@ -191,7 +192,9 @@ def generate_video(model_repo: Optional[str] = None, text_encoder_repo: Optional
     matrices as FP8 e4m3 panels, calculations still in bf16 (ltxk_gemm_w8) - half the weight bytes in memory and per forward.
     ``fp8_scaling``: "channel" (per-output-channel scale, amax -> 448) or "none" (the upstream plain cast).  LoRAs are merged in
     bf16 and the merged weights quantised (never merged into fp8 panels), so a LoRA-merged stage-2 transformer is a fresh fp8
-    model.  A ``transformer=`` / ``stage2_transformer=`` passed in is used as it is."""
+    model.  A ``transformer=`` / ``stage2_transformer=`` passed in is used as it is.
+    ``fp8_activations`` (--fp8-activations; needs ``enable_fp8``, a ValueError without it): the transformers this call builds also
+    quantise the inputs of their in-block Linear layers to e4m3 per row and multiply fp8 x fp8 (ltxk_gemm_w8a8)."""
     t_start = time.perf_counter()
     if isinstance(pipeline, str):
         pipeline = PipelineType(pipeline)
@@ -223,13 +226,15 @@ def generate_video(model_repo: Optional[str] = None, text_encoder_repo: Optional
     from .weights import FP8_SCALINGS
     if fp8_scaling not in FP8_SCALINGS:
         raise ValueError(f"Unknown fp8_scaling: {fp8_scaling!r} (expected one of {FP8_SCALINGS})")
+    if fp8_activations and not enable_fp8:
+        raise ValueError("fp8_activations (--fp8-activations) needs enable_fp8 (--enable-fp8): fp8 activations multiply fp8 weight panels")
 
     def _build(cfg_, weights_) -> LTXModel:
         """A transformer from a module-key weight dict; under enable_fp8 from its quantised twin (an fp8 dict is kept as it is)."""
         if enable_fp8:
             from .weights import quantize_transformer_weights
             weights_ = quantize_transformer_weights(weights_, fp8_scaling)
-        return LTXModel(cfg_, weights_)
+        return LTXModel(cfg_, weights_, fp8_activations=fp8_activations)
 
     out_h, out_w = height, width
     height, width, crop = _pad_dims(height, width, 64 if is_distilled else 32)
@@ -524,6 +529,9 @@ def build_parser() -> argparse.ArgumentParser:
                     help="Keep the transformer's Linear weights as FP8 (e4m3) panels; calculations still in bfloat16")
     ap.add_argument("--fp8-scaling", type=str, choices=["channel", "none"], default="channel",
                     help="(not in the reference CLI) channel: per-output-channel scale; none: the plain cast")
+    ap.add_argument("--fp8-activations", action="store_true", default=False,
+                    help="(not in the reference CLI; needs --enable-fp8) quantise the in-block Linear inputs to FP8 per row and "
+                         "multiply on the fp8 matrix pipe")
     return ap
 
 
@@ -566,6 +574,8 @@ def resolve_cli_heuristics(args, env=None):
 
 def main(argv: Optional[Sequence[str]] = None) -> None:
     args = resolve_cli_heuristics(build_parser().parse_args(argv))
+    if args.fp8_activations and not args.enable_fp8:
+        raise ValueError("--fp8-activations needs --enable-fp8: fp8 activations multiply fp8 weight panels")
     is_dev = args.pipeline == "dev"
     dev = torch.device("cuda:0")
     kw = {}
@@ -611,7 +621,7 @@ def main(argv: Optional[Sequence[str]] = None) -> None:
                    images=images, video_conditionings=videos, loras=args.lora, distilled_loras=args.distilled_lora,
                    conditioning_mode=args.conditioning_mode, stream=args.stream, stage2_dev=args.stage2_dev,
                    fp32_euler=args.fp32_euler, stg_scale=args.stg_scale, stg_blocks=args.stg_blocks, stg_mode=args.stg_mode,
-                   enable_fp8=args.enable_fp8, fp8_scaling=args.fp8_scaling, **kw)
+                   enable_fp8=args.enable_fp8, fp8_scaling=args.fp8_scaling, fp8_activations=args.fp8_activations, **kw)
 
 
 if __name__ == "__main__":

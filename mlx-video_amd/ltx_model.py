@@ -132,7 +132,10 @@ class ContextKV:
 class LTXModel:
     """Velocity model.  ``model(video=Modality(...)) -> (velocity (B,N,128), None)``."""
 
-    def __init__(self, config: LTXModelConfig, weights: Dict[str, torch.Tensor], fuse: int = 15):
+    def __init__(self, config: LTXModelConfig, weights: Dict[str, torch.Tensor], fuse: int = 15, fp8_activations: bool = False):
+        if fp8_activations and not any(torch.is_tensor(v) and v.dtype == FP8 for v in weights.values()):
+            raise ValueError("fp8_activations needs float8_e4m3fn weights (weights.transformer_weights(fp8=True) / "
+                             "quantize_transformer_weights): fp8 activations multiply fp8 weight panels")
         self.config = config
         self.inner_dim = config.inner_dim
         self.num_attention_heads = config.num_attention_heads
@@ -163,6 +166,14 @@ class LTXModel:
         # (_context_kv - the same bits; kept as the reference of the equality tests and for A/B timing)
         self.grouped_context_kv = True
         self._pack(weights)
+        # W8A8 (opt-in, fp8 weights only): the inputs of the in-block Linear GEMMs - nx, att, hff and the text
+        # context - are quantised per row to e4m3 (one ops.quant_rows_fp8 launch in front of the GEMM, the context once per
+        # forward) and multiplied fp8 x fp8 (ltxk_gemm_w8a8).  A launch the library would run as split-K (small M: a weight
+        # stream that gains nothing from fp8 arithmetic) keeps its W8A16 call; with batch_invariant nothing is split, so every
+        # in-block launch is W8A8 and, quantisation being per row, a row's bits stay independent of the batch.  The timestep /
+        # AdaLN GEMMs, patchify, the caption projection and the output head stay W8A16.
+        self.fp8_activations = bool(fp8_activations)
+        self._w8a8_plans: Dict[tuple, bool] = {}
         # the split-K scratch of ops.gemm (small-M launches) must exist before anyone captures a forward into a hipGraph: allocated
         # inside a capture it would come from that graph's private pool
         ops._gemm_workspace(self.tables.device)
@@ -364,6 +375,37 @@ class LTXModel:
         return cls(config, cls.random_weights(config, device, seed), fuse=fuse)
 
     # ------------------------------------------------------------------ forward
+    def _w8a8_launch(self, M: int, N: int, K: int, kw: dict) -> bool:
+        """Whether the ops.gemm call (M,K) x (N,K)^T with keyword arguments ``kw`` runs W8A8: the feature is on and the
+        library would run the W8A16 call single-pass (ops.gemm_plan(w8=True))."""
+        if not self.fp8_activations or K % 128 != 0:
+            return False
+        key = (M, N, K, kw.get("epilogue", ops.EPI_BIAS), kw.get("n_split", 0), kw.get("out_tokens_per_batch", 0),
+               kw.get("sumsq") is not None, kw.get("split_k", True))
+        if key not in self._w8a8_plans:
+            self._w8a8_plans[key] = not ops.gemm_plan(M, N, K, epilogue=key[3], n_split=key[4], out_tokens_per_batch=key[5],
+                                                      sumsq=key[6], split_k=key[7], w8=True).split_k
+        return self._w8a8_plans[key]
+
+    def _quant_for(self, a: torch.Tensor, launches) -> Optional[tuple]:
+        """(a8, a_scale) of ``a`` if any of ``launches`` [(w, bias, kwargs)] runs W8A8, else None: one quantiser launch."""
+        if any(self._w8a8_launch(a.shape[0], w.shape[0], a.shape[1], kw) for w, _, kw in launches):
+            return ops.quant_rows_fp8(a)
+        return None
+
+    def _lin(self, a: torch.Tensor, q: Optional[tuple], launches, fresh: bool = True) -> None:
+        """The ops.gemm launches [(w, bias, kwargs)] over one input ``a``.  ``q`` = (a8, a_scale) buffers (None: fp8
+        activations off - exactly the ops.gemm calls): ``a`` is quantised into them by ONE launch if any of the launches runs
+        W8A8 (``fresh=False``: they already hold ``a`` quantised), and those launches read the quantised copy."""
+        use = [q is not None and self._w8a8_launch(a.shape[0], w.shape[0], a.shape[1], kw) for w, _, kw in launches]
+        if fresh and any(use):
+            ops.quant_rows_fp8(a, out=q)
+        for (w, bias, kw), u in zip(launches, use):
+            if u:
+                ops.gemm(q[0], w, bias, a_scale=q[1], **kw)
+            else:
+                ops.gemm(a, w, bias, **kw)
+
     def _prepare_context(self, context: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """ltx.py:77-89: caption_projection, (B,S,3840) -> (B*S,D)."""
         b, s, c = context.shape
@@ -371,7 +413,17 @@ class LTXModel:
         h = ops.gemm(context.reshape(b * s, c), self.c1_w, self.c1_b, epilogue=ops.EPI_BIAS_GELU, split_k=sk, w_scale=self.c1_s)
         return ops.gemm(h, self.c2_w, self.c2_b, out=out, split_k=sk, w_scale=self.c2_s)
 
-    def _context_kv(self, blk: _Block, ctx: torch.Tensor, b: int, s: int, sp: int, out: Optional[tuple] = None):
+    def _context_kv_launches(self, blk: _Block, k2, vt2, st, s: int):
+        """The text k | V^T GEMM launches of one block as [(w, bias, kwargs)] (one launch with a split output, or two)."""
+        D, sk = self.inner_dim, not self.batch_invariant
+        if self.fuse & 1:
+            return [(blk.wkv2, blk.bkv2, dict(out=k2, out2=vt2, n_split=D, out_tokens_per_batch=s, sumsq=st, split_k=sk, w_scale=blk.skv2))]
+        return [(blk.wkv2[:D], blk.bkv2[:D], dict(out=k2, sumsq=st, split_k=sk, w_scale=_rows(blk.skv2, None, D))),
+                (blk.wkv2[D:], blk.bkv2[D:], dict(out=vt2, out_tokens_per_batch=s, split_k=sk, w_scale=_rows(blk.skv2, D, None)))]
+
+    def _context_kv(self, blk: _Block, ctx: torch.Tensor, b: int, s: int, sp: int, out: Optional[tuple] = None,
+                    ctx_q: Optional[tuple] = None):
+        """``ctx_q``: (ctx8, scale) - the context already quantised for the W8A8 launches (once per forward, not per block)."""
         D, H, eps = self.inner_dim, self.num_attention_heads, self.config.norm_eps
         if out is None:
             k2 = torch.empty((b * s, D), dtype=BF16, device=ctx.device)
@@ -382,14 +434,16 @@ class LTXModel:
             k2, vt2, ss = out
         # k (row-major, with its per-row sums of squares) and V^T from one launch over the packed k|v panel
         st = ss if self.fuse & 2 else None
-        sk = not self.batch_invariant
-        if self.fuse & 1:
-            ops.gemm(ctx, blk.wkv2, blk.bkv2, out=k2, out2=vt2, n_split=D, out_tokens_per_batch=s, sumsq=st, split_k=sk, w_scale=blk.skv2)
-        else:
-            ops.gemm(ctx, blk.wkv2[:D], blk.bkv2[:D], out=k2, sumsq=st, split_k=sk, w_scale=_rows(blk.skv2, None, D))
-            ops.gemm(ctx, blk.wkv2[D:], blk.bkv2[D:], out=vt2, out_tokens_per_batch=s, split_k=sk, w_scale=_rows(blk.skv2, D, None))
+        self._lin(ctx, ctx_q, self._context_kv_launches(blk, k2, vt2, st, s), fresh=False)
         ops.qknorm_rope(k2, 1, D, blk.wkn2, None, None, s, H, eps, sumsq=st)
         return k2, vt2, ss
+
+    def _quant_context(self, ctx: torch.Tensor, s: int) -> Optional[tuple]:
+        """The projected context quantised for the text k | V^T launches of ALL blocks (they share shapes, so one decision and
+        one quantiser launch per forward), or None where those launches stay W8A16."""
+        if not self.fp8_activations:
+            return None
+        return self._quant_for(ctx, self._context_kv_launches(self.blocks[0], None, None, True if self.fuse & 2 else None, s))
 
     def _grouped_context_ok(self, b: int, s: int) -> bool:
         """Whether the grouped launch gives the bits of the per-block ``_context_kv`` calls: it is single-pass, as they are unless
@@ -433,7 +487,8 @@ class LTXModel:
             kv.stacked = (k2, vt2, ss)
             kv.kv = [(k2[i], vt2[i], ss[i]) for i in range(len(self.blocks))]
             return kv
-        new = [self._context_kv(blk, kv.ctx, b, s, sp, kv.kv[i] if kv.kv else None) for i, blk in enumerate(self.blocks)]
+        ctx_q = self._quant_context(kv.ctx, s)
+        new = [self._context_kv(blk, kv.ctx, b, s, sp, kv.kv[i] if kv.kv else None, ctx_q) for i, blk in enumerate(self.blocks)]
         kv.kv = new
         kv.stacked = None
         return kv
@@ -501,6 +556,11 @@ class LTXModel:
         q2 = torch.empty((M, D), dtype=BF16, device=dev)
         q2ss = torch.empty((M, P), dtype=torch.float32, device=dev)
         hff = torch.empty((M, 4 * D), dtype=BF16, device=dev)
+        nx_q = att_q = hff_q = ctx_q = None
+        if self.fp8_activations:           # the quantised twins of the GEMM inputs: e4m3 rows + one fp32 scale per row
+            def qbuf(cols):
+                return (torch.empty((M, cols), dtype=FP8, device=dev), torch.empty((M,), dtype=torch.float32, device=dev))
+            nx_q, att_q, hff_q = qbuf(D), qbuf(D), qbuf(4 * D)
         ms = 6 * D
         kv_buf = kv_all = None
         if ctx_kv is None:
@@ -516,7 +576,8 @@ class LTXModel:
             # on 320x256 tiles with v's 160x256 tiles back-filling behind them; text k|v with q2): 1269.6 us per block either way.
             if self._grouped_context_ok(B, S):
                 kv_all = self._context_kv_all(ctx, B, S, sp64)
-            else:             # per block, one buffer set (the library would split K here, or the fused forms are off)
+            else:
+                ctx_q = self._quant_context(ctx, S)            # once per forward: every block's text k | V^T launch reads it             # per block, one buffer set (the library would split K here, or the fused forms are off)
                 kv_buf = (torch.empty((B * S, D), dtype=BF16, device=dev),
                           torch.zeros((B, D, sp64), dtype=BF16, device=dev) if sp64 != S else torch.empty((B, D, sp64), dtype=BF16, device=dev),
                           torch.empty((B * S, D // 64), dtype=torch.float32, device=dev))
@@ -541,11 +602,11 @@ class LTXModel:
             # with q|k|v as ONE launch (M=1296: 39.4 against 41.2 ms, 3328: 87.6 / 89.2, 5184: 141.5 / 143.8, 6656: 161.5 / 164.7;
             # scripts/exp_qkv_one_launch.py), and at small M every launch is a weight stream with ~5 us of fixed cost)
             if fq and (not (self.fuse & 8) or M <= ops.SPLITK_MAX_M or M % 320 != 0):
-                ops.gemm(nx, blk.wqkv, blk.bqkv, out=qk, out2=vt, n_split=2 * D, out_tokens_per_batch=N, sumsq=s_qk, split_k=sk,
-                         w_scale=blk.sqkv)
+                self._lin(nx, nx_q, [(blk.wqkv, blk.bqkv, dict(out=qk, out2=vt, n_split=2 * D, out_tokens_per_batch=N, sumsq=s_qk, split_k=sk,
+                                                               w_scale=blk.sqkv))])
             else:
-                ops.gemm(nx, blk.wqkv[:2 * D], blk.bqkv[:2 * D], out=qk, sumsq=s_qk, split_k=sk, w_scale=_rows(blk.sqkv, None, 2 * D))
-                ops.gemm(nx, blk.wqkv[2 * D:], blk.bqkv[2 * D:], out=vt, out_tokens_per_batch=N, split_k=sk, w_scale=_rows(blk.sqkv, 2 * D, None))
+                self._lin(nx, nx_q, [(blk.wqkv[:2 * D], blk.bqkv[:2 * D], dict(out=qk, sumsq=s_qk, split_k=sk, w_scale=_rows(blk.sqkv, None, 2 * D))),
+                                     (blk.wqkv[2 * D:], blk.bqkv[2 * D:], dict(out=vt, out_tokens_per_batch=N, split_k=sk, w_scale=_rows(blk.sqkv, 2 * D, None)))])
             skip = skip_rows[li]
             if fp:
                 ops.qknorm_rope(qk[:, D:], 1, D, blk.wkn, cos, sin, N, H, eps, sumsq=qkss[:, P:])
@@ -561,28 +622,28 @@ class LTXModel:
                     ops.flash_attn(qk[t0:t1, :D], qk[t0:t1, D:], vt[r0:r1], att[t0:t1], r1 - r0, H, N, N, scale, tail_split=ts_)
             if skip:          # STG: the skipped rows' attention output is their value projection, v = (V^T)^T
                 ops.attn_value_passthrough(vt, att, B, N, sum(1 << r for r in skip))
-            ops.gemm(att, blk.wo, blk.bo, epilogue=ops.EPI_BIAS_GATE_RES, out=x, resid=x,
-                     gate=mod[:, 2], gate_row=tok2row, gate_stride=ms, sumsq=s_x, split_k=sk, w_scale=blk.so)
+            self._lin(att, att_q, [(blk.wo, blk.bo, dict(epilogue=ops.EPI_BIAS_GATE_RES, out=x, resid=x,
+                                                         gate=mod[:, 2], gate_row=tok2row, gate_stride=ms, sumsq=s_x, split_k=sk, w_scale=blk.so))])
             # text cross-attention (transformer.py:257-261)
             ops.rmsnorm_modulate(x, eps, out=nx, sumsq=s_x)
-            ops.gemm(nx, blk.wq2, blk.bq2, out=q2, sumsq=s_q2, split_k=sk, w_scale=blk.sq2)
+            self._lin(nx, nx_q, [(blk.wq2, blk.bq2, dict(out=q2, sumsq=s_q2, split_k=sk, w_scale=blk.sq2))])
             if ctx_kv is not None:
                 kv = ctx_kv.kv[li]
             elif kv_all is not None:
                 kv = (kv_all[0][li], kv_all[1][li], kv_all[2][li])
             else:
-                kv = self._context_kv(blk, ctx, B, S, sp64, kv_buf)
+                kv = self._context_kv(blk, ctx, B, S, sp64, kv_buf, ctx_q)
             if fp:
                 ops.flash_attn(q2, kv[0], kv[1], att, B, H, N, S, scale, q_sumsq=q2ss, q_norm_weight=blk.wqn2, eps=eps, tail_split=ts_)
             else:
                 ops.qknorm_rope(q2, 1, D, blk.wqn2, None, None, N, H, eps, sumsq=s_q2)
                 ops.flash_attn(q2, kv[0], kv[1], att, B, H, N, S, scale, tail_split=ts_)
-            ops.gemm(att, blk.wo2, blk.bo2, epilogue=ops.EPI_BIAS_RES, out=x, resid=x, sumsq=s_x, split_k=sk, w_scale=blk.so2)
+            self._lin(att, att_q, [(blk.wo2, blk.bo2, dict(epilogue=ops.EPI_BIAS_RES, out=x, resid=x, sumsq=s_x, split_k=sk, w_scale=blk.so2))])
             # feed-forward (transformer.py:343-347)
             ops.rmsnorm_modulate(x, eps, mod[:, 4], mod[:, 3], ms, tok2row, out=nx, sumsq=s_x, scale_is_one_plus=bool(fs))
-            ops.gemm(nx, blk.w1, blk.b1, epilogue=ops.EPI_BIAS_GELU, out=hff, split_k=sk, w_scale=blk.s1)
-            ops.gemm(hff, blk.w2, blk.b2, epilogue=ops.EPI_BIAS_GATE_RES, out=x, resid=x,
-                     gate=mod[:, 5], gate_row=tok2row, gate_stride=ms, sumsq=s_x, split_k=sk, w_scale=blk.s2)
+            self._lin(nx, nx_q, [(blk.w1, blk.b1, dict(epilogue=ops.EPI_BIAS_GELU, out=hff, split_k=sk, w_scale=blk.s1))])
+            self._lin(hff, hff_q, [(blk.w2, blk.b2, dict(epilogue=ops.EPI_BIAS_GATE_RES, out=x, resid=x,
+                                                        gate=mod[:, 5], gate_row=tok2row, gate_stride=ms, sumsq=s_x, split_k=sk, w_scale=blk.s2))])
             if hidden is not None:
                 hidden.append(x.reshape(B, N, D).clone())
 

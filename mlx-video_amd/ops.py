@@ -95,7 +95,8 @@ def gemm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], *, epil
          gate: Optional[torch.Tensor] = None, gate_row: Optional[torch.Tensor] = None,
          gate_stride: int = 0, out_tokens_per_batch: int = 0, alpha: float = 1.0,
          out2: Optional[torch.Tensor] = None, n_split: int = 0, sumsq: Optional[torch.Tensor] = None,
-         split_k: bool = True, w_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
+         split_k: bool = True, w_scale: Optional[torch.Tensor] = None,
+         a_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
     """out = epi(a @ w.T + bias).  a (M,K) (row stride may exceed K), w (N,K) contiguous.
     ``w`` may be ``torch.float8_e4m3fn`` (ltxk_gemm_w8: the panel is read as fp8 and widened in registers; with no ``w_scale``
     the result equals the bf16 call on ``w.to(bfloat16)`` bit for bit); ``w_scale`` (N) fp32 then multiplies the accumulator
@@ -103,9 +104,24 @@ def gemm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], *, epil
     ``n_split``/``out2``: columns >= n_split go transposed per batch (out_tokens_per_batch tokens) to out2
     (B, N-n_split, ld).  ``sumsq``: (M, >= cols/64) fp32, receives the per-64-column sums of squares of the stored
     row-major outputs.  ``split_k=False``: no split-K scratch is offered, so the launch is single-pass (or big-tile) and
-    a row's bits do not depend on M; with it the library may split K at M <= SPLITK_MAX_M (``gemm_plan`` tells)."""
+    a row's bits do not depend on M; with it the library may split K at M <= SPLITK_MAX_M (``gemm_plan`` tells).
+    A ``float8_e4m3fn`` ``a`` together with ``a_scale`` (M) fp32 - what ``quant_rows_fp8`` returns - takes ltxk_gemm_w8a8: fp8
+    operands on the fp8 matrix pipe, acc * a_scale[m] * w_scale[n] in front of the bias.  It needs an fp8 ``w``, K % 128 == 0
+    and 16-byte aligned rows of ``a``; it is always single-pass (``split_k`` is ignored)."""
     w8 = w.dtype == FP8
-    _req(a, BF16, "gemm.a"); _req(w, FP8 if w8 else BF16, "gemm.w")
+    a8 = a.dtype == FP8
+    if a8 != (a_scale is not None):
+        raise TypeError("gemm: a float8_e4m3fn `a` and `a_scale` go together (quant_rows_fp8 gives both)")
+    if a8 and not w8:
+        raise TypeError(f"gemm: float8_e4m3fn activations need a float8_e4m3fn weight, got {w.dtype}")
+    if a8:
+        if a_scale.dtype != torch.float32:
+            raise TypeError(f"gemm.a_scale: expected torch.float32, got {a_scale.dtype}")
+        if a_scale.shape != (a.shape[0],) or not a_scale.is_contiguous():
+            raise ValueError(f"gemm: a_scale must be a contiguous ({a.shape[0]},) vector, got {tuple(a_scale.shape)}")
+    _req(a, FP8 if a8 else BF16, "gemm.a"); _req(w, FP8 if w8 else BF16, "gemm.w")
+    if a8:
+        _req(a_scale, torch.float32, "gemm.a_scale")
     if w_scale is not None:
         if not w8:
             raise TypeError("gemm: w_scale goes with a float8_e4m3fn weight")
@@ -138,6 +154,10 @@ def gemm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], *, epil
     args.alpha = alpha
     args.out2, args.n_split, args.ldo2 = _p(out2), n_split, (out2.stride(-2) if out2 is not None else 0)
     args.sumsq, args.sumsq_ld = _p(sumsq), (sumsq.stride(0) if sumsq is not None else 0)
+    if a8:
+        with _timed("gemm_w8a8", 2.0 * M * N * K, 1.0 * (M * K + N * K) + 2.0 * M * N):
+            check(_lib.load().ltxk_gemm_w8a8(ctypes.byref(args), _p(a_scale), _p(w_scale), _stream()), "ltxk_gemm_w8a8")
+        return out
     if _offers_workspace(M, split_k):
         ws = _gemm_workspace(a.device)
         args.workspace, args.workspace_bytes = ws.data_ptr(), ws.numel() * 4
@@ -171,12 +191,14 @@ _PLAN_ADDR = 1 << 12          # stands in for every device pointer of a planned 
 
 def gemm_plan(M: int, N: int, K: int, *, epilogue: int = EPI_BIAS, lda: Optional[int] = None, ldo: Optional[int] = None,
               out_tokens_per_batch: int = 0, n_split: int = 0, ldo2: Optional[int] = None, sumsq: bool = False,
-              split_k: bool = True, workspace: Optional[Tuple[int, int]] = None, w8: bool = False) -> GemmPlan:
+              split_k: bool = True, workspace: Optional[Tuple[int, int]] = None, w8: bool = False,
+              w8a8: bool = False) -> GemmPlan:
     """The form ``gemm`` takes for an (M,K) x (N,K)^T launch with these options, decided on the host by the function the
     launch itself uses (no device needed).  The split-K scratch is offered exactly as ``gemm`` offers it (``split_k``,
     SPLITK_MAX_M); ``workspace=(address, bytes)`` offers that one instead (address 0: none).  Strides default to those of
     contiguous tensors (V^T: tokens padded to 64).  Raises LtxkError where ``gemm`` would refuse the arguments.
-    ``w8``: the plan of the same call with a float8_e4m3fn weight (ltxk_gemm_w8_plan)."""
+    ``w8``: the plan of the same call with a float8_e4m3fn weight (ltxk_gemm_w8_plan).  ``w8a8``: with float8_e4m3fn
+    activations too (ltxk_gemm_w8a8_plan: always single-pass, 128-wide K-steps)."""
     args = GemmArgs()
     args.A = args.W = args.out = _PLAN_ADDR
     args.M, args.N, args.K = M, N, K
@@ -198,11 +220,34 @@ def gemm_plan(M: int, N: int, K: int, *, epilogue: int = EPI_BIAS, lda: Optional
     elif _offers_workspace(M, split_k):
         args.workspace, args.workspace_bytes = _PLAN_ADDR, GEMM_WORKSPACE_BYTES
     pl = _lib.GemmPlan()
-    if w8:
+    if w8a8:
+        check(_lib.load().ltxk_gemm_w8a8_plan(ctypes.byref(args), ctypes.byref(pl)), "ltxk_gemm_w8a8_plan")
+    elif w8:
         check(_lib.load().ltxk_gemm_w8_plan(ctypes.byref(args), ctypes.byref(pl)), "ltxk_gemm_w8_plan")
     else:
         check(_lib.load().ltxk_gemm_plan(ctypes.byref(args), ctypes.byref(pl)), "ltxk_gemm_plan")
     return GemmPlan(pl.form, pl.tile_rows, pl.tile_cols, pl.row_tiles, pl.col_tiles, pl.slices, pl.ksteps)
+
+
+def quant_rows_fp8(a: torch.Tensor, out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """ltxk_quant_rows_fp8: a (M,K) bf16 (row stride may exceed K) -> (a8 (M,K) float8_e4m3fn, a_scale (M) fp32) with
+    a ~= a8 * a_scale[:, None]: per row scale = max(max|a|, 2^-64) / 448 and a8 = e4m3(a / scale), round to nearest even.
+    ``out=(a8, a_scale)``: write into these (a8 may be a strided view; a_scale contiguous)."""
+    _req(a, BF16, "quant_rows_fp8.a")
+    if a.dim() != 2 or a.stride(1) != 1:
+        raise ValueError(f"quant_rows_fp8: expected a (M,K) matrix with unit inner stride, got {tuple(a.shape)}")
+    M, K = a.shape
+    if out is None:
+        a8 = torch.empty((M, K), dtype=FP8, device=a.device)
+        sc = torch.empty((M,), dtype=torch.float32, device=a.device)
+    else:
+        a8, sc = out
+        _req(a8, FP8, "quant_rows_fp8.out[0]"); _req(sc, torch.float32, "quant_rows_fp8.out[1]")
+        if tuple(a8.shape) != (M, K) or a8.stride(1) != 1 or tuple(sc.shape) != (M,) or not sc.is_contiguous():
+            raise ValueError(f"quant_rows_fp8: out must be ((M,K) fp8 with unit inner stride, (M,) fp32), got {tuple(a8.shape)}, {tuple(sc.shape)}")
+    with _timed("quant_rows_fp8", 0.0, 3.0 * M * K):
+        check(_lib.load().ltxk_quant_rows_fp8(_p(a), a.stride(0), _p(a8), a8.stride(0), _p(sc), M, K, _stream()), "ltxk_quant_rows_fp8")
+    return a8, sc
 
 
 def pointer_table(tensors) -> torch.Tensor:

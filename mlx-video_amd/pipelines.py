@@ -31,6 +31,7 @@ class MLXPipelineConfig:
     conditioning_mode: str = "replace"
     fp8transformer: bool = False        # ltx_pipelines/utils/model_ledger.py:36; --enable-fp8
     fp8_scaling: str = "channel"
+    fp8activations: bool = False        # (not in the reference) --fp8-activations: W8A8 in-block GEMMs; needs fp8transformer
 
 
 def _ensure_list(v):
@@ -89,7 +90,8 @@ def run_generate(prompt: str, pipeline: PipelineType, cfg: MLXPipelineConfig, ou
                             video_conditionings=_normalize_video_conditions(video_conditionings),
                             conditioning_mode=cfg.conditioning_mode, tiling=cfg.tiling, stream=cfg.stream, audio=cfg.audio,
                             loras=_normalize_loras(loras), distilled_loras=_normalize_loras(distilled_loras),
-                            enable_fp8=cfg.fp8transformer, fp8_scaling=cfg.fp8_scaling, **inject)
+                            enable_fp8=cfg.fp8transformer, fp8_scaling=cfg.fp8_scaling, fp8_activations=cfg.fp8activations,
+                            **inject)
     return output_path if output_path is not None else frames
 
 
@@ -118,6 +120,7 @@ class _Base:
     tiling: str = "auto"
     fp8transformer: bool = False
     fp8_scaling: str = "channel"
+    fp8activations: bool = False
 
     def _cfg(self, **over) -> MLXPipelineConfig:
         names = {f.name for f in fields(MLXPipelineConfig)}
