@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define LTXK_VERSION 405
+#define LTXK_VERSION 406
 
 #define LTXK_OK 0
 #define LTXK_EINVAL (-1)   /* bad argument (shape / alignment / null pointer) */
@@ -390,7 +390,7 @@ typedef struct ltxk_conv3d_args {
   int64_t workspace_bytes;
   /* temporal taps: 0 or 3 = the 3x3x3 kernel; 1 = a per-frame 3x3 kernel, w = (Cout,3,3,Cin) (the latent
    * upsampler's nn.Conv2d applied frame by frame, upsampler.py:64-99): only the centre temporal tap exists,
-   * K = 9*Cin instead of 27*Cin.                                                                        */
+   * K = 9*Cin instead of 27*Cin.  A voxel then reads its own frame alone, whatever `causal` says.      */
   int32_t taps_d;
   /* Optional fused PixelNorm (+ AdaLN modulation) + SiLU of the OUTPUT row (decoder.py:136-180: the pixel_norm / scale /
    * shift / SiLU that follows every conv of a res block; utils.py:477-483):
@@ -407,6 +407,29 @@ typedef struct ltxk_conv3d_args {
 
 /* nn.Conv3d 3x3x3 stride 1 inside CausalConv3d (convolution.py:78-222) as implicit GEMM.   */
 int ltxk_conv3d_k3_bf16(const ltxk_conv3d_args* args, void* stream);
+
+/* The launch form ltxk_conv3d_k3_bf16 takes for `args`, decided without launching anything (host only: pointers are checked
+ * for NULL / alignment, never read).  ltxk_conv3d_k3_bf16 decides its form by the same host function, so a plan and a launch
+ * of the same arguments cannot disagree; the same argument checks run and return the same error codes.
+ * Every form computes a row's sum with the same rounding points; the kw-reuse kernel and the split-K slices walk K in another
+ * order than the per-tap single pass.  A tail launch gives its rows the bits of the main tile.                            */
+enum { LTXK_CONV_KERNEL_PER_TAP = 0, LTXK_CONV_KERNEL_KW = 1 };
+struct ltxk_conv3d_plan {   /* a struct tag only: the name is also the function's */
+  int32_t kernel;               /* LTXK_CONV_KERNEL_*: one A tile per tap, or one A panel per (kd, kh) shared by the 3 kw taps */
+  int32_t tile_rows, tile_cols; /* workgroup tile of the main launch: 256 x 128 or 160 x 256 (kw: 256 x 128)             */
+  int32_t row_tiles, col_tiles; /* tiles of the main launch over the voxel rows and over Cout                            */
+  int32_t slices;               /* K slices (1 unless split-K: fp32 slabs in the workspace + a finalize launch)          */
+  int32_t ksteps;               /* K-steps per slice, the last slice may have fewer; per-tap: 64 channels of one tap
+                                 * (taps * Cin/64 in all), kw: 32 channels of the 3 kw taps of one (kd, kh) (9 * Cin/32)   */
+  /* The rows past the last whole round of 256 workgroups run as a second launch of lower tiles (128 rows for the 256-row
+   * tile, 96 for the 160-row tile) over rows [tail_m_base, M); the main launch then covers row_tiles * tile_rows rows.
+   * All three are 0 when there is no tail launch.                                                                       */
+  int32_t tail_tile_rows, tail_m_base, tail_row_tiles;
+  int32_t fused_act;            /* 1: the PixelNorm / modulation / SiLU epilogue runs (act_out set)                      */
+};
+int ltxk_conv3d_plan(const ltxk_conv3d_args* args, struct ltxk_conv3d_plan* plan);
+/* sizeof(struct ltxk_conv3d_plan) in this build (an entry of its own: the ltxk_abi_sizeof index list is closed).          */
+int ltxk_conv3d_plan_sizeof(void);
 
 /* pixel_norm over channels [+ (1+scale)+shift per (batch,channel)] [+ SiLU]: decoder.py:136-180,
  * 415-437; utils.py:477-483.  x,y: (V,C) rows = voxels, C in {64..2048, power of two}.

@@ -71,6 +71,14 @@ class Conv3dArgs(Structure):
     ]
 
 
+class Conv3dPlan(Structure):
+    _fields_ = [
+        ("kernel", c_int32), ("tile_rows", c_int32), ("tile_cols", c_int32), ("row_tiles", c_int32), ("col_tiles", c_int32),
+        ("slices", c_int32), ("ksteps", c_int32),
+        ("tail_tile_rows", c_int32), ("tail_m_base", c_int32), ("tail_row_tiles", c_int32), ("fused_act", c_int32),
+    ]
+
+
 class StepArgs(Structure):
     _fields_ = [
         ("v_pos", c_void_p), ("v_neg", c_void_p), ("v_pert", c_void_p), ("latent", c_void_p), ("out", c_void_p),
@@ -117,6 +125,8 @@ SIGNATURES = {
     "ltxk_silu": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p]),
     "ltxk_latent_to_tokens": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "ltxk_conv3d_k3_bf16": (c_int32, [POINTER(Conv3dArgs), c_void_p]),
+    "ltxk_conv3d_plan": (c_int32, [POINTER(Conv3dArgs), POINTER(Conv3dPlan)]),
+    "ltxk_conv3d_plan_sizeof": (c_int32, []),
     "ltxk_pixelnorm_act": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_float, c_void_p, c_void_p, c_int64,
                                      c_int32, c_void_p]),
     "ltxk_d2s_add": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
@@ -154,6 +164,7 @@ _lib = None
 AB_LIB_PATH = os.path.join(_HERE, "libltxk_ab.so")
 ATTN_NO_TAIL_SPLIT = 1        # ltxk.h: LTXK_ATTN_NO_TAIL_SPLIT
 GEMM_FORM_SINGLE, GEMM_FORM_BIG, GEMM_FORM_SPLITK = 0, 1, 2     # ltxk.h: LTXK_GEMM_FORM_*
+CONV_KERNEL_PER_TAP, CONV_KERNEL_KW = 0, 1                      # ltxk.h: LTXK_CONV_KERNEL_*
 
 
 def _open(path: str) -> ctypes.CDLL:
@@ -175,6 +186,9 @@ def _open(path: str) -> ctypes.CDLL:
     if lib.ltxk_gemm_grouped_args_sizeof() != ctypes.sizeof(GemmGroupedArgs):
         raise LtxkError(f"{path} is stale: sizeof(GemmGroupedArgs) is {lib.ltxk_gemm_grouped_args_sizeof()} in the library, "
                         f"{ctypes.sizeof(GemmGroupedArgs)} in this binding; rebuild it (make -C mlx-video_amd/csrc)")
+    if lib.ltxk_conv3d_plan_sizeof() != ctypes.sizeof(Conv3dPlan):
+        raise LtxkError(f"{path} is stale: sizeof(Conv3dPlan) is {lib.ltxk_conv3d_plan_sizeof()} in the library, "
+                        f"{ctypes.sizeof(Conv3dPlan)} in this binding; rebuild it (make -C mlx-video_amd/csrc)")
     return lib
 
 

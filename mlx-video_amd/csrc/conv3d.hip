@@ -87,7 +87,8 @@ __global__ __launch_bounds__(GEMM_THREADS) void conv3d_k3_kernel(ConvParams p) {
     unsigned zb = 0;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-      int d = vd + k - (p.causal == 1 ? 2 : 1);
+      // (the per-frame 9-tap kernel has only kd = 1, which is the voxel's own frame in every temporal halo mode)
+      int d = vd + k - (p.causal == 1 && p.ntaps == 27 ? 2 : 1);
       if (p.causal == 2) {                                 // plain zero padding in time (latent upsampler)
         if (d < 0 || d >= p.D) { zb |= 64u << k; d = 0; }
       } else {
@@ -760,29 +761,6 @@ static int conv_launch_kw(const ConvParams& p0, hipStream_t stream) {
   return LTXK_OK;
 }
 
-// whole rounds of 256-row tiles, then the rows of the short last round as 128-row tiles (same bits: a row's sum does not
-// depend on the tile it is in)
-template <bool RES>
-static int conv_launch_kw_all(const ConvParams& p0, hipStream_t stream) {
-  ConvParams p = p0;
-  const int CT = (p.Cout + KW_BN - 1) / KW_BN;
-  const int RT = (p.M + 255) / 256;
-  const int tiles = RT * CT;
-  const int rem_rt = (tiles % 256) / CT;
-  const int rt_main = RT - rem_rt;
-  const long tail_rows = (long)p.M - (long)rt_main * 256;
-  const long tail_tiles = (tail_rows + 127) / 128 * CT;
-  if (LTXK_AB_INT("LTXK_CONV_TAIL", 1) && tiles > 256 && rem_rt > 0 && rt_main > 0 && (long)rt_main * CT % 256 < CT && tail_tiles <= 256) {
-    p.m_base = 0; p.RT = rt_main;
-    int rc = conv_launch_kw<4, RES>(p, stream);
-    if (rc != LTXK_OK) return rc;
-    p.m_base = rt_main * 256; p.RT = (int)((tail_rows + 127) / 128);
-    return conv_launch_kw<2, RES>(p, stream);
-  }
-  p.m_base = 0; p.RT = RT;
-  return conv_launch_kw<4, RES>(p, stream);
-}
-
 template <int TT, int WN, bool RES>
 static int conv_launch_plain(const ConvParams& p, hipStream_t stream) {
   using G = GemmGeom<TT, WN>;
@@ -803,74 +781,15 @@ static int conv_launch_plain(const ConvParams& p, hipStream_t stream) {
   return LTXK_OK;
 }
 
-template <int TT, int WN, bool RES>
-static int conv_launch(const ConvParams& p0, hipStream_t stream, float* workspace, size_t workspace_bytes) {
-  using G = GemmGeom<TT, WN>;
-  ConvParams p = p0;
-  p.RT = (p.M + G::BM - 1) / G::BM;
-  p.CT = (p.Cout + G::BN - 1) / G::BN;
-  const int tiles = p.RT * p.CT, nk = p.ntaps * p.cpb;
-  // split K when the tile grid leaves most of the 256 CUs idle (the 1024/512-channel stages of the decoder
-  // have only 1280 / 9216 voxels): S slices of >= 16 K-steps, fp32 slabs in the caller's workspace.
-  int S = 1;
-  if (workspace && tiles <= 128) {
-    S = 256 / tiles;
-    if (S > nk / 16) S = nk / 16;
-    const size_t per = (size_t)p.M * p.Cout * sizeof(float);
-    if ((size_t)S * per > workspace_bytes) S = (int)(workspace_bytes / per);
-    if (S > 16) S = 16;
-  }
-  if (S >= 2) {
-    auto kern = conv3d_k3_kernel<TT, WN, false, true>;
-    static thread_local int attr_dev_s = -1;
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev != attr_dev_s) {
-      hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES);
-      if (e != hipSuccess) { ltxk_set_error("ltxk_conv3d_k3_bf16: hipFuncSetAttribute: %s", hipGetErrorString(e)); return LTXK_ELAUNCH; }
-      attr_dev_s = dev;
-    }
-    p.slab = workspace; p.S = S; p.kper = (nk + S - 1) / S;
-    p.S = (nk + p.kper - 1) / p.kper;                      // drop empty trailing slices
-    hipLaunchKernelGGL(kern, dim3(tiles * p.S), dim3(GEMM_THREADS), G::LDS_BYTES, stream, p);
-    LTXK_CHECK_LAUNCH("ltxk_conv3d_k3_bf16(split-K)");
-    const size_t total = (size_t)p.M * p.Cout / 4;
-    hipLaunchKernelGGL(conv_splitk_finalize_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream,
-                       (const float*)workspace, p.bias, p.resid, p.out, p.M, p.Cout, p.S);
-    LTXK_CHECK_LAUNCH("ltxk_conv3d_k3_bf16(finalize)");
-    return LTXK_OK;
-  }
-  p.slab = nullptr; p.S = 1; p.kper = nk;
-  // A short last round takes as long as a whole one: the 128-channel stage at 33x128x128 voxels is 2112 tiles of 256 rows =
-  // 8.25 rounds of 256 CUs, the 512-channel stage 7.2, the 256-channel stage 27.2.  The rows past the last whole round run as
-  // a second launch of lower tiles (128 instead of 256 rows, 96 instead of 160): more workgroups, less work each - a
-  // fraction of a round instead of one.  Every output row is still the same K-ordered sum: same bits.
-  if constexpr ((TT == 4 && WN == 2) || (TT == 5 && WN == 4)) {
-    constexpr int TTT = TT == 4 ? 2 : 3;                          // tail tile height in 16-row MFMA blocks per wave row
-    using GT = GemmGeom<TTT, WN>;
-    const int tail_env = LTXK_AB_INT("LTXK_CONV_TAIL", 1);        // 0: off (A/B build only)
-    const int rem_rt = (tiles % 256) / p.CT;                      // whole row tiles past the last whole round
-    const int rt_main = p.RT - rem_rt;
-    const long tail_rows = (long)p.M - (long)rt_main * G::BM;
-    const long tail_tiles = (tail_rows + GT::BM - 1) / GT::BM * p.CT;
-    if (tail_env && tiles > 256 && rem_rt > 0 && rt_main > 0 && (long)rt_main * p.CT % 256 < p.CT && tail_tiles <= 256) {
-      ConvParams pm = p;
-      pm.RT = rt_main;
-      int rc = conv_launch_plain<TT, WN, RES>(pm, stream);
-      if (rc != LTXK_OK) return rc;
-      ConvParams pt = p;
-      pt.m_base = rt_main * G::BM;
-      pt.RT = (int)((tail_rows + GT::BM - 1) / GT::BM);
-      return conv_launch_plain<TTT, WN, RES>(pt, stream);
-    }
-  }
-  return conv_launch_plain<TT, WN, RES>(p, stream);
-}
+// The launch form of one ltxk_conv3d_k3_bf16 call: the argument checks, then kernel / tile / split-K slices / tail launch.
+// ltxk_conv3d_k3_bf16 launches what this decides and ltxk_conv3d_plan reports it, so the two cannot drift apart.
+struct ConvForm {
+  struct ltxk_conv3d_plan plan;
+  int M, ntaps;
+  float* ws;         // the split-K scratch on offer (NULL with the fused activation)
+};
 
-}  // namespace ltxk
-
-extern "C" int ltxk_conv3d_k3_bf16(const ltxk_conv3d_args* a, void* stream) {
-  using namespace ltxk;
+static int conv_form(const ltxk_conv3d_args* a, ConvForm& f) {
   LTXK_CHECK_ARG(a != nullptr, "ltxk_conv3d_k3_bf16: null args");
   LTXK_CHECK_ARG(a->x && a->w && a->bias && (a->out || a->act_out) && a->zero_page, "ltxk_conv3d_k3_bf16: null x/w/bias/out/zero_page");
   LTXK_CHECK_ARG(a->B > 0 && a->D > 0 && a->H >= 2 && a->W >= 2, "ltxk_conv3d_k3_bf16: bad volume %dx%dx%dx%d", a->B, a->D, a->H, a->W);
@@ -880,27 +799,40 @@ extern "C" int ltxk_conv3d_k3_bf16(const ltxk_conv3d_args* a, void* stream) {
                  "ltxk_conv3d_k3_bf16: misaligned pointer");
   const long long M = (long long)a->B * a->D * a->H * a->W;
   LTXK_CHECK_ARG(M < (1ll << 31) && M * a->Cin * 2 < (1ll << 32), "ltxk_conv3d_k3_bf16: input volume must be < 4 GiB (32-bit tile offsets)");
-  ConvParams p;
-  p.x = (const bf16*)a->x; p.w = (const bf16*)a->w; p.bias = (const bf16*)a->bias; p.out = (bf16*)a->out;
-  p.resid = (const bf16*)a->resid; p.zero = (const bf16*)a->zero_page;
-  p.B = a->B; p.D = a->D; p.H = a->H; p.W = a->W; p.Cin = a->Cin; p.Cout = a->Cout;
-  p.causal = a->causal; p.pad_mode = a->pad_mode; p.M = (int)M; p.cpb = a->Cin / 64; p.RT = p.CT = 0;
   LTXK_CHECK_ARG(a->taps_d == 0 || a->taps_d == 3 || a->taps_d == 1, "ltxk_conv3d_k3_bf16: taps_d must be 3 (or 0) or 1, got %d", a->taps_d);
-  p.ntaps = a->taps_d == 1 ? 9 : 27; p.kd0 = a->taps_d == 1 ? 1 : 0;
-  p.act_out = (bf16*)a->act_out; p.act_scale = (const bf16*)a->act_scale; p.act_shift = (const bf16*)a->act_shift;
-  p.act_eps = a->act_eps; p.act_silu = a->act_silu; p.rows_per_batch = a->D * a->H * a->W;
-  p.xcd_order = LTXK_AB_INT("LTXK_CONV_XCD", 1);
-  p.m_base = 0;
   if (a->act_out) {
     LTXK_CHECK_ARG(a->Cout == 128 || a->Cout == 256, "ltxk_conv3d_k3_bf16: the fused norm/activation output needs Cout == 128 or 256 (got %d)", a->Cout);
     LTXK_CHECK_ARG((a->act_scale == nullptr) == (a->act_shift == nullptr), "ltxk_conv3d_k3_bf16: act_scale and act_shift must both be set or both NULL");
     LTXK_CHECK_ARG(((uintptr_t)a->act_out & 15) == 0 && (((uintptr_t)a->act_scale | (uintptr_t)a->act_shift) & 7) == 0, "ltxk_conv3d_k3_bf16: misaligned act_* pointer");
   }
-  hipStream_t st = (hipStream_t)stream;
-  const bool res = a->resid != nullptr;
   float* ws = a->act_out ? nullptr : (float*)a->workspace;          // the fused row statistic lives in the tile: no split-K
   const size_t wsb = ws ? (size_t)a->workspace_bytes : 0;
   LTXK_CHECK_ARG(((uintptr_t)ws & 15) == 0, "ltxk_conv3d_k3_bf16: workspace must be 16-byte aligned");
+  f.M = (int)M;
+  f.ntaps = a->taps_d == 1 ? 9 : 27;
+  f.ws = ws;
+  struct ltxk_conv3d_plan& pl = f.plan;
+  pl = {};
+  pl.slices = 1;
+  pl.fused_act = a->act_out ? 1 : 0;
+  // A short last round takes as long as a whole one: the 128-channel stage at 33x128x128 voxels is 2112 tiles of 256 rows =
+  // 8.25 rounds of 256 CUs, the 512-channel stage 7.2, the 256-channel stage 27.2.  The rows past the last whole round run as
+  // a second launch of lower tiles (128 instead of 256 rows, 96 instead of 160): more workgroups, less work each - a
+  // fraction of a round instead of one.  Every output row is still the same K-ordered sum: same bits.
+  const int tail_env = LTXK_AB_INT("LTXK_CONV_TAIL", 1);            // 0: off (A/B build only)
+  auto plan_tail = [&](int bm_tail) {
+    const long tiles = (long)pl.row_tiles * pl.col_tiles;
+    const int rem_rt = (int)((tiles % 256) / pl.col_tiles);         // whole row tiles past the last whole round
+    const int rt_main = pl.row_tiles - rem_rt;
+    const long tail_rows = (long)M - (long)rt_main * pl.tile_rows;
+    const long tail_rt = (tail_rows + bm_tail - 1) / bm_tail;
+    if (tail_env && tiles > 256 && rem_rt > 0 && rt_main > 0 && (long)rt_main * pl.col_tiles % 256 < pl.col_tiles && tail_rt * pl.col_tiles <= 256) {
+      pl.row_tiles = rt_main;
+      pl.tail_tile_rows = bm_tail;
+      pl.tail_m_base = rt_main * pl.tile_rows;
+      pl.tail_row_tiles = (int)tail_rt;
+    }
+  };
   // kw-reuse form (see conv3d_k3_kw_kernel): the 27-tap convolution on volumes at least 64 voxels wide whose tile grid
   // fills the chip without split-K
   {
@@ -909,12 +841,122 @@ extern "C" int ltxk_conv3d_k3_bf16(const ltxk_conv3d_args* a, void* stream) {
     // (A/B build: 2 = wherever legal, 0 = never.  By default only where one 128-column tile spans Cout: with several
     // column tiles the A panel is re-fetched per column tile and the per-tap kernel's 160x256 tile moves fewer bytes.)
     const bool kw_pays = kw_mode == 2 || a->Cout <= KW_BN;
-    if (kw_mode && kw_pays && p.ntaps == 27 && a->W >= 64 && a->Cin % 32 == 0 && !a->act_out && a->out && (tiles_kw > 128 || !ws)) {
-      return res ? conv_launch_kw_all<true>(p, st) : conv_launch_kw_all<false>(p, st);
+    if (kw_mode && kw_pays && f.ntaps == 27 && a->W >= 64 && a->Cin % 32 == 0 && !a->act_out && a->out && (tiles_kw > 128 || !ws)) {
+      pl.kernel = LTXK_CONV_KERNEL_KW;
+      pl.tile_rows = 256; pl.tile_cols = KW_BN;
+      pl.row_tiles = (int)((M + 255) / 256);
+      pl.col_tiles = (a->Cout + KW_BN - 1) / KW_BN;
+      pl.ksteps = 9 * (a->Cin / 32);
+      plan_tail(128);
+      return LTXK_OK;
     }
   }
-  if (a->Cout <= 128) {       // 256x128 tile: no wasted MFMA columns on the 128-channel stage
-    return res ? conv_launch<4, 2, true>(p, st, ws, wsb) : conv_launch<4, 2, false>(p, st, ws, wsb);
+  pl.kernel = LTXK_CONV_KERNEL_PER_TAP;
+  const bool t256 = a->Cout <= 128;       // 256x128 tile: no wasted MFMA columns on the 128-channel stage; else 160x256
+  pl.tile_rows = t256 ? 256 : 160;
+  pl.tile_cols = t256 ? 128 : 256;
+  pl.row_tiles = (int)((M + pl.tile_rows - 1) / pl.tile_rows);
+  pl.col_tiles = (a->Cout + pl.tile_cols - 1) / pl.tile_cols;
+  const int tiles = pl.row_tiles * pl.col_tiles, nk = f.ntaps * (a->Cin / 64);
+  pl.ksteps = nk;
+  // split K when the tile grid leaves most of the 256 CUs idle (the 1024/512-channel stages of the decoder
+  // have only 1280 / 9216 voxels): S slices of >= 16 K-steps, fp32 slabs in the caller's workspace.
+  int S = 1;
+  if (ws && tiles <= 128) {
+    S = 256 / tiles;
+    if (S > nk / 16) S = nk / 16;
+    const size_t per = (size_t)M * a->Cout * sizeof(float);
+    if ((size_t)S * per > wsb) S = (int)(wsb / per);
+    if (S > 16) S = 16;
   }
-  return res ? conv_launch<5, 4, true>(p, st, ws, wsb) : conv_launch<5, 4, false>(p, st, ws, wsb);
+  if (S >= 2) {
+    pl.ksteps = (nk + S - 1) / S;
+    pl.slices = (nk + pl.ksteps - 1) / pl.ksteps;                  // drop empty trailing slices
+    return LTXK_OK;
+  }
+  plan_tail(t256 ? 128 : 96);
+  return LTXK_OK;
+}
+
+// main launch, then the tail launch of lower tiles if the form has one
+template <bool RES>
+static int conv_launch_kw_all(const ConvParams& p0, const ConvForm& f, hipStream_t stream) {
+  const struct ltxk_conv3d_plan& pl = f.plan;
+  ConvParams p = p0;
+  p.m_base = 0; p.RT = pl.row_tiles;
+  int rc = conv_launch_kw<4, RES>(p, stream);
+  if (rc != LTXK_OK || !pl.tail_row_tiles) return rc;
+  p.m_base = pl.tail_m_base; p.RT = pl.tail_row_tiles;
+  return conv_launch_kw<2, RES>(p, stream);
+}
+
+template <int TT, int WN, bool RES>
+static int conv_launch(const ConvParams& p0, const ConvForm& f, hipStream_t stream) {
+  using G = GemmGeom<TT, WN>;
+  const struct ltxk_conv3d_plan& pl = f.plan;
+  ConvParams p = p0;
+  p.RT = pl.row_tiles;
+  p.CT = pl.col_tiles;
+  if (pl.slices >= 2) {
+    auto kern = conv3d_k3_kernel<TT, WN, false, true>;
+    static thread_local int attr_dev_s = -1;
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    if (dev != attr_dev_s) {
+      hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES);
+      if (e != hipSuccess) { ltxk_set_error("ltxk_conv3d_k3_bf16: hipFuncSetAttribute: %s", hipGetErrorString(e)); return LTXK_ELAUNCH; }
+      attr_dev_s = dev;
+    }
+    p.slab = f.ws; p.S = pl.slices; p.kper = pl.ksteps;
+    hipLaunchKernelGGL(kern, dim3(p.RT * p.CT * p.S), dim3(GEMM_THREADS), G::LDS_BYTES, stream, p);
+    LTXK_CHECK_LAUNCH("ltxk_conv3d_k3_bf16(split-K)");
+    const size_t total = (size_t)p.M * p.Cout / 4;
+    hipLaunchKernelGGL(conv_splitk_finalize_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream,
+                       (const float*)f.ws, p.bias, p.resid, p.out, p.M, p.Cout, p.S);
+    LTXK_CHECK_LAUNCH("ltxk_conv3d_k3_bf16(finalize)");
+    return LTXK_OK;
+  }
+  p.slab = nullptr; p.S = 1; p.kper = pl.ksteps;
+  int rc = conv_launch_plain<TT, WN, RES>(p, stream);
+  if (rc != LTXK_OK || !pl.tail_row_tiles) return rc;
+  constexpr int TTT = TT == 4 ? 2 : 3;                            // tail tile height in 16-row MFMA blocks per wave row
+  p.m_base = pl.tail_m_base;
+  p.RT = pl.tail_row_tiles;
+  return conv_launch_plain<TTT, WN, RES>(p, stream);
+}
+
+}  // namespace ltxk
+
+extern "C" int ltxk_conv3d_plan(const ltxk_conv3d_args* a, struct ltxk_conv3d_plan* plan) {
+  using namespace ltxk;
+  LTXK_CHECK_ARG(plan != nullptr, "ltxk_conv3d_plan: null plan");
+  ConvForm f;
+  const int rc = conv_form(a, f);
+  if (rc == LTXK_OK) *plan = f.plan;
+  return rc;
+}
+
+extern "C" int ltxk_conv3d_plan_sizeof(void) { return (int)sizeof(struct ltxk_conv3d_plan); }
+
+extern "C" int ltxk_conv3d_k3_bf16(const ltxk_conv3d_args* a, void* stream) {
+  using namespace ltxk;
+  ConvForm f;
+  const int rc = conv_form(a, f);
+  if (rc != LTXK_OK) return rc;
+  ConvParams p;
+  p.x = (const bf16*)a->x; p.w = (const bf16*)a->w; p.bias = (const bf16*)a->bias; p.out = (bf16*)a->out;
+  p.resid = (const bf16*)a->resid; p.zero = (const bf16*)a->zero_page;
+  p.B = a->B; p.D = a->D; p.H = a->H; p.W = a->W; p.Cin = a->Cin; p.Cout = a->Cout;
+  p.causal = a->causal; p.pad_mode = a->pad_mode; p.M = f.M; p.cpb = a->Cin / 64; p.RT = p.CT = 0;
+  p.ntaps = f.ntaps; p.kd0 = a->taps_d == 1 ? 1 : 0;
+  p.act_out = (bf16*)a->act_out; p.act_scale = (const bf16*)a->act_scale; p.act_shift = (const bf16*)a->act_shift;
+  p.act_eps = a->act_eps; p.act_silu = a->act_silu; p.rows_per_batch = a->D * a->H * a->W;
+  p.xcd_order = LTXK_AB_INT("LTXK_CONV_XCD", 1);
+  p.m_base = 0;
+  p.slab = nullptr; p.S = 1; p.kper = 0;
+  hipStream_t st = (hipStream_t)stream;
+  const bool res = a->resid != nullptr;
+  if (f.plan.kernel == LTXK_CONV_KERNEL_KW) return res ? conv_launch_kw_all<true>(p, f, st) : conv_launch_kw_all<false>(p, f, st);
+  if (f.plan.tile_rows == 256) return res ? conv_launch<4, 2, true>(p, f, st) : conv_launch<4, 2, false>(p, f, st);
+  return res ? conv_launch<5, 4, true>(p, f, st) : conv_launch<5, 4, false>(p, f, st);
 }

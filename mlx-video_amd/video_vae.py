@@ -88,6 +88,56 @@ def conv3d(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, causal: bool, pad_
     return out if act is None else (out, act_out)
 
 
+@dataclass(frozen=True)
+class Conv3dPlan:
+    """ltxk_conv3d_plan: the launch form of one ltxk_conv3d_k3_bf16 call (include/ltxk.h, struct ltxk_conv3d_plan)."""
+    kernel: int               # _lib.CONV_KERNEL_*
+    tile_rows: int
+    tile_cols: int
+    row_tiles: int            # of the main launch
+    col_tiles: int
+    slices: int               # 1 unless split-K
+    ksteps: int               # per slice
+    tail_tile_rows: int       # the tail launch (all 0: none)
+    tail_m_base: int
+    tail_row_tiles: int
+    fused_act: bool
+
+    @property
+    def kw(self) -> bool:
+        return self.kernel == _lib.CONV_KERNEL_KW
+
+    @property
+    def split_k(self) -> bool:
+        return self.slices >= 2
+
+    @property
+    def tail(self) -> bool:
+        return self.tail_row_tiles > 0
+
+
+def conv3d_plan(B: int, D: int, H: int, W: int, Cin: int, Cout: int, *, causal: int = 1, pad_mode: int = PAD_REFLECT,
+                taps_d: int = 3, resid: bool = False, act: bool = False, keep_out: bool = True,
+                workspace: Optional[Tuple[int, int]] = None) -> Conv3dPlan:
+    """The form ``conv3d`` takes for this volume, decided on the host by the function the launch itself uses (no device
+    needed).  The split-K scratch is offered as ``conv3d`` offers it (SPLITK_WORKSPACE_BYTES); ``workspace=(address,
+    bytes)`` offers that one instead (address 0: none).  Raises LtxkError where the launch would refuse the arguments."""
+    addr = ops._PLAN_ADDR
+    a = Conv3dArgs()
+    a.x = a.w = a.bias = a.zero_page = addr
+    a.out = addr if (keep_out or not act) else None
+    a.resid = addr if resid else None
+    a.B, a.D, a.H, a.W, a.Cin, a.Cout = B, D, H, W, Cin, Cout
+    a.causal, a.pad_mode, a.taps_d = int(causal), pad_mode, taps_d
+    a.workspace, a.workspace_bytes = (addr, SPLITK_WORKSPACE_BYTES) if workspace is None else workspace
+    if act:
+        a.act_out = addr
+    pl = _lib.Conv3dPlan()
+    check(_lib.load().ltxk_conv3d_plan(ctypes.byref(a), ctypes.byref(pl)), "ltxk_conv3d_plan")
+    return Conv3dPlan(pl.kernel, pl.tile_rows, pl.tile_cols, pl.row_tiles, pl.col_tiles, pl.slices, pl.ksteps,
+                      pl.tail_tile_rows, pl.tail_m_base, pl.tail_row_tiles, bool(pl.fused_act))
+
+
 def conv_act_fusable(Cout: int, voxels: int, force: bool = False) -> bool:
     """The conv epilogue can carry the following PixelNorm + SiLU when its tile holds whole rows (Cout 128 / 256) and the
     launch would not be split along K anyway (more than 128 tiles: the small 1024 / 512-channel volumes keep split-K).

@@ -292,3 +292,155 @@ def unpatchify(x, C: int, P: int) -> Tensor:
     ch = c[:, None, None] * P * P + (xo % P)[None, None, :] * P + (yo % P)[None, :, None]   # (C,Ho,Wo)
     g = x[:, :, (yo // P)[None, :, None], (xo // P)[None, None, :], ch]                  # (B,D,C,Ho,Wo)
     return g.permute(0, 2, 1, 3, 4).contiguous()
+
+
+# ------------------------------------------------------------------------------------- conv3d (implicit GEMM) + PixelNorm
+U24 = 2.0 ** -24                                      # fp32 unit roundoff
+
+
+def _ulp_dev(x: Tensor) -> Tensor:
+    """bf16 ulp of |x| (float64, on x's device), floored at the smallest normal - test_gemm_splitk_gpu.py's ``_ulp``."""
+    return torch.exp2(torch.floor(torch.log2(x.abs().clamp_min(2.0 ** -126))) - 7)
+
+
+def conv3d_halo(x: Tensor, causal: int, pad_mode: int, taps_d: int = 3) -> Tensor:
+    """The halo of ltxk_conv3d_k3_bf16 (include/ltxk.h; convolution.py:120-157) materialised: x (B,D,H,W,C) ->
+    (B,D+2,H+2,W+2,C), or (B,D,H+2,W+2,C) for the per-frame kernel (taps_d = 1: no temporal halo).
+    Temporal: causal = 1 the first frame twice in front; 0 the first frame in front and the last behind; 2 zeros.
+    Spatial: pad_mode 0 zeros; 1 reflect without the edge sample (row 1 in front, row H-2 behind)."""
+    if taps_d == 3:
+        first, last = x[:, :1], x[:, -1:]
+        if causal == 1:
+            x = torch.cat([first, first, x], 1)
+        elif causal == 0:
+            x = torch.cat([first, x, last], 1)
+        else:
+            z = torch.zeros_like(first)
+            x = torch.cat([z, x, z], 1)
+    if pad_mode == 1:
+        x = torch.cat([x[:, :, 1:2], x, x[:, :, -2:-1]], 2)
+        x = torch.cat([x[:, :, :, 1:2], x, x[:, :, :, -2:-1]], 3)
+    else:
+        zh = torch.zeros_like(x[:, :, :1])
+        x = torch.cat([zh, x, zh], 2)
+        zw = torch.zeros_like(x[:, :, :, :1])
+        x = torch.cat([zw, x, zw], 3)
+    return x
+
+
+def conv3d(x: Tensor, w: Tensor, bias: Tensor, causal: int, pad_mode: int, taps_d: int = 3, resid: Optional[Tensor] = None):
+    """ltxk_conv3d_k3_bf16 in float64, on the device its inputs live on: x (B,D,H,W,Cin) channels-last bf16, w
+    (Cout,3,3,3,Cin) - or (Cout,3,3,Cin) with taps_d = 1 -, bias (Cout), resid (B,D,H,W,Cout) or None.
+    Returns (y, mag), both (B,D,H,W,Cout) float64: y = sum x*w + bias (+ resid), exact up to float64 roundoff (products
+    of bf16 values are exact, the sums carry ~2^-53), mag = sum |x*w| over the same taps.  Nothing is rounded to bf16.
+    The halo is built explicitly (conv3d_halo) and every tap is one matmul of a shifted slice: no library convolution."""
+    B, D, H, W, Cin = x.shape
+    Cout = w.shape[0]
+    xp = conv3d_halo(x.to(F64), int(causal), int(pad_mode), taps_d)
+    w64 = w.to(F64).reshape(Cout, 3 if taps_d == 3 else 1, 3, 3, Cin)
+    y = torch.zeros((B * D * H * W, Cout), dtype=F64, device=x.device)
+    mag = torch.zeros_like(y)
+    for kd in range(w64.shape[1]):
+        for kh in range(3):
+            for kw in range(3):
+                s = xp[:, kd:kd + D, kh:kh + H, kw:kw + W].reshape(-1, Cin)
+                wt = w64[:, kd, kh, kw].t()
+                y += s @ wt
+                mag += s.abs() @ wt.abs()
+    y = (y + bias.to(F64)).reshape(B, D, H, W, Cout)
+    if resid is not None:
+        y = y + resid.to(F64)
+    return y, mag.reshape(B, D, H, W, Cout)
+
+
+def conv3d_bound(out: Tensor, y: Tensor, mag: Tensor, K: int, resid: Optional[Tensor] = None):
+    """(d, bound), element-wise on the inputs' device: the distance of a kernel's bf16 output from ``conv3d``'s y and
+    the most a correct implicit GEMM with fp32 accumulation can be away (test_gemm_splitk_gpu.py's rule, K = taps*Cin):
+      |out - y| <= 1/2 ulp_bf16(out) + K 2^-24 mag + 2^-24 (|y| + K 2^-24 mag)
+    - one bf16 rounding, the fp32 accumulation in ANY order (tap order, the kw kernel's order, K slices and their fp32
+    or float64 sum), the fp32 bias add.  With a residual (y includes it) the output is bf16(bf16(conv + bias) + resid),
+    two roundings and one fp32 add: that file's epi == 4 form."""
+    o = out.to(F64)
+    acc = K * U24 * mag
+    if resid is None:
+        return (o - y).abs(), 0.5 * _ulp_dev(o) + acc + U24 * (y.abs() + acc)
+    r = resid.to(F64)
+    c = y - r
+    ec = acc + U24 * (c.abs() + acc)
+    e1 = 0.5 * _ulp_dev(c.abs() + ec) + ec
+    return (o - y).abs(), 0.5 * _ulp_dev(o) + U24 * (r.abs() + c.abs() + e1) + e1
+
+
+def near_bf16_midpoint(v: Tensor, rel: float = 2.0 ** -18) -> Tensor:
+    """True where the float64 value v lies within rel*|v| of the midpoint of two neighbouring bf16 values: a rounding
+    that a computation carrying a relative error up to rel may take the other way."""
+    v = f64(v)
+    q = ulp_bf16(v)
+    mid = (torch.floor(v / q) + 0.5) * q
+    return (v - mid).abs() <= rel * v.abs()
+
+
+def pixelnorm_act(x, eps: float, scale=None, shift=None, rows_per_batch: int = 0, silu_on: bool = False):
+    """ltxk_pixelnorm_act, the rounding chain of vae_ops.hip's header (oracle/vae.py::pixel_norm, _mod, silu):
+    q = bf16(x^2), m = bf16(mean_c q), e = bf16(m + eps), s = bf16(sqrt e), y = bf16(x / s); then
+    bf16(bf16(y * bf16(1 + scale)) + shift) with row v using scale/shift row v // rows_per_batch; then bf16(silu).
+    x (V,C); scale/shift (B,C) or None.  Returns (out, mag, exempt): mag the terms of the modulation's add (None
+    without it), exempt (V) bool - the rows whose mean q, m + eps or sqrt(e) lies within relative 2^-18 of a bf16
+    rounding midpoint, where an fp32 kernel may round the row statistic the other way and move the whole row."""
+    x = f64(x)
+    V, C = x.shape
+    mq = rbf(x * x).mean(-1, keepdim=True)
+    m = rbf(mq)
+    me = m + eps
+    e = rbf(me)
+    rt = torch.sqrt(e)
+    s = rbf(rt)
+    exempt = (near_bf16_midpoint(mq) | near_bf16_midpoint(me) | near_bf16_midpoint(rt)).reshape(V)
+    y = rbf(x / s)
+    mag = None
+    if scale is not None:
+        b = torch.arange(V) // rows_per_batch
+        one_p = rbf(1.0 + f64(scale))[b]
+        sh = f64(shift)[b]
+        mag = (y * one_p).abs() + sh.abs()
+        y = rbf(rbf(y * one_p) + sh)
+    if silu_on:
+        y = silu(y)
+    return y, mag, exempt
+
+
+def pixelnorm_rows(C: int) -> int:
+    """V of the ltxk_pixelnorm_act edge case for C channels: 2*R*k + 1 >= 257 rows, R = 4 * (64/LPR) rows per workgroup
+    (LPR = min(C/8, 64) lanes per row): whole workgroups plus a lone row in the last one."""
+    R = 4 * (64 // min(C // 8, 64))
+    k = -(-256 // (2 * R))
+    return 2 * R * k + 1
+
+
+PIXELNORM_RPB = 129           # rows of batch 0: a multiple of no rows-per-wave (8, 4, 2), so one wave holds both batches
+PIXELNORM_SEED = 1            # chosen on the reference alone: no row of any C is exempt with it (0 exempts one row at C = 1024, 2048)
+
+
+def pixelnorm_inputs(C: int):
+    """The inputs test_vae_glue_gpu.py feeds ltxk_pixelnorm_act at C channels (test_ref64_cpu.py asserts that at most 1 %
+    of their rows are exempt): x (V,C) randn*3 with row 5 all zero (eps alone under the root) and row 7 constant, two
+    batches' scale and shift (2,C)."""
+    g = torch.Generator().manual_seed(PIXELNORM_SEED * 7919 + C)
+    V = pixelnorm_rows(C)
+    x = torch.randn(V, C, generator=g) * 3
+    x[5] = 0.0
+    x[7] = 1.5
+    scale = 0.5 * torch.randn(2, C, generator=g)
+    shift = torch.randn(2, C, generator=g)
+    return x.to(BF), scale.to(BF), shift.to(BF)
+
+
+def assert_rows_close(got, ref, exempt, *, max_ulps: float, max_frac: float, mag=None, what: str = "") -> Tuple[float, float]:
+    """assert_bf16_close for (V,C) rows of which some are ``exempt`` (pixelnorm_act): every row counts towards max_ulps,
+    only the others towards max_frac.  Returns (max ulps over all rows, fraction off among the non-exempt rows)."""
+    ulps, _ = bf16_stats(got, ref, mag)
+    keep = ~exempt
+    _, frac = bf16_stats(f64(got)[keep], f64(ref)[keep], None if mag is None else f64(mag)[keep])
+    assert ulps <= max_ulps, f"{what}: an element is {ulps:.3g} bf16 ulps off (allowed {max_ulps})"
+    assert frac <= max_frac, f"{what}: {frac:.3e} of the elements of non-exempt rows differ (allowed {max_frac:.3e})"
+    return ulps, frac

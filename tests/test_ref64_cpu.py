@@ -238,3 +238,153 @@ def test_latent_norm_denorm_and_tile_blend_restate_the_formulas():
     one = torch.ones(4)
     out = R.tile_blend([(tile, (2, 3, 4), one, one, one, (0, 0, 0))], 2, 3, 4)
     assert torch.equal(out, tile.double())
+
+
+# ---------------------------------------------------------------------------------------------------- conv3d, PixelNorm
+HALO_MODES = [(c, p, t) for c in (0, 1, 2) for p in (0, 1) for t in (3, 1)]
+
+
+def _conv_data(B, D, H, W, Cin, Cout, taps_d, seed):
+    g = _g(seed)
+    nt = 27 if taps_d == 3 else 9
+    x = torch.randn(B, D, H, W, Cin, generator=g).to(BF)
+    w = (torch.randn((Cout, 3, 3, 3, Cin) if taps_d == 3 else (Cout, 3, 3, Cin), generator=g) * (nt * Cin) ** -0.5).to(BF)
+    b = (0.1 * torch.randn(Cout, generator=g)).to(BF)
+    return x, w, b
+
+
+def _torch_conv_f32(x, w, b, causal, pad_mode, taps_d):
+    """float32 torch convolution of the same bf16 data, halo by torch's own padding ops: (B,D,H,W,Cout) float32."""
+    import torch.nn.functional as F
+    xc = x.float().permute(0, 4, 1, 2, 3)                                  # (B,C,D,H,W)
+    if taps_d == 3:
+        if causal == 2:
+            xc = F.pad(xc, (0, 0, 0, 0, 1, 1))
+        else:
+            xc = F.pad(xc, (0, 0, 0, 0, 2, 0) if causal == 1 else (0, 0, 0, 0, 1, 1), mode="replicate")
+    xc = F.pad(xc, (1, 1, 1, 1, 0, 0), mode="reflect") if pad_mode == 1 else F.pad(xc, (1, 1, 1, 1))
+    wt = w.float().reshape(w.shape[0], 3 if taps_d == 3 else 1, 3, 3, w.shape[-1]).permute(0, 4, 1, 2, 3).contiguous()
+    return F.conv3d(xc, wt, b.float()).permute(0, 2, 3, 4, 1).contiguous()
+
+
+@pytest.mark.parametrize("causal,reflect", [(1, True), (1, False), (0, True), (0, False)])
+def test_conv3d_ref_matches_oracle_causal_conv(causal, reflect):
+    x, w, b = _conv_data(2, 3, 4, 5, 64, 16, 3, 20 + causal * 2 + reflect)
+    y, mag = R.conv3d(x, w, b, causal, int(reflect))
+    want = OV.causal_conv3d(x.permute(0, 4, 1, 2, 3).float(), w, b, P, bool(causal), reflect).permute(0, 2, 3, 4, 1)
+    R.assert_bf16_close(want, R.rbf(y), max_ulps=1, max_frac=2e-2, what="causal_conv3d")     # fp32 sum, rounded once
+    assert bool((mag >= y.sub(b.double()).abs() - 1e-12).all())
+
+
+def test_conv3d_ref_matches_oracle_zero_conv_and_residual():
+    x, w, b = _conv_data(2, 3, 4, 5, 64, 16, 3, 30)
+    y, _ = R.conv3d(x, w, b, 2, 0)
+    want = OV.conv3d_zero(x.permute(0, 4, 1, 2, 3).float(), w, b, P).permute(0, 2, 3, 4, 1)
+    R.assert_bf16_close(want, R.rbf(y), max_ulps=1, max_frac=2e-2, what="conv3d_zero")
+    r = torch.randn(2, 3, 4, 5, 16, generator=_g(31)).to(BF)
+    yr, _ = R.conv3d(x, w, b, 2, 0, resid=r)
+    assert torch.equal(yr, y + r.double())
+    # the per-frame kernel is the centre temporal tap of a 3x3x3 kernel whose other temporal taps are zero
+    w1 = w[:, 1].contiguous()
+    w3 = torch.zeros_like(w)
+    w3[:, 1] = w1
+    y1, m1 = R.conv3d(x, w1, b, 0, 1, taps_d=1)
+    y3, m3 = R.conv3d(x, w3, b, 0, 1)
+    assert torch.equal(y1, y3) and torch.equal(m1, m3)
+    for causal in (1, 2):                                   # per frame: no temporal halo mode reaches it
+        assert torch.equal(R.conv3d(x, w1, b, causal, 1, taps_d=1)[0], y1)
+
+
+def test_conv3d_halo_small_extents():
+    """D = 1 with causal = 0: both temporal halos are the one frame; H = W = 2 with reflect: the reflected sample is the
+    opposite edge."""
+    x = torch.arange(2 * 2 * 3, dtype=torch.float64).reshape(1, 1, 2, 2, 3)
+    h = R.conv3d_halo(x, 0, 1)
+    assert h.shape == (1, 3, 4, 4, 3)
+    assert torch.equal(h[:, 0], h[:, 1]) and torch.equal(h[:, 2], h[:, 1])
+    assert torch.equal(h[0, 1, 0, 1:3], x[0, 0, 1]) and torch.equal(h[0, 1, 3, 1:3], x[0, 0, 0])
+    assert torch.equal(h[0, 1, 1:3, 0], x[0, 0, :, 1]) and torch.equal(h[0, 1, 1:3, 3], x[0, 0, :, 0])
+    assert not R.conv3d_halo(x, 2, 0)[:, 0].any() and R.conv3d_halo(x, 1, 0, taps_d=1).shape == (1, 1, 4, 4, 3)
+
+
+@pytest.mark.parametrize("causal,pad_mode,taps_d", HALO_MODES)
+def test_conv3d_bound_accepts_a_float32_convolution(causal, pad_mode, taps_d):
+    """bf16(float32 torch conv) of the same bf16 data lies inside the element-wise bound in every halo mode, with and
+    without a residual: the bound is not too tight for a correct fp32-accumulating implementation."""
+    Cin, Cout = 64, 24
+    x, w, b = _conv_data(2, 3, 7, 9, Cin, Cout, taps_d, 40 + causal * 4 + pad_mode * 2 + taps_d)
+    K = (27 if taps_d == 3 else 9) * Cin
+    c32 = _torch_conv_f32(x, w, b, causal, pad_mode, taps_d)
+    y, mag = R.conv3d(x, w, b, causal, pad_mode, taps_d)
+    d, bound = R.conv3d_bound(c32.to(BF), y, mag, K)
+    assert bool((d <= bound).all()), float((d / bound).max())
+    assert float((d / bound).max()) > 0.5                    # and it is no loose bound: some element uses half of it
+    r = torch.randn(2, 3, 7, 9, Cout, generator=_g(41)).to(BF)
+    yr, _ = R.conv3d(x, w, b, causal, pad_mode, taps_d, resid=r)
+    d, bound = R.conv3d_bound((c32.to(BF).float() + r.float()).to(BF), yr, mag, K, resid=r)
+    assert bool((d <= bound).all()), float((d / bound).max())
+
+
+@pytest.mark.parametrize("causal", [0, 1])
+def test_conv3d_bound_rejects_one_wrong_halo_tap(causal):
+    """The same float32 output fails the bound when (a) one corner voxel is recomputed with one zero tap where the mode
+    says reflect, (b) the voxels of one frame take their temporal halo from the wrong end - and only those voxels fail."""
+    Cin, Cout = 64, 24
+    B, D, H, W = 2, 3, 7, 9
+    x, w, b = _conv_data(B, D, H, W, Cin, Cout, 3, 50 + causal)
+    K = 27 * Cin
+    y, mag = R.conv3d(x, w, b, causal, 1)
+    good = _torch_conv_f32(x, w, b, causal, 1, 3)
+    # (a) voxel (b=1, d=1, h=0, w=0): the tap (kd, kh, kw) = (1, 0, 0) reads reflect sample x[1, 1, 1, 1]; drop it
+    bad = good.clone()
+    bad[1, 1, 0, 0] -= x[1, 1, 1, 1].float() @ w[:, 1, 0, 0].float().t()
+    d, bound = R.conv3d_bound(bad.to(BF), y, mag, K)
+    over = (d > bound).any(-1)
+    assert bool(over[1, 1, 0, 0]) and int(over.sum()) == 1
+    # (b) frame 0 convolved with the halo frames swapped end for end: [last, x, first]
+    xs = torch.cat([x[:, -1:], x, x[:, :1]], 1)
+    ys, _ = R.conv3d(xs, w, b, 2, 1)                          # zeros in time never reach frames 1 .. D of xs
+    bad = good.clone()
+    bad[:, 0] = ys[:, 1].float()
+    d, bound = R.conv3d_bound(bad.to(BF), y, mag, K)
+    over = (d > bound).any(-1)
+    assert bool(over[:, 0].all()) and not bool(over[:, 1:].any())
+
+
+@pytest.mark.parametrize("mod", [False, True], ids=["nomod", "mod"])
+@pytest.mark.parametrize("silu_on", [False, True], ids=["nosilu", "silu"])
+def test_pixelnorm_act_matches_oracle(mod, silu_on):
+    g = _g(60 + 2 * mod + silu_on)
+    B, C, V = 2, 128, 30
+    x = (torch.randn(B * V, C, generator=g) * 3).to(BF)
+    x[3] = 0.0
+    sc, sh = (0.5 * torch.randn(B, C, generator=g)).to(BF), torch.randn(B, C, generator=g).to(BF)
+    for eps in (1e-8, 1e-6):
+        xc = x.float().reshape(B, V, C).permute(0, 2, 1).reshape(B, C, V, 1, 1)
+        want = OV.pixel_norm(xc, P, eps)
+        if mod:
+            want = OV._mod(want, sc.float().reshape(B, C, 1, 1, 1), sh.float().reshape(B, C, 1, 1, 1), P)
+        if silu_on:
+            want = O.silu(want, P)
+        want = want.reshape(B, C, V).permute(0, 2, 1).reshape(B * V, C)
+        ref, mag, exempt = R.pixelnorm_act(x, R.f32(eps), sc if mod else None, sh if mod else None, V, silu_on)
+        assert not bool(exempt.any())
+        R.assert_bf16_close(want, ref, max_ulps=2 if mod else 1, max_frac=1e-2, mag=mag, what="pixelnorm_act")
+        assert not bool(ref[3].any()) or mod
+
+
+@pytest.mark.parametrize("C", [64, 128, 256, 512, 1024, 2048])
+def test_pixelnorm_gpu_inputs_have_few_exempt_rows(C):
+    """The condition the GPU test's max_frac rests on, for the exact inputs it uses: rows whose statistic sits on a bf16
+    rounding boundary (they may flip as a whole row) are at most 1 % of the rows, in every variant."""
+    x, sc, sh = R.pixelnorm_inputs(C)
+    V = R.pixelnorm_rows(C)
+    assert x.shape == (V, C) and V >= 257 and V % 2 == 1
+    rows_per_wg = 4 * (64 // min(C // 8, 64))
+    assert (V - 1) % (2 * rows_per_wg) == 0 and R.PIXELNORM_RPB % 8 != 0 and R.PIXELNORM_RPB % 2 != 0 and R.PIXELNORM_RPB < V
+    assert not bool(x[5].any()) and bool((x[7] == x[7, 0]).all()) and float(x[7, 0]) != 0.0
+    _, _, exempt = R.pixelnorm_act(x, R.f32(1e-8), sc, sh, R.PIXELNORM_RPB, True)
+    assert int(exempt.sum()) <= V // 100, int(exempt.sum())
+    # the detector itself: a value a relative 2^-20 above a midpoint is near it, 2^-16 is not
+    mid = torch.tensor([1.0 + 2.0 ** -8, 3.0 + 2.0 ** -7, 2.0 ** -20 * (1.5 + 2.0 ** -8)], dtype=torch.float64)
+    assert bool(R.near_bf16_midpoint(mid * (1 + 2.0 ** -20)).all()) and not bool(R.near_bf16_midpoint(mid * (1 + 2.0 ** -16)).any())

@@ -25,6 +25,45 @@ def _st():
     return torch.cuda.current_stream().cuda_stream
 
 
+# ------------------------------------------------------------------------------------------- PixelNorm (+mod, +SiLU)
+@pytest.mark.parametrize("silu", [False, True], ids=["nosilu", "silu"])
+@pytest.mark.parametrize("mod", [False, True], ids=["nomod", "mod"])
+@pytest.mark.parametrize("C", [64, 128, 256, 512, 1024, 2048])
+def test_pixelnorm_act_edges(dev, C, mod, silu):
+    """ltxk_pixelnorm_act, LPR = min(C/8, 64) lanes per row and R = 4 * 64/LPR rows per workgroup, at V = 2*R*k + 1 = 257
+    rows: whole workgroups plus a lone row in the last one (its idle lanes and waves must not store: sentinel rows follow).
+    Two batches of 129 and 128 rows with another modulation row each; 129 is no multiple of the 8, 4 or 2 rows a wave
+    holds, so one wave has rows of both.  Row 5 is all zero (eps alone under the root), row 7 constant.  Catches: the
+    second pass of C = 1024 / 2048 dropped or doubled in the mean, a row statistic reduced over a neighbour's lanes, the
+    batch taken per wave instead of per row, 1 + scale not rounded, and stores past V*C.
+    max_ulps 1 without modulation, 2 with it (an earlier rounding point may flip and carry), max_frac 1e-2: the rule of
+    test_rowops_gpu.py.  A row whose statistic sits within 2^-18 of a bf16 rounding boundary may flip as a whole: those
+    rows (ref64.pixelnorm_act names them) count towards max_ulps only, and test_ref64_cpu.py asserts on these very inputs
+    that they are at most 1 % of the rows."""
+    L = _lib()
+    x, sc, sh = R.pixelnorm_inputs(C)
+    V = R.pixelnorm_rows(C)
+    eps = 1e-8
+    n = V * C
+    out = _sent_bf16((n + 4 * C,), dev)
+    xd, scd, shd = x.to(dev), sc.to(dev), sh.to(dev)
+    L.check(L.load().ltxk_pixelnorm_act(xd.data_ptr(), out.data_ptr(), V, C, eps, scd.data_ptr() if mod else None,
+                                        shd.data_ptr() if mod else None, R.PIXELNORM_RPB, int(silu), _st()), "ltxk_pixelnorm_act")
+    torch.cuda.synchronize()
+    assert _untouched(out[n:])
+    ref, mag, exempt = R.pixelnorm_act(x, R.f32(eps), sc if mod else None, sh if mod else None, R.PIXELNORM_RPB, silu)
+    assert int(exempt.sum()) <= V // 100
+    got = out[:n].view(V, C).cpu()
+    if not mod:
+        assert not bool(got[5].float().any()), "the all-zero row"
+    max_ulps = 2 if mod else 1
+    ulps, _ = R.bf16_stats(got, ref, mag)
+    _, frac = R.bf16_stats(got[~exempt], ref[~exempt], None if mag is None else mag[~exempt])
+    parity.auto(ulps, max_ulps, tag="ulps")
+    parity.auto(frac, 1e-2, tag="frac")
+    R.assert_rows_close(got, ref, exempt, max_ulps=max_ulps, max_frac=1e-2, mag=mag, what=f"pixelnorm C={C}")
+
+
 # ------------------------------------------------------------------------------------------- GroupNorm (+res, +SiLU)
 @pytest.mark.parametrize("silu", [False, True], ids=["nosilu", "silu"])
 @pytest.mark.parametrize("resid", [False, True], ids=["nores", "res"])
