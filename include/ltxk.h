@@ -15,7 +15,10 @@
  *     side tables fp32, indices int32;
  *   - token tensors are row-major (tokens, dim); volumes are channels-last (B,D,H,W,C);
  *   - every call is asynchronous on `stream` (a hipStream_t passed as void*; NULL = the
- *     default stream), re-entrant across streams, and keeps no global mutable state;
+ *     default stream) and re-entrant across streams and threads;
+ *   - no state influences a result or a launch form: both are functions of the arguments and of
+ *     the current device alone.  The only process-wide state is one idempotent bit per (kernel,
+ *     device), "the dynamic-LDS attribute of this kernel is set", and the thread-local error string;
  *   - returns 0 on success, a negative LTXK_E* code on error; ltxk_last_error() returns a
  *     thread-local message.  Nothing throws across the ABI.
  */
@@ -29,7 +32,7 @@
 extern "C" {
 #endif
 
-#define LTXK_VERSION 406
+#define LTXK_VERSION 407
 
 #define LTXK_OK 0
 #define LTXK_EINVAL (-1)   /* bad argument (shape / alignment / null pointer) */
@@ -221,6 +224,28 @@ typedef struct ltxk_attn_args {
 } ltxk_attn_args;
 
 int ltxk_flash_attn(const ltxk_attn_args* args, void* stream);
+
+/* The launch form ltxk_flash_attn takes for `args` on a device of `cus` compute units, decided without launching anything
+ * (host only: pointers are checked for NULL / alignment, never read; cus <= 0 is LTXK_EINVAL).  ltxk_flash_attn decides its form
+ * by the same host function with the current device's CU count, so a plan and a launch of the same arguments cannot disagree;
+ * the same argument checks run and return the same error codes.
+ * KERNEL_128: 128-row query tiles; split_tiles of them (those of the short last round of 2 * cus workgroups) halve their keys
+ * over two workgroups each - the one form whose rows sum their keys in another order.  KERNEL_MIX: per (batch, head) tiles_192
+ * tiles of 192 rows followed by tiles_128 of 128 rows, never split.                                                        */
+enum { LTXK_ATTN_KERNEL_128 = 0, LTXK_ATTN_KERNEL_MIX = 1 };
+struct ltxk_flash_attn_plan {   /* a struct tag only: the name is also the function's */
+  int32_t kernel;          /* LTXK_ATTN_KERNEL_*                                              */
+  int32_t mfma_k;          /* 16; 32 only in the A/B build with LTXK_FA_MFMA=32               */
+  int32_t tiles_192;       /* per (batch, head): 192-row tiles (0 for KERNEL_128)             */
+  int32_t tiles_128;       /* per (batch, head): 128-row tiles                                */
+  int32_t whole_workgroups;/* workgroups that run a whole tile                                */
+  int32_t split_tiles;     /* tiles whose keys are halved over two workgroups (0 for MIX)     */
+  int32_t workgroups;      /* grid size = whole_workgroups + 2 * split_tiles                  */
+  int32_t xcd_order;       /* 1: the XCD-aware tile order                                     */
+};
+int ltxk_flash_attn_plan(const ltxk_attn_args* args, int32_t cus, struct ltxk_flash_attn_plan* plan);
+/* sizeof(struct ltxk_flash_attn_plan) in this build (an entry of its own: the ltxk_abi_sizeof index list is closed).     */
+int ltxk_flash_attn_plan_sizeof(void);
 
 /* The same without query preparation (positional form kept for existing bindings).       */
 int ltxk_flash_attn_bf16(const void* q, int32_t ldq, const void* k, int32_t ldk,

@@ -59,6 +59,13 @@ class AttnArgs(Structure):
     ]
 
 
+class AttnPlan(Structure):
+    _fields_ = [
+        ("kernel", c_int32), ("mfma_k", c_int32), ("tiles_192", c_int32), ("tiles_128", c_int32),
+        ("whole_workgroups", c_int32), ("split_tiles", c_int32), ("workgroups", c_int32), ("xcd_order", c_int32),
+    ]
+
+
 class Conv3dArgs(Structure):
     _fields_ = [
         ("x", c_void_p), ("w", c_void_p), ("bias", c_void_p), ("out", c_void_p),
@@ -106,6 +113,8 @@ SIGNATURES = {
     "ltxk_qknorm_grouped_ss": (c_int32, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_float,
                                          c_void_p, c_int64, c_int32, c_void_p]),
     "ltxk_flash_attn": (c_int32, [POINTER(AttnArgs), c_void_p]),
+    "ltxk_flash_attn_plan": (c_int32, [POINTER(AttnArgs), c_int32, POINTER(AttnPlan)]),
+    "ltxk_flash_attn_plan_sizeof": (c_int32, []),
     "ltxk_flash_attn_bf16": (c_int32, [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32,
                                        c_int32, c_int32, c_int32, c_int32, c_float, c_void_p]),
     "ltxk_rmsnorm_modulate": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_float, c_void_p, c_void_p, c_int32,
@@ -165,6 +174,7 @@ AB_LIB_PATH = os.path.join(_HERE, "libltxk_ab.so")
 ATTN_NO_TAIL_SPLIT = 1        # ltxk.h: LTXK_ATTN_NO_TAIL_SPLIT
 GEMM_FORM_SINGLE, GEMM_FORM_BIG, GEMM_FORM_SPLITK = 0, 1, 2     # ltxk.h: LTXK_GEMM_FORM_*
 CONV_KERNEL_PER_TAP, CONV_KERNEL_KW = 0, 1                      # ltxk.h: LTXK_CONV_KERNEL_*
+ATTN_KERNEL_128, ATTN_KERNEL_MIX = 0, 1                         # ltxk.h: LTXK_ATTN_KERNEL_*
 
 
 def _open(path: str) -> ctypes.CDLL:
@@ -183,12 +193,11 @@ def _open(path: str) -> ctypes.CDLL:
             raise LtxkError(f"{path} is stale: sizeof({st.__name__}) is {lib.ltxk_abi_sizeof(which)} in the library, "
                             f"{ctypes.sizeof(st)} in this binding; rebuild it (make -C mlx-video_amd/csrc)")
     # (structs added after the ltxk_abi_sizeof index list was closed report their size through an entry of their own)
-    if lib.ltxk_gemm_grouped_args_sizeof() != ctypes.sizeof(GemmGroupedArgs):
-        raise LtxkError(f"{path} is stale: sizeof(GemmGroupedArgs) is {lib.ltxk_gemm_grouped_args_sizeof()} in the library, "
-                        f"{ctypes.sizeof(GemmGroupedArgs)} in this binding; rebuild it (make -C mlx-video_amd/csrc)")
-    if lib.ltxk_conv3d_plan_sizeof() != ctypes.sizeof(Conv3dPlan):
-        raise LtxkError(f"{path} is stale: sizeof(Conv3dPlan) is {lib.ltxk_conv3d_plan_sizeof()} in the library, "
-                        f"{ctypes.sizeof(Conv3dPlan)} in this binding; rebuild it (make -C mlx-video_amd/csrc)")
+    for fn, st in ((lib.ltxk_gemm_grouped_args_sizeof, GemmGroupedArgs), (lib.ltxk_conv3d_plan_sizeof, Conv3dPlan),
+                   (lib.ltxk_flash_attn_plan_sizeof, AttnPlan)):
+        if fn() != ctypes.sizeof(st):
+            raise LtxkError(f"{path} is stale: sizeof({st.__name__}) is {fn()} in the library, "
+                            f"{ctypes.sizeof(st)} in this binding; rebuild it (make -C mlx-video_amd/csrc)")
     return lib
 
 

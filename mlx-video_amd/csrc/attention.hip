@@ -824,51 +824,62 @@ __global__ __launch_bounds__(256, 2) void flash_attn16_mix_kernel(FaParams p) {
 }
 
 // (qta, qtb) for Tq rows per (batch, head): qtb in 0..6 tiles of 128 rows, the rest in 192-row tiles, minimising the busiest CU's
-// load in a model of the launch - workgroups dealt in grid order to the least-loaded of `cus` CUs, a CU's time = the summed cost
-// of its workgroups (two co-resident workgroups share its matrix pipe), cost = rows (x 0.875 for the 192-row form, measured) +
-// a fixed part (prologue, Q staging, output tail ~ 2 key tiles' worth).  Returns the model's makespan.
+// load in a model of the launch - 192-row workgroups dealt round-robin over `cus` CUs (at most 1024 of them), 128-row workgroups
+// each to the least-loaded CU, a CU's time = the summed cost of its workgroups (two co-resident workgroups share its matrix
+// pipe), cost = rows (x 0.875 for the 192-row form, measured) + a fixed part (prologue, Q staging, output tail ~ 2 key tiles'
+// worth).  The first strict minimum wins.  Returns the model's makespan.
+// All 128-row workgroups cost the same, so whichever of several equally loaded CUs takes the next one, the loads evolve as the
+// same multiset: after the round-robin deal it has at most two levels (`lo` below `hi`), and every CU on the lower level
+// advances together - a step per level instead of a scan of the CUs per workgroup.
 static long fa_pick_mix(int Tq, int Tk, int BH, int cus, int& qta, int& qtb) {
   long best = -1;
   if (cus > 1024) cus = 1024;
   const long fixed = 8L * 128 * 128 / (Tk < 128 ? 128 : Tk);    // in rows x 8: the fixed part of a workgroup ~ 128 keys' worth of a 128-row tile
   const long ca = 192 * 7 + fixed, cb = 128 * 8 + fixed;        // 0.875 per row of a 192-row tile
+  struct Level { long load, n; };
   for (int nb = 0; nb <= 6; ++nb) {
     const int rest = Tq - 128 * nb;
     if (rest <= -128) break;                                     // more 128-row tiles than rows
     const int na = rest > 0 ? (rest + 191) / 192 : 0;
-    long load[1024];
-    const long wa = (long)na * BH, wb = (long)nb * BH;
-    for (int c = 0; c < cus; ++c) load[c] = (wa / cus + (c < wa % cus ? 1 : 0)) * ca;      // 192-row workgroups, round-robin
-    for (long i = 0; i < wb; ++i) {                              // 128-row workgroups onto the least-loaded CU
-      int m = 0;
-      for (int c = 1; c < cus; ++c)
-        if (load[c] < load[m]) m = c;
-      load[m] += cb;
+    const long wa = (long)na * BH;
+    long left = (long)nb * BH;                                   // 128-row workgroups still to place
+    Level lo = {wa / cus * ca, cus - wa % cus}, hi = {lo.load + ca, wa % cus};      // hi.n == 0: one level only
+    while (left >= lo.n) {                                       // (lo.n >= 1: the deal leaves at least one CU on the lower level)
+      left -= lo.n;
+      lo.load += cb;
+      if (hi.n && lo.load == hi.load) { lo.n += hi.n; hi.n = 0; }
+      else if (hi.n && lo.load > hi.load) { const Level t = lo; lo = hi; hi = t; }
     }
-    long span = 0;
-    for (int c = 0; c < cus; ++c) span = load[c] > span ? load[c] : span;
+    const long low_top = lo.load + (left > 0 ? cb : 0);          // `left` CUs of the lower level take one more
+    const long span = hi.n && hi.load > low_top ? hi.load : low_top;
     if (best < 0 || span < best) { best = span; qta = na; qtb = nb; }
   }
   return best;
 }
 
-}  // namespace ltxk
+// The launch form of one ltxk_flash_attn call on a device of `cus` CUs: the argument checks, then kernel / tiles / tail split.
+// ltxk_flash_attn launches what this decides and ltxk_flash_attn_plan reports it, so the two cannot drift apart.  It reads
+// nothing but its arguments (and, in the A/B build, the LTXK_FA_* switches).
+struct FaForm {
+  int mfma;          // 16: fa_body16 kernels; 32: flash_attn_kernel (A/B build only)
+  bool mix;          // flash_attn16_mix_kernel; else the 128-row kernel of `mfma`
+  int QT;            // 128-row tiles per (batch, head)
+  int xcd;           // FaParams::xcd
+  int n_full, rem;   // workgroups that run a whole tile / tiles split over two tail workgroups each (mix: rem == 0)
+  int qta, qtb;      // mix: 192-row and 128-row tiles per (batch, head)
+};
 
-extern "C" int ltxk_flash_attn(const ltxk_attn_args* a, void* stream) {
-  using namespace ltxk;
+static int fa_form(const ltxk_attn_args* a, int cus, FaForm& f) {
   LTXK_CHECK_ARG(a != nullptr, "ltxk_flash_attn: null args");
-  const void *q = a->q, *k = a->k, *vt = a->vt;
-  void* out = a->out;
   const int32_t ldq = a->ldq, ldk = a->ldk, ldvt = a->ldvt, ldo = a->ldo, B = a->B, H = a->H, Tq = a->Tq, Tk = a->Tk;
-  const float scale = a->scale;
-  LTXK_CHECK_ARG(q && k && vt && out, "ltxk_flash_attn_bf16: null pointer");
+  LTXK_CHECK_ARG(a->q && a->k && a->vt && a->out, "ltxk_flash_attn_bf16: null pointer");
   LTXK_CHECK_ARG(B > 0 && H > 0 && Tq > 0 && Tk > 0, "ltxk_flash_attn_bf16: bad dims");
-  LTXK_CHECK_ARG(scale > 0.f, "ltxk_flash_attn_bf16: scale must be positive");
+  LTXK_CHECK_ARG(a->scale > 0.f, "ltxk_flash_attn_bf16: scale must be positive");
   LTXK_CHECK_ARG(ldq >= H * FA_DH && ldk >= H * FA_DH && ldo >= H * FA_DH, "ltxk_flash_attn_bf16: row strides < H*128");
   LTXK_CHECK_ARG(ldq % 8 == 0 && ldk % 8 == 0 && ldo % 8 == 0, "ltxk_flash_attn_bf16: row strides must be multiples of 8");
   const int tk_pad = (Tk + FA_BK - 1) / FA_BK * FA_BK;
   LTXK_CHECK_ARG(ldvt >= tk_pad && ldvt % 8 == 0, "ltxk_flash_attn_bf16: ldvt=%d must be >= %d (Tk rounded up to 64) and a multiple of 8", ldvt, tk_pad);
-  LTXK_CHECK_ARG((((uintptr_t)q | (uintptr_t)k | (uintptr_t)vt) & 15) == 0 && ((uintptr_t)out & 15) == 0, "ltxk_flash_attn_bf16: misaligned pointer");
+  LTXK_CHECK_ARG((((uintptr_t)a->q | (uintptr_t)a->k | (uintptr_t)a->vt) & 15) == 0 && ((uintptr_t)a->out & 15) == 0, "ltxk_flash_attn_bf16: misaligned pointer");
   if (a->q_sumsq) {
     LTXK_CHECK_ARG(a->q_norm_weight != nullptr, "ltxk_flash_attn: q_sumsq needs q_norm_weight");
     LTXK_CHECK_ARG(a->q_sumsq_n > 0 && a->q_sumsq_n % 8 == 0 && a->q_sumsq_n * 64 == H * FA_DH && a->q_sumsq_ld >= a->q_sumsq_n,
@@ -876,27 +887,8 @@ extern "C" int ltxk_flash_attn(const ltxk_attn_args* a, void* stream) {
     LTXK_CHECK_ARG((((uintptr_t)a->q_sumsq | (uintptr_t)a->q_norm_weight) & 15) == 0 && a->q_sumsq_ld % 4 == 0, "ltxk_flash_attn: q_sumsq / q_norm_weight must be 16-byte aligned");
     LTXK_CHECK_ARG((a->cos == nullptr) == (a->sin == nullptr) && (((uintptr_t)a->cos | (uintptr_t)a->sin) & 15) == 0, "ltxk_flash_attn: cos and sin must both be set (16-byte aligned) or both NULL");
   }
-  FaParams p;
-  p.q = (const bf16*)q; p.k = (const bf16*)k; p.vt = (const bf16*)vt; p.out = (bf16*)out;
-  p.ldq = ldq; p.ldk = ldk; p.ldvt = ldvt; p.ldo = ldo;
-  p.B = B; p.H = H; p.Tq = Tq; p.Tk = Tk;
-  p.c = scale * 1.4426950408889634f;
-  p.q_ss = a->q_sumsq; p.q_ss_ld = a->q_sumsq_ld; p.q_ss_n = a->q_sumsq_n;
-  p.q_w = (const bf16*)a->q_norm_weight; p.cosb = a->q_sumsq ? a->cos : nullptr; p.sinb = a->q_sumsq ? a->sin : nullptr; p.eps = a->eps;
-  static thread_local int attr_dev = -1;
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev != attr_dev) {
-    hipError_t e = hipFuncSetAttribute((const void*)flash_attn_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, FA_LDS);
-    if (e != hipSuccess) { ltxk_set_error("ltxk_flash_attn_bf16: hipFuncSetAttribute: %s", hipGetErrorString(e)); return LTXK_ELAUNCH; }
-    attr_dev = dev;
-  }
-  static thread_local int slots = 0;
-  if (slots == 0) {
-    int cus = 256;
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    slots = 2 * cus;
-  }
+  LTXK_CHECK_ARG(cus > 0, "ltxk_flash_attn_plan: cus=%d must be positive", cus);
+  const int slots = 2 * cus;                                     // two workgroups per CU
   // Forms measured and removed again (numbers at B=2,H=32, Tq=Tk=1280 / 5184, round 1): an 8-wave ping-pong kernel with a
   // 4-deep 128 KiB ring 565 / 930 TF/s, a 5-wave 160-row form 554 / 580, a 48-KiB 3-workgroup form ~430, against 630 / 945
   // for this one.  Round 2 (same box, interleaved rounds; this kernel 52.6 us at Tq=1024,Tk=1280 and 864 us at 5184^2):
@@ -913,25 +905,25 @@ extern "C" int ltxk_flash_attn(const ltxk_attn_args* a, void* stream) {
   // Round 3: the 16x16x32 formulation (fa_body16) - first form equal at 5184^2 (834.7 vs 834.5 us: 13 % higher held clock spent
   // on 18 % more VALU issue), after dropping the cross-lane exchange from the deferral test and the packed fp32 adds 795 vs 830 us
   // at 5184^2 and 67.4 vs 70.1 us at 1280^2: it ships (profiles/r03_attn_*).  LTXK_FA_XCD={1,0}, LTXK_FA_MFMA={16,32} remain in the A/B build.
-  const int xcd_map = LTXK_AB_INT("LTXK_FA_XCD", 1);
-  p.QT = (Tq + 127) / 128;
-  p.xcd = (xcd_map && (B * H) % 8 == 0) ? 1 : 0;
+  f.mfma = LTXK_AB_INT("LTXK_FA_MFMA", FA_DEFAULT_MFMA);
+  f.QT = (Tq + 127) / 128;
+  f.xcd = (LTXK_AB_INT("LTXK_FA_XCD", 1) && (B * H) % 8 == 0) ? 1 : 0;
   // With the tail split on, a tile in the short round sums its keys in a different order than the same rows would in a
   // launch without a short round (e.g. B=1 vs B=2), so batching changes low-order bits; LTXK_ATTN_NO_TAIL_SPLIT in
   // args->flags restores batch-invariant results (an explicit ABI field because it changes output bits).
   const int split = (a->flags & LTXK_ATTN_NO_TAIL_SPLIT) ? 0 : 1;
-  const int tiles = p.QT * B * H;
-  p.n_full = tiles; p.rem = 0;
+  const int tiles = f.QT * B * H;
+  f.mix = false; f.qta = 0; f.qtb = 0;
+  f.n_full = tiles; f.rem = 0;
   if (split && tiles % slots != 0) {
     // r tiles in the short last round.  r <= slots/2: split them all (2r workgroups).  r > slots/2 (round 3; e.g. one
     // B=1 forward of the CFG-pair split: 320 tiles for 512 slots): split the slots - r tiles that fill the round exactly -
     // 2 (slots - r) half workgroups + (2r - slots) whole ones = slots workgroups, no CU left with two whole tiles beside
     // CUs that have one.
     const int r = tiles % slots;
-    p.rem = 2 * r <= slots ? r : (LTXK_AB_INT("LTXK_FA_FILL", 1) ? slots - r : 0);
-    p.n_full = tiles - p.rem;
+    f.rem = 2 * r <= slots ? r : (LTXK_AB_INT("LTXK_FA_FILL", 1) ? slots - r : 0);
+    f.n_full = tiles - f.rem;
   }
-  p.n_a = 0; p.qta = 0; p.qtb = 0;
   // More than one 128-row tile per (batch, head): the mixed 192 / 128-row grid (flash_attn16_mix_kernel).  A/B build: LTXK_FA_QB=2
   // keeps the 128-row kernel with its tail split everywhere, 3 forces 192-row tiles only.
   // Which grid (same box, interleaved, B*H = 32 / 64 / 128; profiles/r04_attn_qb_ab.log): from 1.25 rounds of 128-row tiles up the
@@ -939,46 +931,72 @@ extern "C" int ltxk_flash_attn(const ltxk_attn_args* a, void* stream) {
   // that the chip has fewer workgroups than slots, a CU runs one workgroup - one wave per SIMD, ~0.8 of the shared rate - and the
   // 128-row kernel's key-split tail, which doubles the workgroups, is the faster form (B=1 1280^2: 33.7 against 37.4 us for 192-row tiles).
   const int qb_env = LTXK_AB_INT("LTXK_FA_QB", 0);
-  const long tiles128 = (long)((Tq + 127) / 128) * B * H;
-  if (Tq > 128 && qb_env != 2 && (qb_env == 3 || 4 * tiles128 >= 5L * slots) && LTXK_AB_INT("LTXK_FA_MFMA", FA_DEFAULT_MFMA) == 16) {
-    static thread_local int attr_devm = -1;
-    if (dev != attr_devm) {
-      hipError_t e = hipFuncSetAttribute((const void*)flash_attn16_mix_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, FA_LDS_MIX);
-      if (e != hipSuccess) { ltxk_set_error("ltxk_flash_attn_bf16: hipFuncSetAttribute: %s", hipGetErrorString(e)); return LTXK_ELAUNCH; }
-      attr_devm = dev;
-    }
-    static thread_local int c_tq = 0, c_tk = 0, c_bh = 0, c_qta = 0, c_qtb = 0;      // last two decisions (a forward repeats two shapes)
-    static thread_local int c2_tq = 0, c2_tk = 0, c2_bh = 0, c2_qta = 0, c2_qtb = 0;
-    int qta, qtb;
-    if (qb_env == 3) { qta = (Tq + 191) / 192; qtb = 0; }
-    else if (Tq == c_tq && Tk == c_tk && B * H == c_bh) { qta = c_qta; qtb = c_qtb; }
-    else if (Tq == c2_tq && Tk == c2_tk && B * H == c2_bh) { qta = c2_qta; qtb = c2_qtb; }
-    else {
-      fa_pick_mix(Tq, Tk, B * H, slots / 2, qta, qtb);
-      c2_tq = c_tq; c2_tk = c_tk; c2_bh = c_bh; c2_qta = c_qta; c2_qtb = c_qtb;
-      c_tq = Tq; c_tk = Tk; c_bh = B * H; c_qta = qta; c_qtb = qtb;
-    }
-    p.qta = qta; p.qtb = qtb; p.n_a = qta * B * H;
-    p.n_full = (qta + qtb) * B * H; p.rem = 0;
-    hipLaunchKernelGGL(flash_attn16_mix_kernel, dim3((unsigned)p.n_full), dim3(256), FA_LDS_MIX, (hipStream_t)stream, p);
-    LTXK_CHECK_LAUNCH("ltxk_flash_attn_bf16");
-    return LTXK_OK;
+  if (Tq > 128 && qb_env != 2 && (qb_env == 3 || 4L * tiles >= 5L * slots) && f.mfma == 16) {
+    f.mix = true;
+    if (qb_env == 3) { f.qta = (Tq + 191) / 192; f.qtb = 0; }
+    else fa_pick_mix(Tq, Tk, B * H, cus, f.qta, f.qtb);
+    f.n_full = (f.qta + f.qtb) * B * H; f.rem = 0;
   }
-  const dim3 grid((unsigned)(p.n_full + 2 * p.rem));
-  if (LTXK_AB_INT("LTXK_FA_MFMA", FA_DEFAULT_MFMA) == 16) {
-    static thread_local int attr_dev16 = -1;
-    if (dev != attr_dev16) {
-      hipError_t e = hipFuncSetAttribute((const void*)flash_attn16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, FA_LDS);
-      if (e != hipSuccess) { ltxk_set_error("ltxk_flash_attn_bf16: hipFuncSetAttribute: %s", hipGetErrorString(e)); return LTXK_ELAUNCH; }
-      attr_dev16 = dev;
-    }
-    hipLaunchKernelGGL(flash_attn16_kernel, grid, dim3(256), FA_LDS, (hipStream_t)stream, p);
-    LTXK_CHECK_LAUNCH("ltxk_flash_attn_bf16");
-    return LTXK_OK;
-  }
-  hipLaunchKernelGGL(flash_attn_kernel<4>, grid, dim3(256), FA_LDS, (hipStream_t)stream, p);
+  return LTXK_OK;
+}
+
+static int fa_device_cus() {
+  int dev = 0, cus = 0;
+  (void)hipGetDevice(&dev);
+  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+  return cus;
+}
+
+template <typename Kern>
+static int fa_launch(Kern kern, std::atomic<uint64_t>& attr_set, int lds, const FaForm& f, const FaParams& p, hipStream_t stream) {
+  const int rc = ensure_dyn_lds((const void*)kern, lds, attr_set, "ltxk_flash_attn_bf16");
+  if (rc != LTXK_OK) return rc;
+  hipLaunchKernelGGL(kern, dim3((unsigned)(f.n_full + 2 * f.rem)), dim3(256), lds, stream, p);
   LTXK_CHECK_LAUNCH("ltxk_flash_attn_bf16");
   return LTXK_OK;
+}
+
+}  // namespace ltxk
+
+extern "C" int ltxk_flash_attn_plan(const ltxk_attn_args* a, int32_t cus, struct ltxk_flash_attn_plan* plan) {
+  using namespace ltxk;
+  LTXK_CHECK_ARG(plan != nullptr, "ltxk_flash_attn_plan: null plan");
+  FaForm f;
+  const int rc = fa_form(a, cus, f);
+  if (rc != LTXK_OK) return rc;
+  plan->kernel = f.mix ? LTXK_ATTN_KERNEL_MIX : LTXK_ATTN_KERNEL_128;
+  plan->mfma_k = f.mfma;
+  plan->tiles_192 = f.qta;
+  plan->tiles_128 = f.mix ? f.qtb : f.QT;
+  plan->whole_workgroups = f.n_full;
+  plan->split_tiles = f.rem;
+  plan->workgroups = f.n_full + 2 * f.rem;
+  plan->xcd_order = f.xcd;
+  return LTXK_OK;
+}
+
+extern "C" int ltxk_flash_attn_plan_sizeof(void) { return (int)sizeof(struct ltxk_flash_attn_plan); }
+
+extern "C" int ltxk_flash_attn(const ltxk_attn_args* a, void* stream) {
+  using namespace ltxk;
+  FaForm f;
+  const int rc = fa_form(a, fa_device_cus(), f);
+  if (rc != LTXK_OK) return rc;
+  FaParams p;
+  p.q = (const bf16*)a->q; p.k = (const bf16*)a->k; p.vt = (const bf16*)a->vt; p.out = (bf16*)a->out;
+  p.ldq = a->ldq; p.ldk = a->ldk; p.ldvt = a->ldvt; p.ldo = a->ldo;
+  p.B = a->B; p.H = a->H; p.Tq = a->Tq; p.Tk = a->Tk;
+  p.c = a->scale * 1.4426950408889634f;
+  p.q_ss = a->q_sumsq; p.q_ss_ld = a->q_sumsq_ld; p.q_ss_n = a->q_sumsq_n;
+  p.q_w = (const bf16*)a->q_norm_weight; p.cosb = a->q_sumsq ? a->cos : nullptr; p.sinb = a->q_sumsq ? a->sin : nullptr; p.eps = a->eps;
+  p.QT = f.QT; p.xcd = f.xcd;
+  p.n_full = f.n_full; p.rem = f.rem;
+  p.qta = f.qta; p.qtb = f.qtb; p.n_a = f.qta * a->B * a->H;
+  static std::atomic<uint64_t> set_mix{0}, set_16{0}, set_32{0};     // ensure_dyn_lds: one per kernel
+  hipStream_t st = (hipStream_t)stream;
+  if (f.mix) return fa_launch(flash_attn16_mix_kernel, set_mix, FA_LDS_MIX, f, p, st);
+  if (f.mfma == 16) return fa_launch(flash_attn16_kernel, set_16, FA_LDS, f, p, st);
+  return fa_launch(flash_attn_kernel<4>, set_32, FA_LDS, f, p, st);
 }
 
 extern "C" int ltxk_flash_attn_bf16(const void* q, int32_t ldq, const void* k, int32_t ldk,

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <atomic>
 #include "../../include/ltxk.h"
 
 typedef __bf16 bf16;
@@ -14,10 +15,10 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 #define LTXK_WAVE 64
 
-// A/B switches.  The product library (libltxk.so) reads NO environment variable and keeps no mutable global state
-// (include/ltxk.h, Conventions): LTXK_AB_INT(name, default) is the constant `default` there.  The measurement build
-// (`make ab` -> libltxk_ab.so, -DLTXK_AB; loaded only by scripts/ and by the tests that compare two launch forms of one
-// kernel bit for bit, through mlx_video_amd._lib.use_library) reads the named variable on every call.
+// A/B switches.  The product library (libltxk.so) reads NO environment variable and keeps no state that influences a result
+// or a launch form (include/ltxk.h, Conventions): LTXK_AB_INT(name, default) is the constant `default` there.  The
+// measurement build (`make ab` -> libltxk_ab.so, -DLTXK_AB; loaded only by scripts/ and by the tests that compare two launch
+// forms of one kernel bit for bit, through mlx_video_amd._lib.use_library) reads the named variable on every call.
 #ifdef LTXK_AB
 #include <stdlib.h>
 #define LTXK_AB_INT(name, dflt) ([] { const char* e__ = getenv(name); return e__ ? atoi(e__) : (dflt); }())
@@ -44,6 +45,24 @@ void ltxk_set_error(const char* fmt, ...);
       return LTXK_ELAUNCH;                                                       \
     }                                                                            \
   } while (0)
+
+// Raise a kernel's dynamic-LDS limit (hipFuncSetAttribute) once per (kernel, device), in front of a launch of that kernel:
+// `done` is one `static std::atomic<uint64_t>` per kernel instantiation, a bit per device, set after the first success.
+// These idempotent bits are the library's only process-wide state (include/ltxk.h, Conventions); a device past the 64th is
+// set on every call.  `who` heads the error string.
+static inline int ensure_dyn_lds(const void* kern, int bytes, std::atomic<uint64_t>& done, const char* who) {
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  const uint64_t bit = dev >= 0 && dev < 64 ? 1ull << dev : 0;
+  if (done.load(std::memory_order_acquire) & bit) return LTXK_OK;
+  hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  if (e != hipSuccess) {
+    ltxk_set_error("%s: hipFuncSetAttribute: %s", who, hipGetErrorString(e));
+    return LTXK_ELAUNCH;
+  }
+  done.fetch_or(bit, std::memory_order_release);
+  return LTXK_OK;
+}
 
 // Round fp32 to bf16 storage and back: the "materialise a bf16 array" point of the reference.
 // Written as an opaque v_cvt_pk_bf16_f32 (RNE): with the plain cast pair hipcc (ROCm 7.2,

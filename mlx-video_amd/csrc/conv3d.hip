@@ -745,17 +745,9 @@ static int conv_launch_kw(const ConvParams& p0, hipStream_t stream) {
   if (p.RT == 0) p.RT = (p.M - p.m_base + G::BM - 1) / G::BM;
   p.CT = (p.Cout + KW_BN - 1) / KW_BN;
   auto kern = conv3d_k3_kw_kernel<TT, RES>;
-  static thread_local int attr_dev = -1;
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev != attr_dev) {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS);
-    if (e != hipSuccess) {
-      ltxk_set_error("ltxk_conv3d_k3_bf16: hipFuncSetAttribute: %s", hipGetErrorString(e));
-      return LTXK_ELAUNCH;
-    }
-    attr_dev = dev;
-  }
+  static std::atomic<uint64_t> attr_set{0};
+  const int rc = ensure_dyn_lds((const void*)kern, G::LDS, attr_set, "ltxk_conv3d_k3_bf16");
+  if (rc != LTXK_OK) return rc;
   hipLaunchKernelGGL(kern, dim3(p.RT * p.CT), dim3(GEMM_THREADS), G::LDS, stream, p);
   LTXK_CHECK_LAUNCH("ltxk_conv3d_k3_bf16(kw)");
   return LTXK_OK;
@@ -765,17 +757,9 @@ template <int TT, int WN, bool RES>
 static int conv_launch_plain(const ConvParams& p, hipStream_t stream) {
   using G = GemmGeom<TT, WN>;
   auto kern = conv3d_k3_kernel<TT, WN, RES, false>;
-  static thread_local int attr_dev = -1;
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev != attr_dev) {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES);
-    if (e != hipSuccess) {
-      ltxk_set_error("ltxk_conv3d_k3_bf16: hipFuncSetAttribute: %s", hipGetErrorString(e));
-      return LTXK_ELAUNCH;
-    }
-    attr_dev = dev;
-  }
+  static std::atomic<uint64_t> attr_set{0};
+  const int rc = ensure_dyn_lds((const void*)kern, G::LDS_BYTES, attr_set, "ltxk_conv3d_k3_bf16");
+  if (rc != LTXK_OK) return rc;
   hipLaunchKernelGGL(kern, dim3(p.RT * p.CT), dim3(GEMM_THREADS), G::LDS_BYTES, stream, p);
   LTXK_CHECK_LAUNCH("ltxk_conv3d_k3_bf16");
   return LTXK_OK;
@@ -899,14 +883,9 @@ static int conv_launch(const ConvParams& p0, const ConvForm& f, hipStream_t stre
   p.CT = pl.col_tiles;
   if (pl.slices >= 2) {
     auto kern = conv3d_k3_kernel<TT, WN, false, true>;
-    static thread_local int attr_dev_s = -1;
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev != attr_dev_s) {
-      hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES);
-      if (e != hipSuccess) { ltxk_set_error("ltxk_conv3d_k3_bf16: hipFuncSetAttribute: %s", hipGetErrorString(e)); return LTXK_ELAUNCH; }
-      attr_dev_s = dev;
-    }
+    static std::atomic<uint64_t> attr_set{0};
+    const int rc = ensure_dyn_lds((const void*)kern, G::LDS_BYTES, attr_set, "ltxk_conv3d_k3_bf16");
+    if (rc != LTXK_OK) return rc;
     p.slab = f.ws; p.S = pl.slices; p.kper = pl.ksteps;
     hipLaunchKernelGGL(kern, dim3(p.RT * p.CT * p.S), dim3(GEMM_THREADS), G::LDS_BYTES, stream, p);
     LTXK_CHECK_LAUNCH("ltxk_conv3d_k3_bf16(split-K)");

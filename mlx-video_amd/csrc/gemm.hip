@@ -6,7 +6,6 @@
 // body with template flags.  W8A8 exists as the single-pass 160-row family only - no split-K, big-tile or grouped form.
 #include "gemm_core.h"
 #include <stdlib.h>
-#include <atomic>
 #include <type_traits>
 #include <utility>
 
@@ -665,17 +664,9 @@ __global__ __launch_bounds__(GEMM_THREADS) void gemm_stream_kernel(GemmParams p)
 template <int TT, bool W8>
 static int launch_stream(const GemmParams& p, int ksplit, hipStream_t stream) {
   auto kern = gemm_stream_kernel<TT, W8>;
-  static thread_local int attr_dev = -1;
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev != attr_dev) {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, StreamGeom<TT, W8>::LDS);
-    if (e != hipSuccess) {
-      ltxk_set_error("ltxk_gemm_bf16: hipFuncSetAttribute: %s", hipGetErrorString(e));
-      return LTXK_ELAUNCH;
-    }
-    attr_dev = dev;
-  }
+  static std::atomic<uint64_t> attr_set{0};
+  const int rc = ensure_dyn_lds((const void*)kern, StreamGeom<TT, W8>::LDS, attr_set, "ltxk_gemm_bf16");
+  if (rc != LTXK_OK) return rc;
   hipLaunchKernelGGL(kern, dim3(p.RT * p.CT, ksplit), dim3(GEMM_THREADS), (StreamGeom<TT, W8>::LDS), stream, p);
   LTXK_CHECK_LAUNCH("ltxk_gemm_bf16 (split-K slices)");
   return LTXK_OK;
@@ -762,18 +753,9 @@ template <int TT, int NT, int EPI, int MODE, bool W8, bool A8>
 static int launch(const GemmParams& p, hipStream_t stream) {
   using G = GemmGeom<TT, 4, NT, W8 && !A8>;
   auto kern = gemm_bf16_kernel<TT, NT, EPI, MODE, W8, A8>;
-  static thread_local int attr_dev = -1;
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev != attr_dev) {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       G::LDS_BYTES);
-    if (e != hipSuccess) {
-      ltxk_set_error("ltxk_gemm_bf16: hipFuncSetAttribute: %s", hipGetErrorString(e));
-      return LTXK_ELAUNCH;
-    }
-    attr_dev = dev;
-  }
+  static std::atomic<uint64_t> attr_set{0};
+  const int rc = ensure_dyn_lds((const void*)kern, G::LDS_BYTES, attr_set, "ltxk_gemm_bf16");
+  if (rc != LTXK_OK) return rc;
   hipLaunchKernelGGL(kern, dim3(p.RT * p.CT), dim3(GEMM_THREADS), G::LDS_BYTES, stream, p);
   LTXK_CHECK_LAUNCH("ltxk_gemm_bf16");
   return LTXK_OK;
@@ -1118,17 +1100,9 @@ template <int EPI, int MODE, int RB>
 static int launch_big_rb(const GemmParams& p, hipStream_t stream) {
   constexpr int BIG_LDS = BigGeom<RB>::LDS;
   auto kern = gemm_bf16_big_kernel<EPI, MODE, RB>;
-  static thread_local int attr_dev = -1;
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev != attr_dev) {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, BIG_LDS);
-    if (e != hipSuccess) {
-      ltxk_set_error("ltxk_gemm_bf16: hipFuncSetAttribute: %s", hipGetErrorString(e));
-      return LTXK_ELAUNCH;
-    }
-    attr_dev = dev;
-  }
+  static std::atomic<uint64_t> attr_set{0};
+  const int rc = ensure_dyn_lds((const void*)kern, BIG_LDS, attr_set, "ltxk_gemm_bf16");
+  if (rc != LTXK_OK) return rc;
   hipLaunchKernelGGL(kern, dim3(p.RT * p.CT), dim3(512), BIG_LDS, stream, p);
   LTXK_CHECK_LAUNCH("ltxk_gemm_bf16");
   return LTXK_OK;
@@ -1222,22 +1196,6 @@ __global__ __launch_bounds__(512) void gemm_grouped_big_kernel(GroupedParams gp)
       else gemm_big_tile<LTXK_EPI_BIAS, true, RB>(p, smem, m0, n0, wave, lane);
     }
   }
-}
-
-// hipFuncSetAttribute once per (kernel, device): a bit per device, set after the first success.  (The older launchers keep a
-// thread_local "last device", which sets the attribute again for every thread and every device switch.)
-static int ensure_dyn_lds(const void* kern, int bytes, std::atomic<uint64_t>& done, const char* who) {
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  const uint64_t bit = 1ull << (dev & 63);
-  if (done.load(std::memory_order_acquire) & bit) return LTXK_OK;
-  hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-  if (e != hipSuccess) {
-    ltxk_set_error("%s: hipFuncSetAttribute: %s", who, hipGetErrorString(e));
-    return LTXK_ELAUNCH;
-  }
-  if (dev < 64) done.fetch_or(bit, std::memory_order_release);
-  return LTXK_OK;
 }
 
 template <int RB, int RR>

@@ -4,6 +4,7 @@ on torch's current HIP stream (so a torch.cuda.graph capture records the whole s
 from __future__ import annotations
 
 import ctypes
+import math
 from dataclasses import dataclass
 from typing import Optional, Tuple
 
@@ -340,6 +341,44 @@ def flash_attn(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, out: torch.Te
     with _timed("flash_attn", 4.0 * B * H * Tq * Tk * 128, 2.0 * B * H * 128 * (2 * Tq + 2 * Tk)):
         check(_lib.load().ltxk_flash_attn(ctypes.byref(a), _stream()), "ltxk_flash_attn")
     return out
+
+
+@dataclass(frozen=True)
+class AttnPlan:
+    """ltxk_flash_attn_plan: the launch form of one ltxk_flash_attn call (include/ltxk.h, struct ltxk_flash_attn_plan)."""
+    kernel: int
+    mfma_k: int
+    tiles_192: int
+    tiles_128: int
+    whole_workgroups: int
+    split_tiles: int
+    workgroups: int
+    xcd_order: int
+
+    @property
+    def mix(self) -> bool:
+        return self.kernel == _lib.ATTN_KERNEL_MIX
+
+
+def flash_attn_plan(B: int, H: int, Tq: int, Tk: int, *, cus: int, tail_split: bool = True, fused_q: bool = False) -> AttnPlan:
+    """The form ``flash_attn`` takes for these dimensions on a device of ``cus`` compute units
+    (torch.cuda.get_device_properties(d).multi_processor_count), decided on the host by the function the launch itself uses
+    (no device needed).  Strides are those of contiguous tensors (V^T: keys padded to 64); ``fused_q``: with the fused query
+    preparation's operands.  Raises LtxkError where ``flash_attn`` would refuse the arguments."""
+    a = AttnArgs()
+    a.flags = 0 if tail_split else _lib.ATTN_NO_TAIL_SPLIT
+    a.q = a.k = a.vt = a.out = _PLAN_ADDR
+    a.ldq = a.ldk = a.ldo = H * 128
+    a.ldvt = (Tk + 63) // 64 * 64
+    a.B, a.H, a.Tq, a.Tk, a.scale = B, H, Tq, Tk, 1.0 / math.sqrt(128)
+    if fused_q:
+        a.q_sumsq, a.q_sumsq_ld, a.q_sumsq_n = _PLAN_ADDR, H * 2, H * 2
+        a.q_norm_weight = a.cos = a.sin = _PLAN_ADDR
+        a.eps = 1e-6
+    pl = _lib.AttnPlan()
+    check(_lib.load().ltxk_flash_attn_plan(ctypes.byref(a), cus, ctypes.byref(pl)), "ltxk_flash_attn_plan")
+    return AttnPlan(pl.kernel, pl.mfma_k, pl.tiles_192, pl.tiles_128, pl.whole_workgroups, pl.split_tiles, pl.workgroups,
+                    pl.xcd_order)
 
 
 def rmsnorm_modulate(x: torch.Tensor, eps: float, scale: Optional[torch.Tensor] = None,

@@ -34,6 +34,9 @@ def test_library_exports_every_declared_symbol():
     import ctypes
     for which, st in enumerate((_lib.GemmArgs, _lib.Conv3dArgs, _lib.AttnArgs, _lib.GemmPlan)):   # binding layout == compiled layout
         assert lib.ltxk_abi_sizeof(which) == ctypes.sizeof(st)
+    for fn, st in ((lib.ltxk_gemm_grouped_args_sizeof, _lib.GemmGroupedArgs), (lib.ltxk_conv3d_plan_sizeof, _lib.Conv3dPlan),
+                   (lib.ltxk_flash_attn_plan_sizeof, _lib.AttnPlan)):           # structs with a sizeof entry of their own
+        assert fn() == ctypes.sizeof(st)
 
 
 def test_product_refuses_cpu_tensors():
