@@ -104,16 +104,49 @@ def precompute_freqs_cis(positions: torch.Tensor, dim: int, theta: float = 10000
     return torch.stack(cos_l), torch.stack(sin_l)
 
 
+class Linear:
+    """One Linear layer as the GEMMs read it: the (out,in) matrix ``w`` (bf16 or float8_e4m3fn), the per-output-channel fp32
+    ``scale`` of an e4m3 matrix (None: a bf16 model, or an unscaled fp8 panel) and ``bias``.  Holds what it is given: no copy."""
+    __slots__ = ("w", "scale", "bias")
+
+    def __init__(self, w: torch.Tensor, scale: Optional[torch.Tensor], bias: torch.Tensor):
+        self.w, self.scale, self.bias = w, scale, bias
+
+    @property
+    def N(self) -> int:
+        return self.w.shape[0]
+
+    @property
+    def K(self) -> int:
+        return self.w.shape[1]
+
+    def rows(self, a: Optional[int], b: Optional[int]) -> "Linear":
+        """Output channels [a, b) as a Linear of views: one part of a packed panel."""
+        return Linear(self.w[a:b], None if self.scale is None else self.scale[a:b], self.bias[a:b])
+
+    @staticmethod
+    def cat(parts: Sequence["Linear"]) -> "Linear":
+        """The parts packed row-wise into one panel (an fp8 matrix through its bytes).  No part scaled: no scale; otherwise
+        one scale vector, with ones for the unscaled parts."""
+        ws = [p.w for p in parts]
+        w = torch.cat([t.view(torch.uint8) for t in ws], 0).view(FP8) if ws[0].dtype == FP8 else torch.cat(ws, 0)
+        scale = None
+        if any(p.scale is not None for p in parts):
+            scale = torch.cat([torch.ones(p.N, dtype=torch.float32, device=p.w.device) if p.scale is None else p.scale
+                               for p in parts], 0).contiguous()
+        return Linear(w, scale, torch.cat([p.bias for p in parts], 0))
+
+
 class _Block:
-    __slots__ = ("wqkv", "bqkv", "wqn", "wkn", "wqkn", "wo", "bo", "wq2", "bq2", "wkv2", "bkv2",
-                 "wqn2", "wkn2", "wo2", "bo2", "w1", "b1", "w2", "b2",
-                 # per-output-channel fp32 scales of the e4m3 panels (None: bf16 model, or an unscaled fp8 panel)
-                 "sqkv", "so", "sq2", "skv2", "so2", "s1", "s2")
+    # Linear: self-attention q|k|v (one (3D,D) panel) and to_out, text attention to_q, k|v (one (2D,D) panel) and to_out,
+    # feed-forward in and out; then the q/k-norm weights (wqkn: wqn | wkn for the launch form that normalises both at once)
+    __slots__ = ("qkv", "o", "q2", "kv2", "o2", "ff1", "ff2", "wqn", "wkn", "wqkn", "wqn2", "wkn2")
 
 
-def _rows(t: Optional[torch.Tensor], a: Optional[int], b: Optional[int]) -> Optional[torch.Tensor]:
-    """t[a:b] of a panel's scale vector, which may be absent."""
-    return None if t is None else t[a:b]
+def _vt_buffer(*lead: int, tokens: int, device) -> torch.Tensor:
+    """A V^T buffer (*lead, tokens padded to 64): zero-filled where there is padding, which attention reads."""
+    padded = (tokens + 63) // 64 * 64
+    return (torch.zeros if padded != tokens else torch.empty)((*lead, padded), dtype=BF16, device=device)
 
 
 class ContextKV:
@@ -154,7 +187,7 @@ class LTXModel:
         # every token through the token->row map even when all tokens share one timestep row (A/B runs only)
         self.tok2row_always = False
         # True makes a forward's bits independent of the batch it runs in (B=1 per CFG-pair rank == row b of the B=2
-        # cfg_batch forward): every ops.gemm single-pass (split_k=False - the split-K slice count depends on M, so at
+        # cfg_batch forward): every ops.gemm single-pass (no split-K scratch on offer - the split-K slice count depends on M, so at
         # M <= ops.SPLITK_MAX_M a row sums its products in another order when the launch holds more rows) and every
         # attention without the tail split.  Costs the split-K weight stream of small-M launches.
         self.batch_invariant = False
@@ -200,53 +233,51 @@ class LTXModel:
         self.weight_dtype = FP8 if any(W[k].dtype == FP8 for k in mats) else BF16
         fp8 = self.weight_dtype == FP8
 
-        def gw(k):
-            """-> [matrix, scale or None]"""
+        def load(k):
+            """The Linear of one checkpoint ``*.weight`` key: the matrix, its optional ``<key>_scale`` (fp8 model), its ``.bias``."""
+            bias = g(k[:-len("weight")] + "bias")
             if not fp8:
-                return [g(k), None]
+                return Linear(g(k), None, bias)
             t, sc = W[k], W.get(k + "_scale")
             if t.dtype != FP8 or not t.is_cuda:
                 raise TypeError(f"weight {k}: an fp8 model takes every Linear matrix as a float8_e4m3fn device tensor, got {t.dtype}")
             if sc is not None and (sc.dtype != torch.float32 or sc.shape != (t.shape[0],) or sc.device != t.device):
                 raise TypeError(f"weight {k}_scale: expected a ({t.shape[0]},) float32 device tensor")
-            return [t.contiguous(), None if sc is None else sc.contiguous()]
+            return Linear(t.contiguous(), None if sc is None else sc.contiguous(), bias)
 
-        def cat(parts):
-            """Row-wise concatenation of [matrix, scale] pairs into one packed panel (fp8 through its bytes) and one scale vector."""
-            ws, ss = [w for w, _ in parts], [sc for _, sc in parts]
-            w = torch.cat([t.view(torch.uint8) for t in ws], 0).view(FP8) if fp8 else torch.cat(ws, 0)
-            if all(sc is None for sc in ss):
-                return w, None
-            ones = [torch.ones(t.shape[0], dtype=torch.float32, device=t.device) if sc is None else sc for t, sc in parts]
-            return w, torch.cat(ones, 0).contiguous()
+        def lin(*keys):
+            """``load`` of one key, or of several packed row-wise into one panel; every key goes into the panel table."""
+            parts = [load(k) for k in keys]
+            panel = parts[0] if len(parts) == 1 else Linear.cat(parts)
+            r = 0
+            for k, part in zip(keys, parts):
+                self._panels[k] = (panel, r, r + part.N)
+                r += part.N
+            return panel
 
-        (self.patchify_w, self.patchify_s), self.patchify_b = gw("patchify_proj.weight"), g("patchify_proj.bias")
+        # checkpoint key of every Linear matrix -> (the Linear that holds it, its first row, its end row), in load order
+        self._panels: Dict[str, Tuple[Linear, int, int]] = {}
+        self.patchify = lin("patchify_proj.weight")
         p = "adaln_single.emb.timestep_embedder"
-        (self.t1_w, self.t1_s), self.t1_b = gw(f"{p}.linear1.weight"), g(f"{p}.linear1.bias")
-        (self.t2_w, self.t2_s), self.t2_b = gw(f"{p}.linear2.weight"), g(f"{p}.linear2.bias")
-        (self.ada_w, self.ada_s), self.ada_b = gw("adaln_single.linear.weight"), g("adaln_single.linear.bias")
-        (self.c1_w, self.c1_s), self.c1_b = gw("caption_projection.linear1.weight"), g("caption_projection.linear1.bias")
-        (self.c2_w, self.c2_s), self.c2_b = gw("caption_projection.linear2.weight"), g("caption_projection.linear2.bias")
+        self.t1, self.t2 = lin(f"{p}.linear1.weight"), lin(f"{p}.linear2.weight")
+        self.ada = lin("adaln_single.linear.weight")
+        self.c1, self.c2 = lin("caption_projection.linear1.weight"), lin("caption_projection.linear2.weight")
         self.head_table = g("scale_shift_table").reshape(1, 2, -1)
-        (self.out_w, self.out_s), self.out_b = gw("proj_out.weight"), g("proj_out.bias")
+        self.out = lin("proj_out.weight")
         self.blocks: List[_Block] = []
         tables = []
         for i in range(cfg.num_layers):
             pre = f"transformer_blocks.{i}"
             b = _Block()
             # one (3D,D) panel for to_q|to_k|to_v: a single GEMM launch writes q|k row-major and V^T (split output)
-            b.wqkv, b.sqkv = cat([gw(f"{pre}.attn1.to_{n}.weight") for n in "qkv"])
-            b.bqkv = torch.cat([g(f"{pre}.attn1.to_{n}.bias") for n in "qkv"], 0)
+            b.qkv = lin(*(f"{pre}.attn1.to_{n}.weight" for n in "qkv"))
             b.wqn, b.wkn = g(f"{pre}.attn1.q_norm.weight"), g(f"{pre}.attn1.k_norm.weight")
             b.wqkn = torch.cat([b.wqn, b.wkn], 0)
-            (b.wo, b.so), b.bo = gw(f"{pre}.attn1.to_out.weight"), g(f"{pre}.attn1.to_out.bias")
-            (b.wq2, b.sq2), b.bq2 = gw(f"{pre}.attn2.to_q.weight"), g(f"{pre}.attn2.to_q.bias")
-            b.wkv2, b.skv2 = cat([gw(f"{pre}.attn2.to_k.weight"), gw(f"{pre}.attn2.to_v.weight")])     # text k | V^T, one launch
-            b.bkv2 = torch.cat([g(f"{pre}.attn2.to_k.bias"), g(f"{pre}.attn2.to_v.bias")], 0)
+            b.o, b.q2 = lin(f"{pre}.attn1.to_out.weight"), lin(f"{pre}.attn2.to_q.weight")
+            b.kv2 = lin(f"{pre}.attn2.to_k.weight", f"{pre}.attn2.to_v.weight")     # text k | V^T, one launch
             b.wqn2, b.wkn2 = g(f"{pre}.attn2.q_norm.weight"), g(f"{pre}.attn2.k_norm.weight")
-            (b.wo2, b.so2), b.bo2 = gw(f"{pre}.attn2.to_out.weight"), g(f"{pre}.attn2.to_out.bias")
-            (b.w1, b.s1), b.b1 = gw(f"{pre}.ff.proj_in.weight"), g(f"{pre}.ff.proj_in.bias")
-            (b.w2, b.s2), b.b2 = gw(f"{pre}.ff.proj_out.weight"), g(f"{pre}.ff.proj_out.bias")
+            b.o2 = lin(f"{pre}.attn2.to_out.weight")
+            b.ff1, b.ff2 = lin(f"{pre}.ff.proj_in.weight"), lin(f"{pre}.ff.proj_out.weight")
             tables.append(g(f"{pre}.scale_shift_table"))
             self.blocks.append(b)
         self.tables = torch.stack(tables, 0).contiguous()      # (L,6,D)
@@ -255,8 +286,8 @@ class LTXModel:
         self.wkn2_all = torch.stack([b.wkn2 for b in self.blocks], 0).contiguous()
         for i, b in enumerate(self.blocks):
             b.wkn2 = self.wkn2_all[i]
-        self.wkv2_table = ops.pointer_table([b.wkv2 for b in self.blocks])
-        self.bkv2_table = ops.pointer_table([b.bkv2 for b in self.blocks])
+        self.wkv2_table = ops.pointer_table([b.kv2.w for b in self.blocks])
+        self.bkv2_table = ops.pointer_table([b.kv2.bias for b in self.blocks])
 
     def weight_views(self) -> Dict[str, torch.Tensor]:
         """Checkpoint key -> the (out,in) matrix as it lives inside THIS model: the packed q|k|v and text k|v panels are
@@ -266,39 +297,18 @@ class LTXModel:
             raise TypeError("weight_views: this model keeps its matrices in float8_e4m3fn, which cannot take an in-place LoRA merge; "
                             "merge into the bf16 weight dict (lora.apply_lora_to_weights(weights, specs), the fresh-copy path), "
                             "quantise the result (weights.quantize_transformer_weights) and build a model from it")
-        D = self.inner_dim
-        v = {"patchify_proj.weight": self.patchify_w, "adaln_single.emb.timestep_embedder.linear1.weight": self.t1_w,
-             "adaln_single.emb.timestep_embedder.linear2.weight": self.t2_w, "adaln_single.linear.weight": self.ada_w,
-             "caption_projection.linear1.weight": self.c1_w, "caption_projection.linear2.weight": self.c2_w, "proj_out.weight": self.out_w}
-        for i, b in enumerate(self.blocks):
-            pre = f"transformer_blocks.{i}"
-            for j, n in enumerate("qkv"):
-                v[f"{pre}.attn1.to_{n}.weight"] = b.wqkv[j * D:(j + 1) * D]
-            v[f"{pre}.attn1.to_out.weight"], v[f"{pre}.attn2.to_q.weight"] = b.wo, b.wq2
-            v[f"{pre}.attn2.to_k.weight"], v[f"{pre}.attn2.to_v.weight"] = b.wkv2[:D], b.wkv2[D:]
-            v[f"{pre}.attn2.to_out.weight"], v[f"{pre}.ff.proj_in.weight"], v[f"{pre}.ff.proj_out.weight"] = b.wo2, b.w1, b.w2
-        return v
+        return {k: panel.w[a:b] for k, (panel, a, b) in self._panels.items()}
 
     def weight_bytes(self) -> int:
         """Device bytes of everything this model holds of its checkpoint: the matrices (bf16, or e4m3 panels plus their scale
         vectors), biases, norm weights and scale-shift tables."""
-        seen, total = set(), 0
-
-        def add(t):
-            nonlocal total
-            if torch.is_tensor(t) and t.data_ptr() not in seen:
-                seen.add(t.data_ptr())
-                total += t.numel() * t.element_size()
-
-        for n in ("patchify", "t1", "t2", "ada", "c1", "c2", "out"):
-            for suf in ("_w", "_s", "_b"):
-                add(getattr(self, n + suf))
-        add(self.head_table); add(self.tables); add(self.wkn2_all)
-        for b in self.blocks:
-            for n in _Block.__slots__:
-                if n not in ("wkn2", "wqkn"):          # a row of wkn2_all; a copy of wqn | wkn made for one launch form
-                    add(getattr(b, n))
-        return total
+        held = [t for panel, _, _ in self._panels.values() for t in (panel.w, panel.scale, panel.bias) if t is not None]
+        held += [self.head_table, self.tables, self.wkn2_all]
+        held += [t for b in self.blocks for t in (b.wqn, b.wkn, b.wqn2)]     # (wkn2: a row of wkn2_all; wqkn: a copy of wqn | wkn)
+        once = {}                           # a packed panel is in the table once per key: each tensor counts once, as first seen
+        for t in held:
+            once.setdefault(t.data_ptr(), t)
+        return sum(t.numel() * t.element_size() for t in once.values())
 
     @staticmethod
     def expected_keys(cfg: LTXModelConfig) -> List[str]:
@@ -375,63 +385,70 @@ class LTXModel:
         return cls(config, cls.random_weights(config, device, seed), fuse=fuse)
 
     # ------------------------------------------------------------------ forward
-    def _w8a8_launch(self, M: int, N: int, K: int, kw: dict) -> bool:
-        """Whether the ops.gemm call (M,K) x (N,K)^T with keyword arguments ``kw`` runs W8A8: the feature is on and the
-        library would run the W8A16 call single-pass (ops.gemm_plan(w8=True))."""
-        if not self.fp8_activations or K % 128 != 0:
+    @property
+    def _split_k(self) -> bool:
+        """Whether a GEMM may split K: not in batch_invariant mode.  ``_gemm``, ``_plan`` and the W8A8 memo read it, nothing else."""
+        return not self.batch_invariant
+
+    def _w8a8_launch(self, M: int, lin: Linear, epilogue: int = ops.EPI_BIAS, n_split: int = 0, out_tokens_per_batch: int = 0,
+                     sumsq: Optional[torch.Tensor] = None, **_) -> bool:
+        """Whether the GEMM of ``lin`` over M rows with these keyword arguments runs W8A8: the feature is on and the library would
+        run the W8A16 call single-pass (ops.gemm_plan(w8=True)).  The named keywords are those of ops.gemm that decide the launch
+        form, with ops.gemm's defaults (keep them in step); the call's others (out, resid, gate ...) pass by, ops.gemm checks them."""
+        if not self.fp8_activations or lin.K % 128 != 0:
             return False
-        key = (M, N, K, kw.get("epilogue", ops.EPI_BIAS), kw.get("n_split", 0), kw.get("out_tokens_per_batch", 0),
-               kw.get("sumsq") is not None, kw.get("split_k", True))
+        key = (M, lin.N, lin.K, epilogue, n_split, out_tokens_per_batch, sumsq is not None, self._split_k)
         if key not in self._w8a8_plans:
-            self._w8a8_plans[key] = not ops.gemm_plan(M, N, K, epilogue=key[3], n_split=key[4], out_tokens_per_batch=key[5],
-                                                      sumsq=key[6], split_k=key[7], w8=True).split_k
+            self._w8a8_plans[key] = not self._plan(M, lin.N, lin.K, epilogue=epilogue, n_split=n_split, sumsq=key[6],
+                                                   out_tokens_per_batch=out_tokens_per_batch, w8=True).split_k
         return self._w8a8_plans[key]
 
-    def _quant_for(self, a: torch.Tensor, launches) -> Optional[tuple]:
-        """(a8, a_scale) of ``a`` if any of ``launches`` [(w, bias, kwargs)] runs W8A8, else None: one quantiser launch."""
-        if any(self._w8a8_launch(a.shape[0], w.shape[0], a.shape[1], kw) for w, _, kw in launches):
-            return ops.quant_rows_fp8(a)
-        return None
+    def _gemm(self, a: torch.Tensor, lin: Linear, a_q: Optional[tuple] = None, **kw) -> torch.Tensor:
+        """THE ops.gemm call of the model: ``lin`` over ``a``, or over its quantised twin ``a_q`` = (a8, a_scale) (W8A8).
+        Split-K as batch_invariant allows and the panel's own scale, for every launch."""
+        if a_q is not None:
+            a, kw["a_scale"] = a_q
+        return ops.gemm(a, lin.w, lin.bias, split_k=self._split_k, w_scale=lin.scale, **kw)
 
-    def _lin(self, a: torch.Tensor, q: Optional[tuple], launches, fresh: bool = True) -> None:
-        """The ops.gemm launches [(w, bias, kwargs)] over one input ``a``.  ``q`` = (a8, a_scale) buffers (None: fp8
-        activations off - exactly the ops.gemm calls): ``a`` is quantised into them by ONE launch if any of the launches runs
-        W8A8 (``fresh=False``: they already hold ``a`` quantised), and those launches read the quantised copy."""
-        use = [q is not None and self._w8a8_launch(a.shape[0], w.shape[0], a.shape[1], kw) for w, _, kw in launches]
+    def _plan(self, M: int, N: int, K: int, **kw) -> "ops.GemmPlan":
+        """ops.gemm_plan of a launch as ``_gemm`` issues it."""
+        return ops.gemm_plan(M, N, K, split_k=self._split_k, **kw)
+
+    def _lin(self, a: torch.Tensor, q: Optional[tuple], launches, fresh: bool = True) -> List[torch.Tensor]:
+        """The GEMM launches [(Linear, kwargs)] over one input ``a``.  ``q`` = (a8, a_scale) buffers (None: fp8 activations
+        off - exactly the ops.gemm calls): ``a`` is quantised into them by ONE launch if any of the launches runs W8A8
+        (``fresh=False``: they already hold ``a`` quantised), and those launches read the quantised copy."""
+        use = [q is not None and self._w8a8_launch(a.shape[0], lin, **kw) for lin, kw in launches]
         if fresh and any(use):
             ops.quant_rows_fp8(a, out=q)
-        for (w, bias, kw), u in zip(launches, use):
-            if u:
-                ops.gemm(q[0], w, bias, a_scale=q[1], **kw)
-            else:
-                ops.gemm(a, w, bias, **kw)
+        return [self._gemm(a, lin, q if u else None, **kw) for (lin, kw), u in zip(launches, use)]
+
+    def _linear(self, a: torch.Tensor, lin: Linear, q: Optional[tuple] = None, **kw) -> torch.Tensor:
+        """One Linear over ``a``: ``_lin`` with a single launch (without ``q`` it stays W8A16 / bf16)."""
+        return self._lin(a, q, [(lin, kw)])[0]
 
     def _prepare_context(self, context: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """ltx.py:77-89: caption_projection, (B,S,3840) -> (B*S,D)."""
         b, s, c = context.shape
-        sk = not self.batch_invariant
-        h = ops.gemm(context.reshape(b * s, c), self.c1_w, self.c1_b, epilogue=ops.EPI_BIAS_GELU, split_k=sk, w_scale=self.c1_s)
-        return ops.gemm(h, self.c2_w, self.c2_b, out=out, split_k=sk, w_scale=self.c2_s)
+        return self._linear(self._linear(context.reshape(b * s, c), self.c1, epilogue=ops.EPI_BIAS_GELU), self.c2, out=out)
 
     def _context_kv_launches(self, blk: _Block, k2, vt2, st, s: int):
-        """The text k | V^T GEMM launches of one block as [(w, bias, kwargs)] (one launch with a split output, or two)."""
-        D, sk = self.inner_dim, not self.batch_invariant
+        """The text k | V^T GEMM launches of one block as [(Linear, kwargs)] (one launch with a split output, or two)."""
+        D = self.inner_dim
         if self.fuse & 1:
-            return [(blk.wkv2, blk.bkv2, dict(out=k2, out2=vt2, n_split=D, out_tokens_per_batch=s, sumsq=st, split_k=sk, w_scale=blk.skv2))]
-        return [(blk.wkv2[:D], blk.bkv2[:D], dict(out=k2, sumsq=st, split_k=sk, w_scale=_rows(blk.skv2, None, D))),
-                (blk.wkv2[D:], blk.bkv2[D:], dict(out=vt2, out_tokens_per_batch=s, split_k=sk, w_scale=_rows(blk.skv2, D, None)))]
+            return [(blk.kv2, dict(out=k2, out2=vt2, n_split=D, out_tokens_per_batch=s, sumsq=st))]
+        return [(blk.kv2.rows(None, D), dict(out=k2, sumsq=st)), (blk.kv2.rows(D, None), dict(out=vt2, out_tokens_per_batch=s))]
 
-    def _context_kv(self, blk: _Block, ctx: torch.Tensor, b: int, s: int, sp: int, out: Optional[tuple] = None,
-                    ctx_q: Optional[tuple] = None):
+    def _context_kv_buffers(self, ctx: torch.Tensor, b: int, s: int, *lead: int) -> tuple:
+        """(k, V^T, sumsq) buffers of the text side of one block, or with ``lead`` = (L,) of all blocks."""
+        D = self.inner_dim
+        return (torch.empty((*lead, b * s, D), dtype=BF16, device=ctx.device), _vt_buffer(*lead, b, D, tokens=s, device=ctx.device),
+                torch.empty((*lead, b * s, D // 64), dtype=torch.float32, device=ctx.device))
+
+    def _context_kv(self, blk: _Block, ctx: torch.Tensor, b: int, s: int, out: Optional[tuple] = None, ctx_q: Optional[tuple] = None):
         """``ctx_q``: (ctx8, scale) - the context already quantised for the W8A8 launches (once per forward, not per block)."""
         D, H, eps = self.inner_dim, self.num_attention_heads, self.config.norm_eps
-        if out is None:
-            k2 = torch.empty((b * s, D), dtype=BF16, device=ctx.device)
-            vt2 = torch.zeros((b, D, sp), dtype=BF16, device=ctx.device) if sp != s else \
-                torch.empty((b, D, sp), dtype=BF16, device=ctx.device)
-            ss = torch.empty((b * s, D // 64), dtype=torch.float32, device=ctx.device)
-        else:
-            k2, vt2, ss = out
+        k2, vt2, ss = out if out is not None else self._context_kv_buffers(ctx, b, s)
         # k (row-major, with its per-row sums of squares) and V^T from one launch over the packed k|v panel
         st = ss if self.fuse & 2 else None
         self._lin(ctx, ctx_q, self._context_kv_launches(blk, k2, vt2, st, s), fresh=False)
@@ -441,32 +458,23 @@ class LTXModel:
     def _quant_context(self, ctx: torch.Tensor, s: int) -> Optional[tuple]:
         """The projected context quantised for the text k | V^T launches of ALL blocks (they share shapes, so one decision and
         one quantiser launch per forward), or None where those launches stay W8A16."""
-        if not self.fp8_activations:
-            return None
-        return self._quant_for(ctx, self._context_kv_launches(self.blocks[0], None, None, True if self.fuse & 2 else None, s))
+        launches = self._context_kv_launches(self.blocks[0], None, None, True if self.fuse & 2 else None, s)
+        return ops.quant_rows_fp8(ctx) if any(self._w8a8_launch(ctx.shape[0], lin, **kw) for lin, kw in launches) else None
 
     def _grouped_context_ok(self, b: int, s: int) -> bool:
         """Whether the grouped launch gives the bits of the per-block ``_context_kv`` calls: it is single-pass, as they are unless
         the library would split K at this row count (small M with the split-K scratch on offer)."""
         D = self.inner_dim
-        if not self.grouped_context_kv or (self.fuse & 3) != 3 or D % 256 != 0:
+        # (the grouped launch has no weight-fp8 form: an fp8 model goes per block - the same bits)
+        if not self.grouped_context_kv or (self.fuse & 3) != 3 or D % 256 != 0 or self.weight_dtype != BF16:
             return False
-        if self.weight_dtype != BF16:         # the grouped launch has no weight-fp8 form: per block (the same bits)
-            return False
-        return not ops.gemm_plan(b * s, 2 * D, D, n_split=D, out_tokens_per_batch=s, sumsq=True,
-                                 split_k=not self.batch_invariant).split_k
+        return not self._plan(b * s, 2 * D, D, n_split=D, out_tokens_per_batch=s, sumsq=True).split_k
 
-    def _context_kv_all(self, ctx: torch.Tensor, b: int, s: int, sp: int, out: Optional[tuple] = None):
+    def _context_kv_all(self, ctx: torch.Tensor, b: int, s: int, out: Optional[tuple] = None):
         """``_context_kv`` of every block at once: one grouped GEMM launch over the L packed k|v panels into (L, ...) buffers and
-        one k-norm launch over them.  Returns (k (L,b*s,D), V^T (L,b,D,sp), sumsq (L,b*s,D/64)); block li reads index li."""
-        D, H, eps, L = self.inner_dim, self.num_attention_heads, self.config.norm_eps, len(self.blocks)
-        if out is None:
-            k2 = torch.empty((L, b * s, D), dtype=BF16, device=ctx.device)
-            vt2 = torch.zeros((L, b, D, sp), dtype=BF16, device=ctx.device) if sp != s else \
-                torch.empty((L, b, D, sp), dtype=BF16, device=ctx.device)
-            ss = torch.empty((L, b * s, D // 64), dtype=torch.float32, device=ctx.device)
-        else:
-            k2, vt2, ss = out
+        one k-norm launch over them.  Returns (k (L,b*s,D), V^T (L,b,D,s padded to 64), sumsq (L,b*s,D/64)); block li reads index li."""
+        D, H, eps = self.inner_dim, self.num_attention_heads, self.config.norm_eps
+        k2, vt2, ss = out if out is not None else self._context_kv_buffers(ctx, b, s, len(self.blocks))
         ops.gemm_grouped(ctx, self.wkv2_table, self.bkv2_table, 2 * D, out=k2, out2=vt2, n_split=D, out_tokens_per_batch=s, sumsq=ss)
         ops.qknorm_grouped(k2, self.wkn2_all, H, eps, ss)
         return k2, vt2, ss
@@ -477,19 +485,16 @@ class LTXModel:
         change, always reported separately).  ``out``: refresh an existing object in place."""
         context = context.to(BF16).contiguous()
         b, s, _ = context.shape
-        sp = (s + 63) // 64 * 64
         kv = out if out is not None else ContextKV(context.shape)
         if kv.shape != tuple(context.shape):
             raise ValueError(f"ContextKV was built for context {kv.shape}, got {tuple(context.shape)}")
         kv.ctx = self._prepare_context(context, kv.ctx)
         if self._grouped_context_ok(b, s):
-            k2, vt2, ss = self._context_kv_all(kv.ctx, b, s, sp, kv.stacked)
-            kv.stacked = (k2, vt2, ss)
+            kv.stacked = k2, vt2, ss = self._context_kv_all(kv.ctx, b, s, kv.stacked)
             kv.kv = [(k2[i], vt2[i], ss[i]) for i in range(len(self.blocks))]
             return kv
         ctx_q = self._quant_context(kv.ctx, s)
-        new = [self._context_kv(blk, kv.ctx, b, s, sp, kv.kv[i] if kv.kv else None, ctx_q) for i, blk in enumerate(self.blocks)]
-        kv.kv = new
+        kv.kv = [self._context_kv(blk, kv.ctx, b, s, kv.kv[i] if kv.kv else None, ctx_q) for i, blk in enumerate(self.blocks)]
         kv.stacked = None
         return kv
 
@@ -526,13 +531,12 @@ class LTXModel:
         # Row statistics travel with the residual stream: every GEMM that writes x also emits the per-row sums of
         # squares of what it stored (64-column partials), so the rms_norm that follows does not re-reduce the row.
         P = D // 64
-        sk = not self.batch_invariant
         xss = torch.empty((M, P), dtype=torch.float32, device=dev)
-        x = ops.gemm(latent.reshape(M, C), self.patchify_w, self.patchify_b, sumsq=xss, split_k=sk, w_scale=self.patchify_s)
+        x = self._linear(latent.reshape(M, C), self.patchify, sumsq=xss)
         tproj = ops.timestep_embed(plan.values, 256, float(cfg.timestep_scale_multiplier))
-        h = ops.gemm(tproj, self.t1_w, self.t1_b, epilogue=ops.EPI_BIAS_SILU, split_k=sk, w_scale=self.t1_s)
-        emb = ops.gemm(h, self.t2_w, self.t2_b, split_k=sk, w_scale=self.t2_s)               # embedded_timestep (U,D)
-        ada = ops.gemm(ops.silu(emb), self.ada_w, self.ada_b, split_k=sk, w_scale=self.ada_s)   # (U,6D)
+        h = self._linear(tproj, self.t1, epilogue=ops.EPI_BIAS_SILU)
+        emb = self._linear(h, self.t2)                     # embedded_timestep (U,D)
+        ada = self._linear(ops.silu(emb), self.ada)        # (U,6D)
         # (L,U,6,D): shift, 1+scale, gate, shift, 1+scale, gate - the (1 + scale) factor is the same for every token of a row
         # (without the carried row statistics the self-reducing norm kernel takes the raw scale and adds 1 itself)
         mods = ops.ada_combine(self.tables, ada, cfg.num_layers, U, 6, D, one_plus_mask=0b010010 if self.fuse & 2 else 0)
@@ -545,10 +549,7 @@ class LTXModel:
         else:
             ctx = self._prepare_context(context)
 
-        np64 = (N + 63) // 64 * 64
-        sp64 = (S + 63) // 64 * 64
-        vt = torch.zeros((B, D, np64), dtype=BF16, device=dev) if np64 != N else \
-            torch.empty((B, D, np64), dtype=BF16, device=dev)
+        vt = _vt_buffer(B, D, tokens=N, device=dev)
         qk = torch.empty((M, 2 * D), dtype=BF16, device=dev)
         qkss = torch.empty((M, 2 * P), dtype=torch.float32, device=dev)
         nx = torch.empty((M, D), dtype=BF16, device=dev)
@@ -575,12 +576,12 @@ class LTXModel:
             # 1.264 ms per block - forked graph branches cost more than they overlap; one GRID for two independent GEMMs (q|k
             # on 320x256 tiles with v's 160x256 tiles back-filling behind them; text k|v with q2): 1269.6 us per block either way.
             if self._grouped_context_ok(B, S):
-                kv_all = self._context_kv_all(ctx, B, S, sp64)
+                kv_all = self._context_kv_all(ctx, B, S)
             else:
-                ctx_q = self._quant_context(ctx, S)            # once per forward: every block's text k | V^T launch reads it             # per block, one buffer set (the library would split K here, or the fused forms are off)
-                kv_buf = (torch.empty((B * S, D), dtype=BF16, device=dev),
-                          torch.zeros((B, D, sp64), dtype=BF16, device=dev) if sp64 != S else torch.empty((B, D, sp64), dtype=BF16, device=dev),
-                          torch.empty((B * S, D // 64), dtype=torch.float32, device=dev))
+                # per block (the library would split K here, or the fused forms are off): the context is quantised once per
+                # forward - every block's text k | V^T launch reads it - and the blocks share one buffer set
+                ctx_q = self._quant_context(ctx, S)
+                kv_buf = self._context_kv_buffers(ctx, B, S)
 
         skip_rows = [[] for _ in self.blocks]          # per block: the batch rows whose self-attention is skipped (STG)
         if perturbations is not None:
@@ -602,54 +603,52 @@ class LTXModel:
             # with q|k|v as ONE launch (M=1296: 39.4 against 41.2 ms, 3328: 87.6 / 89.2, 5184: 141.5 / 143.8, 6656: 161.5 / 164.7;
             # scripts/exp_qkv_one_launch.py), and at small M every launch is a weight stream with ~5 us of fixed cost)
             if fq and (not (self.fuse & 8) or M <= ops.SPLITK_MAX_M or M % 320 != 0):
-                self._lin(nx, nx_q, [(blk.wqkv, blk.bqkv, dict(out=qk, out2=vt, n_split=2 * D, out_tokens_per_batch=N, sumsq=s_qk, split_k=sk,
-                                                               w_scale=blk.sqkv))])
+                self._linear(nx, blk.qkv, nx_q, out=qk, out2=vt, n_split=2 * D, out_tokens_per_batch=N, sumsq=s_qk)
             else:
-                self._lin(nx, nx_q, [(blk.wqkv[:2 * D], blk.bqkv[:2 * D], dict(out=qk, sumsq=s_qk, split_k=sk, w_scale=_rows(blk.sqkv, None, 2 * D))),
-                                     (blk.wqkv[2 * D:], blk.bqkv[2 * D:], dict(out=vt, out_tokens_per_batch=N, split_k=sk, w_scale=_rows(blk.sqkv, 2 * D, None)))])
+                self._lin(nx, nx_q, [(blk.qkv.rows(None, 2 * D), dict(out=qk, sumsq=s_qk)),
+                                     (blk.qkv.rows(2 * D, None), dict(out=vt, out_tokens_per_batch=N))])
             skip = skip_rows[li]
+            # the q side of the two attentions: raw q with its row statistics, normalised (and rotated) inside the kernel - or
+            # q normalised by a launch of its own in front
             if fp:
                 ops.qknorm_rope(qk[:, D:], 1, D, blk.wkn, cos, sin, N, H, eps, sumsq=qkss[:, P:])
+                fused1, fused2 = dict(q_norm_weight=blk.wqn, cos=cos, sin=sin, eps=eps), dict(q_sumsq=q2ss, q_norm_weight=blk.wqn2, eps=eps)
             else:
                 ops.qknorm_rope(qk, 2, D, blk.wqkn, cos, sin, N, H, eps, sumsq=s_qk)
+                fused1 = fused2 = {}
             # attention over each maximal run of rows that keep it (all B rows in one launch when nothing is skipped)
             for r0, r1 in _runs(B, skip):
                 t0, t1 = r0 * N, r1 * N
-                if fp:
-                    ops.flash_attn(qk[t0:t1, :D], qk[t0:t1, D:], vt[r0:r1], att[t0:t1], r1 - r0, H, N, N, scale,
-                                   q_sumsq=qkss[t0:t1], q_norm_weight=blk.wqn, cos=cos, sin=sin, eps=eps, tail_split=ts_)
-                else:
-                    ops.flash_attn(qk[t0:t1, :D], qk[t0:t1, D:], vt[r0:r1], att[t0:t1], r1 - r0, H, N, N, scale, tail_split=ts_)
+                ops.flash_attn(qk[t0:t1, :D], qk[t0:t1, D:], vt[r0:r1], att[t0:t1], r1 - r0, H, N, N, scale,
+                               q_sumsq=qkss[t0:t1] if fp else None, tail_split=ts_, **fused1)
             if skip:          # STG: the skipped rows' attention output is their value projection, v = (V^T)^T
                 ops.attn_value_passthrough(vt, att, B, N, sum(1 << r for r in skip))
-            self._lin(att, att_q, [(blk.wo, blk.bo, dict(epilogue=ops.EPI_BIAS_GATE_RES, out=x, resid=x,
-                                                         gate=mod[:, 2], gate_row=tok2row, gate_stride=ms, sumsq=s_x, split_k=sk, w_scale=blk.so))])
+            self._linear(att, blk.o, att_q, epilogue=ops.EPI_BIAS_GATE_RES, out=x, resid=x,
+                         gate=mod[:, 2], gate_row=tok2row, gate_stride=ms, sumsq=s_x)
             # text cross-attention (transformer.py:257-261)
             ops.rmsnorm_modulate(x, eps, out=nx, sumsq=s_x)
-            self._lin(nx, nx_q, [(blk.wq2, blk.bq2, dict(out=q2, sumsq=s_q2, split_k=sk, w_scale=blk.sq2))])
+            self._linear(nx, blk.q2, nx_q, out=q2, sumsq=s_q2)
             if ctx_kv is not None:
                 kv = ctx_kv.kv[li]
             elif kv_all is not None:
                 kv = (kv_all[0][li], kv_all[1][li], kv_all[2][li])
             else:
-                kv = self._context_kv(blk, ctx, B, S, sp64, kv_buf, ctx_q)
-            if fp:
-                ops.flash_attn(q2, kv[0], kv[1], att, B, H, N, S, scale, q_sumsq=q2ss, q_norm_weight=blk.wqn2, eps=eps, tail_split=ts_)
-            else:
+                kv = self._context_kv(blk, ctx, B, S, kv_buf, ctx_q)
+            if not fp:
                 ops.qknorm_rope(q2, 1, D, blk.wqn2, None, None, N, H, eps, sumsq=s_q2)
-                ops.flash_attn(q2, kv[0], kv[1], att, B, H, N, S, scale, tail_split=ts_)
-            self._lin(att, att_q, [(blk.wo2, blk.bo2, dict(epilogue=ops.EPI_BIAS_RES, out=x, resid=x, sumsq=s_x, split_k=sk, w_scale=blk.so2))])
+            ops.flash_attn(q2, kv[0], kv[1], att, B, H, N, S, scale, tail_split=ts_, **fused2)
+            self._linear(att, blk.o2, att_q, epilogue=ops.EPI_BIAS_RES, out=x, resid=x, sumsq=s_x)
             # feed-forward (transformer.py:343-347)
             ops.rmsnorm_modulate(x, eps, mod[:, 4], mod[:, 3], ms, tok2row, out=nx, sumsq=s_x, scale_is_one_plus=bool(fs))
-            self._lin(nx, nx_q, [(blk.w1, blk.b1, dict(epilogue=ops.EPI_BIAS_GELU, out=hff, split_k=sk, w_scale=blk.s1))])
-            self._lin(hff, hff_q, [(blk.w2, blk.b2, dict(epilogue=ops.EPI_BIAS_GATE_RES, out=x, resid=x,
-                                                        gate=mod[:, 5], gate_row=tok2row, gate_stride=ms, sumsq=s_x, split_k=sk, w_scale=blk.s2))])
+            self._linear(nx, blk.ff1, nx_q, epilogue=ops.EPI_BIAS_GELU, out=hff)
+            self._linear(hff, blk.ff2, hff_q, epilogue=ops.EPI_BIAS_GATE_RES, out=x, resid=x,
+                         gate=mod[:, 5], gate_row=tok2row, gate_stride=ms, sumsq=s_x)
             if hidden is not None:
                 hidden.append(x.reshape(B, N, D).clone())
 
         # --- output head (ltx.py:432-457) ---
         ops.layernorm_modulate(x, eps, head[:, 1], head[:, 0], 2 * D, tok2row, out=nx)
-        v = ops.gemm(nx, self.out_w, self.out_b, split_k=sk, w_scale=self.out_s)
+        v = self._linear(nx, self.out)
         return v.reshape(B, N, cfg.out_channels)
 
     def __call__(self, video: Optional[Modality] = None, audio: Optional[Modality] = None,

@@ -7,7 +7,7 @@ import pytest
 import torch
 
 import parity
-from test_gemm_plan_cpu import dit_launches
+from dit_launches import dit_launches
 
 pytestmark = pytest.mark.gpu
 BF = torch.bfloat16

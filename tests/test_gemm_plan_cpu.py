@@ -6,6 +6,8 @@ import os
 
 import pytest
 
+from dit_launches import dit_launches
+
 D = 4096
 MODEL_NK = [(3 * D, D), (2 * D, D), (D, D), (4 * D, D), (D, 4 * D), (6 * D, D), (D, 3840), (D, 256), (D, 128), (128, D)]
 AWKWARD_NK = [(1000, 64 * 67), (4104, 64 * 67), (2056, 64 * 40), (8, 64 * 512), (520, 64 * 97), (12288, 64 * 9)]
@@ -21,30 +23,6 @@ def ops():
         ge.build()
     from mlx_video_amd import ops
     return ops
-
-
-def dit_launches(ops, B, T, S=64, D=D, caption=3840):
-    """(name, M, N, K, gemm options) of every ops.gemm of one LTXModel.forward_tokens (fuse=15, one timestep row) with B
-    batch rows of T video tokens and S text tokens; "qk" / "v" are the two launches of fuse without bit 1 (or with bit 8)."""
-    M, Mc = B * T, B * S
-    return [("patchify", M, D, 128, dict(sumsq=True)),
-            ("caption1", Mc, D, caption, dict(epilogue=ops.EPI_BIAS_GELU)),
-            ("caption2", Mc, D, D, {}),
-            ("text_kv", Mc, 2 * D, D, dict(n_split=D, out_tokens_per_batch=S, sumsq=True)),
-            ("text_k", Mc, D, D, dict(sumsq=True)),
-            ("text_v", Mc, D, D, dict(out_tokens_per_batch=S)),
-            ("timestep1", 1, D, 256, dict(epilogue=ops.EPI_BIAS_SILU)),
-            ("timestep2", 1, D, D, {}),
-            ("adaln", 1, 6 * D, D, {}),
-            ("qkv", M, 3 * D, D, dict(n_split=2 * D, out_tokens_per_batch=T, sumsq=True)),
-            ("qk", M, 2 * D, D, dict(sumsq=True)),
-            ("v", M, D, D, dict(out_tokens_per_batch=T)),
-            ("out", M, D, D, dict(epilogue=ops.EPI_BIAS_GATE_RES, sumsq=True)),
-            ("q2", M, D, D, dict(sumsq=True)),
-            ("o2", M, D, D, dict(epilogue=ops.EPI_BIAS_RES, sumsq=True)),
-            ("ff1", M, 4 * D, D, dict(epilogue=ops.EPI_BIAS_GELU)),
-            ("ff2", M, D, 4 * D, dict(epilogue=ops.EPI_BIAS_GATE_RES, sumsq=True)),
-            ("proj_out", M, 128, D, {})]
 
 
 def _check_split_plan(ops, pl, M, N, K, ws_bytes):
