@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define LTXK_VERSION 407
+#define LTXK_VERSION 408
 
 #define LTXK_OK 0
 #define LTXK_EINVAL (-1)   /* bad argument (shape / alignment / null pointer) */
@@ -391,6 +391,62 @@ int ltxk_step_scalars(const void* ts_all, const float* sig_all, int32_t* step, v
  * out = bf16(x0 + sigma_next*(x - x0)/sigma) in fp32; n elements, any layout.             */
 int ltxk_euler_step(const void* latent, const void* denoised, void* out, int64_t n,
                     float sigma, float sigma_next, void* stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Text stage: from the hidden states of a Gemma-3 forward to the DiT's context.  norm_and_concat_hidden_states
+ * (text_encoder.py:591-639) and the row operations of Embeddings1DConnector (text_encoder.py:271-587) at widths the
+ * DiT's row kernels do not take (D = 3840, H = 30).  The GEMMs and the attention of the connector are ltxk_gemm_bf16
+ * and ltxk_flash_attn.  Gemma itself is not part of this library.
+ *
+ * The layer stack is ONE base pointer with explicit strides (in elements): element (l, b, t, d) of the L hidden states
+ * is x[l*layer_stride + b*batch_stride + t*row_stride + d].  A caller that holds the layers as separately allocated
+ * tensors stacks them first.  x 16-byte aligned; D and every stride a multiple of 8; L*B <= 65535.
+ * Batch row b's valid tokens are the rows [row_start[b], row_start[b] + row_count[b]) (device int32 arrays; left padding:
+ * row_start = T - row_count); a range that leaves [0, T) is clipped to it.  Rows outside are never read.
+ * ------------------------------------------------------------------------------------- */
+
+/* stats[(b*L + l)*3 + {0,1,2}] = fp32 {sum, min, max} over the valid rows x D of layer l, batch row b.  min and max are
+ * exact.  Two launches of fixed shape, no floating-point atomics: 64 workgroups per (b, l) each reduce a contiguous run of
+ * ceil(count/64) rows (8 running sums per thread, then fixed trees), one wave per (b, l) then sums the 64 partials; a
+ * term passes through at most ceil(ceil(count/64) * D/8 / 256) + 17 additions (47 at count = 1024, D = 3840), and the
+ * result of a (b, l) pair does not depend on what else the launch holds.  row_count[b] == 0 writes {0, 0, 0}.
+ * partials: caller-owned scratch of L*B*192 floats.                                        */
+int ltxk_masked_layer_stats(const void* x, int64_t layer_stride, int64_t batch_stride, int64_t row_stride,
+                            const int32_t* row_start, const int32_t* row_count, int32_t L, int32_t B, int32_t T,
+                            int32_t D, float* partials, float* stats, void* stream);
+
+/* out[(row0[b] + t)*ldo + l*D + d] = bf16(8 * (x[l,b,row_start[b]+t,d] - mean) / ((max - min) + 1e-6)) for t < row_count[b],
+ * mean = sum / (row_count[b]*D + 1e-6), with `stats` as written by ltxk_masked_layer_stats: all in fp32, one rounding to
+ * bf16 at the store.  The matrix is compact - `rows` = sum of the counts, row0 (B) their exclusive prefix sums (device
+ * int32) - and LAYER-major: column l*D + d, where the reference's concatenation is d*L + l; the aggregate_embed panel
+ * that multiplies it has its K axis permuted to match, once, when it is loaded.  Padded rows are neither read nor
+ * written (the reference zeroes them and then replaces them by registers).  ldo >= L*D, a multiple of 8.              */
+int ltxk_layer_norm_compact(const void* x, int64_t layer_stride, int64_t batch_stride, int64_t row_stride,
+                            const int32_t* row_start, const int32_t* row_count, const int32_t* row0, const float* stats,
+                            void* out, int64_t ldo, int32_t L, int32_t B, int32_t T, int32_t D, int32_t rows,
+                            void* stream);
+
+/* rms_norm with unit weight (utils.py:398-400) for rows of any width D % 8 == 0, D <= 8192: y = bf16(x * rsqrt(mean(x^2) + eps)),
+ * one pass with the row in registers.  x (M,D) row stride ldx, y (M,D) row stride ldy (y may be x).                  */
+int ltxk_rmsnorm_rows(const void* x, int32_t ldx, void* y, int32_t ldy, int32_t M, int32_t D, float eps, void* stream);
+
+/* ltxk_qknorm_rope for any head count: in place on the q | k halves (columns [0,D) and [D,2D)) of buf (M, ld >= 2D):
+ * RMSNorm over the full D with weight row 0 / 1 of `weight` (2,D) bf16, then the SPLIT rotation over each 128-wide head
+ * with cos/sin (H,T,64) fp32, row m at position m % T (text_encoder.py:308-363).  D == 128*H, 1 <= H <= 64; the kernel
+ * reduces the row itself.  Rounding points are those of ltxk_qknorm_rope.  Columns past 2D are not touched.            */
+int ltxk_qknorm_rope_1d(void* buf, int32_t ld, int32_t M, int32_t D, const void* weight, const float* cos,
+                        const float* sin, int32_t T, int32_t H, float eps, void* stream);
+
+/* In-place exact GELU (nn.gelu, text_encoder.py:388): x = bf16(x * (1 + erf(x / sqrt 2)) / 2) evaluated in fp32 as
+ * (x/2) * erfc(-x / sqrt 2), which keeps its relative accuracy on the negative side.  n elements, x 16-byte aligned.  */
+int ltxk_gelu_erf(void* x, int64_t n, void* stream);
+
+/* The connector's input (text_encoder.py:510-563): out (B,T,D); row t < row_count[b] is row row0[b] + t of the compact
+ * feature matrix feat (feat_rows, ldf), row t >= row_count[b] is registers[t % R] (registers (R,D) bf16): the valid tokens
+ * moved to the front, the learnable registers tiled over the sequence behind them.  Bit-exact copies.                 */
+int ltxk_connector_assemble(const void* feat, int32_t ldf, const void* registers, const int32_t* row0,
+                            const int32_t* row_count, void* out, int32_t B, int32_t T, int32_t D, int32_t R,
+                            int32_t feat_rows, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * Video VAE (volumes are channels-last (B,D,H,W,C) bf16; a row = one voxel)

@@ -164,6 +164,17 @@ SIGNATURES = {
                                               c_void_p]),
     "ltxk_cfg_euler_step": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32,
                                       c_int32, c_float, c_float, c_float, c_int32, c_void_p]),
+    # text stage (csrc/text_ops.hip)
+    "ltxk_masked_layer_stats": (c_int32, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int32, c_int32, c_int32,
+                                          c_int32, c_void_p, c_void_p, c_void_p]),
+    "ltxk_layer_norm_compact": (c_int32, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                          c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p]),
+    "ltxk_rmsnorm_rows": (c_int32, [c_void_p, c_int32, c_void_p, c_int32, c_int32, c_int32, c_float, c_void_p]),
+    "ltxk_qknorm_rope_1d": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_int32,
+                                      c_float, c_void_p]),
+    "ltxk_gelu_erf": (c_int32, [c_void_p, c_int64, c_void_p]),
+    "ltxk_connector_assemble": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32,
+                                          c_int32, c_int32, c_void_p]),
 }
 
 # ltxk_abi_sizeof(i) is the size of ABI_STRUCTS[i]

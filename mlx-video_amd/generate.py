@@ -157,6 +157,39 @@ def _encode_conditionings(items, encoder: Optional[VideoEncoder], height: int, w
     return out
 
 
+def _layer_stack(hs) -> torch.Tensor:
+    """(L,B,T,D) from a stack, a list of (B,T,D) layers, or the batchless (L,T,D) a file holds."""
+    x = torch.stack(list(hs), 0) if isinstance(hs, (list, tuple)) else hs
+    if x.dim() == 3:
+        x = x[:, None]
+    if x.dim() != 4:
+        raise ValueError(f"gemma hidden states must be (L,B,T,D), (L,T,D) or a list of L (B,T,D) tensors, got {tuple(x.shape)}")
+    return x
+
+
+def _connect_gemma(hs, mask, neg_hs, neg_mask, text_connector, model_repo, dev):
+    """(prompt_embeds, negative_prompt_embeds or None) from Gemma hidden states: one TextConnector call, B = 2 with a negative."""
+    if mask is None or (neg_hs is not None and neg_mask is None):
+        raise ValueError("gemma_hidden_states need their gemma_attention_mask (and the negative pair its own)")
+    if text_connector is None:
+        if model_repo is None:
+            raise ValueError("gemma_hidden_states were given without a text connector: pass text_connector= (a TextConnector) or a "
+                             "model_repo whose checkpoint holds the connector weights")
+        from .text_connector import TextConnector
+        from .weights import text_connector_weights
+        root = Path(model_repo)
+        files = [f for f in sorted(root.glob("*.safetensors")) if "upscaler" not in f.name and "upsampler" not in f.name]
+        text_connector = TextConnector(text_connector_weights(files + sorted((root / "connectors").glob("*.safetensors")), dev))
+    x, m = _layer_stack(hs).to(dev), mask.reshape(-1, mask.shape[-1]).to(dev)
+    if neg_hs is None:
+        return text_connector(x, m), None
+    nx, nm = _layer_stack(neg_hs).to(dev), neg_mask.reshape(-1, neg_mask.shape[-1]).to(dev)
+    if nx.shape != x.shape or x.shape[1] != 1:
+        raise ValueError(f"positive and negative gemma hidden states must both be (L,1,T,D) of one shape, got {tuple(x.shape)} and {tuple(nx.shape)}")
+    out = text_connector(torch.cat([x, nx], 1), torch.cat([m, nm], 0))
+    return out[0:1], out[1:2]
+
+
 def generate_video(model_repo: Optional[str] = None, text_encoder_repo: Optional[str] = None, prompt: str = "",
                    pipeline: PipelineType = PipelineType.DISTILLED, negative_prompt: str = DEFAULT_NEGATIVE_PROMPT,
                    height: int = 512, width: int = 512, num_frames: int = 33, num_inference_steps: int = 40,
@@ -179,7 +212,9 @@ def generate_video(model_repo: Optional[str] = None, text_encoder_repo: Optional
                    return_latents: bool = False, lora_in_place: Optional[bool] = None,
                    hoist_context: bool = False, stg_scale: Optional[float] = None, stg_blocks: Optional[list] = None,
                    stg_mode: Optional[str] = None, enable_fp8: bool = False, fp8_scaling: str = "channel",
-                   fp8_activations: bool = False) -> np.ndarray:
+                   fp8_activations: bool = False, gemma_hidden_states=None, gemma_attention_mask: Optional[torch.Tensor] = None,
+                   negative_gemma_hidden_states=None, negative_gemma_attention_mask: Optional[torch.Tensor] = None,
+                   text_connector=None) -> np.ndarray:
     """See the module docstring.  Returns uint8 frames (F,H,W,3) (generate.py:4195-4197).
     ``hoist_context`` (not in the reference, off by default): the part of the forward that depends on the text context only -
     caption projection and the 48 cross-attention K / V^T projections, 3.37 TFLOP that the reference recomputes in every forward
@@ -194,7 +229,11 @@ def generate_video(model_repo: Optional[str] = None, text_encoder_repo: Optional
     bf16 and the merged weights quantised (never merged into fp8 panels), so a LoRA-merged stage-2 transformer is a fresh fp8
     model.  A ``transformer=`` / ``stage2_transformer=`` passed in is used as it is.
     ``fp8_activations`` (--fp8-activations; needs ``enable_fp8``, a ValueError without it): the transformers this call builds also
-    quantise the inputs of their in-block Linear layers to e4m3 per row and multiply fp8 x fp8 (ltxk_gemm_w8a8)."""
+    quantise the inputs of their in-block Linear layers to e4m3 per row and multiply fp8 x fp8 (ltxk_gemm_w8a8).
+    ``gemma_hidden_states`` / ``gemma_attention_mask`` (and the ``negative_`` pair): the text route that starts behind Gemma -
+    the L hidden states of a Gemma-3 forward ((L,1,T,D) stack or list of L (1,T,D)) and its left-padded 0/1 mask (1,T); the
+    feature extractor and the video embeddings connector run here (``text_connector=`` a ``TextConnector``, or loaded from
+    ``model_repo``), positive and negative prompt as one B = 2 call.  ``prompt_embeds`` wins when both are given."""
     t_start = time.perf_counter()
     if isinstance(pipeline, str):
         pipeline = PipelineType(pipeline)
@@ -299,10 +338,14 @@ def generate_video(model_repo: Optional[str] = None, text_encoder_repo: Optional
     if noise_fn is None:
         noise_fn = _default_noise_fn(seed, dev)
 
+    if prompt_embeds is None and gemma_hidden_states is not None:
+        prompt_embeds, negative_prompt_embeds = _connect_gemma(gemma_hidden_states, gemma_attention_mask, negative_gemma_hidden_states,
+                                                               negative_gemma_attention_mask, text_connector, model_repo, dev)
     if prompt_embeds is None:
         if text_encoder is None:
             raise ValueError("prompt_embeds is required: the Gemma-3 text encoder is outside this package "
-                             "(SURVEY.md §2a #17); pass prompt_embeds=(1,1024,3840) or text_encoder=callable")
+                             "(SURVEY.md §2a #17); pass prompt_embeds=(1,1024,3840) or text_encoder=callable, or the hidden states "
+                             "of a Gemma-3 forward as gemma_hidden_states= / gemma_attention_mask=")
         prompt_embeds = text_encoder(prompt)
         negative_prompt_embeds = text_encoder(negative_prompt)
     ctx_pos = prompt_embeds.to(dev).to(BF16)
@@ -517,6 +560,10 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--profile-json", type=str, default=None)
     ap.add_argument("--prompt-embeds", type=str, default=None, help=".pt/.npy file with (1,1024,3840) text embeddings")
     ap.add_argument("--negative-prompt-embeds", type=str, default=None)
+    ap.add_argument("--gemma-hidden-states", type=str, default=None,
+                    help="(not in the reference CLI) .pt/.safetensors file with `hidden_states` (L,T,D) or (L,1,T,D) - the hidden states of a "
+                         "Gemma-3 forward - and `attention_mask` (T), left-padded; the feature extractor and the connector of --model-repo run here")
+    ap.add_argument("--negative-gemma-hidden-states", type=str, default=None, help="the same for the negative prompt")
     ap.add_argument("--synthetic", action="store_true", help="random-init weights + random text embeddings (no checkpoints offline)")
     ap.add_argument("--layers", type=int, default=48)
     # spatio-temporal guidance (the reference's spellings and defaults; it ignores them, this port runs them)
@@ -572,6 +619,27 @@ def resolve_cli_heuristics(args, env=None):
     return args
 
 
+def load_gemma_hidden_states(path: str):
+    """--gemma-hidden-states FILE: a .pt (torch.save of a dict, read with weights_only=True) or .safetensors file with
+    `hidden_states` (L,T,D) or (L,1,T,D) and `attention_mask` (T) or (1,T) -> ((L,1,T,D), (1,T))."""
+    if str(path).endswith(".safetensors"):
+        from safetensors.torch import load_file
+        d = load_file(str(path))
+    else:
+        d = torch.load(path, weights_only=True)
+    if not isinstance(d, dict) or "hidden_states" not in d or "attention_mask" not in d:
+        raise ValueError(f"{path}: expected `hidden_states` and `attention_mask` tensors")
+    hs, mask = d["hidden_states"], d["attention_mask"]
+    if hs.dim() == 3:
+        hs = hs[:, None]
+    if hs.dim() != 4 or hs.shape[1] != 1:
+        raise ValueError(f"{path}: hidden_states must be (L,T,D) or (L,1,T,D), got {tuple(hs.shape)}")
+    mask = mask.reshape(1, -1)
+    if mask.shape[1] != hs.shape[2]:
+        raise ValueError(f"{path}: attention_mask has {mask.shape[1]} positions, hidden_states {hs.shape[2]}")
+    return hs, mask
+
+
 def main(argv: Optional[Sequence[str]] = None) -> None:
     args = resolve_cli_heuristics(build_parser().parse_args(argv))
     if args.fp8_activations and not args.enable_fp8:
@@ -611,6 +679,10 @@ def main(argv: Optional[Sequence[str]] = None) -> None:
             kw["prompt_embeds"] = _load(args.prompt_embeds)
         if args.negative_prompt_embeds:
             kw["negative_prompt_embeds"] = _load(args.negative_prompt_embeds)
+        if args.gemma_hidden_states:
+            kw["gemma_hidden_states"], kw["gemma_attention_mask"] = load_gemma_hidden_states(args.gemma_hidden_states)
+        if args.negative_gemma_hidden_states:
+            kw["negative_gemma_hidden_states"], kw["negative_gemma_attention_mask"] = load_gemma_hidden_states(args.negative_gemma_hidden_states)
     generate_video(model_repo=args.model_repo, prompt=args.prompt, pipeline=PipelineType(args.pipeline),
                    negative_prompt=args.negative_prompt, height=args.height, width=args.width, num_frames=args.num_frames,
                    num_inference_steps=args.steps, cfg_scale=args.cfg_scale, seed=args.seed, fps=args.fps,

@@ -607,3 +607,125 @@ def resize_area(x: torch.Tensor, oh: int, ow: int) -> torch.Tensor:
     out = torch.empty(tuple(x.shape[:-2]) + (oh, ow), dtype=BF16, device=x.device)
     check(_lib.load().ltxk_resize_area(_p(x), int(x.dtype == torch.float32), _p(out), planes, H, W, oh, ow, _stream()), "ltxk_resize_area")
     return out
+
+
+# ------------------------------------------------------------------------------------------- text stage (csrc/text_ops.hip)
+STATS_PARTIALS = 64          # workgroups per (batch row, layer) of ltxk_masked_layer_stats' first stage
+STATS_THREADS = 256          # threads of one of them; a thread keeps 8 running sums
+
+
+def layer_stats_depth(count: int, D: int) -> int:
+    """The longest chain of fp32 additions a term of ltxk_masked_layer_stats' sum passes through (include/ltxk.h): the
+    running sum of a thread's element slot, then the fixed trees 8 slots -> 64 lanes -> 4 waves -> 64 partials."""
+    rows = -(-count // STATS_PARTIALS)
+    return -(-rows * (D // 8) // STATS_THREADS) + 3 + 6 + 2 + 6
+
+
+def _req_layers(x: torch.Tensor, row_start: torch.Tensor, row_count: torch.Tensor, who: str):
+    _req(x, BF16, f"{who}.x")
+    _req(row_start, torch.int32, f"{who}.row_start"); _req(row_count, torch.int32, f"{who}.row_count")
+    if x.dim() != 4 or x.stride(3) != 1:
+        raise ValueError(f"{who}: x must be an (L,B,T,D) stack with unit inner stride, got {tuple(x.shape)} strides {x.stride()}")
+    L, B, T, D = x.shape
+    if tuple(row_start.shape) != (B,) or tuple(row_count.shape) != (B,) or not row_start.is_contiguous() or not row_count.is_contiguous():
+        raise ValueError(f"{who}: row_start / row_count must be contiguous ({B},) vectors")
+    return L, B, T, D
+
+
+def masked_layer_stats(x: torch.Tensor, row_start: torch.Tensor, row_count: torch.Tensor, valid_rows: Optional[int] = None) -> torch.Tensor:
+    """ltxk_masked_layer_stats: x (L,B,T,D) bf16 (any layer / batch / row strides that are multiples of 8), row_start /
+    row_count (B) int32 on the device -> (B,L,3) fp32 {sum, min, max} over rows [start, start+count) x D.
+    ``valid_rows``: the sum of the counts, if the host knows it (the kernel timer's byte count; the kernel reads valid rows only)."""
+    L, B, T, D = _req_layers(x, row_start, row_count, "masked_layer_stats")
+    partials = torch.empty((B * L, 3, STATS_PARTIALS), dtype=torch.float32, device=x.device)
+    stats = torch.empty((B, L, 3), dtype=torch.float32, device=x.device)
+    with _timed("text_layer_stats", 0.0, 2.0 * L * D * (B * T if valid_rows is None else valid_rows)):
+        check(_lib.load().ltxk_masked_layer_stats(_p(x), x.stride(0), x.stride(1), x.stride(2), _p(row_start), _p(row_count),
+                                                  L, B, T, D, _p(partials), _p(stats), _stream()), "ltxk_masked_layer_stats")
+    return stats
+
+
+def layer_norm_compact(x: torch.Tensor, row_start: torch.Tensor, row_count: torch.Tensor, row0: torch.Tensor,
+                       stats: torch.Tensor, out: torch.Tensor, rows: int) -> torch.Tensor:
+    """ltxk_layer_norm_compact: the valid rows of x (L,B,T,D), normalised with ``stats`` of ``masked_layer_stats``, into the
+    first ``rows`` rows of out (>= rows, >= L*D) bf16, layer-major columns l*D + d; row0 (B) int32 = exclusive prefix sums of
+    the counts, ``rows`` their total (the host knows both)."""
+    L, B, T, D = _req_layers(x, row_start, row_count, "layer_norm_compact")
+    _req(row0, torch.int32, "layer_norm_compact.row0"); _req(stats, torch.float32, "layer_norm_compact.stats")
+    _req(out, BF16, "layer_norm_compact.out")
+    if tuple(row0.shape) != (B,) or not row0.is_contiguous() or tuple(stats.shape) != (B, L, 3) or not stats.is_contiguous():
+        raise ValueError("layer_norm_compact: row0 must be a contiguous (B,) vector and stats a contiguous (B,L,3) tensor")
+    if out.dim() != 2 or out.stride(1) != 1 or out.shape[0] < rows or out.shape[1] < L * D:
+        raise ValueError(f"layer_norm_compact: out must be (>= {rows}, >= {L * D}) with unit inner stride, got {tuple(out.shape)}")
+    with _timed("text_layer_norm", 0.0, 4.0 * rows * L * D):
+        check(_lib.load().ltxk_layer_norm_compact(_p(x), x.stride(0), x.stride(1), x.stride(2), _p(row_start), _p(row_count),
+                                                  _p(row0), _p(stats), _p(out), out.stride(0), L, B, T, D, rows, _stream()),
+              "ltxk_layer_norm_compact")
+    return out
+
+
+def rmsnorm_rows(x: torch.Tensor, eps: float = 1e-6, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ltxk_rmsnorm_rows: unit-weight RMSNorm of the rows of x (M,D), any D % 8 == 0 up to 8192; row strides may exceed D."""
+    _req(x, BF16, "rmsnorm_rows.x")
+    if x.dim() != 2 or x.stride(1) != 1:
+        raise ValueError(f"rmsnorm_rows: expected an (M,D) matrix with unit inner stride, got {tuple(x.shape)}")
+    M, D = x.shape
+    if out is None:
+        out = torch.empty((M, D), dtype=BF16, device=x.device)
+    _req(out, BF16, "rmsnorm_rows.out")
+    if tuple(out.shape) != (M, D) or out.stride(1) != 1:
+        raise ValueError(f"rmsnorm_rows: out must be ({M},{D}) with unit inner stride, got {tuple(out.shape)}")
+    with _timed("rmsnorm_rows", 0.0, 4.0 * M * D):
+        check(_lib.load().ltxk_rmsnorm_rows(_p(x), x.stride(0), _p(out), out.stride(0), M, D, eps, _stream()), "ltxk_rmsnorm_rows")
+    return out
+
+
+def qknorm_rope_1d(buf: torch.Tensor, D: int, weight: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, T: int, H: int,
+                   eps: float = 1e-6) -> torch.Tensor:
+    """ltxk_qknorm_rope_1d: in place on columns [0, 2D) of buf (M, ld >= 2D): q | k RMSNorm over the full D with weight (2,D),
+    then split RoPE with cos / sin (H,T,64) fp32; any H >= 1 with D == 128*H."""
+    _req(buf, BF16, "qknorm_rope_1d.buf"); _req(weight, BF16, "qknorm_rope_1d.weight")
+    _req(cos, torch.float32, "qknorm_rope_1d.cos"); _req(sin, torch.float32, "qknorm_rope_1d.sin")
+    if buf.dim() != 2 or buf.stride(1) != 1 or buf.shape[1] < 2 * D:
+        raise ValueError(f"qknorm_rope_1d: buf must be (M, >= {2 * D}) with unit inner stride, got {tuple(buf.shape)}")
+    if tuple(weight.shape) != (2, D) or not weight.is_contiguous():
+        raise ValueError(f"qknorm_rope_1d: weight must be a contiguous (2,{D}) table, got {tuple(weight.shape)}")
+    if tuple(cos.shape) != (H, T, 64) or tuple(sin.shape) != (H, T, 64) or not cos.is_contiguous() or not sin.is_contiguous():
+        raise ValueError(f"qknorm_rope_1d: cos / sin must be contiguous ({H},{T},64) tables, got {tuple(cos.shape)}")
+    with _timed("qknorm_rope_1d", 0.0, 8.0 * buf.shape[0] * D + 8.0 * buf.shape[0] * D):
+        check(_lib.load().ltxk_qknorm_rope_1d(_p(buf), buf.stride(0), buf.shape[0], D, _p(weight), _p(cos), _p(sin), T, H, eps,
+                                              _stream()), "ltxk_qknorm_rope_1d")
+    return buf
+
+
+def gelu_erf_(x: torch.Tensor) -> torch.Tensor:
+    """ltxk_gelu_erf: exact (erf) GELU in place on a contiguous bf16 tensor."""
+    _req(x, BF16, "gelu_erf_.x")
+    if not x.is_contiguous():
+        raise ValueError("gelu_erf_: x must be contiguous")
+    with _timed("gelu_erf", 0.0, 4.0 * x.numel()):
+        check(_lib.load().ltxk_gelu_erf(_p(x), x.numel(), _stream()), "ltxk_gelu_erf")
+    return x
+
+
+def connector_assemble(feat: Optional[torch.Tensor], registers: torch.Tensor, row0: torch.Tensor, row_count: torch.Tensor,
+                       B: int, T: int) -> torch.Tensor:
+    """ltxk_connector_assemble: (B,T,D) connector input - batch row b's first row_count[b] rows are rows row0[b]... of feat
+    (rows, D), the rest registers[t % R].  ``feat`` may be None when every count is 0."""
+    _req(registers, BF16, "connector_assemble.registers")
+    _req(row0, torch.int32, "connector_assemble.row0"); _req(row_count, torch.int32, "connector_assemble.row_count")
+    R, D = registers.shape
+    if not registers.is_contiguous() or tuple(row0.shape) != (B,) or tuple(row_count.shape) != (B,) or \
+            not row0.is_contiguous() or not row_count.is_contiguous():
+        raise ValueError("connector_assemble: registers must be contiguous (R,D), row0 / row_count contiguous (B,) vectors")
+    rows, ldf = 0, 0
+    if feat is not None:
+        _req(feat, BF16, "connector_assemble.feat")
+        if feat.dim() != 2 or feat.stride(1) != 1 or feat.shape[1] != D:
+            raise ValueError(f"connector_assemble: feat must be (rows,{D}) with unit inner stride, got {tuple(feat.shape)}")
+        rows, ldf = feat.shape[0], feat.stride(0)
+    out = torch.empty((B, T, D), dtype=BF16, device=registers.device)
+    with _timed("connector_assemble", 0.0, 4.0 * B * T * D):
+        check(_lib.load().ltxk_connector_assemble(_p(feat) if rows else None, ldf, _p(registers), _p(row0), _p(row_count), _p(out),
+                                                  B, T, D, R, rows, _stream()), "ltxk_connector_assemble")
+    return out

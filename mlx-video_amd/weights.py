@@ -277,6 +277,70 @@ def sniff_timestep_conditioning(path: Path) -> bool:
         return False
 
 
+# ------------------------------------------------------------------------------------------- text connector
+def aggregate_k_to_layer_major(w: torch.Tensor, D: int) -> torch.Tensor:
+    """aggregate_embed.weight (N, D*L) with the checkpoint's K order d*L + l (text_encoder.py:598,633: the hidden states are
+    stacked on the last axis and flattened) -> K order l*D + d, the column order of ltxk_layer_norm_compact's output."""
+    N, K = w.shape
+    if K % D:
+        raise ValueError(f"aggregate_embed.weight has K = {K}, not a multiple of the hidden width {D}")
+    return w.reshape(N, D, K // D).transpose(1, 2).reshape(N, K).contiguous()
+
+
+def aggregate_k_from_layer_major(w: torch.Tensor, D: int) -> torch.Tensor:
+    """The inverse of ``aggregate_k_to_layer_major``."""
+    N, K = w.shape
+    return w.reshape(N, K // D, D).transpose(1, 2).reshape(N, K).contiguous()
+
+
+# (aggregate_embed key, connector prefix) of the three layouts the reference reads (text_encoder.py:756-836), in its order of
+# precedence: the LTX-2 checkpoint itself, a converted `connector.*` file, a diffusers `connectors/` file
+_CONNECTOR_FAMILIES = (("text_embedding_projection.aggregate_embed.weight", "model.diffusion_model.video_embeddings_connector."),
+                       ("text_embedding_projection.aggregate_embed.weight", "connector.video_embeddings_connector."),
+                       ("text_proj_in.weight", "video_connector."))
+
+
+def _connector_key(k: str) -> str:
+    """text_encoder.py:820-828."""
+    return k.replace(".ff.net.0.proj.", ".ff.proj_in.").replace(".ff.net.2.", ".ff.proj_out.").replace(".to_out.0.", ".to_out.")
+
+
+def text_connector_weights(files: Iterable[Path], device) -> Dict[str, torch.Tensor]:
+    """The feature extractor + video embeddings connector of ``text_connector.TextConnector`` from safetensors files, under
+    module keys: ``aggregate_embed.weight_layer_major`` (K axis permuted, ``aggregate_k_to_layer_major``),
+    ``learnable_registers``, ``transformer_1d_blocks.*``.  Three key families are read (text_encoder.py:756-836):
+    `text_embedding_projection.aggregate_embed.weight` + `model.diffusion_model.video_embeddings_connector.*`;
+    `connector.video_embeddings_connector.*`; `text_proj_in.weight` + `video_connector.*` (a diffusers
+    connectors/diffusion_pytorch_model.safetensors).  The first family that has connector tensors wins, as in the reference;
+    `audio_embeddings_connector.*` / `audio_connector.*` are ignored."""
+    files = [Path(f) for f in files]
+    found = []
+    for f in files:
+        keys = [k for k in scan_header(f) if k != "__metadata__"]
+        for fam, (agg_key, prefix) in enumerate(_CONNECTOR_FAMILIES):
+            if any(k.startswith(prefix) for k in keys):
+                found.append((fam, f))
+    if not found:
+        raise ValueError("no text connector in " + ", ".join(str(f) for f in files) + ": expected video_embeddings_connector.* "
+                         "(LTX-2 checkpoint) or video_connector.* (connectors/diffusion_pytorch_model.safetensors) tensors")
+    fam = min(fam for fam, _ in found)
+    agg_key, prefix = _CONNECTOR_FAMILIES[fam]
+    out: Dict[str, torch.Tensor] = {}
+    agg = None
+    for k, v in iter_safetensors(files, want=lambda k: k == agg_key or k.startswith(prefix)):
+        if k == agg_key:
+            agg = v
+        else:
+            out[_connector_key(k[len(prefix):])] = _to_dev(v, device)
+    if agg is None:
+        raise ValueError(f"the connector tensors ({prefix}*) come without {agg_key}")
+    if "learnable_registers" not in out:
+        raise ValueError(f"{prefix}learnable_registers is missing")
+    D = int(out["learnable_registers"].shape[1])
+    out["aggregate_embed.weight_layer_major"] = aggregate_k_to_layer_major(agg.to(device=device, dtype=BF16), D)
+    return out
+
+
 def infer_encoder_blocks(keys: Iterable[str]):
     """Encoder block list from the checkpoint's key set: `down_blocks.i.res_blocks.j.*` => ("res_x", n); a bare
     `down_blocks.i.conv.*` is a compress block whose stride follows the default schedule of encoder.py:95-105."""
@@ -310,12 +374,14 @@ def infer_encoder_blocks(keys: Iterable[str]):
 
 def load_pipeline_modules(model_repo: str, device, need_encoder: bool = False, need_upsampler: bool = False,
                           loras: Optional[list] = None, build_transformer: bool = True, fp8: bool = False,
-                          fp8_scaling: str = "channel") -> dict:
+                          fp8_scaling: str = "channel", need_text_connector: bool = False) -> dict:
     """Local-directory loader (no network: repo *names* are not resolved, utils.py:78-374 is out of scope).
     Headers are scanned first (keys, shapes, `timestep_conditioning` metadata), the architecture is inferred from the
     shapes, then tensors stream one by one straight into device memory under their module keys (ltx.py:548-826,
     decoder.py:594-740, encoder.py:108-187).  Returns the modules plus ``transformer_weights`` / ``transformer_config``
-    (the base dict stays reachable so LoRA-merged twins can be built, generate.py:2957-3031,3229-3237)."""
+    (the base dict stays reachable so LoRA-merged twins can be built, generate.py:2957-3031,3229-3237).
+    ``need_text_connector``: also ``mods["text_connector"]``, a ``TextConnector`` built from the directory's files and its
+    ``connectors/`` sub-directory (``text_connector_weights``)."""
     from .ltx_model import LTXModel
     from .video_vae import LTX2VideoDecoder, VideoEncoder
     root = Path(model_repo)
@@ -386,6 +452,9 @@ def load_pipeline_modules(model_repo: str, device, need_encoder: bool = False, n
         uw = {k: _to_dev(_conv_to_mlx(k, v) if "conv" in k else v, device) for k, v in iter_safetensors(ups[:1])}
         nb = 1 + max((int(k.split(".")[1]) for k in uw if k.startswith("res_blocks.")), default=3)
         mods["upsampler"] = LatentUpsampler(uw, num_blocks_per_stage=nb)
+    if need_text_connector:
+        from .text_connector import TextConnector
+        mods["text_connector"] = TextConnector(text_connector_weights(main + sorted((root / "connectors").glob("*.safetensors")), device))
     return mods
 
 
