@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define LTXK_VERSION 408
+#define LTXK_VERSION 409
 
 #define LTXK_OK 0
 #define LTXK_EINVAL (-1)   /* bad argument (shape / alignment / null pointer) */
@@ -371,6 +371,57 @@ typedef struct ltxk_step_args {
 } ltxk_step_args;
 
 int ltxk_guided_euler_step(const ltxk_step_args* args, void* stream);
+
+/* CFG* and APG: the two x0-space guiders of ltx_core/components/guiders.py that need a global reduction
+ * (CFGStarRescalingGuider :14-43, LtxAPGGuider :57-76).  With r(.) = round to bf16 (every array-valued op of the reference
+ * materialises a bf16 array), p = r(x - sigma*v_pos), n = r(x - sigma*v_neg), k = cfg_scale - 1 (fp32), sums per batch
+ * sample over all C*S elements (masked tokens included), each summand the bf16-rounded product, a sum used as r(sum):
+ *   CFG_STAR: a = r(r(S r(p*n)) / r(r(S r(n*n)) + 1e-8));                       d = r(k * r(p - r(a*n)))
+ *   APG:      g = r(p - n);  norm_threshold > 0 only: nrm = r(sqrt(r(r(S r(g*g)) + 1e-8))), f = min(1, r(norm_threshold/nrm)),
+ *             g = r(g*f);    c = r(r(S r(g*p)) / r(r(S r(p*p)) + 1e-8));  par = r(c*p);
+ *                                                                               d = r(k * r(r(par*eta) + r(g - par)))
+ *   x0 = r(p + d);  with v_pert (STG): x0 = r(x0 + r(stg_scale * r(p - r(x - sigma*v_pert))));
+ * then mask blend, Euler, sigma_next <= 0 and LTXK_STEP_BF16_EULER exactly as ltxk_cfg_euler_step.
+ *
+ * A step is ltxk_guidance_sums (the reductions -> `record`, in device memory) followed by ltxk_guider_euler_step (the tail,
+ * which reads the derived scalars from `record`); the host never reads a sum, so both are captured in a step graph.
+ * record: LTXK_GUIDER_RECORD_FLOATS fp32 per sample, every one written by each ltxk_guidance_sums call:
+ *   CFG_STAR  [0] S r(p*n)  [1] S r(n*n)  [2] 0         [3] 0    [4] 1                    [5] a   [6..7] 0
+ *   APG       [0] S r(g*g)  [1] S r(g*p)  [2] S r(p*p)  [3] nrm  [4] f                    [5] c   [6..7] 0
+ *             ([0] and [3] are 0 and f is 1 when norm_threshold == 0; [0] sums g before the clamp, [1] after it)
+ * Sums are deterministic: no atomics; one fp32 partial per wave (8 serial terms per lane, then the wave butterfly) and a
+ * float64 combine per sample in an order that depends on (C, S) only - not on B, the device or the launch path - so sample
+ * b of a batch has the bits of the same sample launched alone.  Each raw sum is within 1e-5 * S|term| of the exact sum.
+ * CFG_STAR and APG without the clamp make one reduction pass (2 launches), APG with norm_threshold > 0 two (the second
+ * reads f from the record).  workspace: ltxk_guidance_sums_workspace_bytes(B, C, S) bytes, caller-owned, contents
+ * irrelevant on entry.  ltxk_guidance_sums reads v_pos, v_neg, latent, sigma | sigmas_dev[0], guider, norm_threshold.
+ * LTXK_EINVAL: an unknown guider id (plain CFG is ltxk_cfg_euler_step), eta not finite, norm_threshold < 0 or not finite,
+ * NULL v_neg, C % 8 != 0, clean without mask or mask without clean, sigma <= 0 without sigmas_dev, a workspace too small. */
+enum { LTXK_GUIDER_CFG_STAR = 1, LTXK_GUIDER_APG = 2 };
+#define LTXK_GUIDER_RECORD_FLOATS 8
+typedef struct ltxk_guider_args {
+  const void* v_pos;          /* (B,S,C) bf16, 16-byte aligned                                     */
+  const void* v_neg;          /* (B,S,C) bf16, 16-byte aligned; required                           */
+  const void* v_pert;         /* (B,S,C) bf16 or NULL (no STG); tail only                          */
+  const void* latent;         /* (B,C,S) bf16                                                      */
+  void* out;                  /* (B,C,S) bf16; may be `latent`; tail only                          */
+  const void* clean;          /* (B,C,S) bf16 or NULL; tail only                                   */
+  const float* mask;          /* (B,S) fp32 or NULL (with clean); tail only                        */
+  const float* sigmas_dev;    /* 2 fp32 in device memory, or NULL: use sigma / sigma_next          */
+  float* record;              /* (B, LTXK_GUIDER_RECORD_FLOATS) fp32: written by the sums, read by the tail */
+  void* workspace;            /* sums only                                                         */
+  int64_t workspace_bytes;
+  int32_t B, C, S;
+  int32_t guider;             /* LTXK_GUIDER_*                                                     */
+  float cfg_scale, stg_scale, sigma, sigma_next;
+  float eta, norm_threshold;  /* APG: weight of the parallel component; norm clamp (0: none)       */
+  int32_t flags;              /* LTXK_STEP_*                                                       */
+} ltxk_guider_args;
+/* sizeof(ltxk_guider_args) in this build (an entry of its own: the ltxk_abi_sizeof index list is closed).               */
+int ltxk_guider_args_sizeof(void);
+int64_t ltxk_guidance_sums_workspace_bytes(int32_t B, int32_t C, int32_t S);   /* -1 on bad arguments                 */
+int ltxk_guidance_sums(const ltxk_guider_args* args, void* stream);
+int ltxk_guider_euler_step(const ltxk_guider_args* args, void* stream);
 
 /* The value passthrough of a skipped video self-attention (STG, perturbations.py SKIP_VIDEO_SELF_ATTN): for every batch
  * row b whose bit is set in row_mask, out[(b*T+t)*ldo + c] = vt[(b*D+c)*ldvt + t] for t < T, c < D - the V^T buffer of

@@ -95,6 +95,17 @@ class StepArgs(Structure):
     ]
 
 
+class GuiderArgs(Structure):
+    _fields_ = [
+        ("v_pos", c_void_p), ("v_neg", c_void_p), ("v_pert", c_void_p), ("latent", c_void_p), ("out", c_void_p),
+        ("clean", c_void_p), ("mask", c_void_p), ("sigmas_dev", c_void_p), ("record", c_void_p),
+        ("workspace", c_void_p), ("workspace_bytes", c_int64),
+        ("B", c_int32), ("C", c_int32), ("S", c_int32), ("guider", c_int32),
+        ("cfg_scale", c_float), ("stg_scale", c_float), ("sigma", c_float), ("sigma_next", c_float),
+        ("eta", c_float), ("norm_threshold", c_float), ("flags", c_int32),
+    ]
+
+
 # name -> (restype, argtypes); mirrors include/ltxk.h one to one.
 SIGNATURES = {
     "ltxk_version": (c_int32, []),
@@ -160,6 +171,10 @@ SIGNATURES = {
     "ltxk_cfg_euler_step_dev": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32,
                                           c_int32, c_float, c_void_p, c_int32, c_void_p]),
     "ltxk_guided_euler_step": (c_int32, [POINTER(StepArgs), c_void_p]),
+    "ltxk_guider_args_sizeof": (c_int32, []),
+    "ltxk_guidance_sums_workspace_bytes": (c_int64, [c_int32, c_int32, c_int32]),
+    "ltxk_guidance_sums": (c_int32, [POINTER(GuiderArgs), c_void_p]),
+    "ltxk_guider_euler_step": (c_int32, [POINTER(GuiderArgs), c_void_p]),
     "ltxk_attn_value_passthrough": (c_int32, [c_void_p, c_int32, c_void_p, c_int32, c_int32, c_int32, c_int32, c_uint64,
                                               c_void_p]),
     "ltxk_cfg_euler_step": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32,
@@ -186,6 +201,8 @@ ATTN_NO_TAIL_SPLIT = 1        # ltxk.h: LTXK_ATTN_NO_TAIL_SPLIT
 GEMM_FORM_SINGLE, GEMM_FORM_BIG, GEMM_FORM_SPLITK = 0, 1, 2     # ltxk.h: LTXK_GEMM_FORM_*
 CONV_KERNEL_PER_TAP, CONV_KERNEL_KW = 0, 1                      # ltxk.h: LTXK_CONV_KERNEL_*
 ATTN_KERNEL_128, ATTN_KERNEL_MIX = 0, 1                         # ltxk.h: LTXK_ATTN_KERNEL_*
+GUIDER_CFG_STAR, GUIDER_APG = 1, 2                              # ltxk.h: LTXK_GUIDER_*
+GUIDER_RECORD_FLOATS = 8                                        # ltxk.h: LTXK_GUIDER_RECORD_FLOATS
 
 
 def _open(path: str) -> ctypes.CDLL:
@@ -205,7 +222,7 @@ def _open(path: str) -> ctypes.CDLL:
                             f"{ctypes.sizeof(st)} in this binding; rebuild it (make -C mlx-video_amd/csrc)")
     # (structs added after the ltxk_abi_sizeof index list was closed report their size through an entry of their own)
     for fn, st in ((lib.ltxk_gemm_grouped_args_sizeof, GemmGroupedArgs), (lib.ltxk_conv3d_plan_sizeof, Conv3dPlan),
-                   (lib.ltxk_flash_attn_plan_sizeof, AttnPlan)):
+                   (lib.ltxk_flash_attn_plan_sizeof, AttnPlan), (lib.ltxk_guider_args_sizeof, GuiderArgs)):
         if fn() != ctypes.sizeof(st):
             raise LtxkError(f"{path} is stale: sizeof({st.__name__}) is {fn()} in the library, "
                             f"{ctypes.sizeof(st)} in this binding; rebuild it (make -C mlx-video_amd/csrc)")

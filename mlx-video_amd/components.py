@@ -3,7 +3,8 @@ schedulers, patchifier.  In the reference these are only reached from `ltx_pipel
 which no entry point executes, so they are mirrored as small host-side
 torch-tensor helpers with the *intended* contracts (diffusion_steps.py:9-13, guiders.py:23-108,
 noisers.py, schedulers.py:16-107, patchifiers.py:12-60).  The fused production path is
-``denoise.denoise_dev`` / ``ltxk_cfg_euler_step``; tests check that the two agree."""
+``denoise.denoise_dev`` / ``ltxk_cfg_euler_step`` (CFG, STG) and ``ltxk_guidance_sums`` + ``ltxk_guider_euler_step``
+(CFG*, APG; ``guidance.GuiderConfig``); tests check that the two agree."""
 from __future__ import annotations
 
 import math

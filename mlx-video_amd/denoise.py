@@ -15,7 +15,7 @@ import torch
 
 from . import ops
 from .conditioning import LatentState
-from .guidance import BatchedPerturbationConfig, PerturbationConfig, stg_perturbation
+from .guidance import BatchedPerturbationConfig, GuiderConfig, PerturbationConfig, stg_perturbation
 from .ltx_model import ContextKV, LTXModel, TimestepPlan, precompute_freqs_cis
 
 BF16 = torch.bfloat16
@@ -63,11 +63,14 @@ class _StepPlan:
 class _Guidance:
     """What one step evaluates: the positive forward, the negative one (CFG, cfg_scale != 1) and the perturbed one (STG,
     stg_scale != 0), either as separate forwards or - ``batched`` (cfg_batch) - as one forward over the rows
-    [pos | neg | pos+], each block of ``b`` rows."""
+    [pos | neg | pos+], each block of ``b`` rows.  ``guider``: the x0-space guider of the CFG slot when it is not plain CFG
+    (``cfg_star`` / ``apg``; None otherwise, and at cfg_scale == 1, where every guider is disabled)."""
 
-    def __init__(self, b: int, cfg_scale: float, cfg_batch: bool, stg_scale: float, pert: Optional[PerturbationConfig]):
+    def __init__(self, b: int, cfg_scale: float, cfg_batch: bool, stg_scale: float, pert: Optional[PerturbationConfig],
+                 guider: Optional[GuiderConfig] = None):
         self.b = b
         self.use_cfg = cfg_scale != 1.0
+        self.guider = guider if (guider is not None and not guider.is_default and self.use_cfg) else None
         self.use_stg = pert is not None
         self.cfg_scale, self.stg_scale = float(cfg_scale), float(stg_scale)
         self.batched = bool(cfg_batch) and (self.use_cfg or self.use_stg)
@@ -97,7 +100,15 @@ class _Guidance:
         v_pert = tr.forward_tokens(tok, tp, ctx_pos, pe, kv_pos, perturbations=self.pert_alone) if self.use_stg else None
         return v_pos, v_neg, v_pert
 
-    def tail(self, v_pos, v_neg, v_pert, latents, s, s_next, clean, mask_tok, out=None, sigmas_dev=None, bf16_euler=False):
+    def tail(self, v_pos, v_neg, v_pert, latents, s, s_next, clean, mask_tok, out=None, sigmas_dev=None, bf16_euler=False,
+             record=None, workspace=None):
+        if self.guider is not None:   # cfg_star / apg: the reduction launch(es) into the device record, then the tail that reads it
+            g = self.guider
+            record = ops.guidance_sums(v_pos, v_neg, latents, g.kind, s, g.norm_threshold, record=record, workspace=workspace,
+                                       sigmas_dev=sigmas_dev)
+            return ops.guider_euler_step(v_pos, v_neg, v_pert, latents, record, g.kind, self.cfg_scale, self.stg_scale, s, s_next,
+                                         g.eta, g.norm_threshold, clean, mask_tok, out=out, sigmas_dev=sigmas_dev,
+                                         bf16_euler=bf16_euler)
         if v_pert is None:            # no STG: today's CFG step tail, launch for launch
             return ops.cfg_euler_step(v_pos, v_neg, latents, self.cfg_scale, s, s_next, clean, mask_tok, out=out,
                                       sigmas_dev=sigmas_dev, bf16_euler=bf16_euler)
@@ -108,7 +119,8 @@ class _Guidance:
 def _denoise(latents: torch.Tensor, positions: torch.Tensor, ctx_pos_in: torch.Tensor, ctx_neg_in: Optional[torch.Tensor],
              transformer: LTXModel, sig: List[float], cfg_scale: float, state: Optional[LatentState], compile_step: bool,
              cfg_batch: bool, use_graph: bool, graph_cache: Optional[dict], cache_context: bool, bf16_euler: bool,
-             stg_scale: float = 0.0, stg_pert: Optional[PerturbationConfig] = None, stg_key: tuple = ()) -> torch.Tensor:
+             stg_scale: float = 0.0, stg_pert: Optional[PerturbationConfig] = None, stg_key: tuple = (),
+             guider: Optional[GuiderConfig] = None) -> torch.Tensor:
     if state is not None:
         latents = state.latent
     latents = latents.to(BF16).contiguous()
@@ -117,7 +129,7 @@ def _denoise(latents: torch.Tensor, positions: torch.Tensor, ctx_pos_in: torch.T
     if len(sig) < 2:
         return latents
     b = latents.shape[0]
-    gd = _Guidance(b, cfg_scale, cfg_batch, stg_scale, stg_pert)
+    gd = _Guidance(b, cfg_scale, cfg_batch, stg_scale, stg_pert, guider)
     pe = precompute_freqs_cis(positions[:1].contiguous(), transformer.inner_dim, transformer.positional_embedding_theta,
                               transformer.positional_embedding_max_pos, transformer.num_attention_heads)
     plan = _StepPlan(latents, state, gd.reps, sig)
@@ -128,6 +140,8 @@ def _denoise(latents: torch.Tensor, positions: torch.Tensor, ctx_pos_in: torch.T
                state is not None, plan.U, bool(bf16_euler), bool(cache_context))
         if gd.use_stg:                # STG off: today's key
             key = key + stg_key
+        if gd.guider is not None:     # plain CFG: today's key
+            key = key + ("guider",) + gd.guider.key
         cache = graph_cache if graph_cache is not None else {}
         ent = cache.get(key)
         if ent is None:
@@ -162,7 +176,8 @@ def denoise_dev(latents: torch.Tensor, positions: torch.Tensor, text_embeddings_
                 eval_interval: int = 1, compile_step: bool = False, compile_shapeless: bool = False,
                 cfg_batch: bool = False, ui_phase: str = "denoise", use_graph: bool = False,
                 graph_cache: Optional[dict] = None, cache_context: bool = False, stg_scale: float = 0.0,
-                stg_blocks: Optional[Sequence[int]] = None, stg_mode: str = "stg_v") -> torch.Tensor:
+                stg_blocks: Optional[Sequence[int]] = None, stg_mode: str = "stg_v", guider: str = "cfg",
+                apg_eta: float = 1.0, apg_norm_threshold: float = 0.0) -> torch.Tensor:
     """generate.py:1060-1327.  latents (B,128,F,H,W) bf16 on the GPU; returns the same shape.
     ``use_graph``: capture the whole step (forward(s) + fused tail, ~1000 launches) once as a hipGraph and
     replay it per step — the analogue of the reference's mx.compile'd step_fn (generate.py:1109-1177);
@@ -179,13 +194,18 @@ def denoise_dev(latents: torch.Tensor, positions: torch.Tensor, text_embeddings_
     "Spatio-temporal guidance").  With ``cfg_batch`` the three predictions are one B=3 forward [pos, neg, pos+] ([pos, pos+]
     when cfg_scale == 1); without it a third forward.  ``stg_mode``: "stg_v" or "stg_av"; the latter also perturbs the
     audio self-attention upstream, and as this model has no audio branch it acts as "stg_v".  ``stg_blocks`` that is
-    empty or names a block outside [0, num_layers) is a ValueError.  stg_scale == 0: no STG, today's loop bit for bit."""
+    empty or names a block outside [0, num_layers) is a ValueError.  stg_scale == 0: no STG, today's loop bit for bit.
+    ``guider``: what the CFG slot runs - "cfg" (default: today's fused velocity-space tail, launch for launch), "cfg_star"
+    (CFGStarRescalingGuider) or "apg" (LtxAPGGuider with ``apg_eta`` and ``apg_norm_threshold``, 0 = no clamp); the latter two act
+    in x0 space on per-sample dot products that stay on the device (ltxk_guidance_sums + ltxk_guider_euler_step, DESIGN.md
+    §5j), compose with STG, and are disabled at cfg_scale == 1 like CFG itself."""
+    gcfg = GuiderConfig(guider, apg_eta, apg_norm_threshold)
     stg_scale = float(stg_scale or 0.0)
     pert = stg_perturbation(stg_blocks, stg_mode, transformer.config.num_layers) if stg_scale != 0.0 else None
     stg_key = (stg_scale, None if stg_blocks is None else tuple(int(x) for x in stg_blocks), stg_mode)
     sig = [float(s) for s in (sigmas.tolist() if torch.is_tensor(sigmas) else sigmas)]
     return _denoise(latents, positions, text_embeddings_pos, text_embeddings_neg, transformer, sig, cfg_scale, state,
-                    compile_step, cfg_batch, use_graph, graph_cache, cache_context, False, stg_scale, pert, stg_key)
+                    compile_step, cfg_batch, use_graph, graph_cache, cache_context, False, stg_scale, pert, stg_key, gcfg)
 
 
 class _StepGraph:
@@ -215,6 +235,13 @@ class _StepGraph:
         self.kv_a: Optional[ContextKV] = None
         self.kv_b: Optional[ContextKV] = None
         self.cache_context = cache_context
+        # cfg_star / apg: the sums record and the partials workspace, persistent so that the captured launches keep their addresses
+        self.g_rec = self.g_ws = None
+        if gd.guider is not None:
+            bb, cc = latents.shape[:2]
+            self.g_rec = torch.zeros((bb, ops.GUIDER_RECORD_FLOATS), dtype=torch.float32, device=dev)
+            self.g_ws = torch.zeros((ops.guidance_sums_workspace_bytes(bb, cc, latents.numel() // (bb * cc)) // 4,),
+                                    dtype=torch.float32, device=dev)
         self.graph = None
 
     def _load(self, latents, plan: _StepPlan, ctx_pos, ctx_neg, pe) -> None:
@@ -257,7 +284,7 @@ class _StepGraph:
             v_pos, v_neg, v_pert = gd.velocities(self.tr, self.lat_buf, tp, self.pe, None, None, self.ctx_a, self.kv_a,
                                                  self.ctx_b, self.kv_b)
         gd.tail(v_pos, v_neg, v_pert, self.lat_buf, 1.0, 0.0, self.clean, self.mask_tok, out=self.lat_buf, sigmas_dev=self.sig_buf,
-                bf16_euler=self.bf16_euler)
+                bf16_euler=self.bf16_euler, record=self.g_rec, workspace=self.g_ws)
 
     def run(self, latents, plan: _StepPlan, ctx_pos, ctx_neg, pe) -> torch.Tensor:
         self._load(latents, plan, ctx_pos, ctx_neg, pe)

@@ -20,6 +20,7 @@ from __future__ import annotations
 
 import argparse
 import json
+import math
 import time
 from contextlib import contextmanager
 from enum import Enum
@@ -214,7 +215,8 @@ def generate_video(model_repo: Optional[str] = None, text_encoder_repo: Optional
                    stg_mode: Optional[str] = None, enable_fp8: bool = False, fp8_scaling: str = "channel",
                    fp8_activations: bool = False, gemma_hidden_states=None, gemma_attention_mask: Optional[torch.Tensor] = None,
                    negative_gemma_hidden_states=None, negative_gemma_attention_mask: Optional[torch.Tensor] = None,
-                   text_connector=None) -> np.ndarray:
+                   text_connector=None, guider: Optional[str] = None, apg_eta: float = 1.0,
+                   apg_norm_threshold: float = 0.0) -> np.ndarray:
     """See the module docstring.  Returns uint8 frames (F,H,W,3) (generate.py:4195-4197).
     ``hoist_context`` (not in the reference, off by default): the part of the forward that depends on the text context only -
     caption projection and the 48 cross-attention K / V^T projections, 3.37 TFLOP that the reference recomputes in every forward
@@ -233,7 +235,10 @@ def generate_video(model_repo: Optional[str] = None, text_encoder_repo: Optional
     ``gemma_hidden_states`` / ``gemma_attention_mask`` (and the ``negative_`` pair): the text route that starts behind Gemma -
     the L hidden states of a Gemma-3 forward ((L,1,T,D) stack or list of L (1,T,D)) and its left-padded 0/1 mask (1,T); the
     feature extractor and the video embeddings connector run here (``text_connector=`` a ``TextConnector``, or loaded from
-    ``model_repo``), positive and negative prompt as one B = 2 call.  ``prompt_embeds`` wins when both are given."""
+    ``model_repo``), positive and negative prompt as one B = 2 call.  ``prompt_embeds`` wins when both are given.
+    ``guider`` / ``apg_eta`` / ``apg_norm_threshold`` (--guider / --apg-eta / --apg-norm-threshold; not in the reference CLI, the
+    guiders are ltx_core/components/guiders.py): what the CFG slot of every guided (denoise_dev) stage runs - "cfg" (None: the
+    same), "cfg_star" or "apg" (DESIGN.md 5j).  A non-default guider on a run without a guided stage is a ValueError, as for STG."""
     t_start = time.perf_counter()
     if isinstance(pipeline, str):
         pipeline = PipelineType(pipeline)
@@ -262,6 +267,13 @@ def generate_video(model_repo: Optional[str] = None, text_encoder_repo: Optional
                          "without stage2_dev (--stage2-dev)")
     if stg["stg_mode"] not in ("stg_v", "stg_av"):
         raise ValueError(f"Unknown stg_mode: {stg_mode!r}")
+    from .guidance import GuiderConfig
+    gcfg = GuiderConfig(guider or "cfg", apg_eta, apg_norm_threshold)
+    if not gcfg.is_default and is_distilled and not stage2_dev:
+        raise ValueError(f"guider={gcfg.kind!r} needs a guided denoise stage: the {pipeline.value} pipeline has none "
+                         "without stage2_dev (--stage2-dev)")
+    if not gcfg.is_default:           # the default adds no keyword: today's calls
+        stg.update(guider=gcfg.kind, apg_eta=gcfg.eta, apg_norm_threshold=gcfg.norm_threshold)
     from .weights import FP8_SCALINGS
     if fp8_scaling not in FP8_SCALINGS:
         raise ValueError(f"Unknown fp8_scaling: {fp8_scaling!r} (expected one of {FP8_SCALINGS})")
@@ -512,6 +524,20 @@ class _LoraAction(argparse.Action):
         setattr(namespace, self.dest, (getattr(namespace, self.dest) or []) + [item])
 
 
+def _finite_float(text: str) -> float:
+    v = float(text)
+    if not math.isfinite(v):
+        raise argparse.ArgumentTypeError(f"expected a finite number, got {text!r}")
+    return v
+
+
+def _nonneg_float(text: str) -> float:
+    v = _finite_float(text)
+    if v < 0:
+        raise argparse.ArgumentTypeError(f"expected a number >= 0, got {text!r}")
+    return v
+
+
 def build_parser() -> argparse.ArgumentParser:
     """The subset of generate.py:4244-4525 that drives this path."""
     ap = argparse.ArgumentParser(description="LTX-2 video generation on MI355X (libltxk)")
@@ -571,6 +597,12 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--stg-blocks", type=int, nargs="*", default=None, help="Blocks whose video self-attention the STG pass skips (default: all)")
     ap.add_argument("--stg-mode", type=str, choices=["stg_av", "stg_v"], default=None,
                     help="stg_av acts as stg_v: the model has no audio branch")
+    # the guider of the CFG slot (not in the reference CLI; ltx_core/components/guiders.py)
+    ap.add_argument("--guider", type=str, choices=["cfg", "cfg_star", "apg"], default="cfg",
+                    help="cfg: classifier-free guidance; cfg_star: CFG with the negative prediction projected onto the positive one; "
+                         "apg: adaptive projected guidance.  dev pipeline or --stage2-dev")
+    ap.add_argument("--apg-eta", type=_finite_float, default=1.0, help="--guider apg: weight of the guidance component parallel to the prediction")
+    ap.add_argument("--apg-norm-threshold", type=_nonneg_float, default=0.0, help="--guider apg: clamp the guidance norm to this (0: off)")
     # the reference's flag (it parses and ignores it): keep the model in lower precision, calculations still in bfloat16
     ap.add_argument("--enable-fp8", action="store_true", default=False,
                     help="Keep the transformer's Linear weights as FP8 (e4m3) panels; calculations still in bfloat16")
@@ -693,7 +725,8 @@ def main(argv: Optional[Sequence[str]] = None) -> None:
                    images=images, video_conditionings=videos, loras=args.lora, distilled_loras=args.distilled_lora,
                    conditioning_mode=args.conditioning_mode, stream=args.stream, stage2_dev=args.stage2_dev,
                    fp32_euler=args.fp32_euler, stg_scale=args.stg_scale, stg_blocks=args.stg_blocks, stg_mode=args.stg_mode,
-                   enable_fp8=args.enable_fp8, fp8_scaling=args.fp8_scaling, fp8_activations=args.fp8_activations, **kw)
+                   enable_fp8=args.enable_fp8, fp8_scaling=args.fp8_scaling, fp8_activations=args.fp8_activations,
+                   guider=args.guider, apg_eta=args.apg_eta, apg_norm_threshold=args.apg_norm_threshold, **kw)
 
 
 if __name__ == "__main__":

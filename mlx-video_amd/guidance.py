@@ -1,4 +1,6 @@
-"""Perturbation configs of spatio-temporal guidance (STG): ltx_core/guidance/perturbations.py with torch in place of mx.
+"""Guidance configs.  ``GuiderConfig``: which x0-space guider of ltx_core/components/guiders.py the guided denoise loop
+runs in the CFG slot.  The rest: perturbation configs of spatio-temporal guidance (STG), ltx_core/guidance/perturbations.py
+with torch in place of mx.
 
 A ``BatchedPerturbationConfig`` holds one ``PerturbationConfig`` per batch row of a forward.  ``mask(type, block)`` is 1 for
 a row that runs the perturbable operation of ``block`` as usual and 0 for a row in which it is perturbed.  The only type this
@@ -7,11 +9,58 @@ projection instead of softmax(q k^T) v (``LTXModel.forward_tokens``, DESIGN.md "
 types are accepted and have no effect."""
 from __future__ import annotations
 
+import math
 from dataclasses import dataclass
 from enum import Enum
 from typing import List, Optional
 
 import torch
+
+
+GUIDER_KINDS = ("cfg", "cfg_star", "apg")
+
+
+@dataclass(frozen=True)
+class GuiderConfig:
+    """The guider of the CFG slot: ``cfg`` (CFGGuider, the fused velocity-space step tail), ``cfg_star``
+    (CFGStarRescalingGuider) or ``apg`` (LtxAPGGuider with ``eta`` and ``norm_threshold``; 0 = no norm clamp).  The scale is
+    the loop's ``cfg_scale``; at cfg_scale == 1 every kind is disabled, as the reference's ``enabled()``.  ``eta`` and
+    ``norm_threshold`` are validated for every kind and used by ``apg`` only."""
+    kind: str = "cfg"
+    eta: float = 1.0
+    norm_threshold: float = 0.0
+
+    def __post_init__(self):
+        if self.kind not in GUIDER_KINDS:
+            raise ValueError(f"Unknown guider: {self.kind!r} (expected one of {GUIDER_KINDS})")
+        try:
+            eta, thr = float(self.eta), float(self.norm_threshold)
+        except (TypeError, ValueError):
+            raise ValueError(f"apg_eta / apg_norm_threshold must be numbers, got {self.eta!r} / {self.norm_threshold!r}") from None
+        if not math.isfinite(eta):
+            raise ValueError(f"apg_eta must be finite, got {self.eta!r}")
+        if not (math.isfinite(thr) and thr >= 0.0):
+            raise ValueError(f"apg_norm_threshold must be finite and >= 0, got {self.norm_threshold!r}")
+        object.__setattr__(self, "eta", eta)
+        object.__setattr__(self, "norm_threshold", thr)
+
+    @property
+    def is_default(self) -> bool:
+        return self.kind == "cfg"
+
+    @property
+    def key(self) -> tuple:
+        """What distinguishes two captured step graphs."""
+        return (self.kind, self.eta, self.norm_threshold)
+
+    def component(self, scale: float):
+        """The host-side guider of ``components`` this config stands for at ``scale``."""
+        from . import components as C
+        if self.kind == "cfg":
+            return C.CFGGuider(scale)
+        if self.kind == "cfg_star":
+            return C.CFGStarRescalingGuider(scale)
+        return C.LtxAPGGuider(scale, self.eta, self.norm_threshold)
 
 
 class PerturbationType(Enum):

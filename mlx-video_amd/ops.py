@@ -11,7 +11,7 @@ from typing import Optional, Tuple
 import torch
 
 from . import _lib
-from ._lib import AttnArgs, GemmArgs, GemmGroupedArgs, StepArgs, check
+from ._lib import AttnArgs, GemmArgs, GemmGroupedArgs, GuiderArgs, StepArgs, check
 
 EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_SILU, EPI_BIAS_GATE_RES, EPI_BIAS_RES, EPI_SCALE_RES = 0, 1, 2, 3, 4, 5
 BF16 = torch.bfloat16
@@ -559,6 +559,107 @@ def guided_euler_step(v_pos: torch.Tensor, v_neg: Optional[torch.Tensor], v_pert
     a.cfg_scale, a.stg_scale, a.sigma, a.sigma_next = cfg_scale, stg_scale, sigma, sigma_next
     a.flags = int(bf16_euler)
     check(_lib.load().ltxk_guided_euler_step(ctypes.byref(a), _stream()), "ltxk_guided_euler_step")
+    return out
+
+
+GUIDER_IDS = {"cfg_star": _lib.GUIDER_CFG_STAR, "apg": _lib.GUIDER_APG}
+GUIDER_RECORD_FLOATS = _lib.GUIDER_RECORD_FLOATS
+
+
+def guidance_sums_workspace_bytes(B: int, C: int, S: int) -> int:
+    """Bytes of the partial-sum workspace ``guidance_sums`` needs for (B,C,S) (ltxk_guidance_sums_workspace_bytes)."""
+    n = int(_lib.load().ltxk_guidance_sums_workspace_bytes(B, C, S))
+    if n < 0:
+        raise ValueError(f"guidance_sums_workspace_bytes: bad shape B={B} C={C} S={S} (C must be a multiple of 8)")
+    return n
+
+
+def _guider_args(who: str, guider: str, v_pos, v_neg, v_pert, latent, eta, norm_threshold, clean, mask_tok, sigmas_dev) -> GuiderArgs:
+    """The dtype, shape and contiguity checks of ``guided_euler_step`` plus the guider's own; the filled common fields."""
+    if guider not in GUIDER_IDS:
+        raise ValueError(f"{who}: unknown guider {guider!r} (expected one of {sorted(GUIDER_IDS)}; plain CFG is cfg_euler_step)")
+    eta, norm_threshold = float(eta), float(norm_threshold)
+    if not math.isfinite(eta):
+        raise ValueError(f"{who}: eta must be finite, got {eta}")
+    if not (math.isfinite(norm_threshold) and norm_threshold >= 0.0):
+        raise ValueError(f"{who}: norm_threshold must be finite and >= 0, got {norm_threshold}")
+    if v_neg is None:
+        raise ValueError(f"{who}: v_neg is required (the guider compares the positive with the negative prediction)")
+    _req(latent, BF16, f"{who}.latent")
+    _req(v_pos, BF16, f"{who}.v_pos")
+    B, C = latent.shape[:2]
+    S = latent.numel() // (B * C)
+    for name, t in (("v_pos", v_pos), ("v_neg", v_neg), ("v_pert", v_pert)):
+        if t is None:
+            continue
+        _req(t, BF16, f"{who}.{name}")
+        if t.numel() != B * S * C or not t.is_contiguous():
+            raise ValueError(f"{who}: {name} must be a contiguous (B,S,C) = ({B},{S},{C}) tensor, got {tuple(t.shape)}")
+    if not latent.is_contiguous():
+        raise ValueError(f"{who}: latent must be contiguous")
+    if (clean is None) != (mask_tok is None):
+        raise ValueError(f"{who}: clean and mask_tok must both be given or both be None")
+    if clean is not None:
+        _req(clean, BF16, f"{who}.clean")
+        _req(mask_tok, torch.float32, f"{who}.mask_tok")
+    if sigmas_dev is not None:
+        _req(sigmas_dev, torch.float32, f"{who}.sigmas_dev")
+    a = GuiderArgs()
+    a.v_pos, a.v_neg, a.v_pert, a.latent = _p(v_pos), _p(v_neg), _p(v_pert), _p(latent)
+    a.clean, a.mask, a.sigmas_dev = _p(clean), _p(mask_tok), _p(sigmas_dev)
+    a.B, a.C, a.S, a.guider = B, C, S, GUIDER_IDS[guider]
+    a.eta, a.norm_threshold = eta, norm_threshold
+    return a
+
+
+def _guider_record(who: str, record: Optional[torch.Tensor], B: int, device, make: bool) -> torch.Tensor:
+    if record is None and make:
+        return torch.empty((B, GUIDER_RECORD_FLOATS), dtype=torch.float32, device=device)
+    if record is None:
+        raise ValueError(f"{who}: record is required (the output of guidance_sums)")
+    _req(record, torch.float32, f"{who}.record")
+    if tuple(record.shape) != (B, GUIDER_RECORD_FLOATS) or not record.is_contiguous():
+        raise ValueError(f"{who}: record must be a contiguous ({B},{GUIDER_RECORD_FLOATS}) float32 tensor, got {tuple(record.shape)}")
+    return record
+
+
+def guidance_sums(v_pos: torch.Tensor, v_neg: torch.Tensor, latent: torch.Tensor, guider: str, sigma: float,
+                  norm_threshold: float = 0.0, record: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None,
+                  sigmas_dev: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The per-sample sums and derived scalars of the ``cfg_star`` / ``apg`` guider (ltxk_guidance_sums): v_* (B,S,C) tokens,
+    latent (B,C,...) -> ``record`` (B,8) float32 in device memory (layout: include/ltxk.h), which ``guider_euler_step`` reads.
+    Deterministic (no atomics; the summation order depends on (C,S) only).  ``workspace``: a float32 device tensor of at least
+    ``guidance_sums_workspace_bytes`` bytes (allocated when None).  ``sigmas_dev``: sigma is read from device memory."""
+    a = _guider_args("guidance_sums", guider, v_pos, v_neg, None, latent, 1.0, norm_threshold, None, None, sigmas_dev)
+    need = guidance_sums_workspace_bytes(a.B, a.C, a.S)
+    if workspace is None:
+        workspace = torch.empty((need // 4,), dtype=torch.float32, device=latent.device)
+    _req(workspace, torch.float32, "guidance_sums.workspace")
+    if not workspace.is_contiguous() or workspace.numel() * 4 < need:
+        raise ValueError(f"guidance_sums: workspace must be a contiguous float32 tensor of >= {need} bytes")
+    record = _guider_record("guidance_sums", record, a.B, latent.device, make=True)
+    a.record, a.workspace, a.workspace_bytes = _p(record), _p(workspace), workspace.numel() * 4
+    a.sigma = sigma
+    check(_lib.load().ltxk_guidance_sums(ctypes.byref(a), _stream()), "ltxk_guidance_sums")
+    return record
+
+
+def guider_euler_step(v_pos: torch.Tensor, v_neg: torch.Tensor, v_pert: Optional[torch.Tensor], latent: torch.Tensor,
+                      record: torch.Tensor, guider: str, cfg_scale: float, stg_scale: float, sigma: float, sigma_next: float,
+                      eta: float = 1.0, norm_threshold: float = 0.0, clean: Optional[torch.Tensor] = None,
+                      mask_tok: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                      sigmas_dev: Optional[torch.Tensor] = None, bf16_euler: bool = False) -> torch.Tensor:
+    """The step tail under the ``cfg_star`` / ``apg`` guider (ltxk_guider_euler_step): the guider's delta in x0 space with the
+    scalars of ``record`` (from ``guidance_sums`` on the same inputs), the STG term when ``v_pert`` is given, then mask blend
+    and Euler as ``cfg_euler_step``.  ``out`` may be ``latent``."""
+    a = _guider_args("guider_euler_step", guider, v_pos, v_neg, v_pert, latent, eta, norm_threshold, clean, mask_tok, sigmas_dev)
+    record = _guider_record("guider_euler_step", record, a.B, latent.device, make=False)
+    if out is None:
+        out = torch.empty_like(latent)
+    a.record, a.out = _p(record), _p(out)
+    a.cfg_scale, a.stg_scale, a.sigma, a.sigma_next = cfg_scale, stg_scale, sigma, sigma_next
+    a.flags = int(bf16_euler)
+    check(_lib.load().ltxk_guider_euler_step(ctypes.byref(a), _stream()), "ltxk_guider_euler_step")
     return out
 
 

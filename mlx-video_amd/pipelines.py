@@ -32,6 +32,9 @@ class MLXPipelineConfig:
     fp8transformer: bool = False        # ltx_pipelines/utils/model_ledger.py:36; --enable-fp8
     fp8_scaling: str = "channel"
     fp8activations: bool = False        # (not in the reference) --fp8-activations: W8A8 in-block GEMMs; needs fp8transformer
+    guider: str = "cfg"                 # --guider: cfg | cfg_star | apg (ltx_core/components/guiders.py) in every guided stage
+    apg_eta: float = 1.0
+    apg_norm_threshold: float = 0.0
 
 
 def _ensure_list(v):
@@ -91,6 +94,7 @@ def run_generate(prompt: str, pipeline: PipelineType, cfg: MLXPipelineConfig, ou
                             conditioning_mode=cfg.conditioning_mode, tiling=cfg.tiling, stream=cfg.stream, audio=cfg.audio,
                             loras=_normalize_loras(loras), distilled_loras=_normalize_loras(distilled_loras),
                             enable_fp8=cfg.fp8transformer, fp8_scaling=cfg.fp8_scaling, fp8_activations=cfg.fp8activations,
+                            guider=cfg.guider, apg_eta=cfg.apg_eta, apg_norm_threshold=cfg.apg_norm_threshold,
                             **inject)
     return output_path if output_path is not None else frames
 
@@ -121,6 +125,9 @@ class _Base:
     fp8transformer: bool = False
     fp8_scaling: str = "channel"
     fp8activations: bool = False
+    guider: str = "cfg"
+    apg_eta: float = 1.0
+    apg_norm_threshold: float = 0.0
 
     def _cfg(self, **over) -> MLXPipelineConfig:
         names = {f.name for f in fields(MLXPipelineConfig)}

@@ -48,10 +48,15 @@ class CfgPairSharding:
 
     def denoise_dev(self, latents, positions, text_embeddings_pos, text_embeddings_neg, transformer, sigmas,
                     cfg_scale: float = 4.0, state=None, forward_fn: Optional[Callable] = None,
-                    tail_fn: Optional[Callable] = None, tokens_fn: Optional[Callable] = None, use_graph: bool = True):
+                    tail_fn: Optional[Callable] = None, tokens_fn: Optional[Callable] = None, use_graph: bool = True,
+                    guider: str = "cfg"):
         """Sharded twin of denoise.denoise_dev (compiled-step sigma semantics).  ``forward_fn(tok, sigma_bf16,
         ctx) -> velocity`` / ``tail_fn(v_pos, v_neg, latents, cfg, s, s_next) -> latents`` / ``tokens_fn(latents)``
-        default to the HIP path; the CPU (gloo) tests inject stand-ins to exercise the exchange logic."""
+        default to the HIP path; the CPU (gloo) tests inject stand-ins to exercise the exchange logic.  ``guider``: only "cfg";
+        the cfg_star / apg guiders of denoise.denoise_dev are not wired through the sharded loop."""
+        if guider != "cfg":
+            raise ValueError(f"guider={guider!r} is not supported on the sharded path (CfgPairSharding runs plain CFG only); "
+                             "use denoise.denoise_dev on one GPU")
         sig = [float(s) for s in (sigmas.tolist() if torch.is_tensor(sigmas) else sigmas)]
         if forward_fn is None:
             return self._denoise_hip(latents, positions, text_embeddings_pos, text_embeddings_neg, transformer, sig,
