@@ -335,7 +335,11 @@ int ltxk_latent_to_tokens(const void* latent, void* tokens, int32_t B, int32_t C
  *   sigma_next <= 0 => out = x0.
  *   flags & LTXK_STEP_BF16_EULER: the Euler update runs op by op in bf16, the reference's
  *   fp32_euler=False / LTX_FP32_EULER=0 compiled step (generate.py:741-748):
- *   out = bf16(x0 + bf16(bf16(sigma_next * bf16(x - x0)) / sigma)).                        */
+ *   out = bf16(x0 + bf16(bf16(sigma_next * bf16(x - x0)) / sigma)).
+ * Every step-tail entry (this one, _dev, ltxk_guided_euler_step, ltxk_guider_euler_step) runs one host check and one kernel
+ * family (csrc/step_tail.hip).  LTXK_EINVAL from each of them: NULL v_pos / latent / out, B, C or S <= 0, C % 8 != 0, B or C/8
+ * above 65535 (they are grid dimensions), a token tensor (v_pos, v_neg, v_pert) that is not 16-byte aligned, clean without
+ * mask or mask without clean, sigma <= 0 without sigmas_dev.                                */
 enum { LTXK_STEP_BF16_EULER = 1 };
 int ltxk_cfg_euler_step(const void* v_pos, const void* v_neg, const void* latent, void* out,
                         const void* clean, const float* mask, int32_t B, int32_t C, int32_t S,
@@ -357,9 +361,9 @@ int ltxk_cfg_euler_step_dev(const void* v_pos, const void* v_neg, const void* la
  * arithmetic.  sigmas_dev != NULL: {sigma, sigma_next} are read from device memory (as ltxk_cfg_euler_step_dev).
  * v_pert == NULL: the very launch ltxk_cfg_euler_step(_dev) makes (stg_scale ignored).                           */
 typedef struct ltxk_step_args {
-  const void* v_pos;          /* (B,S,C) bf16                                                      */
-  const void* v_neg;          /* (B,S,C) bf16 or NULL (no CFG)                                     */
-  const void* v_pert;         /* (B,S,C) bf16 or NULL (no STG)                                     */
+  const void* v_pos;          /* (B,S,C) bf16, 16-byte aligned                                     */
+  const void* v_neg;          /* (B,S,C) bf16, 16-byte aligned, or NULL (no CFG)                   */
+  const void* v_pert;         /* (B,S,C) bf16, 16-byte aligned, or NULL (no STG)                   */
   const void* latent;         /* (B,C,S) bf16                                                      */
   void* out;                  /* (B,C,S) bf16; may be `latent`                                     */
   const void* clean;          /* (B,C,S) bf16 or NULL                                              */
@@ -395,8 +399,9 @@ int ltxk_guided_euler_step(const ltxk_step_args* args, void* stream);
  * CFG_STAR and APG without the clamp make one reduction pass (2 launches), APG with norm_threshold > 0 two (the second
  * reads f from the record).  workspace: ltxk_guidance_sums_workspace_bytes(B, C, S) bytes, caller-owned, contents
  * irrelevant on entry.  ltxk_guidance_sums reads v_pos, v_neg, latent, sigma | sigmas_dev[0], guider, norm_threshold.
- * LTXK_EINVAL: an unknown guider id (plain CFG is ltxk_cfg_euler_step), eta not finite, norm_threshold < 0 or not finite,
- * NULL v_neg, C % 8 != 0, clean without mask or mask without clean, sigma <= 0 without sigmas_dev, a workspace too small. */
+ * LTXK_EINVAL: what every step-tail entry refuses (see ltxk_cfg_euler_step; ltxk_guidance_sums needs no `out`), and an
+ * unknown guider id (plain CFG is ltxk_cfg_euler_step), eta not finite, norm_threshold < 0 or not finite, NULL v_neg, NULL
+ * record, a workspace too small.                                                                                          */
 enum { LTXK_GUIDER_CFG_STAR = 1, LTXK_GUIDER_APG = 2 };
 #define LTXK_GUIDER_RECORD_FLOATS 8
 typedef struct ltxk_guider_args {

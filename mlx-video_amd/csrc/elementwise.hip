@@ -359,67 +359,6 @@ __global__ void latent_to_tokens_kernel(const bf16* __restrict__ lat, bf16* __re
     *(bf16x8*)(tok + (((size_t)(r * B + b)) * S + s) * C + cg * 8) = v;
 }
 
-// STG: a third velocity (the perturbed forward, vq) pushes the CFG-guided velocity g away from it in velocity space,
-// v = bf16(g + bf16(stg * bf16(v+ - vq))), before x0; without it the kernel is the plain CFG step tail.
-template <bool STG>
-__global__ void cfg_euler_kernel(const bf16* __restrict__ vp, const bf16* __restrict__ vn,
-                                 const bf16* __restrict__ lat, bf16* __restrict__ out,
-                                 const bf16* __restrict__ clean, const float* __restrict__ mask,
-                                 int B, int C, int S, float cfg, float sigma, float sigma_next,
-                                 const float* __restrict__ sig_dev, int flags,
-                                 const bf16* __restrict__ vq = nullptr, float stg = 0.f) {
-  if (sig_dev) {            // graph replay: the two scalars live in device memory
-    sigma = sig_dev[0];
-    sigma_next = sig_dev[1];
-  }
-  const int s = blockIdx.x * blockDim.x + threadIdx.x;
-  const int cg = blockIdx.y, b = blockIdx.z;
-  if (s >= S) return;
-  const size_t tokoff = ((size_t)b * S + s) * C + cg * 8;
-  const bf16x8 p = *(const bf16x8*)(vp + tokoff);
-  bf16x8 n = p;
-  if (vn) n = *(const bf16x8*)(vn + tokoff);
-  bf16x8 q;
-  if constexpr (STG) q = *(const bf16x8*)(vq + tokoff);
-  float m = 1.f;
-  if (mask) m = mask[(size_t)b * S + s];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const size_t li = ((size_t)b * C + cg * 8 + j) * S + s;
-    float v = (float)p[j];
-    if (vn) v = rbf(v + rbf((cfg - 1.0f) * rbf(v - (float)n[j])));
-    if constexpr (STG) v = rbf(v + rbf(stg * rbf((float)p[j] - (float)q[j])));
-    const float x = (float)lat[li];
-    float x0 = rbf(x - sigma * v);
-    if (mask) x0 = rbf(rbf(x0 * m) + rbf((float)clean[li] * rbf(1.0f - m)));
-    float o = x0;
-    if (flags & LTXK_STEP_BF16_EULER) {
-      // fp32_euler=False (generate.py:748): every op of x0 + s'*(x - x0)/s materialises a bf16 array
-      o = x0 + rbf(__fdiv_rn(rbf(sigma_next * rbf(x - x0)), sigma));
-    } else if (sigma_next > 0.f) {
-      const float t1 = x - x0;
-      const float t2 = sigma_next * t1;
-      o = x0 + __fdiv_rn(t2, sigma);
-    }
-    out[li] = (bf16)o;
-  }
-}
-
-__global__ void euler_kernel(const bf16* __restrict__ x, const bf16* __restrict__ x0, bf16* __restrict__ out,
-                             int64_t n8, float sigma, float sigma_next) {
-  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= n8) return;
-  const bf16x8 a = *(const bf16x8*)(x + idx * 8);
-  const bf16x8 d = *(const bf16x8*)(x0 + idx * 8);
-  bf16x8 o;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const float df = (float)d[j];
-    o[j] = (bf16)(df + __fdiv_rn(sigma_next * ((float)a[j] - df), sigma));
-  }
-  *(bf16x8*)(out + idx * 8) = o;
-}
-
 // One wave.  Row *step of the per-step scalar tables -> the buffers the step's kernels read; *step += 1.
 __global__ void step_scalars_kernel(const bf16* __restrict__ ts_all, const float* __restrict__ sig_all,
                                     int32_t* __restrict__ step, bf16* __restrict__ ts, float* __restrict__ sig,
@@ -578,17 +517,6 @@ extern "C" int ltxk_step_scalars(const void* ts_all, const float* sig_all, int32
   hipLaunchKernelGGL(step_scalars_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (const bf16*)ts_all, sig_all, step,
                      (bf16*)ts, sig, U, n_steps);
   LTXK_CHECK_LAUNCH("ltxk_step_scalars");
-  return LTXK_OK;
-}
-
-extern "C" int ltxk_euler_step(const void* latent, const void* denoised, void* out, int64_t n,
-                               float sigma, float sigma_next, void* stream) {
-  LTXK_CHECK_ARG(latent && denoised && out && n > 0 && n % 8 == 0, "ltxk_euler_step: n must be a positive multiple of 8");
-  LTXK_CHECK_ARG(sigma > 0.f, "ltxk_euler_step: sigma must be > 0");
-  const int64_t n8 = n / 8;
-  hipLaunchKernelGGL(euler_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                     (const bf16*)latent, (const bf16*)denoised, (bf16*)out, n8, sigma, sigma_next);
-  LTXK_CHECK_LAUNCH("ltxk_euler_step");
   return LTXK_OK;
 }
 
@@ -754,51 +682,6 @@ extern "C" int ltxk_latent_to_tokens(const void* latent, void* tokens, int32_t B
   hipLaunchKernelGGL(latent_to_tokens_kernel, dim3((S + 63) / 64, C / 8, B), dim3(64), 0, (hipStream_t)stream,
                      (const bf16*)latent, (bf16*)tokens, B, C, S, rep);
   LTXK_CHECK_LAUNCH("ltxk_latent_to_tokens");
-  return LTXK_OK;
-}
-
-static int cfg_euler_launch(const void* v_pos, const void* v_neg, const void* latent, void* out, const void* clean,
-                            const float* mask, int32_t B, int32_t C, int32_t S, float cfg_scale, float sigma,
-                            float sigma_next, const float* sig_dev, int32_t flags, void* stream, const char* name) {
-  LTXK_CHECK_ARG(v_pos && latent && out && B > 0 && S > 0 && C > 0 && C % 8 == 0, "%s: bad arguments", name);
-  LTXK_CHECK_ARG((clean == nullptr) == (mask == nullptr), "%s: clean and mask must both be set or both NULL", name);
-  LTXK_CHECK_ARG(sig_dev != nullptr || sigma > 0.f, "%s: sigma must be > 0", name);
-  hipLaunchKernelGGL(cfg_euler_kernel<false>, dim3((S + 63) / 64, C / 8, B), dim3(64), 0, (hipStream_t)stream,
-                     (const bf16*)v_pos, (const bf16*)v_neg, (const bf16*)latent, (bf16*)out, (const bf16*)clean, mask,
-                     B, C, S, cfg_scale, sigma, sigma_next, sig_dev, (int)flags, nullptr, 0.f);
-  LTXK_CHECK_LAUNCH(name);
-  return LTXK_OK;
-}
-
-extern "C" int ltxk_cfg_euler_step(const void* v_pos, const void* v_neg, const void* latent, void* out,
-                                   const void* clean, const float* mask, int32_t B, int32_t C, int32_t S,
-                                   float cfg_scale, float sigma, float sigma_next, int32_t flags, void* stream) {
-  return cfg_euler_launch(v_pos, v_neg, latent, out, clean, mask, B, C, S, cfg_scale, sigma, sigma_next, nullptr, flags, stream,
-                          "ltxk_cfg_euler_step");
-}
-
-extern "C" int ltxk_cfg_euler_step_dev(const void* v_pos, const void* v_neg, const void* latent, void* out,
-                                       const void* clean, const float* mask, int32_t B, int32_t C, int32_t S,
-                                       float cfg_scale, const float* sigmas_dev, int32_t flags, void* stream) {
-  LTXK_CHECK_ARG(sigmas_dev != nullptr, "ltxk_cfg_euler_step_dev: null sigmas_dev");
-  return cfg_euler_launch(v_pos, v_neg, latent, out, clean, mask, B, C, S, cfg_scale, 1.f, 0.f, sigmas_dev, flags, stream,
-                          "ltxk_cfg_euler_step_dev");
-}
-
-extern "C" int ltxk_guided_euler_step(const ltxk_step_args* a, void* stream) {
-  LTXK_CHECK_ARG(a != nullptr, "ltxk_guided_euler_step: null args");
-  if (a->v_pert == nullptr)      // no STG term: exactly the launch ltxk_cfg_euler_step(_dev) makes
-    return cfg_euler_launch(a->v_pos, a->v_neg, a->latent, a->out, a->clean, a->mask, a->B, a->C, a->S, a->cfg_scale,
-                            a->sigma, a->sigma_next, a->sigmas_dev, a->flags, stream, "ltxk_guided_euler_step");
-  LTXK_CHECK_ARG(a->v_pos && a->latent && a->out && a->B > 0 && a->S > 0 && a->C > 0 && a->C % 8 == 0,
-                 "ltxk_guided_euler_step: bad arguments");
-  LTXK_CHECK_ARG((a->clean == nullptr) == (a->mask == nullptr), "ltxk_guided_euler_step: clean and mask must both be set or both NULL");
-  LTXK_CHECK_ARG(a->sigmas_dev != nullptr || a->sigma > 0.f, "ltxk_guided_euler_step: sigma must be > 0");
-  hipLaunchKernelGGL(cfg_euler_kernel<true>, dim3((a->S + 63) / 64, a->C / 8, a->B), dim3(64), 0, (hipStream_t)stream,
-                     (const bf16*)a->v_pos, (const bf16*)a->v_neg, (const bf16*)a->latent, (bf16*)a->out, (const bf16*)a->clean,
-                     a->mask, a->B, a->C, a->S, a->cfg_scale, a->sigma, a->sigma_next, a->sigmas_dev, (int)a->flags,
-                     (const bf16*)a->v_pert, a->stg_scale);
-  LTXK_CHECK_LAUNCH("ltxk_guided_euler_step");
   return LTXK_OK;
 }
 

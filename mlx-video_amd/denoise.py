@@ -1,6 +1,6 @@
 """Denoise loops: ``denoise_dev`` (CFG) and ``denoise_distilled`` (mlx_video/generate.py:1060-1327,
 564-881), video branch.  The step body is: tokens <- latent transpose, DiT forward(s), then one
-fused kernel for CFG + x0 + mask blend + Euler (ltxk_cfg_euler_step).
+fused kernel for guidance + x0 + mask blend + Euler (ops.step_tail).
 
 Sigma handling follows the reference exactly (SURVEY.md §7 "bf16-quantised timesteps"):
 timesteps = bf16(sigma)*mask always (generate.py:1084,1237); with ``compile_step`` x0 and Euler
@@ -102,18 +102,15 @@ class _Guidance:
 
     def tail(self, v_pos, v_neg, v_pert, latents, s, s_next, clean, mask_tok, out=None, sigmas_dev=None, bf16_euler=False,
              record=None, workspace=None):
-        if self.guider is not None:   # cfg_star / apg: the reduction launch(es) into the device record, then the tail that reads it
-            g = self.guider
+        kw = {}
+        g = self.guider
+        if g is not None:             # cfg_star / apg: the reduction launch(es) into the device record the tail reads
             record = ops.guidance_sums(v_pos, v_neg, latents, g.kind, s, g.norm_threshold, record=record, workspace=workspace,
                                        sigmas_dev=sigmas_dev)
-            return ops.guider_euler_step(v_pos, v_neg, v_pert, latents, record, g.kind, self.cfg_scale, self.stg_scale, s, s_next,
-                                         g.eta, g.norm_threshold, clean, mask_tok, out=out, sigmas_dev=sigmas_dev,
-                                         bf16_euler=bf16_euler)
-        if v_pert is None:            # no STG: today's CFG step tail, launch for launch
-            return ops.cfg_euler_step(v_pos, v_neg, latents, self.cfg_scale, s, s_next, clean, mask_tok, out=out,
-                                      sigmas_dev=sigmas_dev, bf16_euler=bf16_euler)
-        return ops.guided_euler_step(v_pos, v_neg, v_pert, latents, self.cfg_scale, self.stg_scale, s, s_next, clean, mask_tok,
-                                     out=out, sigmas_dev=sigmas_dev, bf16_euler=bf16_euler)
+            kw = dict(guider=g.kind, record=record, eta=g.eta, norm_threshold=g.norm_threshold)
+        return ops.step_tail(v_pos, v_neg, v_pert, latents, cfg_scale=self.cfg_scale, stg_scale=self.stg_scale, sigma=s,
+                             sigma_next=s_next, clean=clean, mask_tok=mask_tok, out=out, sigmas_dev=sigmas_dev,
+                             bf16_euler=bf16_euler, **kw)
 
 
 def _denoise(latents: torch.Tensor, positions: torch.Tensor, ctx_pos_in: torch.Tensor, ctx_neg_in: Optional[torch.Tensor],
@@ -208,21 +205,13 @@ def denoise_dev(latents: torch.Tensor, positions: torch.Tensor, text_embeddings_
                     compile_step, cfg_batch, use_graph, graph_cache, cache_context, False, stg_scale, pert, stg_key, gcfg)
 
 
-class _StepGraph:
-    """One denoise step as a hipGraph.  First node: ltxk_step_scalars, which reads this step's {timestep values,
-    sigma, sigma_next} from device tables and advances a device-side step counter — so the schedule runs as bare
-    graph replays with no host->device traffic in between; the fused tail updates the latents in place.  The
-    first step of the first run executes eagerly (it doubles as the warm-up torch requires before capture:
-    allocator, lazy hipFuncSetAttribute calls), then the step is captured and every later step is a replay."""
+class _StepInputs:
+    """The persistent per-call inputs of a captured step: the buffers the captured kernels read (latents, clean latent, mask,
+    token -> row map, RoPE table, the per-step scalar tables and the device-side step counter), refreshed by ``load``."""
 
-    def __init__(self, latents, plan: _StepPlan, transformer: LTXModel, ctx_pos, gd: _Guidance, bf16_euler, cache_context):
+    def __init__(self, latents, plan: _StepPlan):
         dev = latents.device
-        self.tr = transformer                       # strong reference: id(transformer) in the cache key stays unique
-        self.gd, self.bf16_euler = gd, bf16_euler
         self.lat_buf = torch.empty_like(latents)
-        # the batched forward's rows pos (| neg) (| pos+); unbatched: pos, and neg for CFG
-        self.ctx_a = torch.empty((gd.reps * ctx_pos.shape[0],) + tuple(ctx_pos.shape[1:]), dtype=BF16, device=dev)
-        self.ctx_b = torch.empty_like(ctx_pos) if (gd.use_cfg and not gd.batched) else None
         self.clean = torch.empty_like(plan.clean) if plan.clean is not None else None
         self.mask_tok = torch.empty_like(plan.mask_tok_f32) if plan.mask_tok_f32 is not None else None
         self.tok2row = torch.empty_like(plan.tok2row)
@@ -232,29 +221,10 @@ class _StepGraph:
         self.step = torch.zeros((1,), dtype=torch.int32, device=dev)
         self.ts_buf = torch.zeros((plan.U,), dtype=BF16, device=dev)
         self.sig_buf = torch.zeros((2,), dtype=torch.float32, device=dev)
-        self.kv_a: Optional[ContextKV] = None
-        self.kv_b: Optional[ContextKV] = None
-        self.cache_context = cache_context
-        # cfg_star / apg: the sums record and the partials workspace, persistent so that the captured launches keep their addresses
-        self.g_rec = self.g_ws = None
-        if gd.guider is not None:
-            bb, cc = latents.shape[:2]
-            self.g_rec = torch.zeros((bb, ops.GUIDER_RECORD_FLOATS), dtype=torch.float32, device=dev)
-            self.g_ws = torch.zeros((ops.guidance_sums_workspace_bytes(bb, cc, latents.numel() // (bb * cc)) // 4,),
-                                    dtype=torch.float32, device=dev)
-        self.graph = None
 
-    def _load(self, latents, plan: _StepPlan, ctx_pos, ctx_neg, pe) -> None:
-        """Refresh every per-call input in the buffers the captured kernels read."""
+    def load(self, latents, plan: _StepPlan, pe) -> None:
+        """Refresh every buffer from this call's inputs and rewind the step counter."""
         self.lat_buf.copy_(latents)
-        if self.gd.batched:
-            n = ctx_pos.shape[0]
-            for r, c in enumerate(self.gd.context_rows(ctx_pos, ctx_neg)):
-                self.ctx_a[r * n:(r + 1) * n].copy_(c)
-        else:
-            self.ctx_a.copy_(ctx_pos)
-            if self.ctx_b is not None:
-                self.ctx_b.copy_(ctx_neg)
         if self.clean is not None:
             self.clean.copy_(plan.clean)
             self.mask_tok.copy_(plan.mask_tok_f32)
@@ -269,21 +239,66 @@ class _StepGraph:
         self.ts_all[:nst].copy_(plan.ts_host)
         self.sig_all[:nst].copy_(plan.sig_host)
         self.step.zero_()
+
+    def next_step(self) -> TimestepPlan:
+        """The ltxk_step_scalars node: this step's timestep values -> ``ts_buf``, {sigma, sigma_next} -> ``sig_buf``, and the
+        device-side step counter advances."""
+        ops.step_scalars(self.ts_all, self.sig_all, self.step, self.ts_buf, self.sig_buf)
+        return TimestepPlan(self.ts_buf, self.tok2row)
+
+
+class _StepGraph:
+    """One denoise step as a hipGraph.  First node: ltxk_step_scalars, which reads this step's {timestep values,
+    sigma, sigma_next} from device tables and advances a device-side step counter — so the schedule runs as bare
+    graph replays with no host->device traffic in between; the fused tail updates the latents in place.  The
+    first step of the first run executes eagerly (it doubles as the warm-up torch requires before capture:
+    allocator, lazy hipFuncSetAttribute calls), then the step is captured and every later step is a replay."""
+
+    def __init__(self, latents, plan: _StepPlan, transformer: LTXModel, ctx_pos, gd: _Guidance, bf16_euler, cache_context):
+        dev = latents.device
+        self.tr = transformer                       # strong reference: id(transformer) in the cache key stays unique
+        self.gd, self.bf16_euler = gd, bf16_euler
+        self.inp = _StepInputs(latents, plan)
+        # the batched forward's rows pos (| neg) (| pos+); unbatched: pos, and neg for CFG
+        self.ctx_a = torch.empty((gd.reps * ctx_pos.shape[0],) + tuple(ctx_pos.shape[1:]), dtype=BF16, device=dev)
+        self.ctx_b = torch.empty_like(ctx_pos) if (gd.use_cfg and not gd.batched) else None
+        self.kv_a: Optional[ContextKV] = None
+        self.kv_b: Optional[ContextKV] = None
+        self.cache_context = cache_context
+        # cfg_star / apg: the sums record and the partials workspace, persistent so that the captured launches keep their addresses
+        self.g_rec = self.g_ws = None
+        if gd.guider is not None:
+            bb, cc = latents.shape[:2]
+            self.g_rec = torch.zeros((bb, ops.GUIDER_RECORD_FLOATS), dtype=torch.float32, device=dev)
+            self.g_ws = torch.zeros((ops.guidance_sums_workspace_bytes(bb, cc, latents.numel() // (bb * cc)) // 4,),
+                                    dtype=torch.float32, device=dev)
+        self.graph = None
+
+    def _load(self, latents, plan: _StepPlan, ctx_pos, ctx_neg, pe) -> None:
+        """Refresh every per-call input in the buffers the captured kernels read."""
+        self.inp.load(latents, plan, pe)
+        if self.gd.batched:
+            n = ctx_pos.shape[0]
+            for r, c in enumerate(self.gd.context_rows(ctx_pos, ctx_neg)):
+                self.ctx_a[r * n:(r + 1) * n].copy_(c)
+        else:
+            self.ctx_a.copy_(ctx_pos)
+            if self.ctx_b is not None:
+                self.ctx_b.copy_(ctx_neg)
         if self.cache_context:
             self.kv_a = self.tr.prepare_context(self.ctx_a, out=self.kv_a)
             if self.ctx_b is not None:
                 self.kv_b = self.tr.prepare_context(self.ctx_b, out=self.kv_b)
 
     def _step(self):
-        ops.step_scalars(self.ts_all, self.sig_all, self.step, self.ts_buf, self.sig_buf)
-        tp = TimestepPlan(self.ts_buf, self.tok2row)
-        gd = self.gd
+        gd, inp = self.gd, self.inp
+        tp = inp.next_step()
         if gd.batched:
-            v_pos, v_neg, v_pert = gd.velocities(self.tr, self.lat_buf, tp, self.pe, self.ctx_a, self.kv_a, None, None, None, None)
+            v_pos, v_neg, v_pert = gd.velocities(self.tr, inp.lat_buf, tp, inp.pe, self.ctx_a, self.kv_a, None, None, None, None)
         else:
-            v_pos, v_neg, v_pert = gd.velocities(self.tr, self.lat_buf, tp, self.pe, None, None, self.ctx_a, self.kv_a,
+            v_pos, v_neg, v_pert = gd.velocities(self.tr, inp.lat_buf, tp, inp.pe, None, None, self.ctx_a, self.kv_a,
                                                  self.ctx_b, self.kv_b)
-        gd.tail(v_pos, v_neg, v_pert, self.lat_buf, 1.0, 0.0, self.clean, self.mask_tok, out=self.lat_buf, sigmas_dev=self.sig_buf,
+        gd.tail(v_pos, v_neg, v_pert, inp.lat_buf, 1.0, 0.0, inp.clean, inp.mask_tok, out=inp.lat_buf, sigmas_dev=inp.sig_buf,
                 bf16_euler=self.bf16_euler, record=self.g_rec, workspace=self.g_ws)
 
     def run(self, latents, plan: _StepPlan, ctx_pos, ctx_neg, pe) -> torch.Tensor:
@@ -303,7 +318,7 @@ class _StepGraph:
             start = 1
         for _ in range(start, nst):
             self.graph.replay()
-        return self.lat_buf.clone()
+        return self.inp.lat_buf.clone()
 
 
 def _eager_tail(gd: _Guidance, v_pos, v_neg, v_pert, latents, s_bf, s, s_next, plan):

@@ -500,115 +500,43 @@ def latent_to_tokens(latent: torch.Tensor, rep: int = 1) -> torch.Tensor:
     return out
 
 
-def cfg_euler_step(v_pos: torch.Tensor, v_neg: Optional[torch.Tensor], latent: torch.Tensor, cfg_scale: float,
-                   sigma: float, sigma_next: float, clean: Optional[torch.Tensor] = None,
-                   mask_tok: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
-                   sigmas_dev: Optional[torch.Tensor] = None, bf16_euler: bool = False) -> torch.Tensor:
-    """v_* (B,S,C) tokens; latent (B,C,...) channels-first; mask_tok (B,S) float32.  With ``sigmas_dev`` (2
-    float32 on the device) the scalars are read from device memory (hipGraph replay).  ``out`` may be
-    ``latent`` itself (each element is read and written by one thread).  ``bf16_euler``: the reference's
-    fp32_euler=False compiled step (generate.py:741-748)."""
-    _req(latent, BF16, "cfg_euler_step.latent")
-    B, C = latent.shape[:2]
-    S = latent.numel() // (B * C)
-    if out is None:
-        out = torch.empty_like(latent)
-    if sigmas_dev is not None:
-        check(_lib.load().ltxk_cfg_euler_step_dev(_p(v_pos), _p(v_neg), _p(latent), _p(out), _p(clean), _p(mask_tok),
-                                                  B, C, S, cfg_scale, _p(sigmas_dev), int(bf16_euler), _stream()),
-              "ltxk_cfg_euler_step_dev")
-        return out
-    check(_lib.load().ltxk_cfg_euler_step(_p(v_pos), _p(v_neg), _p(latent), _p(out), _p(clean), _p(mask_tok),
-                                          B, C, S, cfg_scale, sigma, sigma_next, int(bf16_euler), _stream()),
-          "ltxk_cfg_euler_step")
-    return out
-
-
-def guided_euler_step(v_pos: torch.Tensor, v_neg: Optional[torch.Tensor], v_pert: Optional[torch.Tensor], latent: torch.Tensor,
-                      cfg_scale: float, stg_scale: float, sigma: float, sigma_next: float, clean: Optional[torch.Tensor] = None,
-                      mask_tok: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
-                      sigmas_dev: Optional[torch.Tensor] = None, bf16_euler: bool = False) -> torch.Tensor:
-    """``cfg_euler_step`` with the STG term (ltxk_guided_euler_step): v_pert (B,S,C) is the velocity of the perturbed
-    forward; v = bf16(g + bf16(stg_scale * bf16(v_pos - v_pert))) with g the CFG-guided velocity.  ``v_pert=None``: the
-    launch cfg_euler_step makes."""
-    _req(latent, BF16, "guided_euler_step.latent")
-    _req(v_pos, BF16, "guided_euler_step.v_pos")
-    B, C = latent.shape[:2]
-    S = latent.numel() // (B * C)
-    for name, t in (("v_pos", v_pos), ("v_neg", v_neg), ("v_pert", v_pert)):
-        if t is None:
-            continue
-        _req(t, BF16, f"guided_euler_step.{name}")
-        if t.numel() != B * S * C or not t.is_contiguous():
-            raise ValueError(f"guided_euler_step: {name} must be a contiguous (B,S,C) = ({B},{S},{C}) tensor, got {tuple(t.shape)}")
-    if not latent.is_contiguous():
-        raise ValueError("guided_euler_step: latent must be contiguous")
-    if (clean is None) != (mask_tok is None):
-        raise ValueError("guided_euler_step: clean and mask_tok must both be given or both be None")
-    if clean is not None:
-        _req(clean, BF16, "guided_euler_step.clean")
-        _req(mask_tok, torch.float32, "guided_euler_step.mask_tok")
-    if sigmas_dev is not None:
-        _req(sigmas_dev, torch.float32, "guided_euler_step.sigmas_dev")
-    if out is None:
-        out = torch.empty_like(latent)
-    a = StepArgs()
-    a.v_pos, a.v_neg, a.v_pert, a.latent, a.out = _p(v_pos), _p(v_neg), _p(v_pert), _p(latent), _p(out)
-    a.clean, a.mask, a.sigmas_dev = _p(clean), _p(mask_tok), _p(sigmas_dev)
-    a.B, a.C, a.S = B, C, S
-    a.cfg_scale, a.stg_scale, a.sigma, a.sigma_next = cfg_scale, stg_scale, sigma, sigma_next
-    a.flags = int(bf16_euler)
-    check(_lib.load().ltxk_guided_euler_step(ctypes.byref(a), _stream()), "ltxk_guided_euler_step")
-    return out
-
-
 GUIDER_IDS = {"cfg_star": _lib.GUIDER_CFG_STAR, "apg": _lib.GUIDER_APG}
 GUIDER_RECORD_FLOATS = _lib.GUIDER_RECORD_FLOATS
 
 
-def guidance_sums_workspace_bytes(B: int, C: int, S: int) -> int:
-    """Bytes of the partial-sum workspace ``guidance_sums`` needs for (B,C,S) (ltxk_guidance_sums_workspace_bytes)."""
-    n = int(_lib.load().ltxk_guidance_sums_workspace_bytes(B, C, S))
-    if n < 0:
-        raise ValueError(f"guidance_sums_workspace_bytes: bad shape B={B} C={C} S={S} (C must be a multiple of 8)")
-    return n
-
-
-def _guider_args(who: str, guider: str, v_pos, v_neg, v_pert, latent, eta, norm_threshold, clean, mask_tok, sigmas_dev) -> GuiderArgs:
-    """The dtype, shape and contiguity checks of ``guided_euler_step`` plus the guider's own; the filled common fields."""
-    if guider not in GUIDER_IDS:
-        raise ValueError(f"{who}: unknown guider {guider!r} (expected one of {sorted(GUIDER_IDS)}; plain CFG is cfg_euler_step)")
-    eta, norm_threshold = float(eta), float(norm_threshold)
-    if not math.isfinite(eta):
-        raise ValueError(f"{who}: eta must be finite, got {eta}")
-    if not (math.isfinite(norm_threshold) and norm_threshold >= 0.0):
-        raise ValueError(f"{who}: norm_threshold must be finite and >= 0, got {norm_threshold}")
-    if v_neg is None:
-        raise ValueError(f"{who}: v_neg is required (the guider compares the positive with the negative prediction)")
-    _req(latent, BF16, f"{who}.latent")
-    _req(v_pos, BF16, f"{who}.v_pos")
+def _step_tail_args(who: str, v_pos, v_neg, v_pert, latent, guider: str, eta, norm_threshold, clean, mask_tok, sigmas_dev):
+    """The one validator of the step-tail family, and the input fields it checked in the struct of the entry that runs
+    ``guider``: a StepArgs for "cfg", a GuiderArgs for "cfg_star" / "apg".  Nothing is launched on a tensor it refuses."""
+    if guider != "cfg":
+        if guider not in GUIDER_IDS:
+            raise ValueError(f"{who}: unknown guider {guider!r} (expected 'cfg' or one of {sorted(GUIDER_IDS)})")
+        eta, norm_threshold = float(eta), float(norm_threshold)
+        if not math.isfinite(eta):
+            raise ValueError(f"{who}: eta must be finite, got {eta}")
+        if not (math.isfinite(norm_threshold) and norm_threshold >= 0.0):
+            raise ValueError(f"{who}: norm_threshold must be finite and >= 0, got {norm_threshold}")
+        if v_neg is None:
+            raise ValueError(f"{who}: v_neg is required (the guider compares the positive with the negative prediction)")
+    if v_pos is None or (clean is None) != (mask_tok is None):
+        raise ValueError(f"{who}: v_pos is required; clean and mask_tok must both be given or both be None")
     B, C = latent.shape[:2]
-    S = latent.numel() // (B * C)
-    for name, t in (("v_pos", v_pos), ("v_neg", v_neg), ("v_pert", v_pert)):
-        if t is None:
-            continue
-        _req(t, BF16, f"{who}.{name}")
-        if t.numel() != B * S * C or not t.is_contiguous():
-            raise ValueError(f"{who}: {name} must be a contiguous (B,S,C) = ({B},{S},{C}) tensor, got {tuple(t.shape)}")
-    if not latent.is_contiguous():
-        raise ValueError(f"{who}: latent must be contiguous")
-    if (clean is None) != (mask_tok is None):
-        raise ValueError(f"{who}: clean and mask_tok must both be given or both be None")
-    if clean is not None:
-        _req(clean, BF16, f"{who}.clean")
-        _req(mask_tok, torch.float32, f"{who}.mask_tok")
-    if sigmas_dev is not None:
-        _req(sigmas_dev, torch.float32, f"{who}.sigmas_dev")
-    a = GuiderArgs()
+    S = latent.numel() // max(B * C, 1)
+    given = [w for w in (("latent", latent, BF16, B * C * S, "(B,C,...)"), ("v_pos", v_pos, BF16, B * S * C, "(B,S,C)"),
+                         ("v_neg", v_neg, BF16, B * S * C, "(B,S,C)"), ("v_pert", v_pert, BF16, B * S * C, "(B,S,C)"),
+                         ("clean", clean, BF16, B * C * S, "(B,C,S)"), ("mask_tok", mask_tok, torch.float32, B * S, "(B,S)"),
+                         ("sigmas_dev", sigmas_dev, torch.float32, 2, "(2,)")) if w[1] is not None]
+    for name, t, dtype, n, shape in given:          # the kernels index every tensor as a dense array of exactly this size
+        if t.numel() != n or not t.is_contiguous():
+            raise ValueError(f"{who}: {name} must be a contiguous {shape} tensor of {n} elements (B,C,S = {B},{C},{S}), "
+                             f"got {tuple(t.shape)} with strides {tuple(t.stride())}")
+    for name, t, dtype, n, shape in given:
+        _req(t, dtype, f"{who}.{name}")
+    a = StepArgs() if guider == "cfg" else GuiderArgs()
     a.v_pos, a.v_neg, a.v_pert, a.latent = _p(v_pos), _p(v_neg), _p(v_pert), _p(latent)
     a.clean, a.mask, a.sigmas_dev = _p(clean), _p(mask_tok), _p(sigmas_dev)
-    a.B, a.C, a.S, a.guider = B, C, S, GUIDER_IDS[guider]
-    a.eta, a.norm_threshold = eta, norm_threshold
+    a.B, a.C, a.S = B, C, S
+    if guider != "cfg":
+        a.guider, a.eta, a.norm_threshold = GUIDER_IDS[guider], eta, norm_threshold
     return a
 
 
@@ -623,14 +551,84 @@ def _guider_record(who: str, record: Optional[torch.Tensor], B: int, device, mak
     return record
 
 
+def step_tail(v_pos: torch.Tensor, v_neg: Optional[torch.Tensor], v_pert: Optional[torch.Tensor], latent: torch.Tensor, *,
+              cfg_scale: float, stg_scale: float = 0.0, sigma: float, sigma_next: float, guider: str = "cfg",
+              record: Optional[torch.Tensor] = None, eta: float = 1.0, norm_threshold: float = 0.0,
+              clean: Optional[torch.Tensor] = None, mask_tok: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+              sigmas_dev: Optional[torch.Tensor] = None, bf16_euler: bool = False) -> torch.Tensor:
+    """One denoise-step tail, one launch: guidance -> x0 -> mask blend -> Euler.  v_* (B,S,C) tokens; latent (B,C,...)
+    channels-first; mask_tok (B,S) float32.  ``guider`` "cfg": the velocity-space CFG combine (``v_neg=None``: none), and with
+    ``v_pert`` - the velocity of the perturbed forward - the STG term v = bf16(g + bf16(stg_scale * bf16(v_pos - v_pert)))
+    (ltxk_guided_euler_step).  "cfg_star" / "apg": the guider's delta and the STG term in x0 space with the scalars of
+    ``record`` (from ``guidance_sums`` on the same inputs; ltxk_guider_euler_step).  With ``sigmas_dev`` (2 float32 on the
+    device) the scalars are read from device memory (hipGraph replay).  ``out`` may be ``latent`` itself (each element is
+    read and written by one thread).  ``bf16_euler``: the reference's fp32_euler=False compiled step (generate.py:741-748)."""
+    a = _step_tail_args("step_tail", v_pos, v_neg, v_pert, latent, guider, eta, norm_threshold, clean, mask_tok, sigmas_dev)
+    if out is None:
+        out = torch.empty_like(latent)
+    _req(out, BF16, "step_tail.out")
+    if out.numel() != latent.numel() or not out.is_contiguous():
+        raise ValueError(f"step_tail: out must be a contiguous tensor of the latent's size, got {tuple(out.shape)}")
+    a.out = _p(out)
+    a.cfg_scale, a.stg_scale, a.sigma, a.sigma_next = cfg_scale, stg_scale, sigma, sigma_next
+    a.flags = int(bf16_euler)
+    if guider == "cfg":
+        check(_lib.load().ltxk_guided_euler_step(ctypes.byref(a), _stream()), "ltxk_guided_euler_step")
+    else:
+        a.record = _p(_guider_record("step_tail", record, a.B, latent.device, make=False))
+        check(_lib.load().ltxk_guider_euler_step(ctypes.byref(a), _stream()), "ltxk_guider_euler_step")
+    return out
+
+
+def cfg_euler_step(v_pos: torch.Tensor, v_neg: Optional[torch.Tensor], latent: torch.Tensor, cfg_scale: float,
+                   sigma: float, sigma_next: float, clean: Optional[torch.Tensor] = None,
+                   mask_tok: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                   sigmas_dev: Optional[torch.Tensor] = None, bf16_euler: bool = False) -> torch.Tensor:
+    """``step_tail`` with plain CFG and no STG term."""
+    return step_tail(v_pos, v_neg, None, latent, cfg_scale=cfg_scale, sigma=sigma, sigma_next=sigma_next, clean=clean,
+                     mask_tok=mask_tok, out=out, sigmas_dev=sigmas_dev, bf16_euler=bf16_euler)
+
+
+def guided_euler_step(v_pos: torch.Tensor, v_neg: Optional[torch.Tensor], v_pert: Optional[torch.Tensor], latent: torch.Tensor,
+                      cfg_scale: float, stg_scale: float, sigma: float, sigma_next: float, clean: Optional[torch.Tensor] = None,
+                      mask_tok: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                      sigmas_dev: Optional[torch.Tensor] = None, bf16_euler: bool = False) -> torch.Tensor:
+    """``step_tail`` with plain CFG and the STG term of ``v_pert`` (None: the launch ``cfg_euler_step`` makes)."""
+    return step_tail(v_pos, v_neg, v_pert, latent, cfg_scale=cfg_scale, stg_scale=stg_scale, sigma=sigma, sigma_next=sigma_next,
+                     clean=clean, mask_tok=mask_tok, out=out, sigmas_dev=sigmas_dev, bf16_euler=bf16_euler)
+
+
+def guider_euler_step(v_pos: torch.Tensor, v_neg: torch.Tensor, v_pert: Optional[torch.Tensor], latent: torch.Tensor,
+                      record: torch.Tensor, guider: str, cfg_scale: float, stg_scale: float, sigma: float, sigma_next: float,
+                      eta: float = 1.0, norm_threshold: float = 0.0, clean: Optional[torch.Tensor] = None,
+                      mask_tok: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                      sigmas_dev: Optional[torch.Tensor] = None, bf16_euler: bool = False) -> torch.Tensor:
+    """``step_tail`` under the ``cfg_star`` / ``apg`` guider; plain CFG is ``cfg_euler_step``."""
+    if guider == "cfg":
+        raise ValueError("guider_euler_step: 'cfg' is not a guider id here (plain CFG is cfg_euler_step)")
+    return step_tail(v_pos, v_neg, v_pert, latent, cfg_scale=cfg_scale, stg_scale=stg_scale, sigma=sigma, sigma_next=sigma_next,
+                     guider=guider, record=record, eta=eta, norm_threshold=norm_threshold, clean=clean, mask_tok=mask_tok, out=out,
+                     sigmas_dev=sigmas_dev, bf16_euler=bf16_euler)
+
+
+def guidance_sums_workspace_bytes(B: int, C: int, S: int) -> int:
+    """Bytes of the partial-sum workspace ``guidance_sums`` needs for (B,C,S) (ltxk_guidance_sums_workspace_bytes)."""
+    n = int(_lib.load().ltxk_guidance_sums_workspace_bytes(B, C, S))
+    if n < 0:
+        raise ValueError(f"guidance_sums_workspace_bytes: bad shape B={B} C={C} S={S} (C must be a multiple of 8)")
+    return n
+
+
 def guidance_sums(v_pos: torch.Tensor, v_neg: torch.Tensor, latent: torch.Tensor, guider: str, sigma: float,
                   norm_threshold: float = 0.0, record: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None,
                   sigmas_dev: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The per-sample sums and derived scalars of the ``cfg_star`` / ``apg`` guider (ltxk_guidance_sums): v_* (B,S,C) tokens,
-    latent (B,C,...) -> ``record`` (B,8) float32 in device memory (layout: include/ltxk.h), which ``guider_euler_step`` reads.
+    latent (B,C,...) -> ``record`` (B,8) float32 in device memory (layout: include/ltxk.h), which ``step_tail`` reads.
     Deterministic (no atomics; the summation order depends on (C,S) only).  ``workspace``: a float32 device tensor of at least
     ``guidance_sums_workspace_bytes`` bytes (allocated when None).  ``sigmas_dev``: sigma is read from device memory."""
-    a = _guider_args("guidance_sums", guider, v_pos, v_neg, None, latent, 1.0, norm_threshold, None, None, sigmas_dev)
+    if guider == "cfg":
+        raise ValueError("guidance_sums: 'cfg' is not a guider id here (plain CFG has no sums)")
+    a = _step_tail_args("guidance_sums", v_pos, v_neg, None, latent, guider, 1.0, norm_threshold, None, None, sigmas_dev)
     need = guidance_sums_workspace_bytes(a.B, a.C, a.S)
     if workspace is None:
         workspace = torch.empty((need // 4,), dtype=torch.float32, device=latent.device)
@@ -642,25 +640,6 @@ def guidance_sums(v_pos: torch.Tensor, v_neg: torch.Tensor, latent: torch.Tensor
     a.sigma = sigma
     check(_lib.load().ltxk_guidance_sums(ctypes.byref(a), _stream()), "ltxk_guidance_sums")
     return record
-
-
-def guider_euler_step(v_pos: torch.Tensor, v_neg: torch.Tensor, v_pert: Optional[torch.Tensor], latent: torch.Tensor,
-                      record: torch.Tensor, guider: str, cfg_scale: float, stg_scale: float, sigma: float, sigma_next: float,
-                      eta: float = 1.0, norm_threshold: float = 0.0, clean: Optional[torch.Tensor] = None,
-                      mask_tok: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
-                      sigmas_dev: Optional[torch.Tensor] = None, bf16_euler: bool = False) -> torch.Tensor:
-    """The step tail under the ``cfg_star`` / ``apg`` guider (ltxk_guider_euler_step): the guider's delta in x0 space with the
-    scalars of ``record`` (from ``guidance_sums`` on the same inputs), the STG term when ``v_pert`` is given, then mask blend
-    and Euler as ``cfg_euler_step``.  ``out`` may be ``latent``."""
-    a = _guider_args("guider_euler_step", guider, v_pos, v_neg, v_pert, latent, eta, norm_threshold, clean, mask_tok, sigmas_dev)
-    record = _guider_record("guider_euler_step", record, a.B, latent.device, make=False)
-    if out is None:
-        out = torch.empty_like(latent)
-    a.record, a.out = _p(record), _p(out)
-    a.cfg_scale, a.stg_scale, a.sigma, a.sigma_next = cfg_scale, stg_scale, sigma, sigma_next
-    a.flags = int(bf16_euler)
-    check(_lib.load().ltxk_guider_euler_step(ctypes.byref(a), _stream()), "ltxk_guider_euler_step")
-    return out
 
 
 def attn_value_passthrough(vt: torch.Tensor, out: torch.Tensor, B: int, T: int, row_mask: int) -> torch.Tensor:

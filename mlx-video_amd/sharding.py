@@ -9,7 +9,7 @@ redundantly run the fused CFG + x0 + Euler kernel, so the latents stay replicate
 One process per GPU; the weights are a full replica per rank (26 GB of 288 GB).
 
 The step is latency-bound, so the HIP path keeps the host out of it: the forward (with the device-side
-step-scalar node, see denoise._StepGraph) is one captured hipGraph, the fused tail a second one, and the
+step-scalar node, see denoise._StepInputs) is one captured hipGraph, the fused tail a second one, and the
 only eager call between them is the collective itself — no per-step allocation, host->device copy or
 Python tensor op.  No 1/2/4/8-GPU curve has been measured on hardware yet."""
 from __future__ import annotations
@@ -73,7 +73,7 @@ class CfgPairSharding:
     def _denoise_hip(self, latents, positions, ctx_pos, ctx_neg, transformer, sig, cfg_scale, state, use_graph):
         from . import ops
         from .denoise import GRAPH_MAX_STEPS, _StepPlan
-        from .ltx_model import TimestepPlan, precompute_freqs_cis
+        from .ltx_model import precompute_freqs_cis
         BF16 = torch.bfloat16
         latents = (state.latent if state is not None else latents).to(BF16).contiguous()
         pe = precompute_freqs_cis(positions[:1].contiguous(), transformer.inner_dim, transformer.positional_embedding_theta,
@@ -100,56 +100,34 @@ class _ShardGraphs:
     """Forward graph | eager all_gather_into_tensor | tail graph, with persistent buffers refreshed per call."""
 
     def __init__(self, sh: CfgPairSharding, latents, plan, transformer, ctx, cfg_scale):
-        from .denoise import GRAPH_MAX_STEPS
-        BF16 = torch.bfloat16
-        dev = latents.device
+        from .denoise import _StepInputs
         self.sh, self.tr, self.cfg_scale = sh, transformer, cfg_scale
-        self.lat_buf = torch.empty_like(latents)
+        self.inp = _StepInputs(latents, plan)
         self.ctx = torch.empty_like(ctx)
-        self.clean = torch.empty_like(plan.clean) if plan.clean is not None else None
-        self.mask_tok = torch.empty_like(plan.mask_tok_f32) if plan.mask_tok_f32 is not None else None
-        self.tok2row = torch.empty_like(plan.tok2row)
-        self.pe = None
-        self.ts_all = torch.zeros((GRAPH_MAX_STEPS, plan.U), dtype=BF16, device=dev)
-        self.sig_all = torch.zeros((GRAPH_MAX_STEPS, 2), dtype=torch.float32, device=dev)
-        self.step = torch.zeros((1,), dtype=torch.int32, device=dev)
-        self.ts_buf = torch.zeros((plan.U,), dtype=BF16, device=dev)
-        self.sig_buf = torch.zeros((2,), dtype=torch.float32, device=dev)
         b, _, f, h, w = latents.shape
         self.b = b
-        self.vbuf = torch.empty((2 * b, f * h * w, transformer.config.out_channels), dtype=BF16, device=dev)
+        self.vbuf = torch.empty((2 * b, f * h * w, transformer.config.out_channels), dtype=torch.bfloat16, device=latents.device)
         self.v_local = None
         self.g_fwd = self.g_tail = None
 
     def _fwd(self):
         from . import ops
-        from .ltx_model import TimestepPlan
-        ops.step_scalars(self.ts_all, self.sig_all, self.step, self.ts_buf, self.sig_buf)
-        return self.tr.forward_tokens(ops.latent_to_tokens(self.lat_buf), TimestepPlan(self.ts_buf, self.tok2row), self.ctx, self.pe)
+        inp = self.inp
+        return self.tr.forward_tokens(ops.latent_to_tokens(inp.lat_buf), inp.next_step(), self.ctx, inp.pe)
 
     def _tail(self):
         from . import ops
-        ops.cfg_euler_step(self.vbuf[:self.b], self.vbuf[self.b:], self.lat_buf, self.cfg_scale, 1.0, 0.0, self.clean, self.mask_tok,
-                           out=self.lat_buf, sigmas_dev=self.sig_buf)
+        inp = self.inp
+        ops.cfg_euler_step(self.vbuf[:self.b], self.vbuf[self.b:], inp.lat_buf, self.cfg_scale, 1.0, 0.0, inp.clean, inp.mask_tok,
+                           out=inp.lat_buf, sigmas_dev=inp.sig_buf)
 
     def _gather(self):
         self.sh.dist.all_gather_into_tensor(self.vbuf, self.v_local, group=self.sh.group)
 
     def run(self, latents, plan, ctx, pe):
-        self.lat_buf.copy_(latents)
+        self.inp.load(latents, plan, pe)
         self.ctx.copy_(ctx)
-        if self.clean is not None:
-            self.clean.copy_(plan.clean)
-            self.mask_tok.copy_(plan.mask_tok_f32)
-        self.tok2row.copy_(plan.tok2row)
-        if self.pe is None:
-            self.pe = (pe[0].clone(), pe[1].clone())
-        else:
-            self.pe[0].copy_(pe[0]); self.pe[1].copy_(pe[1])
         nst = plan.ts_host.shape[0]
-        self.ts_all[:nst].copy_(plan.ts_host)
-        self.sig_all[:nst].copy_(plan.sig_host)
-        self.step.zero_()
         start = 0
         if self.g_fwd is None:
             side = torch.cuda.Stream()
@@ -171,4 +149,4 @@ class _ShardGraphs:
             self.g_fwd.replay()
             self._gather()
             self.g_tail.replay()
-        return self.lat_buf.clone()
+        return self.inp.lat_buf.clone()

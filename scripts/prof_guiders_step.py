@@ -9,7 +9,8 @@ Prints one JSON line per form (median / min ms per step over the rounds) and the
 `--root`: import the package from another checkout (built there) - `--forms cfg --root <parent commit>` measures the parent's
 CFG step with the same script; `cfg` passes no guider keyword, so it runs on a commit that has none.
 Under `rocprofv3 --kernel-trace --stats -- python scripts/prof_guiders_step.py --forms cfg_star apg_clamp --rounds 1` the stats
-list guider_partial_kernel, guider_finish_kernel and guider_euler_kernel beside the step's other kernels."""
+list guider_partial_kernel, guider_finish_kernel and the step tail (step_tail_kernel<guider, STG>; 0 = plain CFG) beside the step's
+other kernels."""
 import argparse
 import json
 import os

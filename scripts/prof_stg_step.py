@@ -6,7 +6,8 @@ whole-step graph replay.  Three forms in interleaved rounds in one process:
 Prints one JSON line per form (median / min ms per step over the rounds) and the ratios to `cfg`.
   python scripts/prof_stg_step.py [--layers 48] [--steps 8] [--rounds 3] [--only stg29]
 Under `rocprofv3 --kernel-trace --stats -- python scripts/prof_stg_step.py --only stg29 --rounds 1` the stats list the
-value-passthrough kernel (value_passthrough_kernel) beside the step's other kernels."""
+value-passthrough kernel (value_passthrough_kernel) and the step tail (step_tail_kernel<0, true>; <0, false> for `cfg`) beside the
+step's other kernels."""
 import argparse
 import json
 import os

@@ -231,6 +231,41 @@ def test_library_refuses_bad_guider_structs():
     assert lib.ltxk_guidance_sums(None, None) == -1 and lib.ltxk_guider_euler_step(None, None) == -1
 
 
+def test_every_tail_entry_refuses_grid_overflow_and_misaligned_tokens():
+    """The four step-tail entries share one host check: B or C/8 past a grid dimension and a token pointer off a 16-byte
+    boundary are LTXK_EINVAL under the entry's own name, before any launch (stand-in pointers, no GPU is touched).  And the
+    host wrapper of the plain tail refuses what the kernel would misread."""
+    from mlx_video_amd import _lib, ops
+    lib = _lib.load()
+    buf = 4096
+
+    def call(entry, B=1, C=128, v_pos=buf, v_neg=buf):
+        if entry == "ltxk_cfg_euler_step":
+            return lib.ltxk_cfg_euler_step(v_pos, v_neg, buf, buf, None, None, B, C, 64, 6.0, 0.5, 0.25, 0, None)
+        if entry == "ltxk_cfg_euler_step_dev":
+            return lib.ltxk_cfg_euler_step_dev(v_pos, v_neg, buf, buf, None, None, B, C, 64, 6.0, buf, 0, None)
+        a = _lib.StepArgs() if entry == "ltxk_guided_euler_step" else _lib.GuiderArgs()
+        a.v_pos, a.v_neg, a.latent, a.out = v_pos, v_neg, buf, buf
+        a.B, a.C, a.S = B, C, 64
+        a.cfg_scale, a.sigma, a.sigma_next = 6.0, 0.5, 0.25
+        if entry == "ltxk_guider_euler_step":
+            a.record, a.guider, a.eta = buf, _lib.GUIDER_APG, 1.0
+        return getattr(lib, entry)(ctypes.byref(a), None)
+
+    for entry in ("ltxk_cfg_euler_step", "ltxk_cfg_euler_step_dev", "ltxk_guided_euler_step", "ltxk_guider_euler_step"):
+        for over, why in ((dict(B=65536), "grid dimension"), (dict(C=8 * 65536), "grid dimension"),
+                          (dict(v_pos=buf + 8), "16-byte"), (dict(v_neg=buf + 2), "16-byte")):
+            assert call(entry, **over) == -1, (entry, over)
+            msg = lib.ltxk_last_error().decode()
+            assert msg.startswith(entry + ":") and why in msg, (entry, over, msg)
+    x = torch.zeros(1, 128, 4, dtype=torch.bfloat16)
+    v = torch.zeros(1, 4, 128, dtype=torch.bfloat16)
+    with pytest.raises(ValueError, match="v_pos must be a contiguous"):
+        ops.cfg_euler_step(torch.zeros(1, 128, 4, dtype=torch.bfloat16).transpose(1, 2), v, x, 4.0, 0.5, 0.25)
+    with pytest.raises(ValueError, match="v_neg must be a contiguous"):
+        ops.cfg_euler_step(v, torch.zeros(1, 3, 128, dtype=torch.bfloat16), x, 4.0, 0.5, 0.25)
+
+
 # -------------------------------------------------------------------------------------------------------------- C ABI
 def test_header_binding_and_library_agree_on_the_guider_entries():
     from mlx_video_amd import _lib

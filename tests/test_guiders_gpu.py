@@ -266,6 +266,23 @@ def test_plain_cfg_is_unchanged(dev, small):
     assert len(c1) == 4 and set(c0) < set(c1)
 
 
+def test_cached_graph_refreshes_every_step_input(dev, small):
+    """Two calls through one cached step graph, same geometry, other latents, clean latent and mask (other mask values, so
+    other timestep tables and another token -> row map): each equals the eager loop of its own inputs bit for bit.  Catches a
+    persistent step input (denoise._StepInputs) that a later call does not refresh."""
+    g = torch.Generator().manual_seed(73)
+    lat2, clean2 = (torch.randn(1, 128, F_, H_, W_, generator=g).to(BF).to(dev) for _ in range(2))
+    mask2 = torch.ones(1, 1, F_, 1, 1)
+    mask2[:, :, 1] = 0.5                                     # first call: frame 0 clean; this one: frame 1 half denoised
+    other = dict(small, lat=lat2, clean=clean2, mask=mask2.to(BF).to(dev))
+    cache = {}
+    for m in (small, other, small):
+        got = _run(m, cfg_batch=True, use_graph=True, graph_cache=cache)
+        assert torch.equal(_bits(got), _bits(_run(m, cfg_batch=True)))
+    assert len(cache) == 1
+    assert not torch.equal(_run(other, cfg_batch=True), _run(small, cfg_batch=True))
+
+
 def _host_loop(m, kind, eta, thr, cfg_scale=6.0, steps=None):
     """The loop restated: forward_tokens twice, ops.guidance_sums, and the CPU restatement of the tail, per step.
     Returns the latents and the per-step records (steps, B, 8)."""

@@ -376,6 +376,37 @@ def test_cfg_euler_edges(dev, cfg, sn, bf16_euler, masked):
     _close(outs[2], outs[0], max_ulps=0, max_frac=0.0, tag="inplace_")
 
 
+@pytest.mark.parametrize("masked", [False, True], ids=["nomask", "mask"])
+@pytest.mark.parametrize("bf16_euler", [False, True], ids=["f32euler", "bf16euler"])
+def test_flat_tail_entries_equal_step_tail(dev, bf16_euler, masked):
+    """ltxk_cfg_euler_step and ltxk_cfg_euler_step_dev called through the binding (no ops path calls them any more) against
+    ops.step_tail, bit for bit, on B = 2, C = 16 (two channel groups), S = 70 (a full wave and a 6-lane tail).  Catches a
+    flat entry whose arguments reach the shared launch in another order, or that drops sigmas_dev or the flags."""
+    L, ops = _lib(), _ops()
+    g = _g(90 + 2 * bf16_euler + masked)
+    B, C, S = 2, 16, 70
+    n = B * C * S
+    vp, vn = (torch.randn(B, S, C, generator=g).to(BF).to(dev) for _ in range(2))
+    x = torch.randn(B, C, S, generator=g).to(BF).to(dev)
+    clean = torch.randn(B, C, S, generator=g).to(BF).to(dev) if masked else None
+    mask = torch.tensor([0.0, 1.0, 0.75])[torch.randint(0, 3, (B, S), generator=g)].to(dev) if masked else None
+    cs, sig, sig_n = 4.0, R.f32(0.909375), R.f32(0.725)
+    sd = torch.tensor([sig, sig_n], dtype=torch.float32, device=dev)
+    p = lambda t: None if t is None else t.data_ptr()
+    st = torch.cuda.current_stream().cuda_stream
+    want = ops.step_tail(vp, vn, None, x, cfg_scale=cs, sigma=sig, sigma_next=sig_n, clean=clean, mask_tok=mask, bf16_euler=bf16_euler)
+    host, devf = _sent_bf16((n + 128,), dev), _sent_bf16((n + 128,), dev)
+    L.check(L.load().ltxk_cfg_euler_step(p(vp), p(vn), p(x), host[64:].data_ptr(), p(clean), p(mask), B, C, S, cs, sig, sig_n,
+                                         int(bf16_euler), st), "ltxk_cfg_euler_step")
+    L.check(L.load().ltxk_cfg_euler_step_dev(p(vp), p(vn), p(x), devf[64:].data_ptr(), p(clean), p(mask), B, C, S, cs, p(sd),
+                                             int(bf16_euler), st), "ltxk_cfg_euler_step_dev")
+    torch.cuda.synchronize()
+    assert not bool(torch.isnan(want.float()).any())
+    for tag, buf in (("host", host), ("dev", devf)):
+        assert _untouched(buf[:64]) and _untouched(buf[64 + n:]), tag
+        assert torch.equal(buf[64:64 + n].view(torch.int16), want.reshape(-1).view(torch.int16)), tag
+
+
 # ------------------------------------------------------------------------------------------- Euler alone
 @pytest.mark.parametrize("sn", [0.3, 0.0])
 def test_euler_step_edges(dev, sn):
