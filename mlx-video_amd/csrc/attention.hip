@@ -359,14 +359,19 @@ __device__ __forceinline__ void fa_body(const FaParams& p, char* smem, int bh, i
     }
     __syncthreads();
     if (kh == 1) return;
-    const float m1 = xo[4096 + lane], l1 = xo[4096 + 64 + lane];
-    const float m = fmaxf(mc_run, m1);
-    const float a0 = __builtin_amdgcn_exp2f(mc_run - m), a1 = __builtin_amdgcn_exp2f(m1 - m);      // exact powers of two
-    l_tot = l_tot * a0 + l1 * a1;
+    // Tk <= 32: the second half saw masked keys only.  Its offset is ceil(-1e30 c) and its P = exp2(fma(-1e30, c, -M)) is exp2 of
+    // the fma's rounding residual, ~+-1e21: 0 for some c (1/sqrt(128) among them) and +inf for others (scale = 0.1), which the
+    // merge would turn into inf * 0.  That half holds no key: leave it out.
+    if (p.Tk > FA_BK / 2) {
+      const float m1 = xo[4096 + lane], l1 = xo[4096 + 64 + lane];
+      const float m = fmaxf(mc_run, m1);
+      const float a0 = __builtin_amdgcn_exp2f(mc_run - m), a1 = __builtin_amdgcn_exp2f(m1 - m);      // exact powers of two
+      l_tot = l_tot * a0 + l1 * a1;
 #pragma unroll
-    for (int db = 0; db < 4; ++db)
+      for (int db = 0; db < 4; ++db)
 #pragma unroll
-      for (int j = 0; j < 16; ++j) o[db][j] = o[db][j] * a0 + xo[(db * 16 + j) * 64 + lane] * a1;
+        for (int j = 0; j < 16; ++j) o[db][j] = o[db][j] * a0 + xo[(db * 16 + j) * 64 + lane] * a1;
+    }
   }
 
   // ---- epilogue: O[q][d] = O^T[d][q] / l, transposed through a wave-private 8 KiB LDS image so that every
@@ -740,6 +745,7 @@ __device__ __forceinline__ void fa_body16(const FaParams& p, char* smem, int bh,
     if (kh == 1) return;
 #pragma unroll
     for (int qb = 0; qb < 2; ++qb) {
+      if (p.Tk <= FA_BK / 2) continue;                       // a second half of masked keys only holds no key (see fa_body)
       const float m1 = xo[4096 + qb * 128 + lane], l1 = xo[4096 + qb * 128 + 64 + lane];
       const float m = fmaxf(mc_run[qb], m1);
       const float a0 = __builtin_amdgcn_exp2f(mc_run[qb] - m), a1 = __builtin_amdgcn_exp2f(m1 - m);

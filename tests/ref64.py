@@ -9,7 +9,11 @@ Scalars the kernels receive as fp32 are passed in already rounded to fp32 (``f32
 ``assert_bf16_close`` is the comparator: bf16 ulps measured at max(|ref|, mag) with an absolute floor of 2^-126 (a
 kernel that flushes a subnormal result to zero is not wrong); no element more than ``max_ulps`` away and at most
 ``max_frac`` of the elements off at all.  NaN where the reference is finite (an untouched sentinel) counts as infinitely
-far."""
+far.
+
+conv3d / conv3d_bound and attention / attention_bound are of another kind: they round nothing, run on the device their
+inputs live on, and come with an element-wise bound derived from the kernel's rounding points (tests/test_conv3d_bound_gpu.py,
+tests/test_attn_bound_gpu.py)."""
 from __future__ import annotations
 
 import math
@@ -444,3 +448,126 @@ def assert_rows_close(got, ref, exempt, *, max_ulps: float, max_frac: float, mag
     assert ulps <= max_ulps, f"{what}: an element is {ulps:.3g} bf16 ulps off (allowed {max_ulps})"
     assert frac <= max_frac, f"{what}: {frac:.3e} of the elements of non-exempt rows differ (allowed {max_frac:.3e})"
     return ulps, frac
+
+
+# ------------------------------------------------------------------------------------------ flash attention (dh = 128)
+FA_DH = 128
+LOG2E_F32 = 1.4426950408889634
+ATTN_FAMILIES = ("flat", "peaked", "spiked")
+
+
+def attn_c(scale: float) -> float:
+    """The kernel's exponent constant fp32(fp32(scale) * fp32(log2 e)), as oracle.dit.sdpa builds it."""
+    return float(np.float32(np.float32(scale) * np.float32(LOG2E_F32)))
+
+
+def _heads(t: Tensor, H: int) -> Tensor:
+    B, T, _ = t.shape
+    return t.to(F64).reshape(B, T, H, FA_DH).transpose(1, 2)               # (B,H,T,128)
+
+
+def attention_probs(q: Tensor, k: Tensor, H: int, scale: float):
+    """(P, x, smag), each (B,H,Tq,Tk) float64 on the inputs' device: the exact softmax weights of ``attention``, the
+    exponents x = c * q.k^T in the exp2 domain and smag = |q|.|k|^T."""
+    qh, kh = _heads(q, H), _heads(k, H)
+    x = attn_c(scale) * (qh @ kh.transpose(-1, -2))                       # products of bf16 values, sums of 128: exact in float64
+    smag = qh.abs() @ kh.abs().transpose(-1, -2)
+    p = torch.exp2(x - x.amax(-1, keepdim=True))
+    return p / p.sum(-1, keepdim=True), x, smag
+
+
+def attention(q: Tensor, k: Tensor, v: Tensor, H: int, scale: float):
+    """ltxk_flash_attn in float64, on the device its inputs live on: q (B,Tq,H*128), k, v (B,Tk,H*128) bf16.  Per head,
+    with c = attn_c(scale): s = q.k^T (exact), x = c*s, P = 2^(x - rowmax) / rowsum, y = P v.  Returns (y, A, dx), each
+    (B,Tq,H*128) float64: y the exact result (nothing rounded), A = P |v|, and dx (per row and head, broadcast over the
+    channels) the most the EXPONENT of one key can be off in a kernel that forms s in fp32 and x - M with one fma:
+        dx = max_k(c * 128 * 2^-24 * smag) + 2^-24 * (2 max_k |x| + 8)
+    - fp32 accumulation of 128 products in any order; the fma's rounding of a value no larger than |x| + |M| with the
+    integer offset M within 7 of the row max (FA_DEFER = 6 and a ceil)."""
+    B, Tq, D = q.shape
+    c = attn_c(scale)
+    p, x, smag = attention_probs(q, k, H, scale)
+    vh = _heads(v, H)
+    y = p @ vh
+    A = p @ vh.abs()
+    dx = (c * FA_DH * U24 * smag).amax(-1, keepdim=True) + U24 * (2.0 * x.abs().amax(-1, keepdim=True) + 8.0)
+    back = lambda t: t.transpose(1, 2).reshape(B, Tq, D)
+    return back(y), back(A), back(dx.expand(B, H, Tq, FA_DH))
+
+
+def attention_bound(out: Tensor, y: Tensor, A: Tensor, dx: Tensor, Tk: int):
+    """(d, bound), element-wise on the inputs' device: the distance of a kernel's bf16 output from ``attention``'s y and
+    the most a correct kernel with the rounding points of include/ltxk.h can be away, whatever its tiling, deferral
+    history, key split and summation order:
+        e1    = 2^-22 + ln2 * dx * 1.001 + Tk * 2^-24
+        e     = 2^-8 + e1
+        bound = 1/2 ulp_bf16(out) + (e*A + e1*|y|) / (1 - e1) + 2^-22 |y| + 2^-120
+    e1 is the relative error of one un-rounded P: v_exp_f32 (1 ulp), the exponent error dx, and the fp32
+    sums of up to Tk terms in ANY order (tiles, key halves, merge).  The numerator sum bf16(P) v carries e on every term -
+    bf16 keeps 8 significand bits, so half an ulp is up to 2^-8 relative at the bottom of a binade -; l sums the
+    un-rounded P and carries e1 only; 2^-22 |y| is o * (1/l) in fp32; 2^-120 covers a flushed subnormal P.  An output
+    that is NaN (an unwritten sentinel, 0/0) is infinitely far."""
+    o = out.to(F64)
+    e1 = 2.0 ** -22 + math.log(2.0) * dx * 1.001 + Tk * U24
+    e = 2.0 ** -8 + e1
+    bound = 0.5 * _ulp_dev(torch.nan_to_num(o, nan=0.0)) + (e * A + e1 * y.abs()) / (1.0 - e1) + 2.0 ** -22 * y.abs() + 2.0 ** -120
+    d = (o - y).abs()
+    return torch.where(torch.isnan(d), torch.full_like(d, math.inf), d), bound
+
+
+def attention_fused_dx(qp: Tensor, k: Tensor, H: int, scale: float) -> Tensor:
+    """What the fused query preparation adds to ``attention``'s dx, (B,Tq,H*128): its fp32 sum of the row's squares runs in
+    another order than ltxk_qknorm_rope's, a 1-ulp flip of rstd can move at most a couple of elements of the prepared
+    query q' by one bf16 ulp, and two such flips move an exponent by at most
+        2 * c * ulp_bf16(max_d |q'_d|) * max_d |k_d|       per (row, head), the key maximum over all keys of the head."""
+    B, Tq, D = qp.shape
+    qm = _heads(qp, H).abs().amax(-1, keepdim=True)                        # (B,H,Tq,1)
+    km = _heads(k, H).abs().amax(dim=(-1, -2), keepdim=True)               # (B,H,1,1)
+    add = 2.0 * attn_c(scale) * _ulp_dev(qm) * km
+    return add.expand(B, H, Tq, FA_DH).transpose(1, 2).reshape(B, Tq, D)
+
+
+def attention_planted_keys(Tq: int, Tk: int):
+    """[(row, key)] of the spiked family: keys 0, 31, 32, 63, 64, Tk-1 and the first key of the last key tile, those that
+    exist, each planted on query row (7*key) % Tq.  Keys that land on one row hold equal shares of it, and the family's
+    precondition asks 0.25 of the row for each: a row takes three, a fourth moves on to the next row with room (only where
+    Tq divides the stride of several edge keys: Tq = 16, Tk = 97 sends keys 0, 32, 64 and 96 to row 0, and 96 goes to row 1)."""
+    keys = sorted({j for j in (0, 31, 32, 63, 64, Tk - 1, 64 * ((Tk - 1) // 64)) if 0 <= j < Tk})
+    load, pairs = {}, []
+    for j in keys:
+        row = (7 * j) % Tq
+        while load.get(row, 0) >= 3 and min(load.get(r, 0) for r in range(Tq)) < 3:
+            row = (row + 1) % Tq
+        load[row] = load.get(row, 0) + 1
+        pairs.append((row, j))
+    return pairs
+
+
+def attention_plant(q: Tensor, k: Tensor):
+    """k with the spiked family's keys planted from q (k[b, key] = 4 * q[b, row], every head; exact in bf16).  Returns
+    (k, [(row, key)])."""
+    k = k.clone()
+    pairs = attention_planted_keys(q.shape[1], k.shape[1])
+    for row, j in pairs:
+        k[:, j] = (4.0 * q[:, row].float()).to(BF)
+    return k, pairs
+
+
+def attention_inputs(B: int, H: int, Tq: int, Tk: int, family: str, seed: int):
+    """The inputs of the attention bound tests (seeded on the CPU, shared by test_ref64_cpu.py and
+    test_attn_bound_gpu.py): (q (B,Tq,H*128), k, v (B,Tk,H*128), planted), bf16.
+      flat    q, k, v randn;
+      peaked  q randn * 4 - logits of std ~4: a row's mass sits on a few keys;
+      spiked  flat, plus ``attention_plant``: every edge key is the dominant one of some row, which forces a rescale after
+              deferral, in the ragged last tile among others.  planted = its (row, key) pairs, [] otherwise."""
+    assert family in ATTN_FAMILIES, family
+    g = torch.Generator().manual_seed(seed * 1000003 + ((B * 131 + H) * 4099 + Tq) * 4099 + Tk)
+    D = H * FA_DH
+    q = torch.randn(B, Tq, D, generator=g)
+    k = torch.randn(B, Tk, D, generator=g).to(BF)
+    v = torch.randn(B, Tk, D, generator=g).to(BF)
+    q = (q * 4 if family == "peaked" else q).to(BF)
+    planted = []
+    if family == "spiked":
+        k, planted = attention_plant(q, k)
+    return q, k, v, planted

@@ -227,3 +227,33 @@ def test_plan_refuses_what_the_launch_refuses(ops):
         ops.flash_attn_plan(1, 4, 0, 64, cus=256)
     with pytest.raises(LtxkError, match="cus=0"):
         ops.flash_attn_plan(1, 4, 128, 64, cus=0)
+
+
+def test_attn_bound_cases_at_256_cus(ops, monkeypatch):
+    """The forms tests/test_attn_bound_gpu.py aims its cases at, by the plan and by the restatement, and the plans its
+    measurement-build switches produce (each switch must change the plan of the shape it is tried at)."""
+    import test_attn_bound_gpu as G
+    from mlx_video_amd import _lib
+
+    def want_of(pl, want):
+        return {k: getattr(pl, k) for k in want}
+
+    checked = [(shape, ts, want, False) for _, shape, _, variants in G.CASES for ts, want in variants]
+    checked += [(shape, ts, want, True) for _, shape, ts, want in G.FUSED_CASES]
+    for shape, ts, want, fused in checked:
+        B, H, Tq, Tk = shape
+        pl = ops.flash_attn_plan(B, H, Tq, Tk, cus=256, tail_split=ts, fused_q=fused)
+        assert want_of(pl, want) == want, (shape, ts, pl)
+        assert fields(pl) == ref_plan(B * H, Tq, Tk, 256, 0 if ts else NO_TAIL_SPLIT), (shape, ts, pl)
+    for var in ("LTXK_FA_MFMA", "LTXK_FA_QB", "LTXK_FA_XCD", "LTXK_FA_FILL"):
+        monkeypatch.delenv(var, raising=False)
+    if not os.path.exists(_lib.AB_LIB_PATH):
+        pytest.skip("no measurement build")
+    with _lib.use_library(_lib.AB_LIB_PATH):
+        for var, val, shape, want in G.AB_CASES:
+            base = ops.flash_attn_plan(*shape, cus=256)
+            assert want_of(base, G.AB_DEFAULT.get(shape, {})) == G.AB_DEFAULT.get(shape, {}), (shape, base)
+            monkeypatch.setenv(var, val)
+            pl = ops.flash_attn_plan(*shape, cus=256)
+            monkeypatch.delenv(var)
+            assert want_of(pl, want) == want and pl != base, (var, val, shape, pl, base)

@@ -388,3 +388,219 @@ def test_pixelnorm_gpu_inputs_have_few_exempt_rows(C):
     # the detector itself: a value a relative 2^-20 above a midpoint is near it, 2^-16 is not
     mid = torch.tensor([1.0 + 2.0 ** -8, 3.0 + 2.0 ** -7, 2.0 ** -20 * (1.5 + 2.0 ** -8)], dtype=torch.float64)
     assert bool(R.near_bf16_midpoint(mid * (1 + 2.0 ** -20)).all()) and not bool(R.near_bf16_midpoint(mid * (1 + 2.0 ** -16)).any())
+
+
+# ------------------------------------------------------------------------------------------------ flash attention bound
+ATTN_SCALE = 1.0 / math.sqrt(128)
+ATTN_SHAPES = [(1, 3, 200, 70), (1, 2, 77, 200), (2, 2, 129, 65), (1, 1, 16, 5), (1, 2, 320, 1296)]
+ATTN_SEEDS = (0, 1)
+_ATTN_REF = {}
+
+
+def _attn_ref(shape, family, seed):
+    """(q, k, v, planted, (y, A, dx)) of one case, computed once and shared (nothing below writes into it)."""
+    key = (shape, family, seed)
+    if key not in _ATTN_REF:
+        B, H, Tq, Tk = shape
+        q, k, v, planted = R.attention_inputs(B, H, Tq, Tk, family, seed)
+        _ATTN_REF[key] = (q, k, v, planted, R.attention(q, k, v, H, ATTN_SCALE))
+    return _ATTN_REF[key]
+
+
+def _attn_ratio(out, ref, Tk):
+    d, bound = R.attention_bound(out, *ref, Tk)
+    return d / bound
+
+
+def _attn_emulate(q, k, v, H, *, split=False, fault=None, extra_key=None, scale=ATTN_SCALE):
+    """What fa_body16 does, in fp32 on the CPU: 64-key tiles, the ragged last tile's slots masked with -1e30, per 16-row
+    query block (rows past Tq clamped to Tq-1) an online softmax with an integer offset that is raised - to ceil of the
+    block rows' own maxima - only when some row's tile maximum exceeds it by more than 6; P = exp2(fma(s, c, -M)) rounded
+    to bf16 for P.V, l summed from the un-rounded fp32 P.  split: the keys of each tile halved (32 | 32) over two
+    accumulators that are merged at the end with exp2(m_i - m); a second half that saw only masked keys (Tk <= 32) is
+    left out of the merge, as the kernel leaves it out.
+    fault: 'skip_block' - the 16-key block that holds key Tk-1 left out for the last 16-row query block;
+           'swap_merge' - the two halves' merge weights exchanged;
+           'merge_dead_half' - the all-masked second half merged like any other.
+    extra_key: (k_row, v_row) appended as one more, unmasked, key."""
+    B, Tq, D = q.shape
+    Tk = k.shape[1]
+    c = R.attn_c(scale)
+    qh = q.float().reshape(B, Tq, H, 128).transpose(1, 2)
+    kh = k.float().reshape(B, Tk, H, 128).transpose(1, 2)
+    vh = v.float().reshape(B, Tk, H, 128).transpose(1, 2)
+    if extra_key is not None:
+        kh = torch.cat([kh, extra_key[0].float().reshape(B, 1, H, 128).transpose(1, 2)], 2)
+        vh = torch.cat([vh, extra_key[1].float().reshape(B, 1, H, 128).transpose(1, 2)], 2)
+        Tk += 1
+    nb = -(-Tq // 16)
+    rows = torch.arange(nb * 16).clamp_max(Tq - 1)
+    qh = qh[:, :, rows]                                                       # (B,H,nb*16,128), clamped rows
+    nt = -(-Tk // 64)
+    pad = nt * 64 - Tk
+    s = qh @ kh.transpose(-1, -2)                                             # fp32
+    s = torch.cat([s, torch.full((B, H, nb * 16, pad), -1e30)], -1)
+    vh = torch.cat([vh, torch.full((B, H, pad, 128), 1024.0)], 2)             # live padding: P must be exactly 0 there
+    if fault == "skip_block":
+        kb = (Tk - 1) // 16
+        s[:, :, (nb - 1) * 16:, kb * 16:(kb + 1) * 16] = -1e30
+    s = s.reshape(B, H, nb, 16, nt, 64)
+    halves = [(0, 32), (32, 64)] if split else [(0, 64)]
+    acc = []
+    for lo, hi in halves:
+        m = torch.full((B, H, nb, 16, 1), -1e30)
+        l = torch.zeros(B, H, nb, 16, 1)
+        o = torch.zeros(B, H, nb, 16, 128)
+        for t in range(nt):
+            st = s[:, :, :, :, t, lo:hi]
+            mxc = st.amax(-1, keepdim=True) * np.float32(c)                  # fp32 product, as mx * p.c
+            raise_ = ((mxc - m) > 6.0).any(dim=3, keepdim=True)               # one decision per 16-row block
+            m_new = torch.where(raise_, torch.maximum(m, torch.ceil(mxc)), m)
+            alpha = torch.exp2(m - m_new)
+            l, o, m = l * alpha, o * alpha, m_new
+            p = torch.exp2((st.double() * c - m.double()).float())            # fma: one rounding of the exponent
+            l = l + p.sum(-1, keepdim=True)
+            o = o + p.to(BF).float() @ vh[:, :, None, t * 64 + lo:t * 64 + hi]
+        acc.append((m, l, o))
+    if split:
+        (m0, l0, o0), (m1, l1, o1) = acc
+        m = torch.maximum(m0, m1)
+        a0, a1 = torch.exp2(m0 - m), torch.exp2(m1 - m)
+        if fault == "swap_merge":
+            a0, a1 = a1, a0
+        if Tk > 32 or fault is not None:
+            l, o = l0 * a0 + l1 * a1, o0 * a0 + o1 * a1
+        else:
+            l, o = l0, o0
+    else:
+        _, l, o = acc[0]
+    out = (o * (1.0 / l)).to(BF).reshape(B, H, nb * 16, 128)[:, :, :Tq]
+    return out.transpose(1, 2).reshape(B, Tq, D)
+
+
+def _attn_exact_bf16(q, k, v, H, scale=ATTN_SCALE):
+    """bf16 of the exact result: the output of a kernel with no error but the final rounding."""
+    return R.rbf(R.attention(q, k, v, H, scale)[0]).to(BF)
+
+
+@pytest.mark.parametrize("shape", ATTN_SHAPES, ids=lambda s: "x".join(map(str, s)))
+@pytest.mark.parametrize("family", R.ATTN_FAMILIES)
+def test_attention_bound_accepts_every_correct_computation(shape, family):
+    """ref64.attention_bound must pass, on every element, the oracle's flash policy, its fp32-P policy and an fp32
+    emulation of the kernel's own loop with and without the key split.  Worst d / bound measured here over the five shapes
+    and two seeds, per family (flat, peaked, spiked):
+        O.BF16_FLASH      0.692  0.866  0.890
+        O.BF16            0.473  0.467  0.472   (P stays fp32: the final rounding alone)
+        emulation         0.692  0.866  0.890
+        emulation, split  0.692  0.866  0.890
+    (the three bf16-P computations agree to the digits shown: the worst element is set by the rounding of P, which the
+    integer offset makes the same in all of them; with 2^-9 for that rounding the flash policy reaches 1.1 to 1.33)."""
+    B, H, Tq, Tk = shape
+    for seed in ATTN_SEEDS:
+        q, k, v, planted, ref = _attn_ref(shape, family, seed)
+        if family == "spiked":
+            p = R.attention_probs(q, k, H, ATTN_SCALE)[0]
+            assert planted and all(float(p[:, :, r, j].min()) >= 0.25 for r, j in planted), (shape, seed, planted)
+        outs = {"flash": O.sdpa(q.float(), k.float(), v.float(), H, O.BF16_FLASH), "fp32_p": O.sdpa(q.float(), k.float(), v.float(), H, O.BF16),
+                "emulation": _attn_emulate(q, k, v, H), "emulation_split": _attn_emulate(q, k, v, H, split=True)}
+        for name, out in outs.items():
+            worst = float(_attn_ratio(out, ref, Tk).max())
+            print(f"attention bound {shape} {family} seed {seed} {name}: worst d/bound {worst:.3f}")
+            assert worst <= 1.0, (name, shape, family, seed, worst)
+
+
+@pytest.mark.parametrize("shape", ATTN_SHAPES, ids=lambda s: "x".join(map(str, s)))
+@pytest.mark.parametrize("family", R.ATTN_FAMILIES)
+def test_attention_bound_rejects_seeded_faults(shape, family):
+    """Each fault a kernel could have must put at least one element beyond the bound: the last key dropped; one more key
+    that repeats key Tk-1 with v = 1024 (an unmasked pad slot); the last query row carrying row Tq-2's result; one 16-key
+    block skipped for one 16-row query block; the merge weights of the two key halves exchanged.  Measured here over the
+    shapes, families and seeds, worst d / bound (fewest rows beyond): key dropped 4.7 - 490 (11), pad slot 350 - 510 (15), row
+    moved 36 - 440 (1: the row itself), block skipped 1.1 - NaN (1; 1.1 where the block holds a single live key), weights
+    exchanged 56 - NaN (16)."""
+    B, H, Tq, Tk = shape
+    for seed in ATTN_SEEDS:
+        q, k, v, _, ref = _attn_ref(shape, family, seed)
+        good = _attn_exact_bf16(q, k, v, H)
+        faults = {}
+        if Tk > 1:
+            faults["last_key_dropped"] = _attn_exact_bf16(q, k[:, :-1], v[:, :-1], H)
+        faults["pad_slot_unmasked"] = _attn_emulate(q, k, v, H, extra_key=(k[:, -1:], torch.full_like(v[:, -1:], 1024.0)))
+        if Tq > 1:
+            moved = good.clone()
+            moved[:, -1] = good[:, -2]
+            faults["last_row_is_the_row_before"] = moved
+        faults["key_block_skipped"] = _attn_emulate(q, k, v, H, fault="skip_block")
+        faults["merge_weights_swapped"] = _attn_emulate(q, k, v, H, split=True, fault="swap_merge")
+        for name, out in faults.items():
+            ratio = _attn_ratio(out, ref, Tk)
+            n = int((ratio > 1.0).any(-1).sum())
+            print(f"attention bound {shape} {family} seed {seed} {name}: {n} rows beyond, worst {float(ratio.max()):.3g}")
+            assert n >= 1, (name, shape, family, seed)
+
+
+@pytest.mark.parametrize("shape", [(1, 4, 77, 70), (2, 4, 129, 65)], ids=lambda s: "x".join(map(str, s)))
+def test_attention_fused_prep_allowance(shape):
+    """The fused query preparation is held to the bound centred on attention(q', k, v), q' = qknorm_rope(q), with dx
+    enlarged by ref64.attention_fused_dx.  Two one-ulp flips per row and head of q' stay inside it; q' rotated with the
+    next row's cos / sin, or scaled with the next head's weight, does not."""
+    B, H, Tq, Tk = shape
+    D = H * 128
+    for seed in ATTN_SEEDS:
+        q, k, v, _ = R.attention_inputs(B, H, Tq, Tk, "flat", seed)
+        g = _g(seed + 17)
+        w = (1 + 0.1 * torch.randn(1, D, generator=g)).to(BF)
+        ang = torch.rand(H, Tq, 64, generator=g) * (2 * math.pi)
+        cos, sin = torch.cos(ang), torch.sin(ang)
+        prep = lambda w_, c_, s_: R.qknorm_rope(q.reshape(B * Tq, D), w_, c_, s_, Tq, H, 1e-6)[0].to(BF).reshape(B, Tq, D)
+        qp = prep(w, cos, sin)
+        k, _ = R.attention_plant(qp, k)                                     # spiked on q': the flips land on dominant keys too
+        y, A, dx = R.attention(qp, k, v, H, ATTN_SCALE)
+        ref = (y, A, dx + R.attention_fused_dx(qp, k, H, ATTN_SCALE))
+        flipped = qp.clone().reshape(B, Tq, H, 128)
+        up = lambda t: (t.view(torch.int16) + 1).view(BF)                  # the next bf16 away from zero
+        flipped[..., 3] = up(flipped[..., 3].contiguous())
+        flipped[..., 100] = up(flipped[..., 100].contiguous())
+        inside = _attn_ratio(_attn_exact_bf16(flipped.reshape(B, Tq, D), k, v, H), ref, Tk)
+        assert float(inside.max()) <= 1.0, (shape, seed, float(inside.max()))
+        wrong = {"next_row_table": prep(w, cos.roll(-1, 1), sin.roll(-1, 1)), "next_head_weight": prep(w.roll(-128, 1), cos, sin)}
+        for name, qw in wrong.items():
+            ratio = _attn_ratio(_attn_exact_bf16(qw, k, v, H), ref, Tk)
+            assert int((ratio > 1.0).sum()) >= 1, (name, shape, seed)
+
+
+def test_attention_inputs_planted_keys_dominate_on_every_gpu_case_shape():
+    """The spiked family's precondition at every shape tests/test_attn_bound_gpu.py launches (seed 0, the one it uses): from
+    the float64 P, each planted key holds at least 0.25 of its row's mass - in every batch and head."""
+    import test_attn_bound_gpu as G
+    for shape in G.ALL_SHAPES:
+        B, H, Tq, Tk = shape
+        q, k, _, planted = R.attention_inputs(B, H, Tq, Tk, "spiked", 0)
+        assert len(planted) == len({j for j in (0, 31, 32, 63, 64, Tk - 1, 64 * ((Tk - 1) // 64)) if j < Tk})
+        p = R.attention_probs(q, k, H, ATTN_SCALE)[0]
+        worst = min(float(p[:, :, r, j].min()) for r, j in planted)
+        assert worst >= 0.25, (shape, worst)
+
+
+@pytest.mark.parametrize("scale", [0.1, 0.09, 1.0])
+def test_attention_bound_at_other_scales_and_the_all_masked_key_half(scale):
+    """The bound is a function of the scale, not fitted to 1/sqrt(128).  At Tk <= 32 the second key half of a split tile sees
+    masked keys only: its offset is ceil(fp32(-1e30 * c)) and its P is exp2 of the fma's rounding residual, ~+-1e21 - 0 at
+    1/sqrt(128) and 0.09, +inf at 0.1, where merging that half gives inf * 0 (from c = 1 up the offset is never raised
+    from its initial -1e30 and P = 0).  The kernel leaves such a half out;
+    the bound accepts that at every scale and rejects the merged form wherever the residual is positive."""
+    c = R.attn_c(scale)
+    masked = float(np.float32(-1e30))
+    mxc = float(np.float32(np.float32(masked) * np.float32(c)))
+    M = mxc if mxc - masked > 6.0 else masked          # c >= 1: the half's offset stays at its initial -1e30 and P = exp2(-huge) = 0
+    residual = masked * c - M                          # exact in float64 (24 x 24 bits)
+    for shape in [(1, 1, 16, 5), (1, 2, 77, 32), (2, 2, 129, 65)]:
+        B, H, Tq, Tk = shape
+        q, k, v, _ = R.attention_inputs(B, H, Tq, Tk, "flat", 0)
+        ref = R.attention(q, k, v, H, scale)
+        for split in (False, True):
+            worst = float(_attn_ratio(_attn_emulate(q, k, v, H, split=split, scale=scale), ref, Tk).max())
+            assert worst <= 1.0, (shape, scale, split, worst)
+        if Tk <= 32:
+            merged = _attn_ratio(_attn_emulate(q, k, v, H, split=True, fault="merge_dead_half", scale=scale), ref, Tk)
+            assert bool((merged > 1.0).all()) == (residual > 128), (shape, scale, residual, float(merged.max()))
