@@ -10,6 +10,7 @@
 //   M = B*D*H*W voxels (channels-last rows), N = Cout, K = 27*Cin walked tap-major in 64-wide
 //   steps; same 3-stage LDS ring / MFMA loop as the Linear GEMM (gemm_core.h).
 #include "gemm_core.h"
+#include "epilogue.h"
 #include <stdlib.h>
 #include <utility>
 
@@ -250,42 +251,24 @@ __global__ __launch_bounds__(GEMM_THREADS) void conv3d_k3_kernel(ConvParams p) {
   }
 
   // epilogue: acc[tt][nt][j]: voxel = lane&15, co = 4*(lane>>4) + j.  bf16 outputs go through a wave-private LDS
-  // image (128-byte rows, chunks XOR-swizzled by row) and leave as whole 128-byte lines (see gemm.hip).
+  // line image and leave as whole 128-byte lines (epilogue.h).
   const int nq = (lane >> 4) * 4;
   const bool wide = !SPLIT && (p.Cout & 7) == 0;
   const bool do_act = !SPLIT && p.act_out != nullptr, do_out = p.out != nullptr;
-  char* stg = smem + wave * (TT * 16 * 128);
+  const LineImage<128, TT * 16> img{smem + wave * (TT * 16 * 128), lane};
   if (wide) __syncthreads();
   // y of (tt, nt): the conv's bf16 output values (bias, residual), as floats
   auto out_vals = [&](int tt, int nt, float (&y)[4]) __attribute__((always_inline)) {
-    const bf16x4 b = bpre[nt];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) y[j] = rbf(acc[tt][nt][j] + (float)b[j]);
-    if constexpr (HAS_RES) {
-      const bf16x4 r = rres[tt][nt];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) y[j] = rbf(y[j] + (float)r[j]);
-    }
+    bf16x4 r = {};
+    if constexpr (HAS_RES) r = rres[tt][nt];
+    conv_value<HAS_RES>(acc[tt][nt], bpre[nt], r, y);
   };
   auto stage_or_store = [&](bf16* dst, int tt, int nt, int m, int n, bf16x4 o) __attribute__((always_inline)) {
-    if (wide) {
-      const int r = tt * 16 + (lane & 15), cg = lane >> 4;
-      *(bf16x4*)(stg + r * 128 + (((nt * 2 + (cg >> 1)) ^ (r & 7)) << 4) + (cg & 1) * 8) = o;
-    } else {
-      *(bf16x4*)(dst + (size_t)m * p.Cout + n) = o;
-    }
+    if (wide) img.put(tt * 16 + (lane & 15), nt, o);
+    else *(bf16x4*)(dst + (size_t)m * p.Cout + n) = o;
   };
   auto flush_lines = [&](bf16* dst) __attribute__((always_inline)) {
-    if (!wide) return;
-    const int c = lane & 7;
-    const int n = n0 + wn * 64 + c * 8;
-#pragma unroll
-    for (int i = 0; i < TT * 2; ++i) {
-      const int r = i * 8 + (lane >> 3);
-      const int m = m0 + wm * TT * 16 + r;
-      const bf16x8 v = *(const bf16x8*)(stg + r * 128 + ((c ^ (r & 7)) << 4));
-      if (m < p.M && n < p.Cout) *(bf16x8*)(dst + (size_t)m * p.Cout + n) = v;
-    }
+    if (wide) img.flush(dst, p.Cout, m0 + wm * TT * 16, n0 + wn * 64, p.M, p.Cout);
   };
   float rowsq[TT];
 #pragma unroll
@@ -307,12 +290,7 @@ __global__ __launch_bounds__(GEMM_THREADS) void conv3d_k3_kernel(ConvParams p) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) rowsq[tt] += rbf(y[j] * y[j]);          // PixelNorm's mean of squares, squares rounded as in ltxk_pixelnorm_act
       }
-      if (do_out) {
-        bf16x4 o;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) o[j] = (bf16)y[j];
-        stage_or_store(p.out, tt, nt, m, n, o);
-      }
+      if (do_out) stage_or_store(p.out, tt, nt, m, n, to_bf16x4(y));
     }
   }
   if (do_out) flush_lines(p.out);
@@ -322,9 +300,7 @@ __global__ __launch_bounds__(GEMM_THREADS) void conv3d_k3_kernel(ConvParams p) {
     float* part = (float*)(smem + 8 * (TT * 16 * 128));                       // behind the 8 staging images
 #pragma unroll
     for (int tt = 0; tt < TT; ++tt) {
-      float v = rowsq[tt];
-      v = lane_xor16_sum(v);
-      v = lane_xor32_sum(v);
+      const float v = wave_row_sum(rowsq[tt]);
       if (lane < 16) part[((wm * TT + tt) * 16 + lane) * WN + wn] = v;
     }
     __syncthreads();
@@ -374,21 +350,18 @@ __global__ void conv_splitk_finalize_kernel(const float* __restrict__ slab, cons
   if (idx >= total) return;
   const size_t e = idx * 4;
   const int n = (int)(e % Cout);
-  f32x4 a = *(const f32x4*)(slab + e);
-  for (int s = 1; s < S; ++s) {
-    const f32x4 b = *(const f32x4*)(slab + (size_t)s * M * Cout + e);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) a[j] += b[j];
-  }
+  const f32x4 a = sum_slices(slab + e, (size_t)M * Cout, S);
   const bf16x4 bs = *(const bf16x4*)(bias + n);
-  bf16x4 o;
+  float y[4];
+  if (resid) {
+    bf16x4 r;
 #pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    float y = rbf(a[j] + (float)bs[j]);
-    if (resid) y = y + (float)resid[e + j];
-    o[j] = (bf16)y;
+    for (int j = 0; j < 4; ++j) r[j] = resid[e + j];
+    conv_value<true>(a, bs, r, y);
+  } else {
+    conv_value<false>(a, bs, bs, y);
   }
-  *(bf16x4*)(out + e) = o;
+  *(bf16x4*)(out + e) = to_bf16x4(y);
 }
 
 // =====================================================================================================================
@@ -693,9 +666,9 @@ __global__ __launch_bounds__(GEMM_THREADS) void conv3d_k3_kw_kernel(ConvParams p
 #pragma unroll
   for (int nt = 0; nt < 4; ++nt) asm volatile("" ::"v"(bpre[nt]));
 
-  // ---- epilogue (as the kernel above): y = bf16(acc + bias) [+ resid], through a wave-private LDS image, whole lines out ----
+  // ---- epilogue (as the kernel above): y = bf16(acc + bias) [+ resid], through a wave-private LDS line image, whole lines out ----
   const bool wide = (p.Cout & 7) == 0;
-  char* stg = smem + wave * (TT * 16 * 128);
+  const LineImage<128, TT * 16> img{smem + wave * (TT * 16 * 128), lane};
   if (wide) __syncthreads();
 #pragma unroll
   for (int tt = 0; tt < TT; ++tt) {
@@ -705,37 +678,16 @@ __global__ __launch_bounds__(GEMM_THREADS) void conv3d_k3_kw_kernel(ConvParams p
     for (int nt = 0; nt < 4; ++nt) {
       const int n = n0 + wn * 64 + nt * 16 + nq;
       if (n >= p.Cout) continue;
+      bf16x4 r = {};
+      if constexpr (RES) r = rres[tt][nt];
       float y[4];
-      const bf16x4 b = bpre[nt];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) y[j] = rbf(acc[tt][nt][j] + (float)b[j]);
-      if constexpr (RES) {
-        const bf16x4 r = rres[tt][nt];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) y[j] = rbf(y[j] + (float)r[j]);
-      }
-      bf16x4 o;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) o[j] = (bf16)y[j];
-      if (wide) {
-        const int r = tt * 16 + c;
-        *(bf16x4*)(stg + r * 128 + (((nt * 2 + (g >> 1)) ^ (r & 7)) << 4) + (g & 1) * 8) = o;
-      } else {
-        *(bf16x4*)(p.out + (size_t)m * p.Cout + n) = o;
-      }
+      conv_value<RES>(acc[tt][nt], bpre[nt], r, y);
+      const bf16x4 o = to_bf16x4(y);
+      if (wide) img.put(tt * 16 + c, nt, o);
+      else *(bf16x4*)(p.out + (size_t)m * p.Cout + n) = o;
     }
   }
-  if (wide) {
-    const int cc = lane & 7;
-    const int n = n0 + wn * 64 + cc * 8;
-#pragma unroll
-    for (int i = 0; i < TT * 2; ++i) {
-      const int r = i * 8 + (lane >> 3);
-      const int m = m0 + wm * TT * 16 + r;
-      const bf16x8 v = *(const bf16x8*)(stg + r * 128 + ((cc ^ (r & 7)) << 4));
-      if (m < p.M && n < p.Cout) *(bf16x8*)(p.out + (size_t)m * p.Cout + n) = v;
-    }
-  }
+  if (wide) img.flush(p.out, p.Cout, m0 + wm * TT * 16, n0 + wn * 64, p.M, p.Cout);
 }
 
 template <int TT, bool RES>

@@ -5,6 +5,7 @@
 // Also ltxk_gemm_w8 (e4m3 weight panel, bf16 activations) and ltxk_gemm_w8a8 (e4m3 on both sides, fp8 x fp8 MFMA): the same tile
 // body with template flags.  W8A8 exists as the single-pass 160-row family only - no split-K, big-tile or grouped form.
 #include "gemm_core.h"
+#include "epilogue.h"
 #include <stdlib.h>
 #include <type_traits>
 #include <utility>
@@ -71,6 +72,11 @@ struct GemmParams {
   // weight-fp8 forms (W8 kernels; W then points at e4m3fn bytes): per-output-channel fp32 factor on the accumulator, or nullptr
   const float* w_scale;
 };
+
+// where the transposed columns of a launch go: out, or out2 from n_split on (split output)
+__device__ __forceinline__ TransOut trans_out(const GemmParams& p) {
+  return TransOut{p.n_split ? p.out2 : p.out, p.N - p.n_split, p.n_split ? p.ldo2 : p.ldo, p.T, p.M};
+}
 
 // NT = 16-column MFMA tiles per wave: 4 -> 256-column workgroup tiles (64 per wave), 2 -> 128-column ones (32 per wave).
 // W8: W is (N,K) e4m3fn bytes, staged as fp8 (gemm_core.h) and widened after the fragment read; everything else is shared.
@@ -367,12 +373,12 @@ __device__ __forceinline__ void gemm_tile(const GemmParams& p, char* smem, int m
   // ---- epilogue ----
   if constexpr (!TRANS) {
     // acc[tt][nt][j]: token = lane&15, n = 4*(lane>>4) + j.  Written directly that is 16 rows x 32 bytes per store
-    // instruction; with p.wide each wave instead transposes its (16*TT x WC) block through a private LDS image
-    // (rows of WC*2 bytes, 16-byte chunks XOR-swizzled by row) and stores whole rows of it per instruction.
-    constexpr int RB = WC * 2, CPR = RB / 16;       // staged row bytes (128 / 64), 16-byte chunks per row (8 / 4)
+    // instruction; with p.wide each wave instead transposes its (16*TT x WC) block through a private LDS line image
+    // (epilogue.h) and stores whole rows of it per instruction.
+    constexpr int RB = WC * 2;                      // staged row bytes (128 / 64)
     static_assert(8 * TT * 16 * RB + (NT == 2 ? 4 * TT * 64 * 4 : 0) <= G::LDS_BYTES, "the epilogue's LDS images must fit the ring");
     const int nq = (lane >> 4) * 4;
-    char* stg = smem + wave * (TT * 16 * RB);
+    const LineImage<RB, TT * 16> img{smem + wave * (TT * 16 * RB), lane};
     const bool want_ss = p.sumsq != nullptr;
     // NT == 2: a 64-column block of the row statistic spans the waves wn = 2c (columns 0-31) and 2c+1 (32-63).  The even wave
     // hands its lane-wise partial sums through LDS and the odd wave continues them with its own 8 values per lane: the same
@@ -390,62 +396,23 @@ __device__ __forceinline__ void gemm_tile(const GemmParams& p, char* smem, int m
       for (int nt = 0; nt < NT; ++nt) {
         const int n = n0 + wn * WC + nt * 16 + nq;
         if (n >= p.N) continue;
-        float y[4];
-        if (p.bias) {
-          const bf16x4 b = bpre[nt];
-#pragma unroll
-          for (int j = 0; j < 4; ++j) y[j] = rbf(acc[tt][nt][j] + (float)b[j]);
-        } else {
-#pragma unroll
-          for (int j = 0; j < 4; ++j) y[j] = rbf(acc[tt][nt][j]);
-        }
-        if constexpr (EPI == LTXK_EPI_BIAS_GELU) {
-#pragma unroll
-          for (int j = 0; j < 4; ++j) y[j] = gelu_tanh_f(y[j]);
-        } else if constexpr (EPI == LTXK_EPI_BIAS_SILU) {
-#pragma unroll
-          for (int j = 0; j < 4; ++j) y[j] = silu_f(y[j]);
-        } else if constexpr (EPI == LTXK_EPI_BIAS_GATE_RES) {
-          const bf16x4 g = gpre[tt][nt];
-          const bf16x4 r = rres[tt][nt];
-#pragma unroll
-          for (int j = 0; j < 4; ++j) y[j] = (float)r[j] + rbf(y[j] * (float)g[j]);
-        } else if constexpr (EPI == LTXK_EPI_BIAS_RES) {
-          const bf16x4 r = rres[tt][nt];
-#pragma unroll
-          for (int j = 0; j < 4; ++j) y[j] = (float)r[j] + y[j];
-        } else if constexpr (EPI == LTXK_EPI_SCALE_RES) {
-          const bf16x4 r = rres[tt][nt];
-#pragma unroll
-          for (int j = 0; j < 4; ++j) y[j] = (float)r[j] + rbf(p.alpha * acc[tt][nt][j]);
-        }
-        bf16x4 o;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) o[j] = (bf16)y[j];
+        bf16x4 r = {}, g = {};            // (an operand the epilogue does not take)
+        if constexpr (HAS_RES) r = rres[tt][nt];
+        if constexpr (HAS_GATE) g = gpre[tt][nt];
+        const bf16x4 o = epi_value<EPI>(acc[tt][nt], p.bias != nullptr, bpre[nt], r, g, p.alpha);
         if (want_ss) {                  // (uniform branch: the row statistic costs ~3 VALU per element, a quarter of a GELU epilogue)
           if constexpr (NT == 2) {
             if (pair_hi) okeep[tt][nt] = o;
           }
-          if (!pair_hi) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-              const float f = (float)o[j];
-              ss += f * f;
-            }
-          }
+          if (!pair_hi) ss = add_squares(ss, o);
         }
-        if (p.wide) {
-          const int r = tt * 16 + (lane & 15), cg = lane >> 4;
-          *(bf16x4*)(stg + r * RB + (((nt * 2 + (cg >> 1)) ^ (r & (CPR - 1))) << 4) + (cg & 1) * 8) = o;
-        } else {
-          *(bf16x4*)(p.out + (size_t)m * p.ldo + n) = o;
-        }
+        if (p.wide) img.put(tt * 16 + (lane & 15), nt, o);
+        else *(bf16x4*)(p.out + (size_t)m * p.ldo + n) = o;
       }
       if (want_ss) {
         if constexpr (NT == 4) {
           // the wave's 64 columns of row m: 16 values per lane, then the four lanes sharing (lane & 15); fixed order
-          ss = lane_xor16_sum(ss);
-          ss = lane_xor32_sum(ss);
+          ss = wave_row_sum(ss);
           // (a wave whose 64-column block lies past N - the last column tile when N % 256 != 0 - has nothing to report:
           // its slot would be the next row's first partial)
           if (lane < 16 && n0 + wn * 64 < p.N) p.sumsq[(size_t)m * p.sumsq_ld + ((n0 + wn * 64) >> 6)] = ss;
@@ -464,38 +431,19 @@ __device__ __forceinline__ void gemm_tile(const GemmParams& p, char* smem, int m
             if (m >= p.M || n0 + wn * WC >= p.N) continue;
             float ss = xss[tt * 64 + lane];
 #pragma unroll
-            for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-              for (int j = 0; j < 4; ++j) {
-                const float f = (float)okeep[tt][nt][j];
-                ss += f * f;
-              }
-            ss = lane_xor16_sum(ss);
-            ss = lane_xor32_sum(ss);
+            for (int nt = 0; nt < NT; ++nt) ss = add_squares(ss, okeep[tt][nt]);
+            ss = wave_row_sum(ss);
             if (lane < 16) p.sumsq[(size_t)m * p.sumsq_ld + ((n0 + wn * WC) >> 6)] = ss;
           }
         }
       }
     }
-    if (p.wide) {
-      constexpr int RPI = 64 / CPR;                 // rows per store instruction (8 / 16)
-      const int c = lane & (CPR - 1);
-      const int n = n0 + wn * WC + c * 8;
-#pragma unroll
-      for (int i = 0; i < TT * 16 / RPI; ++i) {
-        const int r = i * RPI + lane / CPR;
-        const int m = m0 + wm * TT * 16 + r;
-        const bf16x8 v = *(const bf16x8*)(stg + r * RB + ((c ^ (r & (CPR - 1))) << 4));
-        if (m < p.M && n < p.N) *(bf16x8*)(p.out + (size_t)m * p.ldo + n) = v;
-      }
-    }
+    if (p.wide) img.flush(p.out, p.ldo, m0 + wm * TT * 16, n0 + wn * WC, p.M, p.N);
   } else {
     // acc[tt][nt][j]: n = lane&15, token = 4*(lane>>4) + j ; out[(b*N + n)*ldo + t]
     // (split output: the transposed block has N - n_split rows per batch, lives in out2 and is indexed from n_split)
     const int tq = (lane >> 4) * 4;
-    bf16* const tout = p.n_split ? p.out2 : p.out;
-    const int tld = p.n_split ? p.ldo2 : p.ldo;
-    const int tN = p.N - p.n_split;
+    const TransOut tout = trans_out(p);
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) {
       const int n = n0 + wn * WC + nt * 16 + (lane & 15);
@@ -504,24 +452,7 @@ __device__ __forceinline__ void gemm_tile(const GemmParams& p, char* smem, int m
 #pragma unroll
       for (int tt = 0; tt < TT; ++tt) {
         const int m = m0 + wm * TT * 16 + tt * 16 + tq;
-        if (m >= p.M) continue;
-        bf16x4 o;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) o[j] = (bf16)(acc[tt][nt][j] + b);
-        const int bidx = m / p.T, t = m - bidx * p.T;
-        bf16* dst = tout + ((size_t)bidx * tN + (n - p.n_split)) * tld + t;
-        if ((p.T & 3) == 0 && m + 3 < p.M) {
-          *(bf16x4*)dst = o;
-        } else {
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            const int mj = m + j;
-            if (mj < p.M) {
-              const int bj = mj / p.T, tj = mj - bj * p.T;
-              tout[((size_t)bj * tN + (n - p.n_split)) * tld + tj] = o[j];
-            }
-          }
-        }
+        if (m < p.M) tout.store4(m, n - p.n_split, acc[tt][nt], b);
       }
     }
   }
@@ -673,78 +604,35 @@ static int launch_stream(const GemmParams& p, int ksplit, hipStream_t stream) {
 }
 
 // Second launch of a split-K GEMM: sums the S fp32 slices in slice order (deterministic) and applies the epilogue of
-// gemm_tile - the same formulas and rounding points, one rounding of the fp32 sum.  One thread = 4 consecutive columns of
+// gemm_tile - the same functions of epilogue.h, one rounding of the fp32 sum.  One thread = 4 consecutive columns of
 // one row; a 64-column block of the row statistic is 16 consecutive lanes.  `trans` = every column transposed (V^T).
 __global__ __launch_bounds__(256) void splitk_epilogue_kernel(GemmParams p, int S, int epi, int trans) {
   const int n4 = p.N >> 2;
   const long idx = (long)blockIdx.x * 256 + threadIdx.x;
   const bool live = idx < (long)p.M * n4;
   const int m = live ? (int)(idx / n4) : 0, n = live ? (int)(idx - (long)m * n4) * 4 : 0;
-  const size_t slab = (size_t)p.M * p.N;
-  const float* src = p.part + (size_t)m * p.N + n;
-  f32x4 a = *(const f32x4*)src;
-  int sl = 1;
-  for (; sl + 4 <= S; sl += 4) {                 // four independent loads in flight, added in slice order
-    const f32x4 b0 = *(const f32x4*)(src + (size_t)sl * slab), b1 = *(const f32x4*)(src + (size_t)(sl + 1) * slab);
-    const f32x4 b2 = *(const f32x4*)(src + (size_t)(sl + 2) * slab), b3 = *(const f32x4*)(src + (size_t)(sl + 3) * slab);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) a[j] = ((a[j] + b0[j]) + b1[j]) + b2[j] + b3[j];
-  }
-  for (; sl < S; ++sl) {
-    const f32x4 b = *(const f32x4*)(src + (size_t)sl * slab);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) a[j] += b[j];
-  }
+  f32x4 a = sum_slices(p.part + (size_t)m * p.N + n, (size_t)p.M * p.N, S);
   if (p.w_scale) {                                 // weight-fp8 launches: per-output-channel factor on the summed slices
 #pragma unroll
     for (int j = 0; j < 4; ++j) a[j] *= p.w_scale[n + j];
   }
-  bf16x4 bias = {(bf16)0.f, (bf16)0.f, (bf16)0.f, (bf16)0.f};
+  const bf16x4 zero = {(bf16)0.f, (bf16)0.f, (bf16)0.f, (bf16)0.f};
+  bf16x4 bias = zero;
   if (p.bias) bias = *(const bf16x4*)(p.bias + n);
   if (trans || (p.n_split && n >= p.n_split)) {
     if (!live) return;
-    bf16* const tout = p.n_split ? p.out2 : p.out;
-    const int tld = p.n_split ? p.ldo2 : p.ldo, tN = p.N - p.n_split;
-    const int bidx = m / p.T, t = m - bidx * p.T;
+    const TransOut tout = trans_out(p);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) tout[((size_t)bidx * tN + (n + j - p.n_split)) * tld + t] = (bf16)(a[j] + (float)bias[j]);
+    for (int j = 0; j < 4; ++j) *tout.at(m, n + j - p.n_split) = (bf16)(a[j] + (float)bias[j]);
     return;
   }
-  float y[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) y[j] = p.bias ? rbf(a[j] + (float)bias[j]) : rbf(a[j]);
-  if (epi == LTXK_EPI_BIAS_GELU) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) y[j] = gelu_tanh_f(y[j]);
-  } else if (epi == LTXK_EPI_BIAS_SILU) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) y[j] = silu_f(y[j]);
-  } else if (epi == LTXK_EPI_BIAS_GATE_RES || epi == LTXK_EPI_BIAS_RES || epi == LTXK_EPI_SCALE_RES) {
-    const bf16x4 r = *(const bf16x4*)(p.resid + (size_t)m * p.ldr + n);
-    if (epi == LTXK_EPI_BIAS_GATE_RES) {
-      const bf16x4 g = *(const bf16x4*)(p.gate + (size_t)(p.gate_row ? p.gate_row[m] : 0) * p.gate_stride + n);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) y[j] = (float)r[j] + rbf(y[j] * (float)g[j]);
-    } else if (epi == LTXK_EPI_BIAS_RES) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) y[j] = (float)r[j] + y[j];
-    } else {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) y[j] = (float)r[j] + rbf(p.alpha * a[j]);
-    }
-  }
-  bf16x4 o;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) o[j] = (bf16)y[j];
+  bf16x4 r = zero, g = zero;
+  if (epi == LTXK_EPI_BIAS_GATE_RES || epi == LTXK_EPI_BIAS_RES || epi == LTXK_EPI_SCALE_RES) r = *(const bf16x4*)(p.resid + (size_t)m * p.ldr + n);
+  if (epi == LTXK_EPI_BIAS_GATE_RES) g = *(const bf16x4*)(p.gate + (size_t)(p.gate_row ? p.gate_row[m] : 0) * p.gate_stride + n);
+  const bf16x4 o = epi_value(epi, a, p.bias != nullptr, bias, r, g, p.alpha);
   if (live) *(bf16x4*)(p.out + (size_t)m * p.ldo + n) = o;
   if (p.sumsq) {                                   // (N % 64 == 0: a 64-column block = 16 aligned consecutive lanes of one row)
-    float ss = 0.f;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float f = (float)o[j];
-      ss += f * f;
-    }
-    ss = group_sum<16>(ss);
+    const float ss = group_sum<16>(add_squares(0.f, o));
     if (live && (threadIdx.x & 15) == 0) p.sumsq[(size_t)m * p.sumsq_ld + (n >> 6)] = ss;
   }
 }
@@ -988,6 +876,7 @@ __device__ __forceinline__ void gemm_big_tile(const GemmParams& p, char* smem, i
 
   if constexpr (!TRANS) {
     // ---- epilogue: acc[i][j][q]: row = lane & 15, column = 4 * (lane >> 4) + q; direct 8-byte stores ----
+    static_assert(EPI == LTXK_EPI_BIAS || EPI == LTXK_EPI_BIAS_GELU || EPI == LTXK_EPI_BIAS_SILU, "no residual or gate operands on this tile");
     const int nq = (lane >> 4) * 4;
     const bool want_ss = p.sumsq != nullptr;
     bf16x4 bpre[8];
@@ -1004,39 +893,15 @@ __device__ __forceinline__ void gemm_big_tile(const GemmParams& p, char* smem, i
       for (int j = 0; j < 8; ++j) {
         if (m >= p.M) continue;
         const int n = n0 + wn * 128 + j * 16 + nq;
-        float y[4];
-        if (p.bias) {
-#pragma unroll
-          for (int q = 0; q < 4; ++q) y[q] = rbf(acc[i][j][q] + (float)bpre[j][q]);
-        } else {
-#pragma unroll
-          for (int q = 0; q < 4; ++q) y[q] = rbf(acc[i][j][q]);
-        }
-        if constexpr (EPI == LTXK_EPI_BIAS_GELU) {
-#pragma unroll
-          for (int q = 0; q < 4; ++q) y[q] = gelu_tanh_f(y[q]);
-        } else if constexpr (EPI == LTXK_EPI_BIAS_SILU) {
-#pragma unroll
-          for (int q = 0; q < 4; ++q) y[q] = silu_f(y[q]);
-        }
-        bf16x4 o;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) o[q] = (bf16)y[q];
-        if (want_ss) {                  // the 160x256 kernel's order: 16 values per lane and 64-column block, then the 4 lanes
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const float f = (float)o[q];
-            ss[j >> 2] += f * f;
-          }
-        }
+        const bf16x4 o = epi_value<EPI>(acc[i][j], p.bias != nullptr, bpre[j], bf16x4{}, bf16x4{}, 0.f);   // (no residual, gate or alpha here)
+        // the 160x256 kernel's order: 16 values per lane and 64-column block, then the 4 lanes
+        if (want_ss) ss[j >> 2] = add_squares(ss[j >> 2], o);
         *(bf16x4*)(p.out + (size_t)m * p.ldo + n) = o;
       }
       if (want_ss) {
 #pragma unroll
         for (int b = 0; b < 2; ++b) {
-          float v = ss[b];
-          v = lane_xor16_sum(v);
-          v = lane_xor32_sum(v);
+          const float v = wave_row_sum(ss[b]);
           if (lane < 16 && m < p.M) p.sumsq[(size_t)m * p.sumsq_ld + ((n0 + wn * 128) >> 6) + b] = v;
         }
       }
@@ -1044,9 +909,7 @@ __device__ __forceinline__ void gemm_big_tile(const GemmParams& p, char* smem, i
   } else {
     // acc[i][j][q]: n = lane & 15, token = 4 * (lane >> 4) + q; out[(b * tN + n - n_split) * ld + t]  (as the 160x256 kernel)
     const int tq = (lane >> 4) * 4;
-    bf16* const tout = p.n_split ? p.out2 : p.out;
-    const int tld = p.n_split ? p.ldo2 : p.ldo;
-    const int tN = p.N - p.n_split;
+    const TransOut tout = trans_out(p);
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const int n = n0 + wn * 128 + j * 16 + (lane & 15);
@@ -1054,24 +917,7 @@ __device__ __forceinline__ void gemm_big_tile(const GemmParams& p, char* smem, i
 #pragma unroll
       for (int i = 0; i < RB; ++i) {
         const int m = m0 + wm * 16 * RB + i * 16 + tq;
-        if (m >= p.M) continue;
-        bf16x4 o;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) o[q] = (bf16)(acc[i][j][q] + b);
-        const int bidx = m / p.T, t = m - bidx * p.T;
-        bf16* dst = tout + ((size_t)bidx * tN + (n - p.n_split)) * tld + t;
-        if ((p.T & 3) == 0 && m + 3 < p.M) {
-          *(bf16x4*)dst = o;
-        } else {
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const int mq = m + q;
-            if (mq < p.M) {
-              const int bq = mq / p.T, tqq = mq - bq * p.T;
-              tout[((size_t)bq * tN + (n - p.n_split)) * tld + tqq] = o[q];
-            }
-          }
-        }
+        if (m < p.M) tout.store4(m, n - p.n_split, acc[i][j], b);
       }
     }
   }

@@ -1,4 +1,5 @@
 // MFMA GEMM main loop shared by the dense (Linear) and implicit (conv3d) kernels.
+// (What follows the loop - accumulators to stored bf16 - is shared the same way in epilogue.h.)
 //
 //   C[m,n] = sum_k A[m,k] * W[n,k]          A rows and W rows are both k-contiguous bf16
 //

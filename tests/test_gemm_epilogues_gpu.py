@@ -297,3 +297,68 @@ def test_gemm_split_k_form(dev, M, N, K, S, monkeypatch, ab_lib):
             f"{name}: beyond 1 ulp on {float((d > ulp * 1.001).float().mean()):.2%}, max {float((d / ulp_big).max()):.1f} ulp"
         worst = max(worst, float((x.float() - r.float()).norm() / r.float().norm()))
     parity.auto(worst, 3e-3)
+
+
+@pytest.mark.parametrize("M,N,K,S", [(66, 512, 1024, 4), (320, 256, 512, 2)])
+def test_gemm_epilogue_one_definition_exact_sums(dev, M, N, K, S, monkeypatch, ab_lib):
+    """The epilogue is defined once (csrc/epilogue.h) and called by the 160-row tile, the 320- / 256-row tiles and the split-K
+    epilogue kernel.  With operands whose accumulators are exact in fp32 in ANY summation order (A: integers in [-3, 3], W:
+    integers in [-2, 2] / 8, K <= 1024: every partial sum is a multiple of 1/8 below 768) the three forms hand the epilogue the
+    same fp32 value, so every output - six epilogues, with and without bias, V^T, the split k | V^T launch - must be
+    bit-identical across them, and epilogues 0, 3, 4, 5 must equal a torch restatement (one IEEE fp32 operation, then
+    round-to-nearest-even to bf16, per step) exactly.  The row statistic is bit-identical between the tile forms; split-K adds
+    its 16 lanes in another order and is held to the sum of squares of what it stored.
+    (66, 512, 1024): ragged row tile, T = 33 -> element-store V^T; (320, 256, 512): T = 160 -> vector stores, one big-tile column."""
+    from mlx_video_amd import ops
+    g = torch.Generator(device=dev).manual_seed(M * 13 + N + K)
+    a = torch.randint(-3, 4, (M, K + 64), generator=g, device=dev).to(BF)[:, :K]          # row stride lda = K + 64
+    w = (torch.randint(-2, 3, (N, K), generator=g, device=dev).float() / 8).to(BF)
+    _, _, b, res, gate, grow = _operands(M, N, K, dev, M * 13 + N + K + 1)
+    acc64 = a.double().cpu() @ w.double().cpu().t()
+    assert torch.equal(acc64.float().double(), acc64) and float(acc64.abs().max()) <= 768, "premise: the sums are exact in fp32"
+    T = M // 2
+    ld = (T + 63) // 64 * 64
+
+    def run(big, ksplit, rows):
+        """rows: the tile height the launches must take - 0 = split-K with S slices (every epilogue), else the 160-row family
+        (at most 160) or the big tile of that height where it has the epilogue (0, 1, 2; the others stay single-pass)"""
+        from mlx_video_amd import _lib
+        monkeypatch.setenv("LTXK_GEMM_BIG", big)
+        monkeypatch.setenv("LTXK_GEMM_KSPLIT", ksplit)
+        for epi in range(6):
+            pl = ops.gemm_plan(M, N, K, epilogue=epi, lda=K + 64, ldo=N + 64, sumsq=epi in (0, 3, 4))      # (as _all_outputs launches it)
+            if rows == 0:
+                assert pl.form == _lib.GEMM_FORM_SPLITK and pl.slices == S, (epi, pl)
+            elif rows > 160 and epi <= 2:
+                assert pl.form == _lib.GEMM_FORM_BIG and pl.tile_rows == rows, (epi, pl)
+            else:
+                assert pl.form == _lib.GEMM_FORM_SINGLE and pl.tile_rows <= 160, (epi, pl)
+        for kw in (dict(out_tokens_per_batch=T), dict(out_tokens_per_batch=T, n_split=256, sumsq=True) if N > 256 else None):
+            if kw is not None:
+                pl = ops.gemm_plan(M, N, K, lda=K + 64, **kw)
+                want = _lib.GEMM_FORM_SPLITK if rows == 0 else (_lib.GEMM_FORM_BIG if rows > 160 else _lib.GEMM_FORM_SINGLE)
+                assert pl.form == want and (rows <= 160 or pl.tile_rows == rows), (kw, pl)
+        return _all_outputs(ops, a, w, b, res, gate, grow, T, ld, N, M, dev)
+    single = run("0", "-1", 160)
+    for form, got in (("320-row tile", run("2", "-1", 320)), ("256-row tile", run("3", "-1", 256))):
+        for name, x in single.items():
+            assert torch.equal(x, got[name]), f"{name}: {form} differs from the 160-row tile"
+    split = run("0", str(S), 0)
+    for name, x in single.items():
+        if name.endswith("sumsq"):
+            y = split[name[:-6]] if name != "split.sumsq" else split["split.k"]
+            sq = (y.float() ** 2).reshape(M, -1, 64).sum(-1)
+            assert float((split[name][:, :sq.shape[1]] - sq).abs().max() / sq.abs().max()) < 1e-5, name
+        else:
+            assert torch.equal(x, split[name]), f"{name}: split-K differs from the 160-row tile"
+
+    acc = acc64.float().to(dev)
+    alpha = torch.tensor(0.8, dtype=torch.float32, device=dev)
+    for use_bias in (True, False):
+        yb = ((acc + b.float()) if use_bias else acc).to(BF).float()
+        ref = {0: yb.to(BF),
+               3: (res.float() + (yb * gate.float()[grow.long()]).to(BF).float()).to(BF),
+               4: (res.float() + yb).to(BF),
+               5: (res.float() + (alpha * acc).to(BF).float()).to(BF)}
+        for epi, r in ref.items():
+            assert torch.equal(single[f"epi{epi}.bias{use_bias}"], r), f"epilogue {epi} bias={use_bias}: not the fp32 restatement"
