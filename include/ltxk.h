@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define LTXK_VERSION 409
+#define LTXK_VERSION 410
 
 #define LTXK_OK 0
 #define LTXK_EINVAL (-1)   /* bad argument (shape / alignment / null pointer) */
@@ -452,7 +452,7 @@ int ltxk_euler_step(const void* latent, const void* denoised, void* out, int64_t
  * Text stage: from the hidden states of a Gemma-3 forward to the DiT's context.  norm_and_concat_hidden_states
  * (text_encoder.py:591-639) and the row operations of Embeddings1DConnector (text_encoder.py:271-587) at widths the
  * DiT's row kernels do not take (D = 3840, H = 30).  The GEMMs and the attention of the connector are ltxk_gemm_bf16
- * and ltxk_flash_attn.  Gemma itself is not part of this library.
+ * and ltxk_flash_attn.  The Gemma-3 forward that produces the hidden states is the next section.
  *
  * The layer stack is ONE base pointer with explicit strides (in elements): element (l, b, t, d) of the L hidden states
  * is x[l*layer_stride + b*batch_stride + t*row_stride + d].  A caller that holds the layers as separately allocated
@@ -503,6 +503,76 @@ int ltxk_gelu_erf(void* x, int64_t n, void* stream);
 int ltxk_connector_assemble(const void* feat, int32_t ldf, const void* registers, const int32_t* row0,
                             const int32_t* row_count, void* out, int32_t B, int32_t T, int32_t D, int32_t R,
                             int32_t feat_rows, void* stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Gemma-3 text encoder: token ids to the L+1 hidden states the text stage above consumes.  The reference wraps mlx_vlm's
+ * Gemma3Model (text_encoder.py:47-152: embedding scale :107, left padding and the combined causal-and-padding mask :58-81,
+ * the list [embeddings, h_1 .. h_{L-1}, norm(h_L)] :110-148); the layer itself is the Gemma-3 definition (transformers'
+ * Gemma3TextModel).  The no-bias Linears are ltxk_gemm_bf16; what follows are the four row operations and the attention
+ * that the library had no kernel for.  r(.) = one rounding to bf16 with fp32 arithmetic in front of it.  Row kernels take
+ * any D % 8 == 0, D <= 8192, hold the row in registers, reduce in a fixed order that depends on the row's width only and
+ * use no atomics; pointers 16-byte aligned, row strides multiples of 8.
+ * ------------------------------------------------------------------------------------- */
+
+/* out[m,:] = r(table[ids[m],:] * s): the embedding gather with Gemma's scale, s = bf16(sqrt(D)) passed as a float (62.0 at
+ * D = 3840; text_encoder.py:107 rounds the scale to bf16 first).  table (V,D) bf16 contiguous, ids (M) DEVICE int32,
+ * out (M,D) row stride ldo.  The kernel cannot report an error for device data: an id outside [0, V) reads row 0 / V-1;
+ * a caller that needs the range checked checks its host copy.                                                          */
+int ltxk_embed_rows(const void* table, int32_t V, int32_t D, const int32_t* ids, void* out, int32_t ldo, int32_t M,
+                    float s, void* stream);
+
+/* Gemma RMSNorm (Gemma3RMSNorm): n = r(x * rsqrt(mean(x^2) + eps) * (1 + w)), w (D) bf16 widened so that 1 + w is formed in
+ * fp32.  resid == NULL: y = n.  Otherwise y = r(resid + n), the decoder layer's post-norm-then-add (n is a bf16 tensor in
+ * the model, so it is rounded before the add); y may be resid, and y may be x.  x (M,D) stride ldx, resid stride ldr,
+ * y stride ldy.  The sum of squares: each lane adds its elements in ascending order, then the wave's butterfly.       */
+int ltxk_rmsnorm_weight_rows(const void* x, int32_t ldx, const void* weight, const void* resid, int32_t ldr, void* y,
+                             int32_t ldy, int32_t M, int32_t D, float eps, void* stream);
+
+/* q_norm / k_norm + RoPE, in place on the first (Hq + Hkv) * 256 columns of buf (M, ld): the q | k part of the fused q|k|v
+ * projection, head hh < Hq a query head (q_weight), the next Hkv key heads (k_weight); weights (256) bf16.  Per 256-wide head:
+ *   x' = r(x * rsqrt(mean(x^2) + eps) * (1 + w)), then the rotate-half rotation on the pairs (i, i + 128), i < 128:
+ *   o1 = r(x1' * c - x2' * s), o2 = r(x2' * c + x1' * s), c = cos[t*128 + i], s = sin[t*128 + i], t = m % T.
+ * cos / sin: (T,128) fp32.  The position of a row is its index in the PADDED sequence, 0 .. T-1, whatever the attention
+ * mask - what the reference's nn.RoPE call (offset 0) and transformers' default position_ids both do.  The caller builds the
+ * tables (float64 on the host, rounded to bf16 and widened; one pair for the local base, one for the global base with its
+ * linear position scaling).  Columns past (Hq + Hkv) * 256 are not touched.                                           */
+int ltxk_headnorm_rope(void* buf, int32_t ld, int32_t M, int32_t Hq, int32_t Hkv, const void* q_weight, const void* k_weight,
+                       const float* cos, const float* sin, int32_t T, float eps, void* stream);
+
+/* GeGLU: out[m,f] = r(r(gelu_tanh(g[m,f])) * u[m,f]) for gu = [g | u] (M, 2F) row stride ld, the output of one GEMM over the
+ * stacked gate | up panel; out (M,F) row stride ldo, and out may be gu with ldo == ld (the product then replaces g).
+ * gelu_tanh(x) = x / (1 + exp(-2 sqrt(2/pi) (x + 0.044715 x^3))) in fp32, which keeps its relative accuracy on the
+ * negative side; F % 8 == 0.                                                                                          */
+int ltxk_geglu_tanh(const void* gu, int32_t ld, void* out, int32_t ldo, int32_t M, int32_t F, void* stream);
+
+/* Causal, left-padding-aware, grouped-query attention, head dim 256.
+ *   q  : (B,T,Hq*256)  bf16 row stride ldq          k : (B,T,Hkv*256) bf16 row stride ldk
+ *   vt : (B,Hkv*256,ldvt) bf16 = V transposed, exactly as ltxk_gemm_bf16's split output writes it (n_split = (Hq+Hkv)*256
+ *        gives q | k row-major and V^T in one launch); ldvt >= T, a multiple of 8; columns >= T are read in whole 16-byte
+ *        chunks and must be finite
+ *   out: (B,T,Hq*256) bf16 row stride ldo
+ * Hq % Hkv == 0; query head h reads K/V head h / (Hq/Hkv).  row_start (B) DEVICE int32, the text stage's convention: the
+ * valid tokens of batch row b are [row_start[b], T) (clipped into [0, T]).  window: 0 = none, else a positive count.
+ * Key j is visible to query i iff  row_start[b] <= j <= i  and  (window == 0 or i - j < window).
+ * Rounding points are ltxk_flash_attn's ("flash" policy) over the visible keys: S = q.k^T in fp32; P = exp2(fma(S, scale*log2 e,
+ * -M)) with M an integer row offset (the ceil of the running maximum over visible keys); l = sum P in fp32;
+ * O = r((bf16(P) @ V) / l).  A masked key contributes P = 0 exactly (its K row may hold anything, its V row anything finite).
+ * A query row i < row_start[b] has no visible key and gets an all-zero output row (no NaN, no division by l = 0).
+ * Key tiles wholly outside the visible range of a 64-row query tile are not fetched, and a query tile wholly in the
+ * padding only stores zeros.  Keys are never split across workgroups: the bits of a (batch, head) depend on its own
+ * data, row_start[b], window and T, not on what else the launch holds.                                                */
+typedef struct ltxk_causal_attn_args {
+  const void* q; const void* k; const void* vt; void* out;
+  const int32_t* row_start;
+  int32_t ldq, ldk, ldvt, ldo;
+  int32_t B, Hq, Hkv, T;
+  int32_t window;
+  float scale;
+} ltxk_causal_attn_args;
+
+int ltxk_causal_attn(const ltxk_causal_attn_args* args, void* stream);
+/* sizeof(ltxk_causal_attn_args) in this build (an entry of its own: the ltxk_abi_sizeof index list is closed).          */
+int ltxk_causal_attn_args_sizeof(void);
 
 /* ---------------------------------------------------------------------------------------
  * Video VAE (volumes are channels-last (B,D,H,W,C) bf16; a row = one voxel)

@@ -106,6 +106,14 @@ class GuiderArgs(Structure):
     ]
 
 
+class CausalAttnArgs(Structure):
+    _fields_ = [
+        ("q", c_void_p), ("k", c_void_p), ("vt", c_void_p), ("out", c_void_p), ("row_start", c_void_p),
+        ("ldq", c_int32), ("ldk", c_int32), ("ldvt", c_int32), ("ldo", c_int32),
+        ("B", c_int32), ("Hq", c_int32), ("Hkv", c_int32), ("T", c_int32), ("window", c_int32), ("scale", c_float),
+    ]
+
+
 # name -> (restype, argtypes); mirrors include/ltxk.h one to one.
 SIGNATURES = {
     "ltxk_version": (c_int32, []),
@@ -190,6 +198,15 @@ SIGNATURES = {
     "ltxk_gelu_erf": (c_int32, [c_void_p, c_int64, c_void_p]),
     "ltxk_connector_assemble": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32,
                                           c_int32, c_int32, c_void_p]),
+    # Gemma-3 text encoder (csrc/gemma_ops.hip, csrc/causal_attn.hip)
+    "ltxk_embed_rows": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_float, c_void_p]),
+    "ltxk_rmsnorm_weight_rows": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_int32,
+                                           c_float, c_void_p]),
+    "ltxk_headnorm_rope": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_int32, c_float, c_void_p]),
+    "ltxk_geglu_tanh": (c_int32, [c_void_p, c_int32, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
+    "ltxk_causal_attn": (c_int32, [POINTER(CausalAttnArgs), c_void_p]),
+    "ltxk_causal_attn_args_sizeof": (c_int32, []),
 }
 
 # ltxk_abi_sizeof(i) is the size of ABI_STRUCTS[i]
@@ -222,7 +239,8 @@ def _open(path: str) -> ctypes.CDLL:
                             f"{ctypes.sizeof(st)} in this binding; rebuild it (make -C mlx-video_amd/csrc)")
     # (structs added after the ltxk_abi_sizeof index list was closed report their size through an entry of their own)
     for fn, st in ((lib.ltxk_gemm_grouped_args_sizeof, GemmGroupedArgs), (lib.ltxk_conv3d_plan_sizeof, Conv3dPlan),
-                   (lib.ltxk_flash_attn_plan_sizeof, AttnPlan), (lib.ltxk_guider_args_sizeof, GuiderArgs)):
+                   (lib.ltxk_flash_attn_plan_sizeof, AttnPlan), (lib.ltxk_guider_args_sizeof, GuiderArgs),
+                   (lib.ltxk_causal_attn_args_sizeof, CausalAttnArgs)):
         if fn() != ctypes.sizeof(st):
             raise LtxkError(f"{path} is stale: sizeof({st.__name__}) is {fn()} in the library, "
                             f"{ctypes.sizeof(st)} in this binding; rebuild it (make -C mlx-video_amd/csrc)")

@@ -1,0 +1,280 @@
+"""The Gemma-3 text encoder on the device: token ids to the L+1 hidden states ``TextConnector`` consumes.
+
+The reference wraps ``mlx_vlm``'s Gemma3Model (mlx_video/models/ltx/text_encoder.py:47-152, ``LanguageModel``).  The wrapper is
+followed: the embedding scale rounded to bf16 (:107), left padding with the combined causal-and-padding mask (:58-81), and the
+list ``[embeddings, h_1 .. h_{L-1}, norm(h_L)]`` of L+1 states (:110-148).  The decoder layer is the Gemma-3 definition as
+``transformers`` implements it (``Gemma3TextModel``): (1 + w) RMSNorms before and after attention and feed-forward, per-head
+q/k norms, rotate-half RoPE with a local and a (linearly scaled) global base, grouped-query attention at head dim 256 scaled by
+``query_pre_attn_scalar ** -0.5``, a tanh-GeGLU feed-forward, no biases.
+
+What differs from the reference's mask, and why it computes the same thing: local layers pass the config's sliding window
+to the attention kernel (key j visible to query i iff i - j < window), where the reference uses the full causal mask on every
+layer (:116-132).  The two agree for every T <= window, and the reference's tokeniser call (:929-935, max_length 1024, window
+1024) never produces another length.
+
+The run stays on the padded (B,T) layout.  Padded rows carry finite values through the row kernels and GEMMs and nothing
+reads them: attention never admits a key below row_start and writes zeros to query rows below it.  Every GEMM is called with
+``split_k=False`` and the attention kernel never splits keys, so a batch row's bits do not depend on the batch.
+"""
+from __future__ import annotations
+
+import json
+import math
+from dataclasses import dataclass, field
+from pathlib import Path
+from typing import Dict, Optional, Sequence, Tuple, Union
+
+import numpy as np
+import torch
+
+from . import ops
+from .text_connector import mask_row_counts
+
+BF16 = torch.bfloat16
+HEAD_DIM = 256
+MAX_TOKENS = 1024           # the reference's tokeniser call: max_length 1024, left-padded (text_encoder.py:929-935)
+
+
+@dataclass(frozen=True)
+class GemmaConfig:
+    hidden_size: int = 3840
+    num_hidden_layers: int = 48
+    num_attention_heads: int = 16
+    num_key_value_heads: int = 8
+    head_dim: int = 256
+    intermediate_size: int = 15360
+    vocab_size: int = 262208
+    sliding_window: int = 1024
+    layer_types: Tuple[str, ...] = field(default=())      # "sliding_attention" / "full_attention" per layer; () = by pattern
+    sliding_window_pattern: int = 6
+    query_pre_attn_scalar: float = 256.0
+    rms_norm_eps: float = 1e-6
+    rope_theta: float = 1_000_000.0                       # global layers
+    rope_local_base_freq: float = 10_000.0                # local (sliding) layers
+    rope_scaling_factor: float = 1.0                      # linear position scaling of the global layers
+
+    def __post_init__(self):
+        if self.head_dim != HEAD_DIM:
+            raise ValueError(f"GemmaConfig: head_dim {self.head_dim} is not supported (the attention kernel is built for {HEAD_DIM})")
+        if self.num_attention_heads % self.num_key_value_heads:
+            raise ValueError(f"GemmaConfig: {self.num_attention_heads} heads are not a multiple of {self.num_key_value_heads} KV heads")
+        if self.hidden_size % 8 or self.intermediate_size % 8:
+            raise ValueError("GemmaConfig: hidden and intermediate sizes must be multiples of 8")
+        if self.layer_types and len(self.layer_types) != self.num_hidden_layers:
+            raise ValueError(f"GemmaConfig: {len(self.layer_types)} layer_types for {self.num_hidden_layers} layers")
+        bad = set(self.layer_types) - {"sliding_attention", "full_attention"}
+        if bad:
+            raise ValueError(f"GemmaConfig: unknown layer types {sorted(bad)}")
+        if self.sliding_window <= 0 or self.sliding_window_pattern <= 0:
+            raise ValueError("GemmaConfig: sliding_window and sliding_window_pattern must be positive")
+
+    def is_global(self, i: int) -> bool:
+        """Layer i attends globally: by ``layer_types`` when the config lists them, else i % pattern == pattern - 1
+        (text_encoder.py:123-126)."""
+        if self.layer_types:
+            return self.layer_types[i] == "full_attention"
+        return i % self.sliding_window_pattern == self.sliding_window_pattern - 1
+
+    @staticmethod
+    def from_dict(cfg: dict) -> "GemmaConfig":
+        """From a Gemma-3 ``config.json`` dict: the ``text_config`` entry when there is one, else the top level
+        (text_encoder.py:222-227).  Rope fields in either spelling: ``rope_theta`` / ``rope_local_base_freq`` / ``rope_scaling``
+        or the ``rope_parameters`` dict of newer ``transformers`` ({"full_attention": {...}, "sliding_attention": {...}})."""
+        c = cfg.get("text_config", cfg)
+        if c.get("attn_logit_softcapping") is not None:
+            raise ValueError(f"GemmaConfig: attn_logit_softcapping={c['attn_logit_softcapping']}: attention soft-capping is not supported")
+        d = GemmaConfig()
+        theta, local, factor = c.get("rope_theta", d.rope_theta), c.get("rope_local_base_freq", d.rope_local_base_freq), 1.0
+        scaling = c.get("rope_scaling")
+        rp = c.get("rope_parameters")
+        if rp:
+            full, slide = rp.get("full_attention") or {}, rp.get("sliding_attention") or {}
+            theta, local = full.get("rope_theta", theta), slide.get("rope_theta", local)
+            if slide.get("rope_type", "default") != "default":
+                raise ValueError(f"GemmaConfig: rope type {slide.get('rope_type')!r} on the local layers is not supported")
+            scaling = full if full.get("rope_type", "default") != "default" else scaling
+        if scaling:
+            kind = scaling.get("rope_type", scaling.get("type", "linear"))
+            if kind != "linear":
+                raise ValueError(f"GemmaConfig: rope scaling {kind!r} is not supported (Gemma-3 uses linear)")
+            factor = float(scaling.get("factor", 1.0))
+        lt = c.get("layer_types")
+        return GemmaConfig(
+            hidden_size=int(c.get("hidden_size", d.hidden_size)), num_hidden_layers=int(c.get("num_hidden_layers", d.num_hidden_layers)),
+            num_attention_heads=int(c.get("num_attention_heads", d.num_attention_heads)),
+            num_key_value_heads=int(c.get("num_key_value_heads", d.num_key_value_heads)), head_dim=int(c.get("head_dim", d.head_dim)),
+            intermediate_size=int(c.get("intermediate_size", d.intermediate_size)), vocab_size=int(c.get("vocab_size", d.vocab_size)),
+            sliding_window=int(c.get("sliding_window", d.sliding_window)), layer_types=tuple(lt) if lt else (),
+            sliding_window_pattern=int(c.get("sliding_window_pattern", d.sliding_window_pattern)),
+            query_pre_attn_scalar=float(c.get("query_pre_attn_scalar", d.query_pre_attn_scalar)),
+            rms_norm_eps=float(c.get("rms_norm_eps", d.rms_norm_eps)), rope_theta=float(theta), rope_local_base_freq=float(local),
+            rope_scaling_factor=factor)
+
+    @staticmethod
+    def from_json(path: Union[str, Path]) -> "GemmaConfig":
+        p = Path(path)
+        p = p / "config.json" if p.is_dir() else p
+        with open(p) as f:
+            return GemmaConfig.from_dict(json.load(f))
+
+
+def rope_table_half(T: int, base: float, factor: float = 1.0, dim: int = HEAD_DIM) -> Tuple[torch.Tensor, torch.Tensor]:
+    """cos, sin (T, dim/2) fp32 of the rotate-half RoPE: angle(t, i) = (t / factor) * base^(-2i/dim), float64 on the host,
+    rounded to bf16 (the model hands the tables over in the activations' dtype: a rounding point, kept) and widened -
+    ``rope_table_1d``'s convention."""
+    inv = 1.0 / np.power(float(base), np.arange(0, dim, 2, dtype=np.float64) / dim) / float(factor)
+    ang = np.arange(T, dtype=np.float64)[:, None] * inv[None, :]
+    return tuple(torch.from_numpy(f(ang).astype(np.float32)).to(BF16).to(torch.float32).contiguous() for f in (np.cos, np.sin))
+
+
+class GemmaEncoder:
+    """``GemmaEncoder(weights, config)(input_ids, attention_mask) -> (L+1, B, T, D) bf16`` on the device.  ``weights``: device
+    bf16 tensors under the language model's own keys (``embed_tokens.weight``, ``layers.{i}.self_attn.{q,k,v,o}_proj.weight``,
+    ``...self_attn.{q,k}_norm.weight``, ``...mlp.{gate,up,down}_proj.weight``, the four layer norms, ``norm.weight``)
+    - what ``weights.gemma_weights`` returns.  The q|k|v and gate|up panels are stacked once, here; the dict's own tensors of
+    those are not kept."""
+
+    def __init__(self, weights: Dict[str, torch.Tensor], config: GemmaConfig):
+        self.cfg = c = config
+        if "embed_tokens.weight" not in weights:
+            raise ValueError("no embed_tokens.weight in the Gemma weights (expected the keys of weights.gemma_weights)")
+        g = lambda k: weights[k].to(BF16).contiguous()
+        self.embed = g("embed_tokens.weight")
+        self.device = self.embed.device
+        if tuple(self.embed.shape[1:]) != (c.hidden_size,):
+            raise ValueError(f"embed_tokens.weight is {tuple(self.embed.shape)}, the config's hidden size {c.hidden_size}")
+        self.vocab = int(self.embed.shape[0])
+        self.norm = g("norm.weight")
+        self.embed_scale = float(torch.tensor(c.hidden_size ** 0.5, dtype=BF16))          # text_encoder.py:107
+        self.scale = float(c.query_pre_attn_scalar) ** -0.5
+        nq, nkv = c.num_attention_heads * HEAD_DIM, c.num_key_value_heads * HEAD_DIM
+        self.layers = []
+        for i in range(c.num_hidden_layers):
+            q = f"layers.{i}."
+            qkv = torch.cat([g(q + "self_attn.q_proj.weight"), g(q + "self_attn.k_proj.weight"), g(q + "self_attn.v_proj.weight")], 0)
+            gu = torch.cat([g(q + "mlp.gate_proj.weight"), g(q + "mlp.up_proj.weight")], 0)
+            if tuple(qkv.shape) != (nq + 2 * nkv, c.hidden_size) or tuple(gu.shape) != (2 * c.intermediate_size, c.hidden_size):
+                raise ValueError(f"layer {i}: q|k|v panel {tuple(qkv.shape)} / gate|up panel {tuple(gu.shape)} do not match the config")
+            self.layers.append(dict(
+                qkv=qkv.contiguous(), gu=gu.contiguous(), o=g(q + "self_attn.o_proj.weight"), down=g(q + "mlp.down_proj.weight"),
+                qn=g(q + "self_attn.q_norm.weight"), kn=g(q + "self_attn.k_norm.weight"),
+                n_in=g(q + "input_layernorm.weight"), n_post_attn=g(q + "post_attention_layernorm.weight"),
+                n_pre_ff=g(q + "pre_feedforward_layernorm.weight"), n_post_ff=g(q + "post_feedforward_layernorm.weight"),
+                window=0 if c.is_global(i) else c.sliding_window, is_global=c.is_global(i)))
+        self._rope: Dict[Tuple[int, bool], Tuple[torch.Tensor, torch.Tensor]] = {}
+
+    def _tables(self, T: int, is_global: bool):
+        key = (T, is_global)
+        if key not in self._rope:
+            c = self.cfg
+            cs = rope_table_half(T, c.rope_theta, c.rope_scaling_factor) if is_global else rope_table_half(T, c.rope_local_base_freq)
+            self._rope[key] = tuple(t.to(self.device) for t in cs)
+        return self._rope[key]
+
+    def __call__(self, input_ids: torch.Tensor, attention_mask: torch.Tensor) -> torch.Tensor:
+        counts = mask_row_counts(attention_mask)
+        if input_ids.dim() != 2 or tuple(input_ids.shape) != tuple(attention_mask.shape):
+            raise ValueError(f"input_ids {tuple(input_ids.shape)} and attention_mask {tuple(attention_mask.shape)} must be one (B,T) shape")
+        if input_ids.dtype.is_floating_point or input_ids.dtype == torch.bool:
+            raise TypeError(f"input_ids must be integers, got {input_ids.dtype}")
+        c, dev = self.cfg, self.device
+        B, T = input_ids.shape
+        M, D, F = B * T, c.hidden_size, c.intermediate_size
+        Hq, Hkv = c.num_attention_heads, c.num_key_value_heads
+        nq, nkv = Hq * HEAD_DIM, Hkv * HEAD_DIM
+        ids_host = input_ids.detach().to("cpu").reshape(-1)
+        ids = ids_host.to(torch.int32).to(dev)
+        row_start = torch.tensor([T - n for n in counts], dtype=torch.int32, device=dev)
+        L = c.num_hidden_layers
+        states = torch.empty((L + 1, B, T, D), dtype=BF16, device=dev)
+        x = ops.embed_rows(self.embed, ids, self.embed_scale, out=states[0].view(M, D), ids_host=ids_host)
+        nx = torch.empty((M, D), dtype=BF16, device=dev)
+        qk = torch.empty((M, nq + nkv), dtype=BF16, device=dev)
+        tpad = (T + 63) // 64 * 64
+        vt = (torch.zeros if tpad != T else torch.empty)((B, nkv, tpad), dtype=BF16, device=dev)      # pad columns stay finite
+        att = torch.empty((M, nq), dtype=BF16, device=dev)
+        po = torch.empty((M, D), dtype=BF16, device=dev)
+        gu = torch.empty((M, 2 * F), dtype=BF16, device=dev)
+        for i, ly in enumerate(self.layers):
+            cos, sin = self._tables(T, ly["is_global"])
+            ops.rmsnorm_weight_rows(x, ly["n_in"], c.rms_norm_eps, out=nx)
+            ops.gemm(nx, ly["qkv"], None, out=qk, out2=vt, n_split=nq + nkv, out_tokens_per_batch=T, split_k=False)
+            ops.headnorm_rope(qk, Hq, Hkv, ly["qn"], ly["kn"], cos, sin, T, c.rms_norm_eps)
+            ops.causal_attn(qk[:, :nq], qk[:, nq:], vt, att, row_start, B, Hq, Hkv, T, self.scale, window=ly["window"])
+            ops.gemm(att, ly["o"], None, out=po, split_k=False)
+            # the layer's output goes straight into its slot of the stack (the last layer's into scratch: its slot takes norm(h_L))
+            y = states[i + 1].view(M, D) if i + 1 < L else nx.new_empty((M, D))
+            ops.rmsnorm_weight_rows(po, ly["n_post_attn"], c.rms_norm_eps, resid=x, out=y)
+            ops.rmsnorm_weight_rows(y, ly["n_pre_ff"], c.rms_norm_eps, out=nx)
+            ops.gemm(nx, ly["gu"], None, out=gu, split_k=False)
+            h = ops.geglu_tanh_(gu)
+            ops.gemm(h, ly["down"], None, out=po, split_k=False)
+            ops.rmsnorm_weight_rows(po, ly["n_post_ff"], c.rms_norm_eps, resid=y, out=y)
+            x = y
+        ops.rmsnorm_weight_rows(x, self.norm, c.rms_norm_eps, out=states[L].view(M, D))
+        return states
+
+
+def random_gemma_weights(device, config: GemmaConfig, seed: int = 23, generator_device=None) -> Dict[str, torch.Tensor]:
+    """Seeded stand-in weights under the language model's keys (tests and measurement; no checkpoint is read)."""
+    gd = generator_device or "cpu"
+    g = torch.Generator(device=gd).manual_seed(seed)
+    c = config
+
+    def rn(*shape, std=1.0):
+        return (torch.randn(shape, generator=g, device=gd) * std).to(BF16).to(device)
+
+    D, F, nq, nkv = c.hidden_size, c.intermediate_size, c.num_attention_heads * HEAD_DIM, c.num_key_value_heads * HEAD_DIM
+    W = {"embed_tokens.weight": rn(c.vocab_size, D, std=1.0 / math.sqrt(D)), "norm.weight": rn(D, std=0.1)}
+    for i in range(c.num_hidden_layers):
+        p = f"layers.{i}."
+        W[p + "self_attn.q_proj.weight"] = rn(nq, D, std=1.0 / math.sqrt(D))
+        W[p + "self_attn.k_proj.weight"] = rn(nkv, D, std=1.0 / math.sqrt(D))
+        W[p + "self_attn.v_proj.weight"] = rn(nkv, D, std=1.0 / math.sqrt(D))
+        W[p + "self_attn.o_proj.weight"] = rn(D, nq, std=1.0 / math.sqrt(nq))
+        W[p + "self_attn.q_norm.weight"], W[p + "self_attn.k_norm.weight"] = rn(HEAD_DIM, std=0.1), rn(HEAD_DIM, std=0.1)
+        W[p + "mlp.gate_proj.weight"], W[p + "mlp.up_proj.weight"] = rn(F, D, std=1.0 / math.sqrt(D)), rn(F, D, std=1.0 / math.sqrt(D))
+        W[p + "mlp.down_proj.weight"] = rn(D, F, std=1.0 / math.sqrt(F))
+        for n in ("input_layernorm", "post_attention_layernorm", "pre_feedforward_layernorm", "post_feedforward_layernorm"):
+            W[p + n + ".weight"] = rn(D, std=0.1)
+    return W
+
+
+# ------------------------------------------------------------------------------------------------------------ tokenizer
+def load_tokenizer(path: Union[str, Path]):
+    """The ``tokenizers.Tokenizer`` of a local directory holding ``tokenizer.json`` (or of that file).  Nothing is fetched and
+    repo names are not resolved."""
+    p = Path(path)
+    f = p / "tokenizer.json" if p.is_dir() else p
+    if not f.is_file():
+        raise FileNotFoundError(f"no tokenizer.json at {p}: pass tokenizer_path= a local directory that holds one, or tokenise "
+                                "elsewhere and pass prompt_tokens=(input_ids, attention_mask)")
+    try:
+        from tokenizers import Tokenizer
+    except ImportError as e:
+        raise RuntimeError("the `tokenizers` package is not installed: tokenise elsewhere and pass prompt_tokens=(input_ids, "
+                           "attention_mask), or --prompt-tokens FILE") from e
+    return Tokenizer.from_file(str(f))
+
+
+def _pad_id(tok) -> int:
+    for name in ("<pad>", "[PAD]", "<|pad|>"):
+        i = tok.token_to_id(name)
+        if i is not None:
+            return int(i)
+    return 0                # Gemma's <pad> is id 0
+
+
+def tokenize(tok, prompts: Sequence[str], max_length: int = MAX_TOKENS, pad_id: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(input_ids, attention_mask), each (len(prompts), max_length) int64: every prompt encoded with the tokenizer's own special
+    tokens, truncated to ``max_length`` and LEFT-padded with the pad id, mask 0 on the padding (text_encoder.py:929-935)."""
+    pad = _pad_id(tok) if pad_id is None else int(pad_id)
+    tok.no_padding(); tok.no_truncation()           # a tokenizer.json may carry its own (right-)padding settings
+    ids = torch.full((len(prompts), max_length), pad, dtype=torch.int64)
+    mask = torch.zeros((len(prompts), max_length), dtype=torch.int64)
+    for b, text in enumerate(prompts):
+        e = list(tok.encode(text).ids)[:max_length]
+        if e:
+            ids[b, max_length - len(e):] = torch.tensor(e, dtype=torch.int64)
+            mask[b, max_length - len(e):] = 1
+    return ids, mask

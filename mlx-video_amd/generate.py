@@ -191,6 +191,38 @@ def _connect_gemma(hs, mask, neg_hs, neg_mask, text_connector, model_repo, dev):
     return out[0:1], out[1:2]
 
 
+def _as_tokens(tokens, what: str):
+    """(input_ids, attention_mask) as (1,T) tensors from a pair of tensors / arrays / lists."""
+    if not isinstance(tokens, (tuple, list)) or len(tokens) != 2:
+        raise ValueError(f"{what} must be an (input_ids, attention_mask) pair")
+    ids, mask = (torch.as_tensor(np.asarray(t) if not isinstance(t, torch.Tensor) else t) for t in tokens)
+    ids, mask = ids.reshape(-1, ids.shape[-1]), mask.reshape(-1, mask.shape[-1])
+    if ids.shape != mask.shape or ids.shape[0] != 1:
+        raise ValueError(f"{what}: input_ids and attention_mask must both be (T,) or (1,T), got {tuple(ids.shape)} and {tuple(mask.shape)}")
+    return ids, mask
+
+
+def _encode_gemma(gemma, gemma_repo, tokenizer_path, prompt, negative_prompt, prompt_tokens, negative_prompt_tokens, dev):
+    """(hidden states (L+1,2,T,D), mask (2,T)) of the positive and the negative prompt: tokens -> GemmaEncoder as ONE B = 2 call.
+    Tokens are taken as given, or made from the prompt strings with the tokenizer.json of ``tokenizer_path`` / ``gemma_repo``."""
+    from .gemma import GemmaConfig, GemmaEncoder, load_tokenizer, tokenize
+    if gemma is None:
+        from .weights import gemma_weights
+        gemma = GemmaEncoder(gemma_weights(gemma_repo, dev), GemmaConfig.from_json(gemma_repo))
+    if prompt_tokens is None or negative_prompt_tokens is None:
+        where = tokenizer_path or gemma_repo
+        if where is None:
+            raise ValueError("a Gemma encoder was given without tokens: pass prompt_tokens= and negative_prompt_tokens= "
+                             "((input_ids, attention_mask) pairs), or tokenizer_path= / gemma_repo= a local directory with a tokenizer.json")
+        tok = load_tokenizer(where)
+    pos = _as_tokens(prompt_tokens, "prompt_tokens") if prompt_tokens is not None else tokenize(tok, [prompt])
+    neg = _as_tokens(negative_prompt_tokens, "negative_prompt_tokens") if negative_prompt_tokens is not None else tokenize(tok, [negative_prompt])
+    if pos[0].shape != neg[0].shape:
+        raise ValueError(f"positive and negative prompt tokens must have one length, got {tuple(pos[0].shape)} and {tuple(neg[0].shape)}")
+    ids, mask = torch.cat([pos[0], neg[0]], 0), torch.cat([pos[1], neg[1]], 0)
+    return gemma(ids, mask), mask
+
+
 def generate_video(model_repo: Optional[str] = None, text_encoder_repo: Optional[str] = None, prompt: str = "",
                    pipeline: PipelineType = PipelineType.DISTILLED, negative_prompt: str = DEFAULT_NEGATIVE_PROMPT,
                    height: int = 512, width: int = 512, num_frames: int = 33, num_inference_steps: int = 40,
@@ -216,7 +248,8 @@ def generate_video(model_repo: Optional[str] = None, text_encoder_repo: Optional
                    fp8_activations: bool = False, gemma_hidden_states=None, gemma_attention_mask: Optional[torch.Tensor] = None,
                    negative_gemma_hidden_states=None, negative_gemma_attention_mask: Optional[torch.Tensor] = None,
                    text_connector=None, guider: Optional[str] = None, apg_eta: float = 1.0,
-                   apg_norm_threshold: float = 0.0) -> np.ndarray:
+                   apg_norm_threshold: float = 0.0, gemma=None, gemma_repo: Optional[str] = None,
+                   tokenizer_path: Optional[str] = None, prompt_tokens=None, negative_prompt_tokens=None) -> np.ndarray:
     """See the module docstring.  Returns uint8 frames (F,H,W,3) (generate.py:4195-4197).
     ``hoist_context`` (not in the reference, off by default): the part of the forward that depends on the text context only -
     caption projection and the 48 cross-attention K / V^T projections, 3.37 TFLOP that the reference recomputes in every forward
@@ -236,6 +269,12 @@ def generate_video(model_repo: Optional[str] = None, text_encoder_repo: Optional
     the L hidden states of a Gemma-3 forward ((L,1,T,D) stack or list of L (1,T,D)) and its left-padded 0/1 mask (1,T); the
     feature extractor and the video embeddings connector run here (``text_connector=`` a ``TextConnector``, or loaded from
     ``model_repo``), positive and negative prompt as one B = 2 call.  ``prompt_embeds`` wins when both are given.
+    ``gemma`` (a ``gemma.GemmaEncoder``) or ``gemma_repo`` (a local Gemma-3 directory, --gemma-repo / --text-encoder-repo; a
+    ``text_encoder_repo`` that is an existing local directory counts as one): the text
+    route that starts at the prompt - tokens -> GemmaEncoder -> ``text_connector`` -> context, positive and negative prompt as one
+    B = 2 call.  Tokens are ``prompt_tokens`` / ``negative_prompt_tokens`` ((input_ids, attention_mask) pairs, left-padded), or made
+    from ``prompt`` / ``negative_prompt`` with the tokenizer.json of ``tokenizer_path`` or ``gemma_repo`` (truncated and left-padded to
+    1024; nothing is fetched).  ``prompt_embeds``, ``gemma_hidden_states`` and ``text_encoder`` keep their precedence over it, in that order.
     ``guider`` / ``apg_eta`` / ``apg_norm_threshold`` (--guider / --apg-eta / --apg-norm-threshold; not in the reference CLI, the
     guiders are ltx_core/components/guiders.py): what the CFG slot of every guided (denoise_dev) stage runs - "cfg" (None: the
     same), "cfg_star" or "apg" (DESIGN.md 5j).  A non-default guider on a run without a guided stage is a ValueError, as for STG."""
@@ -353,11 +392,17 @@ def generate_video(model_repo: Optional[str] = None, text_encoder_repo: Optional
     if prompt_embeds is None and gemma_hidden_states is not None:
         prompt_embeds, negative_prompt_embeds = _connect_gemma(gemma_hidden_states, gemma_attention_mask, negative_gemma_hidden_states,
                                                                negative_gemma_attention_mask, text_connector, model_repo, dev)
+    if gemma_repo is None and text_encoder_repo and Path(text_encoder_repo).is_dir():
+        gemma_repo = text_encoder_repo          # the reference's name for it; a repo NAME is not resolved (nothing is fetched)
+    if prompt_embeds is None and text_encoder is None and (gemma is not None or gemma_repo is not None):
+        hs, m = _encode_gemma(gemma, gemma_repo, tokenizer_path, prompt, negative_prompt, prompt_tokens, negative_prompt_tokens, dev)
+        prompt_embeds, negative_prompt_embeds = _connect_gemma(hs[:, 0:1], m[0:1], hs[:, 1:2], m[1:2], text_connector, model_repo, dev)
     if prompt_embeds is None:
         if text_encoder is None:
-            raise ValueError("prompt_embeds is required: the Gemma-3 text encoder is outside this package "
-                             "(SURVEY.md §2a #17); pass prompt_embeds=(1,1024,3840) or text_encoder=callable, or the hidden states "
-                             "of a Gemma-3 forward as gemma_hidden_states= / gemma_attention_mask=")
+            raise ValueError("prompt_embeds is required: pass prompt_embeds=(1,1024,3840) or text_encoder=callable, the hidden states "
+                             "of a Gemma-3 forward as gemma_hidden_states= / gemma_attention_mask=, or run Gemma-3 here: gemma= (a "
+                             "GemmaEncoder) or gemma_repo= (a local Gemma-3 directory, --gemma-repo) with prompt_tokens= / "
+                             "negative_prompt_tokens= or a tokenizer.json (tokenizer_path=, --tokenizer)")
         prompt_embeds = text_encoder(prompt)
         negative_prompt_embeds = text_encoder(negative_prompt)
     ctx_pos = prompt_embeds.to(dev).to(BF16)
@@ -590,6 +635,13 @@ def build_parser() -> argparse.ArgumentParser:
                     help="(not in the reference CLI) .pt/.safetensors file with `hidden_states` (L,T,D) or (L,1,T,D) - the hidden states of a "
                          "Gemma-3 forward - and `attention_mask` (T), left-padded; the feature extractor and the connector of --model-repo run here")
     ap.add_argument("--negative-gemma-hidden-states", type=str, default=None, help="the same for the negative prompt")
+    ap.add_argument("--gemma-repo", "--text-encoder-repo", dest="gemma_repo", type=str, default=None,
+                    help="local Gemma-3 directory (config.json + safetensors, optionally tokenizer.json): the text encoder runs here; "
+                         "--text-encoder-repo is the reference's spelling")
+    ap.add_argument("--tokenizer", type=str, default=None, help="(not in the reference CLI) local directory with a tokenizer.json (default: --gemma-repo)")
+    ap.add_argument("--prompt-tokens", type=str, default=None,
+                    help="(not in the reference CLI) .npz with `input_ids` and `attention_mask`, left-padded: the tokenised --prompt")
+    ap.add_argument("--negative-prompt-tokens", type=str, default=None, help="the same for the negative prompt")
     ap.add_argument("--synthetic", action="store_true", help="random-init weights + random text embeddings (no checkpoints offline)")
     ap.add_argument("--layers", type=int, default=48)
     # spatio-temporal guidance (the reference's spellings and defaults; it ignores them, this port runs them)
@@ -672,6 +724,14 @@ def load_gemma_hidden_states(path: str):
     return hs, mask
 
 
+def load_prompt_tokens(path: str):
+    """--prompt-tokens FILE: an .npz with `input_ids` and `attention_mask` ((T,) or (1,T)) -> ((1,T), (1,T)) int64 tensors."""
+    with np.load(path) as d:
+        if "input_ids" not in d or "attention_mask" not in d:
+            raise ValueError(f"{path}: expected `input_ids` and `attention_mask` arrays")
+        return _as_tokens((d["input_ids"].astype(np.int64), d["attention_mask"].astype(np.int64)), path)
+
+
 def main(argv: Optional[Sequence[str]] = None) -> None:
     args = resolve_cli_heuristics(build_parser().parse_args(argv))
     if args.fp8_activations and not args.enable_fp8:
@@ -695,8 +755,15 @@ def main(argv: Optional[Sequence[str]] = None) -> None:
             kw["transformer"] = LTXModel.random_init(LTXModelConfig(num_layers=args.layers), dev)
         kw["vae_decoder"] = LTX2VideoDecoder(random_decoder_weights(dev))
         g = torch.Generator(device=dev).manual_seed(43)
-        kw["prompt_embeds"] = torch.randn((1, 1024, 3840), generator=g, device=dev).to(BF16)
-        kw["negative_prompt_embeds"] = torch.randn((1, 1024, 3840), generator=g, device=dev).to(BF16)
+        if args.gemma_repo:       # the text route runs for real; only the connector's weights are random (Gemma width, its L + 1 states)
+            from .gemma import GemmaConfig
+            from .text_connector import TextConnector, random_connector_weights
+            gc = GemmaConfig.from_json(args.gemma_repo)
+            kw["text_connector"] = TextConnector(random_connector_weights(dev, D=gc.hidden_size, L=gc.num_hidden_layers + 1, layers=1,
+                                                                          generator_device=dev))
+        else:
+            kw["prompt_embeds"] = torch.randn((1, 1024, 3840), generator=g, device=dev).to(BF16)
+            kw["negative_prompt_embeds"] = torch.randn((1, 1024, 3840), generator=g, device=dev).to(BF16)
         if not is_dev:
             from .upsampler import LatentUpsampler
             from .weights import random_upsampler_weights
@@ -715,6 +782,12 @@ def main(argv: Optional[Sequence[str]] = None) -> None:
             kw["gemma_hidden_states"], kw["gemma_attention_mask"] = load_gemma_hidden_states(args.gemma_hidden_states)
         if args.negative_gemma_hidden_states:
             kw["negative_gemma_hidden_states"], kw["negative_gemma_attention_mask"] = load_gemma_hidden_states(args.negative_gemma_hidden_states)
+    if args.gemma_repo:
+        kw["gemma_repo"], kw["tokenizer_path"] = args.gemma_repo, args.tokenizer
+    if args.prompt_tokens:
+        kw["prompt_tokens"] = load_prompt_tokens(args.prompt_tokens)
+    if args.negative_prompt_tokens:
+        kw["negative_prompt_tokens"] = load_prompt_tokens(args.negative_prompt_tokens)
     generate_video(model_repo=args.model_repo, prompt=args.prompt, pipeline=PipelineType(args.pipeline),
                    negative_prompt=args.negative_prompt, height=args.height, width=args.width, num_frames=args.num_frames,
                    num_inference_steps=args.steps, cfg_scale=args.cfg_scale, seed=args.seed, fps=args.fps,

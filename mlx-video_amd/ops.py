@@ -11,7 +11,7 @@ from typing import Optional, Tuple
 import torch
 
 from . import _lib
-from ._lib import AttnArgs, GemmArgs, GemmGroupedArgs, GuiderArgs, StepArgs, check
+from ._lib import AttnArgs, CausalAttnArgs, GemmArgs, GemmGroupedArgs, GuiderArgs, StepArgs, check
 
 EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_SILU, EPI_BIAS_GATE_RES, EPI_BIAS_RES, EPI_SCALE_RES = 0, 1, 2, 3, 4, 5
 BF16 = torch.bfloat16
@@ -808,4 +808,121 @@ def connector_assemble(feat: Optional[torch.Tensor], registers: torch.Tensor, ro
     with _timed("connector_assemble", 0.0, 4.0 * B * T * D):
         check(_lib.load().ltxk_connector_assemble(_p(feat) if rows else None, ldf, _p(registers), _p(row0), _p(row_count), _p(out),
                                                   B, T, D, R, rows, _stream()), "ltxk_connector_assemble")
+    return out
+
+
+# ------------------------------------------------------------------- Gemma-3 text encoder (csrc/gemma_ops.hip, csrc/causal_attn.hip)
+GEMMA_HEAD_DIM = 256
+GEMMA_ROWS_PER_WG = 4        # rows (waves) per workgroup of ltxk_rmsnorm_weight_rows
+CAUSAL_ATTN_BQ = 64          # query rows per workgroup of ltxk_causal_attn
+CAUSAL_ATTN_BK = 64          # keys per tile
+
+
+def embed_rows(table: torch.Tensor, ids: torch.Tensor, scale: float, out: Optional[torch.Tensor] = None,
+               ids_host: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ltxk_embed_rows: out[m,:] = bf16(table[ids[m],:] * scale).  table (V,D) contiguous bf16, ids (M) int32 on the device.
+    The kernel cannot raise for device data, so the id range is validated here on ``ids_host``, the host copy the caller
+    tokenised (without one, ``ids`` is copied back once - a synchronisation, once per prompt)."""
+    _req(table, BF16, "embed_rows.table"); _req(ids, torch.int32, "embed_rows.ids")
+    if table.dim() != 2 or not table.is_contiguous():
+        raise ValueError(f"embed_rows: table must be a contiguous (V,D) matrix, got {tuple(table.shape)}")
+    if ids.dim() != 1 or not ids.is_contiguous():
+        raise ValueError(f"embed_rows: ids must be a contiguous (M,) vector, got {tuple(ids.shape)}")
+    V, D = table.shape
+    M = ids.shape[0]
+    host = ids.cpu() if ids_host is None else ids_host.reshape(-1)
+    if host.numel() != M:
+        raise ValueError(f"embed_rows: ids_host holds {host.numel()} ids, ids {M}")
+    if M and (int(host.min()) < 0 or int(host.max()) >= V):
+        raise ValueError(f"embed_rows: token ids must lie in [0, {V}), got [{int(host.min())}, {int(host.max())}]")
+    if out is None:
+        out = torch.empty((M, D), dtype=BF16, device=table.device)
+    _req(out, BF16, "embed_rows.out")
+    if tuple(out.shape) != (M, D) or out.stride(1) != 1:
+        raise ValueError(f"embed_rows: out must be ({M},{D}) with unit inner stride, got {tuple(out.shape)}")
+    with _timed("embed_rows", 0.0, 4.0 * M * D):
+        check(_lib.load().ltxk_embed_rows(_p(table), V, D, _p(ids), _p(out), out.stride(0), M, scale, _stream()), "ltxk_embed_rows")
+    return out
+
+
+def rmsnorm_weight_rows(x: torch.Tensor, weight: torch.Tensor, eps: float = 1e-6, resid: Optional[torch.Tensor] = None,
+                        out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ltxk_rmsnorm_weight_rows: Gemma RMSNorm, y = bf16(x * rsqrt(mean(x^2) + eps) * (1 + weight)); with ``resid``
+    y = bf16(resid + that).  x (M,D), any D % 8 == 0 up to 8192, row strides may exceed D; ``out`` may be ``resid`` or ``x``."""
+    _req(x, BF16, "rmsnorm_weight_rows.x"); _req(weight, BF16, "rmsnorm_weight_rows.weight")
+    if x.dim() != 2 or x.stride(1) != 1:
+        raise ValueError(f"rmsnorm_weight_rows: expected an (M,D) matrix with unit inner stride, got {tuple(x.shape)}")
+    M, D = x.shape
+    if tuple(weight.shape) != (D,) or not weight.is_contiguous():
+        raise ValueError(f"rmsnorm_weight_rows: weight must be a contiguous ({D},) vector, got {tuple(weight.shape)}")
+    if resid is not None:
+        _req(resid, BF16, "rmsnorm_weight_rows.resid")
+        if tuple(resid.shape) != (M, D) or resid.stride(1) != 1:
+            raise ValueError(f"rmsnorm_weight_rows: resid must be ({M},{D}) with unit inner stride, got {tuple(resid.shape)}")
+    if out is None:
+        out = torch.empty((M, D), dtype=BF16, device=x.device)
+    _req(out, BF16, "rmsnorm_weight_rows.out")
+    if tuple(out.shape) != (M, D) or out.stride(1) != 1:
+        raise ValueError(f"rmsnorm_weight_rows: out must be ({M},{D}) with unit inner stride, got {tuple(out.shape)}")
+    with _timed("rmsnorm_weight_rows", 0.0, (4.0 if resid is None else 6.0) * M * D):
+        check(_lib.load().ltxk_rmsnorm_weight_rows(_p(x), x.stride(0), _p(weight), _p(resid), resid.stride(0) if resid is not None else 0,
+                                                   _p(out), out.stride(0), M, D, eps, _stream()), "ltxk_rmsnorm_weight_rows")
+    return out
+
+
+def headnorm_rope(buf: torch.Tensor, Hq: int, Hkv: int, q_weight: torch.Tensor, k_weight: torch.Tensor, cos: torch.Tensor,
+                  sin: torch.Tensor, T: int, eps: float = 1e-6) -> torch.Tensor:
+    """ltxk_headnorm_rope: in place on columns [0, (Hq+Hkv)*256) of buf (M, ld): per 256-wide head Gemma RMSNorm with
+    q_weight / k_weight (256,), then rotate-half RoPE with cos / sin (T,128) fp32, row m at position m % T."""
+    _req(buf, BF16, "headnorm_rope.buf"); _req(q_weight, BF16, "headnorm_rope.q_weight"); _req(k_weight, BF16, "headnorm_rope.k_weight")
+    _req(cos, torch.float32, "headnorm_rope.cos"); _req(sin, torch.float32, "headnorm_rope.sin")
+    cols = (Hq + Hkv) * GEMMA_HEAD_DIM
+    if Hq < 1 or Hkv < 1 or buf.dim() != 2 or buf.stride(1) != 1 or buf.shape[1] < cols:
+        raise ValueError(f"headnorm_rope: buf must be (M, >= {cols}) with unit inner stride, got {tuple(buf.shape)}")
+    for w in (q_weight, k_weight):
+        if tuple(w.shape) != (GEMMA_HEAD_DIM,) or not w.is_contiguous():
+            raise ValueError(f"headnorm_rope: q_weight / k_weight must be contiguous ({GEMMA_HEAD_DIM},) vectors, got {tuple(w.shape)}")
+    if tuple(cos.shape) != (T, GEMMA_HEAD_DIM // 2) or tuple(sin.shape) != tuple(cos.shape) or not cos.is_contiguous() or not sin.is_contiguous():
+        raise ValueError(f"headnorm_rope: cos / sin must be contiguous ({T},{GEMMA_HEAD_DIM // 2}) tables, got {tuple(cos.shape)}")
+    with _timed("headnorm_rope", 0.0, 4.0 * buf.shape[0] * cols):
+        check(_lib.load().ltxk_headnorm_rope(_p(buf), buf.stride(0), buf.shape[0], Hq, Hkv, _p(q_weight), _p(k_weight), _p(cos), _p(sin),
+                                             T, eps, _stream()), "ltxk_headnorm_rope")
+    return buf
+
+
+def geglu_tanh_(gu: torch.Tensor) -> torch.Tensor:
+    """ltxk_geglu_tanh in place: gu = [g | u] (M, 2F) -> its first F columns become bf16(bf16(gelu_tanh(g)) * u); returns that
+    (M,F) view (row stride 2F: ``gemm`` takes it as ``a``)."""
+    _req(gu, BF16, "geglu_tanh_.gu")
+    if gu.dim() != 2 or gu.stride(1) != 1 or gu.shape[1] % 16:
+        raise ValueError(f"geglu_tanh_: gu must be (M, 2F) with unit inner stride and F a multiple of 8, got {tuple(gu.shape)}")
+    M, F = gu.shape[0], gu.shape[1] // 2
+    with _timed("geglu_tanh", 0.0, 6.0 * M * F):
+        check(_lib.load().ltxk_geglu_tanh(_p(gu), gu.stride(0), _p(gu), gu.stride(0), M, F, _stream()), "ltxk_geglu_tanh")
+    return gu[:, :F]
+
+
+def causal_attn(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, out: torch.Tensor, row_start: torch.Tensor, B: int, Hq: int,
+                Hkv: int, T: int, scale: float, window: int = 0) -> torch.Tensor:
+    """ltxk_causal_attn (head dim 256): q (B*T, >= Hq*256) view, k (B*T, >= Hkv*256) view, vt (B, Hkv*256, ldvt >= T),
+    out (B*T, Hq*256) view, row_start (B) int32 on the device (valid tokens of batch row b: [row_start[b], T)).  Key j is
+    visible to query i iff row_start <= j <= i and (window == 0 or i - j < window); rows below row_start come out zero."""
+    for t, name in ((q, "q"), (k, "k"), (vt, "vt"), (out, "out")):
+        _req(t, BF16, f"causal_attn.{name}")
+    _req(row_start, torch.int32, "causal_attn.row_start")
+    if tuple(row_start.shape) != (B,) or not row_start.is_contiguous():
+        raise ValueError(f"causal_attn: row_start must be a contiguous ({B},) vector, got {tuple(row_start.shape)}")
+    for t, name, h in ((q, "q", Hq), (k, "k", Hkv), (out, "out", Hq)):
+        if t.dim() != 2 or t.stride(1) != 1 or t.shape[0] != B * T or t.shape[1] < h * GEMMA_HEAD_DIM:
+            raise ValueError(f"causal_attn: {name} must be ({B * T}, >= {h * GEMMA_HEAD_DIM}) with unit inner stride, got {tuple(t.shape)}")
+    if vt.dim() != 3 or vt.stride(2) != 1 or vt.shape[0] != B or vt.shape[1] != Hkv * GEMMA_HEAD_DIM or vt.shape[2] < T or \
+            vt.stride(0) != vt.shape[1] * vt.stride(1):
+        raise ValueError(f"causal_attn: vt must be ({B},{Hkv * GEMMA_HEAD_DIM}, >= {T}) with dense batch stride, got {tuple(vt.shape)} "
+                         f"strides {vt.stride()}")
+    a = CausalAttnArgs()
+    a.q, a.k, a.vt, a.out, a.row_start = _p(q), _p(k), _p(vt), _p(out), _p(row_start)
+    a.ldq, a.ldk, a.ldvt, a.ldo = q.stride(0), k.stride(0), vt.stride(1), out.stride(0)
+    a.B, a.Hq, a.Hkv, a.T, a.window, a.scale = B, Hq, Hkv, T, window, scale
+    with _timed("causal_attn", 2.0 * B * Hq * T * T * GEMMA_HEAD_DIM, 2.0 * B * T * GEMMA_HEAD_DIM * (2 * Hq + 2 * Hkv)):
+        check(_lib.load().ltxk_causal_attn(ctypes.byref(a), _stream()), "ltxk_causal_attn")
     return out

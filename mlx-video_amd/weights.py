@@ -341,6 +341,69 @@ def text_connector_weights(files: Iterable[Path], device) -> Dict[str, torch.Ten
     return out
 
 
+# ------------------------------------------------------------------------------------------------ Gemma-3 text encoder
+_GEMMA_PREFIXES = ("model.language_model.", "language_model.model.", "language_model.")     # longest match first
+_GEMMA_SKIP = ("vision_tower.", "vision_model.", "multi_modal_projector.", "model.vision_tower.", "model.multi_modal_projector.")
+
+
+def gemma_shard_files(root: Path) -> list:
+    """The one shard set of a local Gemma-3 directory the reference would read (text_encoder.py:200-216): an indexed
+    diffusion_pytorch_model-* set, else an indexed model-* set, else the single file of either name, else every *.safetensors."""
+    root = Path(root)
+    if (root / "diffusion_pytorch_model.safetensors.index.json").exists():
+        files = sorted(root.glob("diffusion_pytorch_model-*.safetensors"))
+    elif (root / "model.safetensors.index.json").exists():
+        files = sorted(root.glob("model-*.safetensors"))
+    elif (root / "diffusion_pytorch_model.safetensors").exists():
+        files = [root / "diffusion_pytorch_model.safetensors"]
+    elif (root / "model.safetensors").exists():
+        files = [root / "model.safetensors"]
+    else:
+        files = sorted(root.glob("*.safetensors"))
+    return files or sorted(root.glob("*.safetensors"))
+
+
+def gemma_key(raw_key: str) -> Optional[str]:
+    """The language model's own key (``embed_tokens.weight``, ``layers.{i}...``, ``norm.weight``) of a checkpoint key, None for
+    what the encoder does not use (vision tower, projector, lm_head)."""
+    k = raw_key
+    if any(k.startswith(p) or ("." + p) in k for p in _GEMMA_SKIP):
+        return None
+    for p in _GEMMA_PREFIXES:
+        if k.startswith(p):
+            k = k[len(p):]
+            break
+    if k.startswith("model."):
+        k = k[len("model."):]
+    if k.startswith(("embed_tokens.", "layers.", "norm.")):
+        return k
+    return None
+
+
+def gemma_weights(root, device) -> Dict[str, torch.Tensor]:
+    """The Gemma-3 language model of a local directory as device bf16 tensors under its own keys, for ``gemma.GemmaEncoder``.
+    Streams the shards of ``gemma_shard_files`` one tensor at a time; fp32 tensors are cast to bf16 (text_encoder.py:154-163),
+    vision-tower keys skipped.  A pre-quantised checkpoint (.scales / .biases) raises, as the DiT loader does."""
+    root = Path(root)
+    if not root.is_dir():
+        raise FileNotFoundError(f"{root} is not a local directory (repo names are not resolved and nothing is fetched)")
+    files = gemma_shard_files(root)
+    if not files:
+        raise FileNotFoundError(f"no *.safetensors in {root}")
+    for f in files:
+        if any(k.endswith((".scales", ".biases")) for k in scan_header(f)):
+            raise ValueError(f"{f.name}: pre-quantised MLX checkpoints (.scales/.biases) are not supported: MLX affine quantisation is "
+                             "out of scope; use the bf16 Gemma-3 weights")
+    out: Dict[str, torch.Tensor] = {}
+    for k, v in iter_safetensors(files, want=lambda k: gemma_key(k) is not None):
+        if not v.dtype.is_floating_point:
+            raise ValueError(f"{k}: expected a floating-point tensor, got {v.dtype}")
+        out[gemma_key(k)] = _to_dev(v, device)
+    if "embed_tokens.weight" not in out:
+        raise ValueError(f"no language-model tensors (…embed_tokens.weight) in {', '.join(f.name for f in files)}")
+    return out
+
+
 def infer_encoder_blocks(keys: Iterable[str]):
     """Encoder block list from the checkpoint's key set: `down_blocks.i.res_blocks.j.*` => ("res_x", n); a bare
     `down_blocks.i.conv.*` is a compress block whose stride follows the default schedule of encoder.py:95-105."""
