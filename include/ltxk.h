@@ -483,13 +483,15 @@ int ltxk_layer_norm_compact(const void* x, int64_t layer_stride, int64_t batch_s
                             void* stream);
 
 /* rms_norm with unit weight (utils.py:398-400) for rows of any width D % 8 == 0, D <= 8192: y = bf16(x * rsqrt(mean(x^2) + eps)),
- * one pass with the row in registers.  x (M,D) row stride ldx, y (M,D) row stride ldy (y may be x).                  */
+ * one pass with the row in registers.  x (M,D) row stride ldx, y (M,D) row stride ldy (y may be x).  One kernel body
+ * with ltxk_rmsnorm_weight_rows: the bits of that entry point with a zero weight and no residual.                          */
 int ltxk_rmsnorm_rows(const void* x, int32_t ldx, void* y, int32_t ldy, int32_t M, int32_t D, float eps, void* stream);
 
 /* ltxk_qknorm_rope for any head count: in place on the q | k halves (columns [0,D) and [D,2D)) of buf (M, ld >= 2D):
  * RMSNorm over the full D with weight row 0 / 1 of `weight` (2,D) bf16, then the SPLIT rotation over each 128-wide head
  * with cos/sin (H,T,64) fp32, row m at position m % T (text_encoder.py:308-363).  D == 128*H, 1 <= H <= 64; the kernel
- * reduces the row itself.  Rounding points are those of ltxk_qknorm_rope.  Columns past 2D are not touched.            */
+ * reduces the row itself.  One kernel with ltxk_qknorm_rope (nseg = 2): the same bits where both take H.  Columns past 2D
+ * are not touched.                                                                                                     */
 int ltxk_qknorm_rope_1d(void* buf, int32_t ld, int32_t M, int32_t D, const void* weight, const float* cos,
                         const float* sin, int32_t T, int32_t H, float eps, void* stream);
 

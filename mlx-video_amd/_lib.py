@@ -187,7 +187,7 @@ SIGNATURES = {
                                               c_void_p]),
     "ltxk_cfg_euler_step": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32,
                                       c_int32, c_float, c_float, c_float, c_int32, c_void_p]),
-    # text stage (csrc/text_ops.hip)
+    # text stage (csrc/text_ops.hip; ltxk_qknorm_rope_1d: csrc/elementwise.hip)
     "ltxk_masked_layer_stats": (c_int32, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int32, c_int32, c_int32,
                                           c_int32, c_void_p, c_void_p, c_void_p]),
     "ltxk_layer_norm_compact": (c_int32, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
@@ -198,7 +198,7 @@ SIGNATURES = {
     "ltxk_gelu_erf": (c_int32, [c_void_p, c_int64, c_void_p]),
     "ltxk_connector_assemble": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32,
                                           c_int32, c_int32, c_void_p]),
-    # Gemma-3 text encoder (csrc/gemma_ops.hip, csrc/causal_attn.hip)
+    # Gemma-3 text encoder (csrc/text_ops.hip, csrc/causal_attn.hip)
     "ltxk_embed_rows": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_float, c_void_p]),
     "ltxk_rmsnorm_weight_rows": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_int32,
                                            c_float, c_void_p]),

@@ -53,9 +53,9 @@ struct FaParams {
   float eps;
 };
 
-// RMSNorm * weight (+ SPLIT RoPE) of one wave's Q fragments, same op order and rounding points as qknorm_rope_kernel
-// (elementwise.hip): x = bf16(q * rstd * w); o1 = bf16(x1*c - s*x2), o2 = bf16(x2*c + s*x1) with x2 = x1's partner 64
-// channels up, which is fragment ks+4 of the same lane.
+// RMSNorm * weight (+ SPLIT RoPE) of one wave's Q fragments.  The loop below restates norm_rope of rows.h, the definition the
+// row kernels call (this prologue keeps its own copy: its instruction stream is the measured one): x = bf16(q * rstd * w);
+// o1 = bf16(x1*c - s*x2), o2 = bf16(x2*c + s*x1) with x2 = x1's partner 64 channels up, which is fragment ks+4 of the same lane.
 __device__ __forceinline__ void fa_prep_q(const FaParams& p, bf16x8 (&qf)[8], int b, int h, int qrow, int hh) {
   const int half = p.q_ss_n >> 1;
   const float* sp = p.q_ss + (size_t)(b * p.Tq + qrow) * p.q_ss_ld + hh * half;
@@ -448,8 +448,8 @@ __device__ __forceinline__ constexpr int fa16_keymap(int kb, int r) { return 32 
 __device__ __forceinline__ int fa16_kswz(int row) { return 4 * ((row >> 3) & 3) + (row & 3); }
 
 // RMSNorm * weight (+ SPLIT RoPE) of the wave's Q fragments in the 16x16x32 operand map: fragment (qb, ks) of lane (c,g)
-// holds channels 32ks + 8g + j; the rotation partner 64 channels up is fragment ks + 2 of the same lane.  Same op order
-// and rounding points as fa_prep_q / qknorm_rope_kernel.
+// holds channels 32ks + 8g + j; the rotation partner 64 channels up is fragment ks + 2 of the same lane.  Like fa_prep_q
+// it restates norm_rope of rows.h.
 template <int QB>
 __device__ __forceinline__ void fa16_prep_q(const FaParams& p, bf16x8 (&qf)[QB][4], int b, int h, int q0, int c, int g) {
   const int half = p.q_ss_n >> 1;

@@ -2,6 +2,7 @@
 // 8- or 16-byte vectors; row reductions are wave64 shuffles (one wave per row); every bf16
 // rounding point of the reference's op chain is reproduced.
 #include "common.h"
+#include "rows.h"
 #include <math.h>
 #include <stdlib.h>
 
@@ -143,11 +144,15 @@ __global__ __launch_bounds__(256) void norm_scale_kernel(
 }
 
 // ---------------------------------------------------------------------------------------
-// q/k RMSNorm (full inner dim, learned weight) + SPLIT RoPE, in place.
-// One wave per (row, segment).  Lane map: a wave pass covers 8 heads; 8 lanes per head; lane holds
-// x1 = [j0, j0+8) of the head's first half and x2 = the same offsets of the second half (the rotation
-// partners), so every access is a 16-byte vector and each 8-lane group touches whole 128-byte lines.
+// q/k RMSNorm (full inner dim, learned weight) + SPLIT RoPE, in place; values and rounding points: rows.h.
+// One wave per (row, segment), the segment held in registers.  Lane map: a wave pass covers 8 heads; 8 lanes per head;
+// lane holds x1 = [j0, j0+8) of the head's first half and x2 = the same offsets of the second half (the rotation
+// partners), so every access is a 16-byte vector and each 8-lane group touches whole 128-byte lines.  Lanes past the
+// last head idle, so any H <= 8 * MAXP is served: MAXP = 4 is the DiT's instance (ltxk_qknorm_rope), MAXP = 8 takes
+// the text connector's H in 33..64 (ltxk_qknorm_rope_1d).  ROPE (= tables given) is a compile-time flag: the chain's
+// rotation test folds away, which leaves each pass one straight run of {6 loads, counted waits, arithmetic, 2 stores}.
 // ---------------------------------------------------------------------------------------
+template <int MAXP, bool ROPE>
 __global__ __launch_bounds__(256) void qknorm_rope_kernel(
     bf16* __restrict__ buf, int ld, int M, int nseg, int D, const bf16* __restrict__ weight,
     const float* __restrict__ cosb, const float* __restrict__ sinb, int T, int H, float eps) {
@@ -156,10 +161,9 @@ __global__ __launch_bounds__(256) void qknorm_rope_kernel(
   if (item >= M * nseg) return;
   const int row = item / nseg, sgi = item - row * nseg;
   const int t = row % T;
-  const int npass = (H + 7) >> 3;    // 8 heads per pass (lanes past the last head idle), dh = 128
+  const int npass = (H + 7) >> 3;    // 8 heads per pass, dh = 128
   const int hl = lane >> 3;          // head within pass
   const int j0 = (lane & 7) * 8;     // offset within the 64-wide half
-  constexpr int MAXP = 4;            // H <= 32
   bf16* xr = buf + (size_t)row * ld + (size_t)sgi * D;
   const bf16* wr = weight + (size_t)sgi * D;
   bf16x8 a[MAXP], b[MAXP];
@@ -183,26 +187,10 @@ __global__ __launch_bounds__(256) void qknorm_rope_kernel(
       const int base = (ps * 8 + hl) * 128 + j0;
       const bf16x8 wa = *(const bf16x8*)(wr + base);
       const bf16x8 wb = *(const bf16x8*)(wr + base + 64);
-      f32x4 c0, c1, s0, s1;
-      if (cosb) {
-        const size_t off = ((size_t)(ps * 8 + hl) * T + t) * 64 + j0;
-        c0 = *(const f32x4*)(cosb + off); c1 = *(const f32x4*)(cosb + off + 4);
-        s0 = *(const f32x4*)(sinb + off); s1 = *(const f32x4*)(sinb + off + 4);
-      }
+      RopeTab tab = {};
+      if constexpr (ROPE) tab = rope_load(cosb, sinb, ((size_t)(ps * 8 + hl) * T + t) * 64 + j0);
       bf16x8 oa, ob;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const float x1 = rbf((float)a[ps][j] * rstd * (float)wa[j]);
-        const float x2 = rbf((float)b[ps][j] * rstd * (float)wb[j]);
-        if (cosb) {
-          const float c = j < 4 ? c0[j & 3] : c1[j & 3], sn = j < 4 ? s0[j & 3] : s1[j & 3];
-          oa[j] = (bf16)(x1 * c - sn * x2);
-          ob[j] = (bf16)(x2 * c + sn * x1);
-        } else {
-          oa[j] = (bf16)x1;
-          ob[j] = (bf16)x2;
-        }
-      }
+      norm_rope(a[ps], b[ps], rstd, wa, wb, ROPE, tab, oa, ob);
       *(bf16x8*)(xr + base) = oa;
       *(bf16x8*)(xr + base + 64) = ob;
     }
@@ -241,32 +229,16 @@ __global__ __launch_bounds__(256) void qknorm_rope_ss_kernel(
   for (int i = lane; i < NP; i += 64) ss += sumsq[(size_t)row * ss_ld + sgi * NP + i];
   // weights and the rotation table are requested before the reduction (they do not depend on it)
   bf16x8 wa, wb;
-  f32x4 c0, c1, s0, s1;
+  RopeTab tab;
   if (act) {
     wa = *(const bf16x8*)(wr + base);
     wb = *(const bf16x8*)(wr + base + 64);
-    if (cosb) {
-      const size_t off = ((size_t)head * T + t) * 64 + j0;
-      c0 = *(const f32x4*)(cosb + off); c1 = *(const f32x4*)(cosb + off + 4);
-      s0 = *(const f32x4*)(sinb + off); s1 = *(const f32x4*)(sinb + off + 4);
-    }
+    if (cosb) tab = rope_load(cosb, sinb, ((size_t)head * T + t) * 64 + j0);
   }
   const float rstd = rsqrtf(wave_sum(ss) / (float)D + eps);
   if (!act) return;
   bf16x8 oa, ob;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const float x1 = rbf((float)a[j] * rstd * (float)wa[j]);
-    const float x2 = rbf((float)b[j] * rstd * (float)wb[j]);
-    if (cosb) {
-      const float c = j < 4 ? c0[j & 3] : c1[j & 3], sn = j < 4 ? s0[j & 3] : s1[j & 3];
-      oa[j] = (bf16)(x1 * c - sn * x2);
-      ob[j] = (bf16)(x2 * c + sn * x1);
-    } else {
-      oa[j] = (bf16)x1;
-      ob[j] = (bf16)x2;
-    }
-  }
+  norm_rope(a, b, rstd, wa, wb, cosb != nullptr, tab, oa, ob);
   *(bf16x8*)(xr + base) = oa;
   *(bf16x8*)(xr + base + 64) = ob;
 }
@@ -627,9 +599,29 @@ extern "C" int ltxk_qknorm_rope(void* buf, int32_t ld, int32_t M, int32_t nseg, 
   LTXK_CHECK_ARG((cos == nullptr) == (sin == nullptr), "ltxk_qknorm_rope: cos and sin must both be set or both NULL");
   LTXK_CHECK_ARG(T > 0, "ltxk_qknorm_rope: T must be > 0");
   const dim3 grid((M * nseg + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK);
-  hipLaunchKernelGGL(qknorm_rope_kernel, grid, dim3(256), 0, (hipStream_t)stream, (bf16*)buf, ld, M, nseg, D,
-                     (const bf16*)weight, cos, sin, T, H, eps);
+  if (cos)
+    hipLaunchKernelGGL((qknorm_rope_kernel<4, true>), grid, dim3(256), 0, (hipStream_t)stream, (bf16*)buf, ld, M, nseg, D, (const bf16*)weight, cos, sin, T, H, eps);
+  else
+    hipLaunchKernelGGL((qknorm_rope_kernel<4, false>), grid, dim3(256), 0, (hipStream_t)stream, (bf16*)buf, ld, M, nseg, D, (const bf16*)weight, cos, sin, T, H, eps);
   LTXK_CHECK_LAUNCH("ltxk_qknorm_rope");
+  return LTXK_OK;
+}
+
+// the text connector's entry to the same kernel: q|k of one row side by side (nseg = 2), any 1 <= H <= 64, tables required
+extern "C" int ltxk_qknorm_rope_1d(void* buf, int32_t ld, int32_t M, int32_t D, const void* weight, const float* cos,
+                                   const float* sin, int32_t T, int32_t H, float eps, void* stream) {
+  LTXK_CHECK_ARG(buf && weight && cos && sin && M > 0 && T > 0, "ltxk_qknorm_rope_1d: bad arguments");
+  LTXK_CHECK_ARG(H >= 1 && H <= 64 && D == 128 * H, "ltxk_qknorm_rope_1d: D=%d must be 128*H, 1 <= H=%d <= %d", D, H, 64);
+  LTXK_CHECK_ARG(ld >= 2 * D && ld % 8 == 0 && ((uintptr_t)buf & 15) == 0 && ((uintptr_t)weight & 15) == 0 && ((uintptr_t)cos & 15) == 0 &&
+                     ((uintptr_t)sin & 15) == 0,
+                 "ltxk_qknorm_rope_1d: ld=%d must be >= 2*D and a multiple of 8, pointers 16-byte aligned", ld);
+  LTXK_CHECK_ARG((int64_t)M * 2 <= (int64_t)INT32_MAX, "ltxk_qknorm_rope_1d: too many rows");
+  const dim3 grid((2 * M + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK);
+  if (H <= 32)
+    hipLaunchKernelGGL((qknorm_rope_kernel<4, true>), grid, dim3(256), 0, (hipStream_t)stream, (bf16*)buf, ld, M, 2, D, (const bf16*)weight, cos, sin, T, H, eps);
+  else
+    hipLaunchKernelGGL((qknorm_rope_kernel<8, true>), grid, dim3(256), 0, (hipStream_t)stream, (bf16*)buf, ld, M, 2, D, (const bf16*)weight, cos, sin, T, H, eps);
+  LTXK_CHECK_LAUNCH("ltxk_qknorm_rope_1d");
   return LTXK_OK;
 }
 

@@ -689,7 +689,7 @@ def resize_area(x: torch.Tensor, oh: int, ow: int) -> torch.Tensor:
     return out
 
 
-# ------------------------------------------------------------------------------------------- text stage (csrc/text_ops.hip)
+# ------------------------------------------------------------------------------------------- text stage (csrc/text_ops.hip, csrc/elementwise.hip)
 STATS_PARTIALS = 64          # workgroups per (batch row, layer) of ltxk_masked_layer_stats' first stage
 STATS_THREADS = 256          # threads of one of them; a thread keeps 8 running sums
 
@@ -811,7 +811,7 @@ def connector_assemble(feat: Optional[torch.Tensor], registers: torch.Tensor, ro
     return out
 
 
-# ------------------------------------------------------------------- Gemma-3 text encoder (csrc/gemma_ops.hip, csrc/causal_attn.hip)
+# ------------------------------------------------------------------- Gemma-3 text encoder (csrc/text_ops.hip, csrc/causal_attn.hip)
 GEMMA_HEAD_DIM = 256
 GEMMA_ROWS_PER_WG = 4        # rows (waves) per workgroup of ltxk_rmsnorm_weight_rows
 CAUSAL_ATTN_BQ = 64          # query rows per workgroup of ltxk_causal_attn

@@ -1,4 +1,4 @@
-"""Float64 restatements for the Gemma-3 text encoder (mlx_video_amd/gemma.py, csrc/gemma_ops.hip, csrc/causal_attn.hip).
+"""Float64 restatements for the Gemma-3 text encoder (mlx_video_amd/gemma.py, csrc/text_ops.hip, csrc/causal_attn.hip).
 
 * ``forward``: the whole model in torch with a dtype policy - "f64" rounds nothing, "bf16" rounds to bf16 at the rounding
   points include/ltxk.h states and nowhere else (sums in float64 where the kernels sum in fp32).  The architecture is

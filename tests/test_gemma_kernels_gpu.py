@@ -1,4 +1,4 @@
-"""The kernels of the Gemma-3 text encoder (csrc/gemma_ops.hip, csrc/causal_attn.hip) through mlx_video_amd.ops, each held
+"""The kernels of the Gemma-3 text encoder (csrc/text_ops.hip, csrc/causal_attn.hip) through mlx_video_amd.ops, each held
 element by element to its float64 value.  Every bound is written out from the arithmetic the header states, with u = 2^-24
 (one fp32 rounding), ulp_bf16(v) = 2^(floor(log2 |v|) - 7) and a chain of k fp32 additions of positive terms off by at most
 k*u relative; nothing in them is a measured tolerance.  Outputs sit inside sentinel (NaN) borders that must survive, inputs

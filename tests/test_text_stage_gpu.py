@@ -1,4 +1,4 @@
-"""The text stage on the GPU: the kernels of csrc/text_ops.hip one by one against float64 on the same inputs, then
+"""The text stage on the GPU: its kernels (csrc/text_ops.hip; q/k norm + RoPE: csrc/elementwise.hip) one by one against float64 on the same inputs, then
 text_connector.TextConnector as a whole against tests/ref_text.py, then generate_video through the Gemma-hidden-state route.
 
 Bounds are written out from the arithmetic, with u = 2^-24 (fp32 unit roundoff) and 2^-8 (bf16 unit roundoff: 8 significant
@@ -189,10 +189,13 @@ def test_gelu_erf_all_bf16_patterns(dev):
     parity.check("text.gelu_erf.inputs_not_correctly_rounded", float((d > 0).sum()), 65536.0, note="recorded, not gated")
 
 
-ROW_CASES = [(3840, 30, 70), (384, 3, 37)]
+# (D, H, M).  H = 33 is the first head count past the 4-pass instance of the q/k kernel (pass 4 holds 8 live items; D = 4224 is
+# no multiple of 512); H = 64 fills all 8 passes and D = 8192 is the widest row ltxk_rmsnorm_rows takes.
+ROW_CASES = [(3840, 30, 70), (384, 3, 37), (4224, 33, 5), (8192, 64, 3)]
+ROW_IDS = ["3840x70", "384x37", "4224x5", "8192x3"]
 
 
-@pytest.mark.parametrize("D,H,M", ROW_CASES, ids=["3840x70", "384x37"])
+@pytest.mark.parametrize("D,H,M", ROW_CASES, ids=ROW_IDS)
 def test_rmsnorm_rows(dev, D, H, M):
     """y = x / sqrt(mean(x^2) + eps) in float64.  The kernel: squares of bf16 values are exact in fp32; their sum passes a term
     through k = 8 ceil(D/512) + 6 additions (relative error g(k), all terms positive), then / D, + eps and v_rsq_f32 (1 ulp =
@@ -219,14 +222,15 @@ def test_rmsnorm_rows(dev, D, H, M):
     assert torch.equal(same, yb[:M, :D])
 
 
-@pytest.mark.parametrize("D,H,M", ROW_CASES, ids=["3840x70", "384x37"])
+@pytest.mark.parametrize("D,H,M", ROW_CASES, ids=ROW_IDS)
 def test_qknorm_rope_1d(dev, D, H, M):
     """In float64 on the same inputs and tables: n = x w / sqrt(mean(x^2) + eps) per segment, o1 = n1 c - n2 s, o2 = n2 c + n1 s.
     The kernel rounds the normalised value to bf16 first (the reference's q_norm returns a bf16 array): n^ = n (1 + rho'),
     |rho'| <= rho = 2^-8 + (1 + 2^-8)(g(k)/2 + 5u) with k = 16 ceil(8H/64) + 6 additions in the sum of squares and two
     multiplications; the rotation in fp32 adds u per product and u for the subtraction, all against mag = |n1 c| + |n2 s|; then
     one rounding to bf16:  |out - o| <= 2^-8 |o| + (1 + 2^-8)(rho + 3u (1 + rho)) mag.
-    Neither head count is a multiple of 4; T = 32 < M, so positions wrap; rows past M and columns past 2D stay."""
+    Head counts 30, 3 and 33 are no multiple of 4, 33 and 64 take the 8-pass instance of the kernel; where T = 32 < M positions
+    wrap; rows past M and columns past 2D stay."""
     from mlx_video_amd import ops
     from mlx_video_amd.text_connector import rope_table_1d
     T = 32
@@ -255,6 +259,48 @@ def test_qknorm_rope_1d(dev, D, H, M):
     err = (got - o).abs()
     assert bool((err[bound == 0] == 0).all())
     parity.auto(float((err / bound.clamp_min(1e-300)).max()), 1.0, tag="err_over_bound")
+
+
+@pytest.mark.parametrize("M,D", [(5, 8), (5, 264), (3, 3840), (2, 8192)])
+def test_rmsnorm_entry_points_share_bits(dev, M, D):
+    """ltxk_rmsnorm_rows and ltxk_rmsnorm_weight_rows launch the two instances of one kernel body: with a zero weight 1 + 0 and the multiplication by 1.0f
+    are exact, so the two give the same bits.  Strided views inside sentinel borders, which stay."""
+    from mlx_video_amd import ops
+    g = torch.Generator().manual_seed(7 * D + M)
+    x = (torch.randn(M, D, generator=g) * torch.logspace(-2, 2, M).reshape(M, 1)).to(BF)
+    xb = _sent_bf16((M + 2, D + 8), dev)
+    xb[:M, :D] = x.to(dev)
+    ya, yb = _sent_bf16((M + 2, D + 16), dev), _sent_bf16((M + 2, D + 16), dev)
+    ops.rmsnorm_rows(xb[:M, :D], 1e-6, out=ya[:M, :D])
+    ops.rmsnorm_weight_rows(xb[:M, :D], torch.zeros(D, dtype=BF, device=dev), 1e-6, out=yb[:M, :D])
+    torch.cuda.synchronize()
+    for y in (ya, yb):
+        assert _untouched(y[M:]) and _untouched(y[:, D:])
+    assert not bool(torch.isnan(ya[:M, :D]).any())
+    assert torch.equal(ya[:M, :D].view(torch.int16), yb[:M, :D].view(torch.int16))
+
+
+@pytest.mark.parametrize("H", [4, 12, 32])
+def test_qknorm_entry_points_share_bits(dev, H):
+    """ltxk_qknorm_rope_1d and ltxk_qknorm_rope at nseg = 2 launch one kernel: the same bits on the head counts both take.
+    M = 5 rows at T = 3 positions, so positions wrap; rows past M and columns past 2D stay."""
+    from mlx_video_amd import ops
+    from mlx_video_amd.text_connector import rope_table_1d
+    M, T, D = 5, 3, 128 * H
+    g = torch.Generator().manual_seed(H)
+    x = (torch.randn(M, 2 * D, generator=g) * torch.logspace(-1, 1, M).reshape(M, 1)).to(BF)
+    w = (1.0 + 0.2 * torch.randn(2, D, generator=g)).to(BF).to(dev)
+    cos, sin = (t.to(dev) for t in rope_table_1d(T, H))
+    a, b = _sent_bf16((M + 2, 2 * D + 8), dev), _sent_bf16((M + 2, 2 * D + 8), dev)
+    a[:M, :2 * D] = x.to(dev)
+    b[:M, :2 * D] = x.to(dev)
+    ops.qknorm_rope_1d(a[:M], D, w, cos, sin, T, H, 1e-6)
+    ops.qknorm_rope(b[:M], 2, D, w, cos, sin, T, H, 1e-6)
+    torch.cuda.synchronize()
+    for y in (a, b):
+        assert _untouched(y[M:]) and _untouched(y[:, 2 * D:])
+    assert not bool(torch.isnan(a[:M, :2 * D]).any()) and not torch.equal(a[:M, :2 * D].cpu(), x)
+    assert torch.equal(a[:M, :2 * D].view(torch.int16), b[:M, :2 * D].view(torch.int16))
 
 
 def test_connector_assemble(dev):
