@@ -209,7 +209,7 @@ class LTXModel:
         self._w8a8_plans: Dict[tuple, bool] = {}
         # the split-K scratch of ops.gemm (small-M launches) must exist before anyone captures a forward into a hipGraph: allocated
         # inside a capture it would come from that graph's private pool
-        ops._gemm_workspace(self.tables.device)
+        ops._scratch("gemm_splitk", self.tables.device)
 
     # ------------------------------------------------------------------ weights
     def _pack(self, W: Dict[str, torch.Tensor]) -> None:

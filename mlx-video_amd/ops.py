@@ -11,7 +11,7 @@ from typing import Optional, Tuple
 import torch
 
 from . import _lib
-from ._lib import AttnArgs, CausalAttnArgs, GemmArgs, GemmGroupedArgs, GuiderArgs, StepArgs, check
+from ._lib import AttnArgs, CausalAttnArgs, Conv3dArgs, GemmArgs, GemmGroupedArgs, GuiderArgs, StepArgs, check
 
 EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_SILU, EPI_BIAS_GATE_RES, EPI_BIAS_RES, EPI_SCALE_RES = 0, 1, 2, 3, 4, 5
 BF16 = torch.bfloat16
@@ -73,18 +73,75 @@ def _req(t: torch.Tensor, dtype, name: str) -> None:
         raise TypeError(f"{name}: expected {dtype}, got {t.dtype}")
 
 
-_GEMM_WS = {}
+def _dims(who: str, name: str, t: torch.Tensor, dtype, rank: int) -> torch.Size:
+    """``t.shape`` once its dtype and rank hold: the first two checks of ``_operands``, on their own for the operand a
+    shim derives its sizes from."""
+    if t.dtype != dtype:
+        raise TypeError(f"{who}: {name} must be {dtype}, got {t.dtype}")
+    if t.dim() != rank:
+        raise ValueError(f"{who}: {name} must have {rank} dimensions, got shape {tuple(t.shape)}")
+    return t.shape
+
+
+def _dense_rows(t: torch.Tensor) -> bool:
+    """(..., n, C) rows of a dense (..., n, ld >= C) buffer: unit inner stride, one leading dimension."""
+    st, sh = t.stride(), t.shape
+    return st[-1] == 1 and st[-2] >= sh[-1] and all(st[i] == st[i + 1] * sh[i + 1] for i in range(len(sh) - 2))
+
+
+def _operands(who: str, *operands) -> None:
+    """The one operand check of the VAE / upsampler shims.  An operand is ``(name, tensor or None, dtype, shape, align)``:
+    ``shape`` the exact shape the call derives (an int: the rank alone), ``align`` the byte alignment the C entry or its
+    kernel's vector accesses demand; a sixth item ``True`` allows a leading dimension (``_dense_rows``) in place of
+    contiguity.  Per tensor: dtype, shape, layout, alignment - and only when every operand has passed those, the device, so
+    that each of the other refusals shows on CPU tensors too.  Nothing is launched on a tensor it refuses.
+    One compound test per operand on the way through (this runs in front of every launch); ``_refuse`` words the error."""
+    host = None
+    for op in operands:
+        t = op[1]
+        if t is None:
+            continue
+        shape = op[3]
+        if t.dtype != op[2] or (t.dim() != shape if shape.__class__ is int else t.shape != shape) or \
+                not (t.is_contiguous() if len(op) == 5 else _dense_rows(t)) or t.data_ptr() % op[4]:
+            _refuse(who, *op)
+        if host is None and not t.is_cuda:
+            host = op[0]
+    if host is not None:
+        raise _lib.LtxkError(f"{who}: {host} must be a device tensor (the product path has no CPU fallback)")
+
+
+def _refuse(who: str, name: str, t: torch.Tensor, dtype, shape, align: int, ld: bool = False) -> None:
+    """Raises for the first of ``_operands``' per-tensor checks that ``t`` fails, in their order."""
+    exact = not isinstance(shape, int)
+    _dims(who, name, t, dtype, len(shape) if exact else shape)
+    if exact and t.shape != shape:
+        raise ValueError(f"{who}: {name} must be {tuple(shape)}, got {tuple(t.shape)}")
+    if not (_dense_rows(t) if ld else t.is_contiguous()):
+        raise ValueError(f"{who}: {name} must be {'rows with unit inner stride' if ld else 'contiguous'}, got shape "
+                         f"{tuple(t.shape)} with strides {t.stride()}")
+    raise ValueError(f"{who}: {name} must be {align}-byte aligned")
+
+
 GEMM_WORKSPACE_BYTES = 64 << 20
+SPLITK_WORKSPACE_BYTES = 96 << 20
 SPLITK_MAX_M = 640          # rows up to which a launch is offered the split-K scratch (the library decides; gemm.hip)
+# purpose -> (elements, dtype, constructor) of the per-device buffers the library is handed and never allocates itself
+_SCRATCH_KINDS = {"gemm_splitk": (GEMM_WORKSPACE_BYTES // 4, torch.float32, torch.empty),        # ltxk_gemm_bf16 at small M
+                  "conv_splitk": (SPLITK_WORKSPACE_BYTES // 4, torch.float32, torch.empty),      # ltxk_conv3d_k3_bf16
+                  "zero_page": (256, torch.uint8, torch.zeros)}                                  # the conv's zero-padding halo
+_SCRATCH = {}
 
 
-def _gemm_workspace(dev: torch.device) -> torch.Tensor:
-    """Per-device fp32 scratch handed to ltxk_gemm_bf16 for its split-K form at small M (caller-owned and reused by every
-    call on the stream - launches on one stream are ordered; the library never allocates)."""
-    key = dev.index if dev.index is not None else 0
-    if key not in _GEMM_WS:
-        _GEMM_WS[key] = torch.empty(GEMM_WORKSPACE_BYTES // 4, dtype=torch.float32, device=dev)
-    return _GEMM_WS[key]
+def _scratch(purpose: str, dev: torch.device) -> torch.Tensor:
+    """The per-device buffer of one purpose (_SCRATCH_KINDS): caller-owned and reused by every call on the stream - launches
+    on one stream are ordered."""
+    key = (purpose, dev.index if dev.index is not None else 0)
+    buf = _SCRATCH.get(key)
+    if buf is None:
+        n, dtype, make = _SCRATCH_KINDS[purpose]
+        buf = _SCRATCH[key] = make(n, dtype=dtype, device=dev)
+    return buf
 
 
 def _offers_workspace(M: int, split_k: bool) -> bool:
@@ -160,7 +217,7 @@ def gemm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], *, epil
             check(_lib.load().ltxk_gemm_w8a8(ctypes.byref(args), _p(a_scale), _p(w_scale), _stream()), "ltxk_gemm_w8a8")
         return out
     if _offers_workspace(M, split_k):
-        ws = _gemm_workspace(a.device)
+        ws = _scratch("gemm_splitk", a.device)
         args.workspace, args.workspace_bytes = ws.data_ptr(), ws.numel() * 4
     if w8:
         with _timed("gemm_w8", 2.0 * M * N * K, 2.0 * (M * K + M * N) + 1.0 * N * K):
@@ -925,4 +982,260 @@ def causal_attn(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, out: torch.T
     a.B, a.Hq, a.Hkv, a.T, a.window, a.scale = B, Hq, Hkv, T, window, scale
     with _timed("causal_attn", 2.0 * B * Hq * T * T * GEMMA_HEAD_DIM, 2.0 * B * T * GEMMA_HEAD_DIM * (2 * Hq + 2 * Hkv)):
         check(_lib.load().ltxk_causal_attn(ctypes.byref(a), _stream()), "ltxk_causal_attn")
+    return out
+
+
+# ------------------------------------------------------------------- VAE / upsampler (csrc/conv3d.hip, csrc/vae_ops.hip)
+# Volumes are channels-last (B,D,H,W,C) bf16, a voxel one contiguous row.  Every operand goes through ``_operands``.
+PAD_ZEROS, PAD_REFLECT = 0, 1
+
+
+def conv3d(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, causal: bool, pad_mode: int,
+           resid: Optional[torch.Tensor] = None, act: Optional[dict] = None, keep_out: bool = True):
+    """x (B,D,H,W,Cin) bf16 channels-last; w (Cout,3,3,3,Cin), or (Cout,3,3,Cin) for a per-frame 3x3 kernel;
+    returns (B,D,H,W,Cout).  ``act`` = dict(eps, silu, scale, shift): the PixelNorm (+ modulation) + SiLU that follows
+    this conv is applied to its output rows in the epilogue (Cout 128 / 256) and returned as a second tensor:
+    ``(out, act_out)``; ``keep_out=False`` skips the raw output (``out`` is None) when nothing else reads it."""
+    B, D, H, W, Cin = _dims("conv3d", "x", x, BF16, 5)
+    Cout = w.shape[0]
+    taps_d = 3 if w.dim() == 5 else 1
+    if tuple(w.shape[1:]) != ((3, 3, 3, Cin) if taps_d == 3 else (3, 3, Cin)):
+        raise ValueError(f"conv3d: weight {tuple(w.shape)} does not match Cin={Cin}")
+    oshape = (B, D, H, W, Cout)
+    sc, sh = (act.get("scale"), act.get("shift")) if act is not None else (None, None)
+    if (sc is None) != (sh is None):
+        raise ValueError("conv3d: act['scale'] and act['shift'] must both be given or both be absent")
+    _operands("conv3d", ("x", x, BF16, 5, 16), ("w", w, BF16, w.dim(), 16), ("bias", b, BF16, (Cout,), 2),
+              ("resid", resid, BF16, oshape, 8), ("act['scale']", sc, BF16, (B, Cout), 8), ("act['shift']", sh, BF16, (B, Cout), 8))
+    out = torch.empty(oshape, dtype=BF16, device=x.device) if (keep_out or act is None) else None
+    a = Conv3dArgs()
+    a.x, a.w, a.bias, a.out, a.resid = _p(x), _p(w), _p(b), _p(out), _p(resid)
+    a.zero_page = _p(_scratch("zero_page", x.device))
+    a.B, a.D, a.H, a.W, a.Cin, a.Cout = B, D, H, W, Cin, Cout
+    a.causal, a.pad_mode, a.taps_d = int(causal), pad_mode, taps_d
+    ws = _scratch("conv_splitk", x.device)
+    a.workspace, a.workspace_bytes = _p(ws), ws.numel() * 4
+    act_out = None
+    if act is not None:
+        act_out = torch.empty(oshape, dtype=BF16, device=x.device)
+        a.act_out, a.act_scale, a.act_shift = _p(act_out), _p(sc), _p(sh)
+        a.act_eps, a.act_silu = float(act["eps"]), int(bool(act.get("silu", True)))
+    V = B * D * H * W
+    ntap = 27 if taps_d == 3 else 9
+    with _timed("conv3d_k3", 2.0 * ntap * Cin * Cout * V, 2.0 * V * (Cin + Cout) + 2.0 * ntap * Cin * Cout):
+        check(_lib.load().ltxk_conv3d_k3_bf16(ctypes.byref(a), _stream()), "ltxk_conv3d_k3_bf16")
+    return out if act is None else (out, act_out)
+
+
+@dataclass(frozen=True)
+class Conv3dPlan:
+    """ltxk_conv3d_plan: the launch form of one ltxk_conv3d_k3_bf16 call (include/ltxk.h, struct ltxk_conv3d_plan)."""
+    kernel: int               # _lib.CONV_KERNEL_*
+    tile_rows: int
+    tile_cols: int
+    row_tiles: int            # of the main launch
+    col_tiles: int
+    slices: int               # 1 unless split-K
+    ksteps: int               # per slice
+    tail_tile_rows: int       # the tail launch (all 0: none)
+    tail_m_base: int
+    tail_row_tiles: int
+    fused_act: bool
+
+    @property
+    def kw(self) -> bool:
+        return self.kernel == _lib.CONV_KERNEL_KW
+
+    @property
+    def split_k(self) -> bool:
+        return self.slices >= 2
+
+    @property
+    def tail(self) -> bool:
+        return self.tail_row_tiles > 0
+
+
+def conv3d_plan(B: int, D: int, H: int, W: int, Cin: int, Cout: int, *, causal: int = 1, pad_mode: int = PAD_REFLECT,
+                taps_d: int = 3, resid: bool = False, act: bool = False, keep_out: bool = True,
+                workspace: Optional[Tuple[int, int]] = None) -> Conv3dPlan:
+    """The form ``conv3d`` takes for this volume, decided on the host by the function the launch itself uses (no device
+    needed).  The split-K scratch is offered as ``conv3d`` offers it (SPLITK_WORKSPACE_BYTES); ``workspace=(address,
+    bytes)`` offers that one instead (address 0: none).  Raises LtxkError where the launch would refuse the arguments."""
+    addr = _PLAN_ADDR
+    a = Conv3dArgs()
+    a.x = a.w = a.bias = a.zero_page = addr
+    a.out = addr if (keep_out or not act) else None
+    a.resid = addr if resid else None
+    a.B, a.D, a.H, a.W, a.Cin, a.Cout = B, D, H, W, Cin, Cout
+    a.causal, a.pad_mode, a.taps_d = int(causal), pad_mode, taps_d
+    a.workspace, a.workspace_bytes = (addr, SPLITK_WORKSPACE_BYTES) if workspace is None else workspace
+    if act:
+        a.act_out = addr
+    pl = _lib.Conv3dPlan()
+    check(_lib.load().ltxk_conv3d_plan(ctypes.byref(a), ctypes.byref(pl)), "ltxk_conv3d_plan")
+    return Conv3dPlan(pl.kernel, pl.tile_rows, pl.tile_cols, pl.row_tiles, pl.col_tiles, pl.slices, pl.ksteps,
+                      pl.tail_tile_rows, pl.tail_m_base, pl.tail_row_tiles, bool(pl.fused_act))
+
+
+def pixelnorm_act(x: torch.Tensor, eps: float, silu: bool, scale: Optional[torch.Tensor] = None,
+                  shift: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ltxk_pixelnorm_act over the rows of x (B,...,C) [+ (1+scale)+shift per (batch, channel): scale / shift (B,C)] [+ SiLU]."""
+    if (scale is None) != (shift is None):
+        raise ValueError("pixelnorm_act: scale and shift must both be given or both be None")
+    B = x.shape[0]
+    C = x.shape[-1]
+    _operands("pixelnorm_act", ("x", x, BF16, x.dim(), 16), ("scale", scale, BF16, (B, C), 16), ("shift", shift, BF16, (B, C), 16))
+    V = x.numel() // C
+    out = torch.empty_like(x)
+    with _timed("pixelnorm_act", 0.0, 4.0 * V * C):
+        check(_lib.load().ltxk_pixelnorm_act(_p(x), _p(out), V, C, eps, _p(scale), _p(shift), V // B, int(silu),
+                                             _stream()), "ltxk_pixelnorm_act")
+    return out
+
+
+def d2s_add(conv: torch.Tensor, xin: Optional[torch.Tensor]) -> torch.Tensor:
+    """ltxk_d2s_add: conv (B,D,H,W,8*Co) -> (B,2D-1,2H,2W,Co) plus the tiled residual of xin (B,D,H,W,Ci) (None: none)."""
+    B, D, H, W, C8 = _dims("d2s_add", "conv", conv, BF16, 5)
+    if C8 % 8:
+        raise ValueError(f"d2s_add: conv must be (B,D,H,W,8*Co), got {tuple(conv.shape)}")
+    Co = C8 // 8
+    _operands("d2s_add", ("conv", conv, BF16, 5, 16),
+              ("xin", xin, BF16, None if xin is None else (B, D, H, W) + tuple(xin.shape[-1:]), 16))
+    out = torch.empty((B, 2 * D - 1, 2 * H, 2 * W, Co), dtype=BF16, device=conv.device)
+    with _timed("d2s_add", 0.0, 2.0 * conv.numel() * 2 + (2.0 * xin.numel() if xin is not None else 0)):
+        check(_lib.load().ltxk_d2s_add(_p(conv), _p(xin), _p(out), B, D, H, W, Co, xin.shape[-1] if xin is not None else 0,
+                                       _stream()), "ltxk_d2s_add")
+    return out
+
+
+def groupnorm_act(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, resid=None, silu: bool = True,
+                  groups: int = 32, eps: float = 1e-5) -> torch.Tensor:
+    """ltxk_groupnorm_act: GroupNorm over (voxels, C/groups) of x (B,...,C) + affine [+ resid] [+ SiLU]."""
+    B, C = x.shape[0], x.shape[-1]
+    if C % groups:
+        raise ValueError(f"groupnorm_act: x has {C} channels, no multiple of groups={groups}")
+    _operands("groupnorm_act", ("x", x, BF16, x.dim(), 2), ("gamma", gamma, BF16, (C,), 2), ("beta", beta, BF16, (C,), 2),
+              ("resid", resid, BF16, x.shape, 2))
+    V = x.numel() // (B * C)
+    out = torch.empty_like(x)
+    check(_lib.load().ltxk_groupnorm_act(_p(x), _p(out), _p(gamma), _p(beta), _p(resid), B, V, C, groups, eps, int(silu),
+                                         _stream()), "ltxk_groupnorm_act")
+    return out
+
+
+def latent_denorm_cl(latent: torch.Tensor, mean: torch.Tensor, std: torch.Tensor, noise: Optional[torch.Tensor] = None,
+                     noise_scale: float = 0.0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ltxk_latent_denorm_cl: latent (B,C,...) channels-first -> (B,...,C) channels-last with x*std + mean, mean / std (C);
+    with ``noise`` (the latent's shape) the blend noise*noise_scale + (1-noise_scale)*x comes first."""
+    if latent.dim() < 3:
+        raise ValueError(f"latent_denorm_cl: latent must be (B,C,...), got {tuple(latent.shape)}")
+    B, C = latent.shape[:2]
+    oshape = (B,) + tuple(latent.shape[2:]) + (C,)
+    _operands("latent_denorm_cl", ("latent", latent, BF16, latent.dim(), 2), ("mean", mean, BF16, (C,), 2), ("std", std, BF16, (C,), 2),
+              ("noise", noise, BF16, latent.shape, 2), ("out", out, BF16, oshape, 16))
+    if out is None:
+        out = torch.empty(oshape, dtype=BF16, device=latent.device)
+    check(_lib.load().ltxk_latent_denorm_cl(_p(latent), _p(noise), float(noise_scale) if noise is not None else 0.0, _p(mean), _p(std),
+                                            _p(out), B, C, latent.numel() // (B * C), _stream()), "ltxk_latent_denorm_cl")
+    return out
+
+
+def latent_norm_cf(x: torch.Tensor, mean: torch.Tensor, std: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ltxk_latent_norm_cf: x (B,...,C) channels-last rows (row stride ldx >= C) -> (B,C,...) channels-first with
+    (x - mean)/std, mean / std (C)."""
+    if x.dim() < 3:
+        raise ValueError(f"latent_norm_cf: x must be (B,...,C), got {tuple(x.shape)}")
+    B, C = x.shape[0], x.shape[-1]
+    oshape = (B, C) + tuple(x.shape[1:-1])
+    _operands("latent_norm_cf", ("x", x, BF16, x.dim(), 16, True), ("mean", mean, BF16, (C,), 2), ("std", std, BF16, (C,), 2),
+              ("out", out, BF16, oshape, 2))
+    if out is None:
+        out = torch.empty(oshape, dtype=BF16, device=x.device)
+    check(_lib.load().ltxk_latent_norm_cf(_p(x), x.stride(-2), _p(mean), _p(std), _p(out), B, C, x.numel() // (B * C), _stream()),
+          "ltxk_latent_norm_cf")
+    return out
+
+
+def patchify_cl(video: torch.Tensor, P: int, Cpad: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ltxk_patchify_cl: video (B,C,D,H,W) -> (B,D,H/P,W/P,Cpad) channels-last, channel (c,p_w,p_h), channels from C*P*P up zero."""
+    B, C, D, H, W = _dims("patchify_cl", "video", video, BF16, 5)
+    if P < 1 or H % P or W % P or Cpad < C * P * P:
+        raise ValueError(f"patchify_cl: needs H % P == 0, W % P == 0 and Cpad >= C*P*P, got {tuple(video.shape)}, P={P}, Cpad={Cpad}")
+    oshape = (B, D, H // P, W // P, Cpad)
+    _operands("patchify_cl", ("video", video, BF16, 5, 2), ("out", out, BF16, oshape, 2))
+    if out is None:
+        out = torch.empty(oshape, dtype=BF16, device=video.device)
+    check(_lib.load().ltxk_patchify_cl(_p(video), _p(out), B, C, D, H, W, P, Cpad, _stream()), "ltxk_patchify_cl")
+    return out
+
+
+def unpatchify_cf(x: torch.Tensor, C: int, P: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ltxk_unpatchify_cf: x (B,D,H,W,C*P*P) channels-last -> video (B,C,D,H*P,W*P) channels-first (8-byte aligned at P = 4)."""
+    B, D, H, W, CPP = _dims("unpatchify_cf", "x", x, BF16, 5)
+    if C < 1 or P < 1 or CPP != C * P * P:
+        raise ValueError(f"unpatchify_cf: x must be (B,D,H,W,C*P*P = {C * P * P}), got {tuple(x.shape)}")
+    oshape = (B, C, D, H * P, W * P)
+    _operands("unpatchify_cf", ("x", x, BF16, 5, 2), ("out", out, BF16, oshape, 8 if P == 4 else 2))
+    if out is None:
+        out = torch.empty(oshape, dtype=BF16, device=x.device)
+    check(_lib.load().ltxk_unpatchify_cf(_p(x), _p(out), B, D, H, W, C, P, _stream()), "ltxk_unpatchify_cf")
+    return out
+
+
+def s2d_skip(conv: torch.Tensor, xpad: torch.Tensor, stride: Tuple[int, int, int], out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ltxk_s2d_skip: conv (B,Dp,Hp,Wp,Cc) and the input xpad (B,Dp,Hp,Wp,Cx) it was computed on ->
+    (B,Dp/st,Hp/sh,Wp/sw,Cc*st*sh*sw) = s2d(conv) + the mean over groups of Cx/Cc channels of s2d(xpad)."""
+    st, sh, sw = stride
+    B, Dp, Hp, Wp, Cc = _dims("s2d_skip", "conv", conv, BF16, 5)
+    if st < 1 or sh < 1 or sw < 1 or Dp % st or Hp % sh or Wp % sw:
+        raise ValueError(f"s2d_skip: volume {Dp}x{Hp}x{Wp} not divisible by stride {tuple(stride)}")
+    Cx = xpad.shape[-1] if xpad.dim() else 0
+    if Cx % Cc:
+        raise ValueError(f"s2d_skip: xpad's {Cx} channels are no multiple of conv's {Cc}")
+    oshape = (B, Dp // st, Hp // sh, Wp // sw, Cc * st * sh * sw)
+    _operands("s2d_skip", ("conv", conv, BF16, 5, 2), ("xpad", xpad, BF16, (B, Dp, Hp, Wp, Cx), 2), ("out", out, BF16, oshape, 2))
+    if out is None:
+        out = torch.empty(oshape, dtype=BF16, device=conv.device)
+    check(_lib.load().ltxk_s2d_skip(_p(conv), _p(xpad), _p(out), B, Dp, Hp, Wp, Cc, Cx, st, sh, sw, Cx // Cc, _stream()),
+          "ltxk_s2d_skip")
+    return out
+
+
+def to_uint8(video: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ltxk_to_uint8: video (B,C,F,H,W) bf16 in [-1,1] -> frames (B,F,H,W,C) uint8."""
+    B, C, F, H, W = _dims("to_uint8", "video", video, BF16, 5)
+    oshape = (B, F, H, W, C)
+    _operands("to_uint8", ("video", video, BF16, 5, 2), ("out", out, torch.uint8, oshape, 1))
+    if out is None:
+        out = torch.empty(oshape, dtype=torch.uint8, device=video.device)
+    check(_lib.load().ltxk_to_uint8(_p(video), _p(out), B, C, F, H, W, _stream()), "ltxk_to_uint8")
+    return out
+
+
+def tile_blend_accum(tile: torch.Tensor, mt: torch.Tensor, mh: torch.Tensor, mw: torch.Tensor, acc: torch.Tensor,
+                     wsum: torch.Tensor, t0: int, h0: int, w0: int) -> torch.Tensor:
+    """ltxk_tile_blend_accum: acc[b,c,t0+t,h0+y,w0+x] += tile[b,c,t,y,x] * m and wsum[b,0,t0+t,h0+y,w0+x] += m with
+    m = mt[t]*mh[y]*mw[x], over the leading (len(mt), len(mh), len(mw)) box of tile (B,C,Tt,Th,Tw) bf16; the masks and
+    acc (B,C,F,H,W) / wsum (B,1,F,H,W) are float32.  The box must lie inside both volumes (the library refuses it otherwise)."""
+    F32 = torch.float32
+    B, C, F, H, W = _dims("tile_blend_accum", "acc", acc, F32, 5)
+    _operands("tile_blend_accum", ("tile", tile, BF16, (B, C) + tuple(tile.shape[2:]) if tile.dim() == 5 else 5, 2), ("mt", mt, F32, 1, 4), ("mh", mh, F32, 1, 4),
+              ("mw", mw, F32, 1, 4), ("acc", acc, F32, 5, 4), ("wsum", wsum, F32, (B, 1, F, H, W), 4))
+    Tt, Th, Tw = tile.shape[2:]
+    check(_lib.load().ltxk_tile_blend_accum(_p(tile), Tt, Th, Tw, mt.numel(), mh.numel(), mw.numel(), _p(mt), _p(mh), _p(mw),
+                                            _p(acc), _p(wsum), B, C, F, H, W, t0, h0, w0, _stream()), "ltxk_tile_blend_accum")
+    return acc
+
+
+def tile_blend_finalize(acc: torch.Tensor, wsum: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ltxk_tile_blend_finalize: bf16(acc / max(wsum, 1e-8)), acc (B,C,...) and wsum (B,1,...) float32 -> acc's shape."""
+    if acc.dim() < 3:
+        raise ValueError(f"tile_blend_finalize: acc must be (B,C,...), got {tuple(acc.shape)}")
+    B, C = acc.shape[:2]
+    _operands("tile_blend_finalize", ("acc", acc, torch.float32, acc.dim(), 4),
+              ("wsum", wsum, torch.float32, (B, 1) + tuple(acc.shape[2:]), 4), ("out", out, BF16, acc.shape, 2))
+    if out is None:
+        out = torch.empty(acc.shape, dtype=BF16, device=acc.device)
+    check(_lib.load().ltxk_tile_blend_finalize(_p(acc), _p(wsum), _p(out), B, C, acc.numel() // (B * C), _stream()),
+          "ltxk_tile_blend_finalize")
     return out

@@ -12,130 +12,17 @@ padded copies), and the norm/activation kernels are one-row-per-voxel streams.
 from __future__ import annotations
 
 
-import ctypes
 import math
 from dataclasses import dataclass
-from typing import Callable, Dict, List, Optional, Tuple
+from typing import Callable, Dict, List, Optional
 
 import torch
 
-from . import _lib, ops
-from ._lib import Conv3dArgs, check
+from . import ops
+from .ops import PAD_REFLECT, PAD_ZEROS, conv3d, d2s_add, pixelnorm_act
 
 BF16 = torch.bfloat16
-PAD_ZEROS, PAD_REFLECT = 0, 1
 DEC_CH = (1024, 512, 256, 128)
-
-
-def _p(t):
-    return None if t is None else t.data_ptr()
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-_ZERO_PAGES: Dict[int, torch.Tensor] = {}
-_WORKSPACES: Dict[int, torch.Tensor] = {}
-SPLITK_WORKSPACE_BYTES = 96 << 20
-
-
-def _workspace(dev) -> torch.Tensor:
-    """Per-device fp32 scratch handed to the conv kernel for split-K (caller-owned, reused by every call
-    on the stream; the library never allocates)."""
-    key = dev.index if dev.index is not None else 0
-    if key not in _WORKSPACES:
-        _WORKSPACES[key] = torch.empty(SPLITK_WORKSPACE_BYTES // 4, dtype=torch.float32, device=dev)
-    return _WORKSPACES[key]
-
-
-def _zero_page(dev) -> torch.Tensor:
-    key = dev.index if dev.index is not None else 0
-    if key not in _ZERO_PAGES:
-        _ZERO_PAGES[key] = torch.zeros(256, dtype=torch.uint8, device=dev)
-    return _ZERO_PAGES[key]
-
-
-# ------------------------------------------------------------------------------------ op shims
-def conv3d(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, causal: bool, pad_mode: int,
-           resid: Optional[torch.Tensor] = None, act: Optional[dict] = None, keep_out: bool = True):
-    """x (B,D,H,W,Cin) bf16 channels-last; w (Cout,3,3,3,Cin), or (Cout,3,3,Cin) for a per-frame 3x3 kernel;
-    returns (B,D,H,W,Cout).  ``act`` = dict(eps, silu, scale, shift): the PixelNorm (+ modulation) + SiLU that follows
-    this conv is applied to its output rows in the epilogue (Cout 128 / 256) and returned as a second tensor:
-    ``(out, act_out)``; ``keep_out=False`` skips the raw output (``out`` is None) when nothing else reads it."""
-    B, D, H, W, Cin = x.shape
-    Cout = w.shape[0]
-    taps_d = 3 if w.dim() == 5 else 1
-    if tuple(w.shape[1:]) != ((3, 3, 3, Cin) if taps_d == 3 else (3, 3, Cin)):
-        raise ValueError(f"conv3d: weight {tuple(w.shape)} does not match Cin={Cin}")
-    out = torch.empty((B, D, H, W, Cout), dtype=BF16, device=x.device) if (keep_out or act is None) else None
-    a = Conv3dArgs()
-    a.x, a.w, a.bias, a.out, a.resid = _p(x), _p(w), _p(b), _p(out), _p(resid)
-    a.zero_page = _p(_zero_page(x.device))
-    a.B, a.D, a.H, a.W, a.Cin, a.Cout = B, D, H, W, Cin, Cout
-    a.causal, a.pad_mode, a.taps_d = int(causal), pad_mode, taps_d
-    ws = _workspace(x.device)
-    a.workspace, a.workspace_bytes = _p(ws), ws.numel() * 4
-    act_out = None
-    if act is not None:
-        act_out = torch.empty((B, D, H, W, Cout), dtype=BF16, device=x.device)
-        a.act_out, a.act_scale, a.act_shift = _p(act_out), _p(act.get("scale")), _p(act.get("shift"))
-        a.act_eps, a.act_silu = float(act["eps"]), int(bool(act.get("silu", True)))
-    V = B * D * H * W
-    ntap = 27 if taps_d == 3 else 9
-    with ops._timed("conv3d_k3", 2.0 * ntap * Cin * Cout * V, 2.0 * V * (Cin + Cout) + 2.0 * ntap * Cin * Cout):
-        check(_lib.load().ltxk_conv3d_k3_bf16(ctypes.byref(a), _stream()), "ltxk_conv3d_k3_bf16")
-    return out if act is None else (out, act_out)
-
-
-@dataclass(frozen=True)
-class Conv3dPlan:
-    """ltxk_conv3d_plan: the launch form of one ltxk_conv3d_k3_bf16 call (include/ltxk.h, struct ltxk_conv3d_plan)."""
-    kernel: int               # _lib.CONV_KERNEL_*
-    tile_rows: int
-    tile_cols: int
-    row_tiles: int            # of the main launch
-    col_tiles: int
-    slices: int               # 1 unless split-K
-    ksteps: int               # per slice
-    tail_tile_rows: int       # the tail launch (all 0: none)
-    tail_m_base: int
-    tail_row_tiles: int
-    fused_act: bool
-
-    @property
-    def kw(self) -> bool:
-        return self.kernel == _lib.CONV_KERNEL_KW
-
-    @property
-    def split_k(self) -> bool:
-        return self.slices >= 2
-
-    @property
-    def tail(self) -> bool:
-        return self.tail_row_tiles > 0
-
-
-def conv3d_plan(B: int, D: int, H: int, W: int, Cin: int, Cout: int, *, causal: int = 1, pad_mode: int = PAD_REFLECT,
-                taps_d: int = 3, resid: bool = False, act: bool = False, keep_out: bool = True,
-                workspace: Optional[Tuple[int, int]] = None) -> Conv3dPlan:
-    """The form ``conv3d`` takes for this volume, decided on the host by the function the launch itself uses (no device
-    needed).  The split-K scratch is offered as ``conv3d`` offers it (SPLITK_WORKSPACE_BYTES); ``workspace=(address,
-    bytes)`` offers that one instead (address 0: none).  Raises LtxkError where the launch would refuse the arguments."""
-    addr = ops._PLAN_ADDR
-    a = Conv3dArgs()
-    a.x = a.w = a.bias = a.zero_page = addr
-    a.out = addr if (keep_out or not act) else None
-    a.resid = addr if resid else None
-    a.B, a.D, a.H, a.W, a.Cin, a.Cout = B, D, H, W, Cin, Cout
-    a.causal, a.pad_mode, a.taps_d = int(causal), pad_mode, taps_d
-    a.workspace, a.workspace_bytes = (addr, SPLITK_WORKSPACE_BYTES) if workspace is None else workspace
-    if act:
-        a.act_out = addr
-    pl = _lib.Conv3dPlan()
-    check(_lib.load().ltxk_conv3d_plan(ctypes.byref(a), ctypes.byref(pl)), "ltxk_conv3d_plan")
-    return Conv3dPlan(pl.kernel, pl.tile_rows, pl.tile_cols, pl.row_tiles, pl.col_tiles, pl.slices, pl.ksteps,
-                      pl.tail_tile_rows, pl.tail_m_base, pl.tail_row_tiles, bool(pl.fused_act))
 
 
 def conv_act_fusable(Cout: int, voxels: int, force: bool = False) -> bool:
@@ -148,28 +35,6 @@ def conv_act_fusable(Cout: int, voxels: int, force: bool = False) -> bool:
         return False
     bm = 256 if Cout <= 128 else 160
     return (voxels + bm - 1) // bm > 128
-
-
-def pixelnorm_act(x: torch.Tensor, eps: float, silu: bool, scale: Optional[torch.Tensor] = None,
-                  shift: Optional[torch.Tensor] = None) -> torch.Tensor:
-    B = x.shape[0]
-    C = x.shape[-1]
-    V = x.numel() // C
-    out = torch.empty_like(x)
-    with ops._timed("pixelnorm_act", 0.0, 4.0 * V * C):
-        check(_lib.load().ltxk_pixelnorm_act(_p(x), _p(out), V, C, eps, _p(scale), _p(shift), V // B, int(silu),
-                                             _stream()), "ltxk_pixelnorm_act")
-    return out
-
-
-def d2s_add(conv: torch.Tensor, xin: Optional[torch.Tensor]) -> torch.Tensor:
-    B, D, H, W, C8 = conv.shape
-    Co = C8 // 8
-    out = torch.empty((B, 2 * D - 1, 2 * H, 2 * W, Co), dtype=BF16, device=conv.device)
-    with ops._timed("d2s_add", 0.0, 2.0 * conv.numel() * 2 + (2.0 * xin.numel() if xin is not None else 0)):
-        check(_lib.load().ltxk_d2s_add(_p(conv), _p(xin), _p(out), B, D, H, W, Co, xin.shape[-1] if xin is not None else 0,
-                                       _stream()), "ltxk_d2s_add")
-    return out
 
 
 # ------------------------------------------------------------------------------------ tiling config (host math)
@@ -326,16 +191,10 @@ def decode_with_tiling(decoder_fn, latents: torch.Tensor, tiling_config: TilingC
     dev = latents.device
     acc = torch.zeros((b, 3, out_f, out_h, out_w), dtype=torch.float32, device=dev)
     wsum = torch.zeros((b, 1, out_f, out_h, out_w), dtype=torch.float32, device=dev)
-    lib = _lib.load()
     emitted = 0
 
     def finalize(lo: int, hi: int) -> torch.Tensor:
-        a = acc[:, :, lo:hi].contiguous()
-        w = wsum[:, :, lo:hi].contiguous()
-        o = torch.empty(a.shape, dtype=BF16, device=dev)
-        check(lib.ltxk_tile_blend_finalize(_p(a), _p(w), _p(o), b, 3, (hi - lo) * out_h * out_w, _stream()),
-              "ltxk_tile_blend_finalize")
-        return o
+        return ops.tile_blend_finalize(acc[:, :, lo:hi].contiguous(), wsum[:, :, lo:hi].contiguous())
 
     for ti in range(len(tiv.starts)):
         tsl, tmask = map_temporal_slice(tiv.starts[ti], tiv.ends[ti], tiv.left_ramps[ti], tiv.right_ramps[ti], temporal_scale)
@@ -346,12 +205,11 @@ def decode_with_tiling(decoder_fn, latents: torch.Tensor, tiling_config: TilingC
                 tile_lat = latents[:, :, tiv.starts[ti]:tiv.ends[ti], hiv.starts[hi_]:hiv.ends[hi_], wiv.starts[wi]:wiv.ends[wi]].contiguous()
                 kw = {"noise_fn": noise_fn} if noise_fn is not None else {}
                 tile = decoder_fn(tile_lat, causal=causal, timestep=timestep, debug=False, chunked_conv=chunked_conv, **kw)
+                tile = tile.to(BF16).contiguous()          # this project's decoder: the same object; a foreign callable's tile: made dense bf16
                 _, _, dt_, dh_, dw_ = tile.shape
                 at, ah, aw = min(dt_, tsl.stop - tsl.start), min(dh_, hsl.stop - hsl.start), min(dw_, wsl.stop - wsl.start)
                 mt, mh, mw = tmask[:at].to(dev), hmask[:ah].to(dev), wmask[:aw].to(dev)
-                check(lib.ltxk_tile_blend_accum(_p(tile), dt_, dh_, dw_, at, ah, aw, _p(mt), _p(mh), _p(mw), _p(acc), _p(wsum),
-                                                b, 3, out_f, out_h, out_w, tsl.start, hsl.start, wsl.start, _stream()),
-                      "ltxk_tile_blend_accum")
+                ops.tile_blend_accum(tile, mt, mh, mw, acc, wsum, tsl.start, hsl.start, wsl.start)
         if on_frames_ready is not None and len(tiv.starts) > 1 and ti < len(tiv.starts) - 1:
             nxt = tiv.starts[ti + 1]
             nxt_out = 0 if nxt == 0 else 1 + (nxt - 1) * temporal_scale
@@ -370,11 +228,12 @@ class LTX2VideoDecoder:
     after its key remap (decoder.py:544-591): conv_in.conv.{weight,bias}, up_blocks.{0,2,4,6}.
     res_blocks.{i}.conv{1,2}.conv.*, up_blocks.{1,3,5}.conv.*, conv_out.conv.*, latents_mean/std,
     and with timestep conditioning the time embedders + scale_shift tables.  Conv weights in the
-    MLX layout (O,kD,kH,kW,I)."""
+    MLX layout (O,kD,kH,kW,I).  Every tensor is kept as ``.to(BF16).contiguous()``: for a contiguous bf16 tensor that is
+    the tensor itself (no copy, no launch); anything else is converted once here instead of being misread by a kernel."""
 
     def __init__(self, weights: Dict[str, torch.Tensor], timestep_conditioning: bool = False,
                  num_layers_per_block: int = 5, patch_size: int = 4):
-        self.W = {k: v.contiguous() for k, v in weights.items()}
+        self.W = {k: v.to(BF16).contiguous() for k, v in weights.items()}
         self.timestep_conditioning = timestep_conditioning
         self.num_layers_per_block = num_layers_per_block
         self.patch_size = patch_size
@@ -436,11 +295,7 @@ class LTX2VideoDecoder:
             nz = noise.to(BF16).contiguous()
             tval = self.decode_timestep if timestep is None else float(timestep.reshape(-1)[0])
             st = torch.full((B,), tval * 1000.0, dtype=torch.float32, device=x.device).to(BF16)
-        S = Fl * Hl * Wl
-        xcl = torch.empty((B, Fl, Hl, Wl, C), dtype=BF16, device=x.device)
-        check(_lib.load().ltxk_latent_denorm_cl(_p(x), _p(nz) if tc else None, float(self.decode_noise_scale) if tc else 0.0,
-                                                _p(self.latents_mean), _p(self.latents_std), _p(xcl), B, C, S, _stream()),
-              "ltxk_latent_denorm_cl")
+        xcl = ops.latent_denorm_cl(x, self.latents_mean, self.latents_std, nz if tc else None, self.decode_noise_scale)
         x = conv3d(xcl, W["conv_in.conv.weight"], W["conv_in.conv.bias"], causal, PAD_REFLECT)
         sc = sh = None                          # modulation of the last PixelNorm (before conv_out)
         if tc:
@@ -494,11 +349,7 @@ class LTX2VideoDecoder:
                 x = d2s_add(cv, x)
         x = h_final if h_final is not None else pixelnorm_act(x, 1e-8, True, sc, sh)
         y = conv3d(x, W["conv_out.conv.weight"], W["conv_out.conv.bias"], causal, PAD_REFLECT)
-        _, Fo, Ho, Wo, _ = y.shape
-        P = self.patch_size
-        video = torch.empty((B, 3, Fo, Ho * P, Wo * P), dtype=BF16, device=y.device)
-        check(_lib.load().ltxk_unpatchify_cf(_p(y), _p(video), B, Fo, Ho, Wo, 3, P, _stream()), "ltxk_unpatchify_cf")
-        return video
+        return ops.unpatchify_cf(y, 3, self.patch_size)
 
     def decode_tiled(self, sample: torch.Tensor, tiling_config: Optional[TilingConfig] = None, tiling_mode: str = "auto",
                      causal: bool = False, timestep=None, debug: bool = False,
@@ -526,10 +377,7 @@ class LTX2VideoDecoder:
 
 def to_uint8_frames(video: torch.Tensor) -> torch.Tensor:
     """generate.py:3894-3898: (B,3,F,H,W) bf16 -> (B,F,H,W,3) uint8."""
-    B, C, F, H, W = video.shape
-    out = torch.empty((B, F, H, W, C), dtype=torch.uint8, device=video.device)
-    check(_lib.load().ltxk_to_uint8(_p(video.contiguous()), _p(out), B, C, F, H, W, _stream()), "ltxk_to_uint8")
-    return out
+    return ops.to_uint8(video.contiguous())
 
 
 # ------------------------------------------------------------------------------------ encoder
@@ -541,12 +389,13 @@ ENC_BLOCKS = [("res_x", 4), ("compress_space_res", (1, 2, 2)), ("res_x", 6), ("c
 class VideoEncoder:
     """video_vae.py:220-372 with the default block list of encoder.py:95-105: causal convs, zero
     spatial padding, PixelNorm(eps=1e-6), uniform log-variance head (only the 128 mean channels are
-    computed: the 129th output channel never reaches the caller, video_vae.py:350-372)."""
+    computed: the 129th output channel never reaches the caller, video_vae.py:350-372).  Weights are kept as
+    ``.to(BF16).contiguous()`` - a contiguous bf16 tensor stays the same object, no copy and no launch."""
 
     def __init__(self, weights: Dict[str, torch.Tensor], encoder_blocks=None, patch_size: int = 4):
         self.blocks = list(ENC_BLOCKS if encoder_blocks is None else encoder_blocks)
         self.patch_size = patch_size
-        W = {k: v.contiguous() for k, v in weights.items()}
+        W = {k: v.to(BF16).contiguous() for k, v in weights.items()}
         for k in ("conv_in.weight", "conv_out.weight", "per_channel_statistics.mean", "per_channel_statistics.std"):
             if k not in W:
                 raise ValueError(f"Missing VAE encoder parameter: {k}")
@@ -568,10 +417,7 @@ class VideoEncoder:
             raise ValueError("Invalid number of frames: Encode input must have 1 + 8 * x frames "
                              f"(e.g., 1, 9, 17, ...). Got {F} frames.")
         P = self.patch_size
-        lib = _lib.load()
-        cpad = W["conv_in.weight"].shape[-1]
-        x = torch.empty((B, F, H // P, Wd // P, cpad), dtype=BF16, device=sample.device)
-        check(lib.ltxk_patchify_cl(_p(sample.to(BF16).contiguous()), _p(x), B, C, F, H, Wd, P, cpad, _stream()), "ltxk_patchify_cl")
+        x = ops.patchify_cl(sample.to(BF16).contiguous(), P, W["conv_in.weight"].shape[-1])
         x = conv3d(x, W["conv_in.weight"], W["conv_in.bias"], True, PAD_ZEROS)
         for bi, (kind, arg) in enumerate(self.blocks):
             pre = f"down_blocks.{bi}"
@@ -590,18 +436,10 @@ class VideoEncoder:
                 if Dp % st or Hp % sh or Wp % sw:
                     raise ValueError(f"encoder volume {Dp}x{Hp}x{Wp} not divisible by stride {arg}")
                 cv = conv3d(x, W[f"{pre}.conv.weight"], W[f"{pre}.conv.bias"], True, PAD_ZEROS)
-                Cc = cv.shape[-1]
-                out = torch.empty((Bx, Dp // st, Hp // sh, Wp // sw, Cc * st * sh * sw), dtype=BF16, device=x.device)
-                check(lib.ltxk_s2d_skip(_p(cv), _p(x), _p(out), Bx, Dp, Hp, Wp, Cc, Cx, st, sh, sw, Cx // Cc, _stream()),
-                      "ltxk_s2d_skip")
-                x = out
+                x = ops.s2d_skip(cv, x, arg)
         x = pixelnorm_act(x, 1e-6, True)
         y = conv3d(x, W["conv_out.weight_means"], W["conv_out.bias_means"], True, PAD_ZEROS)
-        Bx, Dl, Hl, Wl, _ = y.shape
-        lat = torch.empty((Bx, 128, Dl, Hl, Wl), dtype=BF16, device=y.device)
-        check(lib.ltxk_latent_norm_cf(_p(y), 128, _p(W["per_channel_statistics.mean"]), _p(W["per_channel_statistics.std"]),
-                                      _p(lat), Bx, 128, Dl * Hl * Wl, _stream()), "ltxk_latent_norm_cf")
-        return lat
+        return ops.latent_norm_cf(y, W["per_channel_statistics.mean"], W["per_channel_statistics.std"])
 
 
 # ------------------------------------------------------------------------------------ synthetic weights / bench / smoke

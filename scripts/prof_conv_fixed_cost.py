@@ -3,7 +3,7 @@
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
-from mlx_video_amd import video_vae as V
+from mlx_video_amd import ops
 dev = torch.device("cuda:0")
 g = torch.Generator(device=dev).manual_seed(0)
 res = {}
@@ -13,12 +13,12 @@ for cin in (64, 128, 256):
     b = torch.zeros(128, device=dev, dtype=torch.bfloat16)
     if os.environ.get("CONV_ZERO_DATA") == "1":          # DVFS probe: all-zero operands (same instruction stream)
         x.zero_(); w.zero_()
-    for _ in range(3): V.conv3d(x, w, b, False, V.PAD_REFLECT)
+    for _ in range(3): ops.conv3d(x, w, b, False, ops.PAD_REFLECT)
     torch.cuda.synchronize()
     gr = torch.cuda.CUDAGraph(); st = torch.cuda.Stream()
     with torch.cuda.stream(st):
         with torch.cuda.graph(gr, stream=st):
-            for _ in range(10): V.conv3d(x, w, b, False, V.PAD_REFLECT)
+            for _ in range(10): ops.conv3d(x, w, b, False, ops.PAD_REFLECT)
     gr.replay(); torch.cuda.synchronize()
     t0 = time.perf_counter(); gr.replay(); torch.cuda.synchronize()
     res[cin] = (time.perf_counter() - t0) / 10 * 1e6

@@ -26,16 +26,14 @@ if case.startswith("attn_"):
     out = torch.empty((B * Tq, D), dtype=BF, device=dev)
     fn = lambda i: ops.flash_attn(q, k, vt, out, B, H, Tq, Tk, 1 / math.sqrt(128))
 elif case in ("conv128", "conv256"):
-    from mlx_video_amd import video_vae as V
     C, vol = (128, (33, 128, 128)) if case == "conv128" else (256, (17, 64, 64))
     x = rnd(1, *vol, C).to(BF)
     w = (rnd(C, 3, 3, 3, C) * 0.02).to(BF)
     b = (rnd(C) * 0.01).to(BF)
-    fn = lambda i: V.conv3d(x, w, b, False, V.PAD_REFLECT)
+    fn = lambda i: ops.conv3d(x, w, b, False, ops.PAD_REFLECT)
 elif case == "pixelnorm128":
-    from mlx_video_amd import video_vae as V
     xs = [rnd(1, 33, 128, 128, 128).to(BF) for _ in range(4)]
-    fn = lambda i: V.pixelnorm_act(xs[i % 4], 1e-8, True)
+    fn = lambda i: ops.pixelnorm_act(xs[i % 4], 1e-8, True)
 else:
     M, D, H, T = 2560, 4096, 32, 1280
     xs = [rnd(M, D).to(BF) for _ in range(8)]                      # rotated: 8 x 21 MB, rows are not simply L2-resident

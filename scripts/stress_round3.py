@@ -5,16 +5,16 @@ compared bit for bit with its first result.   python scripts/stress_round3.py [s
 import math, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
-from mlx_video_amd import ops, video_vae as V
+from mlx_video_amd import ops
 dev = torch.device("cuda:0"); BF = torch.bfloat16
 budget = float(sys.argv[1]) if len(sys.argv) > 1 else 60.0
 g = torch.Generator(device=dev).manual_seed(0)
 rn = lambda *s, sc=1.0: (torch.randn(s, generator=g, device=dev) * sc).to(BF)
 cases = {}
 x = rn(1, 9, 128, 128, 128); w = rn(128, 3, 3, 3, 128, sc=0.02); b = rn(128, sc=0.1); r = rn(1, 9, 128, 128, 128)
-cases["conv_kw_res"] = lambda: V.conv3d(x, w, b, False, V.PAD_REFLECT, resid=r)
+cases["conv_kw_res"] = lambda: ops.conv3d(x, w, b, False, ops.PAD_REFLECT, resid=r)
 x2 = rn(2, 3, 77, 101, 64); w2 = rn(48, 3, 3, 3, 64, sc=0.03); b2 = rn(48, sc=0.1)
-cases["conv_kw_zero_pad_odd"] = lambda: V.conv3d(x2, w2, b2, True, V.PAD_ZEROS)
+cases["conv_kw_zero_pad_odd"] = lambda: ops.conv3d(x2, w2, b2, True, ops.PAD_ZEROS)
 B, H, T, D = 2, 32, 1280, 4096
 q = rn(B * T, D); k = rn(B * T, D); vt = rn(B, D, T); wq = rn(D, sc=0.1) + 1
 ss = (q.float() ** 2).reshape(B * T, D // 64, 64).sum(-1).contiguous()

@@ -101,7 +101,7 @@ def test_block_fullwidth_vs_oracle(dev):
 
 
 def test_vae_fullsize_properties(dev):
-    from mlx_video_amd import _lib
+    from mlx_video_amd import ops
     from mlx_video_amd.video_vae import LTX2VideoDecoder, TilingConfig, random_decoder_weights, to_uint8_frames
     dec = LTX2VideoDecoder(random_decoder_weights(dev, layers=1), num_layers_per_block=1)
     g = torch.Generator(device=dev).manual_seed(3)
@@ -135,13 +135,9 @@ def test_vae_fullsize_properties(dev):
     x = nc[0, 1, 7].float()
     assert torch.equal(u8[0, 7, :, :, 1], ((x + 1) / 2).clamp(0, 1).to(BF).float().mul(255).to(BF).to(torch.uint8))
     # (v) patchify/unpatchify round trip at 33x512x512, bit exact
-    lib = _lib.load()
-    st = torch.cuda.current_stream().cuda_stream
-    pt = torch.empty((1, 33, 128, 128, 64), dtype=BF, device=dev)
-    assert lib.ltxk_patchify_cl(nc.data_ptr(), pt.data_ptr(), 1, 3, 33, 512, 512, 4, 64, st) == 0
-    p48 = pt[..., :48].contiguous()
-    back = torch.empty_like(nc)
-    assert lib.ltxk_unpatchify_cf(p48.data_ptr(), back.data_ptr(), 1, 33, 128, 128, 3, 4, st) == 0
+    pt = ops.patchify_cl(nc, 4, 64)
+    assert pt.shape == (1, 33, 128, 128, 64)
+    back = ops.unpatchify_cf(pt[..., :48].contiguous(), 3, 4)
     torch.cuda.synchronize()
     assert torch.equal(back, nc)
 

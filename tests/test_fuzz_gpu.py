@@ -125,7 +125,7 @@ def _conv_cases(n=14):
 
 @pytest.mark.parametrize("cin,cout,causal,reflect,shape", _conv_cases())
 def test_conv3d_fuzz(dev, cin, cout, causal, reflect, shape):
-    from mlx_video_amd import video_vae as V
+    from mlx_video_amd import ops
     b, d, h, w = shape
     g = torch.Generator().manual_seed(cin * 13 + cout + d * h * w)
     x = torch.randn(b, cin, d, h, w, generator=g).to(BF)
@@ -135,9 +135,9 @@ def test_conv3d_fuzz(dev, cin, cout, causal, reflect, shape):
     ref = OV.causal_conv3d(x.float(), wt, bias, O.BF16, bool(causal), reflect)
     cl = lambda t: t.permute(0, 2, 3, 4, 1).contiguous()
     cf = lambda t: t.permute(0, 4, 1, 2, 3).contiguous()
-    mode = V.PAD_REFLECT if reflect else V.PAD_ZEROS
-    out = V.conv3d(cl(x).to(dev), wt.to(dev), bias.to(dev), bool(causal), mode)
-    out_r = V.conv3d(cl(x).to(dev), wt.to(dev), bias.to(dev), bool(causal), mode, resid=cl(res).to(dev))
+    mode = ops.PAD_REFLECT if reflect else ops.PAD_ZEROS
+    out = ops.conv3d(cl(x).to(dev), wt.to(dev), bias.to(dev), bool(causal), mode)
+    out_r = ops.conv3d(cl(x).to(dev), wt.to(dev), bias.to(dev), bool(causal), mode, resid=cl(res).to(dev))
     torch.cuda.synchronize()
     parity.auto(rel_l2(cf(out), ref), 4e-3)
     parity.auto(rel_l2(cf(out_r), O.BF16.r(ref + res.float())), 4e-3)
@@ -158,7 +158,7 @@ def _kw_conv_cases(n=10):
 
 @pytest.mark.parametrize("cin,cout,causal,reflect,shape", _kw_conv_cases())
 def test_conv3d_kw_form_fuzz_vs_oracle(dev, cin, cout, causal, reflect, shape):
-    from mlx_video_amd import video_vae as V
+    from mlx_video_amd import ops
     b, d, h, w = shape
     assert b * d * h * w > 128 * 256
     g = torch.Generator().manual_seed(cin * 7 + cout * 3 + d * h + w)
@@ -169,9 +169,9 @@ def test_conv3d_kw_form_fuzz_vs_oracle(dev, cin, cout, causal, reflect, shape):
     ref = OV.causal_conv3d(x.float(), wt, bias, O.BF16, bool(causal), reflect)
     cl = lambda t: t.permute(0, 2, 3, 4, 1).contiguous()
     cf = lambda t: t.permute(0, 4, 1, 2, 3).contiguous()
-    mode = V.PAD_REFLECT if reflect else V.PAD_ZEROS
-    out = V.conv3d(cl(x).to(dev), wt.to(dev), bias.to(dev), bool(causal), mode)
-    out_r = V.conv3d(cl(x).to(dev), wt.to(dev), bias.to(dev), bool(causal), mode, resid=cl(res).to(dev))
+    mode = ops.PAD_REFLECT if reflect else ops.PAD_ZEROS
+    out = ops.conv3d(cl(x).to(dev), wt.to(dev), bias.to(dev), bool(causal), mode)
+    out_r = ops.conv3d(cl(x).to(dev), wt.to(dev), bias.to(dev), bool(causal), mode, resid=cl(res).to(dev))
     torch.cuda.synchronize()
     parity.auto(rel_l2(cf(out), ref), 4e-3)
     parity.auto(rel_l2(cf(out_r), O.BF16.r(ref + res.float())), 4e-3)

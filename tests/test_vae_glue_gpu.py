@@ -1,6 +1,8 @@
 """VAE and latent-upsampler glue kernels at their edge shapes, against the float64 references of tests/ref64.py (and,
 for the exact ones, against the oracle or a float32 restatement in the kernel's own operation order).  Outputs go into
-buffers with a NaN-sentinel tail that must survive bit for bit; bounds as in test_rowops_gpu.py."""
+buffers with a NaN-sentinel tail that must survive bit for bit; bounds as in test_rowops_gpu.py.  The calls go through the
+``ops`` shims with ``out=`` a view of the sentinel buffer; ``pixelnorm_act`` and ``groupnorm_act`` allocate their output, so
+their two sentinel tests hand the C entry the buffer themselves."""
 import math
 
 import parity
@@ -104,7 +106,7 @@ def test_latent_denorm_cl_edges(dev, noise_scale):
     """(B=2, C=128, S=65) channels-first -> channels-last with x*std + mean, with the timestep-conditioned noise blend
     at noise_scale 0.05 and 1.0 (0: no noise).  Catches: the partial last 64-wide block along S, mean/std indexed by the
     8-channel group instead of the channel, the blend weights swapped, and stores past B*S*C."""
-    L = _lib()
+    from mlx_video_amd import ops
     g = _g(int(noise_scale * 100))
     B, C, S = 2, 128, 65
     lat = torch.randn(B, C, S, generator=g).to(BF)
@@ -117,9 +119,7 @@ def test_latent_denorm_cl_edges(dev, noise_scale):
     lat_d = lat.to(dev)
     mean_d = mean.to(dev)
     std_d = std.to(dev)
-    L.check(L.load().ltxk_latent_denorm_cl(lat_d.data_ptr(), nd.data_ptr() if noise_scale else None, float(noise_scale),
-                                           mean_d.data_ptr(), std_d.data_ptr(), out.data_ptr(), B, C, S, _st()),
-            "ltxk_latent_denorm_cl")
+    ops.latent_denorm_cl(lat_d, mean_d, std_d, nd, noise_scale, out=out[:n].view(B, S, C))
     torch.cuda.synchronize()
     assert _untouched(out[n:])
     ref, mag = R.latent_denorm_cl(lat, mean, std, noise, noise_scale)
@@ -131,7 +131,7 @@ def test_latent_norm_cf_edges(dev, pad):
     """(B=2, S=65, ldx = C + pad) channels-last -> (B, C=128, S) with (x - mean)/std, std values that are not powers
     of two.  Catches: rows read at stride C instead of ldx (the pad columns hold NaN), the partial last block along S,
     and stores past B*C*S.  Exact against float32 (x - mean)/std -> bf16; within one ulp of float64."""
-    L = _lib()
+    from mlx_video_amd import ops
     g = _g(pad + 1)
     B, C, S = 2, 128, 65
     ldx = C + pad
@@ -144,8 +144,7 @@ def test_latent_norm_cf_edges(dev, pad):
     out = _sent_bf16((n + 64,), dev)
     mean_d = mean.to(dev)
     std_d = std.to(dev)
-    L.check(L.load().ltxk_latent_norm_cf(xb.data_ptr(), ldx, mean_d.data_ptr(), std_d.data_ptr(), out.data_ptr(),
-                                         B, C, S, _st()), "ltxk_latent_norm_cf")
+    ops.latent_norm_cf(xb[..., :C], mean_d, std_d, out=out[:n].view(B, C, S))
     torch.cuda.synchronize()
     assert _untouched(out[n:])
     got = out[:n].view(B, C, S).cpu()
@@ -161,7 +160,7 @@ def test_tile_blend_edges(dev):
     of its own (Tt, Th, Tw) strides, the masks applied to the wrong axis, a wsum per channel instead of per voxel,
     uncovered voxels coming out NaN/inf instead of 0 (max(wsum, 1e-8)), and stores past B*C*F*H*W.  Bit for bit against a
     float32 restatement in launch order; within one ulp of float64."""
-    L = _lib()
+    from mlx_video_amd import ops
     g = _g(11)
     B, C, F, H, W = 2, 3, 5, 9, 11
     Tt, Th, Tw = 3, 6, 7
@@ -171,19 +170,16 @@ def test_tile_blend_edges(dev):
         mt, mh, mw = (torch.rand(k, generator=g) * 0.9 + 0.1 for k in (Tt, Th, Tw))
         tiles.append((tile, (at, ah, aw), mt, mh, mw, off))
     S = F * H * W
-    acc = torch.zeros(B * C * S, device=dev)
-    ws = torch.zeros(B * S, device=dev)
+    acc = torch.zeros((B, C, F, H, W), device=dev)
+    ws = torch.zeros((B, 1, F, H, W), device=dev)
     keep = []
     for tile, (at, ah, aw), mt, mh, mw, (t0, h0, w0) in tiles:
         td, md = tile.to(dev), [m.to(dev) for m in (mt, mh, mw)]
         keep += [td] + md
-        L.check(L.load().ltxk_tile_blend_accum(td.data_ptr(), Tt, Th, Tw, at, ah, aw, md[0].data_ptr(), md[1].data_ptr(),
-                                               md[2].data_ptr(), acc.data_ptr(), ws.data_ptr(), B, C, F, H, W, t0, h0, w0,
-                                               _st()), "ltxk_tile_blend_accum")
+        ops.tile_blend_accum(td, md[0][:at], md[1][:ah], md[2][:aw], acc, ws, t0, h0, w0)
     n = B * C * S
     out = _sent_bf16((n + 64,), dev)
-    L.check(L.load().ltxk_tile_blend_finalize(acc.data_ptr(), ws.data_ptr(), out.data_ptr(), B, C, S, _st()),
-            "ltxk_tile_blend_finalize")
+    ops.tile_blend_finalize(acc, ws, out=out[:n].view(B, C, F, H, W))
     torch.cuda.synchronize()
     assert _untouched(out[n:])
     got = out[:n].view(B, C, F, H, W).cpu()
@@ -208,7 +204,7 @@ def test_to_uint8_every_value(dev):
     """Every finite bf16 in [-4, 4] plus +-inf, laid out as (B=2, C=3, F=5, H=37, W=33) (odd H and W).  Catches: a
     clamp placed before a rounding point instead of after it, rounding instead of truncating, the (B,C,F,H,W) ->
     (B,F,H,W,C) map wrong at odd extents, and stores past the frame buffer.  Exact against oracle/vae.py::to_uint8."""
-    L = _lib()
+    from mlx_video_amd import ops
     B, C, F, H, W = 2, 3, 5, 37, 33
     n = B * C * F * H * W
     vals = torch.cat([_all_finite_bf16(-4.0, 4.0), torch.tensor([math.inf, -math.inf]).to(BF)])
@@ -217,7 +213,7 @@ def test_to_uint8_every_value(dev):
     x = x[torch.randperm(n, generator=_g(3))].reshape(B, C, F, H, W)
     out = torch.full((n + 64,), 0xA5, dtype=torch.uint8, device=dev)
     x_d = x.to(dev)
-    L.check(L.load().ltxk_to_uint8(x_d.data_ptr(), out.data_ptr(), B, C, F, H, W, _st()), "ltxk_to_uint8")
+    ops.to_uint8(x_d, out=out[:n].view(B, F, H, W, C))
     torch.cuda.synchronize()
     assert bool((out[n:] == 0xA5).all())
     got = out[:n].view(B, F, H, W, C).cpu()
@@ -234,7 +230,7 @@ def test_patchify_roundtrip_edges(dev, P):
     patch counts (3 x 5).  Catches: the (c, p_w, p_h) channel order swapped to (c, p_h, p_w), pad channels left
     unwritten, the P = 4 vector store misplaced, and stores past either output.  Exact against OV.patchify /
     OV.unpatchify; unpatchify(patchify(x)) == x."""
-    L = _lib()
+    from mlx_video_amd import ops
     B, C, D = 2, 3, 3
     H, W = 3 * P, 5 * P
     v = torch.randn(B, C, D, H, W, generator=_g(P)).to(BF)
@@ -243,13 +239,13 @@ def test_patchify_roundtrip_edges(dev, P):
     n1 = B * D * (H // P) * (W // P) * cpad
     pt = _sent_bf16((n1 + 64,), dev)
     vd = v.to(dev)
-    L.check(L.load().ltxk_patchify_cl(vd.data_ptr(), pt.data_ptr(), B, C, D, H, W, P, cpad, _st()), "ltxk_patchify_cl")
+    ops.patchify_cl(vd, P, cpad, out=pt[:n1].view(B, D, H // P, W // P, cpad))
     n2 = B * D * (H // P) * (W // P) * cpp
-    ptc = torch.empty(n2, dtype=BF, device=dev)
-    L.check(L.load().ltxk_patchify_cl(vd.data_ptr(), ptc.data_ptr(), B, C, D, H, W, P, cpp, _st()), "ltxk_patchify_cl")
+    ptc = ops.patchify_cl(vd, P, cpp)
+    assert ptc.numel() == n2
     n3 = B * C * D * H * W
     up = _sent_bf16((n3 + 64,), dev)
-    L.check(L.load().ltxk_unpatchify_cf(ptc.data_ptr(), up.data_ptr(), B, D, H // P, W // P, C, P, _st()), "ltxk_unpatchify_cf")
+    ops.unpatchify_cf(ptc, C, P, out=up[:n3].view(B, C, D, H, W))
     torch.cuda.synchronize()
     assert _untouched(pt[n1:]) and _untouched(up[n3:])
     got = pt[:n1].view(B, D, H // P, W // P, cpad).cpu()

@@ -33,7 +33,7 @@ def cf(x):
     (256, 48, False, True, (1, 2, 8, 8)), (1024, 1024, False, True, (1, 2, 4, 4)), (128, 1024, False, True, (1, 1, 2, 2)),
     (512, 128, True, True, (1, 5, 3, 7))])
 def test_conv3d(dev, cin, cout, causal, reflect, shape):
-    from mlx_video_amd import video_vae as V
+    from mlx_video_amd import ops
     b, d, h, w = shape
     g = torch.Generator().manual_seed(cin + cout)
     x = torch.randn(b, cin, d, h, w, generator=g).to(BF)
@@ -41,8 +41,8 @@ def test_conv3d(dev, cin, cout, causal, reflect, shape):
     bias = (torch.randn(cout, generator=g) * 0.1).to(BF)
     res = torch.randn(b, cout, d, h, w, generator=g).to(BF)
     ref = OV.causal_conv3d(x.float(), wt, bias, O.BF16, causal, reflect)
-    out = V.conv3d(cl(x).to(dev), wt.to(dev), bias.to(dev), causal, V.PAD_REFLECT if reflect else V.PAD_ZEROS)
-    out_r = V.conv3d(cl(x).to(dev), wt.to(dev), bias.to(dev), causal, V.PAD_REFLECT if reflect else V.PAD_ZEROS,
+    out = ops.conv3d(cl(x).to(dev), wt.to(dev), bias.to(dev), causal, ops.PAD_REFLECT if reflect else ops.PAD_ZEROS)
+    out_r = ops.conv3d(cl(x).to(dev), wt.to(dev), bias.to(dev), causal, ops.PAD_REFLECT if reflect else ops.PAD_ZEROS,
                      resid=cl(res).to(dev))
     torch.cuda.synchronize()
     parity.auto(rel_l2(cf(out), ref), 3e-3)
@@ -52,7 +52,7 @@ def test_conv3d(dev, cin, cout, causal, reflect, shape):
 @pytest.mark.parametrize("C", [64, 128, 256, 512, 1024, 2048])      # 64: eight lanes per row, two rows per DPP row (common.h group_sum)
 @pytest.mark.parametrize("mod", [False, True])
 def test_pixelnorm_act(dev, C, mod):
-    from mlx_video_amd import video_vae as V
+    from mlx_video_amd import ops
     g = torch.Generator().manual_seed(C)
     x = (torch.randn(2, C, 2, 3, 5, generator=g) * 2).to(BF)
     p = O.BF16
@@ -63,7 +63,7 @@ def test_pixelnorm_act(dev, C, mod):
         sh = torch.randn(2, C, generator=g).to(BF)
         ref = OV._mod(ref, sc.float().reshape(2, C, 1, 1, 1), sh.float().reshape(2, C, 1, 1, 1), p)
     ref = O.silu(ref, p)
-    out = V.pixelnorm_act(cl(x).to(dev), 1e-8, True, sc.to(dev) if mod else None, sh.to(dev) if mod else None)
+    out = ops.pixelnorm_act(cl(x).to(dev), 1e-8, True, sc.to(dev) if mod else None, sh.to(dev) if mod else None)
     torch.cuda.synchronize()
     parity.auto(rel_l2(cf(out), ref), 3e-3)
 
@@ -74,6 +74,7 @@ def test_conv3d_fused_pixelnorm_act(dev, C, res, mod, keep):
     ltxk_pixelnorm_act (same rounding points; only the association of the 128/256-term mean of squares differs, so a rare
     element moves by one bf16 step), and equals the oracle's conv -> pixel_norm -> silu chain.  Ragged volume (rows past M
     in the last tile), two batch rows with different modulation."""
+    from mlx_video_amd import ops
     from mlx_video_amd import video_vae as V
     g = torch.Generator().manual_seed(C + res)
     # more than 128 tiles, so that the un-fused reference launch is not split along K either (split-K sums in another order)
@@ -87,9 +88,9 @@ def test_conv3d_fused_pixelnorm_act(dev, C, res, mod, keep):
     sh = torch.randn(B, C, generator=g).to(BF) if mod else None
     dv = lambda t: None if t is None else t.to(dev)
     act = dict(eps=1e-8, silu=True, scale=dv(sc), shift=dv(sh))
-    y_sep = V.conv3d(cl(x).to(dev), w.to(dev), b.to(dev), False, V.PAD_REFLECT, resid=dv(cl(r)) if res else None)
-    a_sep = V.pixelnorm_act(y_sep, 1e-8, True, dv(sc), dv(sh))
-    y_f, a_f = V.conv3d(cl(x).to(dev), w.to(dev), b.to(dev), False, V.PAD_REFLECT, resid=dv(cl(r)) if res else None, act=act, keep_out=keep)
+    y_sep = ops.conv3d(cl(x).to(dev), w.to(dev), b.to(dev), False, ops.PAD_REFLECT, resid=dv(cl(r)) if res else None)
+    a_sep = ops.pixelnorm_act(y_sep, 1e-8, True, dv(sc), dv(sh))
+    y_f, a_f = ops.conv3d(cl(x).to(dev), w.to(dev), b.to(dev), False, ops.PAD_REFLECT, resid=dv(cl(r)) if res else None, act=act, keep_out=keep)
     torch.cuda.synchronize()
     assert (y_f is None) == (not keep)
     if keep:
@@ -109,7 +110,7 @@ def test_conv3d_fused_pixelnorm_act(dev, C, res, mod, keep):
 
 
 def test_d2s_add_exact(dev):
-    from mlx_video_amd import video_vae as V
+    from mlx_video_amd import ops
     g = torch.Generator().manual_seed(1)
     B, Ci, D, H, W = 1, 64, 3, 2, 3
     Co = Ci // 2
@@ -117,27 +118,24 @@ def test_d2s_add_exact(dev):
     cv = torch.randn(B, Co * 8, D, H, W, generator=g).to(BF)
     ref = O.BF16.r(OV.depth_to_space(cv.float(), 2, 2, 2)[:, :, 1:] +
                    OV.depth_to_space(x.float(), 2, 2, 2).repeat(1, 4, 1, 1, 1)[:, :, 1:])
-    out = V.d2s_add(cl(cv).to(dev), cl(x).to(dev))
+    out = ops.d2s_add(cl(cv).to(dev), cl(x).to(dev))
     torch.cuda.synchronize()
     assert out.shape == (B, 2 * D - 1, 2 * H, 2 * W, Co)
     assert torch.equal(cf(out).float().cpu(), ref)
 
 
 def test_patchify_unpatchify_uint8_exact(dev):
-    from mlx_video_amd import _lib
+    from mlx_video_amd import ops
     from mlx_video_amd import video_vae as V
-    lib = _lib.load()
     g = torch.Generator().manual_seed(2)
     vid = (torch.rand(1, 3, 2, 8, 12, generator=g) * 2.4 - 1.2).to(BF)
     ref_p = OV.patchify(vid.float(), 4)                                  # (1,48,2,2,3)
-    out = torch.empty(1, 2, 2, 3, 64, dtype=BF, device=dev)
-    st = torch.cuda.current_stream().cuda_stream
-    vd = vid.to(dev)
-    assert lib.ltxk_patchify_cl(vd.data_ptr(), out.data_ptr(), 1, 3, 2, 8, 12, 4, 64, st) == 0
-    back = torch.empty(1, 3, 2, 8, 12, dtype=BF, device=dev)
-    o48 = out[..., :48].contiguous()
-    assert lib.ltxk_unpatchify_cf(o48.data_ptr(), back.data_ptr(), 1, 2, 2, 3, 3, 4, st) == 0
+    out = ops.patchify_cl(vid.to(dev), 4, 64)
+    assert out.shape == (1, 2, 2, 3, 64)
+    back = ops.unpatchify_cf(out[..., :48].contiguous(), 3, 4)
+    assert back.shape == (1, 3, 2, 8, 12)
     u8 = V.to_uint8_frames(vid.to(dev))
+    assert torch.equal(u8, ops.to_uint8(vid.to(dev)))
     torch.cuda.synchronize()
     assert torch.equal(cf(out[..., :48]).float().cpu(), ref_p) and float(out[..., 48:].abs().max()) == 0.0
     assert torch.equal(back.cpu(), vid)                                   # unpatchify(patchify(x)) == x
@@ -147,8 +145,7 @@ def test_patchify_unpatchify_uint8_exact(dev):
 
 @pytest.mark.parametrize("stride,cx,cc", [((1, 2, 2), 128, 64), ((2, 1, 1), 64, 64), ((2, 2, 2), 64, 16)])
 def test_s2d_skip(dev, stride, cx, cc):
-    from mlx_video_amd import _lib
-    lib = _lib.load()
+    from mlx_video_amd import ops
     st_, sh, sw = stride
     g = torch.Generator().manual_seed(3)
     B, Dp, Hp, Wp = 1, 4, 4, 6
@@ -160,12 +157,9 @@ def test_s2d_skip(dev, stride, cx, cc):
     gsz = xin.shape[1] // co
     xin = O.BF16.r(xin.reshape(B, co, gsz, *xin.shape[2:]).mean(dim=2))
     ref = O.BF16.r(OV.space_to_depth(cv.float(), st_, sh, sw) + xin)
-    out = torch.empty(B, Dp // st_, Hp // sh, Wp // sw, co, dtype=BF, device=dev)
-    cvd, xd = cl(cv).to(dev), cl(x).to(dev)          # keep alive until the kernel has run
-    rc = lib.ltxk_s2d_skip(cvd.data_ptr(), xd.data_ptr(), out.data_ptr(), B, Dp, Hp, Wp, cc, cx,
-                           st_, sh, sw, cx // cc, torch.cuda.current_stream().cuda_stream)
+    out = ops.s2d_skip(cl(cv).to(dev), cl(x).to(dev), stride)
     torch.cuda.synchronize()
-    assert rc == 0
+    assert out.shape == (B, Dp // st_, Hp // sh, Wp // sw, co)
     parity.auto(rel_l2(cf(out), ref), 2e-3)
 
 
@@ -256,6 +250,59 @@ def test_latent_upsampler(dev):
     parity.auto(rel_l2(out, ref), 2e-2)
 
 
+def test_upsample_latents_takes_float32_statistics(dev):
+    """latent_mean / latent_std as float32 vectors whose values are bf16 values (the round trip bf16 -> float32 is exact)
+    give the bits of the bf16 vectors: upsample_latents converts them instead of handing float32 memory to a bf16 kernel."""
+    from mlx_video_amd.upsampler import LatentUpsampler, upsample_latents
+    W = OV.make_upsampler_weights(mid=128, nb=2)
+    up = LatentUpsampler({k: v.to(dev) for k, v in W.items()}, num_blocks_per_stage=2)
+    g = torch.Generator().manual_seed(8)
+    lat = torch.randn(1, 128, 3, 4, 5, generator=g).to(BF).to(dev)
+    mean = (torch.randn(128, generator=g) * 0.1).to(BF).to(dev)
+    std = (1 + 0.1 * torch.randn(128, generator=g)).abs().to(BF).to(dev)
+    out = upsample_latents(lat, up, mean, std)
+    out32 = upsample_latents(lat.float(), up, mean.float(), std.float())
+    torch.cuda.synchronize()
+    assert out.shape == (1, 128, 3, 8, 10) and out32.dtype == BF
+    assert torch.equal(out, out32)
+
+
+@pytest.mark.parametrize("s_ov,t_ov", [(0, 0), (32, 8)], ids=["overlap0", "overlap32_8"])
+def test_decode_with_tiling_normalises_a_foreign_tile(dev, s_ov, t_ov):
+    """decode_with_tiling takes any callable.  A stub decoder (a deterministic torch function of the tile latent) returns
+    its tile once as contiguous bf16 and once with the same values as float32 through a permuted view: the blended
+    outputs are equal bit for bit.  Latents (1,128,3,3,5) under the smallest tiles the validators accept, 64 px and 16
+    frames = 2 latent cells, with no overlap and with the smallest non-zero one: 2 tiles along t and h, 3 or 4 along w,
+    the odd extents leaving a ragged last tile on every axis."""
+    from mlx_video_amd.video_vae import SpatialTilingConfig, TemporalTilingConfig, TilingConfig, decode_with_tiling
+    lat = torch.randn((1, 128, 3, 3, 5), generator=torch.Generator().manual_seed(11)).to(BF).to(dev)
+    shapes = []
+
+    def stub(foreign):
+        def decoder_fn(x, causal=False, timestep=None, debug=False, chunked_conv=False):
+            f = x.shape[2]
+            v = x[:, :3].float().repeat_interleave(8, dim=2)[:, :, 7:]             # 1 + 8(f-1) frames
+            v = v.repeat_interleave(32, dim=3).repeat_interleave(32, dim=4)
+            v = (v + torch.linspace(-1, 1, v.shape[4], device=x.device)).to(BF)    # position-dependent inside the tile
+            assert v.shape[2] == 1 + 8 * (f - 1)
+            shapes.append(tuple(x.shape[2:]))
+            if not foreign:
+                return v.contiguous()
+            t = v.float().permute(0, 1, 2, 4, 3).contiguous().permute(0, 1, 2, 4, 3)
+            assert t.dtype == torch.float32 and not t.is_contiguous() and torch.equal(t.to(BF), v)
+            return t
+        return decoder_fn
+
+    tc = TilingConfig(SpatialTilingConfig(64, s_ov), TemporalTilingConfig(16, t_ov))
+    own = decode_with_tiling(stub(False), lat, tc)
+    n_tiles = len(shapes)
+    foreign = decode_with_tiling(stub(True), lat, tc)
+    torch.cuda.synchronize()
+    assert n_tiles >= 2 * 2 * 3 and len(set(shapes)) > 1                         # several tiles on every axis, ragged ones among them
+    assert own.shape == (1, 3, 17, 96, 160) and own.dtype == BF and bool(torch.isfinite(own.float()).all())
+    assert torch.equal(own, foreign)
+
+
 def test_lora_merge(dev):
     from mlx_video_amd.lora import LoraSpec, apply_lora_to_weights, merge_lora_pair
     # reference known answer (tests/test_lora.py:8-29): I + 0.5*(1_{4x2}.1_{2x4}) = I + 1 -- at GEMM-legal sizes
@@ -324,7 +371,7 @@ def test_conv3d_short_last_round_as_half_tiles(dev, res, cout, shape, monkeypatc
     256 channels on 3x128x128 = 308 tiles of 160 rows, 512 channels on 2x112x112 = 157 x 2 tiles: the rows past the last
     whole round run as a second launch of lower tiles (conv3d.hip; LTXK_CONV_TAIL=0 in the A/B build switches it off).  Every output row is still one K-ordered
     sum: same bits as the single launch, with and without the residual."""
-    from mlx_video_amd import video_vae as V
+    from mlx_video_amd import ops
     g = torch.Generator(device=dev).manual_seed(3 + cout)
     x = torch.randn((1,) + shape + (128,), generator=g, device=dev).to(torch.bfloat16)
     w = (torch.randn((cout, 3, 3, 3, 128), generator=g, device=dev) * 0.02).to(torch.bfloat16)
@@ -333,7 +380,7 @@ def test_conv3d_short_last_round_as_half_tiles(dev, res, cout, shape, monkeypatc
     outs = {}
     for mode in ("0", "1"):
         monkeypatch.setenv("LTXK_CONV_TAIL", mode)
-        outs[mode] = V.conv3d(x, w, b, True, 0, resid=r)
+        outs[mode] = ops.conv3d(x, w, b, True, 0, resid=r)
         torch.cuda.synchronize()
     assert torch.equal(outs["0"], outs["1"])
     assert float(outs["1"].float().abs().mean()) > 0.05
@@ -388,7 +435,7 @@ def test_conv3d_kw_reuse_kernel_vs_per_tap_kernel(dev, case, monkeypatch):
     in the A/B build): the same products and rounding points summed in another K order -> fp32-order differences only
     (rare single-ulp flips), on every halo mode, widths that do / do not align runs with MFMA blocks, ragged tiles, several
     column tiles, with and without the residual; the tail launch of half tiles gives the same bits as one launch."""
-    from mlx_video_amd import _lib, video_vae as V
+    from mlx_video_amd import _lib, ops
     B, D, H, W, Cin, Cout, causal, pad, res = case
     g = torch.Generator(device=dev).manual_seed(B * 7 + H + W + Cin + Cout)
     x = torch.randn((B, D, H, W, Cin), generator=g, device=dev).to(torch.bfloat16)
@@ -402,7 +449,7 @@ def test_conv3d_kw_reuse_kernel_vs_per_tap_kernel(dev, case, monkeypatch):
                 monkeypatch.delenv(k, raising=False)
             for k, v in env.items():
                 monkeypatch.setenv(k, v)
-            outs[name] = V.conv3d(x, w, b, causal, pad, resid=r)
+            outs[name] = ops.conv3d(x, w, b, causal, pad, resid=r)
             torch.cuda.synchronize()
     assert torch.equal(outs["kw"], outs["kw_no_tail"])
     assert not torch.equal(outs["kw"], outs["per_tap"]) or Cin <= 64, "the kw form did not run (same bits as the per-tap kernel)"
@@ -412,4 +459,4 @@ def test_conv3d_kw_reuse_kernel_vs_per_tap_kernel(dev, case, monkeypatch):
     d = (a - ref).abs()
     assert float((d > 2.0 ** -7 * torch.maximum(a.abs(), ref.abs()).clamp_min(1e-3)).float().mean()) < 1e-3      # > 1 ulp apart: almost never
     # the product library takes the kw form where one column tile spans Cout, the per-tap form otherwise
-    assert torch.equal(V.conv3d(x, w, b, causal, pad, resid=r), outs["kw" if Cout <= 128 else "per_tap"])
+    assert torch.equal(ops.conv3d(x, w, b, causal, pad, resid=r), outs["kw" if Cout <= 128 else "per_tap"])

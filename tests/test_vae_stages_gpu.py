@@ -37,7 +37,7 @@ def cf(x):
 
 
 def test_res_block_128_full_size_stage_budget(dev):
-    from mlx_video_amd import video_vae as V
+    from mlx_video_amd import ops
     p = O.BF16
     C, vol = 128, (33, 128, 128)
     g = torch.Generator().manual_seed(404)
@@ -54,14 +54,14 @@ def test_res_block_128_full_size_stage_budget(dev):
     Wd = {k: v.to(dev) for k, v in W.items()}
     xd = cl(x).to(dev)
     # ---- teacher-forced
-    f0 = V.pixelnorm_act(xd, 1e-8, True)
-    f1 = V.conv3d(cl(t0.to(BF)).to(dev), Wd["b.conv1.conv.weight"], Wd["b.conv1.conv.bias"], False, V.PAD_REFLECT)
-    f2 = V.pixelnorm_act(cl(t1.to(BF)).to(dev), 1e-8, True)
-    f3 = V.conv3d(cl(t2.to(BF)).to(dev), Wd["b.conv2.conv.weight"], Wd["b.conv2.conv.bias"], False, V.PAD_REFLECT, resid=xd)
+    f0 = ops.pixelnorm_act(xd, 1e-8, True)
+    f1 = ops.conv3d(cl(t0.to(BF)).to(dev), Wd["b.conv1.conv.weight"], Wd["b.conv1.conv.bias"], False, ops.PAD_REFLECT)
+    f2 = ops.pixelnorm_act(cl(t1.to(BF)).to(dev), 1e-8, True)
+    f3 = ops.conv3d(cl(t2.to(BF)).to(dev), Wd["b.conv2.conv.weight"], Wd["b.conv2.conv.bias"], False, ops.PAD_REFLECT, resid=xd)
     # ---- chained, as LTX2VideoDecoder runs the block
-    c1 = V.conv3d(f0, Wd["b.conv1.conv.weight"], Wd["b.conv1.conv.bias"], False, V.PAD_REFLECT)
-    c2 = V.pixelnorm_act(c1, 1e-8, True)
-    c3 = V.conv3d(c2, Wd["b.conv2.conv.weight"], Wd["b.conv2.conv.bias"], False, V.PAD_REFLECT, resid=xd)
+    c1 = ops.conv3d(f0, Wd["b.conv1.conv.weight"], Wd["b.conv1.conv.bias"], False, ops.PAD_REFLECT)
+    c2 = ops.pixelnorm_act(c1, 1e-8, True)
+    c3 = ops.conv3d(c2, Wd["b.conv2.conv.weight"], Wd["b.conv2.conv.bias"], False, ops.PAD_REFLECT, resid=xd)
     torch.cuda.synchronize()
     parity.check("vae.stage.res128.pixelnorm_silu_1.teacher_forced", rel_l2(cf(f0), t0), 2e-3)
     parity.check("vae.stage.res128.conv1.teacher_forced", rel_l2(cf(f1), t1), 1e-3)
@@ -75,7 +75,7 @@ def test_res_block_128_full_size_stage_budget(dev):
 
 
 def test_d2s_block_256_to_128_full_size_stage_budget(dev):
-    from mlx_video_amd import video_vae as V
+    from mlx_video_amd import ops
     p = O.BF16
     Ci, vol = 256, (17, 64, 64)
     g = torch.Generator().manual_seed(405)
@@ -87,9 +87,9 @@ def test_d2s_block_256_to_128_full_size_stage_budget(dev):
     t_out = p.r(OV.depth_to_space(t_conv, 2, 2, 2)[:, :, 1:] + xr)
     assert torch.equal(OV.d2s_upsample(x.float(), W, "u", p, False), t_out)
     xd = cl(x).to(dev)
-    f_conv = V.conv3d(xd, W["u.conv.weight"].to(dev), W["u.conv.bias"].to(dev), False, V.PAD_REFLECT)
-    f_out_tf = V.d2s_add(cl(t_conv.to(BF)).to(dev), xd)            # the rearrangement + residual fed the oracle's conv output
-    f_out = V.d2s_add(f_conv, xd)
+    f_conv = ops.conv3d(xd, W["u.conv.weight"].to(dev), W["u.conv.bias"].to(dev), False, ops.PAD_REFLECT)
+    f_out_tf = ops.d2s_add(cl(t_conv.to(BF)).to(dev), xd)            # the rearrangement + residual fed the oracle's conv output
+    f_out = ops.d2s_add(f_conv, xd)
     torch.cuda.synchronize()
     assert f_out.shape == (1, 33, 128, 128, 128)
     parity.check("vae.stage.d2s256.conv.teacher_forced", rel_l2(cf(f_conv), t_conv), 1e-3)
