@@ -1,6 +1,12 @@
 """torch.Tensor -> libltxk C-ABI call shims.  One function per entry point of include/ltxk.h.
 Tensors carry device memory only; all math happens in the HIP kernels.  Every call is queued
-on torch's current HIP stream (so a torch.cuda.graph capture records the whole step)."""
+on torch's current HIP stream (so a torch.cuda.graph capture records the whole step).
+
+The boundary has one rule.  A shim first refuses the argument pairings that need no tensor (a scale without its shift, an
+unknown guider), then hands EVERY tensor operand - outputs, tables and scratch included - to ``_operands``, which checks
+per tensor dtype, shape, layout and alignment and, last, the device; only then is anything allocated or launched.  Sizes
+come from the tensors: an integer a tensor already determines (``ada_combine``'s L,U,K,D, ``flash_attn``'s B,H,Tq,Tk) is
+compared with it and a mismatch refused.  TypeError: dtype; ValueError: shape, layout, alignment; LtxkError: the device."""
 from __future__ import annotations
 
 import ctypes
@@ -16,6 +22,7 @@ from ._lib import AttnArgs, CausalAttnArgs, Conv3dArgs, GemmArgs, GemmGroupedArg
 EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_SILU, EPI_BIAS_GATE_RES, EPI_BIAS_RES, EPI_SCALE_RES = 0, 1, 2, 3, 4, 5
 BF16 = torch.bfloat16
 FP8 = torch.float8_e4m3fn
+F32, I32 = torch.float32, torch.int32
 
 
 class KernelTimer:
@@ -66,44 +73,51 @@ def _p(t: Optional[torch.Tensor]) -> Optional[int]:
     return None if t is None else t.data_ptr()
 
 
-def _req(t: torch.Tensor, dtype, name: str) -> None:
-    if not t.is_cuda:
-        raise _lib.LtxkError(f"{name}: expected a device tensor (the product path has no CPU fallback)")
-    if t.dtype != dtype:
-        raise TypeError(f"{name}: expected {dtype}, got {t.dtype}")
-
-
 def _dims(who: str, name: str, t: torch.Tensor, dtype, rank: int) -> torch.Size:
     """``t.shape`` once its dtype and rank hold: the first two checks of ``_operands``, on their own for the operand a
     shim derives its sizes from."""
+    sh = t.shape
     if t.dtype != dtype:
         raise TypeError(f"{who}: {name} must be {dtype}, got {t.dtype}")
-    if t.dim() != rank:
-        raise ValueError(f"{who}: {name} must have {rank} dimensions, got shape {tuple(t.shape)}")
-    return t.shape
+    if len(sh) != rank:
+        raise ValueError(f"{who}: {name} must have {rank} dimensions, got shape {tuple(sh)}")
+    return sh
 
 
-def _dense_rows(t: torch.Tensor) -> bool:
-    """(..., n, C) rows of a dense (..., n, ld >= C) buffer: unit inner stride, one leading dimension."""
-    st, sh = t.stride(), t.shape
-    return st[-1] == 1 and st[-2] >= sh[-1] and all(st[i] == st[i + 1] * sh[i + 1] for i in range(len(sh) - 2))
+def _dense_rows(t: torch.Tensor, sh, k=True) -> bool:
+    """(..., n, C) rows of a (..., n, ld >= C) buffer with unit inner stride (``sh``: t.shape).  ``k`` True: one leading
+    dimension, the outer dimensions dense; an int: outer strides of their own, each a multiple of k elements (a layer or
+    group stack)."""
+    st = t.stride()
+    n = len(st)
+    if n < 2 or st[-1] != 1 or st[-2] < sh[-1]:
+        return False
+    if k is not True:
+        return not any(s % k for s in st[:-1])
+    return n == 2 or all(st[i] == st[i + 1] * sh[i + 1] for i in range(n - 2))
 
 
 def _operands(who: str, *operands) -> None:
-    """The one operand check of the VAE / upsampler shims.  An operand is ``(name, tensor or None, dtype, shape, align)``:
-    ``shape`` the exact shape the call derives (an int: the rank alone), ``align`` the byte alignment the C entry or its
-    kernel's vector accesses demand; a sixth item ``True`` allows a leading dimension (``_dense_rows``) in place of
-    contiguity.  Per tensor: dtype, shape, layout, alignment - and only when every operand has passed those, the device, so
-    that each of the other refusals shows on CPU tensors too.  Nothing is launched on a tensor it refuses.
-    One compound test per operand on the way through (this runs in front of every launch); ``_refuse`` words the error."""
+    """The one operand check of every shim.  An operand is ``(name, tensor or None, dtype, shape, align)``: ``shape`` the
+    exact shape the call derives - an int: the rank alone; a negative entry ``-n``: at least n along that dimension (``sumsq``
+    (M, >= cols/64), V^T (B, D, ld >= T)) - and ``align`` the byte alignment the C entry or its kernel's vector accesses
+    demand (up to 4 bytes it is the element's own, which torch guarantees, and is not looked at).  The tensor is contiguous
+    unless a sixth item allows more (``_dense_rows``): ``True`` a leading dimension, an int k outer strides of their own that
+    are multiples of k elements.  Per tensor: dtype, shape, layout, alignment - and only when every operand has passed those,
+    the device, so that each of the other refusals shows on CPU tensors too.  Nothing is launched on a tensor it refuses.
+    One compound test per operand on the way through (this runs in front of every launch, and a forward of small launches
+    waits for it: each tensor property is read once, a minimum in the last dimension alone - the common one - has a
+    comparison of its own in front of the general one); ``_refuse`` words the error."""
     host = None
     for op in operands:
         t = op[1]
         if t is None:
             continue
-        shape = op[3]
-        if t.dtype != op[2] or (t.dim() != shape if shape.__class__ is int else t.shape != shape) or \
-                not (t.is_contiguous() if len(op) == 5 else _dense_rows(t)) or t.data_ptr() % op[4]:
+        shape, sh = op[3], t.shape
+        if t.dtype != op[2] or (len(sh) != shape if shape.__class__ is int else sh != shape and (
+                (shape[-1] >= 0 or sh[:-1] != shape[:-1] or sh[-1] < -shape[-1]) and
+                (len(sh) != len(shape) or any(s != n if n >= 0 else s < -n for s, n in zip(sh, shape))))) or \
+                not (t.is_contiguous() or len(op) > 5 and _dense_rows(t, sh, op[5])) or (op[4] > 4 and t.data_ptr() % op[4]):
             _refuse(who, *op)
         if host is None and not t.is_cuda:
             host = op[0]
@@ -111,16 +125,28 @@ def _operands(who: str, *operands) -> None:
         raise _lib.LtxkError(f"{who}: {host} must be a device tensor (the product path has no CPU fallback)")
 
 
-def _refuse(who: str, name: str, t: torch.Tensor, dtype, shape, align: int, ld: bool = False) -> None:
+def _refuse(who: str, name: str, t: torch.Tensor, dtype, shape, align: int, ld=False) -> None:
     """Raises for the first of ``_operands``' per-tensor checks that ``t`` fails, in their order."""
     exact = not isinstance(shape, int)
     _dims(who, name, t, dtype, len(shape) if exact else shape)
-    if exact and t.shape != shape:
-        raise ValueError(f"{who}: {name} must be {tuple(shape)}, got {tuple(t.shape)}")
-    if not (_dense_rows(t) if ld else t.is_contiguous()):
-        raise ValueError(f"{who}: {name} must be {'rows with unit inner stride' if ld else 'contiguous'}, got shape "
-                         f"{tuple(t.shape)} with strides {t.stride()}")
+    if exact and any(s != n if n >= 0 else s < -n for s, n in zip(t.shape, shape)):
+        want = ", ".join(str(n) if n >= 0 else f">={-n}" for n in shape)
+        raise ValueError(f"{who}: {name} must be ({want}{',' if len(shape) == 1 else ''}), got {tuple(t.shape)}")
+    if not (t.is_contiguous() or ld and _dense_rows(t, t.shape, ld)):
+        how = "contiguous" if ld is False else "rows with unit inner stride" if ld is True else \
+            f"rows with unit inner stride, outer strides multiples of {ld}"
+        raise ValueError(f"{who}: {name} must be {how}, got shape {tuple(t.shape)} with strides {t.stride()}")
     raise ValueError(f"{who}: {name} must be {align}-byte aligned")
+
+
+def _table(who: str, name: str, t: Optional[torch.Tensor], D: int, stride: int) -> tuple:
+    """The shape item of a table read as p[row * stride + d] (modulation, gate): (its own rows, D), once a view of more than
+    one row has them ``stride`` elements apart."""
+    if t is None or t.dim() != 2:
+        return (-1, D)
+    if t.stride(0) != stride and t.shape[0] > 1:
+        raise ValueError(f"{who}: the rows of {name} lie {t.stride(0)} elements apart, the stride passed for it is {stride}")
+    return (t.shape[0], D)
 
 
 GEMM_WORKSPACE_BYTES = 64 << 20
@@ -155,14 +181,16 @@ def gemm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], *, epil
          out2: Optional[torch.Tensor] = None, n_split: int = 0, sumsq: Optional[torch.Tensor] = None,
          split_k: bool = True, w_scale: Optional[torch.Tensor] = None,
          a_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """out = epi(a @ w.T + bias).  a (M,K) (row stride may exceed K), w (N,K) contiguous.
+    """out = epi(a @ w.T + bias).  a (M,K) (row stride may exceed K), w (N,K) contiguous, bias (N); out / resid (M,N) rows,
+    gate (rows,N) read as gate[gate_row[m] * gate_stride + n] with gate_row (M) int32.
     ``w`` may be ``torch.float8_e4m3fn`` (ltxk_gemm_w8: the panel is read as fp8 and widened in registers; with no ``w_scale``
     the result equals the bf16 call on ``w.to(bfloat16)`` bit for bit); ``w_scale`` (N) fp32 then multiplies the accumulator
     per output channel before the bias.  A bf16 ``w`` takes ltxk_gemm_bf16 and no ``w_scale``.
-    ``n_split``/``out2``: columns >= n_split go transposed per batch (out_tokens_per_batch tokens) to out2
-    (B, N-n_split, ld).  ``sumsq``: (M, >= cols/64) fp32, receives the per-64-column sums of squares of the stored
-    row-major outputs.  ``split_k=False``: no split-K scratch is offered, so the launch is single-pass (or big-tile) and
-    a row's bits do not depend on M; with it the library may split K at M <= SPLITK_MAX_M (``gemm_plan`` tells).
+    ``out_tokens_per_batch`` = T: ``out`` is (M/T, N, ld >= T), written transposed per batch.  ``n_split``/``out2``: ``out`` is
+    (M, n_split) and columns >= n_split go transposed to out2 (M/T, N-n_split, ld >= T).  ``sumsq``: (M, >= cols/64) fp32,
+    receives the per-64-column sums of squares of the stored row-major outputs.  ``split_k=False``: no split-K scratch is
+    offered, so the launch is single-pass (or big-tile) and a row's bits do not depend on M; with it the library may split K
+    at M <= SPLITK_MAX_M (``gemm_plan`` tells).
     A ``float8_e4m3fn`` ``a`` together with ``a_scale`` (M) fp32 - what ``quant_rows_fp8`` returns - takes ltxk_gemm_w8a8: fp8
     operands on the fp8 matrix pipe, acc * a_scale[m] * w_scale[n] in front of the bias.  It needs an fp8 ``w``, K % 128 == 0
     and 16-byte aligned rows of ``a``; it is always single-pass (``split_k`` is ignored)."""
@@ -172,33 +200,25 @@ def gemm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], *, epil
         raise TypeError("gemm: a float8_e4m3fn `a` and `a_scale` go together (quant_rows_fp8 gives both)")
     if a8 and not w8:
         raise TypeError(f"gemm: float8_e4m3fn activations need a float8_e4m3fn weight, got {w.dtype}")
-    if a8:
-        if a_scale.dtype != torch.float32:
-            raise TypeError(f"gemm.a_scale: expected torch.float32, got {a_scale.dtype}")
-        if a_scale.shape != (a.shape[0],) or not a_scale.is_contiguous():
-            raise ValueError(f"gemm: a_scale must be a contiguous ({a.shape[0]},) vector, got {tuple(a_scale.shape)}")
-    _req(a, FP8 if a8 else BF16, "gemm.a"); _req(w, FP8 if w8 else BF16, "gemm.w")
-    if a8:
-        _req(a_scale, torch.float32, "gemm.a_scale")
-    if w_scale is not None:
-        if not w8:
-            raise TypeError("gemm: w_scale goes with a float8_e4m3fn weight")
-        _req(w_scale, torch.float32, "gemm.w_scale")
-        if w_scale.shape != (w.shape[0],) or not w_scale.is_contiguous():
-            raise ValueError(f"gemm: w_scale must be a contiguous ({w.shape[0]},) vector, got {tuple(w_scale.shape)}")
-    M, K = a.shape
-    N = w.shape[0]
-    if w.shape[1] != K or not w.is_contiguous() or a.stride(1) != 1:
-        raise ValueError(f"gemm: bad operand layout a{tuple(a.shape)} w{tuple(w.shape)}")
+    if w_scale is not None and not w8:
+        raise TypeError("gemm: w_scale goes with a float8_e4m3fn weight")
+    if n_split and out2 is None:
+        raise ValueError("gemm: split output needs a bf16 `out2`")
+    if out is None and out_tokens_per_batch:
+        raise ValueError("gemm: transposed output needs a preallocated `out`")
+    if not n_split:
+        out2 = None
+    adt, wdt, T = FP8 if a8 else BF16, FP8 if w8 else BF16, out_tokens_per_batch
+    M, K = _dims("gemm", "a", a, adt, 2)
+    N = _dims("gemm", "w", w, wdt, 2)[0]
+    cols, nb = n_split or N, M // T if T else 0
+    _operands("gemm", ("a", a, adt, 2, 16, True), ("w", w, wdt, (N, K), 16), ("bias", bias, BF16, (N,), 8),
+              ("out", out, BF16, (nb, N, -T) if T and not n_split else (M, cols), 8, True), ("resid", resid, BF16, (M, N), 8, True),
+              ("gate", gate, BF16, _table("gemm", "gate", gate, N, gate_stride), 8, True), ("gate_row", gate_row, I32, (M,), 4),
+              ("out2", out2, BF16, (nb, N - n_split, -T), 8, True), ("sumsq", sumsq, F32, (M, -(cols // 64)), 4, True),
+              ("w_scale", w_scale, F32, (N,), 4), ("a_scale", a_scale, F32, (M,), 4))
     if out is None:
-        if out_tokens_per_batch:
-            raise ValueError("gemm: transposed output needs a preallocated `out`")
         out = torch.empty((M, N), dtype=BF16, device=a.device)
-    if n_split:
-        if out2 is None or out2.dtype != BF16:
-            raise ValueError("gemm: split output needs a bf16 `out2`")
-    if sumsq is not None and (sumsq.dtype != torch.float32 or sumsq.stride(-1) != 1):
-        raise TypeError("gemm: sumsq must be float32 with unit inner stride")
     args = GemmArgs()
     args.A, args.W, args.bias, args.out = _p(a), _p(w), _p(bias), _p(out)
     args.resid, args.gate, args.gate_row = _p(resid), _p(gate), _p(gate_row)
@@ -291,18 +311,12 @@ def quant_rows_fp8(a: torch.Tensor, out: Optional[Tuple[torch.Tensor, torch.Tens
     """ltxk_quant_rows_fp8: a (M,K) bf16 (row stride may exceed K) -> (a8 (M,K) float8_e4m3fn, a_scale (M) fp32) with
     a ~= a8 * a_scale[:, None]: per row scale = max(max|a|, 2^-64) / 448 and a8 = e4m3(a / scale), round to nearest even.
     ``out=(a8, a_scale)``: write into these (a8 may be a strided view; a_scale contiguous)."""
-    _req(a, BF16, "quant_rows_fp8.a")
-    if a.dim() != 2 or a.stride(1) != 1:
-        raise ValueError(f"quant_rows_fp8: expected a (M,K) matrix with unit inner stride, got {tuple(a.shape)}")
-    M, K = a.shape
+    M, K = _dims("quant_rows_fp8", "a", a, BF16, 2)
+    a8, sc = out if out is not None else (None, None)
+    _operands("quant_rows_fp8", ("a", a, BF16, 2, 16, True), ("out[0]", a8, FP8, (M, K), 8, True), ("out[1]", sc, F32, (M,), 4))
     if out is None:
         a8 = torch.empty((M, K), dtype=FP8, device=a.device)
         sc = torch.empty((M,), dtype=torch.float32, device=a.device)
-    else:
-        a8, sc = out
-        _req(a8, FP8, "quant_rows_fp8.out[0]"); _req(sc, torch.float32, "quant_rows_fp8.out[1]")
-        if tuple(a8.shape) != (M, K) or a8.stride(1) != 1 or tuple(sc.shape) != (M,) or not sc.is_contiguous():
-            raise ValueError(f"quant_rows_fp8: out must be ((M,K) fp8 with unit inner stride, (M,) fp32), got {tuple(a8.shape)}, {tuple(sc.shape)}")
     with _timed("quant_rows_fp8", 0.0, 3.0 * M * K):
         check(_lib.load().ltxk_quant_rows_fp8(_p(a), a.stride(0), _p(a8), a8.stride(0), _p(sc), M, K, _stream()), "ltxk_quant_rows_fp8")
     return a8, sc
@@ -326,19 +340,16 @@ def gemm_grouped(a: torch.Tensor, w_table: torch.Tensor, bias_table: Optional[to
                  sumsq: Optional[torch.Tensor] = None) -> torch.Tensor:
     """ltxk_gemm_bf16_grouped: for every group g, ``gemm(a, W[g], bias[g], out=out[g], out2=out2[g], n_split=...,
     sumsq=sumsq[g], split_k=False)`` - the same bits - as ONE persistent launch.  a (M,K); w_table / bias_table:
-    ``pointer_table`` of G contiguous (N,K) panels / (N) rows; out (G,M,n_split), out2 (G,B,N-n_split,ld), sumsq
-    (G,M,>=n_split/64) fp32, each with contiguous inner dimensions."""
-    _req(a, BF16, "gemm_grouped.a"); _req(out, BF16, "gemm_grouped.out"); _req(out2, BF16, "gemm_grouped.out2")
-    _req(w_table, torch.int64, "gemm_grouped.w_table")
-    M, K = a.shape
-    G = w_table.numel()
-    if a.stride(1) != 1 or out.dim() != 3 or out2.dim() != 4 or out.shape[0] != G or out2.shape[0] != G or \
-            out.stride(-1) != 1 or out2.stride(-1) != 1 or (bias_table is not None and bias_table.numel() != G):
-        raise ValueError(f"gemm_grouped: bad operand layout a{tuple(a.shape)} out{tuple(out.shape)} out2{tuple(out2.shape)} G={G}")
-    if out2.stride(1) != out2.shape[2] * out2.stride(2) or out.shape[1] != M:
-        raise ValueError("gemm_grouped: out2 must be (G,B,N-n_split,ld) with contiguous batches, out (G,M,n_split)")
-    if sumsq is not None and (sumsq.dtype != torch.float32 or sumsq.stride(-1) != 1 or sumsq.dim() != 3 or sumsq.shape[0] != G):
-        raise TypeError("gemm_grouped: sumsq must be (G,M,>=n_split/64) float32 with unit inner stride")
+    ``pointer_table`` of G contiguous (N,K) panels / (N) rows; out (G,M,n_split), out2 (G,B,N-n_split,ld >= tokens), sumsq
+    (G,M,>=n_split/64) fp32, each with unit inner stride, a group stride of its own and, in out2, dense batches."""
+    M, K = _dims("gemm_grouped", "a", a, BF16, 2)
+    G = _dims("gemm_grouped", "w_table", w_table, torch.int64, 1)[0]
+    T = out_tokens_per_batch
+    if out2.dim() == 4 and out2.stride(1) != out2.shape[2] * out2.stride(2):
+        raise ValueError(f"gemm_grouped: out2 must be (G,B,N-n_split,ld) with contiguous batches, got strides {out2.stride()}")
+    _operands("gemm_grouped", ("a", a, BF16, 2, 16, True), ("w_table", w_table, torch.int64, 1, 8), ("bias_table", bias_table, torch.int64, (G,), 8),
+              ("out", out, BF16, (G, M, n_split), 8, 4), ("out2", out2, BF16, (G, M // T if T else 0, N - n_split, -T), 8, 4),
+              ("sumsq", sumsq, F32, (G, M, -(n_split // 64)), 4, 1))
     args = _grouped_args(G, M, N, K, n_split, out_tokens_per_batch)
     args.A, args.W, args.bias = _p(a), _p(w_table), _p(bias_table)
     args.out, args.out2, args.sumsq = _p(out), _p(out2), _p(sumsq)
@@ -379,20 +390,26 @@ def flash_attn(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, out: torch.Te
                Tq: int, Tk: int, scale: float, q_sumsq: Optional[torch.Tensor] = None,
                q_norm_weight: Optional[torch.Tensor] = None, cos: Optional[torch.Tensor] = None,
                sin: Optional[torch.Tensor] = None, eps: float = 1e-6, tail_split: bool = True) -> torch.Tensor:
-    """q (B*Tq, >=H*128) view, k (B*Tk, ...) view, vt (B, H*128, ldvt), out (B*Tq, H*128).  With ``q_sumsq``
-    (B*Tq, >= H*2) the raw q projection is normalised (q_norm_weight) and rotated (cos/sin (H,Tq,64)) inside the kernel.
+    """q (B*Tq, H*128) rows, k (B*Tk, H*128) rows, vt (B, H*128, ld >= Tk), out (B*Tq, H*128) rows.  With ``q_sumsq``
+    (B*Tq, >= H*2) the raw q projection is normalised (q_norm_weight (H*128)) and rotated (cos/sin (H,Tq,64)) inside the
+    kernel; without it those three are not read.
     ``tail_split=False``: LTXK_ATTN_NO_TAIL_SPLIT (results independent of how many (batch, head) pairs share the launch)."""
+    if q_sumsq is None:
+        q_norm_weight = cos = sin = None
+    elif q_norm_weight is None or (cos is None) != (sin is None):
+        raise ValueError("flash_attn: q_sumsq needs q_norm_weight, and cos and sin both or neither")
+    D = H * 128
+    _operands("flash_attn", ("q", q, BF16, (B * Tq, D), 16, True), ("k", k, BF16, (B * Tk, D), 16, True),
+              ("vt", vt, BF16, (B, D, -Tk), 16, True), ("out", out, BF16, (B * Tq, D), 16, True),
+              ("q_sumsq", q_sumsq, F32, (B * Tq, -(H * 2)), 16, True),
+              ("q_norm_weight", q_norm_weight, BF16, (1, D) if q_sumsq is not None and q_norm_weight.dim() == 2 else (D,), 16),
+              ("cos", cos, F32, (H, Tq, 64), 16), ("sin", sin, F32, (H, Tq, 64), 16))
     a = AttnArgs()
     a.flags = 0 if tail_split else _lib.ATTN_NO_TAIL_SPLIT
     a.q, a.k, a.vt, a.out = _p(q), _p(k), _p(vt), _p(out)
     a.ldq, a.ldk, a.ldvt, a.ldo = q.stride(0), k.stride(0), vt.stride(-2), out.stride(0)
     a.B, a.H, a.Tq, a.Tk, a.scale = B, H, Tq, Tk, scale
     if q_sumsq is not None:
-        _req(q_norm_weight, BF16, "flash_attn.q_norm_weight")
-        if q_sumsq.dtype != torch.float32 or q_sumsq.stride(-1) != 1:
-            raise TypeError("flash_attn: q_sumsq must be float32 with unit inner stride")
-        if cos is not None and (cos.dtype != torch.float32 or not cos.is_contiguous() or not sin.is_contiguous()):
-            raise TypeError("flash_attn: cos/sin must be contiguous float32 (H,Tq,64)")
         a.q_sumsq, a.q_sumsq_ld, a.q_sumsq_n = _p(q_sumsq), q_sumsq.stride(0), H * 2
         a.q_norm_weight, a.cos, a.sin, a.eps = _p(q_norm_weight), _p(cos), _p(sin), eps
     with _timed("flash_attn", 4.0 * B * H * Tq * Tk * 128, 2.0 * B * H * 128 * (2 * Tq + 2 * Tk)):
@@ -438,37 +455,46 @@ def flash_attn_plan(B: int, H: int, Tq: int, Tk: int, *, cus: int, tail_split: b
                     pl.xcd_order)
 
 
+def _modulation(who: str, M: int, D: int, scale, shift, mod_stride: int, mod_row) -> tuple:
+    """The modulation operands of a row norm over (M,D): scale / shift are rows of a (rows, D) table that lie ``mod_stride``
+    apart, picked per token by mod_row (M) int32 (None: row 0)."""
+    if (scale is None) != (shift is None):
+        raise ValueError(f"{who}: scale and shift must both be given or both be None")
+    return (("scale", scale, BF16, _table(who, "scale", scale, D, mod_stride), 16, True),
+            ("shift", shift, BF16, _table(who, "shift", shift, D, mod_stride), 16, True), ("mod_row", mod_row, I32, (M,), 4))
+
+
 def rmsnorm_modulate(x: torch.Tensor, eps: float, scale: Optional[torch.Tensor] = None,
                      shift: Optional[torch.Tensor] = None, mod_stride: int = 0,
                      mod_row: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
                      sumsq: Optional[torch.Tensor] = None, scale_is_one_plus: bool = False) -> torch.Tensor:
-    """``sumsq`` (M, D/64) fp32: the rows' sums of squares in 64-column partials (gemm(..., sumsq=)); without it the
+    """x, out (M,D) contiguous; the modulation of row m is scale / shift[mod_row[m] * mod_stride + d].
+    ``sumsq`` (M, >= D/64) fp32: the rows' sums of squares in 64-column partials (gemm(..., sumsq=)); without it the
     kernel reduces the row itself.  ``scale_is_one_plus``: scale holds bf16(1+scale) (needs sumsq)."""
-    _req(x, BF16, "rmsnorm_modulate.x")
-    M, D = x.shape
+    if scale_is_one_plus and sumsq is None:
+        raise ValueError("rmsnorm_modulate: scale_is_one_plus needs sumsq")
+    M, D = _dims("rmsnorm_modulate", "x", x, BF16, 2)
+    _operands("rmsnorm_modulate", ("x", x, BF16, 2, 16), ("out", out, BF16, (M, D), 16),
+              *_modulation("rmsnorm_modulate", M, D, scale, shift, mod_stride, mod_row), ("sumsq", sumsq, F32, (M, -(D // 64)), 4, True))
     if out is None:
         out = torch.empty_like(x)
-    if sumsq is not None:
-        if sumsq.dtype != torch.float32 or sumsq.stride(-1) != 1 or sumsq.shape[0] != M:
-            raise TypeError("rmsnorm_modulate: sumsq must be (M, >= D/64) float32")
-        with _timed("rmsnorm_modulate", 0.0, 4.0 * M * D):
+    with _timed("rmsnorm_modulate", 0.0, 4.0 * M * D):
+        if sumsq is not None:
             check(_lib.load().ltxk_rmsnorm_modulate_ss(_p(x), _p(out), M, D, eps, _p(sumsq), sumsq.stride(0), D // 64, _p(scale),
                                                        _p(shift), mod_stride, _p(mod_row), int(scale_is_one_plus), _stream()),
                   "ltxk_rmsnorm_modulate_ss")
-        return out
-    if scale_is_one_plus:
-        raise ValueError("rmsnorm_modulate: scale_is_one_plus needs sumsq")
-    with _timed("rmsnorm_modulate", 0.0, 4.0 * M * D):
-        check(_lib.load().ltxk_rmsnorm_modulate(_p(x), _p(out), M, D, eps, _p(scale), _p(shift), mod_stride,
-                                                _p(mod_row), _stream()), "ltxk_rmsnorm_modulate")
+        else:
+            check(_lib.load().ltxk_rmsnorm_modulate(_p(x), _p(out), M, D, eps, _p(scale), _p(shift), mod_stride,
+                                                    _p(mod_row), _stream()), "ltxk_rmsnorm_modulate")
     return out
 
 
 def layernorm_modulate(x: torch.Tensor, eps: float, scale: Optional[torch.Tensor] = None,
                        shift: Optional[torch.Tensor] = None, mod_stride: int = 0,
                        mod_row: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    _req(x, BF16, "layernorm_modulate.x")
-    M, D = x.shape
+    M, D = _dims("layernorm_modulate", "x", x, BF16, 2)
+    _operands("layernorm_modulate", ("x", x, BF16, 2, 16), ("out", out, BF16, (M, D), 16),
+              *_modulation("layernorm_modulate", M, D, scale, shift, mod_stride, mod_row))
     if out is None:
         out = torch.empty_like(x)
     check(_lib.load().ltxk_layernorm_modulate(_p(x), _p(out), M, D, eps, _p(scale), _p(shift), mod_stride,
@@ -478,21 +504,21 @@ def layernorm_modulate(x: torch.Tensor, eps: float, scale: Optional[torch.Tensor
 
 def qknorm_rope(buf: torch.Tensor, nseg: int, D: int, weight: torch.Tensor, cos: Optional[torch.Tensor],
                 sin: Optional[torch.Tensor], T: int, H: int, eps: float, sumsq: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """In place on the first nseg*D columns of buf (M, ld).  ``sumsq`` (M, >= nseg*D/64) fp32: precomputed partial
-    sums of squares of those columns (gemm(..., sumsq=))."""
-    _req(buf, BF16, "qknorm_rope.buf")
-    if cos is not None and (cos.dtype != torch.float32 or not cos.is_contiguous()):
-        raise TypeError("qknorm_rope: cos/sin must be contiguous float32 (H,T,64)")
-    if sumsq is not None:
-        if sumsq.dtype != torch.float32 or sumsq.stride(-1) != 1:
-            raise TypeError("qknorm_rope: sumsq must be float32 with unit inner stride")
-        with _timed("qknorm_rope", 0.0, 4.0 * buf.shape[0] * nseg * D + (8.0 * buf.shape[0] * D // 2 if cos is not None else 0.0)):
-            check(_lib.load().ltxk_qknorm_rope_ss(_p(buf), buf.stride(0), buf.shape[0], nseg, D, _p(weight), _p(cos), _p(sin),
+    """In place on the first nseg*D columns of buf (M, ld), D = 128*H: weight (nseg,D) (or flat), cos / sin (H,T,64) fp32 or
+    both None.  ``sumsq`` (M, >= nseg*D/64) fp32: precomputed partial sums of squares of those columns (gemm(..., sumsq=))."""
+    if (cos is None) != (sin is None) or D != 128 * H:
+        raise ValueError(f"qknorm_rope: cos and sin go together, and D = {D} must be 128 * H = {128 * H}")
+    M, ld = _dims("qknorm_rope", "buf", buf, BF16, 2)
+    _operands("qknorm_rope", ("buf", buf if ld == nseg * D else buf[:, :nseg * D], BF16, (M, nseg * D), 16, True),
+              ("weight", weight, BF16, (nseg, D) if weight.dim() == 2 else (nseg * D,), 16), ("cos", cos, F32, (H, T, 64), 16),
+              ("sin", sin, F32, (H, T, 64), 16), ("sumsq", sumsq, F32, (M, -(nseg * D // 64)), 4, True))
+    with _timed("qknorm_rope", 0.0, 4.0 * M * nseg * D + (8.0 * M * D // 2 if cos is not None else 0.0)):
+        if sumsq is not None:
+            check(_lib.load().ltxk_qknorm_rope_ss(_p(buf), buf.stride(0), M, nseg, D, _p(weight), _p(cos), _p(sin),
                                                   T, H, eps, _p(sumsq), sumsq.stride(0), _stream()), "ltxk_qknorm_rope_ss")
-        return buf
-    with _timed("qknorm_rope", 0.0, 4.0 * buf.shape[0] * nseg * D + (8.0 * buf.shape[0] * D // 2 if cos is not None else 0.0)):
-        check(_lib.load().ltxk_qknorm_rope(_p(buf), buf.stride(0), buf.shape[0], nseg, D, _p(weight), _p(cos), _p(sin),
-                                           T, H, eps, _stream()), "ltxk_qknorm_rope")
+        else:
+            check(_lib.load().ltxk_qknorm_rope(_p(buf), buf.stride(0), M, nseg, D, _p(weight), _p(cos), _p(sin),
+                                               T, H, eps, _stream()), "ltxk_qknorm_rope")
     return buf
 
 
@@ -500,11 +526,8 @@ def qknorm_grouped(buf: torch.Tensor, weight: torch.Tensor, H: int, eps: float, 
     """ltxk_qknorm_grouped_ss: q/k RMSNorm without rotation, in place on buf (G,M,D) with weight row g of the (G,D) table
     and the row statistics sumsq (G,M,>=D/64) of ``gemm_grouped`` - the bits of G ``qknorm_rope(buf[g], 1, D, weight[g],
     None, None, ..., sumsq=sumsq[g])`` calls, in one launch."""
-    _req(buf, BF16, "qknorm_grouped.buf"); _req(weight, BF16, "qknorm_grouped.weight"); _req(sumsq, torch.float32, "qknorm_grouped.sumsq")
-    G, M, D = buf.shape
-    if buf.stride(2) != 1 or sumsq.dim() != 3 or sumsq.stride(2) != 1 or sumsq.shape[:2] != buf.shape[:2] or \
-            tuple(weight.shape) != (G, D) or not weight.is_contiguous():
-        raise ValueError(f"qknorm_grouped: bad operand layout buf{tuple(buf.shape)} weight{tuple(weight.shape)} sumsq{tuple(sumsq.shape)}")
+    G, M, D = _dims("qknorm_grouped", "buf", buf, BF16, 3)
+    _operands("qknorm_grouped", ("buf", buf, BF16, 3, 16, 8), ("weight", weight, BF16, (G, D), 16), ("sumsq", sumsq, F32, (G, M, -(D // 64)), 4, 1))
     with _timed("qknorm_rope", 0.0, 4.0 * G * M * D):
         check(_lib.load().ltxk_qknorm_grouped_ss(_p(buf), buf.stride(0), buf.stride(1), G, M, D, _p(weight), H, eps, _p(sumsq),
                                                  sumsq.stride(0), sumsq.stride(1), _stream()), "ltxk_qknorm_grouped_ss")
@@ -512,7 +535,8 @@ def qknorm_grouped(buf: torch.Tensor, weight: torch.Tensor, H: int, eps: float, 
 
 
 def timestep_embed(t: torch.Tensor, dim: int = 256, mult: float = 1.0) -> torch.Tensor:
-    _req(t, BF16, "timestep_embed.t")
+    """t: U bf16 timesteps, contiguous -> (U, dim)."""
+    _operands("timestep_embed", ("t", t, BF16, t.dim(), 2))
     out = torch.empty((t.numel(), dim), dtype=BF16, device=t.device)
     check(_lib.load().ltxk_timestep_embed(_p(t), _p(out), t.numel(), dim, mult, _stream()), "ltxk_timestep_embed")
     return out
@@ -520,8 +544,8 @@ def timestep_embed(t: torch.Tensor, dim: int = 256, mult: float = 1.0) -> torch.
 
 def rope_table(positions: torch.Tensor, freq: torch.Tensor, H: int, dim: int, max_pos) -> tuple:
     """positions (3,T,2) fp32, freq (n_freq) fp32 -> cos, sin (H,T,dim/2/H) fp32."""
-    _req(positions, torch.float32, "rope_table.positions"); _req(freq, torch.float32, "rope_table.freq")
-    T = positions.shape[1]
+    T = _dims("rope_table", "positions", positions, F32, 3)[1]
+    _operands("rope_table", ("positions", positions, F32, (3, T, 2), 4), ("freq", freq, F32, 1, 4))
     per_head = dim // 2 // H
     cos = torch.empty((H, T, per_head), dtype=torch.float32, device=positions.device)
     sin = torch.empty_like(cos)
@@ -533,25 +557,27 @@ def rope_table(positions: torch.Tensor, freq: torch.Tensor, H: int, dim: int, ma
 
 def ada_combine(table: torch.Tensor, ada: torch.Tensor, L: int, U: int, K: int, D: int, one_plus_mask: int = 0) -> torch.Tensor:
     """table (L,K,D), ada (U,K*D) -> (L,U,K,D); rows k with bit k of one_plus_mask set hold bf16(1 + value)."""
-    _req(table, BF16, "ada_combine.table"); _req(ada, BF16, "ada_combine.ada")
+    _operands("ada_combine", ("table", table, BF16, (L, K, D), 16), ("ada", ada, BF16, (U, K * D), 16))
     out = torch.empty((L, U, K, D), dtype=BF16, device=ada.device)
     check(_lib.load().ltxk_ada_combine(_p(table), _p(ada), _p(out), L, U, K, D, one_plus_mask, _stream()), "ltxk_ada_combine")
     return out
 
 
 def silu(x: torch.Tensor) -> torch.Tensor:
-    _req(x, BF16, "silu.x")
+    _operands("silu", ("x", x, BF16, x.dim(), 16))
     out = torch.empty_like(x)
     check(_lib.load().ltxk_silu(_p(x), _p(out), x.numel(), _stream()), "ltxk_silu")
     return out
 
 
 def latent_to_tokens(latent: torch.Tensor, rep: int = 1) -> torch.Tensor:
-    """(B,C,F,H,W) or (B,C,S) -> (rep*B,S,C)."""
-    _req(latent, BF16, "latent_to_tokens.latent")
+    """(B,C,F,H,W) or (B,C,S) -> (rep*B,S,C); a latent that is not contiguous is copied first."""
+    if latent.dim() < 3:
+        raise ValueError(f"latent_to_tokens: latent must be (B,C,...), got {tuple(latent.shape)}")
     B, C = latent.shape[:2]
     S = latent.numel() // (B * C)
     lat = latent.contiguous()
+    _operands("latent_to_tokens", ("latent", lat, BF16, lat.dim(), 2))
     out = torch.empty((rep * B, S, C), dtype=BF16, device=latent.device)
     check(_lib.load().ltxk_latent_to_tokens(_p(lat), _p(out), B, C, S, rep, _stream()), "ltxk_latent_to_tokens")
     return out
@@ -561,9 +587,12 @@ GUIDER_IDS = {"cfg_star": _lib.GUIDER_CFG_STAR, "apg": _lib.GUIDER_APG}
 GUIDER_RECORD_FLOATS = _lib.GUIDER_RECORD_FLOATS
 
 
-def _step_tail_args(who: str, v_pos, v_neg, v_pert, latent, guider: str, eta, norm_threshold, clean, mask_tok, sigmas_dev):
+def _step_tail_args(who: str, v_pos, v_neg, v_pert, latent, guider: str, eta, norm_threshold, clean, mask_tok, sigmas_dev, more):
     """The one validator of the step-tail family, and the input fields it checked in the struct of the entry that runs
-    ``guider``: a StepArgs for "cfg", a GuiderArgs for "cfg_star" / "apg".  Nothing is launched on a tensor it refuses."""
+    ``guider``: a StepArgs for "cfg", a GuiderArgs for "cfg_star" / "apg".  ``more(B, C, S)``: the entry's own operands (out,
+    record, workspace), checked in the same ``_operands`` call.  v_* are (B,S,C), mask_tok (B,S), sigmas_dev (2,); latent,
+    clean and out are (B,C,...) volumes that the kernels index as dense (B,C,S) arrays and that callers pass in the
+    latent's own 5-D shape or flattened, so they are held to the element count B*C*S, not to one shape."""
     if guider != "cfg":
         if guider not in GUIDER_IDS:
             raise ValueError(f"{who}: unknown guider {guider!r} (expected 'cfg' or one of {sorted(GUIDER_IDS)})")
@@ -576,18 +605,13 @@ def _step_tail_args(who: str, v_pos, v_neg, v_pert, latent, guider: str, eta, no
             raise ValueError(f"{who}: v_neg is required (the guider compares the positive with the negative prediction)")
     if v_pos is None or (clean is None) != (mask_tok is None):
         raise ValueError(f"{who}: v_pos is required; clean and mask_tok must both be given or both be None")
+    if latent.dim() < 2:
+        raise ValueError(f"{who}: latent must be (B,C,...), got {tuple(latent.shape)}")
     B, C = latent.shape[:2]
     S = latent.numel() // max(B * C, 1)
-    given = [w for w in (("latent", latent, BF16, B * C * S, "(B,C,...)"), ("v_pos", v_pos, BF16, B * S * C, "(B,S,C)"),
-                         ("v_neg", v_neg, BF16, B * S * C, "(B,S,C)"), ("v_pert", v_pert, BF16, B * S * C, "(B,S,C)"),
-                         ("clean", clean, BF16, B * C * S, "(B,C,S)"), ("mask_tok", mask_tok, torch.float32, B * S, "(B,S)"),
-                         ("sigmas_dev", sigmas_dev, torch.float32, 2, "(2,)")) if w[1] is not None]
-    for name, t, dtype, n, shape in given:          # the kernels index every tensor as a dense array of exactly this size
-        if t.numel() != n or not t.is_contiguous():
-            raise ValueError(f"{who}: {name} must be a contiguous {shape} tensor of {n} elements (B,C,S = {B},{C},{S}), "
-                             f"got {tuple(t.shape)} with strides {tuple(t.stride())}")
-    for name, t, dtype, n, shape in given:
-        _req(t, dtype, f"{who}.{name}")
+    _operands(who, ("latent", latent, BF16, latent.dim(), 2), ("v_pos", v_pos, BF16, (B, S, C), 16), ("v_neg", v_neg, BF16, (B, S, C), 16),
+              ("v_pert", v_pert, BF16, (B, S, C), 16), ("clean", clean, BF16, _volume(clean, B, C, S), 2),
+              ("mask_tok", mask_tok, F32, (B, S), 4), ("sigmas_dev", sigmas_dev, F32, (2,), 4), *more(B, C, S))
     a = StepArgs() if guider == "cfg" else GuiderArgs()
     a.v_pos, a.v_neg, a.v_pert, a.latent = _p(v_pos), _p(v_neg), _p(v_pert), _p(latent)
     a.clean, a.mask, a.sigmas_dev = _p(clean), _p(mask_tok), _p(sigmas_dev)
@@ -597,15 +621,9 @@ def _step_tail_args(who: str, v_pos, v_neg, v_pert, latent, guider: str, eta, no
     return a
 
 
-def _guider_record(who: str, record: Optional[torch.Tensor], B: int, device, make: bool) -> torch.Tensor:
-    if record is None and make:
-        return torch.empty((B, GUIDER_RECORD_FLOATS), dtype=torch.float32, device=device)
-    if record is None:
-        raise ValueError(f"{who}: record is required (the output of guidance_sums)")
-    _req(record, torch.float32, f"{who}.record")
-    if tuple(record.shape) != (B, GUIDER_RECORD_FLOATS) or not record.is_contiguous():
-        raise ValueError(f"{who}: record must be a contiguous ({B},{GUIDER_RECORD_FLOATS}) float32 tensor, got {tuple(record.shape)}")
-    return record
+def _volume(t: Optional[torch.Tensor], B: int, C: int, S: int):
+    """The shape item of a (B,C,...) volume held to its element count: ``t``'s own shape if that has B*C*S elements."""
+    return t.shape if t is not None and t.numel() == B * C * S else (B, C, S)
 
 
 def step_tail(v_pos: torch.Tensor, v_neg: Optional[torch.Tensor], v_pert: Optional[torch.Tensor], latent: torch.Tensor, *,
@@ -620,19 +638,20 @@ def step_tail(v_pos: torch.Tensor, v_neg: Optional[torch.Tensor], v_pert: Option
     ``record`` (from ``guidance_sums`` on the same inputs; ltxk_guider_euler_step).  With ``sigmas_dev`` (2 float32 on the
     device) the scalars are read from device memory (hipGraph replay).  ``out`` may be ``latent`` itself (each element is
     read and written by one thread).  ``bf16_euler``: the reference's fp32_euler=False compiled step (generate.py:741-748)."""
-    a = _step_tail_args("step_tail", v_pos, v_neg, v_pert, latent, guider, eta, norm_threshold, clean, mask_tok, sigmas_dev)
+    if guider != "cfg" and record is None:
+        raise ValueError("step_tail: record is required (the output of guidance_sums)")
+    a = _step_tail_args("step_tail", v_pos, v_neg, v_pert, latent, guider, eta, norm_threshold, clean, mask_tok, sigmas_dev,
+                        lambda B, C, S: (("out", out, BF16, _volume(out, B, C, S), 2),
+                                         ("record", record if guider != "cfg" else None, F32, (B, GUIDER_RECORD_FLOATS), 4)))
     if out is None:
         out = torch.empty_like(latent)
-    _req(out, BF16, "step_tail.out")
-    if out.numel() != latent.numel() or not out.is_contiguous():
-        raise ValueError(f"step_tail: out must be a contiguous tensor of the latent's size, got {tuple(out.shape)}")
     a.out = _p(out)
     a.cfg_scale, a.stg_scale, a.sigma, a.sigma_next = cfg_scale, stg_scale, sigma, sigma_next
     a.flags = int(bf16_euler)
     if guider == "cfg":
         check(_lib.load().ltxk_guided_euler_step(ctypes.byref(a), _stream()), "ltxk_guided_euler_step")
     else:
-        a.record = _p(_guider_record("step_tail", record, a.B, latent.device, make=False))
+        a.record = _p(record)
         check(_lib.load().ltxk_guider_euler_step(ctypes.byref(a), _stream()), "ltxk_guider_euler_step")
     return out
 
@@ -681,18 +700,17 @@ def guidance_sums(v_pos: torch.Tensor, v_neg: torch.Tensor, latent: torch.Tensor
                   sigmas_dev: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The per-sample sums and derived scalars of the ``cfg_star`` / ``apg`` guider (ltxk_guidance_sums): v_* (B,S,C) tokens,
     latent (B,C,...) -> ``record`` (B,8) float32 in device memory (layout: include/ltxk.h), which ``step_tail`` reads.
-    Deterministic (no atomics; the summation order depends on (C,S) only).  ``workspace``: a float32 device tensor of at least
+    Deterministic (no atomics; the summation order depends on (C,S) only).  ``workspace``: a float32 device vector of at least
     ``guidance_sums_workspace_bytes`` bytes (allocated when None).  ``sigmas_dev``: sigma is read from device memory."""
     if guider == "cfg":
         raise ValueError("guidance_sums: 'cfg' is not a guider id here (plain CFG has no sums)")
-    a = _step_tail_args("guidance_sums", v_pos, v_neg, None, latent, guider, 1.0, norm_threshold, None, None, sigmas_dev)
-    need = guidance_sums_workspace_bytes(a.B, a.C, a.S)
+    a = _step_tail_args("guidance_sums", v_pos, v_neg, None, latent, guider, 1.0, norm_threshold, None, None, sigmas_dev,
+                        lambda B, C, S: (("record", record, F32, (B, GUIDER_RECORD_FLOATS), 4),
+                                         ("workspace", workspace, F32, (-(guidance_sums_workspace_bytes(B, C, S) // 4),), 4)))
     if workspace is None:
-        workspace = torch.empty((need // 4,), dtype=torch.float32, device=latent.device)
-    _req(workspace, torch.float32, "guidance_sums.workspace")
-    if not workspace.is_contiguous() or workspace.numel() * 4 < need:
-        raise ValueError(f"guidance_sums: workspace must be a contiguous float32 tensor of >= {need} bytes")
-    record = _guider_record("guidance_sums", record, a.B, latent.device, make=True)
+        workspace = torch.empty((guidance_sums_workspace_bytes(a.B, a.C, a.S) // 4,), dtype=torch.float32, device=latent.device)
+    if record is None:
+        record = torch.empty((a.B, GUIDER_RECORD_FLOATS), dtype=torch.float32, device=latent.device)
     a.record, a.workspace, a.workspace_bytes = _p(record), _p(workspace), workspace.numel() * 4
     a.sigma = sigma
     check(_lib.load().ltxk_guidance_sums(ctypes.byref(a), _stream()), "ltxk_guidance_sums")
@@ -701,16 +719,11 @@ def guidance_sums(v_pos: torch.Tensor, v_neg: torch.Tensor, latent: torch.Tensor
 
 def attn_value_passthrough(vt: torch.Tensor, out: torch.Tensor, B: int, T: int, row_mask: int) -> torch.Tensor:
     """STG's skipped self-attention: rows b with bit b of ``row_mask`` set get out[b*T+t, :D] = vt[b, :, t] (bit-exact
-    transpose of the (B, D, ldvt) V^T buffer into the (B*T, >=D) token-major attention output).  Other rows untouched."""
-    _req(vt, BF16, "attn_value_passthrough.vt")
-    _req(out, BF16, "attn_value_passthrough.out")
-    if vt.dim() != 3 or vt.shape[0] < B or vt.stride(-1) != 1 or vt.stride(0) != vt.shape[1] * vt.stride(1):
-        raise ValueError(f"attn_value_passthrough: vt must be a (B, D, ldvt) buffer with unit inner stride, got {tuple(vt.shape)}")
-    D = vt.shape[1]
-    if vt.shape[2] < T or out.dim() != 2 or out.stride(-1) != 1 or out.shape[0] < B * T or out.shape[1] < D:
-        raise ValueError(f"attn_value_passthrough: shapes do not fit B={B} T={T} D={D}: vt {tuple(vt.shape)}, out {tuple(out.shape)}")
+    transpose of the (>= B, D, ld >= T) V^T buffer into the (>= B*T, >= D) token-major attention output).  Other rows untouched."""
     if not 0 <= int(row_mask) < (1 << 64):
         raise ValueError("attn_value_passthrough: row_mask must fit 64 bits")
+    D = _dims("attn_value_passthrough", "vt", vt, BF16, 3)[1]
+    _operands("attn_value_passthrough", ("vt", vt, BF16, (-B, D, -T), 16, True), ("out", out, BF16, (-(B * T), -D), 16, True))
     check(_lib.load().ltxk_attn_value_passthrough(_p(vt), vt.stride(1), _p(out), out.stride(0), B, D, T, int(row_mask), _stream()),
           "ltxk_attn_value_passthrough")
     return out
@@ -718,27 +731,28 @@ def attn_value_passthrough(vt: torch.Tensor, out: torch.Tensor, B: int, T: int, 
 
 def step_scalars(ts_all: torch.Tensor, sig_all: torch.Tensor, step: torch.Tensor, ts: torch.Tensor, sig: torch.Tensor) -> None:
     """ts_all (steps,U) bf16, sig_all (steps,2) fp32, step (1) int32 -> ts (U), sig (2); step += 1 (device side)."""
-    _req(ts_all, BF16, "step_scalars.ts_all")
-    n, U = ts_all.shape
-    if sig_all.dtype != torch.float32 or tuple(sig_all.shape) != (n, 2) or step.dtype != torch.int32 or ts.numel() != U:
-        raise TypeError("step_scalars: bad table shapes / dtypes")
+    n, U = _dims("step_scalars", "ts_all", ts_all, BF16, 2)
+    _operands("step_scalars", ("ts_all", ts_all, BF16, 2, 2), ("sig_all", sig_all, F32, (n, 2), 4), ("step", step, I32, (1,), 4),
+              ("ts", ts, BF16, (U,), 2), ("sig", sig, F32, (2,), 4))
     check(_lib.load().ltxk_step_scalars(_p(ts_all), _p(sig_all), _p(step), _p(ts), _p(sig), U, n, _stream()), "ltxk_step_scalars")
 
 
 def euler_only(latent: torch.Tensor, denoised: torch.Tensor, sigma: float, sigma_next: float) -> torch.Tensor:
-    _req(latent, BF16, "euler_only.latent"); _req(denoised, BF16, "euler_only.denoised")
-    out = torch.empty_like(latent)
-    check(_lib.load().ltxk_euler_step(_p(latent.contiguous()), _p(denoised.contiguous()), _p(out), latent.numel(),
-                                      sigma, sigma_next, _stream()), "ltxk_euler_step")
+    """out = bf16(x0 + sigma_next * (x - x0) / sigma) over two tensors of one shape; either is copied if not contiguous."""
+    lat, den = latent.contiguous(), denoised.contiguous()
+    _operands("euler_only", ("latent", lat, BF16, lat.dim(), 16), ("denoised", den, BF16, lat.shape, 16))
+    out = torch.empty_like(lat)
+    check(_lib.load().ltxk_euler_step(_p(lat), _p(den), _p(out), lat.numel(), sigma, sigma_next, _stream()), "ltxk_euler_step")
     return out
 
 
 def resize_area(x: torch.Tensor, oh: int, ow: int) -> torch.Tensor:
     """(..., H, W) fp32 / bf16 device tensor -> (..., oh, ow) bf16: cv2.INTER_AREA downscale of every (H,W) plane
-    (prepare_video_for_encoding, utils.py:699-705)."""
-    if not x.is_cuda or x.dtype not in (torch.float32, BF16):
-        raise _lib.LtxkError("resize_area: expected a float32 / bfloat16 device tensor")
+    (prepare_video_for_encoding, utils.py:699-705).  An ``x`` that is not contiguous is copied first."""
+    if x.dim() < 2:
+        raise ValueError(f"resize_area: x must be (..., H, W), got {tuple(x.shape)}")
     x = x.contiguous()
+    _operands("resize_area", ("x", x, F32 if x.dtype == F32 else BF16, x.dim(), 2))
     H, W = x.shape[-2:]
     planes = x.numel() // (H * W)
     out = torch.empty(tuple(x.shape[:-2]) + (oh, ow), dtype=BF16, device=x.device)
@@ -758,22 +772,12 @@ def layer_stats_depth(count: int, D: int) -> int:
     return -(-rows * (D // 8) // STATS_THREADS) + 3 + 6 + 2 + 6
 
 
-def _req_layers(x: torch.Tensor, row_start: torch.Tensor, row_count: torch.Tensor, who: str):
-    _req(x, BF16, f"{who}.x")
-    _req(row_start, torch.int32, f"{who}.row_start"); _req(row_count, torch.int32, f"{who}.row_count")
-    if x.dim() != 4 or x.stride(3) != 1:
-        raise ValueError(f"{who}: x must be an (L,B,T,D) stack with unit inner stride, got {tuple(x.shape)} strides {x.stride()}")
-    L, B, T, D = x.shape
-    if tuple(row_start.shape) != (B,) or tuple(row_count.shape) != (B,) or not row_start.is_contiguous() or not row_count.is_contiguous():
-        raise ValueError(f"{who}: row_start / row_count must be contiguous ({B},) vectors")
-    return L, B, T, D
-
-
 def masked_layer_stats(x: torch.Tensor, row_start: torch.Tensor, row_count: torch.Tensor, valid_rows: Optional[int] = None) -> torch.Tensor:
     """ltxk_masked_layer_stats: x (L,B,T,D) bf16 (any layer / batch / row strides that are multiples of 8), row_start /
     row_count (B) int32 on the device -> (B,L,3) fp32 {sum, min, max} over rows [start, start+count) x D.
     ``valid_rows``: the sum of the counts, if the host knows it (the kernel timer's byte count; the kernel reads valid rows only)."""
-    L, B, T, D = _req_layers(x, row_start, row_count, "masked_layer_stats")
+    L, B, T, D = _dims("masked_layer_stats", "x", x, BF16, 4)
+    _operands("masked_layer_stats", ("x", x, BF16, 4, 16, 8), ("row_start", row_start, I32, (B,), 4), ("row_count", row_count, I32, (B,), 4))
     partials = torch.empty((B * L, 3, STATS_PARTIALS), dtype=torch.float32, device=x.device)
     stats = torch.empty((B, L, 3), dtype=torch.float32, device=x.device)
     with _timed("text_layer_stats", 0.0, 2.0 * L * D * (B * T if valid_rows is None else valid_rows)):
@@ -787,13 +791,9 @@ def layer_norm_compact(x: torch.Tensor, row_start: torch.Tensor, row_count: torc
     """ltxk_layer_norm_compact: the valid rows of x (L,B,T,D), normalised with ``stats`` of ``masked_layer_stats``, into the
     first ``rows`` rows of out (>= rows, >= L*D) bf16, layer-major columns l*D + d; row0 (B) int32 = exclusive prefix sums of
     the counts, ``rows`` their total (the host knows both)."""
-    L, B, T, D = _req_layers(x, row_start, row_count, "layer_norm_compact")
-    _req(row0, torch.int32, "layer_norm_compact.row0"); _req(stats, torch.float32, "layer_norm_compact.stats")
-    _req(out, BF16, "layer_norm_compact.out")
-    if tuple(row0.shape) != (B,) or not row0.is_contiguous() or tuple(stats.shape) != (B, L, 3) or not stats.is_contiguous():
-        raise ValueError("layer_norm_compact: row0 must be a contiguous (B,) vector and stats a contiguous (B,L,3) tensor")
-    if out.dim() != 2 or out.stride(1) != 1 or out.shape[0] < rows or out.shape[1] < L * D:
-        raise ValueError(f"layer_norm_compact: out must be (>= {rows}, >= {L * D}) with unit inner stride, got {tuple(out.shape)}")
+    L, B, T, D = _dims("layer_norm_compact", "x", x, BF16, 4)
+    _operands("layer_norm_compact", ("x", x, BF16, 4, 16, 8), ("row_start", row_start, I32, (B,), 4), ("row_count", row_count, I32, (B,), 4),
+              ("row0", row0, I32, (B,), 4), ("stats", stats, F32, (B, L, 3), 4), ("out", out, BF16, (-rows, -(L * D)), 16, True))
     with _timed("text_layer_norm", 0.0, 4.0 * rows * L * D):
         check(_lib.load().ltxk_layer_norm_compact(_p(x), x.stride(0), x.stride(1), x.stride(2), _p(row_start), _p(row_count),
                                                   _p(row0), _p(stats), _p(out), out.stride(0), L, B, T, D, rows, _stream()),
@@ -803,15 +803,10 @@ def layer_norm_compact(x: torch.Tensor, row_start: torch.Tensor, row_count: torc
 
 def rmsnorm_rows(x: torch.Tensor, eps: float = 1e-6, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """ltxk_rmsnorm_rows: unit-weight RMSNorm of the rows of x (M,D), any D % 8 == 0 up to 8192; row strides may exceed D."""
-    _req(x, BF16, "rmsnorm_rows.x")
-    if x.dim() != 2 or x.stride(1) != 1:
-        raise ValueError(f"rmsnorm_rows: expected an (M,D) matrix with unit inner stride, got {tuple(x.shape)}")
-    M, D = x.shape
+    M, D = _dims("rmsnorm_rows", "x", x, BF16, 2)
+    _operands("rmsnorm_rows", ("x", x, BF16, 2, 16, True), ("out", out, BF16, (M, D), 16, True))
     if out is None:
         out = torch.empty((M, D), dtype=BF16, device=x.device)
-    _req(out, BF16, "rmsnorm_rows.out")
-    if tuple(out.shape) != (M, D) or out.stride(1) != 1:
-        raise ValueError(f"rmsnorm_rows: out must be ({M},{D}) with unit inner stride, got {tuple(out.shape)}")
     with _timed("rmsnorm_rows", 0.0, 4.0 * M * D):
         check(_lib.load().ltxk_rmsnorm_rows(_p(x), x.stride(0), _p(out), out.stride(0), M, D, eps, _stream()), "ltxk_rmsnorm_rows")
     return out
@@ -821,25 +816,18 @@ def qknorm_rope_1d(buf: torch.Tensor, D: int, weight: torch.Tensor, cos: torch.T
                    eps: float = 1e-6) -> torch.Tensor:
     """ltxk_qknorm_rope_1d: in place on columns [0, 2D) of buf (M, ld >= 2D): q | k RMSNorm over the full D with weight (2,D),
     then split RoPE with cos / sin (H,T,64) fp32; any H >= 1 with D == 128*H."""
-    _req(buf, BF16, "qknorm_rope_1d.buf"); _req(weight, BF16, "qknorm_rope_1d.weight")
-    _req(cos, torch.float32, "qknorm_rope_1d.cos"); _req(sin, torch.float32, "qknorm_rope_1d.sin")
-    if buf.dim() != 2 or buf.stride(1) != 1 or buf.shape[1] < 2 * D:
-        raise ValueError(f"qknorm_rope_1d: buf must be (M, >= {2 * D}) with unit inner stride, got {tuple(buf.shape)}")
-    if tuple(weight.shape) != (2, D) or not weight.is_contiguous():
-        raise ValueError(f"qknorm_rope_1d: weight must be a contiguous (2,{D}) table, got {tuple(weight.shape)}")
-    if tuple(cos.shape) != (H, T, 64) or tuple(sin.shape) != (H, T, 64) or not cos.is_contiguous() or not sin.is_contiguous():
-        raise ValueError(f"qknorm_rope_1d: cos / sin must be contiguous ({H},{T},64) tables, got {tuple(cos.shape)}")
-    with _timed("qknorm_rope_1d", 0.0, 8.0 * buf.shape[0] * D + 8.0 * buf.shape[0] * D):
-        check(_lib.load().ltxk_qknorm_rope_1d(_p(buf), buf.stride(0), buf.shape[0], D, _p(weight), _p(cos), _p(sin), T, H, eps,
+    M = _dims("qknorm_rope_1d", "buf", buf, BF16, 2)[0]
+    _operands("qknorm_rope_1d", ("buf", buf[:, :2 * D], BF16, (M, 2 * D), 16, True), ("weight", weight, BF16, (2, D), 16),
+              ("cos", cos, F32, (H, T, 64), 16), ("sin", sin, F32, (H, T, 64), 16))
+    with _timed("qknorm_rope_1d", 0.0, 8.0 * M * D + 8.0 * M * D):
+        check(_lib.load().ltxk_qknorm_rope_1d(_p(buf), buf.stride(0), M, D, _p(weight), _p(cos), _p(sin), T, H, eps,
                                               _stream()), "ltxk_qknorm_rope_1d")
     return buf
 
 
 def gelu_erf_(x: torch.Tensor) -> torch.Tensor:
     """ltxk_gelu_erf: exact (erf) GELU in place on a contiguous bf16 tensor."""
-    _req(x, BF16, "gelu_erf_.x")
-    if not x.is_contiguous():
-        raise ValueError("gelu_erf_: x must be contiguous")
+    _operands("gelu_erf_", ("x", x, BF16, x.dim(), 16))
     with _timed("gelu_erf", 0.0, 4.0 * x.numel()):
         check(_lib.load().ltxk_gelu_erf(_p(x), x.numel(), _stream()), "ltxk_gelu_erf")
     return x
@@ -849,18 +837,10 @@ def connector_assemble(feat: Optional[torch.Tensor], registers: torch.Tensor, ro
                        B: int, T: int) -> torch.Tensor:
     """ltxk_connector_assemble: (B,T,D) connector input - batch row b's first row_count[b] rows are rows row0[b]... of feat
     (rows, D), the rest registers[t % R].  ``feat`` may be None when every count is 0."""
-    _req(registers, BF16, "connector_assemble.registers")
-    _req(row0, torch.int32, "connector_assemble.row0"); _req(row_count, torch.int32, "connector_assemble.row_count")
-    R, D = registers.shape
-    if not registers.is_contiguous() or tuple(row0.shape) != (B,) or tuple(row_count.shape) != (B,) or \
-            not row0.is_contiguous() or not row_count.is_contiguous():
-        raise ValueError("connector_assemble: registers must be contiguous (R,D), row0 / row_count contiguous (B,) vectors")
-    rows, ldf = 0, 0
-    if feat is not None:
-        _req(feat, BF16, "connector_assemble.feat")
-        if feat.dim() != 2 or feat.stride(1) != 1 or feat.shape[1] != D:
-            raise ValueError(f"connector_assemble: feat must be (rows,{D}) with unit inner stride, got {tuple(feat.shape)}")
-        rows, ldf = feat.shape[0], feat.stride(0)
+    R, D = _dims("connector_assemble", "registers", registers, BF16, 2)
+    _operands("connector_assemble", ("feat", feat, BF16, (feat.shape[0], D) if feat is not None and feat.dim() == 2 else (-1, D), 16, True),
+              ("registers", registers, BF16, 2, 16), ("row0", row0, I32, (B,), 4), ("row_count", row_count, I32, (B,), 4))
+    rows, ldf = (feat.shape[0], feat.stride(0)) if feat is not None else (0, 0)
     out = torch.empty((B, T, D), dtype=BF16, device=registers.device)
     with _timed("connector_assemble", 0.0, 4.0 * B * T * D):
         check(_lib.load().ltxk_connector_assemble(_p(feat) if rows else None, ldf, _p(registers), _p(row0), _p(row_count), _p(out),
@@ -880,13 +860,9 @@ def embed_rows(table: torch.Tensor, ids: torch.Tensor, scale: float, out: Option
     """ltxk_embed_rows: out[m,:] = bf16(table[ids[m],:] * scale).  table (V,D) contiguous bf16, ids (M) int32 on the device.
     The kernel cannot raise for device data, so the id range is validated here on ``ids_host``, the host copy the caller
     tokenised (without one, ``ids`` is copied back once - a synchronisation, once per prompt)."""
-    _req(table, BF16, "embed_rows.table"); _req(ids, torch.int32, "embed_rows.ids")
-    if table.dim() != 2 or not table.is_contiguous():
-        raise ValueError(f"embed_rows: table must be a contiguous (V,D) matrix, got {tuple(table.shape)}")
-    if ids.dim() != 1 or not ids.is_contiguous():
-        raise ValueError(f"embed_rows: ids must be a contiguous (M,) vector, got {tuple(ids.shape)}")
-    V, D = table.shape
-    M = ids.shape[0]
+    V, D = _dims("embed_rows", "table", table, BF16, 2)
+    M = _dims("embed_rows", "ids", ids, I32, 1)[0]
+    _operands("embed_rows", ("table", table, BF16, 2, 16), ("ids", ids, I32, 1, 4), ("out", out, BF16, (M, D), 16, True))
     host = ids.cpu() if ids_host is None else ids_host.reshape(-1)
     if host.numel() != M:
         raise ValueError(f"embed_rows: ids_host holds {host.numel()} ids, ids {M}")
@@ -894,9 +870,6 @@ def embed_rows(table: torch.Tensor, ids: torch.Tensor, scale: float, out: Option
         raise ValueError(f"embed_rows: token ids must lie in [0, {V}), got [{int(host.min())}, {int(host.max())}]")
     if out is None:
         out = torch.empty((M, D), dtype=BF16, device=table.device)
-    _req(out, BF16, "embed_rows.out")
-    if tuple(out.shape) != (M, D) or out.stride(1) != 1:
-        raise ValueError(f"embed_rows: out must be ({M},{D}) with unit inner stride, got {tuple(out.shape)}")
     with _timed("embed_rows", 0.0, 4.0 * M * D):
         check(_lib.load().ltxk_embed_rows(_p(table), V, D, _p(ids), _p(out), out.stride(0), M, scale, _stream()), "ltxk_embed_rows")
     return out
@@ -906,21 +879,11 @@ def rmsnorm_weight_rows(x: torch.Tensor, weight: torch.Tensor, eps: float = 1e-6
                         out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """ltxk_rmsnorm_weight_rows: Gemma RMSNorm, y = bf16(x * rsqrt(mean(x^2) + eps) * (1 + weight)); with ``resid``
     y = bf16(resid + that).  x (M,D), any D % 8 == 0 up to 8192, row strides may exceed D; ``out`` may be ``resid`` or ``x``."""
-    _req(x, BF16, "rmsnorm_weight_rows.x"); _req(weight, BF16, "rmsnorm_weight_rows.weight")
-    if x.dim() != 2 or x.stride(1) != 1:
-        raise ValueError(f"rmsnorm_weight_rows: expected an (M,D) matrix with unit inner stride, got {tuple(x.shape)}")
-    M, D = x.shape
-    if tuple(weight.shape) != (D,) or not weight.is_contiguous():
-        raise ValueError(f"rmsnorm_weight_rows: weight must be a contiguous ({D},) vector, got {tuple(weight.shape)}")
-    if resid is not None:
-        _req(resid, BF16, "rmsnorm_weight_rows.resid")
-        if tuple(resid.shape) != (M, D) or resid.stride(1) != 1:
-            raise ValueError(f"rmsnorm_weight_rows: resid must be ({M},{D}) with unit inner stride, got {tuple(resid.shape)}")
+    M, D = _dims("rmsnorm_weight_rows", "x", x, BF16, 2)
+    _operands("rmsnorm_weight_rows", ("x", x, BF16, 2, 16, True), ("weight", weight, BF16, (D,), 16),
+              ("resid", resid, BF16, (M, D), 16, True), ("out", out, BF16, (M, D), 16, True))
     if out is None:
         out = torch.empty((M, D), dtype=BF16, device=x.device)
-    _req(out, BF16, "rmsnorm_weight_rows.out")
-    if tuple(out.shape) != (M, D) or out.stride(1) != 1:
-        raise ValueError(f"rmsnorm_weight_rows: out must be ({M},{D}) with unit inner stride, got {tuple(out.shape)}")
     with _timed("rmsnorm_weight_rows", 0.0, (4.0 if resid is None else 6.0) * M * D):
         check(_lib.load().ltxk_rmsnorm_weight_rows(_p(x), x.stride(0), _p(weight), _p(resid), resid.stride(0) if resid is not None else 0,
                                                    _p(out), out.stride(0), M, D, eps, _stream()), "ltxk_rmsnorm_weight_rows")
@@ -931,18 +894,14 @@ def headnorm_rope(buf: torch.Tensor, Hq: int, Hkv: int, q_weight: torch.Tensor, 
                   sin: torch.Tensor, T: int, eps: float = 1e-6) -> torch.Tensor:
     """ltxk_headnorm_rope: in place on columns [0, (Hq+Hkv)*256) of buf (M, ld): per 256-wide head Gemma RMSNorm with
     q_weight / k_weight (256,), then rotate-half RoPE with cos / sin (T,128) fp32, row m at position m % T."""
-    _req(buf, BF16, "headnorm_rope.buf"); _req(q_weight, BF16, "headnorm_rope.q_weight"); _req(k_weight, BF16, "headnorm_rope.k_weight")
-    _req(cos, torch.float32, "headnorm_rope.cos"); _req(sin, torch.float32, "headnorm_rope.sin")
-    cols = (Hq + Hkv) * GEMMA_HEAD_DIM
-    if Hq < 1 or Hkv < 1 or buf.dim() != 2 or buf.stride(1) != 1 or buf.shape[1] < cols:
-        raise ValueError(f"headnorm_rope: buf must be (M, >= {cols}) with unit inner stride, got {tuple(buf.shape)}")
-    for w in (q_weight, k_weight):
-        if tuple(w.shape) != (GEMMA_HEAD_DIM,) or not w.is_contiguous():
-            raise ValueError(f"headnorm_rope: q_weight / k_weight must be contiguous ({GEMMA_HEAD_DIM},) vectors, got {tuple(w.shape)}")
-    if tuple(cos.shape) != (T, GEMMA_HEAD_DIM // 2) or tuple(sin.shape) != tuple(cos.shape) or not cos.is_contiguous() or not sin.is_contiguous():
-        raise ValueError(f"headnorm_rope: cos / sin must be contiguous ({T},{GEMMA_HEAD_DIM // 2}) tables, got {tuple(cos.shape)}")
-    with _timed("headnorm_rope", 0.0, 4.0 * buf.shape[0] * cols):
-        check(_lib.load().ltxk_headnorm_rope(_p(buf), buf.stride(0), buf.shape[0], Hq, Hkv, _p(q_weight), _p(k_weight), _p(cos), _p(sin),
+    if Hq < 1 or Hkv < 1:
+        raise ValueError(f"headnorm_rope: Hq = {Hq} and Hkv = {Hkv} must be positive")
+    cols, HD = (Hq + Hkv) * GEMMA_HEAD_DIM, GEMMA_HEAD_DIM
+    M = _dims("headnorm_rope", "buf", buf, BF16, 2)[0]
+    _operands("headnorm_rope", ("buf", buf[:, :cols], BF16, (M, cols), 16, True), ("q_weight", q_weight, BF16, (HD,), 16),
+              ("k_weight", k_weight, BF16, (HD,), 16), ("cos", cos, F32, (T, HD // 2), 16), ("sin", sin, F32, (T, HD // 2), 16))
+    with _timed("headnorm_rope", 0.0, 4.0 * M * cols):
+        check(_lib.load().ltxk_headnorm_rope(_p(buf), buf.stride(0), M, Hq, Hkv, _p(q_weight), _p(k_weight), _p(cos), _p(sin),
                                              T, eps, _stream()), "ltxk_headnorm_rope")
     return buf
 
@@ -950,10 +909,11 @@ def headnorm_rope(buf: torch.Tensor, Hq: int, Hkv: int, q_weight: torch.Tensor, 
 def geglu_tanh_(gu: torch.Tensor) -> torch.Tensor:
     """ltxk_geglu_tanh in place: gu = [g | u] (M, 2F) -> its first F columns become bf16(bf16(gelu_tanh(g)) * u); returns that
     (M,F) view (row stride 2F: ``gemm`` takes it as ``a``)."""
-    _req(gu, BF16, "geglu_tanh_.gu")
-    if gu.dim() != 2 or gu.stride(1) != 1 or gu.shape[1] % 16:
-        raise ValueError(f"geglu_tanh_: gu must be (M, 2F) with unit inner stride and F a multiple of 8, got {tuple(gu.shape)}")
-    M, F = gu.shape[0], gu.shape[1] // 2
+    M, F2 = _dims("geglu_tanh_", "gu", gu, BF16, 2)
+    if F2 % 16:
+        raise ValueError(f"geglu_tanh_: gu must be (M, 2F) with F a multiple of 8, got {tuple(gu.shape)}")
+    _operands("geglu_tanh_", ("gu", gu, BF16, 2, 16, True))
+    F = F2 // 2
     with _timed("geglu_tanh", 0.0, 6.0 * M * F):
         check(_lib.load().ltxk_geglu_tanh(_p(gu), gu.stride(0), _p(gu), gu.stride(0), M, F, _stream()), "ltxk_geglu_tanh")
     return gu[:, :F]
@@ -962,20 +922,11 @@ def geglu_tanh_(gu: torch.Tensor) -> torch.Tensor:
 def causal_attn(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, out: torch.Tensor, row_start: torch.Tensor, B: int, Hq: int,
                 Hkv: int, T: int, scale: float, window: int = 0) -> torch.Tensor:
     """ltxk_causal_attn (head dim 256): q (B*T, >= Hq*256) view, k (B*T, >= Hkv*256) view, vt (B, Hkv*256, ldvt >= T),
-    out (B*T, Hq*256) view, row_start (B) int32 on the device (valid tokens of batch row b: [row_start[b], T)).  Key j is
+    out (B*T, >= Hq*256) view, row_start (B) int32 on the device (valid tokens of batch row b: [row_start[b], T)).  Key j is
     visible to query i iff row_start <= j <= i and (window == 0 or i - j < window); rows below row_start come out zero."""
-    for t, name in ((q, "q"), (k, "k"), (vt, "vt"), (out, "out")):
-        _req(t, BF16, f"causal_attn.{name}")
-    _req(row_start, torch.int32, "causal_attn.row_start")
-    if tuple(row_start.shape) != (B,) or not row_start.is_contiguous():
-        raise ValueError(f"causal_attn: row_start must be a contiguous ({B},) vector, got {tuple(row_start.shape)}")
-    for t, name, h in ((q, "q", Hq), (k, "k", Hkv), (out, "out", Hq)):
-        if t.dim() != 2 or t.stride(1) != 1 or t.shape[0] != B * T or t.shape[1] < h * GEMMA_HEAD_DIM:
-            raise ValueError(f"causal_attn: {name} must be ({B * T}, >= {h * GEMMA_HEAD_DIM}) with unit inner stride, got {tuple(t.shape)}")
-    if vt.dim() != 3 or vt.stride(2) != 1 or vt.shape[0] != B or vt.shape[1] != Hkv * GEMMA_HEAD_DIM or vt.shape[2] < T or \
-            vt.stride(0) != vt.shape[1] * vt.stride(1):
-        raise ValueError(f"causal_attn: vt must be ({B},{Hkv * GEMMA_HEAD_DIM}, >= {T}) with dense batch stride, got {tuple(vt.shape)} "
-                         f"strides {vt.stride()}")
+    nq, nkv = Hq * GEMMA_HEAD_DIM, Hkv * GEMMA_HEAD_DIM
+    _operands("causal_attn", ("q", q, BF16, (B * T, -nq), 16, True), ("k", k, BF16, (B * T, -nkv), 16, True),
+              ("vt", vt, BF16, (B, nkv, -T), 16, True), ("out", out, BF16, (B * T, -nq), 16, True), ("row_start", row_start, I32, (B,), 4))
     a = CausalAttnArgs()
     a.q, a.k, a.vt, a.out, a.row_start = _p(q), _p(k), _p(vt), _p(out), _p(row_start)
     a.ldq, a.ldk, a.ldvt, a.ldo = q.stride(0), k.stride(0), vt.stride(1), out.stride(0)
@@ -986,7 +937,7 @@ def causal_attn(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, out: torch.T
 
 
 # ------------------------------------------------------------------- VAE / upsampler (csrc/conv3d.hip, csrc/vae_ops.hip)
-# Volumes are channels-last (B,D,H,W,C) bf16, a voxel one contiguous row.  Every operand goes through ``_operands``.
+# Volumes are channels-last (B,D,H,W,C) bf16, a voxel one contiguous row.
 PAD_ZEROS, PAD_REFLECT = 0, 1
 
 

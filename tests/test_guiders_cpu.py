@@ -260,9 +260,9 @@ def test_every_tail_entry_refuses_grid_overflow_and_misaligned_tokens():
             assert msg.startswith(entry + ":") and why in msg, (entry, over, msg)
     x = torch.zeros(1, 128, 4, dtype=torch.bfloat16)
     v = torch.zeros(1, 4, 128, dtype=torch.bfloat16)
-    with pytest.raises(ValueError, match="v_pos must be a contiguous"):
+    with pytest.raises(ValueError, match="step_tail: v_pos must be contiguous"):
         ops.cfg_euler_step(torch.zeros(1, 128, 4, dtype=torch.bfloat16).transpose(1, 2), v, x, 4.0, 0.5, 0.25)
-    with pytest.raises(ValueError, match="v_neg must be a contiguous"):
+    with pytest.raises(ValueError, match=r"step_tail: v_neg must be \(1, 4, 128\)"):
         ops.cfg_euler_step(v, torch.zeros(1, 3, 128, dtype=torch.bfloat16), x, 4.0, 0.5, 0.25)
 
 
