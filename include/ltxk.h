@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define LTXK_VERSION 410
+#define LTXK_VERSION 411
 
 #define LTXK_OK 0
 #define LTXK_EINVAL (-1)   /* bad argument (shape / alignment / null pointer) */
@@ -575,6 +575,34 @@ typedef struct ltxk_causal_attn_args {
 int ltxk_causal_attn(const ltxk_causal_attn_args* args, void* stream);
 /* sizeof(ltxk_causal_attn_args) in this build (an entry of its own: the ltxk_abi_sizeof index list is closed).          */
 int ltxk_causal_attn_args_sizeof(void);
+
+/* Gemma-3 decoding: ltxk_causal_attn for ONE query position per batch row against a per-layer KV cache, with the append fused.
+ * The cache is held in ltxk_causal_attn's own operand layouts at T = cap, so a prefill writes it with the encoder's launches:
+ *   k_cache : (B,cap,Hkv*256) bf16 row stride ldk          vt_cache : (B,Hkv*256,ldvt >= cap) bf16 = V transposed
+ *   cap % 64 == 0; cache positions > step are read in whole tiles and must be finite (a zero-initialised cache).
+ *   q      : (B,Hq*256) bf16 row stride ldq, the step's normed and rotated query
+ *   k_new  : (B,Hkv*256) row stride ldkn, the step's key after norm and RoPE;  v_new : (B,Hkv*256) row stride ldvn, its value
+ *   out    : (B,Hq*256) row stride ldo
+ *   row_start (B) DEVICE int32 as above; step: host int, 0 <= step < cap, the new token's position in the padded sequence.
+ * Key j is visible iff  row_start[b] <= j <= step  and  (window == 0 or step - j < window).  Key `step` is read from k_new /
+ * v_new, never from the cache, and the launch stores k_new into K row `step` and v_new into V^T column `step` (the append;
+ * the one wave whose keys hold `step` stores it and no other reads that position).  Every other cache element is left as it
+ * was.  row_start[b] > step: an all-zero output row (no NaN); the append still happens.  Hq % Hkv == 0 and Hq/Hkv <= 16: the
+ * query heads of one KV head are the 16-wide operand's columns, so a KV head's cache is read once for its group.
+ * Rounding points: the "flash" policy above.  Keys are split across workgroups: slice s = keys [256 s, 256 s + 256), one
+ * 64-key tile per wave; S in fp32, P = exp2(fma(S, scale*log2 e, -M)) with M the ceil of the tile's maximum over its visible
+ * keys, l = sum P in fp32, O = bf16(P) @ V in fp32.  The four tiles of a slice, then the slices, are merged in ascending order:
+ * M = max M_i, l = sum l_i 2^(M_i - M), O = sum O_i 2^(M_i - M) - M is an integer, so every factor is an exact power of two -
+ * and out = r(O * (1/l)).  A tile wholly outside the visible range is not fetched.  The slices of a launch are
+ * [s0, step/256] with s0 = max(0, step - window + 1) / 256 for a window, else 0: a function of step (and window) only, so
+ * the bits of a (batch row, head) do not depend on B, on cap or on what else the launch holds.  No atomics; the merge of the
+ * slices is a second small launch, as ltxk_gemm_bf16's split-K combine.
+ * partials: caller-owned fp32 scratch of >= B * Hq * (step/256 + 1 - s0) * 258 floats ((M, l, O[256]) per batch row, head and
+ * slice; B * Hq * ceil(cap/256) * 258 serves every step), 16-byte aligned; partials_floats is its size.                  */
+int ltxk_causal_attn_step(const void* q, int32_t ldq, const void* k_new, int32_t ldkn, const void* v_new, int32_t ldvn,
+                          void* k_cache, int32_t ldk, void* vt_cache, int32_t ldvt, void* out, int32_t ldo,
+                          const int32_t* row_start, int32_t B, int32_t Hq, int32_t Hkv, int32_t cap, int32_t step,
+                          int32_t window, float scale, float* partials, int64_t partials_floats, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * Video VAE (volumes are channels-last (B,D,H,W,C) bf16; a row = one voxel)

@@ -207,6 +207,9 @@ SIGNATURES = {
     "ltxk_geglu_tanh": (c_int32, [c_void_p, c_int32, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
     "ltxk_causal_attn": (c_int32, [POINTER(CausalAttnArgs), c_void_p]),
     "ltxk_causal_attn_args_sizeof": (c_int32, []),
+    # Gemma-3 decoding (csrc/causal_attn_step.hip)
+    "ltxk_causal_attn_step": (c_int32, [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32,
+                                        c_void_p, c_int32, c_void_p] + [c_int32] * 6 + [c_float, c_void_p, c_int64, c_void_p]),
 }
 
 # ltxk_abi_sizeof(i) is the size of ABI_STRUCTS[i]

@@ -15,14 +15,20 @@ layer (:116-132).  The two agree for every T <= window, and the reference's toke
 The run stays on the padded (B,T) layout.  Padded rows carry finite values through the row kernels and GEMMs and nothing
 reads them: attention never admits a key below row_start and writes zeros to query rows below it.  Every GEMM is called with
 ``split_k=False`` and the attention kernel never splits keys, so a batch row's bits do not depend on the batch.
+
+Decoding (``GemmaCache``, ``GemmaGenerator``, ``enhance_prompt``): the reference's prompt enhancement (text_encoder.py:1023-1135)
+generates with ``mlx_lm``; here a prefill is the encoder's own layer loop writing K and V^T into a per-layer cache, and a token is
+one pass of M = B-row GEMMs (the weight-streaming split-K form) with the single-position attention step against that cache.
 """
 from __future__ import annotations
 
 import json
 import math
+import re
+import warnings
 from dataclasses import dataclass, field
 from pathlib import Path
-from typing import Dict, Optional, Sequence, Tuple, Union
+from typing import Dict, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -52,6 +58,7 @@ class GemmaConfig:
     rope_theta: float = 1_000_000.0                       # global layers
     rope_local_base_freq: float = 10_000.0                # local (sliding) layers
     rope_scaling_factor: float = 1.0                      # linear position scaling of the global layers
+    final_logit_softcapping: Optional[float] = None       # the generator refuses a non-null value (the encoder forms no logits)
 
     def __post_init__(self):
         if self.head_dim != HEAD_DIM:
@@ -108,7 +115,8 @@ class GemmaConfig:
             sliding_window_pattern=int(c.get("sliding_window_pattern", d.sliding_window_pattern)),
             query_pre_attn_scalar=float(c.get("query_pre_attn_scalar", d.query_pre_attn_scalar)),
             rms_norm_eps=float(c.get("rms_norm_eps", d.rms_norm_eps)), rope_theta=float(theta), rope_local_base_freq=float(local),
-            rope_scaling_factor=factor)
+            rope_scaling_factor=factor,
+            final_logit_softcapping=None if c.get("final_logit_softcapping") is None else float(c["final_logit_softcapping"]))
 
     @staticmethod
     def from_json(path: Union[str, Path]) -> "GemmaConfig":
@@ -172,6 +180,12 @@ class GemmaEncoder:
         return self._rope[key]
 
     def __call__(self, input_ids: torch.Tensor, attention_mask: torch.Tensor) -> torch.Tensor:
+        return self._forward(input_ids, attention_mask, None)
+
+    def _forward(self, input_ids: torch.Tensor, attention_mask: torch.Tensor, cache: Optional["GemmaCache"]) -> torch.Tensor:
+        """The forward over the padded (B,T) layout.  With a ``cache`` (a prefill) each layer's GEMM writes V^T straight into the
+        cache's (B, Hkv*256, cap) buffer instead of the scratch one and the rotated K columns are copied into its K rows; the
+        launches, and so the states' bits, are the same."""
         counts = mask_row_counts(attention_mask)
         if input_ids.dim() != 2 or tuple(input_ids.shape) != tuple(attention_mask.shape):
             raise ValueError(f"input_ids {tuple(input_ids.shape)} and attention_mask {tuple(attention_mask.shape)} must be one (B,T) shape")
@@ -191,15 +205,21 @@ class GemmaEncoder:
         nx = torch.empty((M, D), dtype=BF16, device=dev)
         qk = torch.empty((M, nq + nkv), dtype=BF16, device=dev)
         tpad = (T + 63) // 64 * 64
-        vt = (torch.zeros if tpad != T else torch.empty)((B, nkv, tpad), dtype=BF16, device=dev)      # pad columns stay finite
+        vt = None
+        if cache is None:
+            vt = (torch.zeros if tpad != T else torch.empty)((B, nkv, tpad), dtype=BF16, device=dev)      # pad columns stay finite
         att = torch.empty((M, nq), dtype=BF16, device=dev)
         po = torch.empty((M, D), dtype=BF16, device=dev)
         gu = torch.empty((M, 2 * F), dtype=BF16, device=dev)
         for i, ly in enumerate(self.layers):
             cos, sin = self._tables(T, ly["is_global"])
+            if cache is not None:
+                vt = cache.vt[i]
             ops.rmsnorm_weight_rows(x, ly["n_in"], c.rms_norm_eps, out=nx)
             ops.gemm(nx, ly["qkv"], None, out=qk, out2=vt, n_split=nq + nkv, out_tokens_per_batch=T, split_k=False)
             ops.headnorm_rope(qk, Hq, Hkv, ly["qn"], ly["kn"], cos, sin, T, c.rms_norm_eps)
+            if cache is not None:
+                cache.k[i][:, :T].copy_(qk.view(B, T, nq + nkv)[:, :, nq:])
             ops.causal_attn(qk[:, :nq], qk[:, nq:], vt, att, row_start, B, Hq, Hkv, T, self.scale, window=ly["window"])
             ops.gemm(att, ly["o"], None, out=po, split_k=False)
             # the layer's output goes straight into its slot of the stack (the last layer's into scratch: its slot takes norm(h_L))
@@ -212,7 +232,203 @@ class GemmaEncoder:
             ops.rmsnorm_weight_rows(po, ly["n_post_ff"], c.rms_norm_eps, resid=y, out=y)
             x = y
         ops.rmsnorm_weight_rows(x, self.norm, c.rms_norm_eps, out=states[L].view(M, D))
+        if cache is not None:
+            cache.row_start, cache.length = row_start, T
         return states
+
+
+# ------------------------------------------------------------------------------------------------------------ decoding
+class GemmaCache:
+    """The KV cache of one generation: per layer K (B, cap, Hkv*256) and V^T (B, Hkv*256, cap) bf16 - the attention kernels'
+    own operand layouts, zero-initialised so that positions past the live length are finite - and the attention step's
+    fp32 ``partials`` (one buffer: the launches of a stream are ordered, so the layers share it).  ``length``: the live
+    length = the padded-sequence position of the next token; ``row_start`` (B) int32 on the device, set by the prefill."""
+
+    def __init__(self, config: GemmaConfig, B: int, capacity: int, device):
+        if capacity < 1 or capacity % ops.CAUSAL_ATTN_BK:
+            raise ValueError(f"GemmaCache: capacity {capacity} must be a positive multiple of {ops.CAUSAL_ATTN_BK}")
+        nkv = config.num_key_value_heads * HEAD_DIM
+        L = config.num_hidden_layers
+        self.capacity, self.B, self.length = int(capacity), int(B), 0
+        self.k = [torch.zeros((B, capacity, nkv), dtype=BF16, device=device) for _ in range(L)]
+        self.vt = [torch.zeros((B, nkv, capacity), dtype=BF16, device=device) for _ in range(L)]
+        slices = -(-capacity // ops.CAUSAL_ATTN_STEP_SLICE)
+        self.partials = torch.empty(B * config.num_attention_heads * slices * ops.CAUSAL_ATTN_STEP_PART, dtype=torch.float32, device=device)
+        self.row_start: Optional[torch.Tensor] = None
+
+
+def apply_repetition_penalty(logits: torch.Tensor, context: Sequence[Sequence[int]], penalty: float) -> torch.Tensor:
+    """(B,V) fp32 logits with the ids of ``context[b]`` penalised: a negative logit is multiplied by ``penalty``, any other divided
+    by it - the rule of ``transformers``' RepetitionPenaltyLogitsProcessor (and of mlx_lm's make_logits_processors, which the
+    reference calls).  A new tensor."""
+    out = logits.clone()
+    for b, ctx in enumerate(context):
+        if len(ctx) and penalty != 1.0:
+            idx = torch.tensor(sorted(set(int(t) for t in ctx)), dtype=torch.int64, device=logits.device)
+            sc = out[b, idx]
+            out[b, idx] = torch.where(sc < 0, sc * penalty, sc / penalty)
+    return out
+
+
+def sample_tokens(logits: torch.Tensor, context: Sequence[Sequence[int]], temperature: float, repetition_penalty: float,
+                  generator: Optional[torch.Generator]) -> torch.Tensor:
+    """One token per row of (B,V) fp32 host logits: the repetition penalty over ``context[b]``, then argmax at temperature 0,
+    else a categorical draw from softmax(logits / temperature) with ``generator``.  (B,) int64."""
+    lg = apply_repetition_penalty(logits.detach().to("cpu").to(torch.float32), context, repetition_penalty)
+    if temperature == 0:
+        return lg.argmax(-1)
+    if temperature < 0:
+        raise ValueError(f"temperature must be >= 0, got {temperature}")
+    return torch.multinomial(torch.softmax(lg / temperature, -1), 1, generator=generator)[:, 0]
+
+
+class GemmaGenerator:
+    """KV-cached autoregressive decoding on a ``GemmaEncoder``'s panels (nothing is copied; Gemma-3 ties the output head to
+    the embedding table).  ``prefill`` runs the encoder's layer loop into a ``GemmaCache``; ``step`` runs one token: per layer
+    the input norm, one q|k|v GEMM at M = B rows in the weight-streaming split-K form, norm + RoPE with the table row of the
+    token's position, the attention step against the cache (which appends the token's K and V), o-proj, norms, gate|up, GeGLU,
+    down; then the final norm and the logits GEMM over the embedding table.  Positions are padded-sequence indices, the
+    encoder's convention."""
+
+    def __init__(self, encoder: GemmaEncoder):
+        if encoder.cfg.final_logit_softcapping is not None:
+            raise ValueError(f"GemmaGenerator: final_logit_softcapping={encoder.cfg.final_logit_softcapping}: logit soft-capping is not supported")
+        if encoder.cfg.num_attention_heads // encoder.cfg.num_key_value_heads > 16:
+            raise ValueError("GemmaGenerator: more than 16 query heads per KV head are not supported by the attention step")
+        if encoder.vocab % 8:
+            raise ValueError(f"GemmaGenerator: the vocabulary {encoder.vocab} must be a multiple of 8 (the logits GEMM)")
+        self.enc, self.cfg = encoder, encoder.cfg
+
+    def _logits(self, h: torch.Tensor) -> torch.Tensor:
+        return ops.gemm(h, self.enc.embed, None).to(torch.float32)
+
+    def prefill(self, input_ids: torch.Tensor, attention_mask: torch.Tensor, capacity: int, return_states: bool = False):
+        """(cache, logits (B,V) fp32 of the last position) for a left-padded (B,T) prompt, T <= capacity (a multiple of 64);
+        with ``return_states`` also the encoder's (L+1, B, T, D) states."""
+        B, T = input_ids.shape
+        if T > capacity:
+            raise ValueError(f"prefill: {T} prompt positions do not fit a cache of capacity {capacity}")
+        cache = GemmaCache(self.cfg, B, capacity, self.enc.device)
+        states = self.enc._forward(input_ids, attention_mask, cache)
+        logits = self._logits(states[-1][:, T - 1])
+        return (cache, logits, states) if return_states else (cache, logits)
+
+    def step(self, cache: GemmaCache, token_ids, return_states: bool = False):
+        """logits (B,V) fp32 after feeding one token per batch row at position ``cache.length``; the cache grows by one.  With
+        ``return_states`` also the token's (L+1, B, D) hidden states, the encoder's list at that position."""
+        e, c, dev = self.enc, self.cfg, self.enc.device
+        pos, cap, B = cache.length, cache.capacity, cache.B
+        if cache.row_start is None:
+            raise ValueError("step: the cache has not been prefilled")
+        if pos >= cap:
+            raise ValueError(f"step: the cache is full ({cap} positions)")
+        ids_host = torch.as_tensor(token_ids).detach().to("cpu").reshape(-1).to(torch.int64)
+        if ids_host.numel() != B:
+            raise ValueError(f"step: {ids_host.numel()} token ids for a cache of {B} batch rows")
+        D, F, L = c.hidden_size, c.intermediate_size, c.num_hidden_layers
+        Hq, Hkv = c.num_attention_heads, c.num_key_value_heads
+        nq, nkv = Hq * HEAD_DIM, Hkv * HEAD_DIM
+        states = torch.empty((L + 1, B, D), dtype=BF16, device=dev)
+        x = ops.embed_rows(e.embed, ids_host.to(torch.int32).to(dev), e.embed_scale, out=states[0], ids_host=ids_host)
+        nx = torch.empty((B, D), dtype=BF16, device=dev)
+        qkv = torch.empty((B, nq + 2 * nkv), dtype=BF16, device=dev)
+        att = torch.empty((B, nq), dtype=BF16, device=dev)
+        po = torch.empty((B, D), dtype=BF16, device=dev)
+        gu = torch.empty((B, 2 * F), dtype=BF16, device=dev)
+        for i, ly in enumerate(e.layers):
+            cos, sin = e._tables(cap, ly["is_global"])
+            ops.rmsnorm_weight_rows(x, ly["n_in"], c.rms_norm_eps, out=nx)
+            ops.gemm(nx, ly["qkv"], None, out=qkv, split_k=True)
+            ops.headnorm_rope(qkv, Hq, Hkv, ly["qn"], ly["kn"], cos[pos:pos + 1], sin[pos:pos + 1], 1, c.rms_norm_eps)
+            ops.causal_attn(qkv[:, :nq], cache.k[i].view(B * cap, nkv), cache.vt[i], att, cache.row_start, B, Hq, Hkv, cap, e.scale,
+                            window=ly["window"], step=pos, k_new=qkv[:, nq:nq + nkv], v_new=qkv[:, nq + nkv:], partials=cache.partials)
+            ops.gemm(att, ly["o"], None, out=po, split_k=True)
+            y = states[i + 1] if i + 1 < L else nx.new_empty((B, D))
+            ops.rmsnorm_weight_rows(po, ly["n_post_attn"], c.rms_norm_eps, resid=x, out=y)
+            ops.rmsnorm_weight_rows(y, ly["n_pre_ff"], c.rms_norm_eps, out=nx)
+            ops.gemm(nx, ly["gu"], None, out=gu, split_k=True)
+            h = ops.geglu_tanh_(gu)
+            ops.gemm(h, ly["down"], None, out=po, split_k=True)
+            ops.rmsnorm_weight_rows(po, ly["n_post_ff"], c.rms_norm_eps, resid=y, out=y)
+            x = y
+        ops.rmsnorm_weight_rows(x, e.norm, c.rms_norm_eps, out=states[L])
+        cache.length = pos + 1
+        logits = self._logits(states[L])
+        return (logits, states) if return_states else logits
+
+    def generate(self, input_ids: torch.Tensor, attention_mask: torch.Tensor, max_tokens: int = 512, temperature: float = 0.7,
+                 repetition_penalty: float = 1.3, repetition_context: int = 20, eos_ids: Sequence[int] = (1, 107),
+                 seed: int = 42) -> List[List[int]]:
+        """The new tokens of each batch row, its terminating EOS id included (generation of a row ends there, or at
+        ``max_tokens``).  The defaults are the reference's call (text_encoder.py:1079-1084, 1123): temperature 0.7, repetition
+        penalty 1.3 over the last 20 tokens (the prompt's included), EOS ids 1 and 107.  Sampling is host torch on the fp32
+        logits with a ``torch.Generator`` seeded by ``seed``: seeds are NOT cross-compatible with MLX's generator - the same
+        seed gives the same tokens here and other tokens there (the project's standing convention for random numbers)."""
+        B, T = input_ids.shape
+        if max_tokens < 1:
+            return [[] for _ in range(B)]
+        cache, logits = self.prefill(input_ids, attention_mask, (T + max_tokens + 63) // 64 * 64)
+        ids_host, mask_host = input_ids.detach().to("cpu"), attention_mask.detach().to("cpu").bool()
+        history = [[int(t) for t in ids_host[b][mask_host[b]]] for b in range(B)]
+        gen = torch.Generator(device="cpu").manual_seed(int(seed))
+        eos = set(int(t) for t in eos_ids)
+        out: List[List[int]] = [[] for _ in range(B)]
+        done = [False] * B
+        for n in range(max_tokens):
+            ctx = [h[-repetition_context:] if repetition_context > 0 else [] for h in history]
+            tok = sample_tokens(logits, ctx, temperature, repetition_penalty, gen)
+            for b in range(B):
+                if not done[b]:
+                    t = int(tok[b])
+                    out[b].append(t)
+                    history[b].append(t)
+                    done[b] = t in eos
+            if all(done) or n + 1 == max_tokens:
+                break
+            logits = self.step(cache, tok)          # (a finished row keeps feeding its last token; its output is not kept)
+        return out
+
+
+# ------------------------------------------------------------------------------------------------------ prompt enhancement
+DEFAULT_ENHANCE_SYSTEM_PROMPT = (
+    "You rewrite short video ideas into one detailed prompt for a text-to-video model. Keep the user's subject and intent. "
+    "Describe, in a single flowing paragraph of present-tense sentences and in chronological order: the main subject and its "
+    "appearance, the action and how it unfolds, the setting and background, the lighting and colours, and the camera's framing "
+    "and movement. Be concrete and visual; do not invent dialogue, titles or on-screen text; do not address the user, add "
+    "commentary or use lists. Answer with the rewritten prompt only, in at most 200 words.")
+
+
+def chat_prompt(system_prompt: str, prompt: str) -> str:
+    """The reference's message layout (text_encoder.py:998-1021, 1055-1058) in Gemma-3's turn format: the system text sent as a
+    user turn, a user turn ``user prompt: {prompt}``, then the model turn's opener."""
+    return (f"<start_of_turn>user\n{system_prompt}<end_of_turn>\n"
+            f"<start_of_turn>user\nuser prompt: {prompt}<end_of_turn>\n"
+            "<start_of_turn>model\n")
+
+
+def clean_response(text: str) -> str:
+    """Whitespace stripped, then any leading punctuation removed (text_encoder.py:990-996)."""
+    return re.sub(r"^[^\w\s]+", "", text.strip())
+
+
+def enhance_prompt(generator: GemmaGenerator, tokenizer, prompt: str, system_prompt: Optional[str] = None, max_tokens: int = 512,
+                   temperature: float = 0.7, seed: int = 42, **sampling) -> str:
+    """The user's short prompt rewritten by the model into the long descriptive one LTX-2 was trained on (the reference's
+    ``enhance_t2v``, text_encoder.py:1023-1135).  ``tokenizer``: a ``tokenizers.Tokenizer`` (``load_tokenizer``).  Only the new
+    tokens are decoded (special tokens skipped) and cleaned; an empty result keeps ``prompt`` and warns.  ``sampling``: further
+    keywords of ``GemmaGenerator.generate`` (repetition_penalty, repetition_context, eos_ids)."""
+    text = chat_prompt(system_prompt or DEFAULT_ENHANCE_SYSTEM_PROMPT, prompt)
+    tokenizer.no_padding(); tokenizer.no_truncation()
+    ids = list(tokenizer.encode(text).ids)
+    if not ids:
+        raise ValueError("enhance_prompt: the tokenizer produced no tokens for the chat prompt")
+    input_ids = torch.tensor([ids], dtype=torch.int64)
+    new = generator.generate(input_ids, torch.ones_like(input_ids), max_tokens=max_tokens, temperature=temperature, seed=seed, **sampling)[0]
+    out = clean_response(tokenizer.decode(new, skip_special_tokens=True))
+    if not out:
+        warnings.warn("prompt enhancement produced an empty result: the original prompt is kept")
+        return prompt
+    return out
 
 
 def random_gemma_weights(device, config: GemmaConfig, seed: int = 23, generator_device=None) -> Dict[str, torch.Tensor]:

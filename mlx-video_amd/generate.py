@@ -223,6 +223,37 @@ def _encode_gemma(gemma, gemma_repo, tokenizer_path, prompt, negative_prompt, pr
     return gemma(ids, mask), mask
 
 
+def _check_enhance(gemma, gemma_repo, text_encoder_repo, tokenizer_path, prompt_tokens, prompt_embeds, gemma_hidden_states, text_encoder):
+    """enhance_prompt's preconditions, before anything is loaded: a Gemma-3 model, a tokenizer, and a prompt read as a string."""
+    if gemma_repo is None and text_encoder_repo and Path(text_encoder_repo).is_dir():
+        gemma_repo = text_encoder_repo
+    missing = []
+    if gemma is None and gemma_repo is None:
+        missing.append("a Gemma-3 model: gemma= (a GemmaEncoder) or gemma_repo= (a local Gemma-3 directory, --gemma-repo)")
+    if tokenizer_path is None and gemma_repo is None:
+        missing.append("a tokenizer: tokenizer_path= (--tokenizer) or gemma_repo= a local directory with a tokenizer.json")
+    if missing:
+        raise ValueError("enhance_prompt (--enhance-prompt) needs " + " and ".join(missing))
+    given = [n for n, v in (("prompt_tokens", prompt_tokens), ("prompt_embeds", prompt_embeds), ("gemma_hidden_states", gemma_hidden_states),
+                            ("text_encoder", text_encoder)) if v is not None]
+    if given:
+        raise ValueError(f"enhance_prompt (--enhance-prompt) rewrites the prompt string, which {', '.join(given)} replaces: drop one of the two")
+
+
+def _enhance_prompt(gemma, gemma_repo, tokenizer_path, prompt, system_prompt, max_tokens, temperature, seed, dev, verbose):
+    """(the GemmaEncoder, the enhanced prompt): the encoder is built here when only ``gemma_repo`` was given, and handed on so that
+    the text encode that follows reuses its panels."""
+    from .gemma import GemmaConfig, GemmaEncoder, GemmaGenerator, enhance_prompt, load_tokenizer
+    if gemma is None:
+        from .weights import gemma_weights
+        gemma = GemmaEncoder(gemma_weights(gemma_repo, dev), GemmaConfig.from_json(gemma_repo))
+    tok = load_tokenizer(tokenizer_path or gemma_repo)
+    enhanced = enhance_prompt(GemmaGenerator(gemma), tok, prompt, system_prompt, max_tokens=max_tokens, temperature=temperature, seed=seed)
+    if verbose:
+        print(f"enhanced prompt: {enhanced}")
+    return gemma, enhanced
+
+
 def generate_video(model_repo: Optional[str] = None, text_encoder_repo: Optional[str] = None, prompt: str = "",
                    pipeline: PipelineType = PipelineType.DISTILLED, negative_prompt: str = DEFAULT_NEGATIVE_PROMPT,
                    height: int = 512, width: int = 512, num_frames: int = 33, num_inference_steps: int = 40,
@@ -249,7 +280,9 @@ def generate_video(model_repo: Optional[str] = None, text_encoder_repo: Optional
                    negative_gemma_hidden_states=None, negative_gemma_attention_mask: Optional[torch.Tensor] = None,
                    text_connector=None, guider: Optional[str] = None, apg_eta: float = 1.0,
                    apg_norm_threshold: float = 0.0, gemma=None, gemma_repo: Optional[str] = None,
-                   tokenizer_path: Optional[str] = None, prompt_tokens=None, negative_prompt_tokens=None) -> np.ndarray:
+                   tokenizer_path: Optional[str] = None, prompt_tokens=None, negative_prompt_tokens=None,
+                   enhance_prompt: bool = False, max_tokens: int = 512, temperature: float = 0.7,
+                   enhance_system_prompt: Optional[str] = None) -> np.ndarray:
     """See the module docstring.  Returns uint8 frames (F,H,W,3) (generate.py:4195-4197).
     ``hoist_context`` (not in the reference, off by default): the part of the forward that depends on the text context only -
     caption projection and the 48 cross-attention K / V^T projections, 3.37 TFLOP that the reference recomputes in every forward
@@ -277,12 +310,21 @@ def generate_video(model_repo: Optional[str] = None, text_encoder_repo: Optional
     1024; nothing is fetched).  ``prompt_embeds``, ``gemma_hidden_states`` and ``text_encoder`` keep their precedence over it, in that order.
     ``guider`` / ``apg_eta`` / ``apg_norm_threshold`` (--guider / --apg-eta / --apg-norm-threshold; not in the reference CLI, the
     guiders are ltx_core/components/guiders.py): what the CFG slot of every guided (denoise_dev) stage runs - "cfg" (None: the
-    same), "cfg_star" or "apg" (DESIGN.md 5j).  A non-default guider on a run without a guided stage is a ValueError, as for STG."""
+    same), "cfg_star" or "apg" (DESIGN.md 5j).  A non-default guider on a run without a guided stage is a ValueError, as for STG.
+    ``enhance_prompt`` / ``max_tokens`` / ``temperature`` (--enhance-prompt / --max-tokens / --temperature, the reference's names
+    and defaults) and ``enhance_system_prompt`` (the system text; --enhance-system-prompt FILE; None: the package's default): the
+    positive ``prompt`` is first rewritten by Gemma-3 itself (``gemma.enhance_prompt``: KV-cached decoding on the encoder's panels,
+    sampled with ``seed``) and the rewritten string takes the text route above.  It needs ``gemma`` or ``gemma_repo``
+    and a tokenizer.json (``tokenizer_path`` or ``gemma_repo``), a ValueError that names what is missing otherwise, and a prompt
+    that the text route reads as a string (no ``prompt_tokens`` / ``prompt_embeds`` / ``gemma_hidden_states`` in its place).  Off, the
+    default, nothing of it runs."""
     t_start = time.perf_counter()
     if isinstance(pipeline, str):
         pipeline = PipelineType(pipeline)
     if audio:
         raise ValueError("audio generation is not supported (audio branch is out of scope, SURVEY.md §2a #21)")
+    if enhance_prompt:
+        _check_enhance(gemma, gemma_repo, text_encoder_repo, tokenizer_path, prompt_tokens, prompt_embeds, gemma_hidden_states, text_encoder)
     images_list = list(images or [])
     if image is not None:
         images_list.append((image, image_frame_idx, image_strength))
@@ -394,6 +436,11 @@ def generate_video(model_repo: Optional[str] = None, text_encoder_repo: Optional
                                                                negative_gemma_attention_mask, text_connector, model_repo, dev)
     if gemma_repo is None and text_encoder_repo and Path(text_encoder_repo).is_dir():
         gemma_repo = text_encoder_repo          # the reference's name for it; a repo NAME is not resolved (nothing is fetched)
+    timer = _PhaseTimer(profile or bool(profile_json_path))
+    if enhance_prompt:
+        with timer.phase("prompt_enhance"):
+            gemma, prompt = _enhance_prompt(gemma, gemma_repo, tokenizer_path, prompt, enhance_system_prompt, max_tokens, temperature,
+                                            seed, dev, verbose)
     if prompt_embeds is None and text_encoder is None and (gemma is not None or gemma_repo is not None):
         hs, m = _encode_gemma(gemma, gemma_repo, tokenizer_path, prompt, negative_prompt, prompt_tokens, negative_prompt_tokens, dev)
         prompt_embeds, negative_prompt_embeds = _connect_gemma(hs[:, 0:1], m[0:1], hs[:, 1:2], m[1:2], text_connector, model_repo, dev)
@@ -408,7 +455,6 @@ def generate_video(model_repo: Optional[str] = None, text_encoder_repo: Optional
     ctx_pos = prompt_embeds.to(dev).to(BF16)
     ctx_neg = (negative_prompt_embeds if negative_prompt_embeds is not None else torch.zeros_like(prompt_embeds)).to(dev).to(BF16)
 
-    timer = _PhaseTimer(profile or bool(profile_json_path))
     guide = conditioning_mode == "guide"
 
     def init_state(shape, conds, sigma0):
@@ -642,6 +688,11 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--prompt-tokens", type=str, default=None,
                     help="(not in the reference CLI) .npz with `input_ids` and `attention_mask`, left-padded: the tokenised --prompt")
     ap.add_argument("--negative-prompt-tokens", type=str, default=None, help="the same for the negative prompt")
+    ap.add_argument("--enhance-prompt", action="store_true", help="Enhance the prompt using Gemma (needs --gemma-repo and a tokenizer.json)")
+    ap.add_argument("--max-tokens", type=int, default=512, help="Max tokens for prompt enhancement")
+    ap.add_argument("--temperature", type=float, default=0.7, help="Temperature for prompt enhancement")
+    ap.add_argument("--enhance-system-prompt", type=str, default=None, metavar="FILE",
+                    help="(not in the reference CLI) text file with the system prompt of --enhance-prompt (default: the package's own)")
     ap.add_argument("--synthetic", action="store_true", help="random-init weights + random text embeddings (no checkpoints offline)")
     ap.add_argument("--layers", type=int, default=48)
     # spatio-temporal guidance (the reference's spellings and defaults; it ignores them, this port runs them)
@@ -788,6 +839,10 @@ def main(argv: Optional[Sequence[str]] = None) -> None:
         kw["prompt_tokens"] = load_prompt_tokens(args.prompt_tokens)
     if args.negative_prompt_tokens:
         kw["negative_prompt_tokens"] = load_prompt_tokens(args.negative_prompt_tokens)
+    if args.enhance_prompt:
+        kw.update(enhance_prompt=True, max_tokens=args.max_tokens, temperature=args.temperature)
+        if args.enhance_system_prompt:
+            kw["enhance_system_prompt"] = Path(args.enhance_system_prompt).read_text(encoding="utf-8")
     generate_video(model_repo=args.model_repo, prompt=args.prompt, pipeline=PipelineType(args.pipeline),
                    negative_prompt=args.negative_prompt, height=args.height, width=args.width, num_frames=args.num_frames,
                    num_inference_steps=args.steps, cfg_scale=args.cfg_scale, seed=args.seed, fps=args.fps,

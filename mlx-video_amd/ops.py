@@ -919,20 +919,58 @@ def geglu_tanh_(gu: torch.Tensor) -> torch.Tensor:
     return gu[:, :F]
 
 
+CAUSAL_ATTN_STEP_SLICE = 256  # keys per workgroup of ltxk_causal_attn_step
+CAUSAL_ATTN_STEP_PART = 258   # floats of one partial: M, l, O[256]
+
+
 def causal_attn(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, out: torch.Tensor, row_start: torch.Tensor, B: int, Hq: int,
-                Hkv: int, T: int, scale: float, window: int = 0) -> torch.Tensor:
+                Hkv: int, T: int, scale: float, window: int = 0, *, step: Optional[int] = None, k_new: Optional[torch.Tensor] = None,
+                v_new: Optional[torch.Tensor] = None, partials: Optional[torch.Tensor] = None) -> torch.Tensor:
     """ltxk_causal_attn (head dim 256): q (B*T, >= Hq*256) view, k (B*T, >= Hkv*256) view, vt (B, Hkv*256, ldvt >= T),
     out (B*T, >= Hq*256) view, row_start (B) int32 on the device (valid tokens of batch row b: [row_start[b], T)).  Key j is
-    visible to query i iff row_start <= j <= i and (window == 0 or i - j < window); rows below row_start come out zero."""
+    visible to query i iff row_start <= j <= i and (window == 0 or i - j < window); rows below row_start come out zero.
+
+    With ``step`` (ltxk_causal_attn_step): one query position per batch row against a KV cache.  ``k`` / ``vt`` are the cache in
+    the same layouts with T its capacity (a multiple of 64), q / out are (B, >= Hq*256) rows, ``k_new`` / ``v_new`` (B, >= Hkv*256)
+    the step's rotated key and its value - read in the place of cache position ``step`` and stored there by the launch - and
+    ``partials`` a caller-owned fp32 buffer of at least B * Hq * slices * CAUSAL_ATTN_STEP_PART floats, the 256-key slices of a
+    launch being [s0, step/256] with s0 = max(0, step - window + 1) / 256 under a window, else 0 (B * Hq * ceil(T/256) * 258
+    floats serve every step).  Key j is visible iff row_start <= j <= step and (window == 0 or step - j < window)."""
     nq, nkv = Hq * GEMMA_HEAD_DIM, Hkv * GEMMA_HEAD_DIM
-    _operands("causal_attn", ("q", q, BF16, (B * T, -nq), 16, True), ("k", k, BF16, (B * T, -nkv), 16, True),
-              ("vt", vt, BF16, (B, nkv, -T), 16, True), ("out", out, BF16, (B * T, -nq), 16, True), ("row_start", row_start, I32, (B,), 4))
-    a = CausalAttnArgs()
-    a.q, a.k, a.vt, a.out, a.row_start = _p(q), _p(k), _p(vt), _p(out), _p(row_start)
-    a.ldq, a.ldk, a.ldvt, a.ldo = q.stride(0), k.stride(0), vt.stride(1), out.stride(0)
-    a.B, a.Hq, a.Hkv, a.T, a.window, a.scale = B, Hq, Hkv, T, window, scale
-    with _timed("causal_attn", 2.0 * B * Hq * T * T * GEMMA_HEAD_DIM, 2.0 * B * T * GEMMA_HEAD_DIM * (2 * Hq + 2 * Hkv)):
-        check(_lib.load().ltxk_causal_attn(ctypes.byref(a), _stream()), "ltxk_causal_attn")
+    if step is None:
+        if k_new is not None or v_new is not None or partials is not None:
+            raise ValueError("causal_attn: k_new, v_new and partials belong to the step form (step=)")
+        _operands("causal_attn", ("q", q, BF16, (B * T, -nq), 16, True), ("k", k, BF16, (B * T, -nkv), 16, True),
+                  ("vt", vt, BF16, (B, nkv, -T), 16, True), ("out", out, BF16, (B * T, -nq), 16, True), ("row_start", row_start, I32, (B,), 4))
+        a = CausalAttnArgs()
+        a.q, a.k, a.vt, a.out, a.row_start = _p(q), _p(k), _p(vt), _p(out), _p(row_start)
+        a.ldq, a.ldk, a.ldvt, a.ldo = q.stride(0), k.stride(0), vt.stride(1), out.stride(0)
+        a.B, a.Hq, a.Hkv, a.T, a.window, a.scale = B, Hq, Hkv, T, window, scale
+        with _timed("causal_attn", 2.0 * B * Hq * T * T * GEMMA_HEAD_DIM, 2.0 * B * T * GEMMA_HEAD_DIM * (2 * Hq + 2 * Hkv)):
+            check(_lib.load().ltxk_causal_attn(ctypes.byref(a), _stream()), "ltxk_causal_attn")
+        return out
+    missing = [n for n, t in (("k_new", k_new), ("v_new", v_new), ("partials", partials)) if t is None]
+    if missing:
+        raise ValueError(f"causal_attn: the step form needs {', '.join(missing)}")
+    if B < 1 or Hq < 1 or Hkv < 1 or Hq % Hkv or Hq // Hkv > 16:
+        raise ValueError(f"causal_attn: the step form takes Hq = {Hq} a multiple of Hkv = {Hkv}, at most 16 times it")
+    if T < 1 or T % CAUSAL_ATTN_BK:
+        raise ValueError(f"causal_attn: the cache capacity T = {T} must be a positive multiple of {CAUSAL_ATTN_BK}")
+    if not 0 <= step < T:
+        raise ValueError(f"causal_attn: step = {step} must lie in [0, {T}), the cache capacity")
+    if window < 0:
+        raise ValueError(f"causal_attn: window = {window} must be 0 (none) or a positive count")
+    s0 = max(0, step - window + 1) // CAUSAL_ATTN_STEP_SLICE if window else 0
+    need = B * Hq * (step // CAUSAL_ATTN_STEP_SLICE + 1 - s0) * CAUSAL_ATTN_STEP_PART
+    _operands("causal_attn", ("q", q, BF16, (B, -nq), 16, True), ("k", k, BF16, (B * T, -nkv), 16, True),
+              ("vt", vt, BF16, (B, nkv, -T), 16, True), ("out", out, BF16, (B, -nq), 16, True), ("row_start", row_start, I32, (B,), 4),
+              ("k_new", k_new, BF16, (B, -nkv), 16, True), ("v_new", v_new, BF16, (B, -nkv), 16, True),
+              ("partials", partials, F32, (-need,), 16))
+    live = min(step + 1, window) if window else step + 1
+    with _timed("causal_attn_step", 4.0 * B * Hq * live * GEMMA_HEAD_DIM, 4.0 * B * Hkv * live * GEMMA_HEAD_DIM):
+        check(_lib.load().ltxk_causal_attn_step(_p(q), q.stride(0), _p(k_new), k_new.stride(0), _p(v_new), v_new.stride(0), _p(k), k.stride(0),
+                                                _p(vt), vt.stride(1), _p(out), out.stride(0), _p(row_start), B, Hq, Hkv, T, step, window,
+                                                scale, _p(partials), partials.numel(), _stream()), "ltxk_causal_attn_step")
     return out
 
 

@@ -3,7 +3,7 @@
 The reference's text path (mlx_video/models/ltx/text_encoder.py) is Gemma-3-12B followed by three LTX-2 modules whose
 weights live in the LTX-2 checkpoint: ``norm_and_concat_hidden_states`` (591-639), ``GemmaFeaturesExtractor`` (642-649,
 Linear(L*D -> D), no bias) and ``Embeddings1DConnector`` (426-587).  This module runs those three; Gemma itself, the
-tokenizer, prompt enhancement and the audio connector stay outside the package.  The input boundary is therefore "the
+tokenizer and prompt enhancement are gemma.py's; the audio connector stays outside the package.  The input boundary is therefore "the
 L hidden states of a stock Gemma-3 (``output_hidden_states=True``) plus its 0/1 attention mask", left-padded as the
 reference tokenises.
 
