@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define LTXK_VERSION 411
+#define LTXK_VERSION 412
 
 #define LTXK_OK 0
 #define LTXK_EINVAL (-1)   /* bad argument (shape / alignment / null pointer) */
@@ -650,7 +650,7 @@ int ltxk_conv3d_k3_bf16(const ltxk_conv3d_args* args, void* stream);
  * of the same arguments cannot disagree; the same argument checks run and return the same error codes.
  * Every form computes a row's sum with the same rounding points; the kw-reuse kernel and the split-K slices walk K in another
  * order than the per-tap single pass.  A tail launch gives its rows the bits of the main tile.                            */
-enum { LTXK_CONV_KERNEL_PER_TAP = 0, LTXK_CONV_KERNEL_KW = 1 };
+enum { LTXK_CONV_KERNEL_PER_TAP = 0, LTXK_CONV_KERNEL_KW = 1, LTXK_CONV_KERNEL_TAPS = 2 /* ltxk_conv_taps_bf16 */ };
 struct ltxk_conv3d_plan {   /* a struct tag only: the name is also the function's */
   int32_t kernel;               /* LTXK_CONV_KERNEL_*: one A tile per tap, or one A panel per (kd, kh) shared by the 3 kw taps */
   int32_t tile_rows, tile_cols; /* workgroup tile of the main launch: 256 x 128 or 160 x 256 (kw: 256 x 128)             */
@@ -667,6 +667,54 @@ struct ltxk_conv3d_plan {   /* a struct tag only: the name is also the function'
 int ltxk_conv3d_plan(const ltxk_conv3d_args* args, struct ltxk_conv3d_plan* plan);
 /* sizeof(struct ltxk_conv3d_plan) in this build (an entry of its own: the ltxk_abi_sizeof index list is closed).          */
 int ltxk_conv3d_plan_sizeof(void);
+
+/* ---------------------------------------------------------------------------------------
+ * Audio VAE decoder and vocoder: a stride-1 convolution over the frames of a channels-last volume as implicit GEMM.
+ * Replaces the causal 3x3 nn.Conv2d of the audio decoder (audio_vae/causal_conv_2d.py, resnet.py, upsample.py) and the
+ * dilated nn.Conv1d / polyphase-packed nn.ConvTranspose1d of the vocoder (audio_vae/vocoder.py; time is H, W = 1).
+ * Every one of the B*D frames is an (H,W) image of its own: no tap reads across a frame or batch boundary.
+ *
+ *   y[b,d,h,w,co] = bias[co] + sum_{i<kh, j<kw, ci} x[b,d, h + i*dil_h - pad_top, w + j - pad_left, ci] * w[co,i,j,ci]
+ *
+ * with terms outside the frame zero (they read zero_page; no padded copy exists) and the output extent the input's:
+ * pad_top + pad_bottom == (kh-1)*dil_h, pad_left + pad_right == kw-1.  kh <= 16, kw in {1,3}, dil_h <= 8, Cin 32 or a multiple
+ * of 64 (at 32 a 64-wide K-step spans two taps; with an odd tap count the last half step reads zero_page on both operand
+ * sides), any Cout >= 1 (only valid columns are stored), M = B*D*H*W >= 1.
+ * One epilogue, rounding in this order (acc fp32):
+ *   1. y = bf16(acc + bias)
+ *   2. resid:           y = bf16(y + resid)
+ *   3. n_mean = 2 | 3:  y = bf16((y + mean_a1 [+ mean_a2]) / n_mean), summed in fp32 in that order
+ *   4. out = y                                        (optional)
+ *   5. act_out = max(y, bf16(y * slope))              (optional; leaky ReLU as resnet.py:15-17 writes it)
+ *   6. out_f32 = tanhf(acc + bias), fp32, unrounded   (conv_post + tanh; excludes 2-5)
+ * Small launches split K as ltxk_conv3d_k3_bf16 does: fp32 slabs [slice][M][round_up(Cout,4)] in the workspace, a finalize
+ * launch that sums in slice order and runs the same epilogue.  No atomics: bits depend on the arguments alone.             */
+typedef struct ltxk_conv_taps_args {
+  int32_t struct_bytes;   /* sizeof(ltxk_conv_taps_args) of the caller's build; checked                                  */
+  int32_t B, D, H, W, Cin, Cout;
+  int32_t kh, kw, dil_h;
+  int32_t pad_top, pad_bottom, pad_left, pad_right;
+  int32_t n_mean;         /* 0, or 2 / 3 with mean_a1 [/ mean_a2]                                                        */
+  float slope;            /* of act_out                                                                                  */
+  const void* x;          /* (B,D,H,W,Cin) bf16, 16-byte aligned                                                         */
+  const void* w;          /* (Cout,kh,kw,Cin) bf16, 16-byte aligned                                                      */
+  const void* bias;       /* (Cout) bf16                                                                                 */
+  const void* zero_page;  /* >= 128 zero bytes, 16-byte aligned                                                          */
+  const void* resid;      /* (M,Cout) bf16 or NULL                                                                       */
+  const void* mean_a1;    /* (M,Cout) bf16, n_mean >= 2                                                                  */
+  const void* mean_a2;    /* (M,Cout) bf16, n_mean == 3                                                                  */
+  void* out;              /* (M,Cout) bf16 or NULL                                                                       */
+  void* act_out;          /* (M,Cout) bf16 or NULL                                                                       */
+  float* out_f32;         /* (M,Cout) fp32 or NULL: the tanh form                                                        */
+  void* workspace;        /* fp32 split-K scratch or NULL (no split-K)                                                   */
+  int64_t workspace_bytes;
+} ltxk_conv_taps_args;
+
+int ltxk_conv_taps_bf16(const ltxk_conv_taps_args* args, void* stream);
+/* The launch form of ltxk_conv_taps_bf16 for `args`, by the host function the launch uses: kernel = LTXK_CONV_KERNEL_TAPS,
+ * tile 256 x 128 (Cout > 64) or 256 x 64, ksteps = 64-wide K-steps per slice (ceil(kh*kw*Cin / 64) in all), no tail launch,
+ * fused_act = 0 (that field speaks of the PixelNorm epilogue).                                                          */
+int ltxk_conv_taps_plan(const ltxk_conv_taps_args* args, struct ltxk_conv3d_plan* plan);
 
 /* pixel_norm over channels [+ (1+scale)+shift per (batch,channel)] [+ SiLU]: decoder.py:136-180,
  * 415-437; utils.py:477-483.  x,y: (V,C) rows = voxels, C in {64..2048, power of two}.

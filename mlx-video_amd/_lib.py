@@ -78,6 +78,20 @@ class Conv3dArgs(Structure):
     ]
 
 
+class ConvTapsArgs(Structure):
+    _fields_ = [
+        ("struct_bytes", c_int32),
+        ("B", c_int32), ("D", c_int32), ("H", c_int32), ("W", c_int32), ("Cin", c_int32), ("Cout", c_int32),
+        ("kh", c_int32), ("kw", c_int32), ("dil_h", c_int32),
+        ("pad_top", c_int32), ("pad_bottom", c_int32), ("pad_left", c_int32), ("pad_right", c_int32),
+        ("n_mean", c_int32), ("slope", c_float),
+        ("x", c_void_p), ("w", c_void_p), ("bias", c_void_p), ("zero_page", c_void_p),
+        ("resid", c_void_p), ("mean_a1", c_void_p), ("mean_a2", c_void_p),
+        ("out", c_void_p), ("act_out", c_void_p), ("out_f32", c_void_p),
+        ("workspace", c_void_p), ("workspace_bytes", c_int64),
+    ]
+
+
 class Conv3dPlan(Structure):
     _fields_ = [
         ("kernel", c_int32), ("tile_rows", c_int32), ("tile_cols", c_int32), ("row_tiles", c_int32), ("col_tiles", c_int32),
@@ -155,6 +169,9 @@ SIGNATURES = {
     "ltxk_conv3d_k3_bf16": (c_int32, [POINTER(Conv3dArgs), c_void_p]),
     "ltxk_conv3d_plan": (c_int32, [POINTER(Conv3dArgs), POINTER(Conv3dPlan)]),
     "ltxk_conv3d_plan_sizeof": (c_int32, []),
+    # audio VAE decoder / vocoder (csrc/conv_taps.hip); the struct carries its own size (struct_bytes), checked by the library
+    "ltxk_conv_taps_bf16": (c_int32, [POINTER(ConvTapsArgs), c_void_p]),
+    "ltxk_conv_taps_plan": (c_int32, [POINTER(ConvTapsArgs), POINTER(Conv3dPlan)]),
     "ltxk_pixelnorm_act": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_float, c_void_p, c_void_p, c_int64,
                                      c_int32, c_void_p]),
     "ltxk_d2s_add": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
@@ -219,7 +236,7 @@ _lib = None
 AB_LIB_PATH = os.path.join(_HERE, "libltxk_ab.so")
 ATTN_NO_TAIL_SPLIT = 1        # ltxk.h: LTXK_ATTN_NO_TAIL_SPLIT
 GEMM_FORM_SINGLE, GEMM_FORM_BIG, GEMM_FORM_SPLITK = 0, 1, 2     # ltxk.h: LTXK_GEMM_FORM_*
-CONV_KERNEL_PER_TAP, CONV_KERNEL_KW = 0, 1                      # ltxk.h: LTXK_CONV_KERNEL_*
+CONV_KERNEL_PER_TAP, CONV_KERNEL_KW, CONV_KERNEL_TAPS = 0, 1, 2  # ltxk.h: LTXK_CONV_KERNEL_*
 ATTN_KERNEL_128, ATTN_KERNEL_MIX = 0, 1                         # ltxk.h: LTXK_ATTN_KERNEL_*
 GUIDER_CFG_STAR, GUIDER_APG = 1, 2                              # ltxk.h: LTXK_GUIDER_*
 GUIDER_RECORD_FLOATS = 8                                        # ltxk.h: LTXK_GUIDER_RECORD_FLOATS

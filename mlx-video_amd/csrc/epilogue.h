@@ -81,6 +81,36 @@ __device__ __forceinline__ void conv_value(const f32x4& acc, bf16x4 bias, bf16x4
   }
 }
 
+// ---- the tap convolution's value (conv_taps.hip): conv_value, then the mean with one or two more tensors (summed in fp32 in
+// the order y, a1, a2, divided, rounded once), as floats; its two outputs follow from y ----
+// (NMEAN = 0: no mean.  Operands a form does not name are ignored.)
+__device__ __forceinline__ void taps_value(const f32x4& acc, bf16x4 bias, bool has_res, bf16x4 resid, int n_mean, bf16x4 a1, bf16x4 a2,
+                                           float (&y)[4]) {
+  if (has_res) conv_value<true>(acc, bias, resid, y);
+  else conv_value<false>(acc, bias, resid, y);
+  if (n_mean == 2) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) y[j] = rbf((y[j] + (float)a1[j]) / 2.0f);
+  } else if (n_mean == 3) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) y[j] = rbf(((y[j] + (float)a1[j]) + (float)a2[j]) / 3.0f);
+  }
+}
+// leaky ReLU as the reference writes it: max(y, bf16(y * slope))
+__device__ __forceinline__ bf16x4 taps_leaky(const float (&y)[4], float slope) {
+  float t[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) t[j] = fmaxf(y[j], rbf(y[j] * slope));
+  return to_bf16x4(t);
+}
+// conv_post + tanh: fp32, never rounded to bf16
+__device__ __forceinline__ f32x4 taps_tanh(const f32x4& acc, bf16x4 bias) {
+  f32x4 o;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) o[j] = tanhf(acc[j] + (float)bias[j]);
+  return o;
+}
+
 // ---- the transposed (V^T / split-output) store: token m, column nrel of its block -> out[(m / T) * rows + nrel][m % T] ----
 struct TransOut {
   bf16* out;

@@ -12,9 +12,10 @@ What is injected instead of loaded (nothing exists offline and they are out of s
 #17/#21): text embeddings (the Gemma-3 text encoder's output tensor is an INPUT of this path), model
 weights (`weights=` dicts or ready modules; `model_repo` may point at a local directory of
 safetensors read by ``weights.py``), random draws (`noise_fn`: MLX's threefry stream is not
-reproducible, so seeds are not cross-compatible), audio (not supported).  Frames are returned as the reference returns them (uint8 (F,H,W,3));
+reproducible, so seeds are not cross-compatible), audio latents (`audio_latents=`: the audio DiT branch that would generate them is
+not here; they are decoded to a waveform by ``audio_vae``).  Frames are returned as the reference returns them (uint8 (F,H,W,3));
 `output_path` accepts `.npy`, or a video file written through an ffmpeg child process when an ffmpeg binary
-is installed (media.write_video_ffmpeg); audio muxing is out of scope.
+is installed (media.write_video_ffmpeg); a decoded waveform goes to a `.wav` sidecar and is muxed into that file the same way.
 """
 from __future__ import annotations
 
@@ -282,7 +283,8 @@ def generate_video(model_repo: Optional[str] = None, text_encoder_repo: Optional
                    apg_norm_threshold: float = 0.0, gemma=None, gemma_repo: Optional[str] = None,
                    tokenizer_path: Optional[str] = None, prompt_tokens=None, negative_prompt_tokens=None,
                    enhance_prompt: bool = False, max_tokens: int = 512, temperature: float = 0.7,
-                   enhance_system_prompt: Optional[str] = None) -> np.ndarray:
+                   enhance_system_prompt: Optional[str] = None, audio_latents: Optional[torch.Tensor] = None,
+                   audio_decoder=None, vocoder=None, output_audio: Optional[str] = None) -> np.ndarray:
     """See the module docstring.  Returns uint8 frames (F,H,W,3) (generate.py:4195-4197).
     ``hoist_context`` (not in the reference, off by default): the part of the forward that depends on the text context only -
     caption projection and the 48 cross-attention K / V^T projections, 3.37 TFLOP that the reference recomputes in every forward
@@ -317,7 +319,12 @@ def generate_video(model_repo: Optional[str] = None, text_encoder_repo: Optional
     sampled with ``seed``) and the rewritten string takes the text route above.  It needs ``gemma`` or ``gemma_repo``
     and a tokenizer.json (``tokenizer_path`` or ``gemma_repo``), a ValueError that names what is missing otherwise, and a prompt
     that the text route reads as a string (no ``prompt_tokens`` / ``prompt_embeds`` / ``gemma_hidden_states`` in its place).  Off, the
-    default, nothing of it runs."""
+    default, nothing of it runs.
+    ``audio_latents`` (--audio-latents FILE): finished audio latents (B, 8, T, 16) - the reference's own layout - decoded after the
+    VAE decode under an ``audio_decode`` phase by ``audio_decoder`` / ``vocoder`` (``audio_vae.AudioDecoder`` / ``Vocoder``; loaded
+    from ``model_repo`` when not given) into a stereo 24 kHz waveform.  It is written to ``output_audio`` (--output-audio PATH; by
+    default the ``.wav`` beside ``output_path``) and, where ``output_path`` is a video file and an ffmpeg binary exists, muxed into
+    it (generate.py:4049-4127).  ``audio=True`` - generating those latents, the audio DiT branch - keeps raising."""
     t_start = time.perf_counter()
     if isinstance(pipeline, str):
         pipeline = PipelineType(pipeline)
@@ -561,6 +568,16 @@ def generate_video(model_repo: Optional[str] = None, text_encoder_repo: Optional
         if crop is not None:
             top, left, oh, ow = crop
             video_np = video_np[:, top:top + oh, left:left + ow, :]
+    waveform = None
+    if audio_latents is not None:                                     # generate.py:4049-4127
+        from .audio_vae import decode_audio
+        if audio_decoder is None or vocoder is None:
+            from .weights import load_audio_decoder, load_vocoder
+            audio_decoder = audio_decoder or load_audio_decoder(model_repo, dev)
+            vocoder = vocoder or load_vocoder(model_repo, dev)
+        with timer.phase("audio_decode"):
+            waveform = decode_audio(audio_latents.to(dev), audio_decoder, vocoder)
+            waveform = (waveform[0] if waveform.dim() == 3 else waveform).cpu()
     elapsed = time.perf_counter() - t_start
     if output_path:
         p = Path(output_path)
@@ -570,6 +587,19 @@ def generate_video(model_repo: Optional[str] = None, text_encoder_repo: Optional
         else:                                                          # generate.py:3900-3913 (ffmpeg encoder)
             from .media import write_video_ffmpeg
             write_video_ffmpeg(video_np, p, fps)
+    if waveform is not None and (output_audio or output_path):
+        from .media import mux_video_audio, save_audio
+        wav_path = Path(output_audio) if output_audio else Path(output_path).with_suffix(".wav")
+        wav_path.parent.mkdir(parents=True, exist_ok=True)
+        save_audio(waveform, wav_path, vocoder.output_sample_rate)
+        if output_path and Path(output_path).suffix != ".npy":
+            vp = Path(output_path)
+            tmp = vp.with_name(vp.stem + ".video_only" + vp.suffix)
+            vp.replace(tmp)
+            if mux_video_audio(tmp, wav_path, vp, audio_sample_rate=vocoder.output_sample_rate):
+                tmp.unlink()
+            else:
+                tmp.replace(vp)                                        # no ffmpeg: the silent video and the sidecar stay
     if profile and verbose:
         print(timer.render(elapsed))
     if profile_json_path and timer.times_s:                          # generate.py:4158-4189 (same keys)
@@ -578,7 +608,7 @@ def generate_video(model_repo: Optional[str] = None, text_encoder_repo: Optional
                    "stage1_steps": int(stage1_steps) if is_distilled else None,
                    "stage2_steps": int(stage2_steps) if is_distilled else None, "eval_interval": int(eval_interval),
                    "compile_step": bool(compile_step), "compile_shapeless": bool(compile_shapeless),
-                   "fp32_euler": bool(fp32_euler), "audio": False, "phases_s": {k: float(v) for k, v in timer.times_s.items()},
+                   "fp32_euler": bool(fp32_euler), "audio": waveform is not None, "phases_s": {k: float(v) for k, v in timer.times_s.items()},
                    "peak_memory_gb": float(torch.cuda.max_memory_allocated() / (1024 ** 3))}
         outp.parent.mkdir(parents=True, exist_ok=True)
         outp.write_text(json.dumps(payload, indent=2, sort_keys=True), encoding="utf-8")
@@ -661,6 +691,10 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--seed", type=int, default=42)
     ap.add_argument("--fps", type=float, default=24.0)
     ap.add_argument("--output-path", type=str, default="output.npy")
+    ap.add_argument("--audio-latents", type=str, default=None, metavar="FILE",
+                    help="Finished audio latents (B,8,T,16) as .npy or a torch file: decoded to a 24 kHz stereo waveform after the VAE decode")
+    ap.add_argument("--output-audio", type=str, default=None, metavar="PATH",
+                    help="Where the decoded waveform goes (.wav); default: beside --output-path")
     ap.add_argument("--tiling", type=str, default="auto")
     ap.add_argument("--stage1-steps", type=int, default=None)
     ap.add_argument("--stage2-steps", type=int, default=None)
@@ -833,6 +867,12 @@ def main(argv: Optional[Sequence[str]] = None) -> None:
             kw["gemma_hidden_states"], kw["gemma_attention_mask"] = load_gemma_hidden_states(args.gemma_hidden_states)
         if args.negative_gemma_hidden_states:
             kw["negative_gemma_hidden_states"], kw["negative_gemma_attention_mask"] = load_gemma_hidden_states(args.negative_gemma_hidden_states)
+    if args.audio_latents:
+        kw["audio_latents"] = torch.from_numpy(np.load(args.audio_latents)) if args.audio_latents.endswith(".npy") else \
+            torch.load(args.audio_latents, weights_only=True)
+        kw["output_audio"] = args.output_audio
+    elif args.output_audio:
+        raise ValueError("--output-audio needs --audio-latents: the audio DiT branch that would generate them is not here")
     if args.gemma_repo:
         kw["gemma_repo"], kw["tokenizer_path"] = args.gemma_repo, args.tokenizer
     if args.prompt_tokens:

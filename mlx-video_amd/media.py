@@ -215,3 +215,47 @@ def write_video_ffmpeg(video_np: np.ndarray, path: Union[str, Path], fps: float,
     err = proc.stderr.read() if proc.stderr is not None else b""
     if proc.wait() != 0:
         raise RuntimeError(err.decode(errors="ignore"))
+
+
+AUDIO_SAMPLE_RATE = 24000
+
+
+def save_audio(audio, path: Union[str, Path], sample_rate: int = AUDIO_SAMPLE_RATE) -> None:
+    """(channels, samples) or (samples,) float waveform -> 16-bit PCM WAV, the reference's rule (generate.py:1920-1937):
+    NaN -> 0, +-inf -> +-1, clip to [-1, 1], * 32767 truncated to int16, interleaved, through ``wave``."""
+    import wave
+    a = audio.detach().float().cpu().numpy() if isinstance(audio, torch.Tensor) else np.asarray(audio)
+    if a.ndim == 2:
+        a = a.T
+    a = np.clip(np.nan_to_num(a, nan=0.0, posinf=1.0, neginf=-1.0), -1.0, 1.0)
+    pcm = (a * 32767).astype(np.int16)
+    with wave.open(str(path), "wb") as wf:
+        wf.setnchannels(2 if pcm.ndim == 2 else 1)
+        wf.setsampwidth(2)
+        wf.setframerate(int(sample_rate))
+        wf.writeframes(np.ascontiguousarray(pcm).tobytes())
+
+
+def mux_command(ffmpeg: str, video_path: Union[str, Path], audio_path: Union[str, Path], output_path: Union[str, Path],
+                audio_bitrate: str = "256k", audio_sample_rate: int = AUDIO_SAMPLE_RATE) -> list:
+    """generate.py:1980-2016: the video stream copied, the audio encoded to AAC; no -shortest (the audio may end a hop
+    short of the video, and -shortest would drop the last frames)."""
+    return [ffmpeg, "-y", "-i", str(video_path), "-i", str(audio_path), "-map", "0:v:0", "-map", "1:a:0", "-c:v", "copy",
+            "-c:a", "aac", "-b:a", str(audio_bitrate), "-ar", str(audio_sample_rate), "-ac", "2", "-movflags", "+faststart",
+            str(output_path)]
+
+
+def mux_video_audio(video_path: Union[str, Path], audio_path: Union[str, Path], output_path: Union[str, Path],
+                    audio_bitrate: str = "256k", audio_sample_rate: int = AUDIO_SAMPLE_RATE) -> bool:
+    """Video file + WAV -> one file through an ffmpeg child process.  False where no ffmpeg binary exists (the sidecar WAV
+    stays); RuntimeError with ffmpeg's stderr when it fails."""
+    import shutil
+    import subprocess
+    ffmpeg = shutil.which("ffmpeg")
+    if ffmpeg is None:
+        return False
+    proc = subprocess.run(mux_command(ffmpeg, video_path, audio_path, output_path, audio_bitrate, audio_sample_rate),
+                          stdout=subprocess.DEVNULL, stderr=subprocess.PIPE)
+    if proc.returncode != 0:
+        raise RuntimeError(f"ffmpeg mux failed ({proc.returncode}): {proc.stderr.decode(errors='replace')[-2000:]}")
+    return True

@@ -17,7 +17,7 @@ from typing import Optional, Tuple
 import torch
 
 from . import _lib
-from ._lib import AttnArgs, CausalAttnArgs, Conv3dArgs, GemmArgs, GemmGroupedArgs, GuiderArgs, StepArgs, check
+from ._lib import AttnArgs, CausalAttnArgs, Conv3dArgs, ConvTapsArgs, GemmArgs, GemmGroupedArgs, GuiderArgs, StepArgs, check
 
 EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_SILU, EPI_BIAS_GATE_RES, EPI_BIAS_RES, EPI_SCALE_RES = 0, 1, 2, 3, 4, 5
 BF16 = torch.bfloat16
@@ -979,12 +979,91 @@ def causal_attn(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, out: torch.T
 PAD_ZEROS, PAD_REFLECT = 0, 1
 
 
+def _taps_geometry(who: str, kernel, dilation: int, pad) -> tuple:
+    """(kh, kw, dil, (top, bottom, left, right)) of a ``kernel=`` call, refused where ltxk_conv_taps_bf16 would refuse it."""
+    kh, kw = (int(k) for k in kernel)
+    dil = int(dilation)
+    if not (1 <= kh <= 16 and kw in (1, 3) and 1 <= dil <= 8):
+        raise ValueError(f"{who}: kernel=({kh},{kw}) dilation={dil}: needs kh in [1,16], kw 1 or 3, dilation in [1,8]")
+    if pad is None or len(pad) != 4:
+        raise ValueError(f"{who}: kernel= needs pad=(top, bottom, left, right)")
+    pt, pb, pl_, pr = (int(v) for v in pad)
+    if min(pt, pb, pl_, pr) < 0 or pt + pb != (kh - 1) * dil or pl_ + pr != kw - 1:
+        raise ValueError(f"{who}: pad={tuple(pad)} must sum to ((kh-1)*dilation, kw-1) = ({(kh - 1) * dil}, {kw - 1}): the output extent is the input's")
+    return kh, kw, dil, (pt, pb, pl_, pr)
+
+
+def _conv_taps(x, w, b, resid, keep_out, kernel, dilation, pad, mean_with, leaky, tanh_out):
+    """The ``kernel=`` form of ``conv3d``: ltxk_conv_taps_bf16 (include/ltxk.h has the sum and the epilogue's rounding order)."""
+    who = "conv3d"
+    B, D, H, W, Cin = _dims(who, "x", x, BF16, 5)
+    kh, kw, dil, (pt, pb, pl_, pr) = _taps_geometry(who, kernel, dilation, pad)
+    Cout = w.shape[0]
+    if tuple(w.shape[1:]) != (kh, kw, Cin):
+        raise ValueError(f"{who}: weight {tuple(w.shape)} does not match kernel=({kh},{kw}) and Cin={Cin}")
+    if Cin != 32 and Cin % 64:
+        raise ValueError(f"{who}: Cin={Cin} must be 32 or a multiple of 64 (pad channels with zeros)")
+    mean_with = tuple(mean_with) if mean_with is not None else ()
+    if len(mean_with) > 2:
+        raise ValueError(f"{who}: mean_with takes one or two tensors, got {len(mean_with)}")
+    if tanh_out and (resid is not None or mean_with or leaky is not None):
+        raise ValueError(f"{who}: tanh_out is the final form: no resid, mean_with or leaky")
+    if not tanh_out and leaky is None and not keep_out:
+        raise ValueError(f"{who}: keep_out=False leaves no output without leaky=")
+    oshape = (B, D, H, W, Cout)
+    ra = 16 if Cout % 8 == 0 else 8 if Cout % 4 == 0 else 2
+    a1, a2 = (mean_with + (None, None))[:2]
+    _operands(who, ("x", x, BF16, 5, 16), ("w", w, BF16, (Cout, kh, kw, Cin), 16), ("bias", b, BF16, (Cout,), 2),
+              ("resid", resid, BF16, oshape, ra), ("mean_with[0]", a1, BF16, oshape, ra), ("mean_with[1]", a2, BF16, oshape, ra))
+    dev = x.device
+    a = ConvTapsArgs()
+    a.struct_bytes = ctypes.sizeof(ConvTapsArgs)
+    a.B, a.D, a.H, a.W, a.Cin, a.Cout = B, D, H, W, Cin, Cout
+    a.kh, a.kw, a.dil_h = kh, kw, dil
+    a.pad_top, a.pad_bottom, a.pad_left, a.pad_right = pt, pb, pl_, pr
+    a.x, a.w, a.bias, a.resid, a.mean_a1, a.mean_a2 = _p(x), _p(w), _p(b), _p(resid), _p(a1), _p(a2)
+    a.n_mean = len(mean_with) + 1 if mean_with else 0
+    a.zero_page = _p(_scratch("zero_page", dev))
+    ws = _scratch("conv_splitk", dev)
+    a.workspace, a.workspace_bytes = _p(ws), ws.numel() * 4
+    out = act_out = None
+    if tanh_out:
+        out = torch.empty(oshape, dtype=F32, device=dev)
+        a.out_f32 = _p(out)
+    else:
+        if keep_out:
+            out = torch.empty(oshape, dtype=BF16, device=dev)
+            a.out = _p(out)
+        if leaky is not None:
+            act_out = torch.empty(oshape, dtype=BF16, device=dev)
+            a.act_out, a.slope = _p(act_out), float(leaky)
+    V = B * D * H * W
+    with _timed("conv_taps", 2.0 * kh * kw * Cin * Cout * V, 2.0 * V * (Cin + Cout) + 2.0 * kh * kw * Cin * Cout):
+        check(_lib.load().ltxk_conv_taps_bf16(ctypes.byref(a), _stream()), "ltxk_conv_taps_bf16")
+    return out if leaky is None else (out, act_out)
+
+
 def conv3d(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, causal: bool, pad_mode: int,
-           resid: Optional[torch.Tensor] = None, act: Optional[dict] = None, keep_out: bool = True):
+           resid: Optional[torch.Tensor] = None, act: Optional[dict] = None, keep_out: bool = True, *,
+           kernel: Optional[Tuple[int, int]] = None, dilation: int = 1, pad: Optional[Tuple[int, int, int, int]] = None,
+           mean_with=None, leaky: Optional[float] = None, tanh_out: bool = False):
     """x (B,D,H,W,Cin) bf16 channels-last; w (Cout,3,3,3,Cin), or (Cout,3,3,Cin) for a per-frame 3x3 kernel;
     returns (B,D,H,W,Cout).  ``act`` = dict(eps, silu, scale, shift): the PixelNorm (+ modulation) + SiLU that follows
     this conv is applied to its output rows in the epilogue (Cout 128 / 256) and returned as a second tensor:
-    ``(out, act_out)``; ``keep_out=False`` skips the raw output (``out`` is None) when nothing else reads it."""
+    ``(out, act_out)``; ``keep_out=False`` skips the raw output (``out`` is None) when nothing else reads it.
+
+    With ``kernel=(kh, kw)`` (ltxk_conv_taps_bf16: the audio decoder's causal 3x3 and the vocoder's dilated convolutions):
+    w (Cout,kh,kw,Cin), each (H,W) frame convolved on its own with ``dilation`` along H and explicit zero halos
+    ``pad=(top, bottom, left, right)`` that keep the extent; ``causal`` / ``pad_mode`` / ``act`` do not apply (pad_mode must
+    be PAD_ZEROS).  y = bf16(conv + bias), then bf16(y + resid), then with ``mean_with=(a1[, a2])`` bf16((y + a1 [+ a2]) / n);
+    ``leaky=slope`` returns ``(out, max(y, bf16(y * slope)))`` (``keep_out=False``: out None); ``tanh_out=True`` returns
+    tanh(conv + bias) in float32, never rounded to bf16.  Cin 32 or a multiple of 64, any Cout."""
+    if kernel is not None:
+        if act is not None or pad_mode != PAD_ZEROS:
+            raise ValueError("conv3d: kernel= takes explicit zero halos (pad=): no act, pad_mode must be PAD_ZEROS")
+        return _conv_taps(x, w, b, resid, keep_out, kernel, dilation, pad, mean_with, leaky, tanh_out)
+    if dilation != 1 or pad is not None or mean_with is not None or leaky is not None or tanh_out:
+        raise ValueError("conv3d: dilation, pad, mean_with, leaky and tanh_out belong to the kernel= form")
     B, D, H, W, Cin = _dims("conv3d", "x", x, BF16, 5)
     Cout = w.shape[0]
     taps_d = 3 if w.dim() == 5 else 1
@@ -1046,11 +1125,29 @@ class Conv3dPlan:
 
 def conv3d_plan(B: int, D: int, H: int, W: int, Cin: int, Cout: int, *, causal: int = 1, pad_mode: int = PAD_REFLECT,
                 taps_d: int = 3, resid: bool = False, act: bool = False, keep_out: bool = True,
-                workspace: Optional[Tuple[int, int]] = None) -> Conv3dPlan:
+                workspace: Optional[Tuple[int, int]] = None, kernel: Optional[Tuple[int, int]] = None, dilation: int = 1,
+                pad: Optional[Tuple[int, int, int, int]] = None) -> Conv3dPlan:
     """The form ``conv3d`` takes for this volume, decided on the host by the function the launch itself uses (no device
     needed).  The split-K scratch is offered as ``conv3d`` offers it (SPLITK_WORKSPACE_BYTES); ``workspace=(address,
-    bytes)`` offers that one instead (address 0: none).  Raises LtxkError where the launch would refuse the arguments."""
+    bytes)`` offers that one instead (address 0: none).  Raises LtxkError where the launch would refuse the arguments.
+    ``kernel=(kh, kw)``, ``dilation=``, ``pad=``: the form of the ``kernel=`` call (ltxk_conv_taps_plan)."""
     addr = _PLAN_ADDR
+    if kernel is not None:
+        kh, kw, dil, (pt, pb, pl_, pr) = _taps_geometry("conv3d_plan", kernel, dilation, pad)
+        t = ConvTapsArgs()
+        t.struct_bytes = ctypes.sizeof(ConvTapsArgs)
+        t.x = t.w = t.bias = t.zero_page = t.out = addr
+        t.resid = addr if resid else None
+        t.B, t.D, t.H, t.W, t.Cin, t.Cout = B, D, H, W, Cin, Cout
+        t.kh, t.kw, t.dil_h = kh, kw, dil
+        t.pad_top, t.pad_bottom, t.pad_left, t.pad_right = pt, pb, pl_, pr
+        t.workspace, t.workspace_bytes = (addr, SPLITK_WORKSPACE_BYTES) if workspace is None else workspace
+        pl = _lib.Conv3dPlan()
+        check(_lib.load().ltxk_conv_taps_plan(ctypes.byref(t), ctypes.byref(pl)), "ltxk_conv_taps_plan")
+        return Conv3dPlan(pl.kernel, pl.tile_rows, pl.tile_cols, pl.row_tiles, pl.col_tiles, pl.slices, pl.ksteps,
+                          pl.tail_tile_rows, pl.tail_m_base, pl.tail_row_tiles, bool(pl.fused_act))
+    if dilation != 1 or pad is not None:
+        raise ValueError("conv3d_plan: dilation and pad belong to the kernel= form")
     a = Conv3dArgs()
     a.x = a.w = a.bias = a.zero_page = addr
     a.out = addr if (keep_out or not act) else None

@@ -521,6 +521,116 @@ def load_pipeline_modules(model_repo: str, device, need_encoder: bool = False, n
     return mods
 
 
+# ---- audio VAE decoder and vocoder (convert.py:376-471 as key maps) --------------------------------------------------------
+# Three sources: the tensors of a unified (already converted) checkpoint under `audio_vae.` / `vocoder.` - MLX layouts, the
+# reference loads them as they are -; `audio_vae/` and `vocoder/` `diffusion_pytorch_model.safetensors`; and the full PyTorch
+# checkpoint.  The latter two carry PyTorch layouts: Conv2d (O,I,H,W) -> (O,H,W,I), Conv1d (O,I,k) -> (O,k,I), ConvTranspose1d
+# (I,O,k) -> (O,k,I).  Everything is cast to bf16 like every other module.
+_AUDIO_STATS = {"mean-of-means": "_mean_of_means", "std-of-means": "_std_of_means", "_mean_of_means": "_mean_of_means",
+                "_std_of_means": "_std_of_means"}
+
+
+def _audio_decoder_key(k: str) -> Optional[str]:
+    """The decoder's own name of a checkpoint key, `per_channel_statistics._mean_of_means` / `._std_of_means` for either
+    spelling of the statistics, None for every other tensor (the encoder's included)."""
+    if k in ("latents_mean", "latents_std"):                    # audio_vae/diffusion_pytorch_model.safetensors
+        return "per_channel_statistics." + ("_mean_of_means" if k.endswith("mean") else "_std_of_means")
+    if k.startswith("audio_vae."):
+        k = k[len("audio_vae."):]
+    if k.startswith("decoder."):
+        return k[len("decoder."):]
+    if k.startswith("per_channel_statistics."):
+        name = _AUDIO_STATS.get(k[len("per_channel_statistics."):])
+        return None if name is None else "per_channel_statistics." + name
+    return None
+
+
+def audio_decoder_weights(raw: Dict[str, torch.Tensor], device, layout: str = "pytorch") -> Dict[str, torch.Tensor]:
+    """sanitize_audio_vae_weights (convert.py:376-419) for the decoder: keys by ``_audio_decoder_key``; ``layout`` "pytorch"
+    transposes 4-D conv weights to (O,H,W,I), "mlx" (a unified checkpoint) takes them as they are."""
+    if layout not in ("pytorch", "mlx"):
+        raise ValueError(f"audio_decoder_weights: layout must be 'pytorch' or 'mlx', got {layout!r}")
+    out: Dict[str, torch.Tensor] = {}
+    for k, v in raw.items():
+        kk = _audio_decoder_key(k)
+        if kk is None:
+            continue
+        if layout == "pytorch" and v.ndim == 4 and "conv" in kk.lower() and "weight" in kk:
+            v = v.permute(0, 2, 3, 1)
+        out[kk] = _to_dev(v, device)
+    return out
+
+
+_VOCODER_RENAMES = (("upsamplers.", "ups."), ("resnets.", "resblocks."), ("conv_in.", "conv_pre."), ("conv_out.", "conv_post."))
+
+
+def _vocoder_key(k: str, has_prefix: bool) -> Optional[str]:
+    if has_prefix:
+        if not k.startswith("vocoder."):
+            return None
+        k = k[len("vocoder."):]
+    for old, new in _VOCODER_RENAMES:
+        if k.startswith(old):
+            return new + k[len(old):]
+    return k if k.startswith(("ups.", "resblocks.", "conv_pre.", "conv_post.")) else None
+
+
+def vocoder_weights(raw: Dict[str, torch.Tensor], device, layout: str = "pytorch") -> Dict[str, torch.Tensor]:
+    """sanitize_vocoder_weights (convert.py:422-471): only `vocoder.` keys where any key has that prefix, the upstream
+    names (upsamplers / resnets / conv_in / conv_out) mapped to ups / resblocks / conv_pre / conv_post; ``layout`` "pytorch"
+    transposes Conv1d (O,I,k) and ConvTranspose1d (I,O,k) weights to (O,k,I)."""
+    if layout not in ("pytorch", "mlx"):
+        raise ValueError(f"vocoder_weights: layout must be 'pytorch' or 'mlx', got {layout!r}")
+    has_prefix = any(k.startswith("vocoder.") for k in raw)
+    out: Dict[str, torch.Tensor] = {}
+    for k, v in raw.items():
+        kk = _vocoder_key(k, has_prefix)
+        if kk is None:
+            continue
+        if layout == "pytorch" and v.ndim == 3 and "weight" in kk:
+            v = v.permute(1, 2, 0) if kk.startswith("ups.") else v.permute(0, 2, 1)
+        out[kk] = _to_dev(v, device)
+    return out
+
+
+def _audio_source(model_repo, sub: str, prefix: str, unified: Optional[Dict[str, torch.Tensor]]):
+    """(raw tensors, layout) from the first source that has them (generate.py:1725-1760): the unified dict's `prefix` keys,
+    `<repo>/<sub>/diffusion_pytorch_model.safetensors`, the repo's full checkpoint."""
+    if unified is not None:
+        picked = {k: v for k, v in unified.items() if k.startswith(prefix)}
+        if picked:
+            return picked, "mlx"
+    root = Path(model_repo) if model_repo is not None else None
+    if root is not None:
+        f = root / sub / "diffusion_pytorch_model.safetensors"
+        if f.exists():
+            return read_safetensors([f]), "pytorch"
+        main = [p for p in sorted(root.glob("*.safetensors")) if "upscaler" not in p.name and "upsampler" not in p.name]
+        raw = dict(iter_safetensors(main, want=lambda k: k.startswith(prefix)))
+        if raw:
+            return raw, "pytorch"
+    raise FileNotFoundError(f"{prefix}* weights not found: no unified tensors, no {sub}/diffusion_pytorch_model.safetensors and no "
+                            f"checkpoint with them under {model_repo!r}")
+
+
+def load_audio_decoder(model_repo, device, unified_weights: Optional[Dict[str, torch.Tensor]] = None):
+    """The ``AudioDecoder`` of ``model_repo`` (a local directory) or of ``unified_weights`` (generate.py:1706-1763)."""
+    from .audio_vae import AudioDecoder
+    raw, layout = _audio_source(model_repo, "audio_vae", "audio_vae.", unified_weights)
+    W = audio_decoder_weights(raw, device, layout)
+    # width and depth from the shapes, as the other loaders infer theirs: conv_out reads ch channels, level 0 has num_res_blocks + 1 blocks
+    nres = max((int(k.split(".")[3]) for k in W if k.startswith("up.0.block.")), default=2)
+    return AudioDecoder(W, ch=W["conv_out.conv.weight"].shape[-1], num_res_blocks=nres)
+
+
+def load_vocoder(model_repo, device, unified_weights: Optional[Dict[str, torch.Tensor]] = None):
+    """The ``Vocoder`` of ``model_repo`` or of ``unified_weights`` (generate.py:1766-1812)."""
+    from .audio_vae import Vocoder
+    raw, layout = _audio_source(model_repo, "vocoder", "vocoder.", unified_weights)
+    W = vocoder_weights(raw, device, layout)
+    return Vocoder(W, upsample_initial_channel=W["conv_pre.weight"].shape[0])
+
+
 def random_upsampler_weights(device, mid: int = 1024, seed: int = 99, nb: int = 4) -> Dict[str, torch.Tensor]:
     g = torch.Generator(device=device).manual_seed(seed)
     W: Dict[str, torch.Tensor] = {}
