@@ -4,12 +4,15 @@ plan is split-K (ops.gemm_plan), with an uneven last slice where K allows; M = 6
 
 Bias, +res and scale*res outputs are held to a rigorous element-wise bound: one bf16 rounding of the output (1/2 ulp), the
 fp32 accumulation error K * 2^-24 * sum|a_k w_k| (any summation order, slices included), and the fp32 / bf16 roundings of the
-epilogue's own steps.  A dropped, doubled or mis-bounded slice, or a wrong row of the last partial tile, moves an output by a
-whole partial sum - orders of magnitude beyond it.  GELU, SiLU and gate outputs keep the ulp rules of
-test_gemm_split_k_form, against the float64 reference.  Also: two runs give the same bits, nothing outside the output views
+epilogue's own steps (tests/ref_gemm.py: the bound and its helpers).  A dropped, doubled or mis-bounded slice, or a wrong row
+of the last partial tile, moves an output by a whole partial sum - orders of magnitude beyond it.  GELU, SiLU and gate outputs
+keep the ulp rules of test_gemm_split_k_form, against the float64 reference, and are held to ref_gemm.bound as well (no element
+beyond it).  Also: two runs give the same bits, nothing outside the output views
 is written (sentinels), and sumsq is the sum of squares of what was stored."""
 import pytest
 import torch
+
+import ref_gemm
 
 pytestmark = pytest.mark.gpu
 BF = torch.bfloat16
@@ -22,9 +25,7 @@ CASES = [(1, 4096, 4096), (2, 1000, 64 * 67), (2, 16384, 4096), (31, 4104, 64 * 
          (161, 1000, 64 * 67), (320, 4096, 4096), (639, 4096, 16384), (640, 4096, 16384), (641, 4096, 16384)]
 
 
-def _ulp(x):
-    """bf16 ulp of |x| (float64), floored at the smallest normal."""
-    return torch.exp2(torch.floor(torch.log2(x.abs().clamp_min(2.0 ** -126))) - 7)
+_ulp = ref_gemm.ulp
 
 
 def _ulp_rule(name, got, ref, gate_max):
@@ -40,7 +41,7 @@ def _ulp_rule(name, got, ref, gate_max):
 
 def _bound_check(name, got, ref, bound):
     d = (got.to(F64) - ref).abs()
-    bad = d > bound
+    bad = ref_gemm.beyond(d, bound)
     assert not bool(bad.any()), (f"{name}: {int(bad.sum())} outputs beyond the rounding bound, worst excess "
                                  f"{float((d - bound).max()):.3e} at {tuple(int(i) for i in bad.nonzero()[0])}")
 
@@ -147,6 +148,9 @@ def test_gemm_split_k_against_float64(dev, M, N, K):
                 gv = gate.to(F64)[grow.long()] if row_on else gate.to(F64)[0].expand(M, N)
                 ref = r64 + (yb * gv).to(torch.float32).to(BF).to(F64)
             _ulp_rule(name, out, ref.to(torch.float32).to(BF).to(F64), gmax)
+            gv = (gate[grow.long()] if row_on else gate[0].expand(M, N)) if epi == 3 else None
+            w = ref_gemm.check(name, *ref_gemm.bound(epi, out, s, mag, K, b if bias_on else None, res if epi == 3 else None, gv))
+            print(f"{name}: worst d / bound = {w:.3f}")
         if ss is not None:
             assert bool((ss[:, -1] == -1.0).all()), f"{name}: sumsq written past sumsq_ld's columns"
             sq64 = out.to(F64).pow(2).reshape(M, -1, 64).sum(-1)

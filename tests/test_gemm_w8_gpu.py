@@ -12,6 +12,8 @@ fp32 bias add.  Nothing is added to that bound."""
 import pytest
 import torch
 
+import ref_gemm
+
 pytestmark = pytest.mark.gpu
 BF = torch.bfloat16
 F8 = torch.float8_e4m3fn
@@ -182,14 +184,12 @@ def test_w8_split_k_equals_bf16(dev, M, N, K, slices, ksteps):
              _split_output(ops, a, w8.to(BF), b, T, 256, sumsq=True, split_k=True))
 
 
-def _ulp(x):
-    """bf16 ulp of |x| (float64), floored at the smallest normal."""
-    return torch.exp2(torch.floor(torch.log2(x.abs().clamp_min(2.0 ** -126))) - 7)
+_ulp = ref_gemm.ulp          # (the bound's helpers: tests/ref_gemm.py)
 
 
 def _bound_check(name, got, ref, bound):
     d = (got.to(F64) - ref).abs()
-    bad = d > bound
+    bad = ref_gemm.beyond(d, bound)
     assert not bool(bad.any()), (f"{name}: {int(bad.sum())} outputs beyond the rounding bound, worst excess "
                                  f"{float((d - bound).max()):.3e} at {tuple(int(i) for i in bad.nonzero()[0])}")
 

@@ -5,7 +5,7 @@
    all scales 1.  Every partial sum is an integer below 2^24, so the accumulator is exact in any order: the plain output is the
    float64 product rounded once to bf16, and every epilogue / output form must give the BITS ltxk_gemm_bf16 gives on the same
    integers as bf16 (its sums are exact too, and the epilogue code is shared).  This pins the lane maps and the A/W k assignment.
-2. Random data against float64 under the element-wise bound of tests/test_gemm_w8_gpu.py (helpers restated here): half a bf16
+2. Random data against float64 under the element-wise bound of tests/test_gemm_w8_gpu.py (its helpers are tests/ref_gemm.py's): half a bf16
    ulp of the output + K * 2^-24 * sum|a_k w_k| * a_scale * w_scale for the fp32 accumulation in any order + two more fp32
    roundings for the two scale multiplies + the fp32 bias add.  Nothing is added to that bound; the worst ratio is printed.
 3. Argument errors.   4. quant_rows_fp8 -> gemm composition against the float64 product of the restated quantised operands."""
@@ -13,6 +13,8 @@ import ctypes
 
 import pytest
 import torch
+
+import ref_gemm
 
 pytestmark = pytest.mark.gpu
 BF = torch.bfloat16
@@ -154,9 +156,7 @@ def test_w8a8_exact_integers_split_output(dev, M, T, sumsq):
              _split_output(ops, ab, w8.to(BF), b, T, ns, sumsq=sumsq, extra={}))
 
 
-def _ulp(x):
-    """bf16 ulp of |x| (float64), floored at the smallest normal."""
-    return torch.exp2(torch.floor(torch.log2(x.abs().clamp_min(2.0 ** -126))) - 7)
+_ulp = ref_gemm.ulp          # (the bound's helpers: tests/ref_gemm.py)
 
 
 WORST = {}
@@ -164,10 +164,10 @@ WORST = {}
 
 def _bound_check(name, got, ref, bound):
     d = (got.to(F64) - ref).abs()
-    ratio = float((d / bound).max())
+    ratio = ref_gemm.worst(d, bound)
     WORST[name] = max(WORST.get(name, 0.0), ratio)
     print(f"{name}: worst |error| / bound = {ratio:.3f}")
-    bad = d > bound
+    bad = ref_gemm.beyond(d, bound)
     assert not bool(bad.any()), (f"{name}: {int(bad.sum())} outputs beyond the rounding bound (worst ratio {ratio:.3f}), worst excess "
                                  f"{float((d - bound).max()):.3e} at {tuple(int(i) for i in bad.nonzero()[0])}")
 
