@@ -253,6 +253,15 @@ int ltxk_flash_attn_bf16(const void* q, int32_t ldq, const void* k, int32_t ldk,
                          int32_t B, int32_t H, int32_t Tq, int32_t Tk, float scale,
                          void* stream);
 
+/* ltxk_flash_attn at head dim 64 (the audio transformer, 32 heads x 64: ltx.py AudioOnly; also the head dim of the
+ * cross-modal attentions).  The same struct read at dh = 64: q, k, out (B,T,H*64); vt (B,H*64,ldvt), ldvt >= Tk rounded up
+ * to 64; the alignment and stride rules and the "flash" rounding points above, word for word.  No fused query preparation:
+ * q_sumsq != NULL is LTXK_EINVAL (q_norm_weight, cos, sin, eps and flags are not read).  One launch form: 64-row query
+ * tiles x whole key range per workgroup, keys never split, so a (batch, head)'s bits do not depend on B, H or the grid.
+ * Keys >= Tk get P = 0 and take no part in the row maximum (V^T pad columns may hold any finite value); rows >= Tq are
+ * not stored; no load leaves q, k or vt as sized above.                                                                  */
+int ltxk_flash_attn_dh64(const ltxk_attn_args* args, void* stream);
+
 /* ---------------------------------------------------------------------------------------
  * rms_norm (weight 1) + AdaLN modulation: utils.py:398-400 + transformer.py:253,258,346.
  *   y = bf16(bf16(bf16(rms(x)) * bf16(1+scale)) + shift); scale/shift NULL => plain rms_norm.
@@ -292,6 +301,13 @@ int ltxk_qknorm_rope(void* buf, int32_t ld, int32_t M, int32_t nseg, int32_t D,
 int ltxk_qknorm_rope_ss(void* buf, int32_t ld, int32_t M, int32_t nseg, int32_t D,
                         const void* weight, const float* cos, const float* sin,
                         int32_t T, int32_t H, float eps, const float* sumsq, int32_t sumsq_ld, void* stream);
+
+/* The same chain at head dim 64: D == H*64, 1 <= H <= 32, cos/sin (H,T,32) fp32 or NULL, the rotation partner of channel j
+ * of a head is j + 32.  sumsq as for ltxk_qknorm_rope_ss (D/64 = H partials per segment), or NULL: the kernel then reduces
+ * the row itself.  buf, weight, cos, sin 16-byte aligned.                                   */
+int ltxk_qknorm_rope_dh64(void* buf, int32_t ld, int32_t M, int32_t nseg, int32_t D,
+                          const void* weight, const float* cos, const float* sin,
+                          int32_t T, int32_t H, float eps, const float* sumsq, int32_t sumsq_ld, void* stream);
 
 /* The q/k RMSNorm above without rotation over G stacked buffers in one launch (the text-side k of every block): group g is
  * the (M,D) rows at buf + g*buf_gstride (row stride ld) with weight row g of the (G,D) table and the statistics at

@@ -146,6 +146,7 @@ SIGNATURES = {
     "ltxk_qknorm_grouped_ss": (c_int32, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_float,
                                          c_void_p, c_int64, c_int32, c_void_p]),
     "ltxk_flash_attn": (c_int32, [POINTER(AttnArgs), c_void_p]),
+    "ltxk_flash_attn_dh64": (c_int32, [POINTER(AttnArgs), c_void_p]),
     "ltxk_flash_attn_plan": (c_int32, [POINTER(AttnArgs), c_int32, POINTER(AttnPlan)]),
     "ltxk_flash_attn_plan_sizeof": (c_int32, []),
     "ltxk_flash_attn_bf16": (c_int32, [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32,
@@ -164,6 +165,8 @@ SIGNATURES = {
                                            c_void_p, c_int32, c_void_p, c_int32, c_void_p]),
     "ltxk_qknorm_rope_ss": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
                                       c_int32, c_int32, c_float, c_void_p, c_int32, c_void_p]),
+    "ltxk_qknorm_rope_dh64": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
+                                        c_int32, c_int32, c_float, c_void_p, c_int32, c_void_p]),
     "ltxk_silu": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p]),
     "ltxk_latent_to_tokens": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "ltxk_conv3d_k3_bf16": (c_int32, [POINTER(Conv3dArgs), c_void_p]),

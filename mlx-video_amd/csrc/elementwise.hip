@@ -243,6 +243,55 @@ __global__ __launch_bounds__(256) void qknorm_rope_ss_kernel(
   *(bf16x8*)(xr + base + 64) = ob;
 }
 
+// The same chain at head dim 64 (the audio transformer: 32 heads x 64): a head's halves are 32 wide, the rotation partner of
+// channel j is j + 32 and the tables are (H, T, 32).  One wave per (row, segment); 4 lanes per head, 16 heads per pass, two
+// passes: H <= 32.  The row statistic is the precomputed partials (`sumsq`, D/64 = H per segment) where given, else the
+// wave reduces the row it holds.
+template <bool ROPE>
+__global__ __launch_bounds__(256) void qknorm_rope_dh64_kernel(
+    bf16* __restrict__ buf, int ld, int M, int nseg, int D, const bf16* __restrict__ weight,
+    const float* __restrict__ cosb, const float* __restrict__ sinb, int T, int H, float eps,
+    const float* __restrict__ sumsq, int ss_ld) {
+  const int lane = threadIdx.x & 63;
+  const int item = blockIdx.x * ROWS_PER_BLOCK + (threadIdx.x >> 6);
+  if (item >= M * nseg) return;
+  const int row = item / nseg, sgi = item - row * nseg;
+  const int t = row % T;
+  const int hl = lane >> 2;          // head within pass
+  const int j0 = (lane & 3) * 8;     // offset within the 32-wide half
+  bf16* xr = buf + (size_t)row * ld + (size_t)sgi * D;
+  const bf16* wr = weight + (size_t)sgi * D;
+  bf16x8 a[2], b[2];
+  float sq = 0.f;
+#pragma unroll
+  for (int ps = 0; ps < 2; ++ps)
+    if (ps * 16 + hl < H) {
+      const int base = (ps * 16 + hl) * 64 + j0;
+      a[ps] = *(const bf16x8*)(xr + base);
+      b[ps] = *(const bf16x8*)(xr + base + 32);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const float fa = (float)a[ps][j], fb = (float)b[ps][j];
+        sq += fa * fa + fb * fb;
+      }
+    }
+  if (sumsq) sq = lane < H ? sumsq[(size_t)row * ss_ld + sgi * H + lane] : 0.f;
+  const float rstd = rsqrtf(wave_sum(sq) / (float)D + eps);
+#pragma unroll
+  for (int ps = 0; ps < 2; ++ps)
+    if (ps * 16 + hl < H) {
+      const int base = (ps * 16 + hl) * 64 + j0;
+      const bf16x8 wa = *(const bf16x8*)(wr + base);
+      const bf16x8 wb = *(const bf16x8*)(wr + base + 32);
+      RopeTab tab = {};
+      if constexpr (ROPE) tab = rope_load(cosb, sinb, ((size_t)(ps * 16 + hl) * T + t) * 32 + j0);
+      bf16x8 oa, ob;
+      norm_rope(a[ps], b[ps], rstd, wa, wb, ROPE, tab, oa, ob);
+      *(bf16x8*)(xr + base) = oa;
+      *(bf16x8*)(xr + base + 32) = ob;
+    }
+}
+
 // ---------------------------------------------------------------------------------------
 // small kernels
 // ---------------------------------------------------------------------------------------
@@ -604,6 +653,26 @@ extern "C" int ltxk_qknorm_rope(void* buf, int32_t ld, int32_t M, int32_t nseg, 
   else
     hipLaunchKernelGGL((qknorm_rope_kernel<4, false>), grid, dim3(256), 0, (hipStream_t)stream, (bf16*)buf, ld, M, nseg, D, (const bf16*)weight, cos, sin, T, H, eps);
   LTXK_CHECK_LAUNCH("ltxk_qknorm_rope");
+  return LTXK_OK;
+}
+
+extern "C" int ltxk_qknorm_rope_dh64(void* buf, int32_t ld, int32_t M, int32_t nseg, int32_t D,
+                                     const void* weight, const float* cos, const float* sin,
+                                     int32_t T, int32_t H, float eps, const float* sumsq, int32_t sumsq_ld, void* stream) {
+  LTXK_CHECK_ARG(buf && weight && M > 0 && nseg > 0, "ltxk_qknorm_rope_dh64: null/empty input");
+  LTXK_CHECK_ARG(H >= 1 && H <= 32 && D == H * 64, "ltxk_qknorm_rope_dh64: need D == H*64, 1 <= H <= 32 (D=%d H=%d)", D, H);
+  LTXK_CHECK_ARG((int64_t)nseg * D <= ld && ld % 8 == 0 && (((uintptr_t)buf | (uintptr_t)weight) & 15) == 0,
+                 "ltxk_qknorm_rope_dh64: ld=%d must be >= nseg*D and a multiple of 8, buf and weight 16-byte aligned", ld);
+  LTXK_CHECK_ARG((cos == nullptr) == (sin == nullptr) && (((uintptr_t)cos | (uintptr_t)sin) & 15) == 0,
+                 "ltxk_qknorm_rope_dh64: cos and sin must both be set (16-byte aligned) or both NULL");
+  LTXK_CHECK_ARG(T > 0 && (sumsq == nullptr || sumsq_ld >= nseg * H), "ltxk_qknorm_rope_dh64: T must be > 0, sumsq_ld >= nseg*D/64");
+  LTXK_CHECK_ARG((int64_t)M * nseg <= (int64_t)INT32_MAX, "ltxk_qknorm_rope_dh64: too many rows");
+  const dim3 grid((unsigned)(((int64_t)M * nseg + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK));
+  if (cos)
+    hipLaunchKernelGGL((qknorm_rope_dh64_kernel<true>), grid, dim3(256), 0, (hipStream_t)stream, (bf16*)buf, ld, M, nseg, D, (const bf16*)weight, cos, sin, T, H, eps, sumsq, sumsq_ld);
+  else
+    hipLaunchKernelGGL((qknorm_rope_dh64_kernel<false>), grid, dim3(256), 0, (hipStream_t)stream, (bf16*)buf, ld, M, nseg, D, (const bf16*)weight, cos, sin, T, H, eps, sumsq, sumsq_ld);
+  LTXK_CHECK_LAUNCH("ltxk_qknorm_rope_dh64");
   return LTXK_OK;
 }
 

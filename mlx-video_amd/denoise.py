@@ -1,5 +1,6 @@
 """Denoise loops: ``denoise_dev`` (CFG) and ``denoise_distilled`` (mlx_video/generate.py:1060-1327,
-564-881), video branch.  The step body is: tokens <- latent transpose, DiT forward(s), then one
+564-881), video branch, and ``denoise_audio_only`` (888-1053), the loop of separate audio
+generation.  The step body is: tokens <- latent transpose, DiT forward(s), then one
 fused kernel for guidance + x0 + mask blend + Euler (ops.step_tail).
 
 Sigma handling follows the reference exactly (SURVEY.md §7 "bf16-quantised timesteps"):
@@ -345,3 +346,42 @@ def denoise_distilled(latents: torch.Tensor, positions: torch.Tensor, text_embed
     out = _denoise(latents, positions, text_embeddings, None, transformer, sig, 1.0, state, compile_step, False,
                    use_graph, graph_cache, cache_context, not fp32_euler)
     return out, None
+
+
+def audio_latent_to_volume(audio_latents: torch.Tensor) -> torch.Tensor:
+    """(B,8,T,16) audio latents as the (B,128,T,1,1) volume the video loop takes, channel c*16 + f: its token view
+    (ops.latent_to_tokens) is then the reference's transpose(0,2,1,3).reshape(B,T,128) (generate.py:936-937)."""
+    b, c, t, f = audio_latents.shape
+    return audio_latents.permute(0, 1, 3, 2).reshape(b, c * f, t, 1, 1).contiguous()
+
+
+def audio_volume_to_latent(volume: torch.Tensor, channels: int = 8) -> torch.Tensor:
+    """The inverse of ``audio_latent_to_volume``: (B,128,T,1,1) -> (B,8,T,16)."""
+    b, cf, t = volume.shape[:3]
+    return volume.reshape(b, channels, cf // channels, t).permute(0, 1, 3, 2).contiguous()
+
+
+def denoise_audio_only(audio_latents: torch.Tensor, audio_positions: torch.Tensor, audio_embeddings: torch.Tensor,
+                       transformer: LTXModel, sigmas: Sequence[float], verbose: bool = False, eval_interval: int = 1,
+                       compile_step: bool = False, compile_shapeless: bool = False, fp32_euler: bool = True,
+                       ui_phase: str = "audio_denoise", use_graph: bool = False, graph_cache: Optional[dict] = None,
+                       cache_context: bool = False) -> torch.Tensor:
+    """generate.py:888-1053: the distilled-style loop of separate audio generation over an audio-only transformer
+    (``LTXModelConfig.audio()``), no CFG.  audio_latents (B,8,T,16), audio_positions (B,1,T,2) seconds
+    (``schedulers.create_audio_position_grid``), audio_embeddings (B,S,caption_channels); returns (B,8,T,16) bf16.
+    The latents run through the video loop as a (B,128,T,1,1) volume - converted once on entry and once on exit, where the
+    reference transposes in every step - so the step tail, the sigma handling (x0 with bf16(sigma), Euler in fp32 with the
+    Python floats; bf16 sigmas under ``compile_step``), ``use_graph`` and ``cache_context`` are ``denoise_distilled``'s."""
+    if audio_latents.dim() != 4:
+        raise ValueError(f"audio_latents must be (B,C,T,F), got {tuple(audio_latents.shape)}")
+    b, c, t, f = audio_latents.shape
+    if c * f != transformer.config.in_channels:
+        raise ValueError(f"audio_latents (B,{c},T,{f}) carry {c * f} values per frame, the transformer takes {transformer.config.in_channels}")
+    if tuple(audio_positions.shape) != (b, 1, t, 2):
+        raise ValueError(f"audio_positions must be ({b},1,{t},2), got {tuple(audio_positions.shape)}")
+    if len(transformer.positional_embedding_max_pos) != 1:
+        raise ValueError("denoise_audio_only needs an audio-only transformer (one position axis, LTXModelConfig.audio())")
+    sig = [float(s) for s in (sigmas.tolist() if torch.is_tensor(sigmas) else sigmas)]
+    out = _denoise(audio_latent_to_volume(audio_latents.to(BF16)), audio_positions.to(audio_latents.device), audio_embeddings, None, transformer, sig, 1.0,
+                   None, compile_step, False, use_graph, graph_cache, cache_context, not fp32_euler)
+    return audio_volume_to_latent(out, c)

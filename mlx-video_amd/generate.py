@@ -12,8 +12,8 @@ What is injected instead of loaded (nothing exists offline and they are out of s
 #17/#21): text embeddings (the Gemma-3 text encoder's output tensor is an INPUT of this path), model
 weights (`weights=` dicts or ready modules; `model_repo` may point at a local directory of
 safetensors read by ``weights.py``), random draws (`noise_fn`: MLX's threefry stream is not
-reproducible, so seeds are not cross-compatible), audio latents (`audio_latents=`: the audio DiT branch that would generate them is
-not here; they are decoded to a waveform by ``audio_vae``).  Frames are returned as the reference returns them (uint8 (F,H,W,3));
+reproducible, so seeds are not cross-compatible), audio (`audio=True`: separate generation by an audio-only transformer after the
+video, or finished `audio_latents=`; either way decoded to a waveform by ``audio_vae``; joint audio-video denoising is not here).  Frames are returned as the reference returns them (uint8 (F,H,W,3));
 `output_path` accepts `.npy`, or a video file written through an ffmpeg child process when an ffmpeg binary
 is installed (media.write_video_ffmpeg); a decoded waveform goes to a `.wav` sidecar and is muxed into that file the same way.
 """
@@ -169,8 +169,10 @@ def _layer_stack(hs) -> torch.Tensor:
     return x
 
 
-def _connect_gemma(hs, mask, neg_hs, neg_mask, text_connector, model_repo, dev):
-    """(prompt_embeds, negative_prompt_embeds or None) from Gemma hidden states: one TextConnector call, B = 2 with a negative."""
+def _connect_gemma(hs, mask, neg_hs, neg_mask, text_connector, model_repo, dev, want_audio: bool = False):
+    """(prompt_embeds, negative_prompt_embeds or None) from Gemma hidden states: one TextConnector call, B = 2 with a negative.
+    ``want_audio``: a third item, the positive prompt's AUDIO context from the audio embeddings connector over the same
+    features (``TextConnector.both``) - None when the connector that was passed in has no audio set."""
     if mask is None or (neg_hs is not None and neg_mask is None):
         raise ValueError("gemma_hidden_states need their gemma_attention_mask (and the negative pair its own)")
     if text_connector is None:
@@ -181,8 +183,20 @@ def _connect_gemma(hs, mask, neg_hs, neg_mask, text_connector, model_repo, dev):
         from .weights import text_connector_weights
         root = Path(model_repo)
         files = [f for f in sorted(root.glob("*.safetensors")) if "upscaler" not in f.name and "upsampler" not in f.name]
-        text_connector = TextConnector(text_connector_weights(files + sorted((root / "connectors").glob("*.safetensors")), dev))
+        files = files + sorted((root / "connectors").glob("*.safetensors"))
+        text_connector = TextConnector(text_connector_weights(files, dev),
+                                       text_connector_weights(files, dev, which="audio") if want_audio else None)
     x, m = _layer_stack(hs).to(dev), mask.reshape(-1, mask.shape[-1]).to(dev)
+    if want_audio:
+        both = text_connector.audio_blocks is not None
+        run = text_connector.both if both else (lambda a, b: (text_connector(a, b), None))
+        if neg_hs is not None:
+            nx, nm = _layer_stack(neg_hs).to(dev), neg_mask.reshape(-1, neg_mask.shape[-1]).to(dev)
+            if nx.shape != x.shape or x.shape[1] != 1:
+                raise ValueError(f"positive and negative gemma hidden states must both be (L,1,T,D) of one shape, got {tuple(x.shape)} and {tuple(nx.shape)}")
+            x, m = torch.cat([x, nx], 1), torch.cat([m, nm], 0)
+        video, aud = run(x, m)
+        return video[0:1], (video[1:2] if neg_hs is not None else None), (aud[0:1] if aud is not None else None)
     if neg_hs is None:
         return text_connector(x, m), None
     nx, nm = _layer_stack(neg_hs).to(dev), neg_mask.reshape(-1, neg_mask.shape[-1]).to(dev)
@@ -284,7 +298,9 @@ def generate_video(model_repo: Optional[str] = None, text_encoder_repo: Optional
                    tokenizer_path: Optional[str] = None, prompt_tokens=None, negative_prompt_tokens=None,
                    enhance_prompt: bool = False, max_tokens: int = 512, temperature: float = 0.7,
                    enhance_system_prompt: Optional[str] = None, audio_latents: Optional[torch.Tensor] = None,
-                   audio_decoder=None, vocoder=None, output_audio: Optional[str] = None) -> np.ndarray:
+                   audio_decoder=None, vocoder=None, output_audio: Optional[str] = None, audio_mode: str = "auto",
+                   audio_model_repo: Optional[str] = None, audio_steps: int = 8, audio_transformer: Optional[LTXModel] = None,
+                   audio_prompt_embeds: Optional[torch.Tensor] = None) -> np.ndarray:
     """See the module docstring.  Returns uint8 frames (F,H,W,3) (generate.py:4195-4197).
     ``hoist_context`` (not in the reference, off by default): the part of the forward that depends on the text context only -
     caption projection and the 48 cross-attention K / V^T projections, 3.37 TFLOP that the reference recomputes in every forward
@@ -324,12 +340,33 @@ def generate_video(model_repo: Optional[str] = None, text_encoder_repo: Optional
     VAE decode under an ``audio_decode`` phase by ``audio_decoder`` / ``vocoder`` (``audio_vae.AudioDecoder`` / ``Vocoder``; loaded
     from ``model_repo`` when not given) into a stereo 24 kHz waveform.  It is written to ``output_audio`` (--output-audio PATH; by
     default the ``.wav`` beside ``output_path``) and, where ``output_path`` is a video file and an ffmpeg binary exists, muxed into
-    it (generate.py:4049-4127).  ``audio=True`` - generating those latents, the audio DiT branch - keeps raising."""
+    it (generate.py:4049-4127).
+    ``audio=True`` (--audio): SEPARATE audio generation (generate.py:3930-4047, the reference's ``audio_mode="separate"``): after the
+    video an audio-only transformer (``audio_transformer=``, an ``LTXModel`` of ``LTXModelConfig.audio()``; else loaded from the
+    ``audio_*`` tensors of ``audio_model_repo``'s or ``model_repo``'s checkpoint, ``weights.load_audio_transformer``) denoises
+    (1, 8, T, 16) latents, T = ``compute_audio_frames(num_frames, fps)``, from noise seeded with ``seed`` alone, over
+    ``_subsample_sigmas(STAGE_1_SIGMAS, audio_steps)`` (``audio_steps`` 1..8, --audio-steps) without CFG
+    (``denoise.denoise_audio_only``), under an ``audio_generate`` phase; the latents then take the decode / ``.wav`` / mux path
+    above.  Its context is ``audio_prompt_embeds`` (1,S,3840), or the audio embeddings connector's output where the text
+    route runs the connector here.  ``audio_mode``: "auto" and "separate" are this; "joint" (audio and video denoised together
+    through the cross-modal attentions) is not supported and raises.  With nothing to take an audio transformer from,
+    ``audio=True`` raises as before; ``audio_latents`` given, they win and nothing is generated.  The audio transformer stays bf16
+    under ``enable_fp8``."""
     t_start = time.perf_counter()
     if isinstance(pipeline, str):
         pipeline = PipelineType(pipeline)
-    if audio:
-        raise ValueError("audio generation is not supported (audio branch is out of scope, SURVEY.md §2a #21)")
+    if audio_mode not in ("auto", "separate", "joint"):
+        raise ValueError(f"Unknown audio_mode: {audio_mode!r} (expected 'auto', 'separate' or 'joint')")
+    gen_audio = bool(audio) and audio_latents is None
+    if gen_audio:
+        if audio_mode == "joint":
+            raise ValueError("audio_mode='joint' (joint audio-video denoising) is not supported: audio is generated separately, "
+                             "after the video (audio_mode='separate', which 'auto' resolves to)")
+        if audio_transformer is None and audio_model_repo is None and model_repo is None:
+            raise ValueError("audio generation is not supported without an audio transformer: pass audio_transformer= (an LTXModel of "
+                             "LTXModelConfig.audio()), or audio_model_repo= / model_repo= a local checkpoint directory with the audio_* tensors")
+        if audio_steps < 1 or audio_steps > (len(STAGE_1_SIGMAS) - 1):
+            raise ValueError("--audio-steps must be between 1 and 8.")
     if enhance_prompt:
         _check_enhance(gemma, gemma_repo, text_encoder_repo, tokenizer_path, prompt_tokens, prompt_embeds, gemma_hidden_states, text_encoder)
     images_list = list(images or [])
@@ -439,8 +476,12 @@ def generate_video(model_repo: Optional[str] = None, text_encoder_repo: Optional
         noise_fn = _default_noise_fn(seed, dev)
 
     if prompt_embeds is None and gemma_hidden_states is not None:
-        prompt_embeds, negative_prompt_embeds = _connect_gemma(gemma_hidden_states, gemma_attention_mask, negative_gemma_hidden_states,
-                                                               negative_gemma_attention_mask, text_connector, model_repo, dev)
+        want = gen_audio and audio_prompt_embeds is None
+        got = _connect_gemma(gemma_hidden_states, gemma_attention_mask, negative_gemma_hidden_states,
+                             negative_gemma_attention_mask, text_connector, model_repo, dev, **({"want_audio": True} if want else {}))
+        prompt_embeds, negative_prompt_embeds = got[0], got[1]
+        if want:
+            audio_prompt_embeds = got[2]
     if gemma_repo is None and text_encoder_repo and Path(text_encoder_repo).is_dir():
         gemma_repo = text_encoder_repo          # the reference's name for it; a repo NAME is not resolved (nothing is fetched)
     timer = _PhaseTimer(profile or bool(profile_json_path))
@@ -450,7 +491,11 @@ def generate_video(model_repo: Optional[str] = None, text_encoder_repo: Optional
                                             seed, dev, verbose)
     if prompt_embeds is None and text_encoder is None and (gemma is not None or gemma_repo is not None):
         hs, m = _encode_gemma(gemma, gemma_repo, tokenizer_path, prompt, negative_prompt, prompt_tokens, negative_prompt_tokens, dev)
-        prompt_embeds, negative_prompt_embeds = _connect_gemma(hs[:, 0:1], m[0:1], hs[:, 1:2], m[1:2], text_connector, model_repo, dev)
+        want = gen_audio and audio_prompt_embeds is None
+        got = _connect_gemma(hs[:, 0:1], m[0:1], hs[:, 1:2], m[1:2], text_connector, model_repo, dev, **({"want_audio": True} if want else {}))
+        prompt_embeds, negative_prompt_embeds = got[0], got[1]
+        if want:
+            audio_prompt_embeds = got[2]
     if prompt_embeds is None:
         if text_encoder is None:
             raise ValueError("prompt_embeds is required: pass prompt_embeds=(1,1024,3840) or text_encoder=callable, the hidden states "
@@ -459,6 +504,9 @@ def generate_video(model_repo: Optional[str] = None, text_encoder_repo: Optional
                              "negative_prompt_tokens= or a tokenizer.json (tokenizer_path=, --tokenizer)")
         prompt_embeds = text_encoder(prompt)
         negative_prompt_embeds = text_encoder(negative_prompt)
+    if gen_audio and audio_prompt_embeds is None:
+        raise ValueError("audio=True needs the audio context: pass audio_prompt_embeds= (1,S,3840), or take a text route that runs the "
+                         "connector here (gemma_hidden_states= / gemma= / gemma_repo=) with the audio embeddings connector's weights")
     ctx_pos = prompt_embeds.to(dev).to(BF16)
     ctx_neg = (negative_prompt_embeds if negative_prompt_embeds is not None else torch.zeros_like(prompt_embeds)).to(dev).to(BF16)
 
@@ -569,6 +617,20 @@ def generate_video(model_repo: Optional[str] = None, text_encoder_repo: Optional
             top, left, oh, ow = crop
             video_np = video_np[:, top:top + oh, left:left + ow, :]
     waveform = None
+    if gen_audio:                                                      # generate.py:3930-4047
+        from .denoise import denoise_audio_only
+        from .schedulers import AUDIO_LATENT_CHANNELS, AUDIO_MEL_BINS, compute_audio_frames, create_audio_position_grid
+        with timer.phase("audio_generate"):
+            if audio_transformer is None:
+                from .weights import load_audio_transformer
+                audio_transformer = load_audio_transformer(audio_model_repo or model_repo, dev)
+            audio_frames = compute_audio_frames(num_frames, fps)
+            # seeded from `seed` alone: the audio does not depend on how much noise the video stages drew (generate.py:4025-4028)
+            a_noise = _default_noise_fn(seed, dev)((1, AUDIO_LATENT_CHANNELS, audio_frames, AUDIO_MEL_BINS))
+            a_sig = _subsample_sigmas(list(STAGE_1_SIGMAS), audio_steps, sigma_subsample)
+            audio_latents = denoise_audio_only(a_noise, create_audio_position_grid(1, audio_frames).to(dev),
+                                               audio_prompt_embeds.to(dev).to(BF16), audio_transformer, a_sig,
+                                               fp32_euler=fp32_euler, cache_context=hoist_context)
     if audio_latents is not None:                                     # generate.py:4049-4127
         from .audio_vae import decode_audio
         if audio_decoder is None or vocoder is None:
@@ -695,6 +757,16 @@ def build_parser() -> argparse.ArgumentParser:
                     help="Finished audio latents (B,8,T,16) as .npy or a torch file: decoded to a 24 kHz stereo waveform after the VAE decode")
     ap.add_argument("--output-audio", type=str, default=None, metavar="PATH",
                     help="Where the decoded waveform goes (.wav); default: beside --output-path")
+    ap.add_argument("--audio", action="store_true", default=False,
+                    help="Generate audio separately after the video (an audio-only transformer pass over the checkpoint's audio_* "
+                         "weights), decode it to a 24 kHz stereo waveform and mux it")
+    ap.add_argument("--audio-mode", choices=["auto", "separate", "joint"], default="auto",
+                    help="auto = separate; joint audio-video denoising is not supported")
+    ap.add_argument("--audio-model-repo", type=str, default=None, metavar="DIR",
+                    help="Local checkpoint directory the audio transformer is read from (default: --model-repo)")
+    ap.add_argument("--audio-steps", type=int, default=8, help="Denoise steps of the separate audio pass (1..8)")
+    ap.add_argument("--audio-prompt-embeds", type=str, default=None, metavar="FILE",
+                    help="The audio context (1,S,3840) as .npy or a torch file, where the text route does not run the connector here")
     ap.add_argument("--tiling", type=str, default="auto")
     ap.add_argument("--stage1-steps", type=int, default=None)
     ap.add_argument("--stage2-steps", type=int, default=None)
@@ -871,8 +943,15 @@ def main(argv: Optional[Sequence[str]] = None) -> None:
         kw["audio_latents"] = torch.from_numpy(np.load(args.audio_latents)) if args.audio_latents.endswith(".npy") else \
             torch.load(args.audio_latents, weights_only=True)
         kw["output_audio"] = args.output_audio
+    elif args.audio:
+        kw["output_audio"] = args.output_audio
     elif args.output_audio:
-        raise ValueError("--output-audio needs --audio-latents: the audio DiT branch that would generate them is not here")
+        raise ValueError("--output-audio needs --audio-latents (finished latents) or --audio (generate them)")
+    if args.audio:
+        kw.update(audio=True, audio_mode=args.audio_mode, audio_model_repo=args.audio_model_repo, audio_steps=args.audio_steps)
+        if args.audio_prompt_embeds:
+            f = args.audio_prompt_embeds
+            kw["audio_prompt_embeds"] = torch.from_numpy(np.load(f)) if f.endswith(".npy") else torch.load(f, weights_only=True)
     if args.gemma_repo:
         kw["gemma_repo"], kw["tokenizer_path"] = args.gemma_repo, args.tokenizer
     if args.prompt_tokens:

@@ -2,8 +2,9 @@
 (mlx_video/models/ltx/ltx.py:459-506, transformer.py:13-22,247-261,342-347).
 
 Same names, argument meaning and error behaviour as the reference; every numeric op is a
-libltxk HIP kernel (``ops``).  Video-only (the audio / cross-modal branches are out of scope,
-SURVEY.md §2a #3).
+libltxk HIP kernel (``ops``).  One modality per model: the video transformer (head dim 128, three position axes), or - the
+same class at ``LTXModelConfig.audio()`` - the audio-only transformer of separate audio generation (head dim 64, one position
+axis).  The cross-modal (a2v / v2a) attentions of joint denoising are out of scope.
 
 Data layout in HBM (per GPU, bf16 unless noted):
   * weights: one contiguous (out,in) matrix per Linear, with to_q|to_k of the self-attention
@@ -64,6 +65,16 @@ class LTXModelConfig:
     def inner_dim(self) -> int:
         return self.num_attention_heads * self.attention_head_dim
 
+    @classmethod
+    def audio(cls, **overrides) -> "LTXModelConfig":
+        """The audio-only transformer of the same checkpoint (config.py AudioOnly: audio_num_attention_heads 32,
+        audio_attention_head_dim 64, audio_cross_attention_dim 2048, audio_positional_embedding_max_pos [20], latent
+        width 128 = 8 channels x 16 mel bins): the video architecture at other sizes, with ONE position axis."""
+        kw = dict(num_attention_heads=32, attention_head_dim=64, in_channels=128, out_channels=128, cross_attention_dim=2048,
+                  positional_embedding_max_pos=(20,))
+        kw.update(overrides)
+        return cls(**kw)
+
 
 @dataclass
 class TimestepPlan:
@@ -83,7 +94,8 @@ def precompute_freqs_cis(positions: torch.Tensor, dim: int, theta: float = 10000
     """rope.py:364-416 -> 419-529 (SPLIT, double_precision path, middle-indices grid).
     positions (B,3,N,2) float32 on device.  Returns cos, sin (B,H,N,dim/H/2) float32.  The
     per-index frequency vector theta^linspace(0,1,n)*pi/2 (682 floats) is a host table; the
-    (N x dim/2) trig table is a HIP kernel."""
+    (N x dim/2) trig table is a HIP kernel.  positions (B,1,N,2) with a one-entry ``max_pos`` (the audio transformer): the
+    whole table on the host (``_freqs_cis_one_axis``)."""
     if positions.dtype == BF16:      # rope.py:433-445: warn, then compute from the (already rounded) values in float32
         import warnings
         warnings.warn("Position grid has dtype bfloat16, which causes precision loss in RoPE. "
@@ -91,8 +103,12 @@ def precompute_freqs_cis(positions: torch.Tensor, dim: int, theta: float = 10000
     if positions.dtype != torch.float32:
         positions = positions.to(torch.float32)
     b, nd, n, two = positions.shape
-    if nd != 3 or two != 2:
-        raise ValueError(f"positions must be (B,3,N,2), got {tuple(positions.shape)}")
+    if nd not in (1, 3) or two != 2:
+        raise ValueError(f"positions must be (B,3,N,2), or (B,1,N,2) for one position axis, got {tuple(positions.shape)}")
+    if len(max_pos) != nd:
+        raise ValueError(f"positions have {nd} axes, max_pos {len(max_pos)}")
+    if nd == 1:
+        return _freqs_cis_one_axis(positions, dim, theta, float(max_pos[0]), num_attention_heads)
     n_freq = max(dim // (2 * nd), 1)
     lin = torch.linspace(0.0, 1.0, n_freq, dtype=torch.float32)
     freq = (torch.pow(torch.tensor(theta, dtype=torch.float32), lin) * (math.pi / 2)).to(positions.device)
@@ -102,6 +118,23 @@ def precompute_freqs_cis(positions: torch.Tensor, dim: int, theta: float = 10000
         cos_l.append(c)
         sin_l.append(s)
     return torch.stack(cos_l), torch.stack(sin_l)
+
+
+def _freqs_cis_one_axis(positions: torch.Tensor, dim: int, theta: float, max_pos: float, heads: int,
+                        ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The table for ONE position axis (the audio transformer: positions (B,1,N,2) seconds, max_pos 20), on the host in the
+    fp32 arithmetic of rope.py:419-529: dim/2 frequencies theta^linspace(0,1,dim/2) * pi/2 (no front pad: every slot has a
+    frequency), angle = ((start + end)/2 / max_pos * 2 - 1) * freq, head h takes angles [h*dim/H/2, (h+1)*dim/H/2).
+    N x dim/2 values, computed once per denoise loop (the route of text_connector.rope_table_1d): no kernel."""
+    pos = positions.detach().to("cpu", torch.float32)
+    half = dim // 2
+    lin = torch.linspace(0.0, 1.0, half, dtype=torch.float32)
+    freq = torch.pow(torch.tensor(theta, dtype=torch.float32), lin) * (math.pi / 2)
+    mid = (pos[:, 0, :, 0] + pos[:, 0, :, 1]) / 2.0                       # (B,N)
+    ang = ((mid / max_pos) * 2 - 1).unsqueeze(-1) * freq.reshape(1, 1, -1)      # (B,N,dim/2)
+    b, n = mid.shape
+    out = [f(ang).reshape(b, n, heads, half // heads).transpose(1, 2).contiguous().to(positions.device) for f in (torch.cos, torch.sin)]
+    return out[0], out[1]
 
 
 class Linear:
@@ -183,7 +216,10 @@ class LTXModel:
         #   8: self-attention q|k and v as TWO launches after all - q|k (N=8192) then fills exactly one round of the
         #   320x256-tile kernel, 152 + 74 us against 239 us for the one q|k|v launch on 160x256 tiles at M=2560
         #   (profiles/r02_gemm_big_tile_ab.log); the text k|v pair stays one launch (it takes the big tile as it is)
-        self.fuse = int(fuse)
+        if config.attention_head_dim not in (64, 128):
+            raise ValueError(f"attention_head_dim = {config.attention_head_dim}: the attention kernels take 128 (video) or 64 (audio)")
+        # head dim 64 (the audio transformer): ltxk_flash_attn_dh64 has no fused query preparation - bit 4 is off there
+        self.fuse = int(fuse) & ~4 if config.attention_head_dim == 64 else int(fuse)
         # every token through the token->row map even when all tokens share one timestep row (A/B runs only)
         self.tok2row_always = False
         # True makes a forward's bits independent of the batch it runs in (B=1 per CFG-pair rank == row b of the B=2
@@ -452,7 +488,7 @@ class LTXModel:
         # k (row-major, with its per-row sums of squares) and V^T from one launch over the packed k|v panel
         st = ss if self.fuse & 2 else None
         self._lin(ctx, ctx_q, self._context_kv_launches(blk, k2, vt2, st, s), fresh=False)
-        ops.qknorm_rope(k2, 1, D, blk.wkn2, None, None, s, H, eps, sumsq=st)
+        ops.qknorm_rope(k2, 1, D, blk.wkn2, None, None, s, H, eps, sumsq=st, head_dim=self.config.attention_head_dim)
         return k2, vt2, ss
 
     def _quant_context(self, ctx: torch.Tensor, s: int) -> Optional[tuple]:
@@ -465,7 +501,10 @@ class LTXModel:
         """Whether the grouped launch gives the bits of the per-block ``_context_kv`` calls: it is single-pass, as they are unless
         the library would split K at this row count (small M with the split-K scratch on offer)."""
         D = self.inner_dim
-        # (the grouped launch has no weight-fp8 form: an fp8 model goes per block - the same bits)
+        # (the grouped launch has no weight-fp8 form: an fp8 model goes per block - the same bits; its k-norm launch,
+        # ltxk_qknorm_grouped_ss, is head dim 128 only: a head-dim-64 model goes per block too)
+        if self.config.attention_head_dim != 128:
+            return False
         if not self.grouped_context_kv or (self.fuse & 3) != 3 or D % 256 != 0 or self.weight_dtype != BF16:
             return False
         return not self._plan(b * s, 2 * D, D, n_split=D, out_tokens_per_batch=s, sumsq=True).split_k
@@ -502,7 +541,7 @@ class LTXModel:
                        pe: Tuple[torch.Tensor, torch.Tensor], ctx_kv: Optional[ContextKV] = None,
                        hidden: Optional[List[torch.Tensor]] = None,
                        perturbations: Optional[BatchedPerturbationConfig] = None) -> torch.Tensor:
-        """latent (B,N,128) bf16; context (B,S,3840) bf16; pe = (cos,sin) each (1|B,H,N,64) fp32
+        """latent (B,N,128) bf16; context (B,S,3840) bf16; pe = (cos,sin) each (1|B,H,N,head_dim/2) fp32
         (one table shared by every batch row, as in cfg_batch where it is a broadcast,
         generate.py:1196-1202).  ``ctx_kv``: a ContextKV of THIS context (prepare_context); without it the
         caption projection and the text K/V are recomputed here, as the reference does every forward.
@@ -525,7 +564,8 @@ class LTXModel:
         # one timestep row for every token (an unconditioned CFG pair): no per-token row gather - the kernels then skip a
         # dependent load in front of every modulation / gate read
         tok2row = plan.tok2row if (U > 1 or self.tok2row_always) else None
-        scale = 1.0 / math.sqrt(cfg.attention_head_dim)
+        dh = cfg.attention_head_dim
+        scale = 1.0 / math.sqrt(dh)
 
         # --- prepare (ltx.py:129-158) ---
         # Row statistics travel with the residual stream: every GEMM that writes x also emits the per-row sums of
@@ -611,16 +651,16 @@ class LTXModel:
             # the q side of the two attentions: raw q with its row statistics, normalised (and rotated) inside the kernel - or
             # q normalised by a launch of its own in front
             if fp:
-                ops.qknorm_rope(qk[:, D:], 1, D, blk.wkn, cos, sin, N, H, eps, sumsq=qkss[:, P:])
+                ops.qknorm_rope(qk[:, D:], 1, D, blk.wkn, cos, sin, N, H, eps, sumsq=qkss[:, P:], head_dim=dh)
                 fused1, fused2 = dict(q_norm_weight=blk.wqn, cos=cos, sin=sin, eps=eps), dict(q_sumsq=q2ss, q_norm_weight=blk.wqn2, eps=eps)
             else:
-                ops.qknorm_rope(qk, 2, D, blk.wqkn, cos, sin, N, H, eps, sumsq=s_qk)
+                ops.qknorm_rope(qk, 2, D, blk.wqkn, cos, sin, N, H, eps, sumsq=s_qk, head_dim=dh)
                 fused1 = fused2 = {}
             # attention over each maximal run of rows that keep it (all B rows in one launch when nothing is skipped)
             for r0, r1 in _runs(B, skip):
                 t0, t1 = r0 * N, r1 * N
                 ops.flash_attn(qk[t0:t1, :D], qk[t0:t1, D:], vt[r0:r1], att[t0:t1], r1 - r0, H, N, N, scale,
-                               q_sumsq=qkss[t0:t1] if fp else None, tail_split=ts_, **fused1)
+                               q_sumsq=qkss[t0:t1] if fp else None, tail_split=ts_, head_dim=dh, **fused1)
             if skip:          # STG: the skipped rows' attention output is their value projection, v = (V^T)^T
                 ops.attn_value_passthrough(vt, att, B, N, sum(1 << r for r in skip))
             self._linear(att, blk.o, att_q, epilogue=ops.EPI_BIAS_GATE_RES, out=x, resid=x,
@@ -635,8 +675,8 @@ class LTXModel:
             else:
                 kv = self._context_kv(blk, ctx, B, S, kv_buf, ctx_q)
             if not fp:
-                ops.qknorm_rope(q2, 1, D, blk.wqn2, None, None, N, H, eps, sumsq=s_q2)
-            ops.flash_attn(q2, kv[0], kv[1], att, B, H, N, S, scale, tail_split=ts_, **fused2)
+                ops.qknorm_rope(q2, 1, D, blk.wqn2, None, None, N, H, eps, sumsq=s_q2, head_dim=dh)
+            ops.flash_attn(q2, kv[0], kv[1], att, B, H, N, S, scale, tail_split=ts_, head_dim=dh, **fused2)
             self._linear(att, blk.o2, att_q, epilogue=ops.EPI_BIAS_RES, out=x, resid=x, sumsq=s_x)
             # feed-forward (transformer.py:343-347)
             ops.rmsnorm_modulate(x, eps, mod[:, 4], mod[:, 3], ms, tok2row, out=nx, sumsq=s_x, scale_is_one_plus=bool(fs))

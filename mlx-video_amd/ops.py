@@ -389,16 +389,22 @@ def gemm_grouped_plan(G: int, M: int, N: int, K: int, *, n_split: int, out_token
 def flash_attn(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, out: torch.Tensor, B: int, H: int,
                Tq: int, Tk: int, scale: float, q_sumsq: Optional[torch.Tensor] = None,
                q_norm_weight: Optional[torch.Tensor] = None, cos: Optional[torch.Tensor] = None,
-               sin: Optional[torch.Tensor] = None, eps: float = 1e-6, tail_split: bool = True) -> torch.Tensor:
+               sin: Optional[torch.Tensor] = None, eps: float = 1e-6, tail_split: bool = True, head_dim: int = 128) -> torch.Tensor:
     """q (B*Tq, H*128) rows, k (B*Tk, H*128) rows, vt (B, H*128, ld >= Tk), out (B*Tq, H*128) rows.  With ``q_sumsq``
     (B*Tq, >= H*2) the raw q projection is normalised (q_norm_weight (H*128)) and rotated (cos/sin (H,Tq,64)) inside the
     kernel; without it those three are not read.
-    ``tail_split=False``: LTXK_ATTN_NO_TAIL_SPLIT (results independent of how many (batch, head) pairs share the launch)."""
+    ``tail_split=False``: LTXK_ATTN_NO_TAIL_SPLIT (results independent of how many (batch, head) pairs share the launch).
+    ``head_dim=64``: ltxk_flash_attn_dh64, the same operands at H*64 columns; it has no fused query preparation (``q_sumsq`` is
+    refused) and one launch form, so ``tail_split`` has nothing to decide."""
+    if head_dim not in (64, 128):
+        raise ValueError(f"flash_attn: head_dim = {head_dim} must be 128 or 64")
+    if head_dim == 64 and q_sumsq is not None:
+        raise ValueError("flash_attn: head_dim = 64 has no fused query preparation, q_sumsq must be None")
     if q_sumsq is None:
         q_norm_weight = cos = sin = None
     elif q_norm_weight is None or (cos is None) != (sin is None):
         raise ValueError("flash_attn: q_sumsq needs q_norm_weight, and cos and sin both or neither")
-    D = H * 128
+    D = H * head_dim
     _operands("flash_attn", ("q", q, BF16, (B * Tq, D), 16, True), ("k", k, BF16, (B * Tk, D), 16, True),
               ("vt", vt, BF16, (B, D, -Tk), 16, True), ("out", out, BF16, (B * Tq, D), 16, True),
               ("q_sumsq", q_sumsq, F32, (B * Tq, -(H * 2)), 16, True),
@@ -412,8 +418,11 @@ def flash_attn(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, out: torch.Te
     if q_sumsq is not None:
         a.q_sumsq, a.q_sumsq_ld, a.q_sumsq_n = _p(q_sumsq), q_sumsq.stride(0), H * 2
         a.q_norm_weight, a.cos, a.sin, a.eps = _p(q_norm_weight), _p(cos), _p(sin), eps
-    with _timed("flash_attn", 4.0 * B * H * Tq * Tk * 128, 2.0 * B * H * 128 * (2 * Tq + 2 * Tk)):
-        check(_lib.load().ltxk_flash_attn(ctypes.byref(a), _stream()), "ltxk_flash_attn")
+    with _timed("flash_attn", 4.0 * B * H * Tq * Tk * head_dim, 2.0 * B * H * head_dim * (2 * Tq + 2 * Tk)):
+        if head_dim == 64:
+            check(_lib.load().ltxk_flash_attn_dh64(ctypes.byref(a), _stream()), "ltxk_flash_attn_dh64")
+        else:
+            check(_lib.load().ltxk_flash_attn(ctypes.byref(a), _stream()), "ltxk_flash_attn")
     return out
 
 
@@ -503,17 +512,25 @@ def layernorm_modulate(x: torch.Tensor, eps: float, scale: Optional[torch.Tensor
 
 
 def qknorm_rope(buf: torch.Tensor, nseg: int, D: int, weight: torch.Tensor, cos: Optional[torch.Tensor],
-                sin: Optional[torch.Tensor], T: int, H: int, eps: float, sumsq: Optional[torch.Tensor] = None) -> torch.Tensor:
+                sin: Optional[torch.Tensor], T: int, H: int, eps: float, sumsq: Optional[torch.Tensor] = None,
+                head_dim: int = 128) -> torch.Tensor:
     """In place on the first nseg*D columns of buf (M, ld), D = 128*H: weight (nseg,D) (or flat), cos / sin (H,T,64) fp32 or
-    both None.  ``sumsq`` (M, >= nseg*D/64) fp32: precomputed partial sums of squares of those columns (gemm(..., sumsq=))."""
-    if (cos is None) != (sin is None) or D != 128 * H:
-        raise ValueError(f"qknorm_rope: cos and sin go together, and D = {D} must be 128 * H = {128 * H}")
+    both None.  ``sumsq`` (M, >= nseg*D/64) fp32: precomputed partial sums of squares of those columns (gemm(..., sumsq=)).
+    ``head_dim=64``: ltxk_qknorm_rope_dh64 - D = 64*H, H <= 32, cos / sin (H,T,32), the rotation partner of channel j is j + 32."""
+    if head_dim not in (64, 128):
+        raise ValueError(f"qknorm_rope: head_dim = {head_dim} must be 128 or 64")
+    if (cos is None) != (sin is None) or D != head_dim * H:
+        raise ValueError(f"qknorm_rope: cos and sin go together, and D = {D} must be {head_dim} * H = {head_dim * H}")
     M, ld = _dims("qknorm_rope", "buf", buf, BF16, 2)
     _operands("qknorm_rope", ("buf", buf if ld == nseg * D else buf[:, :nseg * D], BF16, (M, nseg * D), 16, True),
-              ("weight", weight, BF16, (nseg, D) if weight.dim() == 2 else (nseg * D,), 16), ("cos", cos, F32, (H, T, 64), 16),
-              ("sin", sin, F32, (H, T, 64), 16), ("sumsq", sumsq, F32, (M, -(nseg * D // 64)), 4, True))
+              ("weight", weight, BF16, (nseg, D) if weight.dim() == 2 else (nseg * D,), 16), ("cos", cos, F32, (H, T, head_dim // 2), 16),
+              ("sin", sin, F32, (H, T, head_dim // 2), 16), ("sumsq", sumsq, F32, (M, -(nseg * D // 64)), 4, True))
     with _timed("qknorm_rope", 0.0, 4.0 * M * nseg * D + (8.0 * M * D // 2 if cos is not None else 0.0)):
-        if sumsq is not None:
+        if head_dim == 64:
+            check(_lib.load().ltxk_qknorm_rope_dh64(_p(buf), buf.stride(0), M, nseg, D, _p(weight), _p(cos), _p(sin), T, H, eps,
+                                                    _p(sumsq), 0 if sumsq is None else sumsq.stride(0), _stream()),
+                  "ltxk_qknorm_rope_dh64")
+        elif sumsq is not None:
             check(_lib.load().ltxk_qknorm_rope_ss(_p(buf), buf.stride(0), M, nseg, D, _p(weight), _p(cos), _p(sin),
                                                   T, H, eps, _p(sumsq), sumsq.stride(0), _stream()), "ltxk_qknorm_rope_ss")
         else:

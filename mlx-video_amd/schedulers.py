@@ -114,6 +114,35 @@ def create_position_grid(batch_size: int, num_frames: int, height: int, width: i
     return torch.from_numpy(np.broadcast_to(grid[None], (batch_size, 3, n, 2)).copy())
 
 
+AUDIO_LATENT_SAMPLE_RATE = 16000           # the audio VAE's internal sample rate
+AUDIO_HOP_LENGTH = 160
+AUDIO_LATENT_DOWNSAMPLE_FACTOR = 4
+AUDIO_LATENT_CHANNELS = 8
+AUDIO_MEL_BINS = 16
+AUDIO_LATENTS_PER_SECOND = AUDIO_LATENT_SAMPLE_RATE / AUDIO_HOP_LENGTH / AUDIO_LATENT_DOWNSAMPLE_FACTOR      # 25
+
+
+def create_audio_position_grid(batch_size: int, audio_frames: int, sample_rate: int = AUDIO_LATENT_SAMPLE_RATE,
+                               hop_length: int = AUDIO_HOP_LENGTH, downsample_factor: int = AUDIO_LATENT_DOWNSAMPLE_FACTOR,
+                               is_causal: bool = True) -> torch.Tensor:
+    """Per-token [start,end) times in seconds of the audio latent frames, (B,1,T,2) fp32 (generate.py:528-551): latent frame
+    i covers mel frames from i*downsample (causal: shifted by 1 - downsample, clipped at 0), one mel frame is
+    hop_length / sample_rate seconds.  fp32 arithmetic in the reference's order; bit-exact contract."""
+    def seconds(first: int, last: int) -> np.ndarray:
+        mel = np.arange(first, last, dtype=np.float32) * downsample_factor
+        if is_causal:
+            mel = np.clip(mel + 1 - downsample_factor, 0, None)
+        return mel * hop_length / sample_rate
+
+    grid = np.stack([seconds(0, audio_frames), seconds(1, audio_frames + 1)], -1).astype(np.float32)          # (T,2)
+    return torch.from_numpy(np.broadcast_to(grid[None, None], (batch_size, 1, audio_frames, 2)).copy())
+
+
+def compute_audio_frames(num_video_frames: int, fps: float) -> int:
+    """Audio latent frames of a video of this length, 25 per second (generate.py:554-557)."""
+    return round(num_video_frames / fps * AUDIO_LATENTS_PER_SECOND)
+
+
 def cfg_delta(cond: torch.Tensor, uncond: torch.Tensor, scale: float) -> torch.Tensor:
     """generate.py:382-393 / guiders.py CFGGuider.delta (hook contract; host tensors)."""
     return (scale - 1.0) * (cond - uncond)

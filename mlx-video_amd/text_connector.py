@@ -80,7 +80,7 @@ class TextConnector:
     ff.{proj_in,proj_out}}.*``.  Width, heads (D/128), blocks, register count and the number of hidden states L are read off
     the shapes."""
 
-    def __init__(self, weights: Dict[str, torch.Tensor]):
+    def __init__(self, weights: Dict[str, torch.Tensor], audio_weights: Optional[Dict[str, torch.Tensor]] = None):
         reg = weights["learnable_registers"]
         self.device = reg.device
         self.R, self.D = (int(v) for v in reg.shape)
@@ -97,21 +97,36 @@ class TextConnector:
             raise ValueError(f"aggregate_embed.weight must be ({self.D}, L*{self.D}), got {tuple(agg.shape)}")
         self.L = int(agg.shape[1]) // self.D
         self.agg = agg.to(BF16).contiguous()
+        self.blocks = self._block_set(weights)
+        # the audio embeddings connector (text_encoder.py:698, 838-871, 949-952): the same structure - its own registers and
+        # blocks - over the SAME features; ``both`` runs the two sets over features computed once
+        self.audio_registers = self.audio_blocks = None
+        if audio_weights is not None:
+            areg = audio_weights["learnable_registers"]
+            if tuple(areg.shape) != (self.R, self.D):
+                raise ValueError(f"the audio connector's learnable_registers are {tuple(areg.shape)}, the video connector's {(self.R, self.D)}")
+            self.audio_registers = areg.to(BF16).contiguous()
+            self.audio_blocks = self._block_set(audio_weights)
+        self._rope: Dict[int, Tuple[torch.Tensor, torch.Tensor]] = {}
+
+    @staticmethod
+    def _block_set(weights: Dict[str, torch.Tensor]) -> list:
+        """The packed panels of one connector's ``transformer_1d_blocks.*``."""
         n = 1 + max((int(k.split(".")[1]) for k in weights if k.startswith("transformer_1d_blocks.")), default=-1)
         if n <= 0:
             raise ValueError("no transformer_1d_blocks.* in the connector weights")
-        self.blocks = []
+        blocks = []
         for i in range(n):
             p = f"transformer_1d_blocks.{i}."
             g = lambda name: weights[p + name].to(BF16)
-            self.blocks.append(dict(
+            blocks.append(dict(
                 qkv_w=torch.cat([g("attn1.to_q.weight"), g("attn1.to_k.weight"), g("attn1.to_v.weight")], 0).contiguous(),
                 qkv_b=torch.cat([g("attn1.to_q.bias"), g("attn1.to_k.bias"), g("attn1.to_v.bias")], 0).contiguous(),
                 qkn=torch.stack([g("attn1.q_norm.weight"), g("attn1.k_norm.weight")], 0).contiguous(),
                 o_w=g("attn1.to_out.weight").contiguous(), o_b=g("attn1.to_out.bias").contiguous(),
                 ff1_w=g("ff.proj_in.weight").contiguous(), ff1_b=g("ff.proj_in.bias").contiguous(),
                 ff2_w=g("ff.proj_out.weight").contiguous(), ff2_b=g("ff.proj_out.bias").contiguous()))
-        self._rope: Dict[int, Tuple[torch.Tensor, torch.Tensor]] = {}
+        return blocks
 
     # ------------------------------------------------------------------ stages
     def _tables(self, T: int):
@@ -152,9 +167,10 @@ class TextConnector:
         # the total row count of the call, never on the run)
         return ops.gemm(normed, self.agg, None), r0, cnt
 
-    def connect(self, x: torch.Tensor) -> torch.Tensor:
+    def connect(self, x: torch.Tensor, blocks: Optional[list] = None) -> torch.Tensor:
         """Embeddings1DConnector on an assembled (B,T,D) input: the pre-norm blocks and the final unit RMSNorm.  No GEMM here
-        is offered split-K and attention runs without its tail split, so a batch row's output does not depend on the batch."""
+        is offered split-K and attention runs without its tail split, so a batch row's output does not depend on the batch.
+        ``blocks``: the block set to run (None: the video connector's)."""
         B, T, D = x.shape
         H, M = self.H, B * T
         dev = x.device
@@ -166,7 +182,7 @@ class TextConnector:
         vt = (torch.zeros if tpad != T else torch.empty)((B, D, tpad), dtype=BF16, device=dev)
         att = torch.empty((M, D), dtype=BF16, device=dev)
         scale = 1.0 / math.sqrt(HEAD_DIM)
-        for blk in self.blocks:
+        for blk in (self.blocks if blocks is None else blocks):
             ops.rmsnorm_rows(x, NORM_EPS, out=nx)
             ops.gemm(nx, blk["qkv_w"], blk["qkv_b"], out=qk, out2=vt, n_split=2 * D, out_tokens_per_batch=T, split_k=False)
             ops.qknorm_rope_1d(qk, D, blk["qkn"], cos, sin, T, H, NORM_EPS)
@@ -178,7 +194,19 @@ class TextConnector:
             ops.gemm(h, blk["ff2_w"], blk["ff2_b"], epilogue=ops.EPI_BIAS_RES, out=x, resid=x, split_k=False)
         return ops.rmsnorm_rows(x, NORM_EPS).view(B, T, D)
 
-    def __call__(self, hidden_states: Union[torch.Tensor, Sequence[torch.Tensor]], attention_mask: torch.Tensor) -> torch.Tensor:
+    def both(self, hidden_states: Union[torch.Tensor, Sequence[torch.Tensor]], attention_mask: torch.Tensor,
+             ) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(video context, audio context), each (B,T,D): the features are computed once and each connector assembles them with
+        its own registers and runs its own blocks (text_encoder.py:943-952).  Needs ``audio_weights``."""
+        if self.audio_blocks is None:
+            raise ValueError("this TextConnector was built without the audio embeddings connector (audio_weights=)")
+        counts, B, T = self._checked(hidden_states, attention_mask)
+        feat, row0, cnt = self.features(hidden_states, counts)
+        video = self.connect(ops.connector_assemble(feat, self.registers, row0, cnt, B, T))
+        audio = self.connect(ops.connector_assemble(feat, self.audio_registers, row0, cnt, B, T), self.audio_blocks)
+        return video, audio
+
+    def _checked(self, hidden_states, attention_mask: torch.Tensor):
         counts = mask_row_counts(attention_mask)
         B, T = attention_mask.shape
         if T % self.R:
@@ -187,6 +215,10 @@ class TextConnector:
         shape = tuple(hidden_states[0].shape) if isinstance(hidden_states, (list, tuple)) else tuple(hidden_states.shape[1:])
         if shape[:2] != (B, T):
             raise ValueError(f"hidden_states are {shape} per layer but attention_mask is {(B, T)}")
+        return counts, B, T
+
+    def __call__(self, hidden_states: Union[torch.Tensor, Sequence[torch.Tensor]], attention_mask: torch.Tensor) -> torch.Tensor:
+        counts, B, T = self._checked(hidden_states, attention_mask)
         feat, row0, cnt = self.features(hidden_states, counts)
         return self.connect(ops.connector_assemble(feat, self.registers, row0, cnt, B, T))
 

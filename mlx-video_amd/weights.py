@@ -144,6 +144,83 @@ def transformer_weights(raw: Dict[str, torch.Tensor], device, fp8: bool = False,
     return out
 
 
+# top-level / per-block audio names of the joint checkpoint -> the names the one model class reads (ltx.py AudioOnly)
+_AUDIO_TOP = (("audio_patchify_proj.", "patchify_proj."), ("audio_adaln_single.", "adaln_single."),
+              ("audio_caption_projection.", "caption_projection."), ("audio_proj_out.", "proj_out."))
+_AUDIO_BLOCK = (("audio_attn1.", "attn1."), ("audio_attn2.", "attn2."), ("audio_ff.", "ff."))
+
+
+def _audio_transformer_key(raw_key: str) -> Optional[str]:
+    """Checkpoint key -> module key of the AUDIO-ONLY transformer, or None: the ``audio_*`` tensors of the joint checkpoint under
+    the video names.  The cross-modal tensors are not part of it - ``audio_to_video_attn`` (which also starts with ``audio_``),
+    ``video_to_audio_attn``, ``scale_shift_table_a2v_ca_*``, ``av_ca_*`` - nor is ``audio_embeddings_connector``."""
+    from .ltx_model import LTXModel
+    k = raw_key
+    if k.startswith("model.diffusion_model."):
+        m = LTXModel.sanitize({k: None})
+        if not m:
+            return None
+        k = next(iter(m))
+    elif k.startswith("transformer."):
+        k = k[len("transformer."):]
+    if "audio_to_video" in k or "video_to_audio" in k or "a2v_ca" in k or "av_ca_" in k or "embeddings_connector" in k:
+        return None
+    if k == "audio_scale_shift_table":
+        return "scale_shift_table"
+    for old, new in _AUDIO_TOP:
+        if k.startswith(old):
+            return new + k[len(old):]
+    if k.startswith("transformer_blocks."):
+        head, idx, rest = k.split(".", 2)
+        if rest == "audio_scale_shift_table":
+            return f"{head}.{idx}.scale_shift_table"
+        for old, new in _AUDIO_BLOCK:
+            if rest.startswith(old):
+                return f"{head}.{idx}.{new}{rest[len(old):]}"
+    return None
+
+
+def audio_transformer_weights(raw: Dict[str, torch.Tensor], device) -> Dict[str, torch.Tensor]:
+    """Module-key dict of the audio-only transformer (``LTXModel(LTXModelConfig.audio(), ...)``) from the same checkpoint the
+    video transformer is read from: ``_audio_transformer_key``.  bf16 (an fp8 checkpoint is upcast)."""
+    out = {}
+    for k, v in raw.items():
+        kk = _audio_transformer_key(k)
+        if kk is not None:
+            out[kk] = _to_dev(v, device)
+    return out
+
+
+def infer_audio_transformer_config(shapes: Dict[str, Iterable[int]]):
+    """``LTXModelConfig.audio()`` with depth, widths and head count from the shapes of an ``audio_transformer_weights`` dict
+    (head dim 64: the audio transformer's, config.py audio_attention_head_dim)."""
+    from .ltx_model import LTXModelConfig
+    layers = 1 + max((int(k.split(".")[1]) for k in shapes if k.startswith("transformer_blocks.")), default=-1)
+    if layers <= 0 or "patchify_proj.weight" not in shapes:
+        raise ValueError("no audio transformer in this checkpoint: no transformer_blocks.*.audio_* / audio_patchify_proj.weight")
+    inner, in_ch = (int(x) for x in shapes["patchify_proj.weight"])
+    if inner % 64:
+        raise ValueError(f"audio inner dim {inner} is not a multiple of the head dim 64")
+    return LTXModelConfig.audio(num_attention_heads=inner // 64, in_channels=in_ch, out_channels=int(list(shapes["proj_out.weight"])[0]),
+                                num_layers=layers, cross_attention_dim=inner,
+                                caption_channels=int(list(shapes["caption_projection.linear1.weight"])[1]))
+
+
+def load_audio_transformer(model_repo, device):
+    """The audio-only ``LTXModel`` of a local checkpoint directory (generate.py:3969-4015): the ``audio_*`` tensors of its
+    LTX-2 safetensors, streamed one by one; strict (every expected key must be there).  FileNotFoundError / ValueError when the
+    directory or the audio tensors are missing."""
+    from .ltx_model import LTXModel
+    root = Path(model_repo)
+    if not root.is_dir():
+        raise FileNotFoundError(f"model_repo {str(model_repo)!r} is not a local directory; nothing is fetched")
+    main = [f for f in sorted(root.glob("*.safetensors")) if "upscaler" not in f.name and "upsampler" not in f.name]
+    W = {_audio_transformer_key(k): _to_dev(v, device)
+         for k, v in iter_safetensors(main, want=lambda k: _audio_transformer_key(k) is not None)}
+    cfg = infer_audio_transformer_config({k: tuple(v.shape) for k, v in W.items()})
+    return LTXModel(cfg, W)
+
+
 def quantize_transformer_weights(W: Dict[str, torch.Tensor], fp8_scaling: str = "channel") -> Dict[str, torch.Tensor]:
     """A bf16 module-key dict (e.g. after a LoRA merge) -> the dict ``transformer_weights(fp8=True)`` gives; the input is kept."""
     out: Dict[str, torch.Tensor] = {}
@@ -305,26 +382,33 @@ def _connector_key(k: str) -> str:
     return k.replace(".ff.net.0.proj.", ".ff.proj_in.").replace(".ff.net.2.", ".ff.proj_out.").replace(".to_out.0.", ".to_out.")
 
 
-def text_connector_weights(files: Iterable[Path], device) -> Dict[str, torch.Tensor]:
+def text_connector_weights(files: Iterable[Path], device, which: str = "video") -> Dict[str, torch.Tensor]:
     """The feature extractor + video embeddings connector of ``text_connector.TextConnector`` from safetensors files, under
     module keys: ``aggregate_embed.weight_layer_major`` (K axis permuted, ``aggregate_k_to_layer_major``),
     ``learnable_registers``, ``transformer_1d_blocks.*``.  Three key families are read (text_encoder.py:756-836):
     `text_embedding_projection.aggregate_embed.weight` + `model.diffusion_model.video_embeddings_connector.*`;
     `connector.video_embeddings_connector.*`; `text_proj_in.weight` + `video_connector.*` (a diffusers
     connectors/diffusion_pytorch_model.safetensors).  The first family that has connector tensors wins, as in the reference;
-    `audio_embeddings_connector.*` / `audio_connector.*` are ignored."""
+    `audio_embeddings_connector.*` / `audio_connector.*` are ignored.
+    ``which="audio"``: the audio embeddings connector instead (text_encoder.py:838-871) - the same three families with
+    `audio_` in place of `video_` in the prefix, the same aggregate_embed (the feature extractor is shared); the video
+    connector's tensors are then the ignored ones."""
+    if which not in ("video", "audio"):
+        raise ValueError(f"text_connector_weights: which must be 'video' or 'audio', got {which!r}")
+    families = _CONNECTOR_FAMILIES if which == "video" else \
+        tuple((agg, pre.replace("video_", "audio_")) for agg, pre in _CONNECTOR_FAMILIES)
     files = [Path(f) for f in files]
     found = []
     for f in files:
         keys = [k for k in scan_header(f) if k != "__metadata__"]
-        for fam, (agg_key, prefix) in enumerate(_CONNECTOR_FAMILIES):
+        for fam, (agg_key, prefix) in enumerate(families):
             if any(k.startswith(prefix) for k in keys):
                 found.append((fam, f))
     if not found:
-        raise ValueError("no text connector in " + ", ".join(str(f) for f in files) + ": expected video_embeddings_connector.* "
-                         "(LTX-2 checkpoint) or video_connector.* (connectors/diffusion_pytorch_model.safetensors) tensors")
+        raise ValueError("no text connector in " + ", ".join(str(f) for f in files) + f": expected {which}_embeddings_connector.* "
+                         f"(LTX-2 checkpoint) or {which}_connector.* (connectors/diffusion_pytorch_model.safetensors) tensors")
     fam = min(fam for fam, _ in found)
-    agg_key, prefix = _CONNECTOR_FAMILIES[fam]
+    agg_key, prefix = families[fam]
     out: Dict[str, torch.Tensor] = {}
     agg = None
     for k, v in iter_safetensors(files, want=lambda k: k == agg_key or k.startswith(prefix)):
