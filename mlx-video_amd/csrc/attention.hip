@@ -21,7 +21,7 @@
 //                             8 contiguous keys = one 16-byte V^T chunk)
 // V is consumed transposed (V^T: [d][key], key-contiguous); the V projection GEMM writes it
 // in that layout directly (ltxk_gemm_bf16 out_tokens_per_batch).
-#include "common.h"
+#include "attn_tile.h"            // at_keymap, the key map of the 16x16x32 form below
 
 namespace ltxk {
 
@@ -444,7 +444,6 @@ __global__ __launch_bounds__(NW * 64, 2) void flash_attn_kernel(FaParams p) {
 // lane reads it for - instead of row & 15: the 16 lanes of a ds_read_b128 group are {c in 0-3,12-15 of one g} + {c in 4-11
 // of g ^ 1}, both sets closed under c ^ 1, so chunk ^ c is a bijection onto the 16 chunk positions.
 // =====================================================================================================================
-__device__ __forceinline__ constexpr int fa16_keymap(int kb, int r) { return 32 * (kb >> 1) + 8 * (r >> 2) + 4 * (kb & 1) + (r & 3); }
 __device__ __forceinline__ int fa16_kswz(int row) { return 4 * ((row >> 3) & 3) + (row & 3); }
 
 // RMSNorm * weight (+ SPLIT RoPE) of the wave's Q fragments in the 16x16x32 operand map: fragment (qb, ks) of lane (c,g)
@@ -607,7 +606,7 @@ __device__ __forceinline__ void fa_body16(const FaParams& p, char* smem, int bh,
       bf16x8 kfr[KBUF][4];
       auto load_k1 = [&](bf16x8& dst, int gi, int ks) __attribute__((always_inline)) {
         const int kb = (KS == 1 ? gi : 2 * kh + gi);
-        const int row = fa16_keymap(kb, c);
+        const int row = at_keymap(kb, c);
         dst = *(const bf16x8*)(sk + row * 256 + (((4 * ks + g) ^ c) << 4));      // swizzle = fa16_kswz(row) = c
       };
       auto load_k = [&](bf16x8* dst, int gi) __attribute__((always_inline)) {
@@ -655,7 +654,7 @@ __device__ __forceinline__ void fa_body16(const FaParams& p, char* smem, int bh,
         const int kb = KS == 1 ? i : 2 * kh + i;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-          const int key = t * FA_BK + 32 * (kb >> 1) + 8 * g + 4 * (kb & 1) + j;      // fa16_keymap(kb, 4g + j)
+          const int key = t * FA_BK + 32 * (kb >> 1) + 8 * g + 4 * (kb & 1) + j;      // at_keymap(kb, 4g + j)
           if (key >= p.Tk) {
 #pragma unroll
             for (int qb = 0; qb < QB; ++qb) s[i][qb][j] = -1e30f;

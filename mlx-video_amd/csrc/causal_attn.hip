@@ -1,7 +1,7 @@
 // Causal, left-padding-aware, grouped-query attention at head dim 256 (include/ltxk.h, "Gemma-3 text encoder"): the one
 // attention shape of a Gemma-3 forward, which ltxk_flash_attn (dh = 128, no mask, one K/V head per query head) does not take.
-// It runs once per prompt (T <= 1024, 48 layers), so the structure is the plainest that is correct on
-// v_mfma_f32_16x16x32_bf16; none of fa_body16's pipelining is ported.
+// It runs once per prompt (T <= 1024, 48 layers), so the structure is the plainest walk of attn_tile.h's tile; none of
+// fa_body16's pipelining is ported.
 //
 // One workgroup of 4 waves per (batch, query head, 64-row query tile); wave w owns query rows 16w .. 16w+15 and walks the
 // 64-key tiles [t0, t1] that hold a visible key for some row of the tile - tiles wholly below row_start / the window or above
@@ -10,34 +10,18 @@
 // share a CU's 160 KiB, so one's loads run under the other's MFMAs.  Keys are never split across workgroups or waves: a
 // row's sums depend on (row_start, window, T) and its own head's data only.
 //
-// Operand map (the one of fa_body16; g = lane >> 4, c = lane & 15):
-//   S^T block kb (16 keys) = K(kb) . Q^T over 8 k-steps of 32 channels:
-//     A = K fragment : lane (c,g) holds key row keymap(kb, c), channels 32ks + 8g .. +7        (one ds_read_b128)
-//     B = Q fragment : lane (c,g) holds query row c, the same channels                          (registers, whole kernel)
-//     D : lane (c,g) register j = S^T[key keymap(kb, 4g + j)][query c]
-//   keymap(kb, r) = 32 (kb >> 1) + 8 (r >> 2) + 4 (kb & 1) + (r & 3): the 8 scores a lane holds of blocks 2kc, 2kc+1 are the
-//   8 CONTIGUOUS keys 32kc + 8g .. +7 - exactly the k-slots of its B operand in
-//   O^T block db (16 channels) += V^T(db, kc) . P^T(kc), A = V^T fragment: lane (c,g) holds channel 16db + c, keys 32kc + 8g .. +7,
-//   so P goes from the softmax to the matrix pipe in registers.
-//   D : lane (c,g) register j = O^T[channel 16db + 4g + j][query c] - four consecutive channels of one output row per lane.
-// LDS images: K rows of 512 B with 16-byte chunk ch at position ch ^ kswz(row), kswz(row) = 4 ((row >> 3) & 3) + (row & 3) = c
-// for row = keymap(kb, c); V^T rows of 128 B with chunk ch at ch ^ ((d >> 1) & 7).
-//
-// Softmax: the "flash" rounding points of ltxk_flash_attn.  The row offset M is an INTEGER in the exp2 domain, the ceil of the
-// running maximum over the VISIBLE keys seen so far (raised whenever a tile exceeds it: no deferral), so bf16(P) does not
-// depend on the tiling.  A masked key takes no part in the maximum and its P is the constant 0, not exp2 of a large negative
-// number: a row that has met no visible key yet (its window starts in a later tile) keeps M = -1e30, l = 0, O = 0.
-#include "common.h"
+// Mask: key j is visible to query i iff row_start <= j <= i and (no window or i - j < window); a row whose window starts in
+// a later tile has met no visible key yet.  The Q fragments stay in registers for the whole kernel; every K and V^T
+// fragment is one ds_read_b128.
+#include "attn_tile.h"
 
 namespace ltxk {
 
 constexpr int CA_DH = 256;                       // head dim
 constexpr int CA_BQ = 64;                        // query rows per workgroup (16 per wave)
-constexpr int CA_BK = 64;                        // keys per tile
-constexpr int CA_K_BYTES = CA_BK * CA_DH * 2;    // 32 KiB
-constexpr int CA_V_BYTES = CA_DH * CA_BK * 2;    // 32 KiB
+constexpr int CA_K_BYTES = AT_BK * CA_DH * 2;    // 32 KiB
+constexpr int CA_V_BYTES = CA_DH * AT_BK * 2;    // 32 KiB
 constexpr int CA_LDS = CA_K_BYTES + CA_V_BYTES;
-constexpr float CA_NONE = -1e30f;                // "no visible key yet"
 
 struct CaParams {
   const bf16* q; const bf16* k; const bf16* vt; bf16* out;
@@ -46,9 +30,6 @@ struct CaParams {
   int B, Hq, Hkv, T, window, QT;
   float c;                                       // scale * log2(e)
 };
-
-__device__ __forceinline__ constexpr int ca_keymap(int kb, int r) { return 32 * (kb >> 1) + 8 * (r >> 2) + 4 * (kb & 1) + (r & 3); }
-__device__ __forceinline__ int ca_kswz(int row) { return 4 * ((row >> 3) & 3) + (row & 3); }
 
 // Two waves per SIMD = two workgroups per CU: without the hint the compiler takes 224 VGPRs + 80 AGPRs and one workgroup owns the
 // CU; with it 223 VGPRs, no AGPRs, nothing spilled.
@@ -84,7 +65,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   const int qlo = max(q0, rs);
   int klo = rs;
   if (p.window > 0) klo = max(klo, qlo - p.window + 1);
-  const int t0 = klo / CA_BK, t1 = q1 / CA_BK;
+  const int t0 = klo / AT_BK, t1 = q1 / AT_BK;
 
   const int qi = q0 + 16 * wave + c;             // this lane's query row
   bf16x8 qf[8];
@@ -100,26 +81,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   char* sv = smem + CA_K_BYTES;
 
   f32x4 o[16];
-#pragma unroll
-  for (int db = 0; db < 16; ++db)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) o[db][j] = 0.f;
-  float mc_run = CA_NONE, l_run = 0.f;
+  at_zero(o);
+  float mc_run = AT_NONE, l_run = 0.f;
 
   for (int t = t0; t <= t1; ++t) {
     // ---- stage the tile: 2048 16-byte chunks of K and of V^T, 8 + 8 per thread ----
     bf16x8 kr[8], vr[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const int id = i * 256 + tid, row = id >> 5, ch = id & 31;
-      int key = t * CA_BK + row;
-      key = key < T ? key : T - 1;               // rows past the sequence: a copy of the last row, masked below
-      kr[i] = *(const bf16x8*)(kbase + (size_t)key * p.ldk + ch * 8);
-    }
+    at_fetch_k<CA_DH>(kr, kbase, p.ldk, t * AT_BK, T, tid);
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
       const int id = i * 256 + tid, d = id >> 3, ch = id & 7;
-      const int col = t * CA_BK + ch * 8;
+      const int col = t * AT_BK + ch * 8;
       if (col < p.ldvt) vr[i] = *(const bf16x8*)(vbase + (size_t)d * p.ldvt + col);      // ldvt % 8 == 0: the chunk is inside the row
       else {
 #pragma unroll
@@ -127,78 +99,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       }
     }
     __syncthreads();                             // the previous tile's readers are done
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const int id = i * 256 + tid, row = id >> 5, ch = id & 31;
-      *(bf16x8*)(sk + row * 512 + ((ch ^ ca_kswz(row)) << 4)) = kr[i];
-    }
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const int id = i * 256 + tid, d = id >> 3, ch = id & 7;
-      *(bf16x8*)(sv + d * 128 + ((ch ^ ((d >> 1) & 7)) << 4)) = vr[i];
-    }
+    at_stage<CA_DH>(sk, sv, kr, vr, tid);
     __syncthreads();
 
-    // ---- S^T = K . Q^T ----
     f32x4 s[4];
-#pragma unroll
-    for (int kb = 0; kb < 4; ++kb) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) s[kb][j] = 0.f;
-      const int row = ca_keymap(kb, c);
-#pragma unroll
-      for (int ks = 0; ks < 8; ++ks) {
-        const bf16x8 kf = *(const bf16x8*)(sk + row * 512 + (((4 * ks + g) ^ c) << 4));
-        s[kb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[ks], s[kb], 0, 0, 0);
-      }
-    }
-    // ---- mask: key j is visible to query i iff row_start <= j <= i and (no window or i - j < window) ----
-    unsigned vis = 0;
-    float mx = CA_NONE;
-#pragma unroll
-    for (int kb = 0; kb < 4; ++kb)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int key = t * CA_BK + 32 * (kb >> 1) + 8 * g + 4 * (kb & 1) + j;          // ca_keymap(kb, 4g + j)
-        const bool v = key >= rs && key <= qi && qi < T && (p.window == 0 || qi - key < p.window);
-        if (v) { vis |= 1u << (kb * 4 + j); mx = fmaxf(mx, s[kb][j]); }
-      }
-    // ---- online softmax: the key axis is registers x the four lane groups g ----
-    float mxc = mx > -1e29f ? mx * p.c : CA_NONE;
-    mxc = lane_xor32_max(lane_xor16_max(mxc));
-    const float m_new = mxc > -1e29f ? fmaxf(mc_run, __builtin_ceilf(mxc)) : mc_run;
-    if (__any(m_new != mc_run)) {
-      const float alpha = __builtin_amdgcn_exp2f(mc_run - m_new);       // a power of two, 0 from CA_NONE, 1 where nothing moved
-      l_run *= alpha;
-#pragma unroll
-      for (int db = 0; db < 16; ++db)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) o[db][j] *= alpha;
-      mc_run = m_new;
-    }
+    at_scores<CA_DH>(s, qf, [&](int kb, int ks) { return at_kfrag_lds<CA_DH>(sk, kb, ks, c, g); });
+    float m_tile;
+    const unsigned vis = at_mask(s, t * AT_BK, g, p.c, m_tile, [&](int key) {
+      return key >= rs && key <= qi && qi < T && (p.window == 0 || qi - key < p.window);
+    });
     bf16x8 pb[2];
-    float psum = 0.f;
-#pragma unroll
-    for (int kb = 0; kb < 4; ++kb)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const float e = (vis >> (kb * 4 + j)) & 1u ? __builtin_amdgcn_exp2f(__builtin_fmaf(s[kb][j], p.c, -mc_run)) : 0.f;
-        psum += e;
-        pb[kb >> 1][(kb & 1) * 4 + j] = (bf16)e;
-      }
-    l_run += psum;
-    // ---- O^T += V^T . P^T ----
-#pragma unroll
-    for (int db = 0; db < 16; ++db) {
-      const int d = db * 16 + c;
-      const char* vrow = sv + d * 128;
-      const int sw = (d >> 1) & 7;
-#pragma unroll
-      for (int kc = 0; kc < 2; ++kc) {
-        const bf16x8 vf = *(const bf16x8*)(vrow + (((4 * kc + g) ^ sw) << 4));
-        o[db] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pb[kc], o[db], 0, 0, 0);
-      }
-    }
+    at_online(s, vis, m_tile, p.c, mc_run, l_run, o, pb);
+    at_pv<CA_DH>(o, pb, [&](int db, int kc) { return at_vfrag_lds(sv, db, kc, c, g); });
   }
 
   // ---- O = O^T / l; a row without a visible key (a padded query row) is all zeros ----

@@ -4,14 +4,8 @@
 //
 // Launch 1, one workgroup of 4 waves per (batch row, KV head, 256-key slice s = keys [256 s, 256 s + 256)); wave w owns the
 // 64-key tile 256 s + 64 w.  The Hq/Hkv <= 16 query heads of the KV head are the columns of the 16-wide B operand, so the
-// head's cache is read once for its whole group.  Operand maps are causal_attn.hip's (g = lane >> 4, c = lane & 15):
-//   S^T block kb (16 keys) = K(kb) . Q^T over 8 k-steps of 32 channels:
-//     A: lane (c,g) holds key row keymap(kb, c), channels 32ks + 8g .. +7        (one 16-byte global load)
-//     B: lane (c,g) holds query head c of the group, the same channels
-//     D: lane (c,g) register j = S^T[key keymap(kb, 4g + j)][head c]
-//   O^T block db (16 channels) += V^T(db, kc) . P^T(kc):
-//     A: lane (c,g) holds channel 16db + c, keys 32kc + 8g .. +7                  (one 16-byte global load)
-//     D: lane (c,g) register j = O^T[channel 16db + 4g + j][head c]
+// head's cache is read once for its whole group: in attn_tile.h's operand map "query row c" is query head c of the group,
+// and every K and V^T fragment is one 16-byte global load.
 // Key `step` is the new token: its K row is read from k_new and its V^T column from v_new, never from the cache, and the wave
 // whose tile holds `step` stores both into the cache (the append).  Nobody else in the launch touches that row / column.
 // A tile wholly outside [max(row_start, step - window + 1), step] is not fetched: its partial is (M = none, l = 0, O = 0).
@@ -19,18 +13,14 @@
 // (M, l, O[256]) fp32.  Launch 2 merges the slices in ascending order and divides.  M is an integer in the exp2 domain (the
 // ceil of the maximum over the visible keys), so every rescale 2^(M_part - M) is exact; which keys form a partial is a
 // function of `step` (and the host's window) only, never of B, the cache capacity or what else the launch holds.  No atomics.
-#include "common.h"
+#include "attn_tile.h"
 
 namespace ltxk {
 
 constexpr int CS_DH = 256;                       // head dim
-constexpr int CS_BK = 64;                        // keys per wave
-constexpr int CS_SLICE = 256;                    // keys per workgroup
+constexpr int CS_SLICE = 4 * AT_BK;              // keys per workgroup, one tile per wave
 constexpr int CS_PART = 2 + CS_DH;               // floats of one partial: M, l, O[256]
 constexpr int CS_LDS = 4 * (2 * 16 + 16 * CS_DH) * 4;      // per wave: M[16], l[16], O[16][256]
-constexpr float CS_NONE = -1e30f;                // "no visible key"
-
-__device__ __forceinline__ constexpr int cs_keymap(int kb, int r) { return 32 * (kb >> 1) + 8 * (r >> 2) + 4 * (kb & 1) + (r & 3); }
 
 // The first slice a launch covers: slices wholly below the window hold no visible key for any row_start.
 __host__ __device__ __forceinline__ int cs_first_slice(int step, int window) {
@@ -54,13 +44,13 @@ __global__ __launch_bounds__(256) void causal_attn_step_kernel(
   const int si = (int)(blockIdx.x % (unsigned)nslices);
   const int bk = (int)(blockIdx.x / (unsigned)nslices);
   const int b = bk / Hkv, hk = bk - b * Hkv;
-  const int kt = (s0 + si) * CS_SLICE + wave * CS_BK;          // this wave's first key
+  const int kt = (s0 + si) * CS_SLICE + wave * AT_BK;          // this wave's first key
   int rs = row_start[b];
   rs = rs < 0 ? 0 : rs;
   int klo = rs;
   if (window > 0) klo = max(klo, step - window + 1);
-  const bool has_step = step >= kt && step < kt + CS_BK;       // wave-uniform
-  const bool live = kt <= step && kt + CS_BK - 1 >= klo;       // wave-uniform: the tile holds a visible key
+  const bool has_step = step >= kt && step < kt + AT_BK;       // wave-uniform
+  const bool live = kt <= step && kt + AT_BK - 1 >= klo;       // wave-uniform: the tile holds a visible key
 
   bf16* kbase = k_cache + (size_t)b * cap * ldk + (size_t)hk * CS_DH;
   bf16* vbase = vt_cache + ((size_t)b * Hkv + hk) * CS_DH * ldvt;
@@ -76,19 +66,16 @@ __global__ __launch_bounds__(256) void causal_attn_step_kernel(
     }
   }
 
-  float m_tile = CS_NONE, l_tile = 0.f;
+  float m_tile = AT_NONE, l_tile = 0.f;
   f32x4 o[16];
-#pragma unroll
-  for (int db = 0; db < 16; ++db)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) o[db][j] = 0.f;
+  at_zero(o);
 
   if (live) {
     // ---- operands: K and V^T fragments straight from the cache, the group's query heads as B columns ----
     bf16x8 kf[4][8], vf[16][2], qf[8];
 #pragma unroll
     for (int kb = 0; kb < 4; ++kb) {
-      const int key = kt + cs_keymap(kb, c);                   // < cap: kt <= step < cap, both multiples of 64 apart
+      const int key = kt + at_keymap(kb, c);                   // < cap: kt <= step < cap, both multiples of 64 apart
       const bf16* kp = (key == step ? knew : kbase + (size_t)key * ldk) + g * 8;
 #pragma unroll
       for (int ks = 0; ks < 8; ++ks) kf[kb][ks] = *(const bf16x8*)(kp + ks * 32);
@@ -119,44 +106,16 @@ __global__ __launch_bounds__(256) void causal_attn_step_kernel(
         }
       }
     }
-    // ---- S^T = K . Q^T ----
+    // ---- the tile, with no running state; key j is visible iff row_start <= j <= step and (no window or step - j < window):
+    // every head of the group sees the same keys.  (& not &&: seen in the assembly only - with & hipcc keeps the instruction
+    // order the hand-written loop had, all 32 S^T MFMAs and then the score reads; with && it reads the first score blocks back
+    // between them) ----
     f32x4 s[4];
-#pragma unroll
-    for (int kb = 0; kb < 4; ++kb) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) s[kb][j] = 0.f;
-#pragma unroll
-      for (int ks = 0; ks < 8; ++ks) s[kb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[kb][ks], qf[ks], s[kb], 0, 0, 0);
-    }
-    // ---- mask: key j is visible iff row_start <= j <= step and (no window or step - j < window) ----
-    unsigned vis = 0;
-    float mx = CS_NONE;
-#pragma unroll
-    for (int kb = 0; kb < 4; ++kb)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int key = kt + 32 * (kb >> 1) + 8 * g + 4 * (kb & 1) + j;                 // cs_keymap(kb, 4g + j)
-        if (key >= klo && key <= step) { vis |= 1u << (kb * 4 + j); mx = fmaxf(mx, s[kb][j]); }
-      }
-    float mxc = mx > -1e29f ? mx * cl2e : CS_NONE;
-    mxc = lane_xor32_max(lane_xor16_max(mxc));
-    m_tile = mxc > -1e29f ? __builtin_ceilf(mxc) : CS_NONE;   // live tile: every head of the group sees the same keys
+    at_scores<CS_DH>(s, qf, [&](int kb, int ks) { return kf[kb][ks]; });
+    const unsigned vis = at_mask(s, kt, g, cl2e, m_tile, [&](int key) { return (key >= klo) & (key <= step); });
     bf16x8 pb[2];
-    float psum = 0.f;
-#pragma unroll
-    for (int kb = 0; kb < 4; ++kb)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const float e = (vis >> (kb * 4 + j)) & 1u ? __builtin_amdgcn_exp2f(__builtin_fmaf(s[kb][j], cl2e, -m_tile)) : 0.f;
-        psum += e;
-        pb[kb >> 1][(kb & 1) * 4 + j] = (bf16)e;
-      }
-    l_tile = lane_xor32_sum(lane_xor16_sum(psum));
-    // ---- O^T = V^T . P^T ----
-#pragma unroll
-    for (int db = 0; db < 16; ++db)
-#pragma unroll
-      for (int kc = 0; kc < 2; ++kc) o[db] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf[db][kc], pb[kc], o[db], 0, 0, 0);
+    l_tile = lane_xor32_sum(lane_xor16_sum(at_probs(s, vis, cl2e, m_tile, pb)));
+    at_pv<CS_DH>(o, pb, [&](int db, int kc) { return vf[db][kc]; });
   }
 
   // ---- the wave's partial to LDS ----
@@ -170,7 +129,7 @@ __global__ __launch_bounds__(256) void causal_attn_step_kernel(
 
   // ---- merge the four tiles in ascending order: thread = channel, one head of the group at a time ----
   for (int qh = 0; qh < G; ++qh) {
-    float m = CS_NONE;
+    float m = AT_NONE;
 #pragma unroll
     for (int w = 0; w < 4; ++w) m = fmaxf(m, sm_m[w * 16 + qh]);
     float l = 0.f, acc = 0.f;
@@ -194,7 +153,7 @@ __global__ __launch_bounds__(256) void causal_attn_step_combine_kernel(const flo
   const int tid = threadIdx.x;
   const int b = (int)(blockIdx.x / (unsigned)Hq), h = (int)(blockIdx.x % (unsigned)Hq);
   const float* part = partials + ((size_t)b * Hq + h) * nslices * CS_PART;
-  float m = CS_NONE;
+  float m = AT_NONE;
   for (int s = 0; s < nslices; ++s) m = fmaxf(m, part[(size_t)s * CS_PART]);
   float l = 0.f, acc = 0.f;
   if (m > -1e29f) {
@@ -221,7 +180,7 @@ extern "C" int ltxk_causal_attn_step(const void* q, int32_t ldq, const void* k_n
   LTXK_CHECK_ARG(q && k_new && v_new && k_cache && vt_cache && out && row_start && partials, "%s: null pointer", who);
   LTXK_CHECK_ARG(B > 0 && Hq > 0 && Hkv > 0 && cap > 0, "%s: bad dims B=%d Hq=%d Hkv=%d cap=%d", who, B, Hq, Hkv, cap);
   LTXK_CHECK_ARG(Hq % Hkv == 0 && Hq / Hkv <= 16, "%s: Hq=%d must be a multiple of Hkv=%d, at most 16 times it", who, Hq, Hkv);
-  LTXK_CHECK_ARG(cap % CS_BK == 0, "%s: cap=%d must be a multiple of %d", who, cap, CS_BK);
+  LTXK_CHECK_ARG(cap % AT_BK == 0, "%s: cap=%d must be a multiple of %d", who, cap, AT_BK);
   LTXK_CHECK_ARG(step >= 0 && step < cap, "%s: step=%d must lie in [0, cap=%d)", who, step, cap);
   LTXK_CHECK_ARG(scale > 0.f, "%s: scale must be positive", who);
   LTXK_CHECK_ARG(window >= 0, "%s: window=%d must be 0 (none) or a positive count", who, window);
