@@ -280,6 +280,18 @@ int ltxk_rmsnorm_modulate_ss(const void* x, void* y, int32_t M, int32_t D, float
                              int32_t sumsq_ld, int32_t sumsq_n, const void* scale, const void* shift,
                              int32_t mod_stride, const int32_t* mod_row, int32_t flags, void* stream);
 
+/* One normalisation pass, two modulations (the cross-modal section of the AudioVideo block, transformer.py:282-283,
+ * 315-316, 329-330): y0 = modulate(rms(x), scale0, shift0), y1 = modulate(rms(x), scale1, shift1), x read once.  Both
+ * pairs are required and share mod_stride / mod_row; y0 != y1, neither aliases x.  sumsq != NULL: the carried statistic,
+ * as ltxk_rmsnorm_modulate_ss reads it (sumsq_ld, sumsq_n); NULL: the kernel reduces the row itself, as
+ * ltxk_rmsnorm_modulate does.  flags & LTXK_NORM_SCALE_IS_ONE_PLUS (needs sumsq) holds for both scales.  D a multiple of
+ * 512, <= 8192; every pointer but sumsq / mod_row 16-byte aligned.  Each output carries the bits of the single-output
+ * entry called with the same operands.                                                                                  */
+int ltxk_rmsnorm_modulate2(const void* x, void* y0, void* y1, int32_t M, int32_t D, float eps, const float* sumsq,
+                           int32_t sumsq_ld, int32_t sumsq_n, const void* scale0, const void* shift0,
+                           const void* scale1, const void* shift1, int32_t mod_stride, const int32_t* mod_row,
+                           int32_t flags, void* stream);
+
 /* LayerNorm(affine=False) + modulation of the output head: ltx.py:432-457.               */
 int ltxk_layernorm_modulate(const void* x, void* y, int32_t M, int32_t D, float eps,
                             const void* scale, const void* shift, int32_t mod_stride,

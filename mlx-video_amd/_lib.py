@@ -163,6 +163,8 @@ SIGNATURES = {
     "ltxk_ada_combine": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_uint32, c_void_p]),
     "ltxk_rmsnorm_modulate_ss": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_float, c_void_p, c_int32, c_int32, c_void_p,
                                            c_void_p, c_int32, c_void_p, c_int32, c_void_p]),
+    "ltxk_rmsnorm_modulate2": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_float, c_void_p, c_int32, c_int32,
+                                         c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p]),
     "ltxk_qknorm_rope_ss": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
                                       c_int32, c_int32, c_float, c_void_p, c_int32, c_void_p]),
     "ltxk_qknorm_rope_dh64": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p,

@@ -143,6 +143,103 @@ __global__ __launch_bounds__(256) void norm_scale_kernel(
   }
 }
 
+// One normalisation pass, two modulations (ltxk_rmsnorm_modulate2: the cross-modal section of the AudioVideo block reads
+// each residual stream once and modulates it for the a2v and for the v2a attention).  n = rbf(x * rstd) is formed once per
+// element and feeds both outputs; every rounding point is that of the single-output kernels above, so y0 / y1 carry the bits
+// of two launches of them.  SS: the row statistic is the carried partials and the row is cut into pieces as in
+// norm_scale_kernel (every load - x, the partial, both scale / shift pairs - requested before the reduction); otherwise one
+// wave holds the row and reduces it in norm_modulate_kernel's order (per lane: chunk by chunk, element by element).
+template <bool ONE_PLUS>
+__device__ __forceinline__ bf16x8 modulate8(const float (&n)[8], const bf16x8& sc, const bf16x8& sh) {
+  bf16x8 o;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const float one_p = ONE_PLUS ? (float)sc[j] : rbf(1.0f + (float)sc[j]);
+    o[j] = (bf16)(rbf(n[j] * one_p) + (float)sh[j]);
+  }
+  return o;
+}
+
+template <int CH, bool ONE_PLUS>
+__global__ __launch_bounds__(256) void norm_scale2_kernel(
+    const bf16* __restrict__ x, bf16* __restrict__ y0, bf16* __restrict__ y1, int M, int D, float eps,
+    const float* __restrict__ sumsq, int ss_ld, int NP, const bf16* __restrict__ scale0, const bf16* __restrict__ shift0,
+    const bf16* __restrict__ scale1, const bf16* __restrict__ shift1, int mod_stride, const int32_t* __restrict__ mod_row) {
+  const int lane = threadIdx.x & 63;
+  const int wpr = D / (512 * CH);
+  const int item = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int row = item / wpr, piece = item - row * wpr;
+  if (row >= M) return;
+  const int col0 = piece * (512 * CH) + lane * 8;
+  const size_t mrow = (size_t)(mod_row ? mod_row[row] : 0) * mod_stride + col0;
+  const size_t xo = (size_t)row * D + col0;
+  bf16x8 v[CH];
+#pragma unroll
+  for (int i = 0; i < CH; ++i) v[i] = *(const bf16x8*)(x + xo + i * 512);
+  const float ss0 = lane < NP ? sumsq[(size_t)row * ss_ld + lane] : 0.f;
+  bf16x8 sc0[CH], sh0[CH], sc1[CH], sh1[CH];
+#pragma unroll
+  for (int i = 0; i < CH; ++i) {
+    sc0[i] = *(const bf16x8*)(scale0 + mrow + i * 512);
+    sh0[i] = *(const bf16x8*)(shift0 + mrow + i * 512);
+    sc1[i] = *(const bf16x8*)(scale1 + mrow + i * 512);
+    sh1[i] = *(const bf16x8*)(shift1 + mrow + i * 512);
+  }
+  float ss = ss0;
+  for (int i = lane + 64; i < NP; i += 64) ss += sumsq[(size_t)row * ss_ld + i];
+  const float rstd = rsqrtf(wave_sum(ss) / (float)D + eps);
+#pragma unroll
+  for (int i = 0; i < CH; ++i) {
+    float n[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) n[j] = rbf((float)v[i][j] * rstd);
+    *(bf16x8*)(y0 + xo + i * 512) = modulate8<ONE_PLUS>(n, sc0[i], sh0[i]);
+    *(bf16x8*)(y1 + xo + i * 512) = modulate8<ONE_PLUS>(n, sc1[i], sh1[i]);
+  }
+}
+
+__global__ __launch_bounds__(256) void norm_modulate2_kernel(
+    const bf16* __restrict__ x, bf16* __restrict__ y0, bf16* __restrict__ y1, int M, int D, float eps,
+    const bf16* __restrict__ scale0, const bf16* __restrict__ shift0, const bf16* __restrict__ scale1,
+    const bf16* __restrict__ shift1, int mod_stride, const int32_t* __restrict__ mod_row) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * ROWS_PER_BLOCK + (threadIdx.x >> 6);
+  if (row >= M) return;
+  const bf16* xr = x + (size_t)row * D;
+  const int nch = D >> 9;
+  bf16x8 v[MAX_CHUNKS];
+  float sq = 0.f;
+#pragma unroll
+  for (int i = 0; i < MAX_CHUNKS; ++i) {
+    if (i < nch) {
+      v[i] = *(const bf16x8*)(xr + i * 512 + lane * 8);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const float f = (float)v[i][j];
+        sq += f * f;
+      }
+    }
+  }
+  const float rstd = rsqrtf(wave_sum(sq) / (float)D + eps);
+  const size_t mrow = (size_t)(mod_row ? mod_row[row] : 0) * mod_stride;
+  const size_t yo = (size_t)row * D;
+#pragma unroll
+  for (int i = 0; i < MAX_CHUNKS; ++i) {
+    if (i < nch) {
+      const int col = i * 512 + lane * 8;
+      const bf16x8 sc0 = *(const bf16x8*)(scale0 + mrow + col);
+      const bf16x8 sh0 = *(const bf16x8*)(shift0 + mrow + col);
+      const bf16x8 sc1 = *(const bf16x8*)(scale1 + mrow + col);
+      const bf16x8 sh1 = *(const bf16x8*)(shift1 + mrow + col);
+      float n[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) n[j] = rbf((float)v[i][j] * rstd);
+      *(bf16x8*)(y0 + yo + col) = modulate8<false>(n, sc0, sh0);
+      *(bf16x8*)(y1 + yo + col) = modulate8<false>(n, sc1, sh1);
+    }
+  }
+}
+
 // ---------------------------------------------------------------------------------------
 // q/k RMSNorm (full inner dim, learned weight) + SPLIT RoPE, in place; values and rounding points: rows.h.
 // One wave per (row, segment), the segment held in registers.  Lane map: a wave pass covers 8 heads; 8 lanes per head;
@@ -570,6 +667,44 @@ extern "C" int ltxk_rmsnorm_modulate_ss(const void* x, void* y, int32_t M, int32
     case 2: norm_scale_launch<2>(op, grid, st, (const bf16*)x, (bf16*)y, M, D, eps, sumsq, sumsq_ld, sumsq_n, (const bf16*)scale, (const bf16*)shift, mod_stride, mod_row); break;
     case 4: norm_scale_launch<4>(op, grid, st, (const bf16*)x, (bf16*)y, M, D, eps, sumsq, sumsq_ld, sumsq_n, (const bf16*)scale, (const bf16*)shift, mod_stride, mod_row); break;
     default: norm_scale_launch<8>(op, grid, st, (const bf16*)x, (bf16*)y, M, D, eps, sumsq, sumsq_ld, sumsq_n, (const bf16*)scale, (const bf16*)shift, mod_stride, mod_row); break;
+  }
+  LTXK_CHECK_LAUNCH(name);
+  return LTXK_OK;
+}
+
+template <int CH>
+static void norm_scale2_launch(bool one_plus, dim3 grid, hipStream_t st, const bf16* x, bf16* y0, bf16* y1, int M, int D, float eps,
+                               const float* ss, int ss_ld, int np, const bf16* sc0, const bf16* sh0, const bf16* sc1, const bf16* sh1,
+                               int ms, const int32_t* mr) {
+  if (one_plus) hipLaunchKernelGGL((norm_scale2_kernel<CH, true>), grid, dim3(256), 0, st, x, y0, y1, M, D, eps, ss, ss_ld, np, sc0, sh0, sc1, sh1, ms, mr);
+  else hipLaunchKernelGGL((norm_scale2_kernel<CH, false>), grid, dim3(256), 0, st, x, y0, y1, M, D, eps, ss, ss_ld, np, sc0, sh0, sc1, sh1, ms, mr);
+}
+
+extern "C" int ltxk_rmsnorm_modulate2(const void* x, void* y0, void* y1, int32_t M, int32_t D, float eps, const float* sumsq,
+                                      int32_t sumsq_ld, int32_t sumsq_n, const void* scale0, const void* shift0,
+                                      const void* scale1, const void* shift1, int32_t mod_stride, const int32_t* mod_row,
+                                      int32_t flags, void* stream) {
+  const char* name = "ltxk_rmsnorm_modulate2";
+  LTXK_CHECK_ARG(x && y0 && y1 && y0 != y1 && M > 0, "%s: null/empty input, or one buffer for both outputs", name);
+  LTXK_CHECK_ARG(D % 512 == 0 && D > 0 && D <= 512 * MAX_CHUNKS, "%s: D=%d must be a multiple of 512, <= %d", name, D, 512 * MAX_CHUNKS);
+  LTXK_CHECK_ARG(scale0 && shift0 && scale1 && shift1, "%s: both (scale, shift) pairs are required", name);
+  LTXK_CHECK_ARG(mod_stride >= 0 && mod_stride % 8 == 0, "%s: mod_stride must be a multiple of 8", name);
+  LTXK_CHECK_ARG((((uintptr_t)x | (uintptr_t)y0 | (uintptr_t)y1 | (uintptr_t)scale0 | (uintptr_t)shift0 | (uintptr_t)scale1 | (uintptr_t)shift1) & 15) == 0,
+                 "%s: x, the outputs and the modulation tables must be 16-byte aligned", name);
+  LTXK_CHECK_ARG(!sumsq || (sumsq_n > 0 && sumsq_ld >= sumsq_n), "%s: bad sumsq_n/sumsq_ld", name);
+  const bool op = (flags & LTXK_NORM_SCALE_IS_ONE_PLUS) != 0;
+  LTXK_CHECK_ARG(sumsq || !op, "%s: LTXK_NORM_SCALE_IS_ONE_PLUS needs sumsq", name);
+  hipStream_t st = (hipStream_t)stream;
+  const bf16 *xb = (const bf16*)x, *sc0 = (const bf16*)scale0, *sh0 = (const bf16*)shift0, *sc1 = (const bf16*)scale1, *sh1 = (const bf16*)shift1;
+  if (sumsq) {
+    // rows cut into 1024-element pieces (two 16-byte chunks per lane) when D allows, else 512: as ltxk_rmsnorm_modulate_ss
+    const int ch = (D % 1024 == 0) ? 2 : 1;
+    const dim3 grid((unsigned)(((long long)M * (D / (512 * ch)) + 3) / 4));
+    if (ch == 2) norm_scale2_launch<2>(op, grid, st, xb, (bf16*)y0, (bf16*)y1, M, D, eps, sumsq, sumsq_ld, sumsq_n, sc0, sh0, sc1, sh1, mod_stride, mod_row);
+    else norm_scale2_launch<1>(op, grid, st, xb, (bf16*)y0, (bf16*)y1, M, D, eps, sumsq, sumsq_ld, sumsq_n, sc0, sh0, sc1, sh1, mod_stride, mod_row);
+  } else {
+    hipLaunchKernelGGL(norm_modulate2_kernel, dim3((M + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK), dim3(256), 0, st, xb, (bf16*)y0, (bf16*)y1,
+                       M, D, eps, sc0, sh0, sc1, sh1, mod_stride, mod_row);
   }
   LTXK_CHECK_LAUNCH(name);
   return LTXK_OK;

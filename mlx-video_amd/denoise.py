@@ -1,6 +1,7 @@
 """Denoise loops: ``denoise_dev`` (CFG) and ``denoise_distilled`` (mlx_video/generate.py:1060-1327,
-564-881), video branch, and ``denoise_audio_only`` (888-1053), the loop of separate audio
-generation.  The step body is: tokens <- latent transpose, DiT forward(s), then one
+564-881), video branch, ``denoise_audio_only`` (888-1053), the loop of separate audio
+generation, and ``denoise_dev_av`` (1330-1680), the dev loop of joint audio-video denoising over
+``av_model.LTXAVModel``.  The step body is: tokens <- latent transpose, DiT forward(s), then one
 fused kernel for guidance + x0 + mask blend + Euler (ops.step_tail).
 
 Sigma handling follows the reference exactly (SURVEY.md §7 "bf16-quantised timesteps"):
@@ -359,6 +360,155 @@ def audio_volume_to_latent(volume: torch.Tensor, channels: int = 8) -> torch.Ten
     """The inverse of ``audio_latent_to_volume``: (B,128,T,1,1) -> (B,8,T,16)."""
     b, cf, t = volume.shape[:3]
     return volume.reshape(b, channels, cf // channels, t).permute(0, 1, 3, 2).contiguous()
+
+
+class _AVStep:
+    """One joint step over persistent or per-call operands: the AudioVideo forward(s) - one B = 2 forward under ``batched``, else
+    the positive and (CFG) the negative one - and the two fused tails, video then audio."""
+
+    def __init__(self, tr, gd: _Guidance):
+        self.tr, self.gd = tr, gd
+
+    def velocities(self, lat_v, vol_a, tp_v, tp_a, ctx_v, ctx_a, tables):
+        """((video v_pos, v_neg | None), (audio v_pos, v_neg | None)).  ``ctx_v`` / ``ctx_a``: [batched rows] or [pos, neg]."""
+        gd, b = self.gd, self.gd.b
+        pe_v, cpe_v, pe_a, cpe_a = tables
+        tok_v, tok_a = ops.latent_to_tokens(lat_v, rep=gd.reps), ops.latent_to_tokens(vol_a, rep=gd.reps)
+        if gd.batched:
+            vv, va = self.tr.forward_tokens(tok_v, tp_v, ctx_v[0], pe_v, cpe_v, tok_a, tp_a, ctx_a[0], pe_a, cpe_a)
+            return (vv[:b], vv[b:2 * b]), (va[:b], va[b:2 * b])
+        vp, ap = self.tr.forward_tokens(tok_v, tp_v, ctx_v[0], pe_v, cpe_v, tok_a, tp_a, ctx_a[0], pe_a, cpe_a)
+        vn = an = None
+        if gd.use_cfg:
+            vn, an = self.tr.forward_tokens(tok_v, tp_v, ctx_v[1], pe_v, cpe_v, tok_a, tp_a, ctx_a[1], pe_a, cpe_a)
+        return (vp, vn), (ap, an)
+
+
+class _AVStepGraph:
+    """The joint step as a hipGraph on one stream, ``_StepGraph``'s scheme: both modalities' persistent inputs (``_StepInputs``
+    each, with its own ltxk_step_scalars node and device-side step counter), the contexts and the cross tables, refreshed by
+    every call; step 0 of the first run is eager, then the step is captured once and replayed."""
+
+    def __init__(self, lat_v, vol_a, plan_v: _StepPlan, plan_a: _StepPlan, transformer, ctx_v, ctx_a, gd: _Guidance):
+        self.tr = transformer                       # strong reference: id(transformer) in the cache key stays unique
+        self.step = _AVStep(transformer, gd)
+        self.inp_v, self.inp_a = _StepInputs(lat_v, plan_v), _StepInputs(vol_a, plan_a)
+        self.ctx_v = [torch.empty_like(c) for c in ctx_v]
+        self.ctx_a = [torch.empty_like(c) for c in ctx_a]
+        self.cross: Optional[list] = None
+        self.graph = None
+
+    def _load(self, lat_v, vol_a, plan_v, plan_a, ctx_v, ctx_a, tables) -> None:
+        pe_v, cpe_v, pe_a, cpe_a = tables
+        self.inp_v.load(lat_v, plan_v, pe_v)
+        self.inp_a.load(vol_a, plan_a, pe_a)
+        for dst, src in zip(self.ctx_v + self.ctx_a, list(ctx_v) + list(ctx_a)):
+            dst.copy_(src)
+        if self.cross is None:
+            self.cross = [t.clone() for t in (*cpe_v, *cpe_a)]
+        else:
+            for dst, src in zip(self.cross, (*cpe_v, *cpe_a)):
+                dst.copy_(src)
+
+    def _step(self) -> None:
+        iv, ia, gd = self.inp_v, self.inp_a, self.step.gd
+        tables = (iv.pe, tuple(self.cross[:2]), ia.pe, tuple(self.cross[2:]))
+        (vp, vn), (ap, an) = self.step.velocities(iv.lat_buf, ia.lat_buf, iv.next_step(), ia.next_step(), self.ctx_v, self.ctx_a, tables)
+        gd.tail(vp, vn, None, iv.lat_buf, 1.0, 0.0, iv.clean, iv.mask_tok, out=iv.lat_buf, sigmas_dev=iv.sig_buf)
+        gd.tail(ap, an, None, ia.lat_buf, 1.0, 0.0, None, None, out=ia.lat_buf, sigmas_dev=ia.sig_buf)
+
+    def run(self, lat_v, vol_a, plan_v, plan_a, ctx_v, ctx_a, tables):
+        self._load(lat_v, vol_a, plan_v, plan_a, ctx_v, ctx_a, tables)
+        nst, start = plan_v.ts_host.shape[0], 0
+        if self.graph is None:
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                self._step()                              # real step 0, eager (device step counters 0 -> 1)
+            torch.cuda.current_stream().wait_stream(side)
+            self.graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
+                self._step()
+            start = 1
+        for _ in range(start, nst):
+            self.graph.replay()
+        return self.inp_v.lat_buf.clone(), self.inp_a.lat_buf.clone()
+
+
+def denoise_dev_av(video_latents: torch.Tensor, audio_latents: torch.Tensor, video_positions: torch.Tensor,
+                   audio_positions: torch.Tensor, video_embeddings_pos: torch.Tensor, video_embeddings_neg: torch.Tensor,
+                   audio_embeddings_pos: torch.Tensor, audio_embeddings_neg: torch.Tensor, transformer, sigmas,
+                   cfg_scale: float = 4.0, verbose: bool = False, video_state: Optional[LatentState] = None,
+                   eval_interval: int = 1, compile_step: bool = False, compile_shapeless: bool = False, cfg_batch: bool = False,
+                   ui_phase: str = "denoise", use_graph: bool = False, graph_cache: Optional[dict] = None,
+                   cache_context: bool = False, stg_scale: float = 0.0, stg_blocks: Optional[Sequence[int]] = None,
+                   guider: str = "cfg") -> Tuple[torch.Tensor, torch.Tensor]:
+    """generate.py:1330-1680: the dev loop of joint audio-video denoising over an ``av_model.LTXAVModel``.  video_latents
+    (B,128,F,H,W), audio_latents (B,8,T,16), video_positions (B,3,N,2), audio_positions (B,1,T,2) seconds, one context pair per
+    modality; returns (video latents, audio latents) in the shapes given.  Both modalities share sigma; the audio timestep mask
+    is all ones; CFG combines each modality's velocities with its own context pair (``cfg_batch``: one B = 2 forward); x0 uses
+    the bf16 sigma, Euler the Python floats, or the bf16 sigmas under ``compile_step`` - ``denoise_dev``'s rules, through the same
+    fused tail: the audio latents travel as the (B,128,T,1,1) volume.  The video conditioning mask goes through ``video_state``.
+    ``use_graph`` (with ``compile_step``): the whole joint step - forward(s) plus the two tails - captured once on one stream and
+    replayed; ``graph_cache`` keeps it across calls, every per-call input refreshed.  STG, the cfg_star / apg guiders and
+    ``cache_context`` are not part of the joint loop: ValueError."""
+    if float(stg_scale or 0.0) != 0.0 or stg_blocks is not None:
+        raise ValueError("the joint audio-video loop does not do STG (stg_scale / stg_blocks); use denoise_dev for it")
+    if guider != "cfg":
+        raise ValueError(f"the joint audio-video loop does plain CFG only, not the {guider!r} guider (cfg_star / apg: denoise_dev)")
+    if cache_context:
+        raise ValueError("the joint audio-video loop recomputes the text side every step: cache_context is not part of it")
+    sig = [float(s) for s in (sigmas.tolist() if torch.is_tensor(sigmas) else sigmas)]
+    if video_state is not None:
+        video_latents = video_state.latent
+    if audio_latents.dim() != 4 or video_latents.dim() != 5 or audio_latents.shape[0] != video_latents.shape[0]:
+        raise ValueError(f"video_latents must be (B,C,F,H,W) and audio_latents (B,C,T,F) of one batch, got {tuple(video_latents.shape)} "
+                         f"and {tuple(audio_latents.shape)}")
+    lat_v = video_latents.to(BF16).contiguous()
+    ac = audio_latents.shape[1]
+    vol_a = audio_latent_to_volume(audio_latents.to(BF16))
+    if len(sig) < 2:
+        return lat_v, audio_latents.to(BF16)
+    b = lat_v.shape[0]
+    V, A = transformer.video, transformer.audio
+    use_cfg = cfg_scale != 1.0
+    gd = _Guidance(b, cfg_scale, cfg_batch, 0.0, None, None)
+    plan_v, plan_a = _StepPlan(lat_v, video_state, gd.reps, sig), _StepPlan(vol_a, None, gd.reps, sig)
+    dev = lat_v.device
+    vpos, apos = video_positions[:1].to(dev).contiguous(), audio_positions[:1].to(dev).contiguous()
+    tables = (precompute_freqs_cis(vpos, V.inner_dim, V.positional_embedding_theta, V.positional_embedding_max_pos, V.num_attention_heads),
+              transformer.cross_freqs_cis(vpos, V.num_attention_heads),
+              precompute_freqs_cis(apos, A.inner_dim, A.positional_embedding_theta, A.positional_embedding_max_pos, A.num_attention_heads),
+              transformer.cross_freqs_cis(apos, A.num_attention_heads))
+
+    def contexts(pos, neg):
+        pos = pos.to(BF16).contiguous()
+        if not use_cfg:
+            return [pos]
+        neg = neg.to(BF16).contiguous()
+        return [torch.cat([pos, neg], 0).contiguous()] if gd.batched else [pos, neg]
+
+    ctx_v, ctx_a = contexts(video_embeddings_pos, video_embeddings_neg), contexts(audio_embeddings_pos, audio_embeddings_neg)
+    if use_graph and compile_step and len(sig) - 1 <= GRAPH_MAX_STEPS:
+        key = ("av", tuple(lat_v.shape), tuple(vol_a.shape), bool(gd.batched), bool(use_cfg), float(cfg_scale), tuple(ctx_v[0].shape),
+               tuple(ctx_a[0].shape), id(transformer), video_state is not None, plan_v.U)
+        cache = graph_cache if graph_cache is not None else {}
+        ent = cache.get(key)
+        if ent is None:
+            ent = cache[key] = _AVStepGraph(lat_v, vol_a, plan_v, plan_a, transformer, ctx_v, ctx_a, gd)
+        out_v, out_a = ent.run(lat_v, vol_a, plan_v, plan_a, ctx_v, ctx_a, tables)
+        return out_v, audio_volume_to_latent(out_a, ac)
+    step = _AVStep(transformer, gd)
+    for i in range(len(sig) - 1):
+        s_bf, sn_bf = plan_v.sig_bf[i], plan_v.sig_bf[i + 1]
+        (vp, vn), (ap, an) = step.velocities(lat_v, vol_a, plan_v.timestep_plan(i), plan_a.timestep_plan(i), ctx_v, ctx_a, tables)
+        if compile_step or (s_bf == sig[i] and sn_bf == sig[i + 1]):
+            lat_v = gd.tail(vp, vn, None, lat_v, s_bf, sn_bf, plan_v.clean, plan_v.mask_tok_f32)
+            vol_a = gd.tail(ap, an, None, vol_a, s_bf, sn_bf, None, None)
+        else:
+            lat_v = _eager_tail(gd, vp, vn, None, lat_v, s_bf, sig[i], sig[i + 1], plan_v)
+            vol_a = _eager_tail(gd, ap, an, None, vol_a, s_bf, sig[i], sig[i + 1], plan_a)
+    return lat_v, audio_volume_to_latent(vol_a, ac)
 
 
 def denoise_audio_only(audio_latents: torch.Tensor, audio_positions: torch.Tensor, audio_embeddings: torch.Tensor,

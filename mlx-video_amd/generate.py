@@ -13,7 +13,8 @@ What is injected instead of loaded (nothing exists offline and they are out of s
 weights (`weights=` dicts or ready modules; `model_repo` may point at a local directory of
 safetensors read by ``weights.py``), random draws (`noise_fn`: MLX's threefry stream is not
 reproducible, so seeds are not cross-compatible), audio (`audio=True`: separate generation by an audio-only transformer after the
-video, or finished `audio_latents=`; either way decoded to a waveform by ``audio_vae``; joint audio-video denoising is not here).  Frames are returned as the reference returns them (uint8 (F,H,W,3));
+video, `audio_mode="joint"`: audio and video denoised together by the AudioVideo transformer, or finished `audio_latents=`; either
+way decoded to a waveform by ``audio_vae``).  Frames are returned as the reference returns them (uint8 (F,H,W,3));
 `output_path` accepts `.npy`, or a video file written through an ffmpeg child process when an ffmpeg binary
 is installed (media.write_video_ffmpeg); a decoded waveform goes to a `.wav` sidecar and is muxed into that file the same way.
 """
@@ -196,7 +197,9 @@ def _connect_gemma(hs, mask, neg_hs, neg_mask, text_connector, model_repo, dev, 
                 raise ValueError(f"positive and negative gemma hidden states must both be (L,1,T,D) of one shape, got {tuple(x.shape)} and {tuple(nx.shape)}")
             x, m = torch.cat([x, nx], 1), torch.cat([m, nm], 0)
         video, aud = run(x, m)
-        return video[0:1], (video[1:2] if neg_hs is not None else None), (aud[0:1] if aud is not None else None)
+        # (a fourth item: the NEGATIVE prompt's audio context, which joint denoising's CFG takes)
+        return (video[0:1], (video[1:2] if neg_hs is not None else None), (aud[0:1] if aud is not None else None),
+                (aud[1:2] if aud is not None and neg_hs is not None else None))
     if neg_hs is None:
         return text_connector(x, m), None
     nx, nm = _layer_stack(neg_hs).to(dev), neg_mask.reshape(-1, neg_mask.shape[-1]).to(dev)
@@ -300,7 +303,8 @@ def generate_video(model_repo: Optional[str] = None, text_encoder_repo: Optional
                    enhance_system_prompt: Optional[str] = None, audio_latents: Optional[torch.Tensor] = None,
                    audio_decoder=None, vocoder=None, output_audio: Optional[str] = None, audio_mode: str = "auto",
                    audio_model_repo: Optional[str] = None, audio_steps: int = 8, audio_transformer: Optional[LTXModel] = None,
-                   audio_prompt_embeds: Optional[torch.Tensor] = None) -> np.ndarray:
+                   audio_prompt_embeds: Optional[torch.Tensor] = None, av_transformer=None,
+                   audio_negative_prompt_embeds: Optional[torch.Tensor] = None) -> np.ndarray:
     """See the module docstring.  Returns uint8 frames (F,H,W,3) (generate.py:4195-4197).
     ``hoist_context`` (not in the reference, off by default): the part of the forward that depends on the text context only -
     caption projection and the 48 cross-attention K / V^T projections, 3.37 TFLOP that the reference recomputes in every forward
@@ -348,20 +352,45 @@ def generate_video(model_repo: Optional[str] = None, text_encoder_repo: Optional
     ``_subsample_sigmas(STAGE_1_SIGMAS, audio_steps)`` (``audio_steps`` 1..8, --audio-steps) without CFG
     (``denoise.denoise_audio_only``), under an ``audio_generate`` phase; the latents then take the decode / ``.wav`` / mux path
     above.  Its context is ``audio_prompt_embeds`` (1,S,3840), or the audio embeddings connector's output where the text
-    route runs the connector here.  ``audio_mode``: "auto" and "separate" are this; "joint" (audio and video denoised together
-    through the cross-modal attentions) is not supported and raises.  With nothing to take an audio transformer from,
-    ``audio=True`` raises as before; ``audio_latents`` given, they win and nothing is generated.  The audio transformer stays bf16
-    under ``enable_fp8``."""
+    route runs the connector here.  ``audio_mode``: "auto" and "separate" are this.  With nothing to take an audio transformer
+    from, ``audio=True`` raises as before; ``audio_latents`` given, they win and nothing is generated.  The audio transformer stays
+    bf16 under ``enable_fp8``.
+    ``audio_mode="joint"`` (--audio-mode joint; dev pipeline only): audio and video are denoised TOGETHER by the AudioVideo
+    transformer, whose blocks exchange information through the a2v / v2a cross-modal attentions (``denoise.denoise_dev_av``,
+    generate.py:1330-1680) - ``av_transformer=`` (an ``av_model.LTXAVModel``; its ``.video`` is the video transformer), else built
+    from ``model_repo``'s joint checkpoint (``weights.load_av_transformer``).  The audio latents (1, 8, T, 16) come from ``seed`` as
+    above; both modalities share the video schedule and CFG, each with its own context pair: ``audio_prompt_embeds`` /
+    ``audio_negative_prompt_embeds`` (zeros when absent, like the video negative), or the audio connector's outputs for prompt and
+    negative prompt where the text route runs here.  It runs under the ``dev_denoise`` phase (no ``audio_generate``), the
+    profile reports ``audio_mode``, and the result takes the same decode / ``.wav`` / mux path.  The reference's "auto" picks joint
+    for the dev pipeline; here joint is asked for by name.  Refused with it: every other pipeline and ``stage2_dev``, ``enable_fp8``
+    / ``fp8_activations``, STG and the cfg_star / apg guiders, ``hoist_context``, and ``audio_transformer=``."""
     t_start = time.perf_counter()
     if isinstance(pipeline, str):
         pipeline = PipelineType(pipeline)
     if audio_mode not in ("auto", "separate", "joint"):
         raise ValueError(f"Unknown audio_mode: {audio_mode!r} (expected 'auto', 'separate' or 'joint')")
     gen_audio = bool(audio) and audio_latents is None
-    if gen_audio:
-        if audio_mode == "joint":
-            raise ValueError("audio_mode='joint' (joint audio-video denoising) is not supported: audio is generated separately, "
-                             "after the video (audio_mode='separate', which 'auto' resolves to)")
+    joint = gen_audio and audio_mode == "joint"         # "auto" stays separate: joint is asked for by name
+    if joint:
+        if audio_transformer is not None:
+            raise ValueError("audio_mode='joint': audio_transformer= is the separate route's audio-only model and is not supported "
+                             "with it; pass av_transformer= (an av_model.LTXAVModel) or a model_repo with the cross-modal tensors")
+        if pipeline != PipelineType.DEV or stage2_dev:
+            raise ValueError(f"audio_mode='joint' runs in the dev pipeline's denoise loop only, not in the {pipeline.value} pipeline"
+                             f"{' with stage2_dev' if stage2_dev else ''} (the joint branch of the distilled loop and the audio "
+                             "re-noising between stages are not implemented)")
+        if enable_fp8 or fp8_activations:
+            raise ValueError("audio_mode='joint' runs on bf16 weights: enable_fp8 / fp8_activations are not supported with it")
+        if float(stg_scale or 0.0) != 0.0 or (guider or "cfg") != "cfg" or hoist_context:
+            raise ValueError("audio_mode='joint': the joint loop does plain CFG - no STG (stg_scale), no cfg_star / apg guider, no "
+                             "hoist_context")
+        if av_transformer is None and audio_model_repo is None and model_repo is None:
+            raise ValueError("audio_mode='joint' is not supported without the joint transformer: pass av_transformer= (an "
+                             "av_model.LTXAVModel) or model_repo= a local checkpoint directory with the cross-modal tensors")
+        if transformer is None and av_transformer is not None:
+            transformer = av_transformer.video
+    elif gen_audio:
         if audio_transformer is None and audio_model_repo is None and model_repo is None:
             raise ValueError("audio generation is not supported without an audio transformer: pass audio_transformer= (an LTXModel of "
                              "LTXModelConfig.audio()), or audio_model_repo= / model_repo= a local checkpoint directory with the audio_* tensors")
@@ -472,6 +501,9 @@ def generate_video(model_repo: Optional[str] = None, text_encoder_repo: Optional
     if vae_decoder is None:
         raise FileNotFoundError("no VAE decoder: pass vae_decoder= or a model_repo containing VAE weights")
     dev = device or transformer.tables.device
+    if joint and av_transformer is None:
+        from .weights import load_av_transformer
+        av_transformer = load_av_transformer(audio_model_repo or model_repo, dev, video=transformer)
     if noise_fn is None:
         noise_fn = _default_noise_fn(seed, dev)
 
@@ -482,6 +514,8 @@ def generate_video(model_repo: Optional[str] = None, text_encoder_repo: Optional
         prompt_embeds, negative_prompt_embeds = got[0], got[1]
         if want:
             audio_prompt_embeds = got[2]
+            if joint and audio_negative_prompt_embeds is None and len(got) > 3:
+                audio_negative_prompt_embeds = got[3]
     if gemma_repo is None and text_encoder_repo and Path(text_encoder_repo).is_dir():
         gemma_repo = text_encoder_repo          # the reference's name for it; a repo NAME is not resolved (nothing is fetched)
     timer = _PhaseTimer(profile or bool(profile_json_path))
@@ -496,6 +530,8 @@ def generate_video(model_repo: Optional[str] = None, text_encoder_repo: Optional
         prompt_embeds, negative_prompt_embeds = got[0], got[1]
         if want:
             audio_prompt_embeds = got[2]
+            if joint and audio_negative_prompt_embeds is None and len(got) > 3:
+                audio_negative_prompt_embeds = got[3]
     if prompt_embeds is None:
         if text_encoder is None:
             raise ValueError("prompt_embeds is required: pass prompt_embeds=(1,1024,3840) or text_encoder=callable, the hidden states "
@@ -585,10 +621,27 @@ def generate_video(model_repo: Optional[str] = None, text_encoder_repo: Optional
                 conds = _encode_conditionings(images_list, vae_encoder, height, width, num_frames, latent_frames, guide, dev)
         state = init_state(shape, conds, float(sigmas[0])) if conds else None
         latents = state.latent if state is not None else noise_fn(shape)
-        with timer.phase("dev_denoise"):
-            latents = denoise_dev(latents, pos, ctx_pos, ctx_neg, transformer, sigmas, cfg_scale=cfg_scale, state=state,
-                                  compile_step=compile_step, cfg_batch=cfg_batch, use_graph=compile_step, cache_context=hoist_context,
-                                  **stg)
+        if joint:                                                    # audio and video together: generate.py:1330-1680
+            from .denoise import denoise_dev_av
+            from .schedulers import AUDIO_LATENT_CHANNELS, AUDIO_MEL_BINS, compute_audio_frames, create_audio_position_grid
+            if av_transformer.video is not transformer:
+                raise ValueError("audio_mode='joint': transformer= must be av_transformer.video (or left out)")
+            audio_frames = compute_audio_frames(num_frames, fps)
+            # seeded from `seed` alone, as the separate route draws them
+            a_noise = _default_noise_fn(seed, dev)((1, AUDIO_LATENT_CHANNELS, audio_frames, AUDIO_MEL_BINS))
+            a_pos = audio_prompt_embeds.to(dev).to(BF16)
+            a_neg = (audio_negative_prompt_embeds if audio_negative_prompt_embeds is not None else torch.zeros_like(a_pos)).to(dev).to(BF16)
+            with timer.phase("dev_denoise"):
+                latents, audio_latents = denoise_dev_av(latents, a_noise, pos, create_audio_position_grid(1, audio_frames).to(dev),
+                                                        ctx_pos, ctx_neg, a_pos, a_neg, av_transformer, sigmas, cfg_scale=cfg_scale,
+                                                        video_state=state, compile_step=compile_step, cfg_batch=cfg_batch,
+                                                        use_graph=compile_step)
+            gen_audio = False                                        # the latents exist: the separate pass below has nothing to do
+        else:
+            with timer.phase("dev_denoise"):
+                latents = denoise_dev(latents, pos, ctx_pos, ctx_neg, transformer, sigmas, cfg_scale=cfg_scale, state=state,
+                                      compile_step=compile_step, cfg_batch=cfg_batch, use_graph=compile_step,
+                                      cache_context=hoist_context, **stg)
 
     if return_latents:
         return latents
@@ -670,7 +723,8 @@ def generate_video(model_repo: Optional[str] = None, text_encoder_repo: Optional
                    "stage1_steps": int(stage1_steps) if is_distilled else None,
                    "stage2_steps": int(stage2_steps) if is_distilled else None, "eval_interval": int(eval_interval),
                    "compile_step": bool(compile_step), "compile_shapeless": bool(compile_shapeless),
-                   "fp32_euler": bool(fp32_euler), "audio": waveform is not None, "phases_s": {k: float(v) for k, v in timer.times_s.items()},
+                   "fp32_euler": bool(fp32_euler), "audio": waveform is not None,
+                   **({"audio_mode": "joint" if joint else "separate"} if audio else {}), "phases_s": {k: float(v) for k, v in timer.times_s.items()},
                    "peak_memory_gb": float(torch.cuda.max_memory_allocated() / (1024 ** 3))}
         outp.parent.mkdir(parents=True, exist_ok=True)
         outp.write_text(json.dumps(payload, indent=2, sort_keys=True), encoding="utf-8")
@@ -761,7 +815,8 @@ def build_parser() -> argparse.ArgumentParser:
                     help="Generate audio separately after the video (an audio-only transformer pass over the checkpoint's audio_* "
                          "weights), decode it to a 24 kHz stereo waveform and mux it")
     ap.add_argument("--audio-mode", choices=["auto", "separate", "joint"], default="auto",
-                    help="auto = separate; joint audio-video denoising is not supported")
+                    help="auto = separate (audio-only transformer pass after the video); joint = audio and video denoised together "
+                         "through the cross-modal attentions (dev pipeline, a checkpoint with the cross-modal tensors)")
     ap.add_argument("--audio-model-repo", type=str, default=None, metavar="DIR",
                     help="Local checkpoint directory the audio transformer is read from (default: --model-repo)")
     ap.add_argument("--audio-steps", type=int, default=8, help="Denoise steps of the separate audio pass (1..8)")

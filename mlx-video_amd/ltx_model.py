@@ -4,7 +4,8 @@
 Same names, argument meaning and error behaviour as the reference; every numeric op is a
 libltxk HIP kernel (``ops``).  One modality per model: the video transformer (head dim 128, three position axes), or - the
 same class at ``LTXModelConfig.audio()`` - the audio-only transformer of separate audio generation (head dim 64, one position
-axis).  The cross-modal (a2v / v2a) attentions of joint denoising are out of scope.
+axis).  The cross-modal (a2v / v2a) attentions of joint denoising live in av_model.LTXAVModel, which runs two of
+these models block by block through the stage methods ``_fwd_*``.
 
 Data layout in HBM (per GPU, bf16 unless noted):
   * weights: one contiguous (out,in) matrix per Linear, with to_q|to_k of the self-attention
@@ -180,6 +181,14 @@ def _vt_buffer(*lead: int, tokens: int, device) -> torch.Tensor:
     """A V^T buffer (*lead, tokens padded to 64): zero-filled where there is padding, which attention reads."""
     padded = (tokens + 63) // 64 * 64
     return (torch.zeros if padded != tokens else torch.empty)((*lead, padded), dtype=BF16, device=device)
+
+
+class _Fwd:
+    """The state of one forward between its stages (``LTXModel._fwd_*``): sizes, the residual stream ``x`` with its row
+    statistics, the modulation tables and the buffers the blocks share.  Plain attributes, set once by ``_fwd_prepare``."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
 
 
 class ContextKV:
@@ -549,7 +558,22 @@ class LTXModel:
         debug taps, transformer.py; used by the per-layer parity tests).
         ``perturbations``: one PerturbationConfig per batch row (guidance.py); in a row perturbed with SKIP_VIDEO_SELF_ATTN at
         a block, that block's self-attention returns its value projection v instead of softmax(q k^T) v (then to_out, gate and
-        residual as usual) - STG, DESIGN.md "Spatio-temporal guidance".  None: no row is perturbed."""
+        residual as usual) - STG, DESIGN.md "Spatio-temporal guidance".  None: no row is perturbed.
+        The forward is four stages over one ``_Fwd`` state - prepare; per block the self- and text attention, then the
+        feed-forward; the head - so that the AudioVideo model (av_model.py) can run two of these forwards block by block with
+        the cross-modal attentions in between."""
+        st = self._fwd_prepare(latent, plan, context, pe, ctx_kv, perturbations)
+        for li in range(len(self.blocks)):
+            self._fwd_attn(st, li)
+            self._fwd_ff(st, li)
+            if hidden is not None:
+                hidden.append(st.x.reshape(st.B, st.N, self.inner_dim).clone())
+        return self._fwd_head(st)
+
+    def _fwd_prepare(self, latent: torch.Tensor, plan: TimestepPlan, context: torch.Tensor, pe: Tuple[torch.Tensor, torch.Tensor],
+                     ctx_kv: Optional[ContextKV], perturbations: Optional[BatchedPerturbationConfig]) -> "_Fwd":
+        """Everything of ``forward_tokens`` in front of block 0: the residual stream, the modulation tables, the context and
+        the buffers the blocks share."""
         cfg = self.config
         D, H, eps = self.inner_dim, self.num_attention_heads, cfg.norm_eps
         B, N, C = latent.shape
@@ -632,69 +656,85 @@ class LTXModel:
         fq, fs, fp = self.fuse & 1, self.fuse & 2, (self.fuse & 6) == 6
         ts_ = self.attn_tail_split and not self.batch_invariant
         s_x, s_qk, s_q2 = (xss, qkss, q2ss) if fs else (None, None, None)
-        for li, blk in enumerate(self.blocks):
-            mod = mods[li]                                           # (U,6,D): shift, 1+scale, gate x2
-            # self-attention (transformer.py:248-254).  q|k|v from one launch: q,k row-major with their row statistics,
-            # V^T transposed.  k is normalised + rotated in place; q stays RAW in HBM - the attention kernel normalises
-            # and rotates its Q fragments in registers (attention.py:129-136).
-            ops.rmsnorm_modulate(x, eps, mod[:, 1], mod[:, 0], ms, tok2row, out=nx, sumsq=s_x, scale_is_one_plus=bool(fs))
-            # (fuse bit 8: q|k on the 320x256 tile with v as its own launch - a gain only where M is a whole number of 320-row
-            # tiles (M=1280: 35.4 against 35.6 ms per forward, M=2560: 60.3 against 61.0); every other row count is 1-4 % faster
-            # with q|k|v as ONE launch (M=1296: 39.4 against 41.2 ms, 3328: 87.6 / 89.2, 5184: 141.5 / 143.8, 6656: 161.5 / 164.7;
-            # scripts/exp_qkv_one_launch.py), and at small M every launch is a weight stream with ~5 us of fixed cost)
-            if fq and (not (self.fuse & 8) or M <= ops.SPLITK_MAX_M or M % 320 != 0):
-                self._linear(nx, blk.qkv, nx_q, out=qk, out2=vt, n_split=2 * D, out_tokens_per_batch=N, sumsq=s_qk)
-            else:
-                self._lin(nx, nx_q, [(blk.qkv.rows(None, 2 * D), dict(out=qk, sumsq=s_qk)),
-                                     (blk.qkv.rows(2 * D, None), dict(out=vt, out_tokens_per_batch=N))])
-            skip = skip_rows[li]
-            # the q side of the two attentions: raw q with its row statistics, normalised (and rotated) inside the kernel - or
-            # q normalised by a launch of its own in front
-            if fp:
-                ops.qknorm_rope(qk[:, D:], 1, D, blk.wkn, cos, sin, N, H, eps, sumsq=qkss[:, P:], head_dim=dh)
-                fused1, fused2 = dict(q_norm_weight=blk.wqn, cos=cos, sin=sin, eps=eps), dict(q_sumsq=q2ss, q_norm_weight=blk.wqn2, eps=eps)
-            else:
-                ops.qknorm_rope(qk, 2, D, blk.wqkn, cos, sin, N, H, eps, sumsq=s_qk, head_dim=dh)
-                fused1 = fused2 = {}
-            # attention over each maximal run of rows that keep it (all B rows in one launch when nothing is skipped)
-            for r0, r1 in _runs(B, skip):
-                t0, t1 = r0 * N, r1 * N
-                ops.flash_attn(qk[t0:t1, :D], qk[t0:t1, D:], vt[r0:r1], att[t0:t1], r1 - r0, H, N, N, scale,
-                               q_sumsq=qkss[t0:t1] if fp else None, tail_split=ts_, head_dim=dh, **fused1)
-            if skip:          # STG: the skipped rows' attention output is their value projection, v = (V^T)^T
-                ops.attn_value_passthrough(vt, att, B, N, sum(1 << r for r in skip))
-            self._linear(att, blk.o, att_q, epilogue=ops.EPI_BIAS_GATE_RES, out=x, resid=x,
-                         gate=mod[:, 2], gate_row=tok2row, gate_stride=ms, sumsq=s_x)
-            # text cross-attention (transformer.py:257-261)
-            ops.rmsnorm_modulate(x, eps, out=nx, sumsq=s_x)
-            self._linear(nx, blk.q2, nx_q, out=q2, sumsq=s_q2)
-            if ctx_kv is not None:
-                kv = ctx_kv.kv[li]
-            elif kv_all is not None:
-                kv = (kv_all[0][li], kv_all[1][li], kv_all[2][li])
-            else:
-                kv = self._context_kv(blk, ctx, B, S, kv_buf, ctx_q)
-            if not fp:
-                ops.qknorm_rope(q2, 1, D, blk.wqn2, None, None, N, H, eps, sumsq=s_q2, head_dim=dh)
-            ops.flash_attn(q2, kv[0], kv[1], att, B, H, N, S, scale, tail_split=ts_, head_dim=dh, **fused2)
-            self._linear(att, blk.o2, att_q, epilogue=ops.EPI_BIAS_RES, out=x, resid=x, sumsq=s_x)
-            # feed-forward (transformer.py:343-347)
-            ops.rmsnorm_modulate(x, eps, mod[:, 4], mod[:, 3], ms, tok2row, out=nx, sumsq=s_x, scale_is_one_plus=bool(fs))
-            self._linear(nx, blk.ff1, nx_q, epilogue=ops.EPI_BIAS_GELU, out=hff)
-            self._linear(hff, blk.ff2, hff_q, epilogue=ops.EPI_BIAS_GATE_RES, out=x, resid=x,
-                         gate=mod[:, 5], gate_row=tok2row, gate_stride=ms, sumsq=s_x)
-            if hidden is not None:
-                hidden.append(x.reshape(B, N, D).clone())
+        return _Fwd(B=B, N=N, M=M, S=S, U=U, P=P, x=x, xss=xss, tproj=tproj, mods=mods, head=head, tok2row=tok2row, cos=cos, sin=sin,
+                    ctx=ctx, ctx_kv=ctx_kv, kv_all=kv_all, kv_buf=kv_buf, ctx_q=ctx_q, vt=vt, qk=qk, qkss=qkss, nx=nx, att=att, q2=q2,
+                    q2ss=q2ss, hff=hff, nx_q=nx_q, att_q=att_q, hff_q=hff_q, skip_rows=skip_rows, ts_=ts_, s_x=s_x, s_qk=s_qk,
+                    s_q2=s_q2)
 
-        # --- output head (ltx.py:432-457) ---
-        ops.layernorm_modulate(x, eps, head[:, 1], head[:, 0], 2 * D, tok2row, out=nx)
-        v = self._linear(nx, self.out)
-        return v.reshape(B, N, cfg.out_channels)
+    def _fwd_attn(self, st: "_Fwd", li: int) -> None:
+        """Block ``li``'s self-attention and text attention (transformer.py:247-261), onto st.x."""
+        cfg, blk = self.config, self.blocks[li]
+        D, H, eps, dh = self.inner_dim, self.num_attention_heads, cfg.norm_eps, cfg.attention_head_dim
+        B, N, M, S, P, ms, scale = st.B, st.N, st.M, st.S, st.P, 6 * self.inner_dim, 1.0 / math.sqrt(cfg.attention_head_dim)
+        x, nx, qk, vt, att, q2, qkss, q2ss = st.x, st.nx, st.qk, st.vt, st.att, st.q2, st.qkss, st.q2ss
+        nx_q, att_q, tok2row, cos, sin, ts_ = st.nx_q, st.att_q, st.tok2row, st.cos, st.sin, st.ts_
+        s_x, s_qk, s_q2 = st.s_x, st.s_qk, st.s_q2
+        fq, fs, fp = self.fuse & 1, self.fuse & 2, (self.fuse & 6) == 6
+        mod = st.mods[li]                                        # (U,6,D): shift, 1+scale, gate x2
+        # self-attention (transformer.py:248-254).  q|k|v from one launch: q,k row-major with their row statistics,
+        # V^T transposed.  k is normalised + rotated in place; q stays RAW in HBM - the attention kernel normalises
+        # and rotates its Q fragments in registers (attention.py:129-136).
+        ops.rmsnorm_modulate(x, eps, mod[:, 1], mod[:, 0], ms, tok2row, out=nx, sumsq=s_x, scale_is_one_plus=bool(fs))
+        # (fuse bit 8: q|k on the 320x256 tile with v as its own launch - a gain only where M is a whole number of 320-row
+        # tiles (M=1280: 35.4 against 35.6 ms per forward, M=2560: 60.3 against 61.0); every other row count is 1-4 % faster
+        # with q|k|v as ONE launch (M=1296: 39.4 against 41.2 ms, 3328: 87.6 / 89.2, 5184: 141.5 / 143.8, 6656: 161.5 / 164.7;
+        # scripts/exp_qkv_one_launch.py), and at small M every launch is a weight stream with ~5 us of fixed cost)
+        if fq and (not (self.fuse & 8) or M <= ops.SPLITK_MAX_M or M % 320 != 0):
+            self._linear(nx, blk.qkv, nx_q, out=qk, out2=vt, n_split=2 * D, out_tokens_per_batch=N, sumsq=s_qk)
+        else:
+            self._lin(nx, nx_q, [(blk.qkv.rows(None, 2 * D), dict(out=qk, sumsq=s_qk)),
+                                 (blk.qkv.rows(2 * D, None), dict(out=vt, out_tokens_per_batch=N))])
+        skip = st.skip_rows[li]
+        # the q side of the two attentions: raw q with its row statistics, normalised (and rotated) inside the kernel - or
+        # q normalised by a launch of its own in front
+        if fp:
+            ops.qknorm_rope(qk[:, D:], 1, D, blk.wkn, cos, sin, N, H, eps, sumsq=qkss[:, P:], head_dim=dh)
+            fused1, fused2 = dict(q_norm_weight=blk.wqn, cos=cos, sin=sin, eps=eps), dict(q_sumsq=q2ss, q_norm_weight=blk.wqn2, eps=eps)
+        else:
+            ops.qknorm_rope(qk, 2, D, blk.wqkn, cos, sin, N, H, eps, sumsq=s_qk, head_dim=dh)
+            fused1 = fused2 = {}
+        # attention over each maximal run of rows that keep it (all B rows in one launch when nothing is skipped)
+        for r0, r1 in _runs(B, skip):
+            t0, t1 = r0 * N, r1 * N
+            ops.flash_attn(qk[t0:t1, :D], qk[t0:t1, D:], vt[r0:r1], att[t0:t1], r1 - r0, H, N, N, scale,
+                           q_sumsq=qkss[t0:t1] if fp else None, tail_split=ts_, head_dim=dh, **fused1)
+        if skip:          # STG: the skipped rows' attention output is their value projection, v = (V^T)^T
+            ops.attn_value_passthrough(vt, att, B, N, sum(1 << r for r in skip))
+        self._linear(att, blk.o, att_q, epilogue=ops.EPI_BIAS_GATE_RES, out=x, resid=x,
+                     gate=mod[:, 2], gate_row=tok2row, gate_stride=ms, sumsq=s_x)
+        # text cross-attention (transformer.py:257-261)
+        ops.rmsnorm_modulate(x, eps, out=nx, sumsq=s_x)
+        self._linear(nx, blk.q2, nx_q, out=q2, sumsq=s_q2)
+        if st.ctx_kv is not None:
+            kv = st.ctx_kv.kv[li]
+        elif st.kv_all is not None:
+            kv = (st.kv_all[0][li], st.kv_all[1][li], st.kv_all[2][li])
+        else:
+            kv = self._context_kv(blk, st.ctx, B, S, st.kv_buf, st.ctx_q)
+        if not fp:
+            ops.qknorm_rope(q2, 1, D, blk.wqn2, None, None, N, H, eps, sumsq=s_q2, head_dim=dh)
+        ops.flash_attn(q2, kv[0], kv[1], att, B, H, N, S, scale, tail_split=ts_, head_dim=dh, **fused2)
+        self._linear(att, blk.o2, att_q, epilogue=ops.EPI_BIAS_RES, out=x, resid=x, sumsq=s_x)
+
+    def _fwd_ff(self, st: "_Fwd", li: int) -> None:
+        """Block ``li``'s feed-forward (transformer.py:343-347), onto st.x."""
+        blk, mod, eps, ms, fs = self.blocks[li], st.mods[li], self.config.norm_eps, 6 * self.inner_dim, self.fuse & 2
+        x, nx, hff, nx_q, hff_q, tok2row, s_x = st.x, st.nx, st.hff, st.nx_q, st.hff_q, st.tok2row, st.s_x
+        ops.rmsnorm_modulate(x, eps, mod[:, 4], mod[:, 3], ms, tok2row, out=nx, sumsq=s_x, scale_is_one_plus=bool(fs))
+        self._linear(nx, blk.ff1, nx_q, epilogue=ops.EPI_BIAS_GELU, out=hff)
+        self._linear(hff, blk.ff2, hff_q, epilogue=ops.EPI_BIAS_GATE_RES, out=x, resid=x,
+                     gate=mod[:, 5], gate_row=tok2row, gate_stride=ms, sumsq=s_x)
+
+    def _fwd_head(self, st: "_Fwd") -> torch.Tensor:
+        """The output head (ltx.py:432-457): velocity (B,N,out_channels)."""
+        ops.layernorm_modulate(st.x, self.config.norm_eps, st.head[:, 1], st.head[:, 0], 2 * self.inner_dim, st.tok2row, out=st.nx)
+        v = self._linear(st.nx, self.out)
+        return v.reshape(st.B, st.N, self.config.out_channels)
 
     def __call__(self, video: Optional[Modality] = None, audio: Optional[Modality] = None,
                  perturbations: Optional[BatchedPerturbationConfig] = None):
         if audio is not None:
-            raise ValueError("Audio is not enabled for this model")      # ltx.py:468-469
+            raise ValueError("Audio is not enabled for this model (joint denoising: av_model.LTXAVModel)")      # ltx.py:468-469
         if video is None:
             return None, None
         lat = video.latent

@@ -476,17 +476,40 @@ def _modulation(who: str, M: int, D: int, scale, shift, mod_stride: int, mod_row
 def rmsnorm_modulate(x: torch.Tensor, eps: float, scale: Optional[torch.Tensor] = None,
                      shift: Optional[torch.Tensor] = None, mod_stride: int = 0,
                      mod_row: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
-                     sumsq: Optional[torch.Tensor] = None, scale_is_one_plus: bool = False) -> torch.Tensor:
+                     sumsq: Optional[torch.Tensor] = None, scale_is_one_plus: bool = False,
+                     scale2: Optional[torch.Tensor] = None, shift2: Optional[torch.Tensor] = None,
+                     out2: Optional[torch.Tensor] = None):
     """x, out (M,D) contiguous; the modulation of row m is scale / shift[mod_row[m] * mod_stride + d].
     ``sumsq`` (M, >= D/64) fp32: the rows' sums of squares in 64-column partials (gemm(..., sumsq=)); without it the
-    kernel reduces the row itself.  ``scale_is_one_plus``: scale holds bf16(1+scale) (needs sumsq)."""
+    kernel reduces the row itself.  ``scale_is_one_plus``: scale holds bf16(1+scale) (needs sumsq).
+    ``scale2`` / ``shift2``: a second modulation of the same normalised row (ltxk_rmsnorm_modulate2: x is read once) with the
+    same mod_stride / mod_row / scale_is_one_plus, into ``out2``; the call then returns (out, out2), each with the bits of
+    the one-pair call on the same operands."""
     if scale_is_one_plus and sumsq is None:
         raise ValueError("rmsnorm_modulate: scale_is_one_plus needs sumsq")
+    two = scale2 is not None or shift2 is not None
+    if two and (scale is None or shift is None or scale2 is None or shift2 is None):
+        raise ValueError("rmsnorm_modulate: a second modulation needs scale, shift, scale2 and shift2")
+    if out2 is not None and not two:
+        raise ValueError("rmsnorm_modulate: out2 goes with scale2 / shift2")
     M, D = _dims("rmsnorm_modulate", "x", x, BF16, 2)
     _operands("rmsnorm_modulate", ("x", x, BF16, 2, 16), ("out", out, BF16, (M, D), 16),
-              *_modulation("rmsnorm_modulate", M, D, scale, shift, mod_stride, mod_row), ("sumsq", sumsq, F32, (M, -(D // 64)), 4, True))
+              *_modulation("rmsnorm_modulate", M, D, scale, shift, mod_stride, mod_row), ("sumsq", sumsq, F32, (M, -(D // 64)), 4, True),
+              ("scale2", scale2, BF16, _table("rmsnorm_modulate", "scale2", scale2, D, mod_stride), 16, True),
+              ("shift2", shift2, BF16, _table("rmsnorm_modulate", "shift2", shift2, D, mod_stride), 16, True),
+              ("out2", out2, BF16, (M, D), 16))
     if out is None:
         out = torch.empty_like(x)
+    if two:
+        if out2 is None:
+            out2 = torch.empty_like(x)
+        if out2.data_ptr() == out.data_ptr():
+            raise ValueError("rmsnorm_modulate: out and out2 must be two buffers")
+        with _timed("rmsnorm_modulate", 0.0, 6.0 * M * D):
+            check(_lib.load().ltxk_rmsnorm_modulate2(_p(x), _p(out), _p(out2), M, D, eps, _p(sumsq), 0 if sumsq is None else sumsq.stride(0),
+                                                     D // 64, _p(scale), _p(shift), _p(scale2), _p(shift2), mod_stride, _p(mod_row),
+                                                     int(scale_is_one_plus), _stream()), "ltxk_rmsnorm_modulate2")
+        return out, out2
     with _timed("rmsnorm_modulate", 0.0, 4.0 * M * D):
         if sumsq is not None:
             check(_lib.load().ltxk_rmsnorm_modulate_ss(_p(x), _p(out), M, D, eps, _p(sumsq), sumsq.stride(0), D // 64, _p(scale),

@@ -221,6 +221,88 @@ def load_audio_transformer(model_repo, device):
     return LTXModel(cfg, W)
 
 
+_CROSS_MARKS = ("audio_to_video_attn.", "video_to_audio_attn.", "scale_shift_table_a2v_ca_")
+_CROSS_ADALN = ("av_ca_video_scale_shift_adaln_single", "av_ca_audio_scale_shift_adaln_single", "av_ca_a2v_gate_adaln_single",
+                "av_ca_v2a_gate_adaln_single")
+
+
+def _cross_transformer_key(raw_key: str) -> Optional[str]:
+    """Checkpoint key -> module key of the CROSS-MODAL tensors of the joint transformer, or None: ``audio_to_video_attn.*``,
+    ``video_to_audio_attn.*`` and ``scale_shift_table_a2v_ca_*`` of every block and the four ``av_ca_*`` AdaLN-singles - what
+    ``_transformer_key`` and ``_audio_transformer_key`` both leave out."""
+    from .ltx_model import LTXModel
+    k = raw_key
+    if k.startswith("model.diffusion_model."):
+        m = LTXModel.sanitize({k: None})
+        if not m:
+            return None
+        k = next(iter(m))
+    elif k.startswith("transformer."):
+        k = k[len("transformer."):]
+    if k.startswith("transformer_blocks."):
+        return k if any(m in k for m in _CROSS_MARKS) else None
+    return k if k.startswith(tuple(m + "." for m in _CROSS_ADALN)) else None
+
+
+def _missing_cross_keys(video_keys: Iterable[str], cross_keys: Iterable[str]) -> list:
+    """The cross tensors a joint transformer of the video set's depth needs and ``cross_keys`` lacks."""
+    from .av_model import LTXAVModel
+    from .ltx_model import LTXModelConfig
+    layers = 1 + max((int(k.split(".")[1]) for k in video_keys if k.startswith("transformer_blocks.")), default=-1)
+    want = LTXAVModel.expected_cross_keys(LTXModelConfig(num_layers=layers), None)
+    have = set(cross_keys)
+    return [k for k in want if k not in have]
+
+
+def av_transformer_weights(raw: Dict[str, torch.Tensor], device, strict: bool = True):
+    """The three module-key dicts of a joint checkpoint, (video, audio, cross): what ``_transformer_key`` keeps, what
+    ``_audio_transformer_key`` keeps (under the video names), and the cross-modal tensors (``_cross_transformer_key``).  The sets
+    are disjoint by construction - each raw key goes to the first map that takes it - and the embeddings connectors go to none.
+    bf16.  ``strict``: ValueError listing the cross tensors that a joint transformer of the video set's depth needs and the
+    checkpoint lacks."""
+    out = ({}, {}, {})
+    for k, v in raw.items():
+        for dst, key_of in zip(out, (_transformer_key, _audio_transformer_key, _cross_transformer_key)):
+            kk = key_of(k)
+            if kk is not None:
+                dst[kk] = _to_dev(v, device)
+                break
+    if strict:
+        missing = _missing_cross_keys(out[0], out[2])
+        if missing:
+            raise ValueError(f"the checkpoint lacks {len(missing)} cross-modal tensors of the joint transformer: {missing}")
+    return out
+
+
+def load_av_transformer(model_repo, device, video=None):
+    """The ``LTXAVModel`` of a local joint checkpoint directory: video, audio and cross tensors of its LTX-2 safetensors,
+    streamed one by one; strict.  ``video``: the video ``LTXModel`` already built from this checkpoint - only the audio and the
+    cross tensors are then read.  FileNotFoundError / ValueError when the directory or a tensor is missing."""
+    from .av_model import LTXAVModel
+    from .ltx_model import LTXModel
+    root = Path(model_repo)
+    if not root.is_dir():
+        raise FileNotFoundError(f"model_repo {str(model_repo)!r} is not a local directory; nothing is fetched")
+    main = [f for f in sorted(root.glob("*.safetensors")) if "upscaler" not in f.name and "upsampler" not in f.name]
+    maps = ((lambda k: None) if video is not None else _transformer_key, _audio_transformer_key, _cross_transformer_key)
+    sets = ({}, {}, {})
+    for k, v in iter_safetensors(main, want=lambda k: any(m(k) is not None for m in maps)):
+        for dst, key_of in zip(sets, maps):
+            kk = key_of(k)
+            if kk is not None:
+                dst[kk] = _to_dev(v, device)
+                break
+    Wv, Wa, Wc = sets
+    missing = _missing_cross_keys(Wv if video is None else [f"transformer_blocks.{len(video.blocks) - 1}."], Wc)
+    if missing:
+        raise ValueError(f"{root} lacks {len(missing)} cross-modal tensors of the joint transformer (audio_mode='joint' needs a joint "
+                         f"checkpoint): {missing[:8]}{' ...' if len(missing) > 8 else ''}")
+    if video is None:
+        video = LTXModel(infer_transformer_config({k: tuple(v.shape) for k, v in Wv.items()}), Wv)
+    audio = LTXModel(infer_audio_transformer_config({k: tuple(v.shape) for k, v in Wa.items()}), Wa)
+    return LTXAVModel(video, audio, Wc)
+
+
 def quantize_transformer_weights(W: Dict[str, torch.Tensor], fp8_scaling: str = "channel") -> Dict[str, torch.Tensor]:
     """A bf16 module-key dict (e.g. after a LoRA merge) -> the dict ``transformer_weights(fp8=True)`` gives; the input is kept."""
     out: Dict[str, torch.Tensor] = {}
