@@ -18,7 +18,8 @@ import torch
 
 import ref64 as R
 import ref_attn64 as R64
-from test_rowops_gpu import _close, _g, _ops, _sent_bf16, _untouched
+import ref_rows as RR
+from test_rowops_gpu import _close, _g, _ops, _sent_bf16, _untouched, _within
 
 pytestmark = pytest.mark.gpu
 BF = torch.bfloat16
@@ -122,25 +123,12 @@ def test_qknorm_rope_dh64_edges(dev, H, ss, nseg, rope):
     lanes of the second 16-head pass (H = 24), a rotation partner other than j + 32, a table indexed at 64 instead of 32 per
     row, a partials reduction over D/128 instead of D/64 entries, writes past nseg*D or past row M."""
     ops = _ops()
-    g = _g(2000 + 37 * H + 5 * nseg + (2 if rope else 0) + (1 if ss else 0))
-    B, T = 2, 7
-    M, D = B * T, H * DH
+    inp = RR.qknorm_inputs(H, ss, nseg, rope, DH)
+    T, M, D, x, w, cos, sin = inp.T, inp.M, inp.D, inp.x, inp.w, inp.cos, inp.sin
     ld = nseg * D + 64
-    x = torch.randn(M, nseg * D, generator=g).to(BF)
-    w = (1 + 0.3 * torch.randn(nseg, D, generator=g)).to(BF)
-    cos = sin = None
-    if rope:
-        ang = torch.rand(H, T, DH // 2, generator=g) * 8 - 4
-        cos, sin = torch.cos(ang), torch.sin(ang)
     buf = _sent_bf16((M + 2, ld), dev)
     buf[:M, :nseg * D] = x.to(dev)
-    sumsq = None
-    if ss:
-        NP = D // 64
-        ssld = nseg * NP + 3
-        s = torch.full((M, ssld), 1e30)
-        s[:, :nseg * NP] = (x.double() ** 2).reshape(M, nseg * NP, 64).sum(-1).float()
-        sumsq = s.to(dev)
+    sumsq = inp.sumsq.to(dev) if ss else None
     ops.qknorm_rope(buf[:M], nseg, D, w.to(dev), cos.to(dev) if rope else None, sin.to(dev) if rope else None, T, H, 1e-6,
                     sumsq=sumsq, head_dim=DH)
     torch.cuda.synchronize()
@@ -148,3 +136,4 @@ def test_qknorm_rope_dh64_edges(dev, H, ss, nseg, rope):
     assert _untouched(buf[M:]), "a row past M was written"
     ref, mag = R64.qknorm_rope(x, w, cos, sin, T, H, R.f32(1e-6), DH)
     _close(buf[:M, :nseg * D].cpu(), ref, max_ulps=2 if rope else 1, max_frac=1e-2, mag=mag)
+    _within(buf[:M, :nseg * D].cpu(), RR.qknorm_rope(x, w, cos, sin, T, H, R.f32(1e-6), DH, RR.qknorm_partials(inp)))

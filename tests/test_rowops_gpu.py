@@ -8,7 +8,11 @@ inside a larger ld, the tail of a flat buffer) that must survive bit for bit.
 
 Bounds: ``max_ulps`` bf16 ulps at max(|ref|, mag), where mag is the size of the terms an output inherits a rounding from
 (ref64 returns it); 1 for a single fp32 expression rounded once, 2 where an earlier bf16 rounding point can flip and
-carry into the next op, 0 for exact maps and bit-identical launch forms.  ``max_frac``: fraction of elements off at all."""
+carry into the next op, 0 for exact maps and bit-identical launch forms.  ``max_frac``: fraction of elements off at all.
+
+Beside that rule every output is held, element by element and with no exempt share, to the admissible bf16 interval of
+tests/ref_rows.py (``_within``): a float64 interval carried through the kernel's own chain of operations.  The inputs come
+from ref_rows' builders, which tests/test_ref_rows_cpu.py shares."""
 import ctypes
 
 import numpy as np
@@ -17,6 +21,7 @@ import pytest
 import torch
 
 import ref64 as R
+import ref_rows as RR
 
 pytestmark = pytest.mark.gpu
 BF = torch.bfloat16
@@ -34,8 +39,7 @@ def _lib():
     return _lib
 
 
-def _g(seed):
-    return torch.Generator().manual_seed(seed)
+_g = RR.gen
 
 
 def _sent_bf16(shape, dev):
@@ -62,35 +66,32 @@ def _close(got, ref, *, max_ulps, max_frac, mag=None, tag=""):
     R.assert_bf16_close(got, ref, max_ulps=max_ulps, max_frac=max_frac, mag=mag, what=tag)
 
 
+def _within(got, iv, *, cap=RR.AMBIGUOUS_CAP, tag=""):
+    """ref_rows' comparator: every element inside its admissible bf16 interval; the share of elements with two admissible
+    values (a property of the reference alone, capped in test_ref_rows_cpu.py) goes into the ledger."""
+    (n, first), amb, widest = RR.within(got, iv)
+    parity.auto(amb, cap, tag=f"{tag}ambiguous")
+    assert n == 0, (f"{tag}: {n} elements outside their admissible bf16 interval, the first at flat index {first} "
+                    f"(widest interval {widest} bf16 steps)")
+
+
 def _ulp_f32(m):
     m = m.abs().clamp_min(2.0 ** -126)
     return torch.exp2(torch.floor(torch.log2(m)) - 23)
 
 
 # ------------------------------------------------------------------------------------------- self-reducing row norms
-def _norm_case(dev, ln, M, D, mode, seed, special_rows=False):
+def _norm_case(dev, ln, M, D, mode, seed, special_rows=False, small_mean=False):
     ops = _ops()
-    g = _g(seed)
-    x = (torch.randn(M, D, generator=g) + 100) if ln else torch.randn(M, D, generator=g) * 3
-    if special_rows and M >= 2:
-        x[0] = 3.0
-        x[1] = 0.0
-    x = x.to(BF)
+    inp = RR.norm_inputs(ln, M, D, mode, seed, special_rows, small_mean)
+    x, sc, sh = inp.x, inp.sc, inp.sh
     y = _sent_bf16((M + 3, D), dev)
-    sc = sh = rows = None
-    stride = 0
     if mode == "scale_shift":                   # one modulation row, no row map
-        tab = torch.randn(1, 2 * D, generator=g).to(BF)
-        sc, sh, stride = tab[:, D:].expand(M, D), tab[:, :D].expand(M, D), 2 * D
-        td = tab.to(dev)
-        ops_args = (td[:, D:], td[:, :D], stride, None)
+        td = inp.tab.to(dev)
+        ops_args = (td[:, D:], td[:, :D], inp.stride, None)
     elif mode == "mod_row":                     # U = 3 rows of a (U, 6D) table, picked per token
-        U = 3
-        tab = torch.randn(U, 6 * D, generator=g).to(BF)
-        rows = torch.randint(0, U, (M,), generator=g, dtype=torch.int32)
-        sc, sh, stride = tab[rows.long(), D:2 * D], tab[rows.long(), :D], 6 * D
-        td = tab.to(dev)
-        ops_args = (td[:, D:2 * D], td[:, :D], stride, rows.to(dev))
+        td = inp.tab.to(dev)
+        ops_args = (td[:, D:2 * D], td[:, :D], inp.stride, inp.rows.to(dev))
     else:
         ops_args = (None, None, 0, None)
     f = ops.layernorm_modulate if ln else ops.rmsnorm_modulate
@@ -98,7 +99,7 @@ def _norm_case(dev, ln, M, D, mode, seed, special_rows=False):
     torch.cuda.synchronize()
     ref, mag = R.norm_modulate(x, R.f32(1e-6), sc, sh, layernorm=ln)
     assert _untouched(y[M:]), "a row past M was written"
-    return y[:M].cpu(), ref, mag
+    return y[:M].cpu(), ref, mag, RR.norm_modulate(x, R.f32(1e-6), sc, sh, layernorm=ln)
 
 
 @pytest.mark.parametrize("mode", ["none", "scale_shift", "mod_row"])
@@ -110,20 +111,34 @@ def test_norm_modulate_edges(dev, ln, D, M, mode):
     MAX_CHUNKS), a last workgroup whose idle waves store (M % 4 != 0: rows past M must stay NaN), an off-by-one
     `mod_row` or a modulation row read at the wrong stride (U = 3, mod_stride = 6D), and - for LayerNorm, on rows of
     100 + N(0,1) - a one-pass E[x^2] - E[x]^2 variance, which cancels there."""
-    got, ref, mag = _norm_case(dev, ln, M, D, mode, seed=D + 10 * M + (7 if ln else 0))
+    got, ref, mag, iv = _norm_case(dev, ln, M, D, mode, seed=RR.norm_seed(ln, D, M))
     # LayerNorm rows of 100 + N(0,1) hold ~30 distinct bf16 values (ulp 0.5 there), so a value that lands near a rounding
     # midpoint flips as a group: measured up to 3.9 % of a row
     _close(got, ref, max_ulps=1 if mode == "none" else 2, max_frac=0.1 if ln else 1e-2, mag=mag)
+    _within(got, iv, cap=RR.cap(ln))                                # rows of 100 + N(0,1): the named cancellation case
+
+
+@pytest.mark.parametrize("mode", ["none", "mod_row"])
+@pytest.mark.parametrize("D", [512, 8192])
+def test_layernorm_small_mean_edges(dev, D, mode):
+    """LayerNorm on rows of 0.5 + 3 N(0,1), M = 5: without the cancellation of the 100 + N(0,1) rows the admissible
+    intervals are narrow (at most 2 % of the elements have more than one admissible value), so here the LayerNorm chain -
+    mean, centred variance, rstd, n, modulation - is held to its bf16 interval element by element."""
+    got, _, _, iv = _norm_case(dev, True, RR.SMALL_MEAN_M, D, mode, seed=RR.small_mean_seed(D), small_mean=True)
+    _within(got, iv)
 
 
 @pytest.mark.parametrize("ln", [False, True], ids=["rms", "ln"])
 def test_norm_modulate_many_rows_and_flat_rows(dev, ln):
     """M = 4097 rows at D = 512 (a lone row in the last workgroup), and a constant and an all-zero row at D = 2048
     (variance 0 -> rstd = eps^-1/2: a kernel that divides by the variance or skips eps returns inf/NaN there)."""
-    got, ref, mag = _norm_case(dev, ln, 4097, 512, "mod_row", seed=41)
+    cap = RR.cap(ln)
+    got, ref, mag, iv = _norm_case(dev, ln, 4097, 512, "mod_row", seed=41)
     _close(got, ref, max_ulps=2, max_frac=1e-2, mag=mag, tag="m4097_")
-    got, ref, mag = _norm_case(dev, ln, 5, 2048, "none", seed=42, special_rows=True)
+    _within(got, iv, cap=cap, tag="m4097_")
+    got, ref, mag, iv = _norm_case(dev, ln, 5, 2048, "none", seed=42, special_rows=True)
     _close(got, ref, max_ulps=1, max_frac=1e-2, tag="flat_")
+    _within(got, iv, cap=cap, tag="flat_")
     assert torch.isfinite(got.float()).all()
 
 
@@ -137,19 +152,8 @@ def test_rmsnorm_ss_edges(dev, D, M, one_plus):
     into the garbage, a wrong CH = 1 / 2 row split (D = 1536 vs 2048), ONE_PLUS adding 1 twice, and a last partial
     workgroup (M % 4 != 0) that stores."""
     ops = _ops()
-    g = _g(100 + D + M)
-    U = 3
-    x = (torch.randn(M, D, generator=g) * 3).to(BF)
-    NP = D // 64
-    ssld = NP + 5
-    ss = torch.full((M, ssld), 1e30)                                          # garbage past NP
-    ss[:, :NP] = (x.double() ** 2).reshape(M, NP, 64).sum(-1).float()
-    tab = torch.randn(U, 6 * D, generator=g).to(BF)
-    rows = torch.randint(0, U, (M,), generator=g, dtype=torch.int32)
-    sc, sh = tab[rows.long(), D:2 * D], tab[rows.long(), :D]
-    if one_plus:
-        tab[:, D:2 * D] = R.rbf(1.0 + tab[:, D:2 * D].double()).to(BF)
-        sc = tab[rows.long(), D:2 * D]
+    inp = RR.rmsnorm_ss_inputs(D, M, one_plus)
+    x, ss, tab, rows, sc, sh = inp.x, inp.ss, inp.tab, inp.rows, inp.sc, inp.sh
     td = tab.to(dev)
     y = _sent_bf16((M + 3, D), dev)
     ops.rmsnorm_modulate(x.to(dev), 1e-6, td[:, D:2 * D], td[:, :D], 6 * D, rows.to(dev), out=y[:M], sumsq=ss.to(dev),
@@ -161,6 +165,9 @@ def test_rmsnorm_ss_edges(dev, D, M, one_plus):
     ref, mag = R.norm_modulate(x, R.f32(1e-6), sc, sh, one_plus=one_plus)
     _close(y[:M].cpu(), ref, max_ulps=2, max_frac=1e-2, mag=mag, tag="mod_")
     _close(y2[:M].cpu(), R.norm_modulate(x, R.f32(1e-6))[0], max_ulps=1, max_frac=1e-2, tag="plain_")
+    part = ss[:, :inp.NP]
+    _within(y[:M].cpu(), RR.norm_modulate(x, R.f32(1e-6), sc, sh, one_plus=one_plus, partials=part), tag="mod_")
+    _within(y2[:M].cpu(), RR.norm_modulate(x, R.f32(1e-6), partials=part), tag="plain_")
 
 
 # ------------------------------------------------------------------------------------------- q/k norm + rope
@@ -174,25 +181,12 @@ def test_qknorm_rope_edges(dev, H, ss, nseg, rope):
     row instead of row % T, and - for the partials form - a reduction that stops at 64 partials (H = 40: NP = 80) or
     reads another segment's partials.  H = 40 runs in the partials form only: the self-reducing one takes H <= 32."""
     ops = _ops()
-    g = _g(1000 + 37 * H + 5 * nseg + (2 if rope else 0) + (1 if ss else 0))
-    B, T = 2, 7
-    M, D = B * T, H * 128
+    inp = RR.qknorm_inputs(H, ss, nseg, rope)
+    T, M, D, x, w, cos, sin = inp.T, inp.M, inp.D, inp.x, inp.w, inp.cos, inp.sin
     ld = nseg * D + 64
-    x = torch.randn(M, nseg * D, generator=g).to(BF)
-    w = (1 + 0.3 * torch.randn(nseg, D, generator=g)).to(BF)
-    cos = sin = None
-    if rope:
-        ang = torch.rand(H, T, 64, generator=g) * 8 - 4
-        cos, sin = torch.cos(ang), torch.sin(ang)
     buf = _sent_bf16((M + 2, ld), dev)
     buf[:M, :nseg * D] = x.to(dev)
-    sumsq = None
-    if ss:
-        NP = D // 64
-        ssld = nseg * NP + 3
-        s = torch.full((M, ssld), 1e30)
-        s[:, :nseg * NP] = (x.double() ** 2).reshape(M, nseg * NP, 64).sum(-1).float()
-        sumsq = s.to(dev)
+    sumsq = inp.sumsq.to(dev) if ss else None
     ops.qknorm_rope(buf[:M], nseg, D, w.to(dev), cos.to(dev) if rope else None, sin.to(dev) if rope else None, T, H, 1e-6,
                     sumsq=sumsq)
     torch.cuda.synchronize()
@@ -200,6 +194,7 @@ def test_qknorm_rope_edges(dev, H, ss, nseg, rope):
     assert _untouched(buf[M:]), "a row past M was written"
     ref, mag = R.qknorm_rope(x, w, cos, sin, T, H, R.f32(1e-6))
     _close(buf[:M, :nseg * D].cpu(), ref, max_ulps=2 if rope else 1, max_frac=1e-2, mag=mag)
+    _within(buf[:M, :nseg * D].cpu(), RR.qknorm_rope(x, w, cos, sin, T, H, R.f32(1e-6), partials=RR.qknorm_partials(inp)))
 
 
 # ------------------------------------------------------------------------------------------- rope table
@@ -291,10 +286,7 @@ def test_ada_combine_edges(dev, D):
 
 
 # ------------------------------------------------------------------------------------------- silu
-def _all_finite_bf16(lo, hi):
-    b = torch.arange(-32768, 32768, dtype=torch.int32).to(torch.int16).view(BF)
-    f = b.float()
-    return b[torch.isfinite(f) & (f >= lo) & (f <= hi)]
+_all_finite_bf16 = RR.all_finite_bf16
 
 
 def test_silu_every_value(dev):
@@ -302,17 +294,15 @@ def test_silu_every_value(dev):
     partial.  Catches: a silu whose exp(-x) overflows to inf and flushes results that are still normal numbers
     (x in [-91.8, -88.7]), a wrong rounding, and a last vector group that is skipped or stored past n."""
     L = _lib()
-    big = torch.tensor([1e4, -1e4, 1e30, -1e30, 3.0e38, -3.0e38, -88.5, -88.75, -89.0, -90.0, -91.5, -95.0, -104.0])
-    x = torch.cat([_all_finite_bf16(-100.0, 100.0), big.to(BF)])
-    k = (x.numel() // 8 + 255) // 256
-    n = 8 * (256 * k + 3)
-    x = torch.cat([x, torch.zeros(n - x.numel(), dtype=BF)])
+    x = RR.silu_inputs()
+    n = x.numel()
     y = _sent_bf16((n + 64,), dev)
     x_d = x.to(dev)
     L.check(L.load().ltxk_silu(x_d.data_ptr(), y.data_ptr(), n, torch.cuda.current_stream().cuda_stream), "ltxk_silu")
     torch.cuda.synchronize()
     assert _untouched(y[n:])
     _close(y[:n].cpu(), R.silu(x), max_ulps=1, max_frac=1e-2)
+    _within(y[:n].cpu(), RR.silu(x))
 
 
 # ------------------------------------------------------------------------------------------- latent -> tokens
@@ -345,15 +335,8 @@ def test_cfg_euler_edges(dev, cfg, sn, bf16_euler, masked):
     last block along S skipped or stored past S.  The in-place form (out is latent) and the device-scalar form (_dev)
     must give the host form's bits exactly."""
     ops = _ops()
-    g = _g(7 + len(cfg) + int(sn * 10) + 2 * bf16_euler + 4 * masked)
-    B, C, S = 2, 16, 67
-    vp = torch.randn(B, S, C, generator=g).to(BF)
-    vn = torch.randn(B, S, C, generator=g).to(BF) if cfg != "none" else None
-    cs = 1.0 if cfg == "none" else float(cfg)
-    x = torch.randn(B, C, S, generator=g).to(BF)
-    clean = torch.randn(B, C, S, generator=g).to(BF) if masked else None
-    mask = torch.tensor([0.0, 1.0, 0.75])[torch.randint(0, 3, (B, S), generator=g)] if masked else None
-    sig, sig_n = R.f32(0.909375), R.f32(sn)
+    inp = RR.cfg_euler_inputs(cfg, sn, bf16_euler, masked)
+    B, C, S, vp, vn, cs, x, clean, mask, sig, sig_n = inp.B, inp.C, inp.S, inp.vp, inp.vn, inp.cs, inp.x, inp.clean, inp.mask, inp.sig, inp.sig_n
     d = lambda t: None if t is None else t.to(dev)
     n = B * C * S
     outs = []
@@ -372,6 +355,8 @@ def test_cfg_euler_edges(dev, cfg, sn, bf16_euler, masked):
         outs.append(o.cpu())
     ref, mag = R.cfg_euler_step(vp, vn, x, sig, sig_n, cs, clean, mask, bf16_euler=bf16_euler)
     _close(outs[0], ref, max_ulps=2, max_frac=4e-2 if bf16_euler else 1e-2, mag=mag, tag="ref_")   # bf16 Euler: 1.5 % measured
+    _within(outs[0], RR.cfg_euler_step(vp, vn, x, sig, sig_n, cs, clean, mask, bf16_euler=bf16_euler), cap=RR.cap(bf16_euler),
+            tag="ref_")                                             # the bf16 Euler tail: a named cancellation case
     _close(outs[1], outs[0], max_ulps=0, max_frac=0.0, tag="dev_")
     _close(outs[2], outs[0], max_ulps=0, max_frac=0.0, tag="inplace_")
 
@@ -413,11 +398,9 @@ def test_euler_step_edges(dev, sn):
     """Eager Euler update, n = 8*(256*3 + 5) (not a multiple of 2048: a partial last workgroup).  Catches a tail that is
     skipped or stored past n, and sigma / sigma_next swapped.  One rounding of the fp32 formula: <= 1 ulp."""
     L = _lib()
-    g = _g(int(sn * 10))
-    n = 8 * (256 * 3 + 5)
-    x, x0 = torch.randn(n, generator=g).to(BF), torch.randn(n, generator=g).to(BF)
+    inp = RR.euler_inputs(sn)
+    n, x, x0, sig = inp.n, inp.x, inp.x0, inp.sig
     out = _sent_bf16((n + 64,), dev)
-    sig = R.f32(0.9)
     x_d = x.to(dev)
     x0_d = x0.to(dev)
     L.check(L.load().ltxk_euler_step(x_d.data_ptr(), x0_d.data_ptr(), out.data_ptr(), n, sig, R.f32(sn),
@@ -428,6 +411,7 @@ def test_euler_step_edges(dev, sn):
     # the final add cancels often (x0 and the step have either sign): 1.9 % of the elements sit one ulp (at mag) from the
     # float64 value, exactly as the same formula in float32 on the CPU, which the kernel must match bit for bit
     _close(out[:n].cpu(), ref, max_ulps=1, max_frac=4e-2, mag=mag, tag="f64_")
+    _within(out[:n].cpu(), RR.euler_step(x, x0, sig, R.f32(sn)), cap=RR.NO_CAP, tag="f64_")        # a named cancellation case
     s32, sn32 = torch.tensor(sig), torch.tensor(R.f32(sn))
     want = (x0.float() + (sn32 * (x.float() - x0.float())) / s32).to(BF)
     _close(out[:n].cpu(), want, max_ulps=0, max_frac=0.0, tag="f32_")

@@ -2,7 +2,8 @@
 for the exact ones, against the oracle or a float32 restatement in the kernel's own operation order).  Outputs go into
 buffers with a NaN-sentinel tail that must survive bit for bit; bounds as in test_rowops_gpu.py.  The calls go through the
 ``ops`` shims with ``out=`` a view of the sentinel buffer; ``pixelnorm_act`` and ``groupnorm_act`` allocate their output, so
-their two sentinel tests hand the C entry the buffer themselves."""
+their two sentinel tests hand the C entry the buffer themselves.  Every bf16 output is also held, element by element, to its
+admissible interval of tests/ref_rows.py (``_within``; for PixelNorm every row counts, none is exempt)."""
 import math
 
 import parity
@@ -10,9 +11,10 @@ import pytest
 import torch
 
 import ref64 as R
+import ref_rows as RR
 from oracle import dit as O
 from oracle import vae as OV
-from test_rowops_gpu import _all_finite_bf16, _close, _g, _sent_bf16, _untouched
+from test_rowops_gpu import _all_finite_bf16, _close, _g, _sent_bf16, _untouched, _within
 
 pytestmark = pytest.mark.gpu
 BF = torch.bfloat16
@@ -64,6 +66,8 @@ def test_pixelnorm_act_edges(dev, C, mod, silu):
     parity.auto(ulps, max_ulps, tag="ulps")
     parity.auto(frac, 1e-2, tag="frac")
     R.assert_rows_close(got, ref, exempt, max_ulps=max_ulps, max_frac=1e-2, mag=mag, what=f"pixelnorm C={C}")
+    # every row, none exempt: the rounded row statistics m, e, s are intervals themselves
+    _within(got, RR.pixelnorm_act(x, R.f32(eps), sc if mod else None, sh if mod else None, R.PIXELNORM_RPB, silu))
 
 
 # ------------------------------------------------------------------------------------------- GroupNorm (+res, +SiLU)
@@ -77,14 +81,8 @@ def test_groupnorm_act_edges(dev, C, V, resid, silu):
     gamma/beta indexed by the in-group channel instead of the channel, the second batch normalised with the first
     batch's statistics, and stores past B*V*C."""
     L = _lib()
-    g = _g(C + V + 2 * resid + silu)
-    B, G = 2, 32
-    x = (torch.randn(B, V, C, generator=g) + 50).to(BF)
-    x[1] += 3.0                                                   # the two batches have different statistics
-    x = x.to(BF)
-    gam = (1 + 0.3 * torch.randn(C, generator=g)).to(BF)
-    bet = (0.3 * torch.randn(C, generator=g)).to(BF)
-    r = torch.randn(B, V, C, generator=g).to(BF) if resid else None
+    inp = RR.groupnorm_inputs(C, V, resid, silu)
+    B, G, x, gam, bet, r = inp.B, inp.G, inp.x, inp.gam, inp.bet, inp.r
     n = B * V * C
     out = _sent_bf16((n + 64,), dev)
     rd = r.to(dev) if resid else None
@@ -98,6 +96,7 @@ def test_groupnorm_act_edges(dev, C, V, resid, silu):
     assert _untouched(out[n:])
     ref, mag = R.groupnorm_act(x, gam, bet, G, R.f32(1e-5), r, silu)
     _close(out[:n].view(B, V, C).cpu(), ref, max_ulps=2 if (resid or silu) else 1, max_frac=1e-2, mag=mag)
+    _within(out[:n].view(B, V, C).cpu(), RR.groupnorm_act(x, gam, bet, G, R.f32(1e-5), r, silu), cap=RR.cap(RR.groupnorm_cancels(V)))
 
 
 # ------------------------------------------------------------------------------------------- latent (de)normalisation
@@ -107,12 +106,8 @@ def test_latent_denorm_cl_edges(dev, noise_scale):
     at noise_scale 0.05 and 1.0 (0: no noise).  Catches: the partial last 64-wide block along S, mean/std indexed by the
     8-channel group instead of the channel, the blend weights swapped, and stores past B*S*C."""
     from mlx_video_amd import ops
-    g = _g(int(noise_scale * 100))
-    B, C, S = 2, 128, 65
-    lat = torch.randn(B, C, S, generator=g).to(BF)
-    noise = torch.randn(B, C, S, generator=g).to(BF) if noise_scale else None
-    mean = (0.3 * torch.randn(C, generator=g)).to(BF)
-    std = (1 + 0.2 * torch.randn(C, generator=g)).abs().to(BF)
+    inp = RR.latent_denorm_inputs(noise_scale)
+    B, C, S, lat, noise, mean, std = inp.B, inp.C, inp.S, inp.lat, inp.noise, inp.mean, inp.std
     n = B * S * C
     out = _sent_bf16((n + 64,), dev)
     nd = noise.to(dev) if noise_scale else None
@@ -124,6 +119,8 @@ def test_latent_denorm_cl_edges(dev, noise_scale):
     assert _untouched(out[n:])
     ref, mag = R.latent_denorm_cl(lat, mean, std, noise, noise_scale)
     _close(out[:n].view(B, S, C).cpu(), ref, max_ulps=2 if noise_scale else 1, max_frac=4e-2, mag=mag)   # 1.6 % measured
+    _within(out[:n].view(B, S, C).cpu(), RR.latent_denorm_cl(lat, mean, std, noise, noise_scale),
+            cap=RR.cap(RR.latent_denorm_ties(noise_scale)))
 
 
 @pytest.mark.parametrize("pad", [0, 64])
@@ -132,12 +129,8 @@ def test_latent_norm_cf_edges(dev, pad):
     of two.  Catches: rows read at stride C instead of ldx (the pad columns hold NaN), the partial last block along S,
     and stores past B*C*S.  Exact against float32 (x - mean)/std -> bf16; within one ulp of float64."""
     from mlx_video_amd import ops
-    g = _g(pad + 1)
-    B, C, S = 2, 128, 65
-    ldx = C + pad
-    x = torch.randn(B, S, C, generator=g).to(BF)
-    mean = (0.3 * torch.randn(C, generator=g)).to(BF)
-    std = (1.3 + 0.2 * torch.rand(C, generator=g)).to(BF)
+    inp = RR.latent_norm_inputs(pad)
+    B, C, S, ldx, x, mean, std = inp.B, inp.C, inp.S, inp.ldx, inp.x, inp.mean, inp.std
     xb = _sent_bf16((B, S, ldx), dev)
     xb[..., :C] = x.to(dev)
     n = B * C * S
@@ -151,6 +144,7 @@ def test_latent_norm_cf_edges(dev, pad):
     want = ((x.float() - mean.float()) / std.float()).to(BF).transpose(1, 2)
     _close(got, want, max_ulps=0, max_frac=0.0, tag="f32_")
     _close(got, R.latent_norm_cf(x, mean, std), max_ulps=1, max_frac=1e-2, tag="f64_")
+    _within(got, RR.latent_norm_cf(x, mean, std), tag="f64_")
 
 
 # ------------------------------------------------------------------------------------------- tiled-decode blending
@@ -161,14 +155,8 @@ def test_tile_blend_edges(dev):
     uncovered voxels coming out NaN/inf instead of 0 (max(wsum, 1e-8)), and stores past B*C*F*H*W.  Bit for bit against a
     float32 restatement in launch order; within one ulp of float64."""
     from mlx_video_amd import ops
-    g = _g(11)
-    B, C, F, H, W = 2, 3, 5, 9, 11
-    Tt, Th, Tw = 3, 6, 7
-    tiles = []
-    for (at, ah, aw), off in [((3, 6, 7), (0, 0, 0)), ((3, 6, 7), (2, 3, 4)), ((2, 4, 5), (3, 0, 6))]:
-        tile = torch.randn(B, C, Tt, Th, Tw, generator=g).to(BF)
-        mt, mh, mw = (torch.rand(k, generator=g) * 0.9 + 0.1 for k in (Tt, Th, Tw))
-        tiles.append((tile, (at, ah, aw), mt, mh, mw, off))
+    inp = RR.tile_blend_inputs()
+    B, C, F, H, W, tiles = inp.B, inp.C, inp.F, inp.H, inp.W, inp.tiles
     S = F * H * W
     acc = torch.zeros((B, C, F, H, W), device=dev)
     ws = torch.zeros((B, 1, F, H, W), device=dev)
@@ -197,6 +185,7 @@ def test_tile_blend_edges(dev):
     want = (a32 / w32.clamp_min(1e-8)).to(BF)
     _close(got, want, max_ulps=0, max_frac=0.0, tag="f32_")
     _close(got, R.tile_blend(tiles, F, H, W), max_ulps=1, max_frac=1e-2, tag="f64_")
+    _within(got, RR.tile_blend(tiles, F, H, W), tag="f64_")
 
 
 # ------------------------------------------------------------------------------------------- uint8 frames
