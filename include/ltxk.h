@@ -141,6 +141,18 @@ int ltxk_gemm_w8_plan(const ltxk_gemm_args* args, struct ltxk_gemm_plan* plan);
 int ltxk_gemm_w8a8(const ltxk_gemm_args* args, const float* a_scale, const float* w_scale, void* stream);
 int ltxk_gemm_w8a8_plan(const ltxk_gemm_args* args, struct ltxk_gemm_plan* plan);
 
+/* The weight stream of a decode step: out[m,n] = r(acc * w_scale[n] + bias[n]), acc = A[m,:] . W[n,:] in fp32, for
+ * 1 <= M <= 8 rows.  `args` as for ltxk_gemm_w8 (W: (N,K) e4m3fn bytes, 16-byte aligned; A: (M,K) bf16, 16-byte aligned, lda a
+ * multiple of 8; out (M,N) bf16 with row stride ldo; bias (N) bf16 or NULL; w_scale (N) fp32 or NULL = no multiply) with
+ * K % 16 == 0, any N >= 1, LTXK_EPI_BIAS only, and resid, gate, gate_row, out2, n_split, out_tokens_per_batch, sumsq and
+ * workspace all zero: anything else is LTXK_EINVAL.  One launch (csrc/gemv.hip): W goes from memory straight to registers in
+ * 16-byte loads, the rows of A are staged once per workgroup in LDS, a wave reduces a row of W - per lane fp32 FMAs over its
+ * k in ascending order into an even-k and an odd-k accumulator, their sum, then the wave's butterfly - and applies the scale
+ * and the bias as two fp32 operations.  No atomics, no K slices: the bits of out[m,n] are a function of row m of A, row n of
+ * W, w_scale[n] and bias[n] alone, whatever M, N and the other rows are.  (The summation order differs from the MFMA forms',
+ * so the result equals ltxk_gemm_w8's within the rounding bound, not bit for bit.)                                        */
+int ltxk_gemv_w8(const ltxk_gemm_args* args, const float* w_scale, void* stream);
+
 /* Row quantiser in front of ltxk_gemm_w8a8: x (M,K) bf16 with row stride lda -> q (M,K) e4m3fn bytes with row stride ldq
  * (bytes) and a_scale (M) fp32.  Per row, no special cases: amax = max|x|; scale = max(amax, 2^-64) / 448 in fp32 (correctly
  * rounded); q = e4m3 round-to-nearest-even, saturating, of fp32(x) / scale (IEEE fp32 division).  A zero row gives code 0.
@@ -550,6 +562,13 @@ int ltxk_connector_assemble(const void* feat, int32_t ldf, const void* registers
  * a caller that needs the range checked checks its host copy.                                                          */
 int ltxk_embed_rows(const void* table, int32_t V, int32_t D, const int32_t* ids, void* out, int32_t ldo, int32_t M,
                     float s, void* stream);
+
+/* The same gather over an e4m3fn table (V,D), D % 16 == 0: out[m,:] = r((fp32(code) * row_scale[id]) * s), both products
+ * in fp32 in that order; row_scale (V) fp32 or NULL - then out[m,:] = r(fp32(code) * s), which equals ltxk_embed_rows on the
+ * table converted to bf16 bit for bit.  Gemma-3 ties the output head to this table, so one per-row scale serves the gather
+ * (row = token) and the logits GEMM (row = output channel: its w_scale).                                                 */
+int ltxk_embed_rows_fp8(const void* table, const float* row_scale, int32_t V, int32_t D, const int32_t* ids, void* out,
+                        int32_t ldo, int32_t M, float s, void* stream);
 
 /* Gemma RMSNorm (Gemma3RMSNorm): n = r(x * rsqrt(mean(x^2) + eps) * (1 + w)), w (D) bf16 widened so that 1 + w is formed in
  * fp32.  resid == NULL: y = n.  Otherwise y = r(resid + n), the decoder layer's post-norm-then-add (n is a bf16 tensor in

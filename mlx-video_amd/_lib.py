@@ -136,6 +136,7 @@ SIGNATURES = {
     "ltxk_gemm_bf16": (c_int32, [POINTER(GemmArgs), c_void_p]),
     "ltxk_gemm_plan": (c_int32, [POINTER(GemmArgs), POINTER(GemmPlan)]),
     "ltxk_gemm_w8": (c_int32, [POINTER(GemmArgs), c_void_p, c_void_p]),
+    "ltxk_gemv_w8": (c_int32, [POINTER(GemmArgs), c_void_p, c_void_p]),
     "ltxk_gemm_w8_plan": (c_int32, [POINTER(GemmArgs), POINTER(GemmPlan)]),
     "ltxk_gemm_w8a8": (c_int32, [POINTER(GemmArgs), c_void_p, c_void_p, c_void_p]),
     "ltxk_gemm_w8a8_plan": (c_int32, [POINTER(GemmArgs), POINTER(GemmPlan)]),
@@ -222,6 +223,7 @@ SIGNATURES = {
                                           c_int32, c_int32, c_void_p]),
     # Gemma-3 text encoder (csrc/text_ops.hip, csrc/causal_attn.hip)
     "ltxk_embed_rows": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_float, c_void_p]),
+    "ltxk_embed_rows_fp8": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_float, c_void_p]),
     "ltxk_rmsnorm_weight_rows": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_int32,
                                            c_float, c_void_p]),
     "ltxk_headnorm_rope": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,

@@ -274,6 +274,33 @@ __global__ void embed_rows_kernel(const bf16* __restrict__ table, int V, int D, 
   *(bf16x8*)(out + (size_t)m * ldo + cc) = o;
 }
 
+// The same gather over an e4m3fn table: out[m,:] = bf16((fp32(code) * row_scale[id]) * s), both products fp32 in that order, one
+// rounding to bf16; row_scale == nullptr: bf16(fp32(code) * s), which is embed_rows_kernel on the table widened to bf16 (every
+// e4m3 value is a bf16 value).  A work item is 16 codes: one 16-byte load, v_cvt_pk_f32_fp8, two 16-byte stores.
+__global__ void embed_rows_fp8_kernel(const uint8_t* __restrict__ table, const float* __restrict__ row_scale, int V, int D,
+                                      const int32_t* __restrict__ ids, bf16* __restrict__ out, int ldo, int M, float s) {
+  typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+  typedef float f32x2 __attribute__((ext_vector_type(2)));
+  const int cpr = D >> 4;
+  const int64_t ci = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (ci >= (int64_t)M * cpr) return;
+  const int m = (int)(ci / cpr), cc = (int)(ci - (int64_t)m * cpr) * 16;
+  int id = ids[m];
+  id = id < 0 ? 0 : (id >= V ? V - 1 : id);
+  const u32x4 v = *(const u32x4*)(table + (size_t)id * D + cc);
+  const float rs = row_scale ? row_scale[id] : 1.0f;
+  bf16x8 o[2];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const f32x2 lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)v[j], false), hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)v[j], true);
+    const float f[4] = {lo[0], lo[1], hi[0], hi[1]};
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o[j >> 1][(j & 1) * 4 + e] = (bf16)((row_scale ? f[e] * rs : f[e]) * s);
+  }
+  *(bf16x8*)(out + (size_t)m * ldo + cc) = o[0];
+  *(bf16x8*)(out + (size_t)m * ldo + cc + 8) = o[1];
+}
+
 // Per-head RMSNorm (1 + w) + rotate-half RoPE at head dim 256, in place on the first (Hq + Hkv) heads of a row.  A work item
 // is 8 elements of a head's first half and their 8 rotation partners 128 columns up; a head is 16 items = one aligned group
 // of 16 lanes, which reduces the head's 256 squares itself (16 per lane in ascending order, then the group's butterfly).
@@ -442,6 +469,20 @@ extern "C" int ltxk_embed_rows(const void* table, int32_t V, int32_t D, const in
   hipLaunchKernelGGL(embed_rows_kernel, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const bf16*)table, V, D,
                      ids, (bf16*)out, ldo, M, s);
   LTXK_CHECK_LAUNCH("ltxk_embed_rows");
+  return LTXK_OK;
+}
+
+extern "C" int ltxk_embed_rows_fp8(const void* table, const float* row_scale, int32_t V, int32_t D, const int32_t* ids, void* out,
+                                   int32_t ldo, int32_t M, float s, void* stream) {
+  LTXK_CHECK_ARG(table && ids && out && V > 0 && M > 0 && D > 0, "ltxk_embed_rows_fp8: bad arguments");
+  LTXK_CHECK_ARG(D % 16 == 0, "ltxk_embed_rows_fp8: D=%d must be a multiple of 16", D);
+  LTXK_CHECK_ARG(ldo >= D && ldo % 8 == 0 && aligned16(table) && aligned16(out) && ((uintptr_t)ids & 3) == 0 && ((uintptr_t)row_scale & 3) == 0,
+                 "ltxk_embed_rows_fp8: ldo must be >= D and a multiple of 8, table / out 16-byte aligned, ids / row_scale 4-byte aligned");
+  const int64_t chunks = (int64_t)M * (D / 16);
+  LTXK_CHECK_ARG((chunks + 255) / 256 <= (int64_t)INT32_MAX, "ltxk_embed_rows_fp8: too large");
+  hipLaunchKernelGGL(embed_rows_fp8_kernel, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const uint8_t*)table,
+                     row_scale, V, D, ids, (bf16*)out, ldo, M, s);
+  LTXK_CHECK_LAUNCH("ltxk_embed_rows_fp8");
   return LTXK_OK;
 }
 

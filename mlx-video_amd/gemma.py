@@ -16,6 +16,11 @@ The run stays on the padded (B,T) layout.  Padded rows carry finite values throu
 reads them: attention never admits a key below row_start and writes zeros to query rows below it.  Every GEMM is called with
 ``split_k=False`` and the attention kernel never splits keys, so a batch row's bits do not depend on the batch.
 
+FP8 panels (``GemmaEncoder(..., fp8=)``): the projections and the tied embedding table held as e4m3fn with
+``weights.quantize_fp8``'s per-row scale - half the resident bytes and half the bytes a decoded token streams.  The encoder's
+GEMMs are ltxk_gemm_w8 (fp8 through memory, widened in front of the same MFMAs), the gather is ltxk_embed_rows_fp8; on such an
+encoder the generator's M = B-row GEMMs are ltxk_gemv_w8, one launch each instead of a split-K pair.
+
 Decoding (``GemmaCache``, ``GemmaGenerator``, ``enhance_prompt``): the reference's prompt enhancement (text_encoder.py:1023-1135)
 generates with ``mlx_lm``; here a prefill is the encoder's own layer loop writing K and V^T into a per-layer cache, and a token is
 one pass of M = B-row GEMMs (the weight-streaming split-K form) with the single-position attention step against that cache.
@@ -35,8 +40,10 @@ import torch
 
 from . import ops
 from .text_connector import mask_row_counts
+from .weights import FP8_SCALINGS, SCALE_SUFFIX, quantize_fp8
 
 BF16 = torch.bfloat16
+FP8 = torch.float8_e4m3fn
 HEAD_DIM = 256
 MAX_TOKENS = 1024           # the reference's tokeniser call: max_length 1024, left-padded (text_encoder.py:929-935)
 
@@ -140,17 +147,56 @@ class GemmaEncoder:
     bf16 tensors under the language model's own keys (``embed_tokens.weight``, ``layers.{i}.self_attn.{q,k,v,o}_proj.weight``,
     ``...self_attn.{q,k}_norm.weight``, ``...mlp.{gate,up,down}_proj.weight``, the four layer norms, ``norm.weight``)
     - what ``weights.gemma_weights`` returns.  The q|k|v and gate|up panels are stacked once, here; the dict's own tensors of
-    those are not kept."""
+    those are not kept.
 
-    def __init__(self, weights: Dict[str, torch.Tensor], config: GemmaConfig):
+    ``fp8`` ("channel" / "none", ``weights.FP8_SCALINGS``): q|k|v, o, gate|up, down and the embedding table are kept as e4m3fn
+    with ``quantize_fp8``'s per-row scale ("none": the plain cast, no scale); norm weights stay bf16.  Each matrix is quantised
+    on its own as the panels are built and its entry is REMOVED from ``weights``, so that with no other reference held the bf16
+    source is released before the next one is converted (a full bf16 model and its fp8 copy are never resident together).  A
+    per-row scale belongs to its row alone, so the scales of q, k and v concatenated are the scale of the q|k|v panel.  Matrices
+    that already are e4m3fn (with their ``key + SCALE_SUFFIX`` scale, or none: ``gemma_weights(..., fp8=)``) are taken as they
+    are, with or without ``fp8``.  Gemma-3 ties the output head to the embedding table: its one per-row scale serves the gather
+    (row = token) and the logits GEMM (row = output channel)."""
+
+    def __init__(self, weights: Dict[str, torch.Tensor], config: GemmaConfig, fp8: Optional[str] = None):
         self.cfg = c = config
+        if fp8 is not None and fp8 not in FP8_SCALINGS:
+            raise ValueError(f"GemmaEncoder: fp8={fp8!r}: expected None or one of {FP8_SCALINGS}")
         if "embed_tokens.weight" not in weights:
             raise ValueError("no embed_tokens.weight in the Gemma weights (expected the keys of weights.gemma_weights)")
+        given = weights["embed_tokens.weight"].dtype == FP8
+        self.weight_dtype = FP8 if (fp8 is not None or given) else BF16
+        f8 = self.weight_dtype == FP8
         g = lambda k: weights[k].to(BF16).contiguous()
-        self.embed = g("embed_tokens.weight")
+
+        def mat(*keys):
+            """(panel, per-row fp32 scale or None) of the matrices under ``keys`` stacked along their rows."""
+            if not f8:
+                return (g(keys[0]) if len(keys) == 1 else torch.cat([g(k) for k in keys], 0).contiguous()), None
+            parts = []
+            for k in keys:
+                w = weights.pop(k)
+                if w.dtype == FP8:
+                    sc = weights.pop(k + SCALE_SUFFIX, None)
+                    parts.append((w.contiguous(), None if sc is None else sc.to(torch.float32).contiguous()))
+                elif fp8 is None:
+                    raise ValueError(f"{k} is {w.dtype} beside float8_e4m3fn matrices: pass fp8= to have the rest quantised")
+                else:
+                    parts.append(quantize_fp8(w.to(BF16), fp8))
+                del w
+            scaled = any(sc is not None for _, sc in parts)
+            w8 = parts[0][0] if len(parts) == 1 else torch.cat([w.view(torch.uint8) for w, _ in parts], 0).view(FP8)
+            sc = None
+            if scaled:
+                sc = torch.cat([sc if sc is not None else torch.ones(w.shape[0], dtype=torch.float32, device=w.device) for w, sc in parts], 0)
+            return w8.contiguous(), (None if sc is None else sc.contiguous())
+
+        self.embed, self.embed_row_scale = mat("embed_tokens.weight")
         self.device = self.embed.device
         if tuple(self.embed.shape[1:]) != (c.hidden_size,):
             raise ValueError(f"embed_tokens.weight is {tuple(self.embed.shape)}, the config's hidden size {c.hidden_size}")
+        if f8 and c.hidden_size % 16:
+            raise ValueError(f"GemmaEncoder: fp8 panels need a hidden size that is a multiple of 16, got {c.hidden_size}")
         self.vocab = int(self.embed.shape[0])
         self.norm = g("norm.weight")
         self.embed_scale = float(torch.tensor(c.hidden_size ** 0.5, dtype=BF16))          # text_encoder.py:107
@@ -159,17 +205,24 @@ class GemmaEncoder:
         self.layers = []
         for i in range(c.num_hidden_layers):
             q = f"layers.{i}."
-            qkv = torch.cat([g(q + "self_attn.q_proj.weight"), g(q + "self_attn.k_proj.weight"), g(q + "self_attn.v_proj.weight")], 0)
-            gu = torch.cat([g(q + "mlp.gate_proj.weight"), g(q + "mlp.up_proj.weight")], 0)
+            qkv, qkv_s = mat(q + "self_attn.q_proj.weight", q + "self_attn.k_proj.weight", q + "self_attn.v_proj.weight")
+            gu, gu_s = mat(q + "mlp.gate_proj.weight", q + "mlp.up_proj.weight")
             if tuple(qkv.shape) != (nq + 2 * nkv, c.hidden_size) or tuple(gu.shape) != (2 * c.intermediate_size, c.hidden_size):
                 raise ValueError(f"layer {i}: q|k|v panel {tuple(qkv.shape)} / gate|up panel {tuple(gu.shape)} do not match the config")
+            o, o_s = mat(q + "self_attn.o_proj.weight")
+            down, down_s = mat(q + "mlp.down_proj.weight")
             self.layers.append(dict(
-                qkv=qkv.contiguous(), gu=gu.contiguous(), o=g(q + "self_attn.o_proj.weight"), down=g(q + "mlp.down_proj.weight"),
+                qkv=qkv, gu=gu, o=o, down=down, qkv_s=qkv_s, gu_s=gu_s, o_s=o_s, down_s=down_s,
                 qn=g(q + "self_attn.q_norm.weight"), kn=g(q + "self_attn.k_norm.weight"),
                 n_in=g(q + "input_layernorm.weight"), n_post_attn=g(q + "post_attention_layernorm.weight"),
                 n_pre_ff=g(q + "pre_feedforward_layernorm.weight"), n_post_ff=g(q + "post_feedforward_layernorm.weight"),
                 window=0 if c.is_global(i) else c.sliding_window, is_global=c.is_global(i)))
         self._rope: Dict[Tuple[int, bool], Tuple[torch.Tensor, torch.Tensor]] = {}
+
+    def weight_bytes(self) -> int:
+        """Bytes of every resident weight tensor: panels, their scales, the embedding table and the norm weights."""
+        ts = [self.embed, self.embed_row_scale, self.norm] + [v for ly in self.layers for v in ly.values()]
+        return sum(t.numel() * t.element_size() for t in ts if isinstance(t, torch.Tensor))
 
     def _tables(self, T: int, is_global: bool):
         key = (T, is_global)
@@ -201,7 +254,7 @@ class GemmaEncoder:
         row_start = torch.tensor([T - n for n in counts], dtype=torch.int32, device=dev)
         L = c.num_hidden_layers
         states = torch.empty((L + 1, B, T, D), dtype=BF16, device=dev)
-        x = ops.embed_rows(self.embed, ids, self.embed_scale, out=states[0].view(M, D), ids_host=ids_host)
+        x = ops.embed_rows(self.embed, ids, self.embed_scale, out=states[0].view(M, D), ids_host=ids_host, row_scale=self.embed_row_scale)
         nx = torch.empty((M, D), dtype=BF16, device=dev)
         qk = torch.empty((M, nq + nkv), dtype=BF16, device=dev)
         tpad = (T + 63) // 64 * 64
@@ -216,19 +269,19 @@ class GemmaEncoder:
             if cache is not None:
                 vt = cache.vt[i]
             ops.rmsnorm_weight_rows(x, ly["n_in"], c.rms_norm_eps, out=nx)
-            ops.gemm(nx, ly["qkv"], None, out=qk, out2=vt, n_split=nq + nkv, out_tokens_per_batch=T, split_k=False)
+            ops.gemm(nx, ly["qkv"], None, out=qk, out2=vt, n_split=nq + nkv, out_tokens_per_batch=T, split_k=False, w_scale=ly["qkv_s"])
             ops.headnorm_rope(qk, Hq, Hkv, ly["qn"], ly["kn"], cos, sin, T, c.rms_norm_eps)
             if cache is not None:
                 cache.k[i][:, :T].copy_(qk.view(B, T, nq + nkv)[:, :, nq:])
             ops.causal_attn(qk[:, :nq], qk[:, nq:], vt, att, row_start, B, Hq, Hkv, T, self.scale, window=ly["window"])
-            ops.gemm(att, ly["o"], None, out=po, split_k=False)
+            ops.gemm(att, ly["o"], None, out=po, split_k=False, w_scale=ly["o_s"])
             # the layer's output goes straight into its slot of the stack (the last layer's into scratch: its slot takes norm(h_L))
             y = states[i + 1].view(M, D) if i + 1 < L else nx.new_empty((M, D))
             ops.rmsnorm_weight_rows(po, ly["n_post_attn"], c.rms_norm_eps, resid=x, out=y)
             ops.rmsnorm_weight_rows(y, ly["n_pre_ff"], c.rms_norm_eps, out=nx)
-            ops.gemm(nx, ly["gu"], None, out=gu, split_k=False)
+            ops.gemm(nx, ly["gu"], None, out=gu, split_k=False, w_scale=ly["gu_s"])
             h = ops.geglu_tanh_(gu)
-            ops.gemm(h, ly["down"], None, out=po, split_k=False)
+            ops.gemm(h, ly["down"], None, out=po, split_k=False, w_scale=ly["down_s"])
             ops.rmsnorm_weight_rows(po, ly["n_post_ff"], c.rms_norm_eps, resid=y, out=y)
             x = y
         ops.rmsnorm_weight_rows(x, self.norm, c.rms_norm_eps, out=states[L].view(M, D))
@@ -288,9 +341,16 @@ class GemmaGenerator:
     the input norm, one q|k|v GEMM at M = B rows in the weight-streaming split-K form, norm + RoPE with the table row of the
     token's position, the attention step against the cache (which appends the token's K and V), o-proj, norms, gate|up, GeGLU,
     down; then the final norm and the logits GEMM over the embedding table.  Positions are padded-sequence indices, the
-    encoder's convention."""
+    encoder's convention.
 
-    def __init__(self, encoder: GemmaEncoder):
+    On an fp8 encoder with B <= ``ops.GEMV_MAX_M`` the GEMMs of ``GEMV_SHAPES`` run as ltxk_gemv_w8 (``ops.gemm(gemv=True)``): one
+    launch that streams the e4m3 panel straight to registers, and a batch row's bits then do not depend on B.  ``gemv=False``
+    keeps every one of them on the split-K ltxk_gemm_w8 (the measurement's other arm); a bf16 encoder's step is unchanged."""
+
+    # which of the step's five GEMMs take the row-streaming kernel on fp8 panels (DESIGN.md 5p: decided per shape by measurement)
+    GEMV_SHAPES = {"qkv": True, "o": True, "gu": True, "down": True, "logits": True}
+
+    def __init__(self, encoder: GemmaEncoder, gemv: bool = True):
         if encoder.cfg.final_logit_softcapping is not None:
             raise ValueError(f"GemmaGenerator: final_logit_softcapping={encoder.cfg.final_logit_softcapping}: logit soft-capping is not supported")
         if encoder.cfg.num_attention_heads // encoder.cfg.num_key_value_heads > 16:
@@ -298,9 +358,16 @@ class GemmaGenerator:
         if encoder.vocab % 8:
             raise ValueError(f"GemmaGenerator: the vocabulary {encoder.vocab} must be a multiple of 8 (the logits GEMM)")
         self.enc, self.cfg = encoder, encoder.cfg
+        self.gemv = bool(gemv) and encoder.weight_dtype == FP8
+
+    def _gemm(self, which: str, a: torch.Tensor, w: torch.Tensor, w_scale: Optional[torch.Tensor], out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """One M = B-row GEMM of a step: ltxk_gemv_w8 where the shape is routed there, else the weight-streaming split-K form."""
+        if self.gemv and self.GEMV_SHAPES[which] and a.shape[0] <= ops.GEMV_MAX_M and a.shape[1] % 16 == 0:
+            return ops.gemm(a, w, None, out=out, w_scale=w_scale, gemv=True)
+        return ops.gemm(a, w, None, out=out, split_k=True, w_scale=w_scale)
 
     def _logits(self, h: torch.Tensor) -> torch.Tensor:
-        return ops.gemm(h, self.enc.embed, None).to(torch.float32)
+        return self._gemm("logits", h, self.enc.embed, self.enc.embed_row_scale).to(torch.float32)
 
     def prefill(self, input_ids: torch.Tensor, attention_mask: torch.Tensor, capacity: int, return_states: bool = False):
         """(cache, logits (B,V) fp32 of the last position) for a left-padded (B,T) prompt, T <= capacity (a multiple of 64);
@@ -329,7 +396,8 @@ class GemmaGenerator:
         Hq, Hkv = c.num_attention_heads, c.num_key_value_heads
         nq, nkv = Hq * HEAD_DIM, Hkv * HEAD_DIM
         states = torch.empty((L + 1, B, D), dtype=BF16, device=dev)
-        x = ops.embed_rows(e.embed, ids_host.to(torch.int32).to(dev), e.embed_scale, out=states[0], ids_host=ids_host)
+        x = ops.embed_rows(e.embed, ids_host.to(torch.int32).to(dev), e.embed_scale, out=states[0], ids_host=ids_host,
+                           row_scale=e.embed_row_scale)
         nx = torch.empty((B, D), dtype=BF16, device=dev)
         qkv = torch.empty((B, nq + 2 * nkv), dtype=BF16, device=dev)
         att = torch.empty((B, nq), dtype=BF16, device=dev)
@@ -338,17 +406,17 @@ class GemmaGenerator:
         for i, ly in enumerate(e.layers):
             cos, sin = e._tables(cap, ly["is_global"])
             ops.rmsnorm_weight_rows(x, ly["n_in"], c.rms_norm_eps, out=nx)
-            ops.gemm(nx, ly["qkv"], None, out=qkv, split_k=True)
+            self._gemm("qkv", nx, ly["qkv"], ly["qkv_s"], qkv)
             ops.headnorm_rope(qkv, Hq, Hkv, ly["qn"], ly["kn"], cos[pos:pos + 1], sin[pos:pos + 1], 1, c.rms_norm_eps)
             ops.causal_attn(qkv[:, :nq], cache.k[i].view(B * cap, nkv), cache.vt[i], att, cache.row_start, B, Hq, Hkv, cap, e.scale,
                             window=ly["window"], step=pos, k_new=qkv[:, nq:nq + nkv], v_new=qkv[:, nq + nkv:], partials=cache.partials)
-            ops.gemm(att, ly["o"], None, out=po, split_k=True)
+            self._gemm("o", att, ly["o"], ly["o_s"], po)
             y = states[i + 1] if i + 1 < L else nx.new_empty((B, D))
             ops.rmsnorm_weight_rows(po, ly["n_post_attn"], c.rms_norm_eps, resid=x, out=y)
             ops.rmsnorm_weight_rows(y, ly["n_pre_ff"], c.rms_norm_eps, out=nx)
-            ops.gemm(nx, ly["gu"], None, out=gu, split_k=True)
+            self._gemm("gu", nx, ly["gu"], ly["gu_s"], gu)
             h = ops.geglu_tanh_(gu)
-            ops.gemm(h, ly["down"], None, out=po, split_k=True)
+            self._gemm("down", h, ly["down"], ly["down_s"], po)
             ops.rmsnorm_weight_rows(po, ly["n_post_ff"], c.rms_norm_eps, resid=y, out=y)
             x = y
         ops.rmsnorm_weight_rows(x, e.norm, c.rms_norm_eps, out=states[L])

@@ -220,13 +220,13 @@ def _as_tokens(tokens, what: str):
     return ids, mask
 
 
-def _encode_gemma(gemma, gemma_repo, tokenizer_path, prompt, negative_prompt, prompt_tokens, negative_prompt_tokens, dev):
+def _encode_gemma(gemma, gemma_repo, tokenizer_path, prompt, negative_prompt, prompt_tokens, negative_prompt_tokens, dev, fp8=None):
     """(hidden states (L+1,2,T,D), mask (2,T)) of the positive and the negative prompt: tokens -> GemmaEncoder as ONE B = 2 call.
     Tokens are taken as given, or made from the prompt strings with the tokenizer.json of ``tokenizer_path`` / ``gemma_repo``."""
     from .gemma import GemmaConfig, GemmaEncoder, load_tokenizer, tokenize
     if gemma is None:
         from .weights import gemma_weights
-        gemma = GemmaEncoder(gemma_weights(gemma_repo, dev), GemmaConfig.from_json(gemma_repo))
+        gemma = GemmaEncoder(gemma_weights(gemma_repo, dev, fp8=fp8), GemmaConfig.from_json(gemma_repo), fp8=fp8)
     if prompt_tokens is None or negative_prompt_tokens is None:
         where = tokenizer_path or gemma_repo
         if where is None:
@@ -258,13 +258,13 @@ def _check_enhance(gemma, gemma_repo, text_encoder_repo, tokenizer_path, prompt_
         raise ValueError(f"enhance_prompt (--enhance-prompt) rewrites the prompt string, which {', '.join(given)} replaces: drop one of the two")
 
 
-def _enhance_prompt(gemma, gemma_repo, tokenizer_path, prompt, system_prompt, max_tokens, temperature, seed, dev, verbose):
+def _enhance_prompt(gemma, gemma_repo, tokenizer_path, prompt, system_prompt, max_tokens, temperature, seed, dev, verbose, fp8=None):
     """(the GemmaEncoder, the enhanced prompt): the encoder is built here when only ``gemma_repo`` was given, and handed on so that
     the text encode that follows reuses its panels."""
     from .gemma import GemmaConfig, GemmaEncoder, GemmaGenerator, enhance_prompt, load_tokenizer
     if gemma is None:
         from .weights import gemma_weights
-        gemma = GemmaEncoder(gemma_weights(gemma_repo, dev), GemmaConfig.from_json(gemma_repo))
+        gemma = GemmaEncoder(gemma_weights(gemma_repo, dev, fp8=fp8), GemmaConfig.from_json(gemma_repo), fp8=fp8)
     tok = load_tokenizer(tokenizer_path or gemma_repo)
     enhanced = enhance_prompt(GemmaGenerator(gemma), tok, prompt, system_prompt, max_tokens=max_tokens, temperature=temperature, seed=seed)
     if verbose:
@@ -304,7 +304,7 @@ def generate_video(model_repo: Optional[str] = None, text_encoder_repo: Optional
                    audio_decoder=None, vocoder=None, output_audio: Optional[str] = None, audio_mode: str = "auto",
                    audio_model_repo: Optional[str] = None, audio_steps: int = 8, audio_transformer: Optional[LTXModel] = None,
                    audio_prompt_embeds: Optional[torch.Tensor] = None, av_transformer=None,
-                   audio_negative_prompt_embeds: Optional[torch.Tensor] = None) -> np.ndarray:
+                   audio_negative_prompt_embeds: Optional[torch.Tensor] = None, fp8_text_encoder: bool = False) -> np.ndarray:
     """See the module docstring.  Returns uint8 frames (F,H,W,3) (generate.py:4195-4197).
     ``hoist_context`` (not in the reference, off by default): the part of the forward that depends on the text context only -
     caption projection and the 48 cross-attention K / V^T projections, 3.37 TFLOP that the reference recomputes in every forward
@@ -320,6 +320,11 @@ def generate_video(model_repo: Optional[str] = None, text_encoder_repo: Optional
     model.  A ``transformer=`` / ``stage2_transformer=`` passed in is used as it is.
     ``fp8_activations`` (--fp8-activations; needs ``enable_fp8``, a ValueError without it): the transformers this call builds also
     quantise the inputs of their in-block Linear layers to e4m3 per row and multiply fp8 x fp8 (ltxk_gemm_w8a8).
+    ``fp8_text_encoder`` (--fp8-text-encoder): the Gemma-3 encoder this call builds from ``gemma_repo`` keeps its projections and
+    its embedding table as e4m3 panels (``GemmaEncoder(fp8=fp8_scaling)``) - half the resident bytes, and half the
+    bytes a decoded token of ``enhance_prompt`` streams; the one encoder serves the text encode and the enhancement.  It needs
+    ``gemma_repo``; with a passed ``gemma=`` that holds bf16 panels it is a ValueError (drop one of the two; an fp8 ``gemma=`` is
+    taken as it is).  ``enable_fp8`` alone keeps meaning the transformer only.
     ``gemma_hidden_states`` / ``gemma_attention_mask`` (and the ``negative_`` pair): the text route that starts behind Gemma -
     the L hidden states of a Gemma-3 forward ((L,1,T,D) stack or list of L (1,T,D)) and its left-padded 0/1 mask (1,T); the
     feature extractor and the video embeddings connector run here (``text_connector=`` a ``TextConnector``, or loaded from
@@ -433,6 +438,15 @@ def generate_video(model_repo: Optional[str] = None, text_encoder_repo: Optional
         raise ValueError(f"Unknown fp8_scaling: {fp8_scaling!r} (expected one of {FP8_SCALINGS})")
     if fp8_activations and not enable_fp8:
         raise ValueError("fp8_activations (--fp8-activations) needs enable_fp8 (--enable-fp8): fp8 activations multiply fp8 weight panels")
+    if fp8_text_encoder:
+        if gemma is not None and gemma.weight_dtype == BF16:
+            raise ValueError("fp8_text_encoder (--fp8-text-encoder) with a gemma= encoder that holds bf16 panels: drop fp8_text_encoder to "
+                             "run that encoder, or drop gemma= and pass gemma_repo= to have an fp8 one built "
+                             "(or build it yourself: GemmaEncoder(weights, config, fp8=...))")
+        if gemma is None and gemma_repo is None and not (text_encoder_repo and Path(text_encoder_repo).is_dir()):
+            raise ValueError("fp8_text_encoder (--fp8-text-encoder) needs a Gemma-3 model to build: gemma_repo= (a local Gemma-3 "
+                             "directory, --gemma-repo)")
+    gemma_fp8 = {"fp8": fp8_scaling} if fp8_text_encoder else {}          # (off adds no keyword: today's calls)
 
     def _build(cfg_, weights_) -> LTXModel:
         """A transformer from a module-key weight dict; under enable_fp8 from its quantised twin (an fp8 dict is kept as it is)."""
@@ -522,9 +536,10 @@ def generate_video(model_repo: Optional[str] = None, text_encoder_repo: Optional
     if enhance_prompt:
         with timer.phase("prompt_enhance"):
             gemma, prompt = _enhance_prompt(gemma, gemma_repo, tokenizer_path, prompt, enhance_system_prompt, max_tokens, temperature,
-                                            seed, dev, verbose)
+                                            seed, dev, verbose, **gemma_fp8)
     if prompt_embeds is None and text_encoder is None and (gemma is not None or gemma_repo is not None):
-        hs, m = _encode_gemma(gemma, gemma_repo, tokenizer_path, prompt, negative_prompt, prompt_tokens, negative_prompt_tokens, dev)
+        hs, m = _encode_gemma(gemma, gemma_repo, tokenizer_path, prompt, negative_prompt, prompt_tokens, negative_prompt_tokens, dev,
+                              **gemma_fp8)
         want = gen_audio and audio_prompt_embeds is None
         got = _connect_gemma(hs[:, 0:1], m[0:1], hs[:, 1:2], m[1:2], text_connector, model_repo, dev, **({"want_audio": True} if want else {}))
         prompt_embeds, negative_prompt_embeds = got[0], got[1]
@@ -875,6 +890,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--fp8-activations", action="store_true", default=False,
                     help="(not in the reference CLI; needs --enable-fp8) quantise the in-block Linear inputs to FP8 per row and "
                          "multiply on the fp8 matrix pipe")
+    ap.add_argument("--fp8-text-encoder", action="store_true", default=False,
+                    help="(not in the reference CLI; needs --gemma-repo) keep Gemma-3's projections and embedding table as FP8 (e4m3) "
+                         "panels, scaled as --fp8-scaling says: the text encode and --enhance-prompt run on them")
     return ap
 
 
@@ -948,6 +966,8 @@ def main(argv: Optional[Sequence[str]] = None) -> None:
     args = resolve_cli_heuristics(build_parser().parse_args(argv))
     if args.fp8_activations and not args.enable_fp8:
         raise ValueError("--fp8-activations needs --enable-fp8: fp8 activations multiply fp8 weight panels")
+    if args.fp8_text_encoder and not args.gemma_repo:
+        raise ValueError("--fp8-text-encoder needs --gemma-repo: it is the Gemma-3 model built from that directory that keeps fp8 panels")
     is_dev = args.pipeline == "dev"
     dev = torch.device("cuda:0")
     kw = {}
@@ -1028,7 +1048,8 @@ def main(argv: Optional[Sequence[str]] = None) -> None:
                    conditioning_mode=args.conditioning_mode, stream=args.stream, stage2_dev=args.stage2_dev,
                    fp32_euler=args.fp32_euler, stg_scale=args.stg_scale, stg_blocks=args.stg_blocks, stg_mode=args.stg_mode,
                    enable_fp8=args.enable_fp8, fp8_scaling=args.fp8_scaling, fp8_activations=args.fp8_activations,
-                   guider=args.guider, apg_eta=args.apg_eta, apg_norm_threshold=args.apg_norm_threshold, **kw)
+                   guider=args.guider, apg_eta=args.apg_eta, apg_norm_threshold=args.apg_norm_threshold,
+                   **({"fp8_text_encoder": True} if args.fp8_text_encoder else {}), **kw)
 
 
 if __name__ == "__main__":

@@ -180,7 +180,7 @@ def gemm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], *, epil
          gate_stride: int = 0, out_tokens_per_batch: int = 0, alpha: float = 1.0,
          out2: Optional[torch.Tensor] = None, n_split: int = 0, sumsq: Optional[torch.Tensor] = None,
          split_k: bool = True, w_scale: Optional[torch.Tensor] = None,
-         a_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
+         a_scale: Optional[torch.Tensor] = None, gemv: bool = False) -> torch.Tensor:
     """out = epi(a @ w.T + bias).  a (M,K) (row stride may exceed K), w (N,K) contiguous, bias (N); out / resid (M,N) rows,
     gate (rows,N) read as gate[gate_row[m] * gate_stride + n] with gate_row (M) int32.
     ``w`` may be ``torch.float8_e4m3fn`` (ltxk_gemm_w8: the panel is read as fp8 and widened in registers; with no ``w_scale``
@@ -193,7 +193,13 @@ def gemm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], *, epil
     at M <= SPLITK_MAX_M (``gemm_plan`` tells).
     A ``float8_e4m3fn`` ``a`` together with ``a_scale`` (M) fp32 - what ``quant_rows_fp8`` returns - takes ltxk_gemm_w8a8: fp8
     operands on the fp8 matrix pipe, acc * a_scale[m] * w_scale[n] in front of the bias.  It needs an fp8 ``w``, K % 128 == 0
-    and 16-byte aligned rows of ``a``; it is always single-pass (``split_k`` is ignored)."""
+    and 16-byte aligned rows of ``a``; it is always single-pass (``split_k`` is ignored).
+    ``gemv=True`` takes ltxk_gemv_w8, the weight stream of a decode step: a float8_e4m3fn ``w``, M <= GEMV_MAX_M rows,
+    K % 16 == 0, any N, EPI_BIAS with or without ``bias`` / ``w_scale``, and none of the other outputs or operands.  One launch,
+    no workspace (``split_k`` is ignored); a row's bits depend on that row, the panel row, its scale and its bias alone."""
+    if gemv:
+        return _gemv(a, w, bias, epilogue, out, w_scale, resid=resid, gate=gate, gate_row=gate_row, out2=out2, sumsq=sumsq,
+                     a_scale=a_scale, n_split=n_split, out_tokens_per_batch=out_tokens_per_batch)
     w8 = w.dtype == FP8
     a8 = a.dtype == FP8
     if a8 != (a_scale is not None):
@@ -245,6 +251,39 @@ def gemm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], *, epil
         return out
     with _timed("gemm_bf16", 2.0 * M * N * K, 2.0 * (M * K + N * K + M * N)):
         check(_lib.load().ltxk_gemm_bf16(ctypes.byref(args), _stream()), "ltxk_gemm_bf16")
+    return out
+
+
+GEMV_MAX_M = 8              # rows of one ltxk_gemv_w8 launch (csrc/gemv.hip)
+
+
+def _gemv(a, w, bias, epilogue, out, w_scale, **unsupported) -> torch.Tensor:
+    """``gemm(..., gemv=True)``: ltxk_gemv_w8."""
+    if w.dtype != FP8:
+        raise TypeError(f"gemm: gemv=True needs a float8_e4m3fn `w`, got {w.dtype}")
+    for name, v in unsupported.items():
+        if isinstance(v, torch.Tensor) or v:
+            raise ValueError(f"gemm: gemv=True takes no `{name}`")
+    if epilogue != EPI_BIAS:
+        raise ValueError(f"gemm: gemv=True has the `epilogue` EPI_BIAS only, got {epilogue}")
+    M, K = _dims("gemm", "a", a, BF16, 2)
+    N = _dims("gemm", "w", w, FP8, 2)[0]
+    if not 1 <= M <= GEMV_MAX_M:
+        raise ValueError(f"gemm: gemv=True takes `a` of 1 to {GEMV_MAX_M} rows, got {M}")
+    if K % 16:
+        raise ValueError(f"gemm: gemv=True needs `a` and `w` of K % 16 == 0, got K = {K}")
+    if a.stride(0) % 8:
+        raise ValueError(f"gemm: the rows of `a` must lie a multiple of 8 elements apart for gemv=True, got {a.stride(0)}")
+    _operands("gemm", ("a", a, BF16, 2, 16, True), ("w", w, FP8, (N, K), 16), ("bias", bias, BF16, (N,), 2),
+              ("out", out, BF16, (M, N), 2, True), ("w_scale", w_scale, F32, (N,), 4))
+    if out is None:
+        out = torch.empty((M, N), dtype=BF16, device=a.device)
+    args = GemmArgs()
+    args.A, args.W, args.bias, args.out = _p(a), _p(w), _p(bias), _p(out)
+    args.M, args.N, args.K, args.lda, args.ldo = M, N, K, a.stride(0), out.stride(0)
+    args.epilogue, args.alpha = EPI_BIAS, 1.0
+    with _timed("gemv_w8", 2.0 * M * N * K, 2.0 * (M * K + M * N) + 1.0 * N * K):
+        check(_lib.load().ltxk_gemv_w8(ctypes.byref(args), _p(w_scale), _stream()), "ltxk_gemv_w8")
     return out
 
 
@@ -896,13 +935,22 @@ CAUSAL_ATTN_BK = 64          # keys per tile
 
 
 def embed_rows(table: torch.Tensor, ids: torch.Tensor, scale: float, out: Optional[torch.Tensor] = None,
-               ids_host: Optional[torch.Tensor] = None) -> torch.Tensor:
+               ids_host: Optional[torch.Tensor] = None, row_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
     """ltxk_embed_rows: out[m,:] = bf16(table[ids[m],:] * scale).  table (V,D) contiguous bf16, ids (M) int32 on the device.
     The kernel cannot raise for device data, so the id range is validated here on ``ids_host``, the host copy the caller
-    tokenised (without one, ``ids`` is copied back once - a synchronisation, once per prompt)."""
-    V, D = _dims("embed_rows", "table", table, BF16, 2)
+    tokenised (without one, ``ids`` is copied back once - a synchronisation, once per prompt).
+    A ``float8_e4m3fn`` table (D % 16 == 0) takes ltxk_embed_rows_fp8: out[m,:] = bf16((table[ids[m],:] * row_scale[ids[m]]) *
+    scale) with ``row_scale`` (V) fp32, or bf16(table[ids[m],:] * scale) without one - the bf16 call on the widened table."""
+    f8 = table.dtype == FP8
+    if row_scale is not None and not f8:
+        raise TypeError("embed_rows: row_scale goes with a float8_e4m3fn table")
+    tdt = FP8 if f8 else BF16
+    V, D = _dims("embed_rows", "table", table, tdt, 2)
     M = _dims("embed_rows", "ids", ids, I32, 1)[0]
-    _operands("embed_rows", ("table", table, BF16, 2, 16), ("ids", ids, I32, 1, 4), ("out", out, BF16, (M, D), 16, True))
+    if f8 and D % 16:
+        raise ValueError(f"embed_rows: a float8_e4m3fn table must have rows of a multiple of 16 elements, got {D}")
+    _operands("embed_rows", ("table", table, tdt, 2, 16), ("ids", ids, I32, 1, 4), ("out", out, BF16, (M, D), 16, True),
+              ("row_scale", row_scale, F32, (V,), 4))
     host = ids.cpu() if ids_host is None else ids_host.reshape(-1)
     if host.numel() != M:
         raise ValueError(f"embed_rows: ids_host holds {host.numel()} ids, ids {M}")
@@ -910,6 +958,11 @@ def embed_rows(table: torch.Tensor, ids: torch.Tensor, scale: float, out: Option
         raise ValueError(f"embed_rows: token ids must lie in [0, {V}), got [{int(host.min())}, {int(host.max())}]")
     if out is None:
         out = torch.empty((M, D), dtype=BF16, device=table.device)
+    if f8:
+        with _timed("embed_rows_fp8", 0.0, 3.0 * M * D):
+            check(_lib.load().ltxk_embed_rows_fp8(_p(table), _p(row_scale), V, D, _p(ids), _p(out), out.stride(0), M, scale, _stream()),
+                  "ltxk_embed_rows_fp8")
+        return out
     with _timed("embed_rows", 0.0, 4.0 * M * D):
         check(_lib.load().ltxk_embed_rows(_p(table), V, D, _p(ids), _p(out), out.stride(0), M, scale, _stream()), "ltxk_embed_rows")
     return out

@@ -546,10 +546,18 @@ def gemma_key(raw_key: str) -> Optional[str]:
     return None
 
 
-def gemma_weights(root, device) -> Dict[str, torch.Tensor]:
+def gemma_weights(root, device, fp8: Optional[str] = None, fp8_scaling: str = "channel") -> Dict[str, torch.Tensor]:
     """The Gemma-3 language model of a local directory as device bf16 tensors under its own keys, for ``gemma.GemmaEncoder``.
     Streams the shards of ``gemma_shard_files`` one tensor at a time; fp32 tensors are cast to bf16 (text_encoder.py:154-163),
-    vision-tower keys skipped.  A pre-quantised checkpoint (.scales / .biases) raises, as the DiT loader does."""
+    vision-tower keys skipped.  A pre-quantised checkpoint (.scales / .biases) raises, as the DiT loader does.
+    ``fp8`` (one of FP8_SCALINGS, or True for ``fp8_scaling``): the matrices - the projections and the embedding table - come
+    back as e4m3fn with ``key + SCALE_SUFFIX`` scales under "channel", each quantised as it streams (``_put_transformer_tensor``:
+    no bf16 copy of the model is ever resident); an F8_E4M3 tensor of the checkpoint is kept as it is, unscaled.  Norm weights
+    stay bf16."""
+    if fp8 is True:
+        fp8 = fp8_scaling
+    if fp8 is not None and fp8 is not False and fp8 not in FP8_SCALINGS:
+        raise ValueError(f"fp8 scaling {fp8!r}: expected one of {FP8_SCALINGS}")
     root = Path(root)
     if not root.is_dir():
         raise FileNotFoundError(f"{root} is not a local directory (repo names are not resolved and nothing is fetched)")
@@ -564,7 +572,10 @@ def gemma_weights(root, device) -> Dict[str, torch.Tensor]:
     for k, v in iter_safetensors(files, want=lambda k: gemma_key(k) is not None):
         if not v.dtype.is_floating_point:
             raise ValueError(f"{k}: expected a floating-point tensor, got {v.dtype}")
-        out[gemma_key(k)] = _to_dev(v, device)
+        if fp8:
+            _put_transformer_tensor(out, gemma_key(k), v, device, True, fp8)
+        else:
+            out[gemma_key(k)] = _to_dev(v, device)
     if "embed_tokens.weight" not in out:
         raise ValueError(f"no language-model tensors (…embed_tokens.weight) in {', '.join(f.name for f in files)}")
     return out
