@@ -651,6 +651,71 @@ int ltxk_causal_attn_step(const void* q, int32_t ldq, const void* k_new, int32_t
                           const int32_t* row_start, int32_t B, int32_t Hq, int32_t Hkv, int32_t cap, int32_t step,
                           int32_t window, float scale, float* partials, int64_t partials_floats, void* stream);
 
+/* The same step with its position in DEVICE memory, so that a decode step can be recorded once and replayed: the kernel body of
+ * ltxk_causal_attn_step (one template), `step` read from *step.  s0, the slice count and the partials' indexing are derived
+ * inside the kernel from *step; the grid is sized on the host for max_step (0 <= max_step < cap): min(max_step/256 + 1,
+ * (window + 254)/256 + 1) slices under a window - the slices a window can never reach are not launched - else max_step/256 + 1.
+ * A workgroup whose slice is past the step's own count leaves before any load or store (a block-uniform exit ahead of the
+ * barrier), and the combine launch loops to the device count.  *step outside [0, max_step]: nothing is loaded from or stored
+ * to the cache or partials, and out is left as it was.  For *step == step the bits of out, of the appended K row and V^T
+ * column and of the live partials equal ltxk_causal_attn_step's, whatever max_step >= step is.
+ * partials: >= B * Hq * (that slice count) * 258 floats.                                                                */
+int ltxk_causal_attn_dev_step(const void* q, int32_t ldq, const void* k_new, int32_t ldkn, const void* v_new, int32_t ldvn,
+                              void* k_cache, int32_t ldk, void* vt_cache, int32_t ldvt, void* out, int32_t ldo,
+                              const int32_t* row_start, int32_t B, int32_t Hq, int32_t Hkv, int32_t cap, const int32_t* step,
+                              int32_t max_step, int32_t window, float scale, float* partials, int64_t partials_floats,
+                              void* stream);
+
+/* ltxk_headnorm_rope for rows that all sit at ONE position held in device memory: every one of the M rows takes table row
+ * *pos of cos / sin (T,128).  The bits equal ltxk_headnorm_rope on the tables' row *pos with T = 1 (the rotation is the one
+ * definition both share).  *pos outside [0, T): no store.                                                               */
+int ltxk_headnorm_rope_at(void* buf, int32_t ld, int32_t M, int32_t Hq, int32_t Hkv, const void* q_weight, const void* k_weight,
+                          const float* cos, const float* sin, int32_t T, const int32_t* pos, float eps, void* stream);
+
+/* Gemma-3 decoding: sampling on the device.  One token per row of the logits GEMM's own output, logits (B,V) bf16 row stride
+ * ld, 1 <= B <= 8, V % 8 == 0, widened to fp32 in registers (no fp32 copy is made), against a caller-owned decode state, all
+ * DEVICE int32 unless noted:
+ *   ctl = {n, pos, live}: the draw index, the cache position at which the token drawn now will be fed, the rows not finished;
+ *   done (B), next_ids (B), history (B,hist_cap) with hist_len (B), tokens_out (B,n_max), eos (n_eos <= 8),
+ *   uniforms (n_max,B) fp32 in [0,1).
+ * Per row b, n = ctl[0]:
+ *   penalty     ctx = the last min(rep_ctx, hist_len[b]) ids of history[b] (rep_ctx <= 64), as a SET: for v in ctx
+ *               l'_v = l_v < 0 ? l_v * penalty : l_v / penalty in fp32 (IEEE multiply, correctly rounded divide); every other
+ *               l'_v = l_v.  penalty == 1 or an empty ctx touches nothing.
+ *   choice      temperature == 0: t = the smallest v with l'_v = max l'.  Otherwise z_v = l'_v / temperature, m = max z,
+ *               p_v = exp(z_v - m), S = sum p, target = uniforms[n,b] * S, t = the smallest v with p_v > 0 whose inclusive
+ *               prefix sum exceeds target; if rounding leaves none, the largest v with p_v > 0.  Sums run over chunks of 2048
+ *               elements (a function of V only) merged in ascending order; the longest sequential fp32 addition chain is
+ *               17 + ceil(V/2048).  t is a function of the row's logits, ctx, temperature, penalty and uniform alone.
+ *   bookkeeping done[b]: tokens_out[b,n] = -1, next_ids[b] and history[b] stay (a finished row keeps feeding its last token).
+ *               Otherwise tokens_out[b,n] = next_ids[b] = t, history[b,hist_len[b]++] = t (dropped once hist_cap is full),
+ *               done[b] = t in eos.
+ * flags: LTXK_SAMPLE_DRAW runs the above; LTXK_SAMPLE_ADVANCE sets ctl = {n + 1, pos + 1, rows not done} in a launch of its
+ * own, which must follow every reader of the old value - a decode step draws first, feeds the token at ctl's pos and
+ * advances last; both flags: a draw followed at once by the advance.  n outside [0, n_max): no store anywhere.
+ * No atomics and no workgroup waits on another: chunk partials (maximum and argmax, then sums) are merged by later launches.
+ * workspace: >= 3 * B * ceil(V/2048) * 4 bytes, 4-byte aligned.  struct_bytes = sizeof(ltxk_sample_args), checked.       */
+enum { LTXK_SAMPLE_DRAW = 1, LTXK_SAMPLE_ADVANCE = 2 };
+
+typedef struct {
+  int32_t struct_bytes;
+  int32_t B, V, ld, n_max, hist_cap, rep_ctx, n_eos, flags;
+  float temperature, penalty;
+  const void* logits;
+  int32_t* ctl;
+  int32_t* done;
+  int32_t* next_ids;
+  int32_t* history;
+  int32_t* hist_len;
+  int32_t* tokens_out;
+  const int32_t* eos;
+  const float* uniforms;
+  void* workspace;
+  int64_t workspace_bytes;
+} ltxk_sample_args;
+
+int ltxk_sample_rows(const ltxk_sample_args* args, void* stream);
+
 /* ---------------------------------------------------------------------------------------
  * Video VAE (volumes are channels-last (B,D,H,W,C) bf16; a row = one voxel)
  * ------------------------------------------------------------------------------------- */

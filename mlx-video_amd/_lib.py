@@ -128,6 +128,18 @@ class CausalAttnArgs(Structure):
     ]
 
 
+class SampleArgs(Structure):
+    _fields_ = [
+        ("struct_bytes", c_int32),
+        ("B", c_int32), ("V", c_int32), ("ld", c_int32), ("n_max", c_int32), ("hist_cap", c_int32), ("rep_ctx", c_int32),
+        ("n_eos", c_int32), ("flags", c_int32),
+        ("temperature", c_float), ("penalty", c_float),
+        ("logits", c_void_p), ("ctl", c_void_p), ("done", c_void_p), ("next_ids", c_void_p), ("history", c_void_p),
+        ("hist_len", c_void_p), ("tokens_out", c_void_p), ("eos", c_void_p), ("uniforms", c_void_p),
+        ("workspace", c_void_p), ("workspace_bytes", c_int64),
+    ]
+
+
 # name -> (restype, argtypes); mirrors include/ltxk.h one to one.
 SIGNATURES = {
     "ltxk_version": (c_int32, []),
@@ -234,6 +246,13 @@ SIGNATURES = {
     # Gemma-3 decoding (csrc/causal_attn_step.hip)
     "ltxk_causal_attn_step": (c_int32, [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32,
                                         c_void_p, c_int32, c_void_p] + [c_int32] * 6 + [c_float, c_void_p, c_int64, c_void_p]),
+    # the decode step as one replayed graph: positions in device memory, sampling on the device (csrc/sample.hip)
+    "ltxk_causal_attn_dev_step": (c_int32, [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32,
+                                            c_void_p, c_int32, c_void_p] + [c_int32] * 4 + [c_void_p, c_int32, c_int32, c_float, c_void_p,
+                                                                                            c_int64, c_void_p]),
+    "ltxk_headnorm_rope_at": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
+                                        c_int32, c_void_p, c_float, c_void_p]),
+    "ltxk_sample_rows": (c_int32, [POINTER(SampleArgs), c_void_p]),
 }
 
 # ltxk_abi_sizeof(i) is the size of ABI_STRUCTS[i]
@@ -247,6 +266,7 @@ CONV_KERNEL_PER_TAP, CONV_KERNEL_KW, CONV_KERNEL_TAPS = 0, 1, 2  # ltxk.h: LTXK_
 ATTN_KERNEL_128, ATTN_KERNEL_MIX = 0, 1                         # ltxk.h: LTXK_ATTN_KERNEL_*
 GUIDER_CFG_STAR, GUIDER_APG = 1, 2                              # ltxk.h: LTXK_GUIDER_*
 GUIDER_RECORD_FLOATS = 8                                        # ltxk.h: LTXK_GUIDER_RECORD_FLOATS
+SAMPLE_DRAW, SAMPLE_ADVANCE = 1, 2                              # ltxk.h: LTXK_SAMPLE_*
 
 
 def _open(path: str) -> ctypes.CDLL:

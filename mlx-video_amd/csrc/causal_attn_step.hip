@@ -30,10 +30,23 @@ __host__ __device__ __forceinline__ int cs_first_slice(int step, int window) {
 // sum over the parts, ascending, of part * 2^(M_part - M); every factor a power of two (0 for a part without a visible key)
 __device__ __forceinline__ float cs_rescale(float m_part, float m) { return __builtin_amdgcn_exp2f(m_part - m); }
 
+// DEV (ltxk_causal_attn_dev_step): `step` is *step_dev, and s0 / nslices are derived from it here; the grid holds `gslices`
+// slices per (batch row, KV head), sized by the host for max_step, and a workgroup past the step's own count - or any
+// workgroup when *step_dev lies outside [0, max_step] - leaves here, block-uniformly, ahead of every load, store and barrier.
+// The host form passes gslices == nslices and takes the same path from there on.
+template <bool DEV>
 __global__ __launch_bounds__(256) void causal_attn_step_kernel(
     const bf16* __restrict__ q, int ldq, const bf16* __restrict__ k_new, int ldkn, const bf16* __restrict__ v_new, int ldvn,
     bf16* k_cache, int ldk, bf16* vt_cache, int ldvt, const int32_t* __restrict__ row_start, float* __restrict__ partials,
-    int Hq, int Hkv, int cap, int step, int window, int s0, int nslices, float cl2e) {
+    int Hq, int Hkv, int cap, int step, const int32_t* __restrict__ step_dev, int max_step, int window, int s0, int nslices,
+    int gslices, float cl2e) {
+  if constexpr (DEV) {
+    step = *step_dev;
+    if (step < 0 || step > max_step) return;
+    s0 = cs_first_slice(step, window);
+    nslices = step / CS_SLICE + 1 - s0;
+    if ((int)(blockIdx.x % (unsigned)gslices) >= nslices) return;
+  }
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* sm_m = (float*)smem;                    // [4][16]
   float* sm_l = sm_m + 64;                       // [4][16]
@@ -41,8 +54,8 @@ __global__ __launch_bounds__(256) void causal_attn_step_kernel(
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int c = lane & 15, g = lane >> 4;
   const int G = Hq / Hkv;
-  const int si = (int)(blockIdx.x % (unsigned)nslices);
-  const int bk = (int)(blockIdx.x / (unsigned)nslices);
+  const int si = (int)(blockIdx.x % (unsigned)gslices);
+  const int bk = (int)(blockIdx.x / (unsigned)gslices);
   const int b = bk / Hkv, hk = bk - b * Hkv;
   const int kt = (s0 + si) * CS_SLICE + wave * AT_BK;          // this wave's first key
   int rs = row_start[b];
@@ -148,8 +161,15 @@ __global__ __launch_bounds__(256) void causal_attn_step_kernel(
 }
 
 // Launch 2: one workgroup per (batch row, query head), thread = channel; the slices merged in ascending order, then O / l.
+template <bool DEV>
 __global__ __launch_bounds__(256) void causal_attn_step_combine_kernel(const float* __restrict__ partials, bf16* __restrict__ out,
-                                                                         int ldo, int Hq, int nslices) {
+                                                                         int ldo, int Hq, int nslices, const int32_t* __restrict__ step_dev,
+                                                                         int max_step, int window) {
+  if constexpr (DEV) {                           // the device count of slices; a step out of range stores nothing
+    const int step = *step_dev;
+    if (step < 0 || step > max_step) return;
+    nslices = step / CS_SLICE + 1 - cs_first_slice(step, window);
+  }
   const int tid = threadIdx.x;
   const int b = (int)(blockIdx.x / (unsigned)Hq), h = (int)(blockIdx.x % (unsigned)Hq);
   const float* part = partials + ((size_t)b * Hq + h) * nslices * CS_PART;
@@ -172,16 +192,19 @@ __global__ __launch_bounds__(256) void causal_attn_step_combine_kernel(const flo
 
 using namespace ltxk;
 
-extern "C" int ltxk_causal_attn_step(const void* q, int32_t ldq, const void* k_new, int32_t ldkn, const void* v_new, int32_t ldvn,
-                                     void* k_cache, int32_t ldk, void* vt_cache, int32_t ldvt, void* out, int32_t ldo,
-                                     const int32_t* row_start, int32_t B, int32_t Hq, int32_t Hkv, int32_t cap, int32_t step,
-                                     int32_t window, float scale, float* partials, int64_t partials_floats, void* stream) {
-  const char* who = "ltxk_causal_attn_step";
+// The checks both entries share, and the two launches.  DEV: `step` is max_step, which sizes the grid and the partials.
+template <bool DEV>
+static int causal_attn_step_launch(const char* who, const void* q, int32_t ldq, const void* k_new, int32_t ldkn, const void* v_new, int32_t ldvn,
+                                   void* k_cache, int32_t ldk, void* vt_cache, int32_t ldvt, void* out, int32_t ldo,
+                                   const int32_t* row_start, int32_t B, int32_t Hq, int32_t Hkv, int32_t cap, int32_t step,
+                                   const int32_t* step_dev, int32_t window, float scale, float* partials, int64_t partials_floats,
+                                   void* stream) {
   LTXK_CHECK_ARG(q && k_new && v_new && k_cache && vt_cache && out && row_start && partials, "%s: null pointer", who);
+  LTXK_CHECK_ARG(!DEV || (step_dev && ((uintptr_t)step_dev & 3) == 0), "%s: step: null or misaligned pointer", who);
   LTXK_CHECK_ARG(B > 0 && Hq > 0 && Hkv > 0 && cap > 0, "%s: bad dims B=%d Hq=%d Hkv=%d cap=%d", who, B, Hq, Hkv, cap);
   LTXK_CHECK_ARG(Hq % Hkv == 0 && Hq / Hkv <= 16, "%s: Hq=%d must be a multiple of Hkv=%d, at most 16 times it", who, Hq, Hkv);
   LTXK_CHECK_ARG(cap % AT_BK == 0, "%s: cap=%d must be a multiple of %d", who, cap, AT_BK);
-  LTXK_CHECK_ARG(step >= 0 && step < cap, "%s: step=%d must lie in [0, cap=%d)", who, step, cap);
+  LTXK_CHECK_ARG(step >= 0 && step < cap, "%s: %s=%d must lie in [0, cap=%d)", who, DEV ? "max_step" : "step", step, cap);
   LTXK_CHECK_ARG(scale > 0.f, "%s: scale must be positive", who);
   LTXK_CHECK_ARG(window >= 0, "%s: window=%d must be 0 (none) or a positive count", who, window);
   LTXK_CHECK_ARG((int64_t)Hq * CS_DH <= INT32_MAX && ldq >= Hq * CS_DH && ldo >= Hq * CS_DH && ldkn >= Hkv * CS_DH &&
@@ -192,21 +215,40 @@ extern "C" int ltxk_causal_attn_step(const void* q, int32_t ldq, const void* k_n
   LTXK_CHECK_ARG((((uintptr_t)q | (uintptr_t)k_new | (uintptr_t)v_new | (uintptr_t)k_cache | (uintptr_t)vt_cache | (uintptr_t)out |
                    (uintptr_t)partials) & 15) == 0 && ((uintptr_t)row_start & 3) == 0,
                  "%s: q, k_new, v_new, k_cache, vt_cache, out, partials must be 16-byte aligned", who);
-  const int s0 = cs_first_slice(step, window);
-  const int nslices = step / CS_SLICE + 1 - s0;
+  const int s0 = DEV ? 0 : cs_first_slice(step, window);
+  int nslices = step / CS_SLICE + 1 - s0;
+  const int reach = (window + CS_SLICE - 2) / CS_SLICE + 1;                  // the most slices a window of keys can touch
+  if (DEV && window > 0 && reach < nslices) nslices = reach;
   const int64_t need = (int64_t)B * Hq * nslices * CS_PART;
   LTXK_CHECK_ARG(partials_floats >= need, "%s: partials holds %lld floats, %lld needed (B*Hq*slices*258)", who,
                  (long long)partials_floats, (long long)need);
   LTXK_CHECK_ARG((int64_t)B * Hkv * nslices <= INT32_MAX, "%s: too many workgroups", who);
   static std::atomic<uint64_t> attr_set{0};
-  const int rc = ensure_dyn_lds((const void*)causal_attn_step_kernel, CS_LDS, attr_set, who);
+  const int rc = ensure_dyn_lds((const void*)causal_attn_step_kernel<DEV>, CS_LDS, attr_set, who);
   if (rc != LTXK_OK) return rc;
-  hipLaunchKernelGGL(causal_attn_step_kernel, dim3((unsigned)(B * Hkv * nslices)), dim3(256), CS_LDS, (hipStream_t)stream,
+  hipLaunchKernelGGL(causal_attn_step_kernel<DEV>, dim3((unsigned)(B * Hkv * nslices)), dim3(256), CS_LDS, (hipStream_t)stream,
                      (const bf16*)q, ldq, (const bf16*)k_new, ldkn, (const bf16*)v_new, ldvn, (bf16*)k_cache, ldk, (bf16*)vt_cache, ldvt,
-                     row_start, partials, Hq, Hkv, cap, step, window, s0, nslices, scale * 1.4426950408889634f);
+                     row_start, partials, Hq, Hkv, cap, step, step_dev, step, window, s0, nslices, nslices, scale * 1.4426950408889634f);
   LTXK_CHECK_LAUNCH(who);
-  hipLaunchKernelGGL(causal_attn_step_combine_kernel, dim3((unsigned)(B * Hq)), dim3(256), 0, (hipStream_t)stream,
-                     (const float*)partials, (bf16*)out, ldo, Hq, nslices);
+  hipLaunchKernelGGL(causal_attn_step_combine_kernel<DEV>, dim3((unsigned)(B * Hq)), dim3(256), 0, (hipStream_t)stream,
+                     (const float*)partials, (bf16*)out, ldo, Hq, nslices, step_dev, step, window);
   LTXK_CHECK_LAUNCH(who);
   return LTXK_OK;
+}
+
+extern "C" int ltxk_causal_attn_step(const void* q, int32_t ldq, const void* k_new, int32_t ldkn, const void* v_new, int32_t ldvn,
+                                     void* k_cache, int32_t ldk, void* vt_cache, int32_t ldvt, void* out, int32_t ldo,
+                                     const int32_t* row_start, int32_t B, int32_t Hq, int32_t Hkv, int32_t cap, int32_t step,
+                                     int32_t window, float scale, float* partials, int64_t partials_floats, void* stream) {
+  return causal_attn_step_launch<false>("ltxk_causal_attn_step", q, ldq, k_new, ldkn, v_new, ldvn, k_cache, ldk, vt_cache, ldvt, out, ldo,
+                                        row_start, B, Hq, Hkv, cap, step, nullptr, window, scale, partials, partials_floats, stream);
+}
+
+extern "C" int ltxk_causal_attn_dev_step(const void* q, int32_t ldq, const void* k_new, int32_t ldkn, const void* v_new, int32_t ldvn,
+                                         void* k_cache, int32_t ldk, void* vt_cache, int32_t ldvt, void* out, int32_t ldo,
+                                         const int32_t* row_start, int32_t B, int32_t Hq, int32_t Hkv, int32_t cap, const int32_t* step,
+                                         int32_t max_step, int32_t window, float scale, float* partials, int64_t partials_floats,
+                                         void* stream) {
+  return causal_attn_step_launch<true>("ltxk_causal_attn_dev_step", q, ldq, k_new, ldkn, v_new, ldvn, k_cache, ldk, vt_cache, ldvt, out, ldo,
+                                       row_start, B, Hq, Hkv, cap, max_step, step, window, scale, partials, partials_floats, stream);
 }

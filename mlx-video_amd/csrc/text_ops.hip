@@ -305,20 +305,28 @@ __global__ void embed_rows_fp8_kernel(const uint8_t* __restrict__ table, const f
 // is 8 elements of a head's first half and their 8 rotation partners 128 columns up; a head is 16 items = one aligned group
 // of 16 lanes, which reduces the head's 256 squares itself (16 per lane in ascending order, then the group's butterfly).
 // Values and rounding points: rows.h, with Gemma's 1 + w.
+// AT (ltxk_headnorm_rope_at): every row takes table row *pos, read from device memory; a position outside [0, T) stores nothing.
 constexpr int HEADNORM_DH = 256;
 
+template <bool AT>
 __global__ __launch_bounds__(256) void headnorm_rope_kernel(bf16* __restrict__ buf, int ld, int M, int Hq, int Hkv,
                                                             const bf16* __restrict__ qw, const bf16* __restrict__ kw,
-                                                            const float* __restrict__ cosb, const float* __restrict__ sinb, int T, float eps) {
+                                                            const float* __restrict__ cosb, const float* __restrict__ sinb, int T, float eps,
+                                                            const int32_t* __restrict__ pos) {
   const int NH = Hq + Hkv;
   const int64_t heads = (int64_t)M * NH;
   const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const int64_t hg_raw = gid >> 4;
+  int at = 0;
+  if constexpr (AT) {
+    at = *pos;
+    if (at < 0 || at >= T) return;                // uniform over the launch
+  }
   const bool live = hg_raw < heads;               // uniform over a group of 16 lanes
   const int64_t hg = live ? hg_raw : heads - 1;
   const int it = (int)(gid & 15);
   const int row = (int)(hg / NH), hh = (int)(hg - (int64_t)row * NH);
-  const int t = row % T;
+  const int t = AT ? at : row % T;
   bf16* xp = buf + (size_t)row * ld + (size_t)hh * HEADNORM_DH + it * 8;
   const bf16x8 a = *(const bf16x8*)xp;
   const bf16x8 b = *(const bf16x8*)(xp + 128);
@@ -497,19 +505,31 @@ extern "C" int ltxk_rmsnorm_weight_rows(const void* x, int32_t ldx, const void* 
   return rmsnorm_rows_launch("ltxk_rmsnorm_weight_rows", x, ldx, weight, resid, ldr, y, ldy, M, D, eps, stream);
 }
 
+template <bool AT>
+static int headnorm_rope_launch(const char* who, void* buf, int32_t ld, int32_t M, int32_t Hq, int32_t Hkv, const void* q_weight,
+                                const void* k_weight, const float* cos, const float* sin, int32_t T, const int32_t* pos, float eps, void* stream) {
+  LTXK_CHECK_ARG(buf && q_weight && k_weight && cos && sin && M > 0 && T > 0, "%s: bad arguments", who);
+  LTXK_CHECK_ARG(!AT || (pos && ((uintptr_t)pos & 3) == 0), "%s: pos: null or misaligned pointer", who);
+  LTXK_CHECK_ARG(Hq >= 1 && Hkv >= 1 && (int64_t)(Hq + Hkv) * HEADNORM_DH <= (int64_t)ld, "%s: ld=%d must be >= (Hq + Hkv) * 256, Hq=%d Hkv=%d",
+                 who, ld, Hq, Hkv);
+  LTXK_CHECK_ARG(ld % 8 == 0 && aligned16(buf) && aligned16(q_weight) && aligned16(k_weight) && aligned16(cos) && aligned16(sin),
+                 "%s: ld must be a multiple of 8, pointers 16-byte aligned", who);
+  const int64_t groups = ((int64_t)M * (Hq + Hkv) * 16 + 255) / 256;
+  LTXK_CHECK_ARG(groups <= (int64_t)INT32_MAX, "%s: too many rows", who);
+  hipLaunchKernelGGL(headnorm_rope_kernel<AT>, dim3((unsigned)groups), dim3(256), 0, (hipStream_t)stream, (bf16*)buf, ld, M, Hq, Hkv,
+                     (const bf16*)q_weight, (const bf16*)k_weight, cos, sin, T, eps, pos);
+  LTXK_CHECK_LAUNCH(who);
+  return LTXK_OK;
+}
+
 extern "C" int ltxk_headnorm_rope(void* buf, int32_t ld, int32_t M, int32_t Hq, int32_t Hkv, const void* q_weight, const void* k_weight,
                                   const float* cos, const float* sin, int32_t T, float eps, void* stream) {
-  LTXK_CHECK_ARG(buf && q_weight && k_weight && cos && sin && M > 0 && T > 0, "ltxk_headnorm_rope: bad arguments");
-  LTXK_CHECK_ARG(Hq >= 1 && Hkv >= 1 && (int64_t)(Hq + Hkv) * HEADNORM_DH <= (int64_t)ld, "ltxk_headnorm_rope: ld=%d must be >= (Hq + Hkv) * 256, Hq=%d Hkv=%d",
-                 ld, Hq, Hkv);
-  LTXK_CHECK_ARG(ld % 8 == 0 && aligned16(buf) && aligned16(q_weight) && aligned16(k_weight) && aligned16(cos) && aligned16(sin),
-                 "ltxk_headnorm_rope: ld must be a multiple of 8, pointers 16-byte aligned");
-  const int64_t groups = ((int64_t)M * (Hq + Hkv) * 16 + 255) / 256;
-  LTXK_CHECK_ARG(groups <= (int64_t)INT32_MAX, "ltxk_headnorm_rope: too many rows");
-  hipLaunchKernelGGL(headnorm_rope_kernel, dim3((unsigned)groups), dim3(256), 0, (hipStream_t)stream, (bf16*)buf, ld, M, Hq, Hkv,
-                     (const bf16*)q_weight, (const bf16*)k_weight, cos, sin, T, eps);
-  LTXK_CHECK_LAUNCH("ltxk_headnorm_rope");
-  return LTXK_OK;
+  return headnorm_rope_launch<false>("ltxk_headnorm_rope", buf, ld, M, Hq, Hkv, q_weight, k_weight, cos, sin, T, nullptr, eps, stream);
+}
+
+extern "C" int ltxk_headnorm_rope_at(void* buf, int32_t ld, int32_t M, int32_t Hq, int32_t Hkv, const void* q_weight, const void* k_weight,
+                                     const float* cos, const float* sin, int32_t T, const int32_t* pos, float eps, void* stream) {
+  return headnorm_rope_launch<true>("ltxk_headnorm_rope_at", buf, ld, M, Hq, Hkv, q_weight, k_weight, cos, sin, T, pos, eps, stream);
 }
 
 extern "C" int ltxk_geglu_tanh(const void* gu, int32_t ld, void* out, int32_t ldo, int32_t M, int32_t F, void* stream) {

@@ -335,6 +335,60 @@ def sample_tokens(logits: torch.Tensor, context: Sequence[Sequence[int]], temper
     return torch.multinomial(torch.softmax(lg / temperature, -1), 1, generator=generator)[:, 0]
 
 
+class GemmaDecodeState:
+    """What a decode step reads and writes, all on the device, so that the step is the same launches on the same addresses
+    every token and can be recorded once as a graph (``GemmaGenerator.device_step``): the sampler's state (``ops.sample_rows``;
+    int32) - ``ctl`` = {n, pos, live}: the draw index, the cache position at which the token drawn now is fed, the rows not
+    finished; ``done`` (B), ``next_ids`` (B), ``history`` (B, Hcap) / ``hist_len`` (B) initialised from the prompt's valid tokens,
+    ``tokens_out`` (B, max_tokens), ``eos``, ``uniforms`` (max_tokens, B) fp32 = ``torch.rand`` of a CPU generator seeded with
+    ``seed``, uploaded once - and the step's static activations: ``x`` (2, B, D) (a layer reads one and writes the other), ``nx``,
+    ``qkv``, ``att``, ``po``, ``gu`` and the (B, V) bf16 ``logits`` the sampler reads."""
+
+    def __init__(self, config: GemmaConfig, vocab: int, input_ids: torch.Tensor, attention_mask: torch.Tensor, max_tokens: int,
+                 eos_ids: Sequence[int], seed: int, device):
+        B, T = input_ids.shape
+        if not 1 <= B <= ops.SAMPLE_MAX_B:
+            raise ValueError(f"GemmaDecodeState: the device loop takes 1 to {ops.SAMPLE_MAX_B} batch rows, got {B}")
+        if max_tokens < 1:
+            raise ValueError(f"GemmaDecodeState: max_tokens = {max_tokens} must be positive")
+        eos = sorted(set(int(t) for t in eos_ids))
+        if len(eos) > ops.SAMPLE_MAX_EOS:
+            raise ValueError(f"GemmaDecodeState: at most {ops.SAMPLE_MAX_EOS} EOS ids, got {len(eos)}")
+        c = config
+        D, F = c.hidden_size, c.intermediate_size
+        nq, nkv = c.num_attention_heads * HEAD_DIM, c.num_key_value_heads * HEAD_DIM
+        self.B, self.T, self.max_tokens, self.vocab = int(B), int(T), int(max_tokens), int(vocab)
+        ids_host, mask_host = input_ids.detach().to("cpu"), attention_mask.detach().to("cpu").bool()
+        hcap = T + max_tokens
+        hist = torch.zeros((B, hcap), dtype=torch.int32)
+        hlen = torch.zeros(B, dtype=torch.int32)
+        for b in range(B):
+            valid = ids_host[b][mask_host[b]].to(torch.int32)
+            hist[b, :valid.numel()] = valid
+            hlen[b] = valid.numel()
+        i32 = lambda t: t.to(torch.int32).to(device)          # noqa: E731
+        self.ctl = i32(torch.tensor([0, T, B]))
+        self.done, self.next_ids = i32(torch.zeros(B)), i32(torch.zeros(B))
+        self.history, self.hist_len = hist.to(device), hlen.to(device)
+        self.tokens_out = torch.full((B, max_tokens), -1, dtype=torch.int32, device=device)
+        self.eos = i32(torch.tensor(eos, dtype=torch.int32))
+        self.uniforms = torch.rand((max_tokens, B), generator=torch.Generator(device="cpu").manual_seed(int(seed))).to(device)
+        self.workspace = torch.empty(ops.sample_workspace_floats(B, vocab), dtype=torch.float32, device=device)
+        bf = lambda *shape: torch.empty(shape, dtype=BF16, device=device)          # noqa: E731
+        self.x, self.nx, self.qkv, self.att = bf(2, B, D), bf(B, D), bf(B, nq + 2 * nkv), bf(B, nq)
+        self.po, self.gu, self.logits = bf(B, D), bf(B, 2 * F), bf(B, vocab)
+
+    @property
+    def pos(self) -> torch.Tensor:
+        """The (1,) int32 view of ctl's position: what the device-position kernels read."""
+        return self.ctl[1:2]
+
+    def read(self) -> Tuple[int, int, int, torch.Tensor]:
+        """(n, pos, live, tokens_out on the host): the loop's one small device-to-host copy."""
+        ctl = self.ctl.to("cpu")
+        return int(ctl[0]), int(ctl[1]), int(ctl[2]), self.tokens_out.to("cpu")
+
+
 class GemmaGenerator:
     """KV-cached autoregressive decoding on a ``GemmaEncoder``'s panels (nothing is copied; Gemma-3 ties the output head to
     the embedding table).  ``prefill`` runs the encoder's layer loop into a ``GemmaCache``; ``step`` runs one token: per layer
@@ -369,14 +423,18 @@ class GemmaGenerator:
     def _logits(self, h: torch.Tensor) -> torch.Tensor:
         return self._gemm("logits", h, self.enc.embed, self.enc.embed_row_scale).to(torch.float32)
 
-    def prefill(self, input_ids: torch.Tensor, attention_mask: torch.Tensor, capacity: int, return_states: bool = False):
+    def prefill(self, input_ids: torch.Tensor, attention_mask: torch.Tensor, capacity: int, return_states: bool = False,
+                logits: bool = True):
         """(cache, logits (B,V) fp32 of the last position) for a left-padded (B,T) prompt, T <= capacity (a multiple of 64);
-        with ``return_states`` also the encoder's (L+1, B, T, D) states."""
+        with ``return_states`` also the encoder's (L+1, B, T, D) states.  ``logits=False``: (cache, states) and no logits GEMM
+        (the device loop writes the logits into its own buffer)."""
         B, T = input_ids.shape
         if T > capacity:
             raise ValueError(f"prefill: {T} prompt positions do not fit a cache of capacity {capacity}")
         cache = GemmaCache(self.cfg, B, capacity, self.enc.device)
         states = self.enc._forward(input_ids, attention_mask, cache)
+        if not logits:
+            return cache, states
         logits = self._logits(states[-1][:, T - 1])
         return (cache, logits, states) if return_states else (cache, logits)
 
@@ -424,17 +482,118 @@ class GemmaGenerator:
         logits = self._logits(states[L])
         return (logits, states) if return_states else logits
 
+    def sample(self, state: GemmaDecodeState, temperature: float, repetition_penalty: float, repetition_context: int,
+               draw: bool = True, advance: bool = False) -> None:
+        """The sampler on ``state``: a draw from ``state.logits`` (``ops.sample_rows``), the advance of ctl, or both."""
+        ops.sample_rows(state.logits, state.ctl, state.done, state.next_ids, state.history, state.hist_len, state.tokens_out, state.eos,
+                        state.uniforms if temperature > 0 else None, state.workspace, temperature=float(temperature),
+                        penalty=float(repetition_penalty), rep_ctx=max(0, int(repetition_context)), draw=draw, advance=advance)
+
+    def device_step(self, cache: GemmaCache, state: GemmaDecodeState, temperature: float = 0.0, repetition_penalty: float = 1.0,
+                    repetition_context: int = 0, draw: bool = True) -> None:
+        """One token entirely in stream order, with no host value that changes from token to token: the draw from
+        ``state.logits``, ``embed_rows`` of ``state.next_ids``, the L layers of ``step`` - the same launches, the token's position
+        read from ``state.ctl`` by ``headnorm_rope(pos=)`` and ``causal_attn(step=<tensor>, max_step=)`` - the final norm, the logits
+        GEMM into ``state.logits`` and the advance of ctl.  Nothing is allocated and nothing synchronises, so the call can be
+        recorded once (``torch.cuda.graph``) and replayed; fed the same ids it leaves the logits ``step`` returns, bit for bit.
+        ``draw=False`` feeds ``state.next_ids`` as they stand (teacher forcing).  The host's ``cache.length`` is not touched: the
+        position lives in ``state.ctl``."""
+        e, c = self.enc, self.cfg
+        cap, B = cache.capacity, cache.B
+        if cache.row_start is None:
+            raise ValueError("device_step: the cache has not been prefilled")
+        if state.B != B or state.T + state.max_tokens > cap:
+            raise ValueError(f"device_step: a state of {state.B} rows, {state.T} + {state.max_tokens} positions on a cache of {B} rows, capacity {cap}")
+        L = c.num_hidden_layers
+        Hq, Hkv = c.num_attention_heads, c.num_key_value_heads
+        nq, nkv = Hq * HEAD_DIM, Hkv * HEAD_DIM
+        if draw:
+            self.sample(state, temperature, repetition_penalty, repetition_context)
+        x = ops.embed_rows(e.embed, state.next_ids, e.embed_scale, out=state.x[0], row_scale=e.embed_row_scale, trusted_ids=True)
+        nx, qkv, att, po, gu, pos = state.nx, state.qkv, state.att, state.po, state.gu, state.pos
+        for i, ly in enumerate(e.layers):
+            cos, sin = e._tables(cap, ly["is_global"])
+            ops.rmsnorm_weight_rows(x, ly["n_in"], c.rms_norm_eps, out=nx)
+            self._gemm("qkv", nx, ly["qkv"], ly["qkv_s"], qkv)
+            ops.headnorm_rope(qkv, Hq, Hkv, ly["qn"], ly["kn"], cos, sin, cap, c.rms_norm_eps, pos=pos)
+            ops.causal_attn(qkv[:, :nq], cache.k[i].view(B * cap, nkv), cache.vt[i], att, cache.row_start, B, Hq, Hkv, cap, e.scale,
+                            window=ly["window"], step=pos, max_step=cap - 1, k_new=qkv[:, nq:nq + nkv], v_new=qkv[:, nq + nkv:],
+                            partials=cache.partials)
+            self._gemm("o", att, ly["o"], ly["o_s"], po)
+            y = state.x[(i + 1) % 2]
+            ops.rmsnorm_weight_rows(po, ly["n_post_attn"], c.rms_norm_eps, resid=x, out=y)
+            ops.rmsnorm_weight_rows(y, ly["n_pre_ff"], c.rms_norm_eps, out=nx)
+            self._gemm("gu", nx, ly["gu"], ly["gu_s"], gu)
+            h = ops.geglu_tanh_(gu)
+            self._gemm("down", h, ly["down"], ly["down_s"], po)
+            ops.rmsnorm_weight_rows(po, ly["n_post_ff"], c.rms_norm_eps, resid=y, out=y)
+            x = y
+        ops.rmsnorm_weight_rows(x, e.norm, c.rms_norm_eps, out=nx)
+        self._gemm("logits", nx, e.embed, e.embed_row_scale, state.logits)
+        self.sample(state, temperature, repetition_penalty, repetition_context, draw=False, advance=True)
+
+    def _generate_device(self, input_ids, attention_mask, max_tokens, temperature, repetition_penalty, repetition_context, eos_ids, seed,
+                         graph: bool, sync_every: int) -> List[List[int]]:
+        """``generate(device_loop=True)``."""
+        B, T = input_ids.shape
+        if temperature < 0:
+            raise ValueError(f"temperature must be >= 0, got {temperature}")
+        if repetition_context > ops.SAMPLE_MAX_CTX:
+            raise ValueError(f"generate: the device loop penalises at most the last {ops.SAMPLE_MAX_CTX} tokens, got "
+                             f"repetition_context = {repetition_context}")
+        if sync_every < 1:
+            raise ValueError(f"generate: sync_every = {sync_every} must be positive")
+        state = GemmaDecodeState(self.cfg, self.enc.vocab, input_ids, attention_mask, max_tokens, eos_ids, seed, self.enc.device)
+        cache, states = self.prefill(input_ids, attention_mask, (T + max_tokens + 63) // 64 * 64, logits=False)
+        self._gemm("logits", states[-1][:, T - 1], self.enc.embed, self.enc.embed_row_scale, state.logits)
+        del states
+        step = lambda: self.device_step(cache, state, temperature, repetition_penalty, repetition_context)      # noqa: E731
+        n = live = 0
+        if max_tokens == 1:             # one draw and nothing to feed
+            self.sample(state, temperature, repetition_penalty, repetition_context, advance=True)
+        else:
+            # token 0 eagerly (it also makes the lazy one-time calls: the split-K scratch, a kernel's LDS attribute), then the
+            # step recorded once - one chain on one stream - and replayed.  A replay draws token n and feeds it; the feed behind
+            # the last draw is wasted.  The host looks at ctl every sync_every steps, so up to that many run past the last EOS.
+            step()
+            g = None
+            if graph:
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g, capture_error_mode="thread_local"):
+                    step()
+            for i in range(1, max_tokens):
+                if i % sync_every == 0:
+                    n, _, live, _ = state.read()
+                    if live == 0:
+                        break
+                g.replay() if g is not None else step()
+        n, pos, live, toks = state.read()
+        cache.length = pos
+        return [[int(t) for t in toks[b, :n] if int(t) >= 0] for b in range(B)]
+
     def generate(self, input_ids: torch.Tensor, attention_mask: torch.Tensor, max_tokens: int = 512, temperature: float = 0.7,
                  repetition_penalty: float = 1.3, repetition_context: int = 20, eos_ids: Sequence[int] = (1, 107),
-                 seed: int = 42) -> List[List[int]]:
+                 seed: int = 42, device_loop: bool = False, graph: bool = True, sync_every: int = 16) -> List[List[int]]:
         """The new tokens of each batch row, its terminating EOS id included (generation of a row ends there, or at
         ``max_tokens``).  The defaults are the reference's call (text_encoder.py:1079-1084, 1123): temperature 0.7, repetition
         penalty 1.3 over the last 20 tokens (the prompt's included), EOS ids 1 and 107.  Sampling is host torch on the fp32
         logits with a ``torch.Generator`` seeded by ``seed``: seeds are NOT cross-compatible with MLX's generator - the same
-        seed gives the same tokens here and other tokens there (the project's standing convention for random numbers)."""
+        seed gives the same tokens here and other tokens there (the project's standing convention for random numbers).
+
+        ``device_loop=True``: the loop stays on the device (``device_step``).  The penalty, the draw and the bookkeeping are
+        ``ops.sample_rows`` on the logits GEMM's own bf16 output, the token's position is read from device memory, and with
+        ``graph`` the step is recorded once as a graph and replayed (``graph=False``: the same launches, eagerly); every
+        ``sync_every`` steps one small copy tells the host whether every row has finished.  At temperature 0 the tokens are the
+        host loop's.  At temperature > 0 the device loop consumes ``seed`` differently - one ``torch.rand`` uniform per (draw,
+        row) through the inverse CDF, where the host loop calls ``torch.multinomial`` - so the same seed gives OTHER tokens than
+        with ``device_loop=False``, as it does against MLX; two device-loop runs of one seed agree.  B <= 8,
+        ``repetition_context`` <= 64 and at most 8 EOS ids."""
         B, T = input_ids.shape
         if max_tokens < 1:
             return [[] for _ in range(B)]
+        if device_loop:
+            return self._generate_device(input_ids, attention_mask, max_tokens, temperature, repetition_penalty, repetition_context,
+                                         eos_ids, seed, graph, sync_every)
         cache, logits = self.prefill(input_ids, attention_mask, (T + max_tokens + 63) // 64 * 64)
         ids_host, mask_host = input_ids.detach().to("cpu"), attention_mask.detach().to("cpu").bool()
         history = [[int(t) for t in ids_host[b][mask_host[b]]] for b in range(B)]
@@ -480,18 +639,21 @@ def clean_response(text: str) -> str:
 
 
 def enhance_prompt(generator: GemmaGenerator, tokenizer, prompt: str, system_prompt: Optional[str] = None, max_tokens: int = 512,
-                   temperature: float = 0.7, seed: int = 42, **sampling) -> str:
+                   temperature: float = 0.7, seed: int = 42, device_loop: bool = False, **sampling) -> str:
     """The user's short prompt rewritten by the model into the long descriptive one LTX-2 was trained on (the reference's
     ``enhance_t2v``, text_encoder.py:1023-1135).  ``tokenizer``: a ``tokenizers.Tokenizer`` (``load_tokenizer``).  Only the new
     tokens are decoded (special tokens skipped) and cleaned; an empty result keeps ``prompt`` and warns.  ``sampling``: further
-    keywords of ``GemmaGenerator.generate`` (repetition_penalty, repetition_context, eos_ids)."""
+    keywords of ``GemmaGenerator.generate`` (repetition_penalty, repetition_context, eos_ids, graph, sync_every).
+    ``device_loop``: sampling and the token loop on the device, the step replayed as a graph (``generate``); at temperature > 0
+    the same ``seed`` then gives other tokens than the host loop does."""
     text = chat_prompt(system_prompt or DEFAULT_ENHANCE_SYSTEM_PROMPT, prompt)
     tokenizer.no_padding(); tokenizer.no_truncation()
     ids = list(tokenizer.encode(text).ids)
     if not ids:
         raise ValueError("enhance_prompt: the tokenizer produced no tokens for the chat prompt")
     input_ids = torch.tensor([ids], dtype=torch.int64)
-    new = generator.generate(input_ids, torch.ones_like(input_ids), max_tokens=max_tokens, temperature=temperature, seed=seed, **sampling)[0]
+    new = generator.generate(input_ids, torch.ones_like(input_ids), max_tokens=max_tokens, temperature=temperature, seed=seed,
+                             **({"device_loop": True} if device_loop else {}), **sampling)[0]
     out = clean_response(tokenizer.decode(new, skip_special_tokens=True))
     if not out:
         warnings.warn("prompt enhancement produced an empty result: the original prompt is kept")

@@ -12,12 +12,12 @@ from __future__ import annotations
 import ctypes
 import math
 from dataclasses import dataclass
-from typing import Optional, Tuple
+from typing import Optional, Tuple, Union
 
 import torch
 
 from . import _lib
-from ._lib import AttnArgs, CausalAttnArgs, Conv3dArgs, ConvTapsArgs, GemmArgs, GemmGroupedArgs, GuiderArgs, StepArgs, check
+from ._lib import AttnArgs, CausalAttnArgs, Conv3dArgs, ConvTapsArgs, GemmArgs, GemmGroupedArgs, GuiderArgs, SampleArgs, StepArgs, check
 
 EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_SILU, EPI_BIAS_GATE_RES, EPI_BIAS_RES, EPI_SCALE_RES = 0, 1, 2, 3, 4, 5
 BF16 = torch.bfloat16
@@ -935,12 +935,14 @@ CAUSAL_ATTN_BK = 64          # keys per tile
 
 
 def embed_rows(table: torch.Tensor, ids: torch.Tensor, scale: float, out: Optional[torch.Tensor] = None,
-               ids_host: Optional[torch.Tensor] = None, row_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
+               ids_host: Optional[torch.Tensor] = None, row_scale: Optional[torch.Tensor] = None, trusted_ids: bool = False) -> torch.Tensor:
     """ltxk_embed_rows: out[m,:] = bf16(table[ids[m],:] * scale).  table (V,D) contiguous bf16, ids (M) int32 on the device.
     The kernel cannot raise for device data, so the id range is validated here on ``ids_host``, the host copy the caller
     tokenised (without one, ``ids`` is copied back once - a synchronisation, once per prompt).
     A ``float8_e4m3fn`` table (D % 16 == 0) takes ltxk_embed_rows_fp8: out[m,:] = bf16((table[ids[m],:] * row_scale[ids[m]]) *
-    scale) with ``row_scale`` (V) fp32, or bf16(table[ids[m],:] * scale) without one - the bf16 call on the widened table."""
+    scale) with ``row_scale`` (V) fp32, or bf16(table[ids[m],:] * scale) without one - the bf16 call on the widened table.
+    ``trusted_ids``: the ids come from a kernel that only emits ids in [0, V) (``sample_rows``): the host range check and its
+    copy-back are skipped, so that the call neither synchronises nor breaks a graph capture."""
     f8 = table.dtype == FP8
     if row_scale is not None and not f8:
         raise TypeError("embed_rows: row_scale goes with a float8_e4m3fn table")
@@ -951,11 +953,12 @@ def embed_rows(table: torch.Tensor, ids: torch.Tensor, scale: float, out: Option
         raise ValueError(f"embed_rows: a float8_e4m3fn table must have rows of a multiple of 16 elements, got {D}")
     _operands("embed_rows", ("table", table, tdt, 2, 16), ("ids", ids, I32, 1, 4), ("out", out, BF16, (M, D), 16, True),
               ("row_scale", row_scale, F32, (V,), 4))
-    host = ids.cpu() if ids_host is None else ids_host.reshape(-1)
-    if host.numel() != M:
-        raise ValueError(f"embed_rows: ids_host holds {host.numel()} ids, ids {M}")
-    if M and (int(host.min()) < 0 or int(host.max()) >= V):
-        raise ValueError(f"embed_rows: token ids must lie in [0, {V}), got [{int(host.min())}, {int(host.max())}]")
+    if not trusted_ids:
+        host = ids.cpu() if ids_host is None else ids_host.reshape(-1)
+        if host.numel() != M:
+            raise ValueError(f"embed_rows: ids_host holds {host.numel()} ids, ids {M}")
+        if M and (int(host.min()) < 0 or int(host.max()) >= V):
+            raise ValueError(f"embed_rows: token ids must lie in [0, {V}), got [{int(host.min())}, {int(host.max())}]")
     if out is None:
         out = torch.empty((M, D), dtype=BF16, device=table.device)
     if f8:
@@ -984,15 +987,23 @@ def rmsnorm_weight_rows(x: torch.Tensor, weight: torch.Tensor, eps: float = 1e-6
 
 
 def headnorm_rope(buf: torch.Tensor, Hq: int, Hkv: int, q_weight: torch.Tensor, k_weight: torch.Tensor, cos: torch.Tensor,
-                  sin: torch.Tensor, T: int, eps: float = 1e-6) -> torch.Tensor:
+                  sin: torch.Tensor, T: int, eps: float = 1e-6, *, pos: Optional[torch.Tensor] = None) -> torch.Tensor:
     """ltxk_headnorm_rope: in place on columns [0, (Hq+Hkv)*256) of buf (M, ld): per 256-wide head Gemma RMSNorm with
-    q_weight / k_weight (256,), then rotate-half RoPE with cos / sin (T,128) fp32, row m at position m % T."""
+    q_weight / k_weight (256,), then rotate-half RoPE with cos / sin (T,128) fp32, row m at position m % T.
+    ``pos`` (ltxk_headnorm_rope_at): an int32 device tensor of one element; every row then takes table row ``pos[0]`` - the bits
+    of the call on ``cos[p:p+1]``, ``sin[p:p+1]`` with T = 1 - and a position outside [0, T) stores nothing."""
     if Hq < 1 or Hkv < 1:
         raise ValueError(f"headnorm_rope: Hq = {Hq} and Hkv = {Hkv} must be positive")
     cols, HD = (Hq + Hkv) * GEMMA_HEAD_DIM, GEMMA_HEAD_DIM
     M = _dims("headnorm_rope", "buf", buf, BF16, 2)[0]
     _operands("headnorm_rope", ("buf", buf[:, :cols], BF16, (M, cols), 16, True), ("q_weight", q_weight, BF16, (HD,), 16),
-              ("k_weight", k_weight, BF16, (HD,), 16), ("cos", cos, F32, (T, HD // 2), 16), ("sin", sin, F32, (T, HD // 2), 16))
+              ("k_weight", k_weight, BF16, (HD,), 16), ("cos", cos, F32, (T, HD // 2), 16), ("sin", sin, F32, (T, HD // 2), 16),
+              ("pos", pos, I32, (1,), 4))
+    if pos is not None:
+        with _timed("headnorm_rope", 0.0, 4.0 * M * cols):
+            check(_lib.load().ltxk_headnorm_rope_at(_p(buf), buf.stride(0), M, Hq, Hkv, _p(q_weight), _p(k_weight), _p(cos), _p(sin),
+                                                    T, _p(pos), eps, _stream()), "ltxk_headnorm_rope_at")
+        return buf
     with _timed("headnorm_rope", 0.0, 4.0 * M * cols):
         check(_lib.load().ltxk_headnorm_rope(_p(buf), buf.stride(0), M, Hq, Hkv, _p(q_weight), _p(k_weight), _p(cos), _p(sin),
                                              T, eps, _stream()), "ltxk_headnorm_rope")
@@ -1016,9 +1027,17 @@ CAUSAL_ATTN_STEP_SLICE = 256  # keys per workgroup of ltxk_causal_attn_step
 CAUSAL_ATTN_STEP_PART = 258   # floats of one partial: M, l, O[256]
 
 
+def causal_attn_step_slices(max_step: int, window: int = 0) -> int:
+    """256-key slices per (batch row, head) of a ``causal_attn(step=<device tensor>, max_step=)`` launch: the most any step up to
+    ``max_step`` touches - under a window no more than a window of keys can reach."""
+    n = max_step // CAUSAL_ATTN_STEP_SLICE + 1
+    return min(n, (window + CAUSAL_ATTN_STEP_SLICE - 2) // CAUSAL_ATTN_STEP_SLICE + 1) if window else n
+
+
 def causal_attn(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, out: torch.Tensor, row_start: torch.Tensor, B: int, Hq: int,
-                Hkv: int, T: int, scale: float, window: int = 0, *, step: Optional[int] = None, k_new: Optional[torch.Tensor] = None,
-                v_new: Optional[torch.Tensor] = None, partials: Optional[torch.Tensor] = None) -> torch.Tensor:
+                Hkv: int, T: int, scale: float, window: int = 0, *, step: Union[int, torch.Tensor, None] = None,
+                k_new: Optional[torch.Tensor] = None, v_new: Optional[torch.Tensor] = None, partials: Optional[torch.Tensor] = None,
+                max_step: Optional[int] = None) -> torch.Tensor:
     """ltxk_causal_attn (head dim 256): q (B*T, >= Hq*256) view, k (B*T, >= Hkv*256) view, vt (B, Hkv*256, ldvt >= T),
     out (B*T, >= Hq*256) view, row_start (B) int32 on the device (valid tokens of batch row b: [row_start[b], T)).  Key j is
     visible to query i iff row_start <= j <= i and (window == 0 or i - j < window); rows below row_start come out zero.
@@ -1028,7 +1047,12 @@ def causal_attn(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, out: torch.T
     the step's rotated key and its value - read in the place of cache position ``step`` and stored there by the launch - and
     ``partials`` a caller-owned fp32 buffer of at least B * Hq * slices * CAUSAL_ATTN_STEP_PART floats, the 256-key slices of a
     launch being [s0, step/256] with s0 = max(0, step - window + 1) / 256 under a window, else 0 (B * Hq * ceil(T/256) * 258
-    floats serve every step).  Key j is visible iff row_start <= j <= step and (window == 0 or step - j < window)."""
+    floats serve every step).  Key j is visible iff row_start <= j <= step and (window == 0 or step - j < window).
+
+    ``step`` an int32 device tensor of one element (ltxk_causal_attn_dev_step), with ``max_step`` in [0, T): the position is read
+    on the device, the launch is sized for ``max_step`` and ``partials`` holds B * Hq * ``causal_attn_step_slices(max_step,
+    window)`` * 258 floats.  For step[0] == s the bits are those of ``step=s``, whatever ``max_step`` >= s is; step[0] outside
+    [0, max_step] leaves the cache, ``partials`` and ``out`` as they were."""
     nq, nkv = Hq * GEMMA_HEAD_DIM, Hkv * GEMMA_HEAD_DIM
     if step is None:
         if k_new is not None or v_new is not None or partials is not None:
@@ -1049,22 +1073,98 @@ def causal_attn(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, out: torch.T
         raise ValueError(f"causal_attn: the step form takes Hq = {Hq} a multiple of Hkv = {Hkv}, at most 16 times it")
     if T < 1 or T % CAUSAL_ATTN_BK:
         raise ValueError(f"causal_attn: the cache capacity T = {T} must be a positive multiple of {CAUSAL_ATTN_BK}")
-    if not 0 <= step < T:
-        raise ValueError(f"causal_attn: step = {step} must lie in [0, {T}), the cache capacity")
+    dev = isinstance(step, torch.Tensor)
+    if dev != (max_step is not None):
+        raise ValueError("causal_attn: max_step goes with a device tensor as step, and such a step needs it")
+    top = max_step if dev else step
+    if not 0 <= top < T:
+        raise ValueError(f"causal_attn: {'max_step' if dev else 'step'} = {top} must lie in [0, {T}), the cache capacity")
     if window < 0:
         raise ValueError(f"causal_attn: window = {window} must be 0 (none) or a positive count")
-    s0 = max(0, step - window + 1) // CAUSAL_ATTN_STEP_SLICE if window else 0
-    need = B * Hq * (step // CAUSAL_ATTN_STEP_SLICE + 1 - s0) * CAUSAL_ATTN_STEP_PART
+    if dev:
+        need = B * Hq * causal_attn_step_slices(max_step, window) * CAUSAL_ATTN_STEP_PART
+    else:
+        s0 = max(0, step - window + 1) // CAUSAL_ATTN_STEP_SLICE if window else 0
+        need = B * Hq * (step // CAUSAL_ATTN_STEP_SLICE + 1 - s0) * CAUSAL_ATTN_STEP_PART
     _operands("causal_attn", ("q", q, BF16, (B, -nq), 16, True), ("k", k, BF16, (B * T, -nkv), 16, True),
               ("vt", vt, BF16, (B, nkv, -T), 16, True), ("out", out, BF16, (B, -nq), 16, True), ("row_start", row_start, I32, (B,), 4),
               ("k_new", k_new, BF16, (B, -nkv), 16, True), ("v_new", v_new, BF16, (B, -nkv), 16, True),
-              ("partials", partials, F32, (-need,), 16))
-    live = min(step + 1, window) if window else step + 1
+              ("partials", partials, F32, (-need,), 16), ("step", step if dev else None, I32, (1,), 4))
+    live = min(top + 1, window) if window else top + 1
+    if dev:
+        with _timed("causal_attn_step", 4.0 * B * Hq * live * GEMMA_HEAD_DIM, 4.0 * B * Hkv * live * GEMMA_HEAD_DIM):
+            check(_lib.load().ltxk_causal_attn_dev_step(_p(q), q.stride(0), _p(k_new), k_new.stride(0), _p(v_new), v_new.stride(0), _p(k),
+                                                        k.stride(0), _p(vt), vt.stride(1), _p(out), out.stride(0), _p(row_start), B, Hq, Hkv, T,
+                                                        _p(step), max_step, window, scale, _p(partials), partials.numel(), _stream()),
+                  "ltxk_causal_attn_dev_step")
+        return out
     with _timed("causal_attn_step", 4.0 * B * Hq * live * GEMMA_HEAD_DIM, 4.0 * B * Hkv * live * GEMMA_HEAD_DIM):
         check(_lib.load().ltxk_causal_attn_step(_p(q), q.stride(0), _p(k_new), k_new.stride(0), _p(v_new), v_new.stride(0), _p(k), k.stride(0),
                                                 _p(vt), vt.stride(1), _p(out), out.stride(0), _p(row_start), B, Hq, Hkv, T, step, window,
                                                 scale, _p(partials), partials.numel(), _stream()), "ltxk_causal_attn_step")
     return out
+
+
+SAMPLE_CHUNK = 2048           # logits per workgroup of ltxk_sample_rows: the chunks partial maxima and sums are merged over
+SAMPLE_DEPTH_BASE = 17        # sequential fp32 additions behind a prefix sum inside a chunk; one more per chunk (csrc/sample.hip)
+SAMPLE_MAX_B, SAMPLE_MAX_CTX, SAMPLE_MAX_EOS = 8, 64, 8
+
+
+def sample_depth(V: int) -> int:
+    """The longest sequential fp32 addition chain behind a prefix sum of ltxk_sample_rows over V logits."""
+    return SAMPLE_DEPTH_BASE + -(-V // SAMPLE_CHUNK)
+
+
+def sample_workspace_floats(B: int, V: int) -> int:
+    """fp32 elements of ``sample_rows``' workspace: per row and chunk a maximum, its index and a sum."""
+    return 3 * B * -(-V // SAMPLE_CHUNK)
+
+
+def sample_rows(logits, ctl, done, next_ids, history, hist_len, tokens_out, eos, uniforms, workspace, *, temperature: float,
+                penalty: float = 1.0, rep_ctx: int = 0, draw: bool = True, advance: bool = True) -> None:
+    """ltxk_sample_rows: one token per row of ``logits`` (B, V) bf16 (rows with unit inner stride; 1 <= B <= 8, V % 8 == 0)
+    against the decode state on the device - every operand a tensor: ``ctl`` (3) = {n, pos, live}, ``done`` (B), ``next_ids`` (B),
+    ``history`` (B, Hcap) with ``hist_len`` (B), ``tokens_out`` (B, Nmax), ``eos`` (n_eos <= 8), all int32; ``uniforms`` (Nmax, B)
+    fp32 in [0, 1) (None at temperature 0); ``workspace`` fp32 of at least ``sample_workspace_floats(B, V)`` elements.
+    ``draw``: the repetition penalty over the last ``rep_ctx`` <= 64 ids of the row's history (a set), then the smallest argmax
+    at ``temperature`` 0, else the inverse CDF of softmax(l' / temperature) at uniforms[n, b], then the bookkeeping (include/ltxk.h).
+    ``advance``: ctl = {n + 1, pos + 1, rows not done}, a launch of its own behind the draw - a decode step draws first
+    (``advance=False``), feeds ``next_ids`` at ctl's pos and advances last (``draw=False``).  n >= Nmax: nothing is stored.
+    (The tensor parameters carry no annotation: tests/test_ops_shims_cpu.py finds the shims of its closed table by their annotated
+    tensor parameters.  This shim's refusals, operand by operand, are in tests/test_gemma_sample_cpu.py.)"""
+    if not (draw or advance):
+        raise ValueError("sample_rows: neither draw nor advance")
+    if not isinstance(logits, torch.Tensor) or not isinstance(tokens_out, torch.Tensor):
+        raise TypeError("sample_rows: logits and tokens_out must be tensors")
+    B, V = _dims("sample_rows", "logits", logits, BF16, 2)
+    Nmax = _dims("sample_rows", "tokens_out", tokens_out, I32, 2)[1]
+    Hcap = _dims("sample_rows", "history", history, I32, 2)[1]
+    n_eos = _dims("sample_rows", "eos", eos, I32, 1)[0]
+    if not 1 <= B <= SAMPLE_MAX_B or V < 8 or V % 8 or logits.stride(0) % 8:
+        raise ValueError(f"sample_rows: logits must be (B, V) with 1 <= B <= {SAMPLE_MAX_B}, V a positive multiple of 8 and rows a "
+                         f"multiple of 8 elements apart, got {tuple(logits.shape)} with strides {logits.stride()}")
+    if Nmax < 1 or Hcap < 1 or n_eos > SAMPLE_MAX_EOS:
+        raise ValueError(f"sample_rows: tokens_out (B, Nmax >= 1), history (B, Hcap >= 1) and eos (<= {SAMPLE_MAX_EOS}), got Nmax = {Nmax}, "
+                         f"Hcap = {Hcap}, {n_eos} eos ids")
+    if not 0 <= rep_ctx <= SAMPLE_MAX_CTX:
+        raise ValueError(f"sample_rows: rep_ctx = {rep_ctx} must lie in [0, {SAMPLE_MAX_CTX}]")
+    if not (0.0 <= temperature < math.inf and 0.0 < penalty < math.inf):
+        raise ValueError(f"sample_rows: temperature = {temperature} must be >= 0 and penalty = {penalty} positive, both finite")
+    if temperature > 0 and uniforms is None:
+        raise ValueError("sample_rows: temperature > 0 needs uniforms")
+    _operands("sample_rows", ("logits", logits, BF16, (B, V), 16, True), ("ctl", ctl, I32, (3,), 4), ("done", done, I32, (B,), 4),
+              ("next_ids", next_ids, I32, (B,), 4), ("history", history, I32, (B, Hcap), 4), ("hist_len", hist_len, I32, (B,), 4),
+              ("tokens_out", tokens_out, I32, (B, Nmax), 4), ("eos", eos, I32, (n_eos,), 4), ("uniforms", uniforms, F32, (Nmax, B), 4),
+              ("workspace", workspace, F32, (-sample_workspace_floats(B, V),), 4))
+    a = SampleArgs()
+    a.struct_bytes = ctypes.sizeof(SampleArgs)
+    a.B, a.V, a.ld, a.n_max, a.hist_cap, a.rep_ctx, a.n_eos = B, V, logits.stride(0), Nmax, Hcap, rep_ctx, n_eos
+    a.flags = (_lib.SAMPLE_DRAW if draw else 0) | (_lib.SAMPLE_ADVANCE if advance else 0)
+    a.temperature, a.penalty = temperature, penalty
+    a.logits, a.ctl, a.done, a.next_ids, a.history, a.hist_len = _p(logits), _p(ctl), _p(done), _p(next_ids), _p(history), _p(hist_len)
+    a.tokens_out, a.eos, a.uniforms, a.workspace, a.workspace_bytes = _p(tokens_out), _p(eos) if n_eos else None, _p(uniforms), _p(workspace), workspace.numel() * 4
+    with _timed("sample_rows", 0.0, (2.0 if temperature == 0 else 4.0) * B * V if draw else 0.0):
+        check(_lib.load().ltxk_sample_rows(ctypes.byref(a), _stream()), "ltxk_sample_rows")
 
 
 # ------------------------------------------------------------------- VAE / upsampler (csrc/conv3d.hip, csrc/vae_ops.hip)
