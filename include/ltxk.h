@@ -153,6 +153,18 @@ int ltxk_gemm_w8a8_plan(const ltxk_gemm_args* args, struct ltxk_gemm_plan* plan)
  * so the result equals ltxk_gemm_w8's within the rounding bound, not bit for bit.)                                        */
 int ltxk_gemv_w8(const ltxk_gemm_args* args, const float* w_scale, void* stream);
 
+/* The same weight stream on an OCP MXFP4 panel: out[m,n] = r(A[m,:] . w[n,:] + bias[n]) in fp32 with
+ * w[n,k] = e2m1(code[n,k]) * 2^(E[n, k/32] - 127), for 1 <= M <= 8 rows.  args->W: the (N, K/2) code bytes, element 2i in the low
+ * nibble of byte i (torch.float4_e2m1fn_x2's order), 16-byte aligned; w_block_scales: the (N, K/32) e8m0 bytes, row-contiguous,
+ * 4-byte aligned (E = 255 is NaN, as the format defines it; the project's quantiser never writes it).  A, out and bias as for
+ * ltxk_gemv_w8; K >= 32 and K % 32 == 0, any N >= 1, LTXK_EPI_BIAS only, and resid, gate, gate_row, out2, n_split,
+ * out_tokens_per_batch, sumsq and workspace all zero: anything else is LTXK_EINVAL.  One launch (csrc/gemv4.hip): a lane's
+ * 16-byte load is 32 codes = one scale block, widened two at a time by v_cvt_scalef32_pk_f32_fp4 with the block's scale (exact),
+ * then per lane fp32 FMAs over its k in ascending order into an even-k and an odd-k accumulator, their sum, the wave's
+ * butterfly, the bias as one fp32 add, one rounding to bf16.  No atomics, no K slices: the bits of out[m,n] are a function of
+ * row m of A, row n of the codes, its scale row and bias[n] alone, whatever M, N and the other rows are.                  */
+int ltxk_gemv_w4(const ltxk_gemm_args* args, const uint8_t* w_block_scales, void* stream);
+
 /* Row quantiser in front of ltxk_gemm_w8a8: x (M,K) bf16 with row stride lda -> q (M,K) e4m3fn bytes with row stride ldq
  * (bytes) and a_scale (M) fp32.  Per row, no special cases: amax = max|x|; scale = max(amax, 2^-64) / 448 in fp32 (correctly
  * rounded); q = e4m3 round-to-nearest-even, saturating, of fp32(x) / scale (IEEE fp32 division).  A zero row gives code 0.

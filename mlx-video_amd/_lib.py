@@ -149,6 +149,7 @@ SIGNATURES = {
     "ltxk_gemm_plan": (c_int32, [POINTER(GemmArgs), POINTER(GemmPlan)]),
     "ltxk_gemm_w8": (c_int32, [POINTER(GemmArgs), c_void_p, c_void_p]),
     "ltxk_gemv_w8": (c_int32, [POINTER(GemmArgs), c_void_p, c_void_p]),
+    "ltxk_gemv_w4": (c_int32, [POINTER(GemmArgs), c_void_p, c_void_p]),
     "ltxk_gemm_w8_plan": (c_int32, [POINTER(GemmArgs), POINTER(GemmPlan)]),
     "ltxk_gemm_w8a8": (c_int32, [POINTER(GemmArgs), c_void_p, c_void_p, c_void_p]),
     "ltxk_gemm_w8a8_plan": (c_int32, [POINTER(GemmArgs), POINTER(GemmPlan)]),

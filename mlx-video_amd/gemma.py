@@ -40,7 +40,7 @@ import torch
 
 from . import ops
 from .text_connector import mask_row_counts
-from .weights import FP8_SCALINGS, SCALE_SUFFIX, quantize_fp8
+from .weights import FP8_SCALINGS, MXFP4_BLOCK, SCALE_SUFFIX, quantize_fp8, quantize_mxfp4
 
 BF16 = torch.bfloat16
 FP8 = torch.float8_e4m3fn
@@ -399,12 +399,31 @@ class GemmaGenerator:
 
     On an fp8 encoder with B <= ``ops.GEMV_MAX_M`` the GEMMs of ``GEMV_SHAPES`` run as ltxk_gemv_w8 (``ops.gemm(gemv=True)``): one
     launch that streams the e4m3 panel straight to registers, and a batch row's bits then do not depend on B.  ``gemv=False``
-    keeps every one of them on the split-K ltxk_gemm_w8 (the measurement's other arm); a bf16 encoder's step is unchanged."""
+    keeps every one of them on the split-K ltxk_gemm_w8 (the measurement's other arm); a bf16 encoder's step is unchanged.
+
+    ``decode_panels="mxfp4"`` (opt-in; None is the generator above, launch for launch): the generator builds, layer by layer, an
+    OCP MXFP4 copy (``weights.quantize_mxfp4``: e2m1 codes, one e8m0 scale per 32 k; 4.25 bits per weight) of those of q|k|v, o,
+    gate|up, down and the tied table whose ``GEMV4_SHAPES`` entry is true when it is built (``routing4`` keeps that table; a
+    subclass with another ``GEMV4_SHAPES`` routes otherwise), from the encoder's panels - a bf16 panel as it is, an fp8 panel
+    as code * row scale in fp32, in row chunks, so that never more than one widened chunk is held - and ``step`` / ``device_step`` run a GEMM of ``GEMV4_SHAPES``
+    at B <= ``GEMV4_MAX_B`` as ltxk_gemv_w4 on the copy (otherwise the path above, on the encoder's panel).  The table copy
+    serves the steps' logits only: the embedding gather and ``prefill`` (its logits included) stay on the encoder's panels, so
+    the K / V of the prompt come from the bf16 / fp8 weights and those of the decoded tokens from the MXFP4 ones - the two are
+    4-bit roundings apart, as a 4-bit model's cache would be against its 16-bit prefill.  The hidden states that condition the
+    DiT never touch the copy.  The routing is host-static and the panels are fixed buffers, so the device loop and its graph
+    replay work unchanged.  Every K (hidden size, Hq * 256, intermediate size) must be a multiple of 32."""
 
     # which of the step's five GEMMs take the row-streaming kernel on fp8 panels (DESIGN.md 5p: decided per shape by measurement)
     GEMV_SHAPES = {"qkv": True, "o": True, "gu": True, "down": True, "logits": True}
+    # which of them take ltxk_gemv_w4 on MXFP4 decode panels (DESIGN.md 5r: decided per shape by measurement at B = 1 - q|k|v and o
+    # are launch-bound 12 - 14 us either way and stay on the encoder's panel), and up to which batch: at 5 - 8 rows ltxk_gemv_w8 is
+    # the faster kernel on four of the five shapes.  Both were measured against ltxk_gemv_w8 on an fp8 encoder only; on a bf16
+    # encoder the other path is the split-K bf16 GEMM, which nobody has measured against ltxk_gemv_w4
+    GEMV4_SHAPES = {"qkv": False, "o": False, "gu": True, "down": True, "logits": True}
+    GEMV4_MAX_B = 4
+    MXFP4_CHUNK_ROWS = 8192          # rows widened to fp32 at a time while the copy is built
 
-    def __init__(self, encoder: GemmaEncoder, gemv: bool = True):
+    def __init__(self, encoder: GemmaEncoder, gemv: bool = True, decode_panels: Optional[str] = None):
         if encoder.cfg.final_logit_softcapping is not None:
             raise ValueError(f"GemmaGenerator: final_logit_softcapping={encoder.cfg.final_logit_softcapping}: logit soft-capping is not supported")
         if encoder.cfg.num_attention_heads // encoder.cfg.num_key_value_heads > 16:
@@ -413,9 +432,68 @@ class GemmaGenerator:
             raise ValueError(f"GemmaGenerator: the vocabulary {encoder.vocab} must be a multiple of 8 (the logits GEMM)")
         self.enc, self.cfg = encoder, encoder.cfg
         self.gemv = bool(gemv) and encoder.weight_dtype == FP8
+        if decode_panels not in (None, "mxfp4"):
+            raise ValueError(f"GemmaGenerator: decode_panels={decode_panels!r}: expected None or 'mxfp4'")
+        self.decode_panels = decode_panels
+        # per layer {"qkv" | "o" | "gu" | "down": (codes, block_scales)}, and the table's pair; None without decode_panels
+        self.panels4: Optional[List[Dict[str, Tuple[torch.Tensor, torch.Tensor]]]] = None
+        self.table4: Optional[Tuple[torch.Tensor, torch.Tensor]] = None
+        self.routing4: Dict[str, bool] = {}
+        if decode_panels == "mxfp4":
+            c = encoder.cfg
+            for name, k in (("hidden_size", c.hidden_size), ("num_attention_heads * 256", c.num_attention_heads * HEAD_DIM),
+                            ("intermediate_size", c.intermediate_size)):
+                if k % MXFP4_BLOCK:
+                    raise ValueError(f"GemmaGenerator: decode_panels='mxfp4' needs {name} = {k} to be a multiple of {MXFP4_BLOCK}")
+            # only the shapes routed to ltxk_gemv_w4 get a copy: the table as it stands when the generator is built
+            self.routing4 = dict(self.GEMV4_SHAPES)
+            self.panels4 = [{n: self._mxfp4(ly[n], ly[n + "_s"]) for n in ("qkv", "o", "gu", "down") if self.routing4[n]}
+                            for ly in encoder.layers]
+            if self.routing4["logits"]:
+                self.table4 = self._mxfp4(encoder.embed, encoder.embed_row_scale)
 
-    def _gemm(self, which: str, a: torch.Tensor, w: torch.Tensor, w_scale: Optional[torch.Tensor], out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """One M = B-row GEMM of a step: ltxk_gemv_w8 where the shape is routed there, else the weight-streaming split-K form."""
+    def _mxfp4(self, w: torch.Tensor, row_scale: Optional[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The MXFP4 pair of one of the encoder's panels: rows are independent, so it is built ``MXFP4_CHUNK_ROWS`` rows at a time
+        from the chunk widened to fp32 (an fp8 chunk times its rows' scales)."""
+        codes = torch.empty((w.shape[0], w.shape[1] // 2), dtype=torch.uint8, device=w.device)
+        scales = torch.empty((w.shape[0], w.shape[1] // MXFP4_BLOCK), dtype=torch.uint8, device=w.device)
+        for r0 in range(0, w.shape[0], self.MXFP4_CHUNK_ROWS):
+            r1 = min(r0 + self.MXFP4_CHUNK_ROWS, w.shape[0])
+            wide = w[r0:r1].to(torch.float32)
+            if row_scale is not None:
+                wide = wide * row_scale[r0:r1, None]
+            codes[r0:r1], scales[r0:r1] = quantize_mxfp4(wide)
+            del wide
+        return codes, scales
+
+    def _p4(self, layer: Optional[int], which: str) -> Optional[Tuple[torch.Tensor, torch.Tensor]]:
+        """The MXFP4 pair a step's GEMM is routed to (``layer`` None: the table), or None: the encoder's panel."""
+        if self.panels4 is None or not self.routing4[which]:
+            return None
+        return self.table4 if layer is None else self.panels4[layer][which]
+
+    def decode_weight_bytes(self, B: int = 1) -> int:
+        """The weight bytes one decoded token of ``B`` batch rows streams: the five GEMMs' panels as ``step`` routes them (an MXFP4
+        pair's codes and block scales, or the encoder's panel and its row scales), the norm weights, and the B gathered rows of
+        the embedding table."""
+        e = self.enc
+        nb = lambda *ts: sum(t.numel() * t.element_size() for t in ts if isinstance(t, torch.Tensor))      # noqa: E731
+        w4 = B <= min(self.GEMV4_MAX_B, ops.GEMV4_MAX_M)
+        total = nb(e.norm) + B * (e.embed.shape[1] * e.embed.element_size() + (4 if e.embed_row_scale is not None else 0))
+        for i, ly in enumerate(e.layers):
+            total += nb(ly["qn"], ly["kn"], ly["n_in"], ly["n_post_attn"], ly["n_pre_ff"], ly["n_post_ff"])
+            for n in ("qkv", "o", "gu", "down"):
+                p4 = self._p4(i, n) if w4 else None
+                total += nb(*p4) if p4 is not None else nb(ly[n], ly[n + "_s"])
+        p4 = self._p4(None, "logits") if w4 else None
+        return total + (nb(*p4) if p4 is not None else nb(e.embed, e.embed_row_scale))
+
+    def _gemm(self, which: str, a: torch.Tensor, w: torch.Tensor, w_scale: Optional[torch.Tensor], out: Optional[torch.Tensor] = None,
+              p4: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> torch.Tensor:
+        """One M = B-row GEMM of a step: ltxk_gemv_w4 on the MXFP4 pair ``p4`` when the step hands one over (``_p4``), else
+        ltxk_gemv_w8 where the shape is routed there, else the weight-streaming split-K form."""
+        if p4 is not None and a.shape[0] <= min(self.GEMV4_MAX_B, ops.GEMV4_MAX_M):
+            return ops.gemv_w4(a, p4[0], p4[1], None, out=out)
         if self.gemv and self.GEMV_SHAPES[which] and a.shape[0] <= ops.GEMV_MAX_M and a.shape[1] % 16 == 0:
             return ops.gemm(a, w, None, out=out, w_scale=w_scale, gemv=True)
         return ops.gemm(a, w, None, out=out, split_k=True, w_scale=w_scale)
@@ -464,22 +542,22 @@ class GemmaGenerator:
         for i, ly in enumerate(e.layers):
             cos, sin = e._tables(cap, ly["is_global"])
             ops.rmsnorm_weight_rows(x, ly["n_in"], c.rms_norm_eps, out=nx)
-            self._gemm("qkv", nx, ly["qkv"], ly["qkv_s"], qkv)
+            self._gemm("qkv", nx, ly["qkv"], ly["qkv_s"], qkv, self._p4(i, "qkv"))
             ops.headnorm_rope(qkv, Hq, Hkv, ly["qn"], ly["kn"], cos[pos:pos + 1], sin[pos:pos + 1], 1, c.rms_norm_eps)
             ops.causal_attn(qkv[:, :nq], cache.k[i].view(B * cap, nkv), cache.vt[i], att, cache.row_start, B, Hq, Hkv, cap, e.scale,
                             window=ly["window"], step=pos, k_new=qkv[:, nq:nq + nkv], v_new=qkv[:, nq + nkv:], partials=cache.partials)
-            self._gemm("o", att, ly["o"], ly["o_s"], po)
+            self._gemm("o", att, ly["o"], ly["o_s"], po, self._p4(i, "o"))
             y = states[i + 1] if i + 1 < L else nx.new_empty((B, D))
             ops.rmsnorm_weight_rows(po, ly["n_post_attn"], c.rms_norm_eps, resid=x, out=y)
             ops.rmsnorm_weight_rows(y, ly["n_pre_ff"], c.rms_norm_eps, out=nx)
-            self._gemm("gu", nx, ly["gu"], ly["gu_s"], gu)
+            self._gemm("gu", nx, ly["gu"], ly["gu_s"], gu, self._p4(i, "gu"))
             h = ops.geglu_tanh_(gu)
-            self._gemm("down", h, ly["down"], ly["down_s"], po)
+            self._gemm("down", h, ly["down"], ly["down_s"], po, self._p4(i, "down"))
             ops.rmsnorm_weight_rows(po, ly["n_post_ff"], c.rms_norm_eps, resid=y, out=y)
             x = y
         ops.rmsnorm_weight_rows(x, e.norm, c.rms_norm_eps, out=states[L])
         cache.length = pos + 1
-        logits = self._logits(states[L])
+        logits = self._gemm("logits", states[L], e.embed, e.embed_row_scale, None, self._p4(None, "logits")).to(torch.float32)
         return (logits, states) if return_states else logits
 
     def sample(self, state: GemmaDecodeState, temperature: float, repetition_penalty: float, repetition_context: int,
@@ -514,22 +592,22 @@ class GemmaGenerator:
         for i, ly in enumerate(e.layers):
             cos, sin = e._tables(cap, ly["is_global"])
             ops.rmsnorm_weight_rows(x, ly["n_in"], c.rms_norm_eps, out=nx)
-            self._gemm("qkv", nx, ly["qkv"], ly["qkv_s"], qkv)
+            self._gemm("qkv", nx, ly["qkv"], ly["qkv_s"], qkv, self._p4(i, "qkv"))
             ops.headnorm_rope(qkv, Hq, Hkv, ly["qn"], ly["kn"], cos, sin, cap, c.rms_norm_eps, pos=pos)
             ops.causal_attn(qkv[:, :nq], cache.k[i].view(B * cap, nkv), cache.vt[i], att, cache.row_start, B, Hq, Hkv, cap, e.scale,
                             window=ly["window"], step=pos, max_step=cap - 1, k_new=qkv[:, nq:nq + nkv], v_new=qkv[:, nq + nkv:],
                             partials=cache.partials)
-            self._gemm("o", att, ly["o"], ly["o_s"], po)
+            self._gemm("o", att, ly["o"], ly["o_s"], po, self._p4(i, "o"))
             y = state.x[(i + 1) % 2]
             ops.rmsnorm_weight_rows(po, ly["n_post_attn"], c.rms_norm_eps, resid=x, out=y)
             ops.rmsnorm_weight_rows(y, ly["n_pre_ff"], c.rms_norm_eps, out=nx)
-            self._gemm("gu", nx, ly["gu"], ly["gu_s"], gu)
+            self._gemm("gu", nx, ly["gu"], ly["gu_s"], gu, self._p4(i, "gu"))
             h = ops.geglu_tanh_(gu)
-            self._gemm("down", h, ly["down"], ly["down_s"], po)
+            self._gemm("down", h, ly["down"], ly["down_s"], po, self._p4(i, "down"))
             ops.rmsnorm_weight_rows(po, ly["n_post_ff"], c.rms_norm_eps, resid=y, out=y)
             x = y
         ops.rmsnorm_weight_rows(x, e.norm, c.rms_norm_eps, out=nx)
-        self._gemm("logits", nx, e.embed, e.embed_row_scale, state.logits)
+        self._gemm("logits", nx, e.embed, e.embed_row_scale, state.logits, self._p4(None, "logits"))
         self.sample(state, temperature, repetition_penalty, repetition_context, draw=False, advance=True)
 
     def _generate_device(self, input_ids, attention_mask, max_tokens, temperature, repetition_penalty, repetition_context, eos_ids, seed,
@@ -639,13 +717,16 @@ def clean_response(text: str) -> str:
 
 
 def enhance_prompt(generator: GemmaGenerator, tokenizer, prompt: str, system_prompt: Optional[str] = None, max_tokens: int = 512,
-                   temperature: float = 0.7, seed: int = 42, device_loop: bool = False, **sampling) -> str:
+                   temperature: float = 0.7, seed: int = 42, device_loop: bool = False, mxfp4: bool = False, **sampling) -> str:
     """The user's short prompt rewritten by the model into the long descriptive one LTX-2 was trained on (the reference's
     ``enhance_t2v``, text_encoder.py:1023-1135).  ``tokenizer``: a ``tokenizers.Tokenizer`` (``load_tokenizer``).  Only the new
     tokens are decoded (special tokens skipped) and cleaned; an empty result keeps ``prompt`` and warns.  ``sampling``: further
     keywords of ``GemmaGenerator.generate`` (repetition_penalty, repetition_context, eos_ids, graph, sync_every).
     ``device_loop``: sampling and the token loop on the device, the step replayed as a graph (``generate``); at temperature > 0
-    the same ``seed`` then gives other tokens than the host loop does."""
+    the same ``seed`` then gives other tokens than the host loop does.  ``mxfp4``: decode on 4-bit panels (opt-in; the text encoding is not
+    affected) - a ``generator`` built without ``decode_panels="mxfp4"`` is replaced by one with them on the same encoder."""
+    if mxfp4 and generator.decode_panels != "mxfp4":
+        generator = GemmaGenerator(generator.enc, gemv=generator.gemv, decode_panels="mxfp4")
     text = chat_prompt(system_prompt or DEFAULT_ENHANCE_SYSTEM_PROMPT, prompt)
     tokenizer.no_padding(); tokenizer.no_truncation()
     ids = list(tokenizer.encode(text).ids)

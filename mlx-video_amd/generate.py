@@ -259,7 +259,7 @@ def _check_enhance(gemma, gemma_repo, text_encoder_repo, tokenizer_path, prompt_
 
 
 def _enhance_prompt(gemma, gemma_repo, tokenizer_path, prompt, system_prompt, max_tokens, temperature, seed, dev, verbose, fp8=None,
-                    device_loop=False):
+                    device_loop=False, mxfp4=False):
     """(the GemmaEncoder, the enhanced prompt): the encoder is built here when only ``gemma_repo`` was given, and handed on so that
     the text encode that follows reuses its panels."""
     from .gemma import GemmaConfig, GemmaEncoder, GemmaGenerator, enhance_prompt, load_tokenizer
@@ -267,8 +267,10 @@ def _enhance_prompt(gemma, gemma_repo, tokenizer_path, prompt, system_prompt, ma
         from .weights import gemma_weights
         gemma = GemmaEncoder(gemma_weights(gemma_repo, dev, fp8=fp8), GemmaConfig.from_json(gemma_repo), fp8=fp8)
     tok = load_tokenizer(tokenizer_path or gemma_repo)
-    enhanced = enhance_prompt(GemmaGenerator(gemma), tok, prompt, system_prompt, max_tokens=max_tokens, temperature=temperature, seed=seed,
-                              **({"device_loop": True} if device_loop else {}))          # (off adds no keyword: today's call)
+    generator = GemmaGenerator(gemma, **({"decode_panels": "mxfp4"} if mxfp4 else {}))
+    enhanced = enhance_prompt(generator, tok, prompt, system_prompt, max_tokens=max_tokens, temperature=temperature, seed=seed,
+                              **({"device_loop": True} if device_loop else {}),          # (off adds no keyword: today's call)
+                              **({"mxfp4": True} if mxfp4 else {}))
     if verbose:
         print(f"enhanced prompt: {enhanced}")
     return gemma, enhanced
@@ -307,7 +309,7 @@ def generate_video(model_repo: Optional[str] = None, text_encoder_repo: Optional
                    audio_model_repo: Optional[str] = None, audio_steps: int = 8, audio_transformer: Optional[LTXModel] = None,
                    audio_prompt_embeds: Optional[torch.Tensor] = None, av_transformer=None,
                    audio_negative_prompt_embeds: Optional[torch.Tensor] = None, fp8_text_encoder: bool = False,
-                   enhance_device_loop: bool = False) -> np.ndarray:
+                   enhance_device_loop: bool = False, enhance_mxfp4: bool = False) -> np.ndarray:
     """See the module docstring.  Returns uint8 frames (F,H,W,3) (generate.py:4195-4197).
     ``hoist_context`` (not in the reference, off by default): the part of the forward that depends on the text context only -
     caption projection and the 48 cross-attention K / V^T projections, 3.37 TFLOP that the reference recomputes in every forward
@@ -352,6 +354,10 @@ def generate_video(model_repo: Optional[str] = None, text_encoder_repo: Optional
     by ``ops.sample_rows``, the decode step recorded once as a graph and replayed.  Off, the default, the host loop
     runs.  At ``temperature`` 0 both give the same prompt; above it the device loop consumes ``seed`` differently from the host
     loop's ``torch.multinomial``, so the same seed gives another rewrite.  A ValueError without ``enhance_prompt``.
+    ``enhance_mxfp4`` (--enhance-mxfp4; not in the reference CLI; opt-in): the enhancement decodes on an OCP MXFP4 copy of the
+    encoder's panels (``GemmaGenerator(decode_panels="mxfp4")``, ltxk_gemv_w4: 4.25 bits per weight streamed per token; DESIGN.md
+    5r).  The rewrite is a 4-bit model's; the text encoding that conditions the DiT stays on the encoder's own bf16 / fp8 panels
+    and is not affected.  It composes with ``fp8_text_encoder`` and ``enhance_device_loop``.  A ValueError without ``enhance_prompt``.
     ``audio_latents`` (--audio-latents FILE): finished audio latents (B, 8, T, 16) - the reference's own layout - decoded after the
     VAE decode under an ``audio_decode`` phase by ``audio_decoder`` / ``vocoder`` (``audio_vae.AudioDecoder`` / ``Vocoder``; loaded
     from ``model_repo`` when not given) into a stereo 24 kHz waveform.  It is written to ``output_audio`` (--output-audio PATH; by
@@ -410,6 +416,8 @@ def generate_video(model_repo: Optional[str] = None, text_encoder_repo: Optional
             raise ValueError("--audio-steps must be between 1 and 8.")
     if enhance_device_loop and not enhance_prompt:
         raise ValueError("enhance_device_loop (--enhance-device-loop) is a mode of enhance_prompt (--enhance-prompt), which is off")
+    if enhance_mxfp4 and not enhance_prompt:
+        raise ValueError("enhance_mxfp4 (--enhance-mxfp4) is a mode of enhance_prompt (--enhance-prompt), which is off")
     if enhance_prompt:
         _check_enhance(gemma, gemma_repo, text_encoder_repo, tokenizer_path, prompt_tokens, prompt_embeds, gemma_hidden_states, text_encoder)
     images_list = list(images or [])
@@ -545,7 +553,8 @@ def generate_video(model_repo: Optional[str] = None, text_encoder_repo: Optional
     if enhance_prompt:
         with timer.phase("prompt_enhance"):
             gemma, prompt = _enhance_prompt(gemma, gemma_repo, tokenizer_path, prompt, enhance_system_prompt, max_tokens, temperature,
-                                            seed, dev, verbose, **({"device_loop": True} if enhance_device_loop else {}), **gemma_fp8)
+                                            seed, dev, verbose, **({"device_loop": True} if enhance_device_loop else {}),
+                                            **({"mxfp4": True} if enhance_mxfp4 else {}), **gemma_fp8)
     if prompt_embeds is None and text_encoder is None and (gemma is not None or gemma_repo is not None):
         hs, m = _encode_gemma(gemma, gemma_repo, tokenizer_path, prompt, negative_prompt, prompt_tokens, negative_prompt_tokens, dev,
                               **gemma_fp8)
@@ -879,6 +888,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--enhance-device-loop", action="store_true",
                     help="(not in the reference CLI) run --enhance-prompt's token loop on the device: sampling in a HIP kernel, the decode "
                          "step replayed as one graph; at --temperature > 0 the same --seed gives other tokens than the host loop")
+    ap.add_argument("--enhance-mxfp4", action="store_true",
+                    help="(not in the reference CLI) decode --enhance-prompt on 4-bit (OCP MXFP4) panels built from the Gemma weights: "
+                         "opt-in, about half the bytes per token of --fp8-text-encoder; the text encoding is unaffected")
     ap.add_argument("--enhance-system-prompt", type=str, default=None, metavar="FILE",
                     help="(not in the reference CLI) text file with the system prompt of --enhance-prompt (default: the package's own)")
     ap.add_argument("--synthetic", action="store_true", help="random-init weights + random text embeddings (no checkpoints offline)")
@@ -980,6 +992,8 @@ def main(argv: Optional[Sequence[str]] = None) -> None:
         raise ValueError("--fp8-activations needs --enable-fp8: fp8 activations multiply fp8 weight panels")
     if args.fp8_text_encoder and not args.gemma_repo:
         raise ValueError("--fp8-text-encoder needs --gemma-repo: it is the Gemma-3 model built from that directory that keeps fp8 panels")
+    if args.enhance_mxfp4 and not args.enhance_prompt:
+        raise ValueError("--enhance-mxfp4 is a mode of --enhance-prompt, which is off")
     is_dev = args.pipeline == "dev"
     dev = torch.device("cuda:0")
     kw = {}
@@ -1049,6 +1063,8 @@ def main(argv: Optional[Sequence[str]] = None) -> None:
         kw.update(enhance_prompt=True, max_tokens=args.max_tokens, temperature=args.temperature)
         if args.enhance_device_loop:
             kw["enhance_device_loop"] = True
+        if args.enhance_mxfp4:
+            kw["enhance_mxfp4"] = True
         if args.enhance_system_prompt:
             kw["enhance_system_prompt"] = Path(args.enhance_system_prompt).read_text(encoding="utf-8")
     generate_video(model_repo=args.model_repo, prompt=args.prompt, pipeline=PipelineType(args.pipeline),

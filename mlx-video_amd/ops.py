@@ -18,6 +18,7 @@ import torch
 
 from . import _lib
 from ._lib import AttnArgs, CausalAttnArgs, Conv3dArgs, ConvTapsArgs, GemmArgs, GemmGroupedArgs, GuiderArgs, SampleArgs, StepArgs, check
+from .weights import MXFP4_BLOCK          # k per e8m0 block scale
 
 EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_SILU, EPI_BIAS_GATE_RES, EPI_BIAS_RES, EPI_SCALE_RES = 0, 1, 2, 3, 4, 5
 BF16 = torch.bfloat16
@@ -284,6 +285,37 @@ def _gemv(a, w, bias, epilogue, out, w_scale, **unsupported) -> torch.Tensor:
     args.epilogue, args.alpha = EPI_BIAS, 1.0
     with _timed("gemv_w8", 2.0 * M * N * K, 2.0 * (M * K + M * N) + 1.0 * N * K):
         check(_lib.load().ltxk_gemv_w8(ctypes.byref(args), _p(w_scale), _stream()), "ltxk_gemv_w8")
+    return out
+
+
+GEMV4_MAX_M = 8             # rows of one ltxk_gemv_w4 launch (csrc/gemv4.hip: no instance spills, so all 8)
+
+
+def gemv_w4(a, codes, block_scales, bias=None, out=None):
+    """out = a @ w.T + bias on an OCP MXFP4 panel (ltxk_gemv_w4): ``a`` (M, K) bf16, 1 <= M <= GEMV4_MAX_M, rows a multiple of 8
+    elements apart; ``codes`` (N, K/2) uint8, two e2m1 codes per byte, low nibble first; ``block_scales`` (N, K/32) uint8 e8m0
+    (``weights.quantize_mxfp4`` gives both); K % 32 == 0; ``bias`` (N) bf16; ``out`` (M, N) bf16 rows.  One launch, no workspace;
+    a row's bits depend on that row, the panel row, its scale row and its bias alone.  (Its refusals - dtype, shape and layout of
+    every operand, each before the device - are tabulated in tests/test_mxfp4_cpu.py.)"""
+    M, K = _dims("gemv_w4", "a", a, BF16, 2)
+    N = _dims("gemv_w4", "codes", codes, torch.uint8, 2)[0]
+    if not 1 <= M <= GEMV4_MAX_M:
+        raise ValueError(f"gemv_w4: `a` must have 1 to {GEMV4_MAX_M} rows, got {M}")
+    if K == 0 or K % MXFP4_BLOCK:
+        raise ValueError(f"gemv_w4: needs K % {MXFP4_BLOCK} == 0 (one scale per {MXFP4_BLOCK} k), got K = {K}")
+    if a.stride(0) % 8:
+        raise ValueError(f"gemv_w4: the rows of `a` must lie a multiple of 8 elements apart, got {a.stride(0)}")
+    _operands("gemv_w4", ("a", a, BF16, 2, 16, True), ("codes", codes, torch.uint8, (N, K // 2), 16),
+              ("block_scales", block_scales, torch.uint8, (N, K // MXFP4_BLOCK), 4), ("bias", bias, BF16, (N,), 2),
+              ("out", out, BF16, (M, N), 2, True))
+    if out is None:
+        out = torch.empty((M, N), dtype=BF16, device=a.device)
+    args = GemmArgs()
+    args.A, args.W, args.bias, args.out = _p(a), _p(codes), _p(bias), _p(out)
+    args.M, args.N, args.K, args.lda, args.ldo = M, N, K, a.stride(0), out.stride(0)
+    args.epilogue, args.alpha = EPI_BIAS, 1.0
+    with _timed("gemv_w4", 2.0 * M * N * K, 2.0 * (M * K + M * N) + 0.5 * N * K + 1.0 * N * (K // MXFP4_BLOCK)):
+        check(_lib.load().ltxk_gemv_w4(ctypes.byref(args), _p(block_scales), _stream()), "ltxk_gemv_w4")
     return out
 
 

@@ -88,6 +88,66 @@ def dequantize_fp8(w8: torch.Tensor, scale: Optional[torch.Tensor] = None, dtype
     return w.to(dtype)
 
 
+MXFP4_BLOCK = 32                    # OCP MXFP4: e2m1 elements, one e8m0 scale per 32 consecutive k
+# the e2m1 magnitudes by their 3-bit index (1 exponent-ish bit pair, 1 mantissa bit); code = sign << 3 | index
+_E2M1 = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+# midpoints between neighbouring magnitudes, and whether a tie at that midpoint goes UP (to the even index)
+_E2M1_MID = (0.25, 0.75, 1.25, 1.75, 2.5, 3.5, 5.0)
+
+
+def quantize_mxfp4(w: torch.Tensor):
+    """(N,K) float matrix, K % 32 == 0 -> (codes (N, K/2) uint8, block_scales (N, K/32) uint8): OCP MXFP4.  fp32 arithmetic on
+    the matrix's device.  Per row and block of 32 consecutive k: amax = max |w|; scale byte E = clamp(floor(log2 amax) - 2,
+    -127, 127) + 127 (the OCP rule, e2m1's emax = 2; floor(log2) read from the exponent field by ``frexp``), a zero block 127;
+    byte 255 (NaN) is never written.  Per element x = w / 2^(E-127) (a power of two: exact), code = the nearest of +-{0, 0.5, 1,
+    1.5, 2, 3, 4, 6}, ties to the even 3-bit magnitude index, |x| > 6 saturating to +-6, the sign bit kept (-0 stays -0).
+    Element 2i sits in the low nibble of byte i, 2i+1 in the high one (``torch.float4_e2m1fn_x2``'s order).
+    |w - dequantize_mxfp4| <= amax_block / 4, the worst case being the clamp at 6 (amax just below 8 x 2^(E-127))."""
+    if w.ndim != 2 or w.shape[1] == 0 or w.shape[1] % MXFP4_BLOCK:
+        raise ValueError(f"quantize_mxfp4: expected an (N, K) matrix with K a positive multiple of {MXFP4_BLOCK}, got shape {tuple(w.shape)}")
+    if not w.dtype.is_floating_point:
+        raise ValueError(f"quantize_mxfp4: expected a floating-point matrix, got {w.dtype}")
+    wf = w.to(torch.float32)
+    if not bool(torch.isfinite(wf).all()):
+        raise ValueError("quantize_mxfp4: the matrix holds NaN or Inf")
+    N, K = wf.shape
+    blk = wf.view(N, K // MXFP4_BLOCK, MXFP4_BLOCK)
+    amax = blk.abs().amax(dim=2)
+    # frexp: amax = m * 2^ex with m in [0.5, 1), so floor(log2 amax) = ex - 1 (subnormals included)
+    ex = torch.frexp(amax)[1].to(torch.int32)
+    e = torch.where(amax > 0, (ex - 1 - 2).clamp(-127, 127), torch.zeros_like(ex))
+    # x = w * 2^-e in two exact steps (2^-e itself can be beyond fp32 at e = -127; a product that underflows is below every midpoint)
+    half = torch.div(e, 2, rounding_mode="floor")
+    x = blk * torch.exp2(-half.to(torch.float32))[..., None] * torch.exp2(-(e - half).to(torch.float32))[..., None]
+    ax = x.abs()
+    idx = torch.zeros_like(ax, dtype=torch.int32)
+    for i, mid in enumerate(_E2M1_MID):          # index = number of midpoints passed; a tie passes it when the upper index is even
+        idx += ((ax >= mid) if (i + 1) % 2 == 0 else (ax > mid)).to(torch.int32)
+    code = (idx | (torch.signbit(blk).to(torch.int32) << 3)).to(torch.uint8).view(N, K)
+    codes = (code[:, 0::2] | (code[:, 1::2] << 4)).contiguous()
+    return codes, (e + 127).to(torch.uint8).contiguous()
+
+
+def dequantize_mxfp4(codes: torch.Tensor, block_scales: torch.Tensor, dtype=torch.float32) -> torch.Tensor:
+    """The (N,K) matrix an MXFP4 pair stands for: e2m1(code) * 2^(E-127), computed in float64 and exact in fp32 for scale
+    bytes 1 .. 254 (byte 255 gives NaN, the format's meaning).  ``codes`` uint8 (or a ``torch.float4_e2m1fn_x2`` view of them)."""
+    if codes.dtype != torch.uint8:
+        codes = codes.view(torch.uint8)
+    if block_scales.dtype != torch.uint8:
+        raise TypeError(f"dequantize_mxfp4: block_scales must be uint8, got {block_scales.dtype}")
+    if codes.ndim != 2 or block_scales.ndim != 2 or (codes.shape[1] * 2) % MXFP4_BLOCK or \
+            tuple(block_scales.shape) != (codes.shape[0], codes.shape[1] * 2 // MXFP4_BLOCK):
+        raise ValueError(f"dequantize_mxfp4: codes {tuple(codes.shape)} and block_scales {tuple(block_scales.shape)} are not an "
+                         f"(N, K/2) / (N, K/{MXFP4_BLOCK}) pair")
+    N, K = codes.shape[0], codes.shape[1] * 2
+    nib = torch.stack([codes & 0xF, codes >> 4], dim=2).view(N, K).to(torch.int64)
+    mag = torch.tensor(_E2M1, dtype=torch.float64, device=codes.device)[nib & 7]
+    val = torch.where((nib & 8) != 0, -mag, mag)
+    sc = torch.exp2(block_scales.to(torch.float64) - 127.0)
+    sc = torch.where(block_scales == 255, torch.full_like(sc, math.nan), sc)
+    return (val.view(N, K // MXFP4_BLOCK, MXFP4_BLOCK) * sc[..., None]).view(N, K).to(dtype)
+
+
 def is_fp8_matrix_key(key: str, t: torch.Tensor) -> bool:
     """The tensors --enable-fp8 keeps in e4m3: the (out,in) matrices of the Linear layers (every one of them is a GEMM panel
     of LTXModel._pack); biases, norm weights and the scale-shift tables stay bf16."""
