@@ -729,6 +729,32 @@ typedef struct {
 int ltxk_sample_rows(const ltxk_sample_args* args, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Step cache (csrc/step_cache.hip): the device side of a timestep-aware step cache of the denoise loop
+ * ------------------------------------------------------------------------------------- */
+/* ltxk_step_cache_probe: cur, prev (rows, D) bf16, contiguous, 16-byte aligned, not overlapping (checked), D % 8 == 0.  One pass reads both
+ * once and writes prev <- cur (a copy of the bytes); sums[0] = S_d = sum |f32(cur) - f32(prev)| (each difference rounded once,
+ * to fp32) and sums[1] = S_p = sum |f32(prev)| over the OLD prev, fp32, DEVICE.  Summation order, a function of rows * D alone
+ * (not of the grid, the device or timing): chunks of 8192 consecutive elements, inside a chunk 256 threads of four 8-element
+ * vectors (vector 256 * k + t of the chunk, k ascending, elements ascending, one chain from 0), the wave butterfly 32 .. 1,
+ * the four wave totals in ascending order; the chunk partials go through `workspace` and a second launch adds them in
+ * ascending chunk order.  The longest sequential fp32 addition chain is ltxk_step_cache_depth = 40 + ceil(rows * D / 8192) - 1.
+ * No atomics and no workgroup waits on another.  flags: LTXK_PROBE_INIT = the copy alone; sums and workspace are not
+ * touched (and may be null).  workspace: >= ltxk_step_cache_workspace_bytes(rows, D) = 2 * chunks * 4 bytes, 4-byte aligned,
+ * contents irrelevant on entry.  The two size functions return -1 on rows < 1, D < 8, D % 8 != 0 or rows * D > 2^35.   */
+enum { LTXK_PROBE_INIT = 1 };
+int64_t ltxk_step_cache_workspace_bytes(int64_t rows, int32_t D);
+int32_t ltxk_step_cache_depth(int64_t rows, int32_t D);
+int ltxk_step_cache_probe(const void* cur, void* prev, int64_t rows, int32_t D, int32_t flags, float* sums, void* workspace,
+                          int64_t workspace_bytes, void* stream);
+
+/* The residual of a computed step and its reuse, n bf16 elements each, n % 8 == 0, 16-byte aligned, not overlapping (checked), in place:
+ *   ltxk_residual_store:  r <- rbf(f32(x) - f32(r))     (r holds the copy of x taken in front of block 0 on entry)
+ *   ltxk_residual_apply:  x <- rbf(f32(x) + f32(r))
+ * rbf: round to nearest even to bf16.                                                                                   */
+int ltxk_residual_store(const void* x, void* r, int64_t n, void* stream);
+int ltxk_residual_apply(void* x, const void* r, int64_t n, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Video VAE (volumes are channels-last (B,D,H,W,C) bf16; a row = one voxel)
  * ------------------------------------------------------------------------------------- */
 enum { LTXK_PAD_ZEROS = 0, LTXK_PAD_REFLECT = 1 };

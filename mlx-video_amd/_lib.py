@@ -254,6 +254,12 @@ SIGNATURES = {
     "ltxk_headnorm_rope_at": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
                                         c_int32, c_void_p, c_float, c_void_p]),
     "ltxk_sample_rows": (c_int32, [POINTER(SampleArgs), c_void_p]),
+    # step cache of the denoise loop (csrc/step_cache.hip)
+    "ltxk_step_cache_workspace_bytes": (c_int64, [c_int64, c_int32]),
+    "ltxk_step_cache_depth": (c_int32, [c_int64, c_int32]),
+    "ltxk_step_cache_probe": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_int64, c_void_p]),
+    "ltxk_residual_store": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p]),
+    "ltxk_residual_apply": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p]),
 }
 
 # ltxk_abi_sizeof(i) is the size of ABI_STRUCTS[i]
@@ -268,6 +274,7 @@ ATTN_KERNEL_128, ATTN_KERNEL_MIX = 0, 1                         # ltxk.h: LTXK_A
 GUIDER_CFG_STAR, GUIDER_APG = 1, 2                              # ltxk.h: LTXK_GUIDER_*
 GUIDER_RECORD_FLOATS = 8                                        # ltxk.h: LTXK_GUIDER_RECORD_FLOATS
 SAMPLE_DRAW, SAMPLE_ADVANCE = 1, 2                              # ltxk.h: LTXK_SAMPLE_*
+PROBE_INIT = 1                                                  # ltxk.h: LTXK_PROBE_INIT
 
 
 def _open(path: str) -> ctypes.CDLL:

@@ -11,6 +11,7 @@ float (1288,1293-1301).  ``fp32_euler=False`` (LTX_FP32_EULER=0) only changes th
 distilled step (generate.py:741-748): the Euler update then runs op by op in bf16."""
 from __future__ import annotations
 
+import math
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
@@ -115,16 +116,143 @@ class _Guidance:
                              bf16_euler=bf16_euler, **kw)
 
 
+class StepCache:
+    """A timestep-aware step cache (TeaCache) for ``denoise_dev`` / ``denoise_distilled``: a step whose input to block 0 has
+    barely moved since the step before skips the transformer blocks and adds the residual (x behind the last block minus x in
+    front of block 0) of the last computed step instead.  Opt-in, not in the reference.
+
+    One object serves one denoise call at a time; a call resets it and leaves ``report``.  The measure is m_i, block 0's
+    modulated self-attention input of the positive rows at step i; the device returns S_d = sum |m_i - m_(i-1)| and
+    S_p = sum |m_(i-1)| (ops.step_cache_probe), the host decides (``decide``).  A step has ONE decision, shared by its
+    forwards; with b > 1 samples it is joint over them (the sums run over all b positive rows), so a sample's result then
+    depends on its batch - with b = 1 it is the sample's own.  Each forward (pos, neg, pos+; or the one batched forward) keeps
+    a residual of its own.  ``threshold`` tau >= 0: 0 never skips, inf skips every step but the first and the last.
+    ``coefficients``: the polynomial applied to rel = S_d / S_p before it is accumulated, highest degree first
+    (numpy.poly1d); the default (1, 0) is the identity, not a calibrated fit.  ``schedule``: a list of booleans, True =
+    compute, one per step, that overrides the policy (the probe still runs and reports); its first entry must be True.
+    ``report``: per step {"rel", "acc", "computed", "s_d", "s_p"}; step 0 has no distance (None); "acc" is the accumulator the
+    decision compared with tau, before its reset."""
+
+    def __init__(self, threshold: float, coefficients: Sequence[float] = (1.0, 0.0), schedule: Optional[Sequence[bool]] = None):
+        threshold = float(threshold)
+        if not threshold >= 0.0:
+            raise ValueError(f"StepCache: threshold = {threshold} must be >= 0")
+        coefficients = tuple(float(c) for c in coefficients)
+        if not coefficients or not all(math.isfinite(c) for c in coefficients):
+            raise ValueError(f"StepCache: coefficients = {coefficients} must be one or more finite numbers, highest degree first")
+        if schedule is not None:
+            schedule = [bool(s) for s in schedule]
+            if not schedule or not schedule[0]:
+                raise ValueError("StepCache: schedule must start with a computed step (there is no residual before it)")
+        self.threshold, self.coefficients, self.schedule = threshold, coefficients, schedule
+        self.report: List[dict] = []
+        self._acc = 0.0
+        self._n = 0
+
+    @staticmethod
+    def decide(i: int, n: int, s_d: Optional[float], s_p: Optional[float], acc: float, threshold: float,
+               coefficients: Sequence[float] = (1.0, 0.0)) -> Tuple[bool, float, Optional[float]]:
+        """The policy, a pure host function in Python floats: (compute, acc compared with the threshold, rel) of step ``i`` of
+        ``n`` given the two sums and the accumulator ``acc`` carried into the step (0 after a computed step).  Step 0 and step
+        n - 1 are computed.  Otherwise rel = s_d / s_p, acc += poly(rel) by Horner, compute = not (acc < threshold).
+        s_p == 0 or a sum that is not finite: compute."""
+        if i == 0:
+            return True, 0.0, None
+        if s_d is None or s_p is None or not (math.isfinite(s_d) and math.isfinite(s_p)) or s_p == 0.0:
+            return True, 0.0, None
+        rel = s_d / s_p
+        if i == n - 1:
+            return True, 0.0, rel
+        p = 0.0
+        for c in coefficients:
+            p = p * rel + c
+        acc = acc + p
+        return (not acc < threshold), acc, rel
+
+    def reset(self, n: int) -> None:
+        if self.schedule is not None and len(self.schedule) != n:
+            raise ValueError(f"StepCache: schedule has {len(self.schedule)} entries, the call {n} steps")
+        self.report, self._acc, self._n = [], 0.0, n
+
+    def step(self, i: int, s_d: Optional[float], s_p: Optional[float]) -> bool:
+        """Record step ``i`` with its sums (None at step 0) and return whether it is computed."""
+        compute, acc, rel = self.decide(i, self._n, s_d, s_p, self._acc, self.threshold, self.coefficients)
+        if self.schedule is not None:
+            compute = self.schedule[i]
+        self.report.append({"rel": rel, "acc": acc, "computed": compute, "s_d": s_d, "s_p": s_p})
+        self._acc = 0.0 if compute else acc
+        return compute
+
+    @property
+    def counts(self) -> Dict[str, int]:
+        c = sum(1 for r in self.report if r["computed"])
+        return {"steps": len(self.report), "computed": c, "skipped": len(self.report) - c}
+
+
+class _CachedForwards:
+    """The forwards of one step under a step cache, cut in three: ``prepare`` (every forward's part in front of block 0),
+    ``probe`` (m_i of the first forward's positive rows, the two sums, prev <- m_i) and ``finish`` (per forward the blocks
+    and the residual store, or the residual apply; then the head).  Owns what outlives a step: prev, the probe's buffers
+    and one residual per forward."""
+
+    def __init__(self, gd: _Guidance, tr: LTXModel, b: int, n_tok: int, dev):
+        self.gd, self.tr = gd, tr
+        D = tr.inner_dim
+        self.rows = b * n_tok
+        nf = 1 if gd.batched else 1 + gd.use_cfg + gd.use_stg
+        self.resid = [torch.empty((gd.reps * self.rows, D), dtype=BF16, device=dev) for _ in range(nf)]
+        self.m = torch.empty((self.rows, D), dtype=BF16, device=dev)
+        self.prev = torch.zeros_like(self.m)
+        self.sums = torch.zeros((2,), dtype=torch.float32, device=dev)
+        self.ws = torch.empty((ops.step_cache_workspace_bytes(self.rows, D) // 4,), dtype=torch.float32, device=dev)
+
+    def prepare(self, lat, tp, pe, ctx_rows, kv_rows, ctx_pos, kv_pos, ctx_neg, kv_neg) -> list:
+        gd, tr = self.gd, self.tr
+        if gd.batched:
+            return [tr._fwd_prepare(ops.latent_to_tokens(lat, rep=gd.reps), tp, ctx_rows, pe, kv_rows, gd.pert_batched)]
+        tok = ops.latent_to_tokens(lat, rep=1)
+        sts = [tr._fwd_prepare(tok, tp, ctx_pos, pe, kv_pos, None)]
+        if gd.use_cfg:
+            sts.append(tr._fwd_prepare(tok, tp, ctx_neg, pe, kv_neg, None))
+        if gd.use_stg:
+            sts.append(tr._fwd_prepare(tok, tp, ctx_pos, pe, kv_pos, gd.pert_alone))
+        return sts
+
+    def probe(self, sts: list, init: bool) -> None:
+        self.tr.step_cache_input(sts[0], self.rows, self.m)
+        ops.step_cache_probe(self.m, self.prev, self.sums, self.ws, init=init)
+
+    def finish(self, sts: list, compute: bool):
+        gd, b = self.gd, self.gd.b
+        vs = [self.tr.forward_cached(st, r, compute) for st, r in zip(sts, self.resid)]
+        if gd.batched:
+            v = vs[0]
+            return v[:b], (v[b:2 * b] if gd.use_cfg else None), (v[(gd.reps - 1) * b:] if gd.use_stg else None)
+        return vs[0], (vs[1] if gd.use_cfg else None), (vs[-1] if gd.use_stg else None)
+
+
+def _refuse_step_cache(step_cache, who: str) -> None:
+    if step_cache is not None:
+        raise ValueError(f"{who} does not take a step cache (step_cache): it is part of denoise_dev and denoise_distilled only")
+
+
 def _denoise(latents: torch.Tensor, positions: torch.Tensor, ctx_pos_in: torch.Tensor, ctx_neg_in: Optional[torch.Tensor],
              transformer: LTXModel, sig: List[float], cfg_scale: float, state: Optional[LatentState], compile_step: bool,
              cfg_batch: bool, use_graph: bool, graph_cache: Optional[dict], cache_context: bool, bf16_euler: bool,
              stg_scale: float = 0.0, stg_pert: Optional[PerturbationConfig] = None, stg_key: tuple = (),
-             guider: Optional[GuiderConfig] = None) -> torch.Tensor:
+             guider: Optional[GuiderConfig] = None, step_cache: Optional[StepCache] = None) -> torch.Tensor:
+    if step_cache is not None and not isinstance(step_cache, StepCache):
+        raise TypeError(f"step_cache must be a StepCache or None, got {type(step_cache).__name__}")
     if state is not None:
         latents = state.latent
     latents = latents.to(BF16).contiguous()
     use_cfg = cfg_scale != 1.0
     bf16_euler = bf16_euler and compile_step          # the eager body always updates in fp32 (generate.py:835-849)
+    if step_cache is not None:
+        step_cache.reset(max(len(sig) - 1, 0))
+        # a skipped step must not pay for the text K | V^T of blocks it never runs: the text-only part is prepared once per
+        # call - the same bits, it is a function of the context alone
+        cache_context = True
     if len(sig) < 2:
         return latents
     b = latents.shape[0]
@@ -141,12 +269,14 @@ def _denoise(latents: torch.Tensor, positions: torch.Tensor, ctx_pos_in: torch.T
             key = key + stg_key
         if gd.guider is not None:     # plain CFG: today's key
             key = key + ("guider",) + gd.guider.key
+        if step_cache is not None:    # no step cache: today's key.  (The policy runs on the host: one capture serves every
+            key = key + ("step_cache",)                               # threshold, polynomial and schedule)
         cache = graph_cache if graph_cache is not None else {}
         ent = cache.get(key)
         if ent is None:
-            ent = _StepGraph(latents, plan, transformer, ctx_pos, gd, bf16_euler, cache_context)
+            ent = _StepGraph(latents, plan, transformer, ctx_pos, gd, bf16_euler, cache_context, cached=step_cache is not None)
             cache[key] = ent
-        return ent.run(latents, plan, ctx_pos, ctx_neg, pe)
+        return ent.run(latents, plan, ctx_pos, ctx_neg, pe, step_cache)
     ctx_cat = torch.cat(gd.context_rows(ctx_pos, ctx_neg), 0).contiguous() if gd.batched else None
     kv_pos = kv_neg = kv_cat = None
     if cache_context:
@@ -155,10 +285,18 @@ def _denoise(latents: torch.Tensor, positions: torch.Tensor, ctx_pos_in: torch.T
         else:
             kv_pos = transformer.prepare_context(ctx_pos)
             kv_neg = transformer.prepare_context(ctx_neg) if use_cfg else None
+    cf = None
+    if step_cache is not None:
+        cf = _CachedForwards(gd, transformer, b, latents.numel() // (b * latents.shape[1]), latents.device)
     for i in range(len(sig) - 1):
         s_bf, sn_bf = plan.sig_bf[i], plan.sig_bf[i + 1]
         tp = plan.timestep_plan(i)
-        v_pos, v_neg, v_pert = gd.velocities(transformer, latents, tp, pe, ctx_cat, kv_cat, ctx_pos, kv_pos, ctx_neg, kv_neg)
+        if cf is None:
+            v_pos, v_neg, v_pert = gd.velocities(transformer, latents, tp, pe, ctx_cat, kv_cat, ctx_pos, kv_pos, ctx_neg, kv_neg)
+        else:       # one prepare per forward, the probe, one host read of the two sums, then either branch
+            sts = cf.prepare(latents, tp, pe, ctx_cat, kv_cat, ctx_pos, kv_pos, ctx_neg, kv_neg)
+            cf.probe(sts, init=i == 0)
+            v_pos, v_neg, v_pert = cf.finish(sts, step_cache.step(i, *(cf.sums.tolist() if i else (None, None))))
         # x0 uses the bf16 sigma in both paths; Euler: bf16 sigmas if compiled else Python floats.
         # The fused kernel takes one sigma for x0 and the ratio terms; when they differ (eager path)
         # x0 and Euler run as two launches.
@@ -176,7 +314,7 @@ def denoise_dev(latents: torch.Tensor, positions: torch.Tensor, text_embeddings_
                 cfg_batch: bool = False, ui_phase: str = "denoise", use_graph: bool = False,
                 graph_cache: Optional[dict] = None, cache_context: bool = False, stg_scale: float = 0.0,
                 stg_blocks: Optional[Sequence[int]] = None, stg_mode: str = "stg_v", guider: str = "cfg",
-                apg_eta: float = 1.0, apg_norm_threshold: float = 0.0) -> torch.Tensor:
+                apg_eta: float = 1.0, apg_norm_threshold: float = 0.0, step_cache: Optional[StepCache] = None) -> torch.Tensor:
     """generate.py:1060-1327.  latents (B,128,F,H,W) bf16 on the GPU; returns the same shape.
     ``use_graph``: capture the whole step (forward(s) + fused tail, ~1000 launches) once as a hipGraph and
     replay it per step — the analogue of the reference's mx.compile'd step_fn (generate.py:1109-1177);
@@ -197,14 +335,18 @@ def denoise_dev(latents: torch.Tensor, positions: torch.Tensor, text_embeddings_
     ``guider``: what the CFG slot runs - "cfg" (default: today's fused velocity-space tail, launch for launch), "cfg_star"
     (CFGStarRescalingGuider) or "apg" (LtxAPGGuider with ``apg_eta`` and ``apg_norm_threshold``, 0 = no clamp); the latter two act
     in x0 space on per-sample dot products that stay on the device (ltxk_guidance_sums + ltxk_guider_euler_step, DESIGN.md
-    §5j), compose with STG, and are disabled at cfg_scale == 1 like CFG itself."""
+    §5j), compose with STG, and are disabled at cfg_scale == 1 like CFG itself.
+    ``step_cache``: a ``StepCache`` - steps whose input to block 0 has barely moved skip the transformer blocks and reuse the
+    last computed step's residual; it implies ``cache_context`` (same bits: the text side is a function of the
+    context alone).  None: today's loop, branch for branch."""
     gcfg = GuiderConfig(guider, apg_eta, apg_norm_threshold)
     stg_scale = float(stg_scale or 0.0)
     pert = stg_perturbation(stg_blocks, stg_mode, transformer.config.num_layers) if stg_scale != 0.0 else None
     stg_key = (stg_scale, None if stg_blocks is None else tuple(int(x) for x in stg_blocks), stg_mode)
     sig = [float(s) for s in (sigmas.tolist() if torch.is_tensor(sigmas) else sigmas)]
     return _denoise(latents, positions, text_embeddings_pos, text_embeddings_neg, transformer, sig, cfg_scale, state,
-                    compile_step, cfg_batch, use_graph, graph_cache, cache_context, False, stg_scale, pert, stg_key, gcfg)
+                    compile_step, cfg_batch, use_graph, graph_cache, cache_context, False, stg_scale, pert, stg_key, gcfg,
+                    step_cache)
 
 
 class _StepInputs:
@@ -256,8 +398,14 @@ class _StepGraph:
     first step of the first run executes eagerly (it doubles as the warm-up torch requires before capture:
     allocator, lazy hipFuncSetAttribute calls), then the step is captured and every later step is a replay."""
 
-    def __init__(self, latents, plan: _StepPlan, transformer: LTXModel, ctx_pos, gd: _Guidance, bf16_euler, cache_context):
+    def __init__(self, latents, plan: _StepPlan, transformer: LTXModel, ctx_pos, gd: _Guidance, bf16_euler, cache_context,
+                 cached: bool = False):
         dev = latents.device
+        # step cache: the step is three graphs - probe, full body, skip body - and the host picks a body per step (_run_cached)
+        bb, cc = latents.shape[:2]
+        self.cf = _CachedForwards(gd, transformer, bb, latents.numel() // (bb * cc), dev) if cached else None
+        self.sts: Optional[list] = None
+        self.g_probe = self.g_full = self.g_skip = None
         self.tr = transformer                       # strong reference: id(transformer) in the cache key stays unique
         self.gd, self.bf16_euler = gd, bf16_euler
         self.inp = _StepInputs(latents, plan)
@@ -303,9 +451,59 @@ class _StepGraph:
         gd.tail(v_pos, v_neg, v_pert, inp.lat_buf, 1.0, 0.0, inp.clean, inp.mask_tok, out=inp.lat_buf, sigmas_dev=inp.sig_buf,
                 bf16_euler=self.bf16_euler, record=self.g_rec, workspace=self.g_ws)
 
-    def run(self, latents, plan: _StepPlan, ctx_pos, ctx_neg, pe) -> torch.Tensor:
+    # --- step cache: probe | full | skip.  What crosses from one graph to another - the forwards' _Fwd states (self.sts), prev,
+    # the residuals, the sums - is either allocated before the captures (self.cf) or referenced from here across all three
+    # captures of one shared pool, so no later capture is handed its memory.  One stream, no parallel branches.
+    def _prepare_probe(self, init: bool) -> list:
+        gd, inp, cf = self.gd, self.inp, self.cf
+        tp = inp.next_step()
+        if gd.batched:
+            sts = cf.prepare(inp.lat_buf, tp, inp.pe, self.ctx_a, self.kv_a, None, None, None, None)
+        else:
+            sts = cf.prepare(inp.lat_buf, tp, inp.pe, None, None, self.ctx_a, self.kv_a, self.ctx_b, self.kv_b)
+        cf.probe(sts, init)
+        return sts
+
+    def _body(self, sts: list, compute: bool) -> None:
+        gd, inp = self.gd, self.inp
+        v_pos, v_neg, v_pert = self.cf.finish(sts, compute)
+        gd.tail(v_pos, v_neg, v_pert, inp.lat_buf, 1.0, 0.0, inp.clean, inp.mask_tok, out=inp.lat_buf, sigmas_dev=inp.sig_buf,
+                bf16_euler=self.bf16_euler, record=self.g_rec, workspace=self.g_ws)
+
+    def _run_cached(self, nst: int, sc: StepCache) -> torch.Tensor:
+        cf, start = self.cf, 0
+        if self.g_probe is None:
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                self._body(self._prepare_probe(init=True), True)     # real step 0, eager: prev <- m_0, the first residuals
+                # the launches the captures would otherwise see first: the skip body's add and the probe's merge, on scratch
+                scratch = torch.zeros((2, 1, 8), dtype=BF16, device=self.inp.lat_buf.device)
+                ops.residual_apply(scratch[0], scratch[1])
+                ops.step_cache_probe(scratch[0], scratch[1], torch.zeros_like(cf.sums), torch.zeros_like(cf.sums))
+            torch.cuda.current_stream().wait_stream(side)
+            sc.step(0, None, None)
+            pool = torch.cuda.graph_pool_handle()
+            self.g_probe, self.g_full, self.g_skip = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.g_probe, pool=pool, capture_error_mode="thread_local"):
+                self.sts = self._prepare_probe(init=False)
+            with torch.cuda.graph(self.g_full, pool=pool, capture_error_mode="thread_local"):
+                self._body(self.sts, True)
+            with torch.cuda.graph(self.g_skip, pool=pool, capture_error_mode="thread_local"):
+                self._body(self.sts, False)
+            start = 1
+        for i in range(start, nst):
+            self.g_probe.replay()
+            # step 0 of a later call: the replayed probe has compared m_0 with the last call's prev; its sums are not read
+            compute = sc.step(i, *(cf.sums.tolist() if i else (None, None)))
+            (self.g_full if compute else self.g_skip).replay()
+        return self.inp.lat_buf.clone()
+
+    def run(self, latents, plan: _StepPlan, ctx_pos, ctx_neg, pe, step_cache: Optional[StepCache] = None) -> torch.Tensor:
         self._load(latents, plan, ctx_pos, ctx_neg, pe)
         nst = plan.ts_host.shape[0]
+        if self.cf is not None:       # (the host's cache state was rewound by StepCache.reset; prev is rewritten by step 0)
+            return self._run_cached(nst, step_cache)
         start = 0
         if self.graph is None:
             side = torch.cuda.Stream()
@@ -338,14 +536,15 @@ def denoise_distilled(latents: torch.Tensor, positions: torch.Tensor, text_embed
                       audio_embeddings=None, eval_interval: int = 1, compile_step: bool = False,
                       compile_shapeless: bool = False, fp32_euler: bool = True,
                       ui_phase: str = "denoise", use_graph: bool = False, graph_cache: Optional[dict] = None,
-                      cache_context: bool = False) -> Tuple[torch.Tensor, None]:
+                      cache_context: bool = False, step_cache: Optional[StepCache] = None) -> Tuple[torch.Tensor, None]:
     """generate.py:564-881, video branch (no CFG).  ``fp32_euler=False`` selects the bf16 Euler update of the
-    compiled step (generate.py:741-748); the un-compiled loop body always updates in fp32 (835-849)."""
+    compiled step (generate.py:741-748); the un-compiled loop body always updates in fp32 (835-849).
+    ``step_cache``: a ``StepCache``, as in ``denoise_dev`` (implies ``cache_context``); None: today's loop."""
     if audio_latents is not None:
         raise ValueError("audio latents are not supported: the audio branch is out of scope (SURVEY.md §2a #3)")
     sig = [float(s) for s in (sigmas.tolist() if torch.is_tensor(sigmas) else sigmas)]
     out = _denoise(latents, positions, text_embeddings, None, transformer, sig, 1.0, state, compile_step, False,
-                   use_graph, graph_cache, cache_context, not fp32_euler)
+                   use_graph, graph_cache, cache_context, not fp32_euler, step_cache=step_cache)
     return out, None
 
 
@@ -442,7 +641,7 @@ def denoise_dev_av(video_latents: torch.Tensor, audio_latents: torch.Tensor, vid
                    eval_interval: int = 1, compile_step: bool = False, compile_shapeless: bool = False, cfg_batch: bool = False,
                    ui_phase: str = "denoise", use_graph: bool = False, graph_cache: Optional[dict] = None,
                    cache_context: bool = False, stg_scale: float = 0.0, stg_blocks: Optional[Sequence[int]] = None,
-                   guider: str = "cfg") -> Tuple[torch.Tensor, torch.Tensor]:
+                   guider: str = "cfg", step_cache=None) -> Tuple[torch.Tensor, torch.Tensor]:
     """generate.py:1330-1680: the dev loop of joint audio-video denoising over an ``av_model.LTXAVModel``.  video_latents
     (B,128,F,H,W), audio_latents (B,8,T,16), video_positions (B,3,N,2), audio_positions (B,1,T,2) seconds, one context pair per
     modality; returns (video latents, audio latents) in the shapes given.  Both modalities share sigma; the audio timestep mask
@@ -451,7 +650,8 @@ def denoise_dev_av(video_latents: torch.Tensor, audio_latents: torch.Tensor, vid
     fused tail: the audio latents travel as the (B,128,T,1,1) volume.  The video conditioning mask goes through ``video_state``.
     ``use_graph`` (with ``compile_step``): the whole joint step - forward(s) plus the two tails - captured once on one stream and
     replayed; ``graph_cache`` keeps it across calls, every per-call input refreshed.  STG, the cfg_star / apg guiders and
-    ``cache_context`` are not part of the joint loop: ValueError."""
+    ``cache_context`` and a step cache (``step_cache``) are not part of the joint loop: ValueError."""
+    _refuse_step_cache(step_cache, "the joint audio-video loop (denoise_dev_av)")
     if float(stg_scale or 0.0) != 0.0 or stg_blocks is not None:
         raise ValueError("the joint audio-video loop does not do STG (stg_scale / stg_blocks); use denoise_dev for it")
     if guider != "cfg":
@@ -515,13 +715,14 @@ def denoise_audio_only(audio_latents: torch.Tensor, audio_positions: torch.Tenso
                        transformer: LTXModel, sigmas: Sequence[float], verbose: bool = False, eval_interval: int = 1,
                        compile_step: bool = False, compile_shapeless: bool = False, fp32_euler: bool = True,
                        ui_phase: str = "audio_denoise", use_graph: bool = False, graph_cache: Optional[dict] = None,
-                       cache_context: bool = False) -> torch.Tensor:
+                       cache_context: bool = False, step_cache=None) -> torch.Tensor:
     """generate.py:888-1053: the distilled-style loop of separate audio generation over an audio-only transformer
     (``LTXModelConfig.audio()``), no CFG.  audio_latents (B,8,T,16), audio_positions (B,1,T,2) seconds
     (``schedulers.create_audio_position_grid``), audio_embeddings (B,S,caption_channels); returns (B,8,T,16) bf16.
     The latents run through the video loop as a (B,128,T,1,1) volume - converted once on entry and once on exit, where the
     reference transposes in every step - so the step tail, the sigma handling (x0 with bf16(sigma), Euler in fp32 with the
-    Python floats; bf16 sigmas under ``compile_step``), ``use_graph`` and ``cache_context`` are ``denoise_distilled``'s."""
+    Python floats; bf16 sigmas under ``compile_step``), ``use_graph`` and ``cache_context`` are ``denoise_distilled``'s.  A step cache (``step_cache``) is not part of this loop: ValueError."""
+    _refuse_step_cache(step_cache, "the audio-only loop (denoise_audio_only)")
     if audio_latents.dim() != 4:
         raise ValueError(f"audio_latents must be (B,C,T,F), got {tuple(audio_latents.shape)}")
     b, c, t, f = audio_latents.shape

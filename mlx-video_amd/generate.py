@@ -309,7 +309,9 @@ def generate_video(model_repo: Optional[str] = None, text_encoder_repo: Optional
                    audio_model_repo: Optional[str] = None, audio_steps: int = 8, audio_transformer: Optional[LTXModel] = None,
                    audio_prompt_embeds: Optional[torch.Tensor] = None, av_transformer=None,
                    audio_negative_prompt_embeds: Optional[torch.Tensor] = None, fp8_text_encoder: bool = False,
-                   enhance_device_loop: bool = False, enhance_mxfp4: bool = False) -> np.ndarray:
+                   enhance_device_loop: bool = False, enhance_mxfp4: bool = False,
+                   step_cache_threshold: Optional[float] = None,
+                   step_cache_coefficients: Optional[Sequence[float]] = None) -> np.ndarray:
     """See the module docstring.  Returns uint8 frames (F,H,W,3) (generate.py:4195-4197).
     ``hoist_context`` (not in the reference, off by default): the part of the forward that depends on the text context only -
     caption projection and the 48 cross-attention K / V^T projections, 3.37 TFLOP that the reference recomputes in every forward
@@ -382,7 +384,16 @@ def generate_video(model_repo: Optional[str] = None, text_encoder_repo: Optional
     negative prompt where the text route runs here.  It runs under the ``dev_denoise`` phase (no ``audio_generate``), the
     profile reports ``audio_mode``, and the result takes the same decode / ``.wav`` / mux path.  The reference's "auto" picks joint
     for the dev pipeline; here joint is asked for by name.  Refused with it: every other pipeline and ``stage2_dev``, ``enable_fp8``
-    / ``fp8_activations``, STG and the cfg_star / apg guiders, ``hoist_context``, and ``audio_transformer=``."""
+    / ``fp8_activations``, STG and the cfg_star / apg guiders, ``hoist_context``, and ``audio_transformer=``.
+    ``step_cache_threshold`` / ``step_cache_coefficients`` (--step-cache-threshold X / --step-cache-coefficients C ...; not in the
+    reference, off by default): a timestep-aware step cache (TeaCache, ``denoise.StepCache``) in every video denoise
+    call - a step whose input to block 0 has moved little since the step before skips the 48 blocks and reuses the last
+    computed step's residual.  The threshold is >= 0 (0 never skips; the latents are then today's, bit for bit); the
+    coefficients are a polynomial applied to the relative distance, highest degree first - the default (1, 0) is the identity,
+    NOT a calibrated fit, and no trained checkpoint has been run: which threshold gives which skip rate at which quality is
+    open.  It implies ``hoist_context`` (same bits).  Each stage of a two-stage pipeline has a cache of its own; the profile
+    JSON gains ``step_cache`` with the computed / skipped steps per denoise call.  Coefficients without a threshold, a negative
+    or NaN threshold, and ``audio_mode="joint"`` with a step cache are ValueErrors."""
     t_start = time.perf_counter()
     if isinstance(pipeline, str):
         pipeline = PipelineType(pipeline)
@@ -414,6 +425,25 @@ def generate_video(model_repo: Optional[str] = None, text_encoder_repo: Optional
                              "LTXModelConfig.audio()), or audio_model_repo= / model_repo= a local checkpoint directory with the audio_* tensors")
         if audio_steps < 1 or audio_steps > (len(STAGE_1_SIGMAS) - 1):
             raise ValueError("--audio-steps must be between 1 and 8.")
+    if step_cache_threshold is None and step_cache_coefficients is not None:
+        raise ValueError("step_cache_coefficients (--step-cache-coefficients) shape the step cache's decision: they need "
+                         "step_cache_threshold (--step-cache-threshold)")
+    step_caches = []                  # one StepCache per video denoise call: each stage has a cache lifetime of its own
+    if step_cache_threshold is not None:
+        from .denoise import StepCache
+        if joint:
+            raise ValueError("audio_mode='joint': the joint loop does not take a step cache (step_cache_threshold)")
+        if step_cache_coefficients is None:
+            step_cache_coefficients = (1.0, 0.0)
+        StepCache(step_cache_threshold, step_cache_coefficients)       # refuses a bad threshold or polynomial here
+
+    def step_cache_kw() -> dict:
+        """The keyword of one denoise call: nothing when the cache is off (today's call), else a fresh StepCache."""
+        if step_cache_threshold is None:
+            return {}
+        step_caches.append(StepCache(step_cache_threshold, step_cache_coefficients))
+        return {"step_cache": step_caches[-1]}
+
     if enhance_device_loop and not enhance_prompt:
         raise ValueError("enhance_device_loop (--enhance-device-loop) is a mode of enhance_prompt (--enhance-prompt), which is off")
     if enhance_mxfp4 and not enhance_prompt:
@@ -609,7 +639,8 @@ def generate_video(model_repo: Optional[str] = None, text_encoder_repo: Optional
         latents = state1.latent if state1 is not None else noise_fn(shape1)
         with timer.phase("stage1_denoise"):
             latents, _ = denoise_distilled(latents, pos1, ctx_pos, transformer, sig1, state=state1,
-                                           compile_step=compile_step, fp32_euler=fp32_euler, use_graph=compile_step, cache_context=hoist_context)
+                                           compile_step=compile_step, fp32_euler=fp32_euler, use_graph=compile_step, cache_context=hoist_context,
+                                           **step_cache_kw())
         with timer.phase("upsample"):
             from .upsampler import upsample_latents
             latents = upsample_latents(latents, upsampler, vae_decoder.latents_mean, vae_decoder.latents_std)
@@ -638,10 +669,11 @@ def generate_video(model_repo: Optional[str] = None, text_encoder_repo: Optional
             if stage2_dev:
                 latents = denoise_dev(latents, pos2, ctx_pos, ctx_neg, tr2, torch.tensor(sig2), cfg_scale=cfg_scale,
                                       state=state2, compile_step=compile_step, cfg_batch=cfg_batch, use_graph=compile_step, cache_context=hoist_context,
-                                      **stg)
+                                      **stg, **step_cache_kw())
             else:
                 latents, _ = denoise_distilled(latents, pos2, ctx_pos, tr2, sig2, state=state2, compile_step=compile_step,
-                                               fp32_euler=fp32_euler, use_graph=compile_step, cache_context=hoist_context)
+                                               fp32_euler=fp32_euler, use_graph=compile_step, cache_context=hoist_context,
+                                               **step_cache_kw())
     else:
         lh, lw = height // 32, width // 32
         n_tok = latent_frames * lh * lw
@@ -674,7 +706,7 @@ def generate_video(model_repo: Optional[str] = None, text_encoder_repo: Optional
             with timer.phase("dev_denoise"):
                 latents = denoise_dev(latents, pos, ctx_pos, ctx_neg, transformer, sigmas, cfg_scale=cfg_scale, state=state,
                                       compile_step=compile_step, cfg_batch=cfg_batch, use_graph=compile_step,
-                                      cache_context=hoist_context, **stg)
+                                      cache_context=hoist_context, **stg, **step_cache_kw())
 
     if return_latents:
         return latents
@@ -759,6 +791,9 @@ def generate_video(model_repo: Optional[str] = None, text_encoder_repo: Optional
                    "fp32_euler": bool(fp32_euler), "audio": waveform is not None,
                    **({"audio_mode": "joint" if joint else "separate"} if audio else {}), "phases_s": {k: float(v) for k, v in timer.times_s.items()},
                    "peak_memory_gb": float(torch.cuda.max_memory_allocated() / (1024 ** 3))}
+        if step_caches:               # off: today's keys
+            payload["step_cache"] = {"threshold": step_caches[0].threshold, "coefficients": list(step_caches[0].coefficients),
+                                     "calls": [c.counts for c in step_caches]}
         outp.parent.mkdir(parents=True, exist_ok=True)
         outp.write_text(json.dumps(payload, indent=2, sort_keys=True), encoding="utf-8")
     return video_np
@@ -798,6 +833,13 @@ def _finite_float(text: str) -> float:
     v = float(text)
     if not math.isfinite(v):
         raise argparse.ArgumentTypeError(f"expected a finite number, got {text!r}")
+    return v
+
+
+def _step_cache_threshold(text: str) -> float:
+    v = float(text)
+    if not v >= 0:                        # inf is a threshold (skip all but the ends); NaN and negatives are not
+        raise argparse.ArgumentTypeError(f"expected a threshold >= 0, got {text!r}")
     return v
 
 
@@ -906,6 +948,13 @@ def build_parser() -> argparse.ArgumentParser:
                          "apg: adaptive projected guidance.  dev pipeline or --stage2-dev")
     ap.add_argument("--apg-eta", type=_finite_float, default=1.0, help="--guider apg: weight of the guidance component parallel to the prediction")
     ap.add_argument("--apg-norm-threshold", type=_nonneg_float, default=0.0, help="--guider apg: clamp the guidance norm to this (0: off)")
+    # timestep-aware step cache (not in the reference; denoise.StepCache)
+    ap.add_argument("--step-cache-threshold", type=_step_cache_threshold, default=None, metavar="X",
+                    help="(not in the reference CLI) skip the transformer blocks of a step while the accumulated relative change of "
+                         "block 0's input stays below X >= 0 (0: never skip; inf: every step but the first and last); unset: off")
+    ap.add_argument("--step-cache-coefficients", type=_finite_float, nargs="+", default=None, metavar="C",
+                    help="polynomial applied to the relative change before it is accumulated, highest degree first "
+                         "(default 1 0: the identity, not a calibrated fit); needs --step-cache-threshold")
     # the reference's flag (it parses and ignores it): keep the model in lower precision, calculations still in bfloat16
     ap.add_argument("--enable-fp8", action="store_true", default=False,
                     help="Keep the transformer's Linear weights as FP8 (e4m3) panels; calculations still in bfloat16")
@@ -994,9 +1043,13 @@ def main(argv: Optional[Sequence[str]] = None) -> None:
         raise ValueError("--fp8-text-encoder needs --gemma-repo: it is the Gemma-3 model built from that directory that keeps fp8 panels")
     if args.enhance_mxfp4 and not args.enhance_prompt:
         raise ValueError("--enhance-mxfp4 is a mode of --enhance-prompt, which is off")
+    if args.step_cache_coefficients is not None and args.step_cache_threshold is None:
+        raise ValueError("--step-cache-coefficients needs --step-cache-threshold")
     is_dev = args.pipeline == "dev"
     dev = torch.device("cuda:0")
     kw = {}
+    if args.step_cache_threshold is not None:
+        kw.update(step_cache_threshold=args.step_cache_threshold, step_cache_coefficients=args.step_cache_coefficients)
     # generate.py:4667-4694: --image items without an explicit index/strength take --image-frame-idx / --image-strength
     images = [(pth, args.image_frame_idx if fi is None else fi, args.image_strength if st is None else st) for pth, fi, st in args.image]
     if args.condition_image:

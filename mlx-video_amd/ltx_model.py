@@ -731,6 +731,32 @@ class LTXModel:
         v = self._linear(st.nx, self.out)
         return v.reshape(st.B, st.N, self.config.out_channels)
 
+    # --- step cache (denoise.StepCache): the forward cut in front of and behind its blocks ---
+    def step_cache_input(self, st: "_Fwd", rows: int, out: torch.Tensor) -> torch.Tensor:
+        """Block 0's modulated self-attention input of the first ``rows`` token rows of a prepared forward, into ``out``
+        (rows, D): the launch at the top of ``_fwd_attn(st, 0)`` over those rows, in a buffer of its own - a row's bits do not
+        depend on the rows beside it, so they are the bits block 0 will compute.  Leaves ``st`` untouched."""
+        mod, fs = st.mods[0], self.fuse & 2
+        ops.rmsnorm_modulate(st.x[:rows], self.config.norm_eps, mod[:, 1], mod[:, 0], 6 * self.inner_dim,
+                             None if st.tok2row is None else st.tok2row[:rows], out=out,
+                             sumsq=None if st.s_x is None else st.s_x[:rows], scale_is_one_plus=bool(fs))
+        return out
+
+    def forward_cached(self, st: "_Fwd", resid: torch.Tensor, compute: bool) -> torch.Tensor:
+        """The rest of a prepared forward under a step cache.  ``compute``: ``resid`` (M, D) takes a copy of the residual stream
+        in front of block 0, the blocks run as in ``forward_tokens``, and resid <- rbf(x_out - x_in).  Otherwise the blocks
+        are skipped: x <- rbf(x + resid) with the residual of the last computed step.  Then the head, which reduces its rows
+        itself (the carried row statistics of ``st`` are not read behind the last block)."""
+        if compute:
+            resid.copy_(st.x)
+            for li in range(len(self.blocks)):
+                self._fwd_attn(st, li)
+                self._fwd_ff(st, li)
+            ops.residual_store(st.x, resid)
+        else:
+            ops.residual_apply(st.x, resid)
+        return self._fwd_head(st)
+
     def __call__(self, video: Optional[Modality] = None, audio: Optional[Modality] = None,
                  perturbations: Optional[BatchedPerturbationConfig] = None):
         if audio is not None:

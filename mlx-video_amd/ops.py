@@ -1199,6 +1199,92 @@ def sample_rows(logits, ctl, done, next_ids, history, hist_len, tokens_out, eos,
         check(_lib.load().ltxk_sample_rows(ctypes.byref(a), _stream()), "ltxk_sample_rows")
 
 
+# ------------------------------------------------------------------- step cache of the denoise loop (csrc/step_cache.hip)
+STEP_CACHE_CHUNK = 8192       # elements per workgroup of ltxk_step_cache_probe: the chunks its partial sums are merged over
+STEP_CACHE_DEPTH_BASE = 40    # sequential fp32 additions behind a chunk's partial; one more per further chunk
+
+
+def _step_cache_chunks(who: str, rows: int, D: int) -> int:
+    rows, D = int(rows), int(D)
+    if rows < 1 or D < 8 or D % 8 or rows * D > 1 << 35:
+        raise ValueError(f"{who}: rows = {rows} must be positive, D = {D} a positive multiple of 8 and rows * D at most 2^35")
+    return -(-rows * D // STEP_CACHE_CHUNK)
+
+
+def step_cache_workspace_bytes(rows: int, D: int) -> int:
+    """Bytes of the partial-sum workspace ``step_cache_probe`` needs for (rows, D) (ltxk_step_cache_workspace_bytes; a size
+    function: it hands the library no tensor)."""
+    n = 8 * _step_cache_chunks("step_cache_workspace_bytes", rows, D)
+    lib = _lib.load()
+    if lib.ltxk_step_cache_workspace_bytes(int(rows), int(D)) != n:
+        raise _lib.LtxkError("step_cache_workspace_bytes: the library cuts (rows, D) into other chunks than this binding; rebuild it")
+    return n
+
+
+def step_cache_depth(rows: int, D: int) -> int:
+    """The longest sequential fp32 addition chain behind a sum of ltxk_step_cache_probe over (rows, D) (ltxk_step_cache_depth)."""
+    d = STEP_CACHE_DEPTH_BASE + _step_cache_chunks("step_cache_depth", rows, D) - 1
+    lib = _lib.load()
+    if lib.ltxk_step_cache_depth(int(rows), int(D)) != d:
+        raise _lib.LtxkError("step_cache_depth: the library sums (rows, D) in another order than this binding; rebuild it")
+    return d
+
+
+def step_cache_probe(cur, prev, sums, workspace, *, init: bool = False) -> None:
+    """ltxk_step_cache_probe: ``cur``, ``prev`` (rows, D) bf16, contiguous, 16-byte aligned, D % 8 == 0.  One pass:
+    sums[0] = sum |cur - prev|, sums[1] = sum |prev| (``sums`` (2,) fp32 on the device, ``prev`` as it was on entry), and
+    prev <- cur.  The summation order depends on (rows, D) alone (csrc/step_cache.hip); ``workspace``: fp32 of at least
+    ``step_cache_workspace_bytes(rows, D) // 4`` elements.  ``init``: the copy alone - ``sums`` and ``workspace`` are not touched
+    and may be None.  (No tensor annotations, as ``sample_rows``; the refusals are in tests/test_step_cache_cpu.py.)"""
+    who = "step_cache_probe"
+    if not isinstance(cur, torch.Tensor) or not isinstance(prev, torch.Tensor):
+        raise TypeError(f"{who}: cur and prev must be tensors")
+    rows, D = _dims(who, "cur", cur, BF16, 2)
+    nws = 2 * _step_cache_chunks(who, rows, D)
+    if not init and (sums is None or workspace is None):
+        raise ValueError(f"{who}: sums and workspace are required unless init")
+    _operands(who, ("cur", cur, BF16, (rows, D), 16), ("prev", prev, BF16, (rows, D), 16), ("sums", sums, F32, (2,), 4),
+              ("workspace", workspace, F32, (-nws,), 4))
+    if cur.data_ptr() == prev.data_ptr():
+        raise ValueError(f"{who}: cur and prev must be two buffers")
+    with _timed(who, 0.0 if init else 5.0 * rows * D, (4.0 if init else 6.0) * rows * D):
+        check(_lib.load().ltxk_step_cache_probe(_p(cur), _p(prev), rows, D, _lib.PROBE_INIT if init else 0, _p(sums), _p(workspace),
+                                                0 if workspace is None else workspace.numel() * 4, _stream()), "ltxk_step_cache_probe")
+
+
+def _residual_operands(who: str, x, r) -> tuple:
+    """The two operands of a residual shim, once ``x`` fixes the shape: bf16, a positive multiple of 8 elements."""
+    if not isinstance(x, torch.Tensor) or not isinstance(r, torch.Tensor):
+        raise TypeError(f"{who}: x and r must be tensors")
+    shape = x.shape
+    _dims(who, "x", x, BF16, len(shape))
+    if x.numel() < 8 or x.numel() % 8:
+        raise ValueError(f"{who}: x must hold a positive multiple of 8 elements, got shape {tuple(shape)}")
+    return ("x", x, BF16, shape, 16), ("r", r, BF16, shape, 16)
+
+
+def residual_store(x, r) -> None:
+    """ltxk_residual_store: r <- rbf(f32(x) - f32(r)) in place, x and r bf16 of one shape, contiguous, 16-byte aligned,
+    numel % 8 == 0.  On entry ``r`` holds the copy of the residual stream taken in front of block 0, ``x`` the stream behind the
+    last block.  (No tensor annotations, as ``sample_rows``.)"""
+    _operands("residual_store", *_residual_operands("residual_store", x, r))
+    if x.data_ptr() == r.data_ptr():
+        raise ValueError("residual_store: x and r must be two buffers")
+    n = x.numel()
+    with _timed("residual_store", float(n), 6.0 * n):
+        check(_lib.load().ltxk_residual_store(_p(x), _p(r), n, _stream()), "ltxk_residual_store")
+
+
+def residual_apply(x, r) -> None:
+    """ltxk_residual_apply: x <- rbf(f32(x) + f32(r)) in place; operands as ``residual_store``."""
+    _operands("residual_apply", *_residual_operands("residual_apply", x, r))
+    if x.data_ptr() == r.data_ptr():
+        raise ValueError("residual_apply: x and r must be two buffers")
+    n = x.numel()
+    with _timed("residual_apply", float(n), 6.0 * n):
+        check(_lib.load().ltxk_residual_apply(_p(x), _p(r), n, _stream()), "ltxk_residual_apply")
+
+
 # ------------------------------------------------------------------- VAE / upsampler (csrc/conv3d.hip, csrc/vae_ops.hip)
 # Volumes are channels-last (B,D,H,W,C) bf16, a voxel one contiguous row.
 PAD_ZEROS, PAD_REFLECT = 0, 1

@@ -35,6 +35,8 @@ class MLXPipelineConfig:
     guider: str = "cfg"                 # --guider: cfg | cfg_star | apg (ltx_core/components/guiders.py) in every guided stage
     apg_eta: float = 1.0
     apg_norm_threshold: float = 0.0
+    step_cache_threshold: Optional[float] = None      # (not in the reference) --step-cache-threshold: denoise.StepCache; None: off
+    step_cache_coefficients: Optional[tuple] = None   # --step-cache-coefficients, highest degree first; None: the identity
 
 
 def _ensure_list(v):
@@ -95,6 +97,9 @@ def run_generate(prompt: str, pipeline: PipelineType, cfg: MLXPipelineConfig, ou
                             loras=_normalize_loras(loras), distilled_loras=_normalize_loras(distilled_loras),
                             enable_fp8=cfg.fp8transformer, fp8_scaling=cfg.fp8_scaling, fp8_activations=cfg.fp8activations,
                             guider=cfg.guider, apg_eta=cfg.apg_eta, apg_norm_threshold=cfg.apg_norm_threshold,
+                            # the step cache adds its keywords only when it is on: off is today's call
+                            **({} if cfg.step_cache_threshold is None else
+                               {"step_cache_threshold": cfg.step_cache_threshold, "step_cache_coefficients": cfg.step_cache_coefficients}),
                             **inject)
     return output_path if output_path is not None else frames
 
@@ -128,6 +133,8 @@ class _Base:
     guider: str = "cfg"
     apg_eta: float = 1.0
     apg_norm_threshold: float = 0.0
+    step_cache_threshold: Optional[float] = None
+    step_cache_coefficients: Optional[tuple] = None
 
     def _cfg(self, **over) -> MLXPipelineConfig:
         names = {f.name for f in fields(MLXPipelineConfig)}

@@ -49,11 +49,15 @@ class CfgPairSharding:
     def denoise_dev(self, latents, positions, text_embeddings_pos, text_embeddings_neg, transformer, sigmas,
                     cfg_scale: float = 4.0, state=None, forward_fn: Optional[Callable] = None,
                     tail_fn: Optional[Callable] = None, tokens_fn: Optional[Callable] = None, use_graph: bool = True,
-                    guider: str = "cfg"):
+                    guider: str = "cfg", step_cache=None):
         """Sharded twin of denoise.denoise_dev (compiled-step sigma semantics).  ``forward_fn(tok, sigma_bf16,
         ctx) -> velocity`` / ``tail_fn(v_pos, v_neg, latents, cfg, s, s_next) -> latents`` / ``tokens_fn(latents)``
         default to the HIP path; the CPU (gloo) tests inject stand-ins to exercise the exchange logic.  ``guider``: only "cfg";
-        the cfg_star / apg guiders of denoise.denoise_dev are not wired through the sharded loop."""
+        the cfg_star / apg guiders of denoise.denoise_dev are not wired through the sharded loop.  ``step_cache``: only None; a
+        step cache needs one decision per step shared by both ranks, which the sharded loop does not exchange."""
+        if step_cache is not None:
+            raise ValueError("a step cache (step_cache) is not supported on the sharded path (CfgPairSharding); "
+                             "use denoise.denoise_dev on one GPU")
         if guider != "cfg":
             raise ValueError(f"guider={guider!r} is not supported on the sharded path (CfgPairSharding runs plain CFG only); "
                              "use denoise.denoise_dev on one GPU")
