@@ -141,6 +141,34 @@ int ltxk_gemm_w8_plan(const ltxk_gemm_args* args, struct ltxk_gemm_plan* plan);
 int ltxk_gemm_w8a8(const ltxk_gemm_args* args, const float* a_scale, const float* w_scale, void* stream);
 int ltxk_gemm_w8a8_plan(const ltxk_gemm_args* args, struct ltxk_gemm_plan* plan);
 
+/* The same GEMM with both operands in OCP MXFP4 (opt-in): out = epilogue(sum_k a[m,k] * w[n,k]) with
+ * a[m,k] = e2m1(codeA[m,k]) * 2^(EA[m, k/32] - 127) and w likewise.  args->A: (M, K/2) code bytes, element 2i in the low nibble of
+ * byte i, row stride lda in BYTES (pointer and lda 16-byte aligned, lda >= K/2) - what ltxk_quant_rows_mxfp4 writes; args->W: the
+ * (N, K/2) code bytes of weights.quantize_mxfp4, rows contiguous, 16-byte aligned - the panel ltxk_gemv_w4 reads, no re-packing.
+ * a_block_scales (M, K/32) and w_block_scales (N, K/32): the e8m0 bytes with their row strides in bytes; pointers and strides
+ * 8-byte aligned, strides >= K/32, both required.  args->K counts k (elements) and must be a multiple of LTXK_MXFP4_KSTEP = 256;
+ * N % 8 == 0; anything else is LTXK_EINVAL and nothing is launched.
+ * One v_mfma_scale_f32_16x16x128_f8f6f4 with both formats e2m1 per 16x16 tile and 128 k: a lane's 16 bytes are 32 consecutive k =
+ * one scale block, and the block's e8m0 byte is the lane's scale operand - the e8m0 scales are the only scales, no fp32 multiply
+ * follows.  Then the bias and the epilogue of ltxk_gemm_bf16 (every epilogue, the transposed and split outputs and sumsq are the
+ * shared code).  Scale byte 255 is NaN, as the format defines it; the project's quantisers never write it.
+ * Launch forms: the single-pass 160-row family only (every tile height, both tile widths); args->workspace is ignored and a row's
+ * bits depend neither on M nor on the tile.  ltxk_gemm_mxfp4_plan reports SINGLE with that tile and ksteps = K / 256.  There is
+ * no split-K, big-tile or grouped form.                                                                                      */
+#define LTXK_MXFP4_KSTEP 256
+int ltxk_gemm_mxfp4(const ltxk_gemm_args* args, const uint8_t* a_block_scales, int32_t ld_a_scales,
+                    const uint8_t* w_block_scales, int32_t ld_w_scales, void* stream);
+int ltxk_gemm_mxfp4_plan(const ltxk_gemm_args* args, struct ltxk_gemm_plan* plan);
+
+/* Row quantiser in front of ltxk_gemm_mxfp4: x (M,K) bf16 with row stride lda (elements) -> codes (M, K/2) bytes with row stride
+ * ldq (bytes) and block_scales (M, K/32) e8m0 bytes with row stride lds (bytes), in the layout and arithmetic of
+ * weights.quantize_mxfp4, bit for bit.  Per row and 32 consecutive k: E = clamp(floor(log2 amax) - 2, -127, 127) + 127, a zero block
+ * 127, never 255; element = nearest e2m1 magnitude of x / 2^(E-127), ties to the even 3-bit index, saturating at +-6, sign bit
+ * kept (-0 stays -0); element 2i in the low nibble.  Inputs must be finite.  K % 32 == 0; x and lda 16-byte, codes and ldq
+ * 16-byte, scales and lds 1-byte aligned (the GEMM wants them 8-byte aligned).  No atomics; a row's bits depend on that row only. */
+int ltxk_quant_rows_mxfp4(const void* x, int32_t lda, void* codes, int32_t ldq, uint8_t* block_scales, int32_t lds,
+                          int32_t M, int32_t K, void* stream);
+
 /* The weight stream of a decode step: out[m,n] = r(acc * w_scale[n] + bias[n]), acc = A[m,:] . W[n,:] in fp32, for
  * 1 <= M <= 8 rows.  `args` as for ltxk_gemm_w8 (W: (N,K) e4m3fn bytes, 16-byte aligned; A: (M,K) bf16, 16-byte aligned, lda a
  * multiple of 8; out (M,N) bf16 with row stride ldo; bias (N) bf16 or NULL; w_scale (N) fp32 or NULL = no multiply) with

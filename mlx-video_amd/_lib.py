@@ -154,6 +154,9 @@ SIGNATURES = {
     "ltxk_gemm_w8a8": (c_int32, [POINTER(GemmArgs), c_void_p, c_void_p, c_void_p]),
     "ltxk_gemm_w8a8_plan": (c_int32, [POINTER(GemmArgs), POINTER(GemmPlan)]),
     "ltxk_quant_rows_fp8": (c_int32, [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_void_p]),
+    "ltxk_gemm_mxfp4": (c_int32, [POINTER(GemmArgs), c_void_p, c_int32, c_void_p, c_int32, c_void_p]),
+    "ltxk_gemm_mxfp4_plan": (c_int32, [POINTER(GemmArgs), POINTER(GemmPlan)]),
+    "ltxk_quant_rows_mxfp4": (c_int32, [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
     "ltxk_gemm_bf16_grouped": (c_int32, [POINTER(GemmGroupedArgs), c_void_p]),
     "ltxk_gemm_grouped_args_sizeof": (c_int32, []),
     "ltxk_gemm_grouped_plan": (c_int32, [POINTER(GemmGroupedArgs), POINTER(GemmGroupedPlan)]),

@@ -50,7 +50,7 @@ class LTXAVModel:
         if cv.num_layers != ca.num_layers:
             raise ValueError(f"LTXAVModel: the video model has {cv.num_layers} blocks, the audio model {ca.num_layers}")
         if video.weight_dtype != BF16 or audio.weight_dtype != BF16 or video.fp8_activations or audio.fp8_activations:
-            raise ValueError("LTXAVModel: joint denoising runs on bf16 sub-models (no fp8 weights or activations)")
+            raise ValueError("LTXAVModel: joint denoising runs on bf16 sub-models (no fp8 or MXFP4 weights, no fp8 activations)")
         if video.num_attention_heads != audio.num_attention_heads:
             # the reference builds the video cross table with the VIDEO head count and applies it to a q of AUDIO heads
             raise ValueError(f"LTXAVModel: the cross-modal attentions need one head count, got video {video.num_attention_heads}, "

@@ -4,6 +4,8 @@
 // transformer.py:254,257,347 as epilogues.
 // Also ltxk_gemm_w8 (e4m3 weight panel, bf16 activations) and ltxk_gemm_w8a8 (e4m3 on both sides, fp8 x fp8 MFMA): the same tile
 // body with template flags.  W8A8 exists as the single-pass 160-row family only - no split-K, big-tile or grouped form.
+// And ltxk_gemm_mxfp4 (OCP MXFP4 on both sides, the e8m0 block scales as the MFMA's scale operands): the same tile body again,
+// in kernels and with a parameter block of their own (gemm_mxfp4_kernel / GemmParams4); single-pass 160-row family only.
 #include "gemm_core.h"
 #include "epilogue.h"
 #include <stdlib.h>
@@ -73,6 +75,14 @@ struct GemmParams {
   const float* w_scale;
 };
 
+// MXFP4 x MXFP4 forms (gemm_mxfp4_kernel): A and W point at code bytes, K and lda count code BYTES (k / 2), and the e8m0 block
+// scales of both sides come with their row strides in bytes.  A parameter block of its own: the other kernels' stays as it was.
+struct GemmParams4 : GemmParams {
+  const uint8_t* a_mx;
+  const uint8_t* w_mx;
+  int ld_amx, ld_wmx;
+};
+
 // where the transposed columns of a launch go: out, or out2 from n_split on (split output)
 __device__ __forceinline__ TransOut trans_out(const GemmParams& p) {
   return TransOut{p.n_split ? p.out2 : p.out, p.N - p.n_split, p.n_split ? p.ldo2 : p.ldo, p.T, p.M};
@@ -82,9 +92,13 @@ __device__ __forceinline__ TransOut trans_out(const GemmParams& p) {
 // W8: W is (N,K) e4m3fn bytes, staged as fp8 (gemm_core.h) and widened after the fragment read; everything else is shared.
 // A8 (with W8): A is e4m3fn bytes too - 128-k K-steps of 128-byte rows on both sides, multiplied as fp8 by MmaPipe8 (gemm_core.h);
 // loader, ring, counted waits and epilogues are the shared code, plus the per-row factor a_scale on the accumulators.
-template <int TT, int NT, int EPI, bool TRANS, bool W8 = false, bool A8 = false>
-__device__ __forceinline__ void gemm_tile(const GemmParams& p, char* smem, int m0, int n0, int kbase, int nk, int wave, int lane) {
+// A4 (with W8 and A8, whose byte geometry it shares): both operands are MXFP4 code bytes (two k per byte), 256-k K-steps of 128-byte
+// rows, multiplied by MmaPipe4 with the e8m0 block scales of both sides as the instruction's scale operands (P = GemmParams4: K
+// and lda count code BYTES there); no fp32 scale multiply follows.
+template <int TT, int NT, int EPI, bool TRANS, bool W8 = false, bool A8 = false, bool A4 = false, class P = GemmParams>
+__device__ __forceinline__ void gemm_tile(const P& p, char* smem, int m0, int n0, int kbase, int nk, int wave, int lane) {
   static_assert(W8 || !A8, "fp8 activations go with fp8 weights");
+  static_assert(!A4 || (W8 && A8), "the MXFP4 form is staged like the fp8 x fp8 one");
   constexpr bool W64 = W8 && !A8;             // the W half of a stage holds 64-byte fp8 rows (W8A16)
   constexpr int KSTEP = A8 ? GEMM_BK8 : GEMM_BK;
   using G = GemmGeom<TT, 4, NT, W64>;
@@ -144,6 +158,27 @@ __device__ __forceinline__ void gemm_tile(const GemmParams& p, char* smem, int m
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) acc[tt][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
 
+  // A4: this lane's scale rows (W tiles, then A tiles; rows clamped like the loader's) and the first K-step's scales, requested in
+  // front of everything else so that the first counted wait retires them
+  std::conditional_t<A4, MxScales<TT, NT>, NoScales> mx;
+  if constexpr (A4) {
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) {
+      int n = n0 + wn * WC + nt * 16 + (lane & 15);
+      n = n < p.N ? n : p.N - 1;
+      mx.off[nt] = (unsigned)n * (unsigned)p.ld_wmx;
+    }
+#pragma unroll
+    for (int tt = 0; tt < TT; ++tt) {
+      int m = m0 + wm * TT * 16 + tt * 16 + (lane & 15);
+      m = m < p.M ? m : p.M - 1;
+      mx.off[NT + tt] = (unsigned)m * (unsigned)p.ld_amx;
+    }
+    mx.wbase = p.w_mx;
+    mx.abase = p.a_mx;
+    mx.sel = 0x0c0c0000u | ((4u + (lane >> 4)) << 8) | (unsigned)(lane >> 4);
+    mx.request(kbase);
+  }
   LTXK_STAMP(0);
   // Epilogue operands (bias, residual tile, gate rows) are requested up front and arrive under the main loop instead
   // of as a dependent-load chain (gate_row -> gate -> arithmetic) and a 21 MB residual burst when the loop ends.  They
@@ -257,7 +292,16 @@ __device__ __forceinline__ void gemm_tile(const GemmParams& p, char* smem, int m
     auto issue = [&](int i) __attribute__((always_inline)) {
       if constexpr (KC != -2 && KC != -3) issue_piece(i, kt2, s2);
     };
-    if constexpr (A8 || TT >= 2) {
+    if constexpr (A4) {
+      // the scales requested a K-step ago have been retired (by the first wait, then by each step's settle); the next step's go
+      // out in front of this step's LDS-DMA pieces and are retired behind the MFMAs with those pieces still in flight
+      // (settle also retires whatever else was issued in front of this step's pieces - the gate loads, a residual band - which the
+      // other forms leave in flight: nothing is read early, the counted waits of the next steps just find less to wait for)
+      mx.take();
+      if constexpr (KC != -3) mx.request(kbase + (kt + 1 < nk ? kt + 1 : nk - 1));      // (the last step of a peeled tail has no successor)
+      pipe.step(smem + s * G::STAGE_BYTES, wm, wn, lane, acc, issue, mx);
+      mx.template settle<(KC != -2 && KC != -3) ? PER_STAGE : 0>();
+    } else if constexpr (A8 || TT >= 2) {
       pipe.step(smem + s * G::STAGE_BYTES, wm, wn, lane, acc, issue);
     } else {
       mma_stage_pipelined<TT, 4, TRANS, NT, W8>(smem + s * G::STAGE_BYTES, wm, wn, lane, acc, issue);
@@ -278,7 +322,10 @@ __device__ __forceinline__ void gemm_tile(const GemmParams& p, char* smem, int m
     }
     if constexpr (A8 || TT >= 2) pipe.finish(acc);
   };
-  if constexpr (A8) {
+  if constexpr (A4) {
+    MmaPipe4<TT, TRANS, NT> pipe;
+    kloop(pipe);
+  } else if constexpr (A8) {
     MmaPipe8<TT, TRANS, NT> pipe;
     kloop(pipe);
   } else if constexpr (TT >= 2) {
@@ -323,7 +370,7 @@ __device__ __forceinline__ void gemm_tile(const GemmParams& p, char* smem, int m
     }
   }
   LTXK_STAMP(3);
-  if constexpr (A8) {
+  if constexpr (A8 && !A4) {
     // per-row scale of the quantised activations on the fp32 accumulators, first (then w_scale, then the shared epilogue)
 #pragma unroll
     for (int tt = 0; tt < TT; ++tt) {
@@ -346,7 +393,7 @@ __device__ __forceinline__ void gemm_tile(const GemmParams& p, char* smem, int m
         for (int j = 0; j < 4; ++j) acc[tt][nt][j] *= sa[j];
     }
   }
-  if constexpr (W8) {
+  if constexpr (W8 && !A4) {
     // per-output-channel scale on the fp32 accumulators, in front of the shared epilogue (no scale: no multiply)
     if (p.w_scale) {
 #pragma unroll
@@ -492,6 +539,28 @@ __global__ __launch_bounds__(GEMM_THREADS) void gemm_bf16_kernel(GemmParams p) {
     ltxk_gemm_stamps[(size_t)blockIdx.x * 8 + 6] = ((unsigned long long)xcc << 32) | hw;
   }
 #endif
+}
+
+// The same tile kernel on MXFP4 operands (ltxk_gemm_mxfp4): a K-step is 128 code bytes = 256 k
+template <int TT, int NT, int EPI, int MODE>
+__global__ __launch_bounds__(GEMM_THREADS) void gemm_mxfp4_kernel(GemmParams4 p) {
+  using G = GemmGeom<TT, 4, NT, false>;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  int rt, ct;
+  map_tile(blockIdx.x, p.RT, p.CT, rt, ct);
+  const int m0 = rt * G::BM, n0 = ct * G::BN;
+  const int nk = p.K / GEMM_BK8;
+  if constexpr (MODE == 0) {
+    gemm_tile<TT, NT, EPI, false, true, true, true>(p, smem, m0, n0, 0, nk, wave, lane);
+  } else if constexpr (MODE == 1) {
+    gemm_tile<TT, NT, LTXK_EPI_BIAS, true, true, true, true>(p, smem, m0, n0, 0, nk, wave, lane);
+  } else {
+    if (n0 < p.n_split) gemm_tile<TT, NT, EPI, false, true, true, true>(p, smem, m0, n0, 0, nk, wave, lane);
+    else gemm_tile<TT, NT, LTXK_EPI_BIAS, true, true, true, true>(p, smem, m0, n0, 0, nk, wave, lane);
+  }
 }
 
 // One K slice of a small-M (weight-streaming) launch on the 128-column tile: nothing but the main loop and the fp32 tile store,
@@ -673,6 +742,45 @@ static int dispatch_tt(const GemmParams& p, int tt, int epi, bool trans, hipStre
     case 3: return dispatch_epi<3, NT, W8, A8>(p, epi, trans, st);
     case 2: return dispatch_epi<2, NT, W8, A8>(p, epi, trans, st);
     default: return dispatch_epi<1, NT, W8, A8>(p, epi, trans, st);
+  }
+}
+
+template <int TT, int NT, int EPI, int MODE>
+static int launch4(const GemmParams4& p, hipStream_t stream) {
+  using G = GemmGeom<TT, 4, NT, false>;
+  auto kern = gemm_mxfp4_kernel<TT, NT, EPI, MODE>;
+  static std::atomic<uint64_t> attr_set{0};
+  const int rc = ensure_dyn_lds((const void*)kern, G::LDS_BYTES, attr_set, "ltxk_gemm_mxfp4");
+  if (rc != LTXK_OK) return rc;
+  hipLaunchKernelGGL(kern, dim3(p.RT * p.CT), dim3(GEMM_THREADS), G::LDS_BYTES, stream, p);
+  LTXK_CHECK_LAUNCH("ltxk_gemm_mxfp4");
+  return LTXK_OK;
+}
+
+template <int TT, int NT>
+static int dispatch_epi4(const GemmParams4& p, int epi, bool trans, hipStream_t stream) {
+  if (p.n_split) return launch4<TT, NT, LTXK_EPI_BIAS, 2>(p, stream);
+  if (trans) return launch4<TT, NT, LTXK_EPI_BIAS, 1>(p, stream);
+  switch (epi) {
+    case LTXK_EPI_BIAS: return launch4<TT, NT, LTXK_EPI_BIAS, 0>(p, stream);
+    case LTXK_EPI_BIAS_GELU: return launch4<TT, NT, LTXK_EPI_BIAS_GELU, 0>(p, stream);
+    case LTXK_EPI_BIAS_SILU: return launch4<TT, NT, LTXK_EPI_BIAS_SILU, 0>(p, stream);
+    case LTXK_EPI_BIAS_GATE_RES: return launch4<TT, NT, LTXK_EPI_BIAS_GATE_RES, 0>(p, stream);
+    case LTXK_EPI_BIAS_RES: return launch4<TT, NT, LTXK_EPI_BIAS_RES, 0>(p, stream);
+    case LTXK_EPI_SCALE_RES: return launch4<TT, NT, LTXK_EPI_SCALE_RES, 0>(p, stream);
+  }
+  ltxk_set_error("ltxk_gemm_mxfp4: unknown epilogue %d", epi);
+  return LTXK_EINVAL;
+}
+
+template <int NT>
+static int dispatch_tt4(const GemmParams4& p, int tt, int epi, bool trans, hipStream_t st) {
+  switch (tt) {
+    case 5: return dispatch_epi4<5, NT>(p, epi, trans, st);
+    case 4: return dispatch_epi4<4, NT>(p, epi, trans, st);
+    case 3: return dispatch_epi4<3, NT>(p, epi, trans, st);
+    case 2: return dispatch_epi4<2, NT>(p, epi, trans, st);
+    default: return dispatch_epi4<1, NT>(p, epi, trans, st);
   }
 }
 
@@ -1127,14 +1235,15 @@ struct GemmForm {
 // with the same M, N, K and workspace, so the two calls sum every row's products in the same order.
 // a8: the form of ltxk_gemm_w8a8 - A is e4m3 bytes (lda in bytes, a multiple of 16), K-steps are 128 wide, and the launch is
 // always the single-pass 160-row family with the tile pick_tile gives: no big tile, no split-K.
-static int gemm_form(const ltxk_gemm_args* a, GemmForm& f, bool w8 = false, bool a8 = false) {
+// a4 (with a8): the form of ltxk_gemm_mxfp4 - A and W are MXFP4 code bytes (lda in bytes, at least K / 2), K-steps are 256 wide.
+static int gemm_form(const ltxk_gemm_args* a, GemmForm& f, bool w8 = false, bool a8 = false, bool a4 = false) {
   LTXK_CHECK_ARG(a != nullptr, "ltxk_gemm_bf16: null args");
   LTXK_CHECK_ARG(a->A && a->W && a->out, "ltxk_gemm_bf16: null A/W/out");
   LTXK_CHECK_ARG(a->M > 0 && a->N > 0 && a->K > 0, "ltxk_gemm_bf16: bad dims M=%d N=%d K=%d", a->M, a->N, a->K);
-  const int bk = a8 ? GEMM_BK8 : GEMM_BK;
+  const int bk = a4 ? LTXK_MXFP4_KSTEP : (a8 ? GEMM_BK8 : GEMM_BK);
   LTXK_CHECK_ARG(a->K % bk == 0, "ltxk_gemm_bf16: K=%d must be a multiple of %d", a->K, bk);
   LTXK_CHECK_ARG(a->N % 8 == 0, "ltxk_gemm_bf16: N=%d must be a multiple of 8", a->N);
-  LTXK_CHECK_ARG(a->lda >= a->K && a->lda % (a8 ? 16 : 8) == 0, "ltxk_gemm_bf16: lda=%d (K=%d) must be >=K, multiple of %d", a->lda, a->K, a8 ? 16 : 8);
+  LTXK_CHECK_ARG(a->lda >= (a4 ? a->K / 2 : a->K) && a->lda % (a8 ? 16 : 8) == 0, "ltxk_gemm_bf16: lda=%d (K=%d) must be >=%s, multiple of %d", a->lda, a->K, a4 ? "K/2" : "K", a8 ? 16 : 8);
   LTXK_CHECK_ARG(((uintptr_t)a->A & 15) == 0 && ((uintptr_t)a->W & 15) == 0 && ((uintptr_t)a->out & 7) == 0,
                  "ltxk_gemm_bf16: A/W must be 16-byte aligned, out 8-byte aligned");
   // (checked here and not only by the single-pass dispatch: the split-K epilogue launch would run an unknown one as EPI_BIAS)
@@ -1333,6 +1442,47 @@ extern "C" int ltxk_gemm_w8a8_plan(const ltxk_gemm_args* a, struct ltxk_gemm_pla
   const int rc = gemm_form(a, f, true, true);
   if (rc == LTXK_OK) *plan = f.plan;
   return rc;
+}
+
+extern "C" int ltxk_gemm_mxfp4_plan(const ltxk_gemm_args* a, struct ltxk_gemm_plan* plan) {
+  using namespace ltxk;
+  LTXK_CHECK_ARG(plan != nullptr, "ltxk_gemm_mxfp4_plan: null plan");
+  GemmForm f;
+  const int rc = gemm_form(a, f, true, true, true);
+  if (rc == LTXK_OK) *plan = f.plan;
+  return rc;
+}
+
+extern "C" int ltxk_gemm_mxfp4(const ltxk_gemm_args* a, const uint8_t* a_block_scales, int32_t ld_a_scales,
+                               const uint8_t* w_block_scales, int32_t ld_w_scales, void* stream) {
+  using namespace ltxk;
+  GemmForm f;
+  const int rc = gemm_form(a, f, true, true, true);
+  if (rc != LTXK_OK) return rc;
+  LTXK_CHECK_ARG(a_block_scales != nullptr && w_block_scales != nullptr, "ltxk_gemm_mxfp4: both block-scale panels are required");
+  LTXK_CHECK_ARG(((uintptr_t)a_block_scales & 7) == 0 && ((uintptr_t)w_block_scales & 7) == 0 && ld_a_scales % 8 == 0 && ld_w_scales % 8 == 0,
+                 "ltxk_gemm_mxfp4: block-scale panels and their row strides must be 8-byte aligned");
+  LTXK_CHECK_ARG((int64_t)a->M * ld_a_scales < (1LL << 31) && (int64_t)a->N * ld_w_scales < (1LL << 31), "ltxk_gemm_mxfp4: a block-scale panel of 2 GiB or more");
+  LTXK_CHECK_ARG(ld_a_scales >= a->K / 32 && ld_w_scales >= a->K / 32, "ltxk_gemm_mxfp4: scale row strides %d / %d below K/32=%d", ld_a_scales, ld_w_scales, a->K / 32);
+  const bool split = f.split, trans = f.trans;
+  GemmParams4 p;
+  p.A = (const bf16*)a->A; p.W = (const bf16*)a->W; p.bias = (const bf16*)a->bias;
+  p.out = (bf16*)a->out; p.resid = (const bf16*)a->resid; p.gate = (const bf16*)a->gate;
+  p.gate_row = a->gate_row;
+  p.M = a->M; p.N = a->N; p.K = a->K / 2; p.lda = a->lda; p.ldo = a->ldo; p.ldr = a->ldr;      // (K: code bytes per row)
+  p.gate_stride = a->gate_stride; p.T = (trans || split) ? a->out_tokens_per_batch : 1; p.alpha = a->alpha;
+  p.out2 = (bf16*)a->out2; p.n_split = split ? a->n_split : 0; p.ldo2 = a->ldo2;
+  p.sumsq = a->sumsq; p.sumsq_ld = a->sumsq_ld;
+  const int wide_env = LTXK_AB_INT("LTXK_GEMM_WIDE", 1);
+  p.wide = (!trans && wide_env && a->epilogue != LTXK_EPI_BIAS_GELU && a->ldo % 8 == 0 && ((uintptr_t)a->out & 15) == 0) ? 1 : 0;
+  p.RT = f.plan.row_tiles;
+  p.CT = f.plan.col_tiles;
+  p.part = nullptr;
+  p.ksteps = f.plan.ksteps;
+  p.w_scale = nullptr;
+  p.a_mx = a_block_scales; p.w_mx = w_block_scales; p.ld_amx = ld_a_scales; p.ld_wmx = ld_w_scales;
+  hipStream_t st = (hipStream_t)stream;
+  return f.nt == 2 ? dispatch_tt4<2>(p, f.tt, a->epilogue, trans, st) : dispatch_tt4<4>(p, f.tt, a->epilogue, trans, st);
 }
 
 extern "C" int ltxk_gemm_grouped_args_sizeof(void) { return (int)sizeof(ltxk_gemm_grouped_args); }

@@ -311,7 +311,7 @@ def generate_video(model_repo: Optional[str] = None, text_encoder_repo: Optional
                    audio_negative_prompt_embeds: Optional[torch.Tensor] = None, fp8_text_encoder: bool = False,
                    enhance_device_loop: bool = False, enhance_mxfp4: bool = False,
                    step_cache_threshold: Optional[float] = None,
-                   step_cache_coefficients: Optional[Sequence[float]] = None) -> np.ndarray:
+                   step_cache_coefficients: Optional[Sequence[float]] = None, enable_mxfp4: bool = False) -> np.ndarray:
     """See the module docstring.  Returns uint8 frames (F,H,W,3) (generate.py:4195-4197).
     ``hoist_context`` (not in the reference, off by default): the part of the forward that depends on the text context only -
     caption projection and the 48 cross-attention K / V^T projections, 3.37 TFLOP that the reference recomputes in every forward
@@ -327,6 +327,11 @@ def generate_video(model_repo: Optional[str] = None, text_encoder_repo: Optional
     model.  A ``transformer=`` / ``stage2_transformer=`` passed in is used as it is.
     ``fp8_activations`` (--fp8-activations; needs ``enable_fp8``, a ValueError without it): the transformers this call builds also
     quantise the inputs of their in-block Linear layers to e4m3 per row and multiply fp8 x fp8 (ltxk_gemm_w8a8).
+    ``enable_mxfp4`` (--enable-mxfp4; opt-in): every video transformer this call builds - the LoRA-merged stage-2 one
+    included - keeps the matrices of its in-block Linear layers as OCP MXFP4 (4.25 bits per weight) and multiplies them with
+    activations quantised to MXFP4 per row and 32 k, on the fp4 block-scaled MFMA (ltxk_gemm_mxfp4); everything else stays bf16.
+    LoRAs are merged in bf16 and the result quantised, as for fp8.  Not together with ``enable_fp8`` / ``fp8_activations``, nor with
+    ``audio_mode="joint"``: a ValueError.  A ``transformer=`` / ``stage2_transformer=`` passed in is used as it is.
     ``fp8_text_encoder`` (--fp8-text-encoder): the Gemma-3 encoder this call builds from ``gemma_repo`` keeps its projections and
     its embedding table as e4m3 panels (``GemmaEncoder(fp8=fp8_scaling)``) - half the resident bytes, and half the
     bytes a decoded token of ``enhance_prompt`` streams; the one encoder serves the text encode and the enhancement.  It needs
@@ -409,8 +414,8 @@ def generate_video(model_repo: Optional[str] = None, text_encoder_repo: Optional
             raise ValueError(f"audio_mode='joint' runs in the dev pipeline's denoise loop only, not in the {pipeline.value} pipeline"
                              f"{' with stage2_dev' if stage2_dev else ''} (the joint branch of the distilled loop and the audio "
                              "re-noising between stages are not implemented)")
-        if enable_fp8 or fp8_activations:
-            raise ValueError("audio_mode='joint' runs on bf16 weights: enable_fp8 / fp8_activations are not supported with it")
+        if enable_fp8 or fp8_activations or enable_mxfp4:
+            raise ValueError("audio_mode='joint' runs on bf16 weights: enable_fp8 / fp8_activations / enable_mxfp4 are not supported with it")
         if float(stg_scale or 0.0) != 0.0 or (guider or "cfg") != "cfg" or hoist_context:
             raise ValueError("audio_mode='joint': the joint loop does plain CFG - no STG (stg_scale), no cfg_star / apg guider, no "
                              "hoist_context")
@@ -483,6 +488,9 @@ def generate_video(model_repo: Optional[str] = None, text_encoder_repo: Optional
     from .weights import FP8_SCALINGS
     if fp8_scaling not in FP8_SCALINGS:
         raise ValueError(f"Unknown fp8_scaling: {fp8_scaling!r} (expected one of {FP8_SCALINGS})")
+    if enable_mxfp4 and (enable_fp8 or fp8_activations):
+        raise ValueError("enable_mxfp4 (--enable-mxfp4) and enable_fp8 / fp8_activations (--enable-fp8 / --fp8-activations) are two formats "
+                         "of the same matrices: choose one")
     if fp8_activations and not enable_fp8:
         raise ValueError("fp8_activations (--fp8-activations) needs enable_fp8 (--enable-fp8): fp8 activations multiply fp8 weight panels")
     if fp8_text_encoder:
@@ -500,6 +508,9 @@ def generate_video(model_repo: Optional[str] = None, text_encoder_repo: Optional
         if enable_fp8:
             from .weights import quantize_transformer_weights
             weights_ = quantize_transformer_weights(weights_, fp8_scaling)
+        if enable_mxfp4:              # (an MXFP4 dict is kept as it is; the model recognises it)
+            from .weights import quantize_transformer_weights_mxfp4
+            return LTXModel(cfg_, quantize_transformer_weights_mxfp4(weights_))
         return LTXModel(cfg_, weights_, fp8_activations=fp8_activations)
 
     out_h, out_w = height, width
@@ -529,7 +540,7 @@ def generate_video(model_repo: Optional[str] = None, text_encoder_repo: Optional
     # here (this call owns them); a caller that passes its own model opts in explicitly
     if lora_in_place is None:
         lora_in_place = transformer is None and transformer_weights is None
-    if enable_fp8 and (transformer is None or transformer.weight_dtype != BF16):
+    if (enable_fp8 or enable_mxfp4) and (transformer is None or transformer.weight_dtype != BF16):
         # fp8 panels take no in-place merge: merge-then-quantise builds the merged model afresh, and an fp8 replica is no
         # larger than what the in-place merge was saving
         lora_in_place = False
@@ -540,7 +551,8 @@ def generate_video(model_repo: Optional[str] = None, text_encoder_repo: Optional
         mods = load_pipeline_modules(model_repo, device or torch.device("cuda:0"), need_encoder=bool(images_list or video_conditionings),
                                      need_upsampler=is_distilled, build_transformer=False,
                                      # with LoRAs to merge the base dict stays bf16 (they are merged in bf16, then quantised)
-                                     fp8=enable_fp8 and not (loras or distilled_loras), fp8_scaling=fp8_scaling)
+                                     fp8=enable_fp8 and not (loras or distilled_loras), fp8_scaling=fp8_scaling,
+                                     **({"mxfp4": True} if enable_mxfp4 and not (loras or distilled_loras) else {}))
         transformer_weights, transformer_config = mods["transformer_weights"], mods["transformer_config"]
         vae_decoder = vae_decoder or mods["vae_decoder"]
         vae_encoder, upsampler = vae_encoder or mods.get("vae_encoder"), upsampler or mods.get("upsampler")
@@ -791,6 +803,8 @@ def generate_video(model_repo: Optional[str] = None, text_encoder_repo: Optional
                    "fp32_euler": bool(fp32_euler), "audio": waveform is not None,
                    **({"audio_mode": "joint" if joint else "separate"} if audio else {}), "phases_s": {k: float(v) for k, v in timer.times_s.items()},
                    "peak_memory_gb": float(torch.cuda.max_memory_allocated() / (1024 ** 3))}
+        if enable_mxfp4:              # off: today's keys
+            payload["weight_format"] = "mxfp4"
         if step_caches:               # off: today's keys
             payload["step_cache"] = {"threshold": step_caches[0].threshold, "coefficients": list(step_caches[0].coefficients),
                                      "calls": [c.counts for c in step_caches]}
@@ -963,6 +977,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--fp8-activations", action="store_true", default=False,
                     help="(not in the reference CLI; needs --enable-fp8) quantise the in-block Linear inputs to FP8 per row and "
                          "multiply on the fp8 matrix pipe")
+    ap.add_argument("--enable-mxfp4", action="store_true", default=False,
+                    help="(not in the reference CLI; opt-in) keep the in-block Linear matrices of the video transformer as OCP MXFP4 and "
+                         "multiply them with MXFP4-quantised activations on the fp4 block-scaled MFMA; not with --enable-fp8")
     ap.add_argument("--fp8-text-encoder", action="store_true", default=False,
                     help="(not in the reference CLI; needs --gemma-repo) keep Gemma-3's projections and embedding table as FP8 (e4m3) "
                          "panels, scaled as --fp8-scaling says: the text encode and --enhance-prompt run on them")
@@ -1037,6 +1054,8 @@ def load_prompt_tokens(path: str):
 
 def main(argv: Optional[Sequence[str]] = None) -> None:
     args = resolve_cli_heuristics(build_parser().parse_args(argv))
+    if args.enable_mxfp4 and (args.enable_fp8 or args.fp8_activations):
+        raise ValueError("--enable-mxfp4 and --enable-fp8 / --fp8-activations are two formats of the same matrices: choose one")
     if args.fp8_activations and not args.enable_fp8:
         raise ValueError("--fp8-activations needs --enable-fp8: fp8 activations multiply fp8 weight panels")
     if args.fp8_text_encoder and not args.gemma_repo:
@@ -1059,7 +1078,7 @@ def main(argv: Optional[Sequence[str]] = None) -> None:
         videos.append((args.reference_video, 0, 1.0))
     if args.synthetic:
         from .video_vae import random_decoder_weights
-        if args.enable_fp8:       # the weight dict instead of the model: generate_video quantises what it builds
+        if args.enable_fp8 or args.enable_mxfp4:       # the weight dict instead of the model: generate_video quantises what it builds
             kw["transformer_config"] = LTXModelConfig(num_layers=args.layers)
             kw["transformer_weights"] = LTXModel.random_weights(kw["transformer_config"], dev)
         else:
@@ -1132,7 +1151,8 @@ def main(argv: Optional[Sequence[str]] = None) -> None:
                    fp32_euler=args.fp32_euler, stg_scale=args.stg_scale, stg_blocks=args.stg_blocks, stg_mode=args.stg_mode,
                    enable_fp8=args.enable_fp8, fp8_scaling=args.fp8_scaling, fp8_activations=args.fp8_activations,
                    guider=args.guider, apg_eta=args.apg_eta, apg_norm_threshold=args.apg_norm_threshold,
-                   **({"fp8_text_encoder": True} if args.fp8_text_encoder else {}), **kw)
+                   **({"fp8_text_encoder": True} if args.fp8_text_encoder else {}),
+                   **({"enable_mxfp4": True} if args.enable_mxfp4 else {}), **kw)
 
 
 if __name__ == "__main__":

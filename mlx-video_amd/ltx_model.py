@@ -30,6 +30,13 @@ from .guidance import BatchedPerturbationConfig, PerturbationType
 
 BF16 = torch.bfloat16
 FP8 = torch.float8_e4m3fn
+MXFP4 = torch.float4_e2m1fn_x2          # ``weight_dtype`` of a model whose in-block matrices are OCP MXFP4 panels
+MXSCALE_SUFFIX = "_mxscale"             # "<name>.weight" (uint8 codes) comes with "<name>.weight_mxscale" ((N, K/32) uint8 e8m0)
+
+
+def is_mxfp4_weights(weights) -> bool:
+    """Whether a module-key weight dict holds MXFP4 matrices (weights.quantize_transformer_weights_mxfp4)."""
+    return any(k.endswith(MXSCALE_SUFFIX) for k in weights)
 
 
 @dataclass(frozen=True)
@@ -140,11 +147,13 @@ def _freqs_cis_one_axis(positions: torch.Tensor, dim: int, theta: float, max_pos
 
 class Linear:
     """One Linear layer as the GEMMs read it: the (out,in) matrix ``w`` (bf16 or float8_e4m3fn), the per-output-channel fp32
-    ``scale`` of an e4m3 matrix (None: a bf16 model, or an unscaled fp8 panel) and ``bias``.  Holds what it is given: no copy."""
-    __slots__ = ("w", "scale", "bias")
+    ``scale`` of an e4m3 matrix (None: a bf16 model, or an unscaled fp8 panel) and ``bias``.  An MXFP4 panel
+    (weights.quantize_mxfp4) is ``w`` = the (out, in/2) uint8 codes with ``mx`` = the (out, in/32) uint8 block scales.  Holds what
+    it is given: no copy."""
+    __slots__ = ("w", "scale", "bias", "mx")
 
-    def __init__(self, w: torch.Tensor, scale: Optional[torch.Tensor], bias: torch.Tensor):
-        self.w, self.scale, self.bias = w, scale, bias
+    def __init__(self, w: torch.Tensor, scale: Optional[torch.Tensor], bias: torch.Tensor, mx: Optional[torch.Tensor] = None):
+        self.w, self.scale, self.bias, self.mx = w, scale, bias, mx
 
     @property
     def N(self) -> int:
@@ -152,17 +161,20 @@ class Linear:
 
     @property
     def K(self) -> int:
-        return self.w.shape[1]
+        return self.w.shape[1] * (2 if self.mx is not None else 1)
 
     def rows(self, a: Optional[int], b: Optional[int]) -> "Linear":
         """Output channels [a, b) as a Linear of views: one part of a packed panel."""
-        return Linear(self.w[a:b], None if self.scale is None else self.scale[a:b], self.bias[a:b])
+        return Linear(self.w[a:b], None if self.scale is None else self.scale[a:b], self.bias[a:b],
+                      None if self.mx is None else self.mx[a:b])
 
     @staticmethod
     def cat(parts: Sequence["Linear"]) -> "Linear":
         """The parts packed row-wise into one panel (an fp8 matrix through its bytes).  No part scaled: no scale; otherwise
         one scale vector, with ones for the unscaled parts."""
         ws = [p.w for p in parts]
+        if parts[0].mx is not None:         # block scales are per row: a plain concatenation of codes and of scales
+            return Linear(torch.cat(ws, 0), None, torch.cat([p.bias for p in parts], 0), torch.cat([p.mx for p in parts], 0))
         w = torch.cat([t.view(torch.uint8) for t in ws], 0).view(FP8) if ws[0].dtype == FP8 else torch.cat(ws, 0)
         scale = None
         if any(p.scale is not None for p in parts):
@@ -211,6 +223,13 @@ class LTXModel:
         if fp8_activations and not any(torch.is_tensor(v) and v.dtype == FP8 for v in weights.values()):
             raise ValueError("fp8_activations needs float8_e4m3fn weights (weights.transformer_weights(fp8=True) / "
                              "quantize_transformer_weights): fp8 activations multiply fp8 weight panels")
+        if is_mxfp4_weights(weights):
+            if fp8_activations:
+                raise ValueError("fp8_activations on an MXFP4 weight dict: its in-block GEMMs run on MXFP4 operands on both sides "
+                                 "(ops.gemm_mxfp4); fp8 activations go with float8_e4m3fn weights")
+            if config.attention_head_dim != 128:
+                raise ValueError(f"MXFP4 weights with attention_head_dim = {config.attention_head_dim}: the MXFP4 DiT is the video "
+                                 "transformer (head dim 128); the head-dim-64 audio configuration is not supported")
         self.config = config
         self.inner_dim = config.inner_dim
         self.num_attention_heads = config.num_attention_heads
@@ -275,12 +294,23 @@ class LTXModel:
         # an fp8 matrix may come with a per-output-channel scale under "<key>_scale" and stays fp8 inside the model - every
         # GEMM over it is ltxk_gemm_w8, no bf16 copy of a panel is ever made.
         mats = [k for k in self.expected_keys(cfg) if k.endswith(".weight") and W[k].ndim == 2]
-        self.weight_dtype = FP8 if any(W[k].dtype == FP8 for k in mats) else BF16
+        # Or the in-block matrices are MXFP4 (weights.quantize_transformer_weights_mxfp4): uint8 codes under the key and the e8m0
+        # block scales under "<key>_mxscale"; every GEMM over them is ltxk_gemm_mxfp4 on quantised activations and
+        # everything else stays bf16.
+        mxfp4 = is_mxfp4_weights(W)
+        self.weight_dtype = MXFP4 if mxfp4 else (FP8 if any(W[k].dtype == FP8 for k in mats) else BF16)
         fp8 = self.weight_dtype == FP8
 
         def load(k):
             """The Linear of one checkpoint ``*.weight`` key: the matrix, its optional ``<key>_scale`` (fp8 model), its ``.bias``."""
             bias = g(k[:-len("weight")] + "bias")
+            if mxfp4 and k + MXSCALE_SUFFIX in W:
+                c, sc = W[k], W[k + MXSCALE_SUFFIX]
+                if c.dtype != torch.uint8 or sc.dtype != torch.uint8 or not c.is_cuda or c.ndim != 2 or sc.device != c.device or \
+                        tuple(sc.shape) != (c.shape[0], c.shape[1] // 16) or (2 * c.shape[1]) % ops.MXFP4_KSTEP:
+                    raise TypeError(f"weight {k}: an MXFP4 matrix is (N, K/2) uint8 codes with (N, K/32) uint8 block scales under "
+                                    f"{k + MXSCALE_SUFFIX!r} on the device, K a multiple of {ops.MXFP4_KSTEP}")
+                return Linear(c.contiguous(), None, bias, sc.contiguous())
             if not fp8:
                 return Linear(g(k), None, bias)
             t, sc = W[k], W.get(k + "_scale")
@@ -339,15 +369,16 @@ class LTXModel:
         returned as their row ranges.  Writing through these views changes the model (lora.apply_lora_to_weights(...,
         in_place=True): the stage-2 transformer of the distilled pipeline without a second 21-GB replica, generate.py:3229-3283)."""
         if self.weight_dtype != BF16:
-            raise TypeError("weight_views: this model keeps its matrices in float8_e4m3fn, which cannot take an in-place LoRA merge; "
+            fmt, fn = ("MXFP4", "quantize_transformer_weights_mxfp4") if self.weight_dtype == MXFP4 else ("float8_e4m3fn", "quantize_transformer_weights")
+            raise TypeError(f"weight_views: this model keeps its matrices in {fmt}, which cannot take an in-place LoRA merge; "
                             "merge into the bf16 weight dict (lora.apply_lora_to_weights(weights, specs), the fresh-copy path), "
-                            "quantise the result (weights.quantize_transformer_weights) and build a model from it")
+                            f"quantise the result (weights.{fn}) and build a model from it")
         return {k: panel.w[a:b] for k, (panel, a, b) in self._panels.items()}
 
     def weight_bytes(self) -> int:
         """Device bytes of everything this model holds of its checkpoint: the matrices (bf16, or e4m3 panels plus their scale
         vectors), biases, norm weights and scale-shift tables."""
-        held = [t for panel, _, _ in self._panels.values() for t in (panel.w, panel.scale, panel.bias) if t is not None]
+        held = [t for panel, _, _ in self._panels.values() for t in (panel.w, panel.scale, panel.bias, panel.mx) if t is not None]
         held += [self.head_table, self.tables, self.wkn2_all]
         held += [t for b in self.blocks for t in (b.wqn, b.wkn, b.wqn2)]     # (wkn2: a row of wkn2_all; wqkn: a copy of wqn | wkn)
         once = {}                           # a packed panel is in the table once per key: each tensor counts once, as first seen
@@ -451,6 +482,10 @@ class LTXModel:
     def _gemm(self, a: torch.Tensor, lin: Linear, a_q: Optional[tuple] = None, **kw) -> torch.Tensor:
         """THE ops.gemm call of the model: ``lin`` over ``a``, or over its quantised twin ``a_q`` = (a8, a_scale) (W8A8).
         Split-K as batch_invariant allows and the panel's own scale, for every launch."""
+        if lin.mx is not None:
+            if a_q is None:
+                raise ValueError("an MXFP4 panel multiplies quantised activations only (ops.gemm_mxfp4): no buffers were given")
+            return ops.gemm_mxfp4(a_q[0], a_q[1], lin.w, lin.mx, lin.bias, **kw)
         if a_q is not None:
             a, kw["a_scale"] = a_q
         return ops.gemm(a, lin.w, lin.bias, split_k=self._split_k, w_scale=lin.scale, **kw)
@@ -463,6 +498,11 @@ class LTXModel:
         """The GEMM launches [(Linear, kwargs)] over one input ``a``.  ``q`` = (a8, a_scale) buffers (None: fp8 activations
         off - exactly the ops.gemm calls): ``a`` is quantised into them by ONE launch if any of the launches runs W8A8
         (``fresh=False``: they already hold ``a`` quantised), and those launches read the quantised copy."""
+        if any(lin.mx is not None for lin, _ in launches):
+            # MXFP4 panels: every launch is ltxk_gemm_mxfp4 over the one quantised copy, whatever M is (no other GEMM to fall back to)
+            if fresh:
+                ops.quant_rows_mxfp4(a, out=q)
+            return [self._gemm(a, lin, q, **kw) for lin, kw in launches]
         use = [q is not None and self._w8a8_launch(a.shape[0], lin, **kw) for lin, kw in launches]
         if fresh and any(use):
             ops.quant_rows_fp8(a, out=q)
@@ -503,6 +543,8 @@ class LTXModel:
     def _quant_context(self, ctx: torch.Tensor, s: int) -> Optional[tuple]:
         """The projected context quantised for the text k | V^T launches of ALL blocks (they share shapes, so one decision and
         one quantiser launch per forward), or None where those launches stay W8A16."""
+        if self.weight_dtype == MXFP4:
+            return ops.quant_rows_mxfp4(ctx)
         launches = self._context_kv_launches(self.blocks[0], None, None, True if self.fuse & 2 else None, s)
         return ops.quant_rows_fp8(ctx) if any(self._w8a8_launch(ctx.shape[0], lin, **kw) for lin, kw in launches) else None
 
@@ -626,6 +668,10 @@ class LTXModel:
             def qbuf(cols):
                 return (torch.empty((M, cols), dtype=FP8, device=dev), torch.empty((M,), dtype=torch.float32, device=dev))
             nx_q, att_q, hff_q = qbuf(D), qbuf(D), qbuf(4 * D)
+        if self.weight_dtype == MXFP4:     # the quantised twins for ltxk_gemm_mxfp4: code bytes + e8m0 block scales per row
+            def qbuf4(cols):
+                return (torch.empty((M, cols // 2), dtype=torch.uint8, device=dev), torch.empty((M, cols // 32), dtype=torch.uint8, device=dev))
+            nx_q, att_q, hff_q = qbuf4(D), qbuf4(D), qbuf4(4 * D)
         ms = 6 * D
         kv_buf = kv_all = None
         if ctx_kv is None:

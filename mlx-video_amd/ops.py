@@ -319,6 +319,87 @@ def gemv_w4(a, codes, block_scales, bias=None, out=None):
     return out
 
 
+MXFP4_KSTEP = 256           # k per K-step of ltxk_gemm_mxfp4 (LTXK_MXFP4_KSTEP): K must be a multiple of it
+
+
+def quant_rows_mxfp4(a, out=None):
+    """ltxk_quant_rows_mxfp4: ``a`` (M, K) bf16 (row stride may exceed K), K % 32 == 0 -> (codes (M, K/2) uint8, block_scales
+    (M, K/32) uint8), bit for bit ``weights.quantize_mxfp4(a)``: OCP MXFP4, one e8m0 scale per 32 consecutive k, element 2i in the
+    low nibble.  ``out=(codes, block_scales)``: write into these (either may be rows of a wider buffer)."""
+    M, K = _dims("quant_rows_mxfp4", "a", a, BF16, 2)
+    if K == 0 or K % MXFP4_BLOCK:
+        raise ValueError(f"quant_rows_mxfp4: needs K % {MXFP4_BLOCK} == 0 (one scale per {MXFP4_BLOCK} k), got K = {K}")
+    if a.stride(0) % 8:
+        raise ValueError(f"quant_rows_mxfp4: the rows of `a` must lie a multiple of 8 elements apart, got {a.stride(0)}")
+    q, sc = out if out is not None else (None, None)
+    if q is not None and q.dim() == 2 and q.stride(0) % 16:
+        raise ValueError(f"quant_rows_mxfp4: the rows of out[0] must lie a multiple of 16 bytes apart, got {q.stride(0)}")
+    _operands("quant_rows_mxfp4", ("a", a, BF16, 2, 16, True), ("out[0]", q, torch.uint8, (M, K // 2), 16, True),
+              ("out[1]", sc, torch.uint8, (M, K // MXFP4_BLOCK), 1, True))
+    if out is None:
+        q = torch.empty((M, K // 2), dtype=torch.uint8, device=a.device)
+        sc = torch.empty((M, K // MXFP4_BLOCK), dtype=torch.uint8, device=a.device)
+    with _timed("quant_rows_mxfp4", 0.0, 2.0 * M * K + 0.5 * M * K + 1.0 * M * (K // MXFP4_BLOCK)):
+        check(_lib.load().ltxk_quant_rows_mxfp4(_p(a), a.stride(0), _p(q), q.stride(0), _p(sc), sc.stride(0), M, K, _stream()),
+              "ltxk_quant_rows_mxfp4")
+    return q, sc
+
+
+def gemm_mxfp4(a, a_scales, w, w_scales, bias=None, *, epilogue=EPI_BIAS, out=None, resid=None, gate=None, gate_row=None,
+               gate_stride=0, out_tokens_per_batch=0, alpha=1.0, out2=None, n_split=0, sumsq=None):
+    """out = epi(deq(a) @ deq(w).T + bias) with both operands in OCP MXFP4 (ltxk_gemm_mxfp4): ``a`` (M, K/2) uint8 codes (rows may
+    be a multiple of 16 bytes apart) with ``a_scales`` (M, K/32) uint8 - what ``quant_rows_mxfp4`` returns - and ``w`` (N, K/2) /
+    ``w_scales`` (N, K/32), the contiguous pair of ``weights.quantize_mxfp4``.  K % MXFP4_KSTEP == 0, N % 8 == 0.  Epilogues,
+    ``out``, ``out2`` / ``n_split``, ``out_tokens_per_batch`` and ``sumsq`` as for ``gemm``.  Always single-pass: a row's bits
+    depend on that row, the panel and the epilogue operands alone.  (Refusals: tests/test_mxfp4_dit_cpu.py.)"""
+    U8 = torch.uint8
+    M, K2 = _dims("gemm_mxfp4", "a", a, U8, 2)
+    N = _dims("gemm_mxfp4", "w", w, U8, 2)[0]
+    K = 2 * K2
+    if K == 0 or K % MXFP4_KSTEP:
+        raise ValueError(f"gemm_mxfp4: needs K % {MXFP4_KSTEP} == 0, got K = {K} ({K2} code bytes per row of `a`)")
+    if N % 8:
+        raise ValueError(f"gemm_mxfp4: needs N % 8 == 0, got N = {N}")
+    if a.stride(0) % 16:
+        raise ValueError(f"gemm_mxfp4: the rows of `a` must lie a multiple of 16 bytes apart, got {a.stride(0)}")
+    if a_scales is not None and a_scales.dim() == 2 and a_scales.stride(0) % 8:
+        raise ValueError(f"gemm_mxfp4: the rows of `a_scales` must lie a multiple of 8 bytes apart, got {a_scales.stride(0)}")
+    if a_scales is None or w_scales is None:
+        raise TypeError("gemm_mxfp4: both block-scale panels are required")
+    if n_split and out2 is None:
+        raise ValueError("gemm_mxfp4: split output needs a bf16 `out2`")
+    if out is None and out_tokens_per_batch:
+        raise ValueError("gemm_mxfp4: transposed output needs a preallocated `out`")
+    if not n_split:
+        out2 = None
+    T = out_tokens_per_batch
+    cols, nb = n_split or N, M // T if T else 0
+    _operands("gemm_mxfp4", ("a", a, U8, 2, 16, True), ("a_scales", a_scales, U8, (M, K // MXFP4_BLOCK), 8, True),
+              ("w", w, U8, (N, K2), 16), ("w_scales", w_scales, U8, (N, K // MXFP4_BLOCK), 8), ("bias", bias, BF16, (N,), 8),
+              ("out", out, BF16, (nb, N, -T) if T and not n_split else (M, cols), 8, True), ("resid", resid, BF16, (M, N), 8, True),
+              ("gate", gate, BF16, _table("gemm_mxfp4", "gate", gate, N, gate_stride), 8, True), ("gate_row", gate_row, I32, (M,), 4),
+              ("out2", out2, BF16, (nb, N - n_split, -T), 8, True), ("sumsq", sumsq, F32, (M, -(cols // 64)), 4, True))
+    if out is None:
+        out = torch.empty((M, N), dtype=BF16, device=a.device)
+    args = GemmArgs()
+    args.A, args.W, args.bias, args.out = _p(a), _p(w), _p(bias), _p(out)
+    args.resid, args.gate, args.gate_row = _p(resid), _p(gate), _p(gate_row)
+    args.M, args.N, args.K = M, N, K
+    args.lda = a.stride(0)
+    args.ldo = out.stride(-2)
+    args.ldr = resid.stride(0) if resid is not None else 0
+    args.gate_stride = gate_stride
+    args.epilogue = epilogue
+    args.out_tokens_per_batch = out_tokens_per_batch
+    args.alpha = alpha
+    args.out2, args.n_split, args.ldo2 = _p(out2), n_split, (out2.stride(-2) if out2 is not None else 0)
+    args.sumsq, args.sumsq_ld = _p(sumsq), (sumsq.stride(0) if sumsq is not None else 0)
+    with _timed("gemm_mxfp4", 2.0 * M * N * K, 0.53125 * (M * K + N * K) + 2.0 * M * N):
+        check(_lib.load().ltxk_gemm_mxfp4(ctypes.byref(args), _p(a_scales), a_scales.stride(0), _p(w_scales), w_scales.stride(0),
+                                          _stream()), "ltxk_gemm_mxfp4")
+    return out
+
+
 @dataclass(frozen=True)
 class GemmPlan:
     """ltxk_gemm_plan: the launch form of one ltxk_gemm_bf16 call (_lib.GEMM_FORM_*), its tile, and its K slices."""
@@ -341,17 +422,18 @@ _PLAN_ADDR = 1 << 12          # stands in for every device pointer of a planned 
 def gemm_plan(M: int, N: int, K: int, *, epilogue: int = EPI_BIAS, lda: Optional[int] = None, ldo: Optional[int] = None,
               out_tokens_per_batch: int = 0, n_split: int = 0, ldo2: Optional[int] = None, sumsq: bool = False,
               split_k: bool = True, workspace: Optional[Tuple[int, int]] = None, w8: bool = False,
-              w8a8: bool = False) -> GemmPlan:
+              w8a8: bool = False, mxfp4: bool = False) -> GemmPlan:
     """The form ``gemm`` takes for an (M,K) x (N,K)^T launch with these options, decided on the host by the function the
     launch itself uses (no device needed).  The split-K scratch is offered exactly as ``gemm`` offers it (``split_k``,
     SPLITK_MAX_M); ``workspace=(address, bytes)`` offers that one instead (address 0: none).  Strides default to those of
     contiguous tensors (V^T: tokens padded to 64).  Raises LtxkError where ``gemm`` would refuse the arguments.
     ``w8``: the plan of the same call with a float8_e4m3fn weight (ltxk_gemm_w8_plan).  ``w8a8``: with float8_e4m3fn
-    activations too (ltxk_gemm_w8a8_plan: always single-pass, 128-wide K-steps)."""
+    activations too (ltxk_gemm_w8a8_plan: always single-pass, 128-wide K-steps).  ``mxfp4``: the plan of ``gemm_mxfp4``
+    (ltxk_gemm_mxfp4_plan: always single-pass, MXFP4_KSTEP-wide K-steps; ``lda`` in bytes, K/2 by default)."""
     args = GemmArgs()
     args.A = args.W = args.out = _PLAN_ADDR
     args.M, args.N, args.K = M, N, K
-    args.lda = K if lda is None else lda
+    args.lda = (K // 2 if mxfp4 else K) if lda is None else lda
     ld_t = (out_tokens_per_batch + 63) // 64 * 64
     args.ldo = ldo if ldo is not None else (ld_t if out_tokens_per_batch and not n_split else (n_split or N))
     if epilogue in (EPI_BIAS_GATE_RES, EPI_BIAS_RES, EPI_SCALE_RES):
@@ -369,7 +451,9 @@ def gemm_plan(M: int, N: int, K: int, *, epilogue: int = EPI_BIAS, lda: Optional
     elif _offers_workspace(M, split_k):
         args.workspace, args.workspace_bytes = _PLAN_ADDR, GEMM_WORKSPACE_BYTES
     pl = _lib.GemmPlan()
-    if w8a8:
+    if mxfp4:
+        check(_lib.load().ltxk_gemm_mxfp4_plan(ctypes.byref(args), ctypes.byref(pl)), "ltxk_gemm_mxfp4_plan")
+    elif w8a8:
         check(_lib.load().ltxk_gemm_w8a8_plan(ctypes.byref(args), ctypes.byref(pl)), "ltxk_gemm_w8a8_plan")
     elif w8:
         check(_lib.load().ltxk_gemm_w8_plan(ctypes.byref(args), ctypes.byref(pl)), "ltxk_gemm_w8_plan")

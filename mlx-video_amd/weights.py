@@ -154,9 +154,26 @@ def is_fp8_matrix_key(key: str, t: torch.Tensor) -> bool:
     return key.endswith(".weight") and t.ndim == 2
 
 
-def _put_transformer_tensor(out: Dict[str, torch.Tensor], key: str, v: torch.Tensor, device, fp8: bool, fp8_scaling: str) -> None:
+MXSCALE_SUFFIX = "_mxscale"         # "<name>.weight" (uint8 MXFP4 codes) is accompanied by "<name>.weight_mxscale" ((N, K/32) uint8)
+_MXFP4_LINEARS = tuple(f".{a}.{n}.weight" for a in ("attn1", "attn2") for n in ("to_q", "to_k", "to_v", "to_out")) + \
+    (".ff.proj_in.weight", ".ff.proj_out.weight")
+
+
+def is_mxfp4_matrix_key(key: str, t: torch.Tensor) -> bool:
+    """The tensors --enable-mxfp4 keeps in MXFP4: the matrices of the IN-BLOCK Linear layers (attn1 / attn2 to_q, to_k, to_v,
+    to_out, ff.proj_in, ff.proj_out).  Patchify, the timestep and AdaLN Linears, the caption projection, proj_out, biases, norm
+    weights and tables stay bf16."""
+    return key.startswith("transformer_blocks.") and key.endswith(_MXFP4_LINEARS) and t.ndim == 2
+
+
+def _put_transformer_tensor(out: Dict[str, torch.Tensor], key: str, v: torch.Tensor, device, fp8: bool, fp8_scaling: str,
+                            mxfp4: bool = False) -> None:
     """One checkpoint tensor under its module key.  fp8: Linear matrices go to e4m3fn - an F8_E4M3 tensor of the checkpoint as
-    it is (no upcast, no scale), anything else quantised here, one tensor at a time, on the device it will live on."""
+    it is (no upcast, no scale), anything else quantised here, one tensor at a time, on the device it will live on.  mxfp4: the
+    in-block Linear matrices go to MXFP4 codes + "<key>_mxscale" block scales the same way; everything else is bf16."""
+    if mxfp4 and is_mxfp4_matrix_key(key, v):
+        out[key], out[key + MXSCALE_SUFFIX] = quantize_mxfp4(v.to(device=device))
+        return
     if fp8 and is_fp8_matrix_key(key, v):
         if v.dtype == FP8:
             out[key] = v.to(device=device).contiguous()
@@ -191,16 +208,21 @@ def _transformer_key(raw_key: str) -> Optional[str]:
     return k
 
 
-def transformer_weights(raw: Dict[str, torch.Tensor], device, fp8: bool = False, fp8_scaling: str = "channel") -> Dict[str, torch.Tensor]:
+def transformer_weights(raw: Dict[str, torch.Tensor], device, fp8: bool = False, fp8_scaling: str = "channel",
+                        mxfp4: bool = False) -> Dict[str, torch.Tensor]:
     """Module-key dict of the video transformer.  ``fp8``: the Linear matrices as e4m3fn panels (plus "<key>_scale" vectors
-    under ``fp8_scaling="channel"``) for LTXModel's weight-fp8 GEMMs; off, every tensor is bf16 (an fp8 checkpoint is upcast)."""
+    under ``fp8_scaling="channel"``) for LTXModel's weight-fp8 GEMMs; off, every tensor is bf16 (an fp8 checkpoint is upcast).
+    ``mxfp4``: the in-block Linear matrices as MXFP4 codes plus "<key>_mxscale" block scales (``is_mxfp4_matrix_key``) for
+    ltxk_gemm_mxfp4, the rest bf16; not together with ``fp8``."""
+    if fp8 and mxfp4:
+        raise ValueError("transformer_weights: fp8 and mxfp4 are two weight formats of the same matrices; choose one")
     if fp8 and fp8_scaling not in FP8_SCALINGS:
         raise ValueError(f"fp8 scaling {fp8_scaling!r}: expected one of {FP8_SCALINGS}")
     out = {}
     for k, v in raw.items():
         kk = _transformer_key(k)
         if kk is not None:
-            _put_transformer_tensor(out, kk, v, device, fp8, fp8_scaling)
+            _put_transformer_tensor(out, kk, v, device, fp8, fp8_scaling, mxfp4)
     return out
 
 
@@ -371,6 +393,21 @@ def quantize_transformer_weights(W: Dict[str, torch.Tensor], fp8_scaling: str = 
             out[k] = v
         else:
             _put_transformer_tensor(out, k, v, v.device, True, fp8_scaling)
+    return out
+
+
+def quantize_transformer_weights_mxfp4(W: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """A bf16 module-key dict (e.g. after a LoRA merge) -> the dict ``transformer_weights(mxfp4=True)`` gives: the in-block Linear
+    matrices as ``quantize_mxfp4`` codes under their keys and block scales under "<key>_mxscale", tensor by tensor on the device
+    each lives on; every other tensor is the same object.  The input is kept; an already quantised dict passes through unchanged."""
+    if any(k.endswith(MXSCALE_SUFFIX) for k in W):
+        return dict(W)
+    out: Dict[str, torch.Tensor] = {}
+    for k, v in W.items():
+        if is_mxfp4_matrix_key(k, v):
+            out[k], out[k + MXSCALE_SUFFIX] = quantize_mxfp4(v)
+        else:
+            out[k] = v
     return out
 
 
@@ -674,16 +711,20 @@ def infer_encoder_blocks(keys: Iterable[str]):
 
 def load_pipeline_modules(model_repo: str, device, need_encoder: bool = False, need_upsampler: bool = False,
                           loras: Optional[list] = None, build_transformer: bool = True, fp8: bool = False,
-                          fp8_scaling: str = "channel", need_text_connector: bool = False) -> dict:
+                          fp8_scaling: str = "channel", need_text_connector: bool = False, mxfp4: bool = False) -> dict:
     """Local-directory loader (no network: repo *names* are not resolved, utils.py:78-374 is out of scope).
     Headers are scanned first (keys, shapes, `timestep_conditioning` metadata), the architecture is inferred from the
     shapes, then tensors stream one by one straight into device memory under their module keys (ltx.py:548-826,
     decoder.py:594-740, encoder.py:108-187).  Returns the modules plus ``transformer_weights`` / ``transformer_config``
     (the base dict stays reachable so LoRA-merged twins can be built, generate.py:2957-3031,3229-3237).
     ``need_text_connector``: also ``mods["text_connector"]``, a ``TextConnector`` built from the directory's files and its
-    ``connectors/`` sub-directory (``text_connector_weights``)."""
+    ``connectors/`` sub-directory (``text_connector_weights``).
+    ``mxfp4``: the transformer's in-block Linear matrices as MXFP4 (``transformer_weights(mxfp4=True)``), each quantised as it
+    streams; with ``loras`` the merge runs on the bf16 dict and the result is quantised.  Not together with ``fp8``."""
     from .ltx_model import LTXModel
     from .video_vae import LTX2VideoDecoder, VideoEncoder
+    if fp8 and mxfp4:
+        raise ValueError("load_pipeline_modules: fp8 and mxfp4 are two weight formats of the same matrices; choose one")
     root = Path(model_repo)
     if not root.exists():
         raise FileNotFoundError(f"model_repo {model_repo!r} is not a local directory; HF downloads are not available offline")
@@ -722,7 +763,7 @@ def load_pipeline_modules(model_repo: str, device, need_encoder: bool = False, n
         tk = _transformer_key(k)
         if tk is not None:
             # (a LoRA is merged into bf16 matrices and the merged dict quantised: merge-then-quantise)
-            _put_transformer_tensor(tw, tk, v, device, fp8 and not loras, fp8_scaling)
+            _put_transformer_tensor(tw, tk, v, device, fp8 and not loras, fp8_scaling, mxfp4 and not loras)
             continue
         dk = _vae_decoder_key(k)
         if dk is not None:
@@ -741,6 +782,8 @@ def load_pipeline_modules(model_repo: str, device, need_encoder: bool = False, n
             w = apply_lora_to_weights(tw, [LoraSpec(Path(p), float(s)) for p, s in loras])
             if fp8:
                 w = quantize_transformer_weights(w, fp8_scaling)
+            if mxfp4:
+                w = quantize_transformer_weights_mxfp4(w)
         mods["transformer"] = LTXModel(tcfg, w)
     nres = 1 + max((int(k.split(".")[3]) for k in dw if k.startswith("up_blocks.0.res_blocks.")), default=4)
     mods["vae_decoder"] = LTX2VideoDecoder(dw, timestep_conditioning=any(sniff_timestep_conditioning(f) for f in main),
